@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Attention-layer benchmark for the rectified block-sparse attention path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One step = one pass of the whole hot path (K1 pool_stats .. K5 block_sparse_fwd) over one synthetic
 HunyuanVideo-720p attention call: B=1, H=24, S=115 200 visual + 256 text (200 valid), D=128, bf16, top_k = 90
@@ -14,10 +14,18 @@ time = max over ranks.  Launched without an outer launcher, this process never t
 torch.distributed.run (WORLD_SIZE set) it is a rank.  Rank 0 prints ONE JSON line.
 
 The line's `value` is regime R2 of SURVEY.md 8(d) (exactly top_k kept visual blocks + the text blocks, independent
-block centroids).  Sub-records measured in the same run (N = 1): `regimes.r1` (Gilbert neighbours, p = 0.05),
-`regimes.locality` (spatially smooth centroids -> neighbouring query blocks keep overlapping lists, Gilbert
-neighbours, p = 0.05), `api` (the public operator and a processor __call__ end to end), `sustained` (>= 2 s of
-back-to-back steps), `cpu_baseline` (reference dense path + the rectified sparse path on the same mask, host cores).
+block centroids).  A plain run does only that: set-up, W warm-up steps, exactly K timed steps, the JSON line.
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed is written as DIR/<name>.npy (float32 /
+float64, < 64 MB in all; see dump_outputs).  The inputs depend only on the arguments, so two builds can be compared file
+for file.
+
+--full adds everything else, measured in the same run: the output check of the timed launch (`check`, exit 3 when it
+fails), at N = 1 the sub-records `regimes.r1` (Gilbert neighbours, p = 0.05), `regimes.locality` (spatially smooth
+centroids -> neighbouring query blocks keep overlapping lists, Gilbert neighbours, p = 0.05), `api` (the public operator
+and a processor __call__ end to end), `sustained` (>= 6 s of back-to-back steps), `box_ref`, `fp8`, live PMC traffic
+(--no-extras / --no-live-traffic leave these out), `cpu_baseline` (reference dense path + the rectified sparse path on
+the same mask, host cores; --no-cpu-baseline leaves it out), and at N > 1 the all-gather of O with its transports.
 """
 import argparse
 import hashlib
@@ -757,6 +765,42 @@ def measure_traffic_live(regime: str, fp8: bool, timeout_s: int = 150, workload:
                 f"memory-side (fabric) bytes per launch = FETCH_SIZE x2 + WRITE_SIZE; includes Infinity-Cache hits; l2_hit_rate {hit:.4f}")
 
 
+DUMP_ROWS_BYTES = 48 << 20   # budget of out_rows.npy (float32); the other files are small
+DUMP_SEED = 7
+
+
+def dump_outputs(comm, call, out_dir):
+    """What the caller of the timed path receives after its last step, written as float32 / float64 .npy files under out_dir
+    (rank 0 writes; at N > 1 every rank contributes its heads, in head order):
+      out_rows.npy      float32 [B, n, H, D]  rows of O [B, S, H, D]: a fixed seeded sample of query rows (sorted) plus every
+                                              row of the last 128-row block (text rows where the layout has them)
+      out_rows_index.npy float64 [n]          which rows of S those are
+      out_head_sum.npy  float64 [B, H, D]     sum of O over ALL S rows, per head and channel (covers the rows not sampled)
+      kept_counts.npy   float32 [B, H, NBv]   kept key blocks per visual query block (the mask the select pass chose)"""
+    import numpy as np
+    import torch
+    out = call.out                                       # [B, S, H_local, D]
+    B, S, H_local, D = out.shape
+    n = max(1, min(S, DUMP_ROWS_BYTES // (4 * B * max(1, comm.world) * H_local * D)))
+    tail = np.arange(max(0, S - 128), S)
+    rng = np.random.default_rng(DUMP_SEED)
+    body = rng.choice(S - len(tail), size=min(S - len(tail), max(0, n - len(tail))), replace=False) if S > len(tail) else []
+    rows = np.unique(np.concatenate([np.asarray(body, dtype=np.int64), tail]))
+    idx = torch.from_numpy(rows).to(out.device)
+    parts = dict(out_rows=out.index_select(1, idx).float().cpu().numpy(),
+                 out_head_sum=torch.sum(out, dim=1, dtype=torch.float64).cpu().numpy(),
+                 kept_counts=call.bufs["counts"].reshape(B, H_local, -1).float().cpu().numpy())
+    if comm.dist is not None:                            # heads of every rank, in rank (= head) order
+        got = [None] * comm.world
+        comm.dist.all_gather_object(got, parts)
+        parts = {name: np.concatenate([g[name] for g in got], axis=2 if name == "out_rows" else 1) for name in parts}
+    if comm.rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        parts["out_rows_index"] = rows.astype(np.float64)
+        for name, arr in parts.items():
+            np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(arr))
+
+
 def dry_worker(args, comm):
     """Host logic only (gloo, no GPU): sharding, barriers, max-over-ranks timing, the JSON line."""
     from rectified_spaattn_amd import parallel
@@ -803,7 +847,13 @@ def main():
                          "allgather_heads) and p2p (rsa_allgather_heads_p2p); each is reported beside the torch.distributed one "
                          "('' = none)")
     ap.add_argument("--dry", action="store_true", help="host logic only (gloo, CPU): for the multi-process tests")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: output check, sub-records, live traffic, CPU baseline, N > 1 exchange")
     args = ap.parse_args()
+    if args.dry and args.dump_outputs:
+        ap.error("--dump-outputs: a --dry run computes no outputs")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
@@ -830,18 +880,22 @@ def main():
     main_regime = args.regime
     q, k, v = gen_inputs(wl, H_local, head0, dev, REGIMES[main_regime][0], D=D)
     rec, call = run_regime(comm, args, wl, main_regime, q, k, v, spec, args.steps, args.warmup, want_call=True)
-    # the headline launch's own output, checked on every rank (a rank with a wrong O fails the whole line)
     comm.local_sync()
-    try:
-        check = check_output(call, spec, args.qkv_fp8)
-    except Exception as e:  # noqa: BLE001
-        check = dict(ok=False, error=repr(e)[:300])
-    check["ok"] = comm.all_ok(bool(check.get("ok")))
-    sample = capture_sparse_sample(call) if (world == 1 and not args.no_cpu_baseline) else None
+    if args.dump_outputs:
+        dump_outputs(comm, call, args.dump_outputs)
+    check, sample = None, None
+    if args.full:
+        # the headline launch's own output, checked on every rank (a rank with a wrong O fails the whole line)
+        try:
+            check = check_output(call, spec, args.qkv_fp8)
+        except Exception as e:  # noqa: BLE001
+            check = dict(ok=False, error=repr(e)[:300])
+        check["ok"] = comm.all_ok(bool(check.get("ok")))
+        sample = capture_sparse_sample(call) if (world == 1 and not args.no_cpu_baseline) else None
 
     extras = {}
     gather = None
-    if world > 1:  # the optional exchange step at the layer boundary: all-gather of O along the head axis
+    if world > 1 and (args.full or args.gather_output):  # the exchange step at the layer boundary: all-gather of O along heads
         # Self-check of every exchange (the first real N-GPU run is the driver's, with no one watching): each rank publishes
         # per-head fingerprints of its LOCAL O (fp64 sum, sum of squares, 8 whole rows: parallel.head_checksums); after each
         # transport's timed steps every rank recomputes them from the buffer that transport gathered; a transport whose buffer
@@ -879,7 +933,7 @@ def main():
         if not ok_t:
             gather = dict(ranks=world, rccl_version=rccl_ver, error=f"torch.distributed all_gather: {why_t}",
                           bytes_per_rank=gather["bytes_per_rank"], transport=gather["transport"], verified=False)
-        for tr in [t for t in args.gather_transports.split(",") if t]:
+        for tr in [t for t in args.gather_transports.split(",") if t and args.full]:
             B_, S_, Hl_, D_ = call.out.shape
             hg, err = None, None
             try:   # the library's own transports (C-ABI): the set-up may fail on one rank (librccl missing, IPC refused)
@@ -922,7 +976,7 @@ def main():
             else:
                 gather[tr] = {"error": terr or "a wait timed out on another rank"}
             hg.close()
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         # sustained: >= 6 s of back-to-back steps of the headline regime, with the clock / power the chip holds meanwhile
         n_sus = max(args.steps, int(6.5 / max(rec["ms_per_step"] * 1e-3, 1e-4)))
 
@@ -987,7 +1041,7 @@ def main():
 
     if rank != 0:
         comm.close()
-        if not check.get("ok"):
+        if check is not None and not check.get("ok"):
             sys.exit(3)
         return
 
@@ -996,7 +1050,7 @@ def main():
     traffic, tnote = (None, "N > 1: traffic is collected at N = 1")
     if world == 1:
         traffic, tnote = load_traffic(tname) if args.workload == "hunyuan_720p_128f" else (None, "no committed traffic json for this workload")
-        if not args.no_extras and not args.no_live_traffic and not comm.one_device:
+        if args.full and not args.no_extras and not args.no_live_traffic and not comm.one_device:
             torch.cuda.synchronize()
             live, lnote = measure_traffic_live(main_regime, args.qkv_fp8, workload=args.workload)
             if live is not None:
@@ -1041,7 +1095,8 @@ def main():
         res["config"]["one_device_test"] = "all ranks time-slice cuda:0 over gloo: functional evidence, not a measurement"
     if args.gather_output and gather is not None and "value" in gather:  # headline = the gather-inclusive variant
         res["value"], res["ms_per_step"] = gather["value"], gather["ms_per_step"]
-    res["check"] = check
+    if check is not None:
+        res["check"] = check
     res.update(extras)
     if traffic is not None:   # the second wall: memory-side (Infinity Fabric / Infinity Cache) bytes per second under K5
         res["roofline"]["traffic_tbps"] = round(traffic / max(rec["k5_ms"], 1e-6) / 1e9, 3)
@@ -1049,7 +1104,7 @@ def main():
         res["roofline"]["clock"] = extras["sustained"].get("smi")
     if "box_ref" in extras:
         res["roofline"]["box_ref"] = extras["box_ref"]
-    if world == 1:
+    if world == 1 and args.full:
         if args.no_cpu_baseline:
             res["cpu_baseline"] = None
         else:
@@ -1061,7 +1116,7 @@ def main():
             res["cpu_baseline"] = cb
     print(json.dumps(res))
     comm.close()
-    if not check.get("ok"):
+    if check is not None and not check.get("ok"):
         print(f"bench.py: the output check FAILED: {check}", file=sys.stderr)
         sys.exit(3)
 

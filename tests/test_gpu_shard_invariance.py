@@ -124,7 +124,7 @@ def test_bench_two_ranks_on_one_device():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-extras", "--no-cpu-baseline", "--gather-transports", "p2p"],
+                        "--full", "--no-extras", "--no-cpu-baseline", "--gather-transports", "p2p"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -188,7 +188,7 @@ def test_bench_eight_ranks_on_one_device():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--workload", "tiny8", "--steps", "4",
-                        "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--gather-transports", "rccl,p2p"],
+                        "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--gather-transports", "rccl,p2p"],
                        capture_output=True, text=True, timeout=1200, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
