@@ -108,7 +108,7 @@ int rsa_version(void);
  *     if (rsa_abi_check(RSA_HEADER_VERSION, sizeof(rsa_buffers), sizeof(rsa_layout)) != RSA_OK) refuse to run;
  * RSA_OK iff the library was built from a header with the same struct sizes and the same major.minor; RSA_ERR_UNSUPPORTED
  * otherwise.  (The Python host calls it when it loads the library; examples/c_host does too.) */
-#define RSA_HEADER_VERSION 600
+#define RSA_HEADER_VERSION 601
 int rsa_abi_check(int header_version, size_t sizeof_rsa_buffers, size_t sizeof_rsa_layout);
 
 /* Process-global switch (default 0).  K5 plans two things from the SIZE OF THE LAUNCH: how many pieces the dense text rows
@@ -200,11 +200,41 @@ int rsa_dense_dropout_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_te
                           int64_t mask_stride_q, int64_t mask_stride_k, int causal, int empty_rows_nan, float drop_rate,
                           uint64_t seed, rsa_out4 out, void* stream);
 
+/* ---- 64-token blocks (since 0.6.1; the reference's block_size_M = block_size_N = 64, rectified_hunyuan_attn.py:171-222,
+ * :283-389).  Every function above keeps its 128-token meaning; these take the block size beside the layout.  All rsa_layout
+ * members count blocks of `block` tokens (NB_total = ceil(S / block), text rows start at NBv * block).  rsa_buffers is the same
+ * struct, sized by rsa_buffer_bytes_ex.  block = 128 gives exactly the calls above; block = 64 is the 2-byte path (no fp8
+ * form); anything else is RSA_ERR_UNSUPPORTED. ---- */
+typedef struct rsa_layout_ex {
+    rsa_layout base;
+    int32_t block;           /* tokens per block: 64 or 128 */
+    int32_t reserved[3];     /* zero (the _ex entry points return RSA_ERR_BAD_ARG otherwise) */
+} rsa_layout_ex;
+int rsa_buffer_bytes_ex(const rsa_layout_ex* lay, size_t sizes[RSA_NUM_BUFFERS], size_t* total);
+int rsa_carve_workspace_ex(const rsa_layout_ex* lay, void* ws, size_t ws_bytes, rsa_buffers* out);
+int rsa_pool_stats_ex(const rsa_layout_ex* lay, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const rsa_buffers* buf,
+                      void* stream);
+int rsa_pooled_scores_ex(const rsa_layout_ex* lay, rsa_tensor4 k, const rsa_buffers* buf, void* stream);
+int rsa_select_mask_ex(const rsa_layout_ex* lay, const uint8_t* neighbor, int top_k, float p_remain,
+                       const rsa_buffers* buf, void* stream);
+int rsa_compensation_ex(const rsa_layout_ex* lay, const rsa_buffers* buf, void* stream);
+/* At block 64 one workgroup (4 waves) owns the query blocks 2i and 2i + 1 and walks the union of their kept lists, one 64-key
+ * tile per entry; each wave pair masks the tiles its own block did not keep. */
+int rsa_block_sparse_fwd_ex(const rsa_layout_ex* lay, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                            const rsa_buffers* buf, rsa_out4 out, void* stream);
+int rsa_rectified_attention_ex(const rsa_layout_ex* lay, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                               const uint8_t* neighbor, int top_k, float p_remain, void* workspace,
+                               size_t workspace_bytes, rsa_out4 out, void* stream);
+
 /* Stand-alone GAPR for callers of estimate_pr_gain (gapr_mask.py:4): blocks are [BH, N, 128, D] contiguous
  * 2-byte elements, pools [BH, N, D] fp32, scores [BH, NQ, NK] fp32 -> mask [BH, NQ, NK] uint8 (1 = ~gapr_mask). */
 int rsa_estimate_pr_gain(int BH, int NQ, int NK, int D, int dtype, const void* q_blocks, const void* k_blocks,
                          const float* q_pools, const float* k_pools, const float* scores, float* scratch_aq,
                          float* scratch_ak, uint8_t* mask_out, void* stream);
+/* ... with blocks of `block` tokens ([BH, N, block, D]): 64 or 128 (since 0.6.1). */
+int rsa_estimate_pr_gain_ex(int BH, int NQ, int NK, int D, int dtype, int block, const void* q_blocks, const void* k_blocks,
+                            const float* q_pools, const float* k_pools, const float* scores, float* scratch_aq,
+                            float* scratch_ak, uint8_t* mask_out, void* stream);
 
 /* ---- host-side geometry: produces the hot path's `neighbor` input and the token permutation ---- */
 

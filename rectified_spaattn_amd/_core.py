@@ -14,12 +14,20 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib
-from ._lib import BLOCK, BUFFER_NAMES, RsaBuffers, RsaFp8Operands, RsaLayout, RsaOut4, RsaTensor4
+from ._lib import BLOCK, BUFFER_NAMES, RsaBuffers, RsaFp8Operands, RsaLayout, RsaLayoutEx, RsaOut4, RsaTensor4
+
+
+def check_block(block: int) -> int:
+    """The block sizes the HIP path serves: block_size_M == block_size_N in {64, 128}."""
+    if block not in _lib.BLOCKS:
+        raise NotImplementedError(f"the HIP path is built for block_size_M = block_size_N in {_lib.BLOCKS}, got {block}")
+    return int(block)
 
 
 @dataclass
 class LayoutSpec:
-    """Geometry of one call; see include/rsa.h::rsa_layout for the field meanings."""
+    """Geometry of one call; see include/rsa.h::rsa_layout for the field meanings.  Every count is in blocks of `block`
+    tokens (128, or 64 through the library's _ex entry points)."""
     S: int
     NB_total: int
     NBv: int
@@ -30,52 +38,57 @@ class LayoutSpec:
     first_frame_blocks: int
     q_text_valid: int
     kv_text_valid: int
+    block: int = BLOCK
 
     # -- the reference's variants (file:line under the reference root) ---------------------------------
     @staticmethod
-    def hunyuan(S: int, num_true: int) -> "LayoutSpec":
+    def hunyuan(S: int, num_true: int, block: int = BLOCK) -> "LayoutSpec":
         """rectified_hunyuan_attn.py:313-332: text tail padded to 256, num_true = attention_mask.sum()."""
-        if S % BLOCK:
-            raise ValueError("HunyuanVideo layout needs S % 128 == 0 (the reference reshapes without padding)")
-        NB = S // BLOCK
-        NBv = NB - 256 // BLOCK
+        b = check_block(block)
+        if S % b:
+            raise ValueError(f"HunyuanVideo layout needs S % {b} == 0 (the reference reshapes without padding)")
+        NB = S // b
+        NBv = NB - 256 // b
         n_txt = 256 - (S - num_true)
         if NBv < 0 or n_txt <= 0 or n_txt > 256:
             # reference: attenable == 0 makes scores[..., :-0] empty and crashes (SURVEY appendix B-3)
             raise ValueError(f"HunyuanVideo layout needs 1..256 valid text tokens, got {n_txt}")
-        return LayoutSpec(S, NB, NBv, n_txt, num_true, num_true, (num_true + BLOCK - 1) // BLOCK, 0,
-                          num_true - NBv * BLOCK, num_true)
+        return LayoutSpec(S, NB, NBv, n_txt, num_true, num_true, (num_true + b - 1) // b, 0,
+                          num_true - NBv * b, num_true, b)
 
     @staticmethod
-    def flux(S: int, text_length: int, s_k: Optional[int] = None) -> "LayoutSpec":
+    def flux(S: int, text_length: int, s_k: Optional[int] = None, block: int = BLOCK) -> "LayoutSpec":
         """rectified_flux_attn.py:307-320."""
-        if S % BLOCK:
-            raise ValueError("Flux layout needs S % 128 == 0")
+        b = check_block(block)
+        if S % b:
+            raise ValueError(f"Flux layout needs S % {b} == 0")
         s_k = S if s_k is None else int(s_k)
-        NB = S // BLOCK
-        NBv = NB - text_length // BLOCK
-        return LayoutSpec(S, NB, NBv, text_length, s_k, S, (s_k + BLOCK - 1) // BLOCK, 0, S - NBv * BLOCK, s_k)
+        NB = S // b
+        NBv = NB - text_length // b
+        return LayoutSpec(S, NB, NBv, text_length, s_k, S, (s_k + b - 1) // b, 0, S - NBv * b, s_k, b)
 
     @staticmethod
-    def cogvideo(S: int, text_length: int, s_k: Optional[int] = None) -> "LayoutSpec":
-        """rectified_cogvideo_attn.py:306-322 (zero-pad to x128, every text block kept)."""
-        NB = (S + BLOCK - 1) // BLOCK
-        pad = NB * BLOCK - S
-        NBv = NB - (text_length + pad) // BLOCK
-        if NBv < 0 or text_length > S - NBv * BLOCK:
-            # the reference cuts the text rows at normal_blocks * 128 and hands flash-attn cu_seqlens_q = [0, text_length]
+    def cogvideo(S: int, text_length: int, s_k: Optional[int] = None, block: int = BLOCK) -> "LayoutSpec":
+        """rectified_cogvideo_attn.py:306-322 (zero-pad to a multiple of the block, every text block kept)."""
+        b = check_block(block)
+        NB = (S + b - 1) // b
+        pad = NB * b - S
+        NBv = NB - (text_length + pad) // b
+        if NBv < 0 or text_length > S - NBv * b:
+            # the reference cuts the text rows at normal_blocks * block and hands flash-attn cu_seqlens_q = [0, text_length]
             # (rectified_cogvideo_attn.py:318-320,:359-366): with fewer rows than text_length behind the cut that reads past the
             # tensor -- the layout only exists when the visual tokens fill whole blocks
             raise ValueError(f"CogVideoX layout: the {S - text_length} visual tokens of S = {S}, text_length = {text_length} must be a "
-                             f"multiple of {BLOCK}")
+                             f"multiple of {b}")
         s_k = S if s_k is None else int(s_k)
-        return LayoutSpec(S, NB, NBv, text_length, S, S, NB, 0, text_length, s_k)
+        return LayoutSpec(S, NB, NBv, text_length, S, S, NB, 0, text_length, s_k, b)
 
     @staticmethod
-    def wan(S: int, first_frame_blocks: Optional[int] = 0) -> "LayoutSpec":
+    def wan(S: int, first_frame_blocks: Optional[int] = 0, block: int = BLOCK) -> "LayoutSpec":
         """rectified_wan21_attn.py:297-313 (visual only)."""
-        NB = (S + BLOCK - 1) // BLOCK
-        return LayoutSpec(S, NB, NB, 0, S, S, NB, int(first_frame_blocks or 0), 0, S)
+        b = check_block(block)
+        NB = (S + b - 1) // b
+        return LayoutSpec(S, NB, NB, 0, S, S, NB, int(first_frame_blocks or 0), 0, S, b)
 
     @property
     def L(self) -> int:
@@ -85,6 +98,10 @@ class LayoutSpec:
         return RsaLayout(B, H, D, self.S, self.NB_total, self.NBv, self.n_txt, self.kv_valid, self.pool_valid,
                          self.text_end_block, self.first_frame_blocks, self.q_text_valid, self.kv_text_valid,
                          dtype_code(dtype))
+
+    def to_c_ex(self, B: int, H: int, D: int, dtype: torch.dtype) -> RsaLayoutEx:
+        """The layout with its block size (rsa_layout_ex: the _ex entry points)."""
+        return RsaLayoutEx(self.to_c(B, H, D, dtype), self.block)
 
 
 def check_head_dim(D: int) -> None:
@@ -198,7 +215,7 @@ def cached_buffers(spec: LayoutSpec, B: int, H: int, D: int, device) -> Dict[str
     if not BUFFER_CACHE or (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
         return alloc_buffers(spec, B, H, D, device)
     stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-    key = (dev.type, dev.index, stream, B, H, D, spec.S, spec.NB_total, spec.NBv, spec.n_txt)
+    key = (dev.type, dev.index, stream, B, H, D, spec.S, spec.NB_total, spec.NBv, spec.n_txt, spec.block)
     hit = _BUF_CACHE.pop(key, None)
     if hit is None:
         hit = alloc_buffers(spec, B, H, D, device)
@@ -292,6 +309,13 @@ class StagedCall:
             self.k = _k_for_pv(self.k)
         self.spec, self.top_k, self.p = spec, int(top_k), float(p_remain)
         self.lay = spec.to_c(B, H, D, q.dtype)
+        # 128-token blocks: the original entry points, exactly as before; 64: their _ex forms with rsa_layout_ex
+        self.ex = spec.block != BLOCK
+        if self.ex:
+            self.lay_ex = spec.to_c_ex(B, H, D, q.dtype)
+            if qkv_fp8:
+                raise NotImplementedError(f"qkv_fp8={qkv_fp8!r}: the fp8 K5 is built for 128-token blocks only "
+                                          f"(block {spec.block} runs the 2-byte kernel)")
         self.bufs = cached_buffers(spec, B, H, D, q.device) if reuse_buffers else alloc_buffers(spec, B, H, D, q.device)
         self.cb = _c_buffers(self.bufs)
         self.out = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device)
@@ -317,25 +341,35 @@ class StagedCall:
             _lib.check(self.L.rsa_quantize_fp8(ctypes.byref(self.lay), tq, tk, tv, ctypes.byref(self.cf), _stream()),
                        "rsa_quantize_fp8")
 
+    def _fn(self, name: str):
+        """(entry point, layout argument): name with rsa_layout, or name_ex with rsa_layout_ex for 64-token blocks."""
+        if self.ex:
+            return getattr(self.L, name + "_ex"), ctypes.byref(self.lay_ex)
+        return getattr(self.L, name), ctypes.byref(self.lay)
+
     def select_pool(self):
         """K1 (writing the e4m3 images of Q, K, V as it goes when qkv_fp8)."""
         L, lay, cb, st = self.L, ctypes.byref(self.lay), ctypes.byref(self.cb), _stream()
         tq, tk, tv = self.t
         with torch.cuda.device(self.q.device):
-            if self.fp8 is not None:
+            if self.ex:
+                fn, lx = self._fn("rsa_pool_stats")
+                _lib.check(fn(lx, tq, tk, tv, cb, st), "rsa_pool_stats_ex")
+            elif self.fp8 is not None:
                 _lib.check(L.rsa_pool_stats_fp8(lay, tq, tk, tv, cb, ctypes.byref(self.cf), st), "rsa_pool_stats_fp8")
             else:
                 _lib.check(L.rsa_pool_stats(lay, tq, tk, tv, cb, st), "rsa_pool_stats")
 
     def select_rest(self):
         """K2..K4 (need only K1's statistics)."""
-        L, lay, cb, st = self.L, ctypes.byref(self.lay), ctypes.byref(self.cb), _stream()
+        cb, st = ctypes.byref(self.cb), _stream()
         tk = self.t[1]
+        (k2, lay), (k3, _), (k4, _) = self._fn("rsa_pooled_scores"), self._fn("rsa_select_mask"), self._fn("rsa_compensation")
         with torch.cuda.device(self.q.device):
-            _lib.check(L.rsa_pooled_scores(lay, tk, cb, st), "rsa_pooled_scores")
-            _lib.check(L.rsa_select_mask(lay, self.nbr.data_ptr() if self.nbr is not None else None, self.top_k,
-                                         self.p, cb, st), "rsa_select_mask")
-            _lib.check(L.rsa_compensation(lay, cb, st), "rsa_compensation")
+            _lib.check(k2(lay, tk, cb, st), "rsa_pooled_scores")
+            _lib.check(k3(lay, self.nbr.data_ptr() if self.nbr is not None else None, self.top_k,
+                          self.p, cb, st), "rsa_select_mask")
+            _lib.check(k4(lay, cb, st), "rsa_compensation")
 
     def select(self):
         self.select_pool()
@@ -355,9 +389,9 @@ class StagedCall:
                                                            ctypes.byref(self.cb), self.o4, _stream()),
                            "rsa_block_sparse_fwd_fp8")
             return self.out
+        k5, lay = self._fn("rsa_block_sparse_fwd")
         with torch.cuda.device(self.q.device):
-            _lib.check(self.L.rsa_block_sparse_fwd(ctypes.byref(self.lay), tq, tk, tv, ctypes.byref(self.cb),
-                                                   self.o4, _stream()), "rsa_block_sparse_fwd")
+            _lib.check(k5(lay, tq, tk, tv, ctypes.byref(self.cb), self.o4, _stream()), "rsa_block_sparse_fwd")
         return self.out
 
 
@@ -538,10 +572,14 @@ def rectified_attention_onecall(q: torch.Tensor, k: torch.Tensor, v: torch.Tenso
     L = _lib.lib()
     B, H, S, D = q.shape
     q, k, v = _as_bhsd(q), _as_bhsd(k), _as_bhsd(v)
-    lay = spec.to_c(B, H, D, q.dtype)
+    ex = spec.block != BLOCK
+    if ex and qkv_fp8:
+        raise NotImplementedError(f"qkv_fp8={qkv_fp8!r}: the fp8 K5 is built for 128-token blocks only")
+    lay = spec.to_c_ex(B, H, D, q.dtype) if ex else spec.to_c(B, H, D, q.dtype)
     sizes = (ctypes.c_size_t * _lib.NUM_BUFFERS)()
     total = ctypes.c_size_t()
-    _lib.check(L.rsa_buffer_bytes(ctypes.byref(lay), ctypes.byref(sizes), ctypes.byref(total)), "rsa_buffer_bytes")
+    _lib.check((L.rsa_buffer_bytes_ex if ex else L.rsa_buffer_bytes)(ctypes.byref(lay), ctypes.byref(sizes), ctypes.byref(total)),
+               "rsa_buffer_bytes")
     if workspace is None or workspace.numel() < total.value:
         workspace = torch.empty(total.value, dtype=torch.uint8, device=q.device)
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device)
@@ -563,7 +601,7 @@ def rectified_attention_onecall(q: torch.Tensor, k: torch.Tensor, v: torch.Tenso
                        name8)
         return out.view(B, S, H * D), workspace
     with torch.cuda.device(q.device):
-        _lib.check(L.rsa_rectified_attention(ctypes.byref(lay), _t4(q), _t4(k), _t4(v),
+        _lib.check((L.rsa_rectified_attention_ex if ex else L.rsa_rectified_attention)(ctypes.byref(lay), _t4(q), _t4(k), _t4(v),
                                              nbr.data_ptr() if nbr is not None else None, int(top_k),
                                              float(p_remain), workspace.data_ptr(), workspace.numel(), o4, _stream()),
                    "rsa_rectified_attention")

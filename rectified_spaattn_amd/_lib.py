@@ -18,7 +18,8 @@ LIB_PATH = os.path.join(_HERE, "librsa_hip.so")
 
 RSA_BF16, RSA_FP16 = 0, 1
 BLOCK = 128
-HEADER_VERSION = 600   # RSA_HEADER_VERSION of include/rsa.h this ctypes mirror follows (rsa_abi_check)
+BLOCKS = (64, 128)     # block sizes the library serves (64 through the _ex entry points, rsa.h 0.6.1)
+HEADER_VERSION = 601   # RSA_HEADER_VERSION of include/rsa.h this ctypes mirror follows (rsa_abi_check)
 
 
 class RsaError(RuntimeError):
@@ -29,6 +30,10 @@ class RsaLayout(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "B", "H", "D", "S", "NB_total", "NBv", "n_txt", "kv_valid", "pool_valid", "text_end_block",
         "first_frame_blocks", "q_text_valid", "kv_text_valid", "dtype")]
+
+
+class RsaLayoutEx(ctypes.Structure):
+    _fields_ = [("base", RsaLayout), ("block", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
 class RsaTensor4(ctypes.Structure):
@@ -107,6 +112,16 @@ def lib():
     L.rsa_block_sparse_fwd.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaBuffers), RsaOut4, vp]
     L.rsa_rectified_attention.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, vp, i32, f32, vp, sz,
                                           RsaOut4, vp]
+    L.rsa_buffer_bytes_ex.argtypes = [P(RsaLayoutEx), P(sz * NUM_BUFFERS), P(sz)]
+    L.rsa_carve_workspace_ex.argtypes = [P(RsaLayoutEx), vp, sz, P(RsaBuffers)]
+    L.rsa_pool_stats_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaBuffers), vp]
+    L.rsa_pooled_scores_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, P(RsaBuffers), vp]
+    L.rsa_select_mask_ex.argtypes = [P(RsaLayoutEx), vp, i32, f32, P(RsaBuffers), vp]
+    L.rsa_compensation_ex.argtypes = [P(RsaLayoutEx), P(RsaBuffers), vp]
+    L.rsa_block_sparse_fwd_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaBuffers), RsaOut4, vp]
+    L.rsa_rectified_attention_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, RsaTensor4, RsaTensor4, vp, i32, f32, vp, sz,
+                                             RsaOut4, vp]
+    L.rsa_estimate_pr_gain_ex.argtypes = [i32] * 6 + [vp] * 9
     L.rsa_dense_fwd.argtypes = [i32] * 6 + [RsaTensor4, RsaTensor4, RsaTensor4, i32, i32, RsaOut4, vp]
     L.rsa_dense_causal_fwd.argtypes = L.rsa_dense_fwd.argtypes
     L.rsa_dense_causal_fwd.restype = i32
@@ -157,7 +172,9 @@ def lib():
         getattr(L, name).restype = i32
     for name in ("rsa_buffer_bytes", "rsa_carve_workspace", "rsa_pool_stats", "rsa_pooled_scores",
                  "rsa_select_mask", "rsa_compensation", "rsa_block_sparse_fwd", "rsa_rectified_attention",
-                 "rsa_dense_fwd", "rsa_dense_masked_fwd", "rsa_estimate_pr_gain"):
+                 "rsa_dense_fwd", "rsa_dense_masked_fwd", "rsa_estimate_pr_gain", "rsa_buffer_bytes_ex", "rsa_carve_workspace_ex",
+                 "rsa_pool_stats_ex", "rsa_pooled_scores_ex", "rsa_select_mask_ex", "rsa_compensation_ex", "rsa_block_sparse_fwd_ex",
+                 "rsa_rectified_attention_ex", "rsa_estimate_pr_gain_ex"):
         getattr(L, name).restype = i32
     # kernel-variant switches for A/B runs and the variant tests; rsa_set_tuning works only under RSA_TUNING=1
     for key in ("k5_tsplit", "k3_prefix", "k3_long", "k4_split", "k5_rows256", "k5_static", "k5_w64", "k5_gsync", "k5_gsync_ratio", "k5_text_last", "k5_tail_split"):
@@ -178,7 +195,8 @@ EXPORTED = ("rsa_version", "rsa_abi_check", "rsa_buffer_bytes", "rsa_carve_works
             "rsa_pool_stats_fp8", "rsa_dense_fp8_bytes", "rsa_dense_fwd_fp8", "rsa_dense_causal_fwd_fp8", "rsa_dense_fwd_fp8pv", "rsa_rel_l1",
             "rsa_comm_unique_id", "rsa_comm_create", "rsa_comm_destroy", "rsa_comm_count", "rsa_allgather_heads",
             "rsa_allgather_heads_p2p", "rsa_p2p_state_bytes", "rsa_p2p_state_alloc", "rsa_p2p_state_free", "rsa_p2p_state_timeout", "rsa_ipc_export", "rsa_ipc_open", "rsa_ipc_close",
-            "rsa_ipc_offset")
+            "rsa_ipc_offset", "rsa_buffer_bytes_ex", "rsa_carve_workspace_ex", "rsa_pool_stats_ex", "rsa_pooled_scores_ex",
+            "rsa_select_mask_ex", "rsa_compensation_ex", "rsa_block_sparse_fwd_ex", "rsa_rectified_attention_ex", "rsa_estimate_pr_gain_ex")
 
 
 def check(status: int, what: str):

@@ -21,10 +21,13 @@ def _int_at(x, idx: int, default: Optional[int] = None) -> int:
     return int(v.item()) if isinstance(v, torch.Tensor) else int(v)
 
 
-def _check_blocks(bm: int, bn: int):
-    if bm != BLOCK or bn != BLOCK:
+def _check_blocks(bm: int, bn: int) -> int:
+    """block_size_M == block_size_N in {64, 128} (the reference slices keys by num_query_blocks * block_size_N,
+    rectified_hunyuan_attn.py:191, which only means something when the two agree)."""
+    if bm != bn or bm not in (64, BLOCK):
         raise NotImplementedError("the HIP path is built for block_size_M = block_size_N = 128 "
-                                  "(the only value the reference scripts use)")
+                                  "(the only value the reference scripts use) or = 64")
+    return int(bm)
 
 
 # PROCESS DEFAULT of the K5 operand precision (a processor / call can override it: processor.qkv_fp8, qkv_fp8=...):
@@ -72,21 +75,29 @@ def run(variant: str, query, key, value, top_k, prob_threshold, block_neighbor_l
         cu_seqlens_q=None, cu_seqlens_kv=None, text_length: int = 256, first_frame_blocks=None,
         block_size_M: int = 128, block_size_N: int = 128, qkv_fp8: Optional[bool] = None):
     """qkv_fp8: per-call choice of the K5 operand precision (None = the process default set_qkv_fp8())."""
-    _check_blocks(block_size_M, block_size_N)
+    blk = _check_blocks(block_size_M, block_size_N)
     B, H, S, D = query.shape
     if variant == "hunyuan":
-        spec = _core.LayoutSpec.hunyuan(S, _int_at(cu_seqlens_q, 1))
+        spec = _core.LayoutSpec.hunyuan(S, _int_at(cu_seqlens_q, 1), block=blk)
     elif variant == "flux":
-        spec = _core.LayoutSpec.flux(S, int(text_length), _int_at(cu_seqlens_kv, 1, S))
+        spec = _core.LayoutSpec.flux(S, int(text_length), _int_at(cu_seqlens_kv, 1, S), block=blk)
     elif variant == "cogvideo":
-        spec = _core.LayoutSpec.cogvideo(S, int(text_length), _int_at(cu_seqlens_kv, 1, S))
+        spec = _core.LayoutSpec.cogvideo(S, int(text_length), _int_at(cu_seqlens_kv, 1, S), block=blk)
     elif variant == "wan":
-        spec = _core.LayoutSpec.wan(S, first_frame_blocks)
+        spec = _core.LayoutSpec.wan(S, first_frame_blocks, block=blk)
     else:
         raise ValueError(variant)
+    if blk != BLOCK:
+        # the fp8 K5 is built for 128-token blocks: the process default falls back to the 2-byte kernel (as for head dims
+        # without an fp8 kernel), an explicit per-call request is refused rather than silently not honoured
+        if qkv_fp8 is not None and _fp8_mode(qkv_fp8, D):
+            raise NotImplementedError(f"qkv_fp8={qkv_fp8!r} with block_size {blk}: the fp8 kernels are built for "
+                                      "128-token blocks only")
+        fp8 = False
+    else:
+        fp8 = _fp8_mode(QKV_FP8 if qkv_fp8 is None else qkv_fp8, D)
     return _core.rectified_attention(query, key, value, spec, int(top_k), float(prob_threshold),
-                                     block_neighbor_list, shape_xfuse=shape_xfuse,
-                                     qkv_fp8=_fp8_mode(QKV_FP8 if qkv_fp8 is None else qkv_fp8, D))
+                                     block_neighbor_list, shape_xfuse=shape_xfuse, qkv_fp8=fp8)
 
 
 # ---- small helpers shared by the processors ---------------------------------------------------------

@@ -97,6 +97,8 @@ struct AttnArgs {
     int gsync_ratio;                          // ... walks that keep 1 / gsync_ratio of the keys or more are not held (default 2)
     int rows256;                              // 64-row kernel, dense calls: NQB / NBv count 256-row tiles (four waves per workgroup, one K/V ring)
     int k5_static;                            // 64-row kernel, bf16: the steady state keeps the softmax reference it is entered with (checked, redone if it overflowed)
+    int blk;                                  // tokens per block: 128, or 64 (sparse calls through the _ex entry points: the 32-row kernel's pair walk)
+    int txt0;                                 // blk 64: first text query row (NBv * 64); text units of 128 rows from there
 #ifdef RSA_K5_DIAG
     unsigned long long* dbg;                  // diagnostics build only (make diag): per-wave s_memtime sums, see tools/diag_k5.py
 #endif

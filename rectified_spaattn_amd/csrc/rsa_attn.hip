@@ -74,7 +74,7 @@ extern "C" int rsa_set_tuning(const char* key, int value) {
 // are written as zeros (as the 1-workgroup form does).
 template <typename Tag>
 __global__ __launch_bounds__(256) void text_combine_kernel(const float* __restrict__ tpart, unsigned short* out,
-                                                           long osb, long osh, long oss, int D, int H, int NBv, int ntq,
+                                                           long osb, long osh, long oss, int D, int H, int txt0, int ntq,
                                                            int tsplit, int q_text_end, int Sq, long rows_total) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void text_combine_kernel(const float* __restri
     const int r = (int)(row % RSA_BLOCK);
     const long bh = bhq / ntq;
     const int tq = (int)(bhq % ntq);
-    const int grow = (NBv + tq) * RSA_BLOCK + r;
+    const int grow = txt0 + tq * RSA_BLOCK + r;   // (txt0 = NBv * block: the text rows, in units of 128)
     if (grow >= Sq) return;
     const float* base = tpart + (bhq * tsplit * RSA_BLOCK + r) * (long)(D + 2);
     const long pstride = (long)RSA_BLOCK * (D + 2);
@@ -136,18 +136,22 @@ __global__ __launch_bounds__(256) void text_combine_kernel(const float* __restri
 }
 
 // (also used by the fp8 kernel's host side, rsa_attn_fp8_kernel.hip)
-int rsa_launch_text_combine(const float* tpart, unsigned short* out, long osb, long osh, long oss, int D, int H, int NBv,
-                            int ntq, int tsplit, int q_text_end, int Sq, int BH, int dtype, hipStream_t s) {
+static int launch_text_combine_at(const float* tpart, unsigned short* out, long osb, long osh, long oss, int D, int H, int txt0,
+                                  int ntq, int tsplit, int q_text_end, int Sq, int BH, int dtype, hipStream_t s) {
     const long rows = (long)BH * ntq * RSA_BLOCK;
     if (rows <= 0) return RSA_OK;
     const dim3 grid((unsigned)((rows + 3) / 4));
     if (dtype == RSA_BF16)
-        text_combine_kernel<bf16_tag><<<grid, 256, 0, s>>>(tpart, out, osb, osh, oss, D, H, NBv, ntq, tsplit, q_text_end,
+        text_combine_kernel<bf16_tag><<<grid, 256, 0, s>>>(tpart, out, osb, osh, oss, D, H, txt0, ntq, tsplit, q_text_end,
                                                          Sq, rows);
     else
-        text_combine_kernel<fp16_tag><<<grid, 256, 0, s>>>(tpart, out, osb, osh, oss, D, H, NBv, ntq, tsplit, q_text_end,
+        text_combine_kernel<fp16_tag><<<grid, 256, 0, s>>>(tpart, out, osb, osh, oss, D, H, txt0, ntq, tsplit, q_text_end,
                                                          Sq, rows);
     return rsa_launch_status();
+}
+int rsa_launch_text_combine(const float* tpart, unsigned short* out, long osb, long osh, long oss, int D, int H, int NBv,
+                            int ntq, int tsplit, int q_text_end, int Sq, int BH, int dtype, hipStream_t s) {
+    return launch_text_combine_at(tpart, out, osb, osh, oss, D, H, NBv * RSA_BLOCK, ntq, tsplit, q_text_end, Sq, BH, dtype, s);
 }
 int rsa_text_split_enabled() { return g_k5_tsplit; }
 int rsa_shard_invariant() { return g_shard_invariant; }
@@ -238,8 +242,8 @@ static int launch_tail_combine(const AttnArgs& a, int dtype, hipStream_t s) {
 }
 
 static int launch_text_combine(const AttnArgs& a, int BH, int D, int dtype, hipStream_t s) {
-    return rsa_launch_text_combine(a.tpart, a.out, a.osb, a.osh, a.oss, D, a.H, a.NBv, a.NQB - a.NBv, a.tsplit,
-                                   a.q_text_end, a.Sq, BH, dtype, s);
+    return launch_text_combine_at(a.tpart, a.out, a.osb, a.osh, a.oss, D, a.H, a.txt0, a.NQB - a.NBv, a.tsplit,
+                                  a.q_text_end, a.Sq, BH, dtype, s);
 }
 
 // Aligned starts (rsa_attn.h): the counters are a ring of slots in a __device__ array of the code object (no allocation, nothing
@@ -295,14 +299,15 @@ static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes
     // split-KV for the dense text rows: without it one workgroup walks every key block of a text query block (902 at the
     // HunyuanVideo shape = 10 kept lists) -- hidden among 21 600 sparse blocks on one GPU, the critical path when the
     // heads are sharded over 8
-    const int n_txt_items = (a.kv_text_valid + RSA_BLOCK - 1) / RSA_BLOCK;
+    const int n_txt_items = (a.kv_text_valid + a.blk - 1) / a.blk;
     a.tsplit = 1; a.tper = n_txt_items;
     if (a.mode == MODE_SPARSE && ntq > 0 && a.tpart && g_k5_tsplit && n_txt_items >= 32) {
         int sp = n_txt_items / 16;
         // 16 pieces per text block; 32 (RSA_TEXT_SPLIT, what tpart is sized for) on grids of fewer than 8 generations, where the
         // pieces of 0.6 of a sparse walk's life would be the last to finish behind a split tail (and the combine pass that
         // doubles with them is still small)
-        int cap = ((long)BH * ((a.NBv + 7) & ~7) < 8 * 512 && !g_shard_invariant) ? RSA_TEXT_SPLIT : 16;
+        int cap = ((long)BH * (a.blk == 64 ? (((a.NBv + 1) >> 1) + 7) & ~7 : (a.NBv + 7) & ~7) < 8 * 512 && !g_shard_invariant)
+                      ? RSA_TEXT_SPLIT : 16;
         const int room = rsa_text_split_capacity(tpart_bytes, BH, ntq, D);   // what the caller's buffer holds
         if (cap > room) cap = room;
         a.tsplit = sp > cap ? cap : sp;
@@ -313,7 +318,7 @@ static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes
     a.heavy_last = a.tsplit > 1 && g_k5_text_last;
     a.BH = BH;
     a.n_heavy_pad = (n_heavy + 7) & ~7;
-    a.NBp = (a.NBv + 7) & ~7;
+    a.NBp = a.blk == 64 ? (((a.NBv + 1) >> 1) + 7) & ~7 : (a.NBv + 7) & ~7;   // (blk 64: pairs of query blocks)
     long nblocks = (long)a.n_heavy_pad + (long)BH * a.NBp;
     // Tail split (64-row kernel, sparse lists): 512 workgroups run at a time (2 per CU), each for about as long as the others, so
     // a launch costs ceil(workgroups / 512) lives; when the last generation of sparse blocks is less than half full, its blocks'
@@ -321,7 +326,7 @@ static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes
     // pass.  Which blocks are split depends on the grid: a sharded and an unsharded run then agree on those blocks within
     // rounding, not byte for byte (tuning key k5_tail_split = 0 keeps every walk whole).
     a.tail_first = a.tail_n = a.tail_p = 0; a.tail_part = nullptr;
-    const bool w64 = D == 128 && (g_k5_w64 & 1);
+    const bool w64 = D == 128 && (g_k5_w64 & 1) && a.blk == RSA_BLOCK;
     if (w64 && a.mode == MODE_SPARSE && a.tpart && (a.heavy_last || n_heavy == 0)) {
         // the pieces AND the text-row pieces behind them must fit the 512 slots together: otherwise whatever starts late (0.6 of a
         // life for a text piece) ends the launch as late as the unsplit tail did (measured: 3 heads of the headline shape, 456
@@ -338,7 +343,8 @@ static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes
     if (nblocks > 0x7FFFFFFF) return RSA_ERR_UNSUPPORTED;
     if (a.NB_total > 8192) return RSA_ERR_UNSUPPORTED;  // kept list lives in LDS as u16, 16 KiB max
     const size_t lds_bytes = (size_t)4 * 64 * D * 2 + (((size_t)a.NB_total * 2 + 15) & ~(size_t)15);
-    const bool use64 = (D == 128 && (g_k5_w64 & 1)) || (D == 64 && (g_k5_w64 & 2));
+    // (64-token blocks: the 32-row kernel, whose 64-key tiles are exactly one block)
+    const bool use64 = a.blk == RSA_BLOCK && ((D == 128 && (g_k5_w64 & 1)) || (D == 64 && (g_k5_w64 & 2)));
     const int st = use64 ? rsa_launch_bsfwd64(a, dim3((unsigned)nblocks), lds_bytes, D, dtype, s)
                          : rsa_launch_bsfwd(a, dim3((unsigned)nblocks), lds_bytes, D, dtype, s);
     if (st != RSA_OK) return st;
@@ -364,9 +370,9 @@ static int check_out(const rsa_out4& o) {
     return RSA_OK;
 }
 
-extern "C" int rsa_block_sparse_fwd(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
-                                    const rsa_buffers* buf, rsa_out4 out, void* stream) {
-    int st = rsa_check_layout(l);
+static int block_sparse_fwd_b(const rsa_layout* l, int blk, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                              const rsa_buffers* buf, rsa_out4 out, void* stream) {
+    int st = rsa_check_layout_b(l, blk);
     if (st != RSA_OK) return st;
     if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v)) ||
         (st = check_out(out)))
@@ -379,14 +385,24 @@ extern "C" int rsa_block_sparse_fwd(const rsa_layout* l, rsa_tensor4 q, rsa_tens
     a.tpart = buf->tpart;
     a.mode = MODE_SPARSE; a.H = l->H; a.Sq = l->S; a.Sk = l->S;
     a.NBv = l->NBv; a.NQB = l->NB_total; a.NB_total = l->NB_total;
+    a.blk = blk; a.txt0 = l->NBv * blk;
+    if (blk == 64) a.NQB = l->NBv + (l->NB_total - l->NBv + 1) / 2;   // text rows in 128-row units
     a.kv_valid = l->kv_valid; a.kv_text_valid = l->kv_text_valid;
-    a.q_text_end = l->NBv * RSA_BLOCK + l->q_text_valid;
+    a.q_text_end = l->NBv * blk + l->q_text_valid;
     a.q_split = 0; a.kv_split = 0; a.causal = 0; a.rows256 = 0;
     a.qk_scale = (float)((1.0 / sqrt((double)l->D)) * 1.44269504);  // sm_scale * 1.44269504 (hunyuan :145)
 #ifdef RSA_K5_DIAG
     a.dbg = reinterpret_cast<unsigned long long*>(g_dbg_ptr);
 #endif
     return launch_attn(a, l->B * l->H, l->D, l->dtype, buf->tpart_bytes, static_cast<hipStream_t>(stream));
+}
+extern "C" int rsa_block_sparse_fwd(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                                    const rsa_buffers* buf, rsa_out4 out, void* stream) {
+    return block_sparse_fwd_b(l, RSA_BLOCK, q, k, v, buf, out, stream);
+}
+extern "C" int rsa_block_sparse_fwd_ex(const rsa_layout_ex* lx, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                                       const rsa_buffers* buf, rsa_out4 out, void* stream) {
+    return rsa_layout_ex_ok(lx) ? block_sparse_fwd_b(&lx->base, lx->block, q, k, v, buf, out, stream) : RSA_ERR_BAD_ARG;
 }
 
 static int dense_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
@@ -405,6 +421,7 @@ static int dense_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_tensor4
     a.tpart = nullptr;
     a.tsplit = 1; a.tper = 0;
     a.mode = MODE_DENSE; a.H = H; a.Sq = Sq; a.Sk = Sk;
+    a.blk = RSA_BLOCK; a.txt0 = 0;
     // head dim 128 through the 64-row kernel: 256-row tiles once there are at least two of them (a shorter call keeps 128-row tiles)
     a.rows256 = (((D == 128 && (g_k5_w64 & 1)) || (D == 64 && (g_k5_w64 & 2))) && g_k5_rows256 && Sq > 256) ? 1 : 0;
 #ifdef RSA_K5_FORMS
@@ -442,4 +459,20 @@ extern "C" int rsa_rectified_attention(const rsa_layout* l, rsa_tensor4 q, rsa_t
     if ((st = rsa_select_mask(l, neighbor, top_k, p_remain, &buf, stream))) return st;
     if ((st = rsa_compensation(l, &buf, stream))) return st;
     return rsa_block_sparse_fwd(l, q, k, v, &buf, out, stream);
+}
+
+extern "C" int rsa_rectified_attention_ex(const rsa_layout_ex* lx, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                                          const uint8_t* neighbor, int top_k, float p_remain, void* workspace,
+                                          size_t workspace_bytes, rsa_out4 out, void* stream) {
+    if (!rsa_layout_ex_ok(lx)) return RSA_ERR_BAD_ARG;
+    if (lx->block == RSA_BLOCK)
+        return rsa_rectified_attention(&lx->base, q, k, v, neighbor, top_k, p_remain, workspace, workspace_bytes, out, stream);
+    rsa_buffers buf;
+    int st = rsa_carve_workspace_ex(lx, workspace, workspace_bytes, &buf);
+    if (st != RSA_OK) return st;
+    if ((st = rsa_pool_stats_ex(lx, q, k, v, &buf, stream))) return st;
+    if ((st = rsa_pooled_scores_ex(lx, k, &buf, stream))) return st;
+    if ((st = rsa_select_mask_ex(lx, neighbor, top_k, p_remain, &buf, stream))) return st;
+    if ((st = rsa_compensation_ex(lx, &buf, stream))) return st;
+    return rsa_block_sparse_fwd_ex(lx, q, k, v, &buf, out, stream);
 }

@@ -101,7 +101,13 @@ __device__ __forceinline__ void k5_block(f32x16 (&o)[D / 32], const s16x8 (&q)[D
 // -DRSA_K5_FORMS) carry both at either head dim plus 0 = the block as hipcc schedules it (round 2's kernel).  0 and 1 are
 // bit-identical to each other, 2 differs from them by the rounding order of S - m.
 constexpr int k5_product_form(int D) { return D == 128 ? 2 : 1; }
-template <int D, typename Tag, bool WIDE, int FORM>
+// BLK: tokens per block.  128: the 128-row query block of the header above, two 64-key tiles per kept block.  64 (the _ex entry
+// points): the workgroup owns the PAIR of query blocks (2 qblk, 2 qblk + 1), waves 0-1 the first, 2-3 the second, and walks the
+// union of their kept lists -- one 64-key tile per entry, staged once for both; the entries carry which of the two kept them
+// (bits 14 / 15 of the LDS list), and a wave pair masks the tiles of the other's list to -inf (exact: they add 0 to O and l, and
+// -inf leaves the running maximum alone), so every row gets the bytes its own list would give.  Dense text rows: 128-row units
+// from row NBv * 64 on (a.txt0).
+template <int D, typename Tag, bool WIDE, int FORM, int BLK = 128>
 __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     constexpr int NW = 4;                   // 4 waves x 32 query rows
     constexpr int KS = D / 16;
@@ -136,13 +142,15 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
         const int j = v % a.NBp;
         const int chunk = a.NBp >> 3;
         qblk = (j & 7) * chunk + (j >> 3);
-        if (qblk >= a.NBv) return;
+        if (qblk >= (BLK == 64 ? (a.NBv + 1) >> 1 : a.NBv)) return;
     }
     const int b = bh / a.H, h = bh % a.H;
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int grow = qblk * 128 + 32 * wv + r;
+    // BLK 64: qblk is the pair (sparse) or the 128-row text unit (text); qw = this wave's own query block
+    const int grow = (BLK == 64 && text ? a.txt0 + (qblk - a.NBv) * 128 : qblk * 128) + 32 * wv + r;
+    const int qw = BLK == 64 ? 2 * qblk + (wv >> 1) : qblk;
 
     // ---------------- per-row plan ----------------
     int lo_r = 0, hi_r = 0;
@@ -151,15 +159,15 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     const int32_t* list = nullptr;
     bool rectify = false;
     if (a.mode == MODE_SPARSE) {
-        if (qblk < a.NBv) {
-            const long rowi = (long)bh * a.NBv + qblk;
+        if (BLK == 64 ? !text : qblk < a.NBv) {
+            const long rowi = (long)bh * a.NBv + (BLK == 64 ? 2 * qblk : qblk);
             list = a.cols + rowi * a.NB_total;
             n_items = a.counts[rowi];
             lo_max = 0; hi_min = hi_max = a.kv_valid;
             rectify = a.R != nullptr;
-            hi_r = a.kv_valid; store_r = grow < a.Sq;
+            hi_r = a.kv_valid; store_r = grow < a.Sq && (BLK == 128 || qw < a.NBv);
         } else {
-            n_items = (a.kv_text_valid + RSA_BLOCK - 1) / RSA_BLOCK;
+            n_items = (a.kv_text_valid + BLK - 1) / BLK;
             if (a.tsplit > 1) {   // split-KV: this workgroup's slice of the key blocks
                 first_blk = tsp * a.tper;
                 n_items = n_items - first_blk < a.tper ? n_items - first_blk : a.tper;
@@ -206,22 +214,78 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     }
     n_items = __builtin_amdgcn_readfirstlane(n_items);
     const bool use_list = list != nullptr;
-    if (use_list) {
-        for (int i = t; i < n_items; i += 64 * NW) lds_list[i] = (unsigned short)list[i];
-        __syncthreads();
+    if constexpr (BLK == 64) {
+        if (use_list) {
+            // union of the pair's lists: both scattered into two bitmaps (in the K/V tile area, free until the first staging),
+            // one word per thread (NB_total <= 8 192: <= 256 words), a workgroup prefix sum of the popcounts, then each thread
+            // writes its word's entries in ascending order: block | kept by 2 qblk << 14 | kept by 2 qblk + 1 << 15
+            unsigned* bm = reinterpret_cast<unsigned*>(lds);
+            int* wsum = reinterpret_cast<int*>(lds + 2 * 256 * 4);
+            const int nw = (a.NB_total + 31) >> 5;
+            for (int i = t; i < 2 * nw; i += 64 * NW) bm[i] = 0u;
+            __syncthreads();
+#pragma unroll
+            for (int hb = 0; hb < 2; ++hb) {
+                const int qb = 2 * qblk + hb;
+                if (qb < a.NBv) {
+                    const long ri = (long)bh * a.NBv + qb;
+                    const int32_t* li = a.cols + ri * a.NB_total;
+                    const int n = a.counts[ri];
+                    for (int i = t; i < n; i += 64 * NW) {
+                        const int c = li[i];
+                        atomicOr(&bm[hb * nw + (c >> 5)], 1u << (c & 31));
+                    }
+                }
+            }
+            __syncthreads();
+            const unsigned w0 = t < nw ? bm[t] : 0u, w1 = t < nw ? bm[nw + t] : 0u;
+            unsigned u = w0 | w1;
+            const int c = __popc(u);
+            int x = c;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(x, d, 64);
+                if (lane >= d) x += y;
+            }
+            if (lane == 63) wsum[t >> 6] = x;
+            __syncthreads();
+            int off = x - c;
+            for (int ww = 0; ww < (t >> 6); ++ww) off += wsum[ww];
+            n_items = __builtin_amdgcn_readfirstlane(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+            while (u) {
+                const int bit = __ffs(u) - 1;
+                u &= u - 1;
+                lds_list[off++] = (unsigned short)((32 * t + bit) | (((w0 >> bit) & 1u) << 14) | (((w1 >> bit) & 1u) << 15));
+            }
+            __syncthreads();
+        }
+    } else {
+        if (use_list) {
+            for (int i = t; i < n_items; i += 64 * NW) lds_list[i] = (unsigned short)list[i];
+            __syncthreads();
+        }
     }
     auto blk_of = [&](int item) -> int { return use_list ? (int)lds_list[item] : first_blk + item; };
-    int n_tiles = 2 * n_items;
-    if (n_items > 0) {
+    // BLK 64: the raw list entry (block | owner bits; text walks: both owners) and the KEY WORD the tile queue carries: first key
+    // | owner bits << 28 (kkey / kmine take it apart).  BLK 128: the key itself.
+    auto raw64 = [&](int item) -> int { return use_list ? (int)lds_list[item] : (first_blk + item) | (3 << 14); };
+    auto kword = [&](int raw) -> int { return ((raw & 0x3FFF) * 64) | ((raw >> 14) << 28); };
+    auto kkey = [&](int kw) -> int { return BLK == 64 ? (kw & 0x0FFFFFFF) : kw; };
+    int n_tiles = BLK == 64 ? n_items : 2 * n_items;
+    if (BLK == 128 && n_items > 0) {
         const int last_blk = blk_of(n_items - 1);
         if (last_blk * RSA_BLOCK + 64 >= hi_max) n_tiles -= 1;
     }
     n_tiles = __builtin_amdgcn_readfirstlane(n_tiles);
     const int kv_limit = hi_max < a.Sk ? hi_max : a.Sk;
     auto key0_of = [&](int tile) -> int {  // first key of tile `tile` (clamped index: callers guard tile < n_tiles)
-        const int it = tile >> 1;
-        const int blk = __builtin_amdgcn_readfirstlane(blk_of(it < n_items ? it : (n_items > 0 ? n_items - 1 : 0)));
-        return blk * RSA_BLOCK + (tile & 1) * 64;
+        if constexpr (BLK == 64) {
+            return kword(__builtin_amdgcn_readfirstlane(raw64(tile < n_items ? tile : (n_items > 0 ? n_items - 1 : 0))));
+        } else {
+            const int it = tile >> 1;
+            const int blk = __builtin_amdgcn_readfirstlane(blk_of(it < n_items ? it : (n_items > 0 ? n_items - 1 : 0)));
+            return blk * RSA_BLOCK + (tile & 1) * 64;
+        }
     };
 
     // ---------------- Q fragments (B operand) ----------------
@@ -257,7 +321,8 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     const long kstep = (long)(4 * RPI) * a.kss * 2, vstep = (long)(4 * RPI) * a.vss * 2;  // bytes per group
     // the 64-key tile starting at key `key_first` -> LDS byte offset `lds_off` (tile slots: K0 K1 V0 V1)
-    auto dma = [&](int is_v, int key_first, unsigned lds_off) {
+    auto dma = [&](int is_v, int key_word, unsigned lds_off) {
+        const int key_first = kkey(key_word);
         const unsigned ld0 = lds_base + lds_off + wv * 1024;
         const unsigned char* base = is_v ? vbase : kbase;
         const long ss = is_v ? a.vss : a.kss;
@@ -358,13 +423,13 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
         const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
         mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
     };
-    auto apply_mask_sub = [&](f32x16& S, int key_first) {
+    auto apply_mask_sub = [&](f32x16& S, int key_first, bool mine) {
         int kbase = key_first + 4 * hh;
         asm volatile("" : "+v"(kbase));   // rare branch: keep its 16 key indices out of the loop's live registers
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int kk = kbase + (i & 3) + 8 * (i >> 2);
-            if (kk < lo_r || kk >= hi_r) S[i] = -INFINITY;
+            if (kk < lo_r || kk >= hi_r || !mine) S[i] = -INFINITY;
         }
     };
 
@@ -390,9 +455,10 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     // VS = slot parity of `tile` (its K and V slots); next scores = K(tile) sub-tile 1 (SUB 0) / K(tile+1) sub-tile 0 (SUB 1).
     auto half = [&](auto VS, auto SUB, int key0, f32x16& S_cur, float& mx_cur, f32x16& S_nxt, float& mx_nxt) {
         constexpr int vs = decltype(VS)::value, sub = decltype(SUB)::value;
-        const int kfirst = key0 + 32 * sub;
-        if (kfirst < lo_max || kfirst + 32 > hi_min) {
-            apply_mask_sub(S_cur, kfirst);
+        const int kfirst = kkey(key0) + 32 * sub;
+        const bool mine = BLK == 128 || ((key0 >> (28 + (wv >> 1))) & 1);   // (BLK 64: the tile is in this wave pair's list)
+        if (kfirst < lo_max || kfirst + 32 > hi_min || !mine) {
+            apply_mask_sub(S_cur, kfirst, mine);
             rowmax_sub(S_cur, mx_cur);
         }
         if constexpr (FORM == 2) {
@@ -516,7 +582,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     };
 
     // ---------------- prologue + main loop ----------------
-    if (qblk < a.NBv || a.mode != MODE_SPARSE) rsa_gsync_wait(a.gsync, gs_tk, n_items, a.NB_total, a.gsync_ratio);   // aligned starts: in front of the first staging instruction (text-row pieces do not wait, as in the 64-row and e4m3 kernels)
+    if ((BLK == 64 ? !text : qblk < a.NBv) || a.mode != MODE_SPARSE) rsa_gsync_wait(a.gsync, gs_tk, n_items, a.NB_total, a.gsync_ratio);   // aligned starts: in front of the first staging instruction (text-row pieces do not wait, as in the 64-row and e4m3 kernels)
     f32x16 SA, SB;
     float mxA = -INFINITY, mxB = -INFINITY;
     int key0 = 0;
@@ -535,6 +601,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     // The kept-list entry of tile+3 is read from LDS one advance() EARLY into a register (pref_raw) and only made scalar
     // here: the LDS round trip (~100 cycles, once per tile and wave) is off the wave's critical path.
     auto raw_item = [&](int tile) -> int {   // block index of `tile`'s list entry, still per lane (index clamped)
+        if constexpr (BLK == 64) return raw64(tile < n_items ? tile : (n_items > 0 ? n_items - 1 : 0));
         const int it = tile >> 1;
         return blk_of(it < n_items ? it : (n_items > 0 ? n_items - 1 : 0));
     };
@@ -542,7 +609,8 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     auto advance = [&](int tile) {  // after finishing `tile`: shift the key queue, tile+3's first key from the prefetched entry
         key0 = kq1;
         kq1 = kq2;
-        kq2 = __builtin_amdgcn_readfirstlane(pref_raw) * RSA_BLOCK + ((tile + 3) & 1) * 64;
+        if constexpr (BLK == 64) kq2 = kword(__builtin_amdgcn_readfirstlane(pref_raw));
+        else kq2 = __builtin_amdgcn_readfirstlane(pref_raw) * RSA_BLOCK + ((tile + 3) & 1) * 64;
         pref_raw = raw_item(tile + 4);
     };
     {
@@ -570,7 +638,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     const auto swl = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
     const float l_tot = RSM ? lacc[0] : __uint_as_float(swl[0]) + __uint_as_float(swl[1]);   // (RSM: already complete over both lane halves)
     bool done = false;
-    if (a.mode == MODE_SPARSE && a.tsplit > 1 && qblk >= a.NBv) {
+    if (a.mode == MODE_SPARSE && a.tsplit > 1 && (BLK == 64 ? text : qblk >= a.NBv)) {
         // split-KV partial of a text block: unnormalised O (fp32), m (log2 domain) and l per row; the combine
         // kernel (rsa_attn.hip) merges the tsplit parts
         const int ntq = a.NQB - a.NBv;
@@ -598,14 +666,14 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) cv[dt][g] = make_float4(0, 0, 0, 0);
         if (rectify && !zero_r) {
-            const long rowi = (long)bh * a.NBv + qblk;
+            const long rowi = (long)bh * a.NBv + qw;
             const float* cp = a.comp + rowi * D;
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) cv[dt][g] = *reinterpret_cast<const float4*>(cp + 32 * dt + 8 * g + 4 * hh);
         }
-        if (rectify) Rv = a.R[(long)bh * a.NBv + qblk];
+        if (rectify) Rv = a.R[(long)bh * a.NBv + qw];
         if (zero_r) inv = 0.0f;
         const float sc = inv * Rv;
         unsigned short* op = a.out + (long)b * a.osb + (long)h * a.osh + (long)grow * a.oss;
@@ -679,6 +747,21 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
 int g_rsa_k5_form = -1;   // A/B and diagnostics builds: tuning key "k5_form" (see the FORM template parameter); -1 = the product's choice
 #endif
 int rsa_launch_bsfwd(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
+    if (a.blk == 64) {   // (64-token blocks: the product form, pair-union walk; no A/B forms)
+        const bool wide64 = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
+#define RSA_K5B(DD, TT) \
+        do { \
+            if (wide64) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, k5_product_form(DD), 64>), a, true, grid, 256, lds_bytes, s); \
+            else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false, k5_product_form(DD), 64>), a, true, grid, 256, lds_bytes, s); \
+        } while (0)
+        if (D == 128) {
+            if (dtype == RSA_BF16) RSA_K5B(128, bf16_tag); else RSA_K5B(128, fp16_tag);
+        } else {
+            if (dtype == RSA_BF16) RSA_K5B(64, bf16_tag); else RSA_K5B(64, fp16_tag);
+        }
+#undef RSA_K5B
+        return rsa_launch_status();
+    }
     // the 16-byte output stores need 16-byte aligned rows; anything else takes the 8-byte form
     const bool wide = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
 #ifdef RSA_K5_FORMS

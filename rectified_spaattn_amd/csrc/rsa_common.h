@@ -64,22 +64,30 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-static inline int rsa_check_layout(const rsa_layout* l) {
+// blk: tokens per block (RSA_BLOCK, or 64 through the _ex entry points of 0.6.1)
+static inline int rsa_check_layout_b(const rsa_layout* l, int blk) {
+    if (blk != 64 && blk != 128) return RSA_ERR_UNSUPPORTED;
     if (!l) return RSA_ERR_BAD_ARG;
     if (l->B <= 0 || l->H <= 0 || l->S <= 0) return RSA_ERR_BAD_ARG;
     if (l->D != 64 && l->D != 128) return RSA_ERR_UNSUPPORTED;
     if (l->dtype != RSA_BF16 && l->dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
-    if (l->NB_total != (l->S + RSA_BLOCK - 1) / RSA_BLOCK) return RSA_ERR_BAD_ARG;
+    if (l->NB_total != (l->S + blk - 1) / blk) return RSA_ERR_BAD_ARG;
     if (l->NBv < 0 || l->NBv > l->NB_total) return RSA_ERR_BAD_ARG;
     if (l->n_txt < 0 || l->kv_valid < 0 || l->kv_valid > l->S) return RSA_ERR_BAD_ARG;
-    if (l->n_txt > 0 && (long)l->NBv * RSA_BLOCK + l->n_txt > l->S) return RSA_ERR_BAD_ARG;
+    if (l->n_txt > 0 && (long)l->NBv * blk + l->n_txt > l->S) return RSA_ERR_BAD_ARG;
     if (l->pool_valid < 0 || l->pool_valid > l->S) return RSA_ERR_BAD_ARG;
     if (l->text_end_block < 0 || l->text_end_block > l->NB_total) return RSA_ERR_BAD_ARG;
     if (l->first_frame_blocks < 0) return RSA_ERR_BAD_ARG;
-    if (l->q_text_valid < 0 || (long)l->NBv * RSA_BLOCK + l->q_text_valid > (long)l->NB_total * RSA_BLOCK)
+    if (l->q_text_valid < 0 || (long)l->NBv * blk + l->q_text_valid > (long)l->NB_total * blk)
         return RSA_ERR_BAD_ARG;
     if (l->kv_text_valid < 0 || l->kv_text_valid > l->S) return RSA_ERR_BAD_ARG;
     return RSA_OK;
+}
+
+static inline int rsa_check_layout(const rsa_layout* l) { return rsa_check_layout_b(l, RSA_BLOCK); }
+// rsa_layout_ex as the _ex entry points accept it: present, reserved words zero (a later release may give them a meaning)
+static inline bool rsa_layout_ex_ok(const rsa_layout_ex* lx) {
+    return lx && lx->reserved[0] == 0 && lx->reserved[1] == 0 && lx->reserved[2] == 0;
 }
 
 static inline int rsa_check_tensor(const rsa_tensor4& t) {

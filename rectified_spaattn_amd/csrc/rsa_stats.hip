@@ -25,8 +25,10 @@ struct PoolArgs {
 };
 
 // F8: the fp8 operand path's form -- the block is in registers anyway, so its e4m3 image is written in the same pass
-template <int D, typename Tag, bool F8>
+// BLK: tokens per block (128, or 64 through the _ex entry points): thread rows 16 i + g, i < BLK / 16, same reduction tree
+template <int D, typename Tag, bool F8, int BLK = RSA_BLOCK>
 __global__ __launch_bounds__(D * 2) void pool_stats_kernel(PoolArgs a) {
+    constexpr int NI = BLK / 16;     // rows per thread
     constexpr int CH = D / 8;        // 16-byte chunks per row
     constexpr int NTH = 16 * CH;     // threads
     constexpr int NW = NTH / 64;     // waves
@@ -45,8 +47,8 @@ __global__ __launch_bounds__(D * 2) void pool_stats_kernel(PoolArgs a) {
 
     float x[8][8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int row = blk * RSA_BLOCK + 16 * i + g;
+    for (int i = 0; i < NI; ++i) {
+        const int row = blk * BLK + 16 * i + g;
         uint4 raw = make_uint4(0, 0, 0, 0);
         if (row < valid) raw = *reinterpret_cast<const uint4*>(base + (long)row * ss);
         const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(D * 2) void pool_stats_kernel(PoolArgs a) {
         for (int e = 0; e < 8; ++e) {
             s[e] = x[0][e];
 #pragma unroll
-            for (int i = 1; i < 8; ++i) s[e] = s[e] + x[i][e];
+            for (int i = 1; i < NI; ++i) s[e] = s[e] + x[i][e];
         }
         // tree over g: in-wave lanes differ in g by multiples of CH
 #pragma unroll
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(D * 2) void pool_stats_kernel(PoolArgs a) {
                 tot = (red[0][c * 8 + e] + red[1][c * 8 + e]) + (red[2 % NW][c * 8 + e] + red[3 % NW][c * 8 + e]);
             else
                 tot = red[0][c * 8 + e] + red[1][c * 8 + e];
-            mean[e] = tot * (1.0f / RSA_BLOCK);
+            mean[e] = tot * (1.0f / BLK);
         }
     }
     const long orow = ((long)bh * a.nblk[which] + blk) * D + c * 8;
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(D * 2) void pool_stats_kernel(PoolArgs a) {
         for (int e = 0; e < 8; ++e) {
             s[e] = fabsf(x[0][e] - mean[e]);
 #pragma unroll
-            for (int i = 1; i < 8; ++i) s[e] = s[e] + fabsf(x[i][e] - mean[e]);
+            for (int i = 1; i < NI; ++i) s[e] = s[e] + fabsf(x[i][e] - mean[e]);
         }
 #pragma unroll
         for (int m = CH; m < 64; m <<= 1)
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(D * 2) void pool_stats_kernel(PoolArgs a) {
                           (red[2 % NW][c * 8 + e] + red[3 % NW][c * 8 + e]);
                 else
                     tot = red[0][c * 8 + e] + red[1][c * 8 + e];
-                r[e] = tot * (1.0f / RSA_BLOCK);
+                r[e] = tot * (1.0f / BLK);
             }
             float4* o = reinterpret_cast<float4*>(a.mad[which] + orow);
             o[0] = make_float4(r[0], r[1], r[2], r[3]);
@@ -163,6 +165,7 @@ struct ScoreArgs {
     float* scores;
     uint8_t* unrel;
     int NBv, n_txt, NS, D, H, BH;
+    int txt0;                    // token row of the first text token (NBv * block)
 };
 
 typedef float k2_f32x16 __attribute__((ext_vector_type(16)));
@@ -184,7 +187,7 @@ __device__ __forceinline__ void pooled_scores_tile(const ScoreArgs& a, int bh, i
     const unsigned short* kt = nullptr;
     if (MODE == 1) {
         const int b = bh / a.H, hd = bh % a.H;
-        kt = a.ktxt + (long)b * a.ksb + (long)hd * a.ksh + (long)a.NBv * RSA_BLOCK * a.kss;
+        kt = a.ktxt + (long)b * a.ksb + (long)hd * a.ksh + (long)a.txt0 * a.kss;
     }
     const bool live = i0 + 32 * wi < a.NBv && j0 + 32 * wj < ncols;   // wave-uniform
 
@@ -430,6 +433,7 @@ struct SelectArgs {
     int use_prefix;   // 1 = try the sorted-head path first (same result; tuning key "k3_prefix" for the A/B tests)
     int et_len;       // floats in the et[] region: >= n_txt and >= 2 * RSA_SEL_CAP (the sorted-head candidates reuse it)
     float thr, scale;
+    float blk;        // tokens per block: IPAR's weight of a visual block (rectified_hunyuan_attn.py:218-222)
 };
 int g_rsa_k3_prefix = 1;
 int g_rsa_k3_long = 0;    // 1 = the workgroup-per-row kernel for every row length (tuning key "k3_long": the tests compare the two)
@@ -625,11 +629,11 @@ __global__ __launch_bounds__(256) void select_mask_kernel(SelectArgs a) {
         }
         const float normal_sum = wave_tree4(pn);
         const float text_sum = wave_tree4(pt);
-        const float denom = normal_sum * 128.0f + text_sum;
+        const float denom = normal_sum * a.blk + text_sum;
 #pragma unroll
         for (int m = 0; m < KPL; ++m) {
             const int j = lane + 64 * m;
-            if (j < a.NBv) pr[j] = (xv[m] * 128.0f) / denom;
+            if (j < a.NBv) pr[j] = (xv[m] * a.blk) / denom;
         }
         if (lane == 0) pr[a.NBv] = text_sum / denom;
     } else {
@@ -847,9 +851,9 @@ __global__ __launch_bounds__(256) void select_mask_long_kernel(SelectArgs a) {
         for (int u = t; u < a.n_txt; u += 256) pt = pt + xs[a.NBv + u];
         const float normal_sum = block_tree_sum(pn, red);
         const float text_sum = block_tree_sum(pt, red);      // (its barriers sit behind every thread's reads of the text entries)
-        const float denom = normal_sum * 128.0f + text_sum;
+        const float denom = normal_sum * a.blk + text_sum;
         __syncthreads();
-        for (int j = t; j < a.NBv; j += 256) xs[j] = (xs[j] * 128.0f) / denom;
+        for (int j = t; j < a.NBv; j += 256) xs[j] = (xs[j] * a.blk) / denom;
         if (t == 0) xs[a.NBv] = text_sum / denom;
     }
     __syncthreads();
@@ -1148,8 +1152,10 @@ __global__ void gapr_compare_kernel(const float* qbar, const float* aq, const fl
 // =====================================================================================================
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-extern "C" int rsa_buffer_bytes(const rsa_layout* l, size_t sizes[RSA_NUM_BUFFERS], size_t* total) {
-    int st = rsa_check_layout(l);
+// (blk = 64: the text / tail partials keep their 128-row pieces; NB_total - NBv counts 64-token blocks, at least as many
+// pieces as the 128-row text units K5 walks at that block size -- rsa_attn.hip::launch_attn)
+static int buffer_bytes_b(const rsa_layout* l, int blk, size_t sizes[RSA_NUM_BUFFERS], size_t* total) {
+    int st = rsa_check_layout_b(l, blk);
     if (st != RSA_OK) return st;
     if (!sizes || !total) return RSA_ERR_BAD_ARG;
     const size_t BH = (size_t)l->B * l->H, NBv = l->NBv, NB = l->NB_total, D = l->D;
@@ -1168,9 +1174,16 @@ extern "C" int rsa_buffer_bytes(const rsa_layout* l, size_t sizes[RSA_NUM_BUFFER
     return RSA_OK;
 }
 
-extern "C" int rsa_carve_workspace(const rsa_layout* l, void* ws, size_t ws_bytes, rsa_buffers* out) {
+extern "C" int rsa_buffer_bytes(const rsa_layout* l, size_t sizes[RSA_NUM_BUFFERS], size_t* total) {
+    return buffer_bytes_b(l, RSA_BLOCK, sizes, total);
+}
+extern "C" int rsa_buffer_bytes_ex(const rsa_layout_ex* lx, size_t sizes[RSA_NUM_BUFFERS], size_t* total) {
+    return rsa_layout_ex_ok(lx) ? buffer_bytes_b(&lx->base, lx->block, sizes, total) : RSA_ERR_BAD_ARG;
+}
+
+static int carve_workspace_b(const rsa_layout* l, int blk, void* ws, size_t ws_bytes, rsa_buffers* out) {
     size_t sizes[RSA_NUM_BUFFERS], total;
-    int st = rsa_buffer_bytes(l, sizes, &total);
+    int st = buffer_bytes_b(l, blk, sizes, &total);
     if (st != RSA_OK) return st;
     if (!ws || !out || (reinterpret_cast<uintptr_t>(ws) & 255)) return RSA_ERR_BAD_ARG;
     if (ws_bytes < total) return RSA_ERR_WORKSPACE;
@@ -1188,11 +1201,17 @@ extern "C" int rsa_carve_workspace(const rsa_layout* l, void* ws, size_t ws_byte
     out->tpart_bytes = sizes[14];
     return RSA_OK;
 }
+extern "C" int rsa_carve_workspace(const rsa_layout* l, void* ws, size_t ws_bytes, rsa_buffers* out) {
+    return carve_workspace_b(l, RSA_BLOCK, ws, ws_bytes, out);
+}
+extern "C" int rsa_carve_workspace_ex(const rsa_layout_ex* lx, void* ws, size_t ws_bytes, rsa_buffers* out) {
+    return rsa_layout_ex_ok(lx) ? carve_workspace_b(&lx->base, lx->block, ws, ws_bytes, out) : RSA_ERR_BAD_ARG;
+}
 
 // K1, optionally writing the e4m3 images of the blocks it pools (rsa_common.h); rsa_pool_stats is the public form without
-int rsa_pool_stats_f8(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const rsa_buffers* buf,
-                      const Fp8Emit* f8, void* stream) {
-    int st = rsa_check_layout(l);
+static int pool_stats_b(const rsa_layout* l, int blk, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const rsa_buffers* buf,
+                        const Fp8Emit* f8, void* stream) {
+    int st = rsa_check_layout_b(l, blk);
     if (st != RSA_OK) return st;
     if (!buf || !buf->qbar || !buf->aq || !buf->kbar || !buf->ak || !buf->vbar) return RSA_ERR_BAD_ARG;
     if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v))) return st;
@@ -1203,7 +1222,8 @@ int rsa_pool_stats_f8(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_ten
         a.sb[i] = ts[i]->stride_b; a.sh[i] = ts[i]->stride_h; a.ss[i] = ts[i]->stride_s;
         a.ext_mean[i] = nullptr;
     }
-    const int vis_tok = l->NBv * RSA_BLOCK;
+    if (f8 != nullptr && blk != RSA_BLOCK) return RSA_ERR_UNSUPPORTED;   // (the fp8 operand images are 128-row blocks)
+    const int vis_tok = l->NBv * blk;
     a.mean[0] = buf->qbar; a.mad[0] = buf->aq; a.nblk[0] = l->NBv; a.valid[0] = l->S < vis_tok ? l->S : vis_tok;
     a.mean[1] = buf->kbar; a.mad[1] = buf->ak; a.nblk[1] = l->NBv;
     a.valid[1] = l->pool_valid < vis_tok ? l->pool_valid : vis_tok;
@@ -1224,6 +1244,16 @@ int rsa_pool_stats_f8(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_ten
         }
         return rsa_launch_status();
     }
+    if (blk == 64) {
+        if (l->D == 128) {
+            if (l->dtype == RSA_BF16) pool_stats_kernel<128, bf16_tag, false, 64><<<grid, 256, 0, s>>>(a);
+            else pool_stats_kernel<128, fp16_tag, false, 64><<<grid, 256, 0, s>>>(a);
+        } else {
+            if (l->dtype == RSA_BF16) pool_stats_kernel<64, bf16_tag, false, 64><<<grid, 128, 0, s>>>(a);
+            else pool_stats_kernel<64, fp16_tag, false, 64><<<grid, 128, 0, s>>>(a);
+        }
+        return rsa_launch_status();
+    }
     if (l->D == 128) {
         if (l->dtype == RSA_BF16) pool_stats_kernel<128, bf16_tag, false><<<grid, 256, 0, s>>>(a);
         else pool_stats_kernel<128, fp16_tag, false><<<grid, 256, 0, s>>>(a);
@@ -1233,14 +1263,22 @@ int rsa_pool_stats_f8(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_ten
     }
     return rsa_launch_status();
 }
+int rsa_pool_stats_f8(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const rsa_buffers* buf,
+                      const Fp8Emit* f8, void* stream) {
+    return pool_stats_b(l, RSA_BLOCK, q, k, v, buf, f8, stream);
+}
 
 extern "C" int rsa_pool_stats(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
                               const rsa_buffers* buf, void* stream) {
     return rsa_pool_stats_f8(l, q, k, v, buf, nullptr, stream);
 }
+extern "C" int rsa_pool_stats_ex(const rsa_layout_ex* lx, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                                 const rsa_buffers* buf, void* stream) {
+    return rsa_layout_ex_ok(lx) ? pool_stats_b(&lx->base, lx->block, q, k, v, buf, nullptr, stream) : RSA_ERR_BAD_ARG;
+}
 
-extern "C" int rsa_pooled_scores(const rsa_layout* l, rsa_tensor4 k, const rsa_buffers* buf, void* stream) {
-    int st = rsa_check_layout(l);
+static int pooled_scores_b(const rsa_layout* l, int blk, rsa_tensor4 k, const rsa_buffers* buf, void* stream) {
+    int st = rsa_check_layout_b(l, blk);
     if (st != RSA_OK) return st;
     if (!buf || !buf->qbar || !buf->aq || !buf->kbar || !buf->ak || !buf->scores || !buf->unrel)
         return RSA_ERR_BAD_ARG;
@@ -1252,6 +1290,7 @@ extern "C" int rsa_pooled_scores(const rsa_layout* l, rsa_tensor4 k, const rsa_b
     a.ksb = k.stride_b; a.ksh = k.stride_h; a.kss = k.stride_s;
     a.scores = buf->scores; a.unrel = buf->unrel;
     a.NBv = l->NBv; a.n_txt = l->n_txt; a.NS = l->NBv + l->n_txt; a.D = l->D; a.H = l->H;
+    a.txt0 = l->NBv * blk;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int BH = l->B * l->H;
     const unsigned nti = (unsigned)((l->NBv + 63) / 64);
@@ -1271,9 +1310,16 @@ extern "C" int rsa_pooled_scores(const rsa_layout* l, rsa_tensor4 k, const rsa_b
     return rsa_launch_status();
 }
 
-extern "C" int rsa_select_mask(const rsa_layout* l, const uint8_t* neighbor, int top_k, float p_remain,
-                               const rsa_buffers* buf, void* stream) {
-    int st = rsa_check_layout(l);
+extern "C" int rsa_pooled_scores(const rsa_layout* l, rsa_tensor4 k, const rsa_buffers* buf, void* stream) {
+    return pooled_scores_b(l, RSA_BLOCK, k, buf, stream);
+}
+extern "C" int rsa_pooled_scores_ex(const rsa_layout_ex* lx, rsa_tensor4 k, const rsa_buffers* buf, void* stream) {
+    return rsa_layout_ex_ok(lx) ? pooled_scores_b(&lx->base, lx->block, k, buf, stream) : RSA_ERR_BAD_ARG;
+}
+
+static int select_mask_b(const rsa_layout* l, int blk, const uint8_t* neighbor, int top_k, float p_remain,
+                         const rsa_buffers* buf, void* stream) {
+    int st = rsa_check_layout_b(l, blk);
     if (st != RSA_OK) return st;
     if (!buf || !buf->scores || !buf->unrel || !buf->probs || !buf->w || !buf->R || !buf->bitmask || !buf->cols ||
         !buf->counts || top_k < 0)
@@ -1289,6 +1335,7 @@ extern "C" int rsa_select_mask(const rsa_layout* l, const uint8_t* neighbor, int
     a.N2 = n2; a.NB_total = l->NB_total; a.NW = (l->NB_total + 31) / 32;
     a.text_end_block = l->text_end_block; a.ffb = l->first_frame_blocks; a.top_k = top_k;
     a.thr = p_remain;
+    a.blk = (float)blk;
     a.scale = (float)(1.0 / sqrt((double)l->D));  // head_dim ** -0.5 rounded to fp32 (hunyuan :208)
     a.rows_total = l->B * l->H * l->NBv;
     a.use_prefix = g_rsa_k3_prefix;
@@ -1337,9 +1384,17 @@ extern "C" int rsa_select_mask(const rsa_layout* l, const uint8_t* neighbor, int
     if (st != RSA_OK) return st;
     return st;
 }
+extern "C" int rsa_select_mask(const rsa_layout* l, const uint8_t* neighbor, int top_k, float p_remain,
+                               const rsa_buffers* buf, void* stream) {
+    return select_mask_b(l, RSA_BLOCK, neighbor, top_k, p_remain, buf, stream);
+}
+extern "C" int rsa_select_mask_ex(const rsa_layout_ex* lx, const uint8_t* neighbor, int top_k, float p_remain,
+                                  const rsa_buffers* buf, void* stream) {
+    return rsa_layout_ex_ok(lx) ? select_mask_b(&lx->base, lx->block, neighbor, top_k, p_remain, buf, stream) : RSA_ERR_BAD_ARG;
+}
 
-extern "C" int rsa_compensation(const rsa_layout* l, const rsa_buffers* buf, void* stream) {
-    int st = rsa_check_layout(l);
+static int compensation_b(const rsa_layout* l, int blk, const rsa_buffers* buf, void* stream) {
+    int st = rsa_check_layout_b(l, blk);
     if (st != RSA_OK) return st;
     if (!buf || !buf->w || !buf->vbar || !buf->comp) return RSA_ERR_BAD_ARG;
     if (l->NBv == 0) return RSA_OK;
@@ -1357,11 +1412,18 @@ extern "C" int rsa_compensation(const rsa_layout* l, const rsa_buffers* buf, voi
     else compensation_kernel<64><<<grid, 128, 0, s>>>(buf->w, buf->vbar, buf->comp, l->NBv, L, l->NB_total);
     return rsa_launch_status();
 }
+extern "C" int rsa_compensation(const rsa_layout* l, const rsa_buffers* buf, void* stream) {
+    return compensation_b(l, RSA_BLOCK, buf, stream);
+}
+extern "C" int rsa_compensation_ex(const rsa_layout_ex* lx, const rsa_buffers* buf, void* stream) {
+    return rsa_layout_ex_ok(lx) ? compensation_b(&lx->base, lx->block, buf, stream) : RSA_ERR_BAD_ARG;
+}
 
-extern "C" int rsa_estimate_pr_gain(int BH, int NQ, int NK, int D, int dtype, const void* q_blocks,
-                                    const void* k_blocks, const float* q_pools, const float* k_pools,
-                                    const float* scores, float* scratch_aq, float* scratch_ak, uint8_t* mask_out,
-                                    void* stream) {
+extern "C" int rsa_estimate_pr_gain_ex(int BH, int NQ, int NK, int D, int dtype, int block, const void* q_blocks,
+                                       const void* k_blocks, const float* q_pools, const float* k_pools,
+                                       const float* scores, float* scratch_aq, float* scratch_ak, uint8_t* mask_out,
+                                       void* stream) {
+    if (block != 64 && block != RSA_BLOCK) return RSA_ERR_UNSUPPORTED;
     if (BH <= 0 || NQ <= 0 || NK <= 0 || !q_blocks || !k_blocks || !q_pools || !k_pools || !scores || !scratch_aq ||
         !scratch_ak || !mask_out)
         return RSA_ERR_BAD_ARG;
@@ -1377,14 +1439,22 @@ extern "C" int rsa_estimate_pr_gain(int BH, int NQ, int NK, int D, int dtype, co
         float* scratch = which == 0 ? scratch_aq : scratch_ak;
         for (int i = 0; i < 3; ++i) {
             a.src[i] = static_cast<const unsigned short*>(which == 0 ? q_blocks : k_blocks);
-            a.sb[i] = 0; a.sh[i] = (long)N * RSA_BLOCK * D; a.ss[i] = D;
+            a.sb[i] = 0; a.sh[i] = (long)N * block * D; a.ss[i] = D;
             a.mean[i] = scratch; a.mad[i] = scratch + (size_t)BH * N * D;
-            a.nblk[i] = i == 0 ? N : 0; a.valid[i] = N * RSA_BLOCK;
+            a.nblk[i] = i == 0 ? N : 0; a.valid[i] = N * block;
             a.ext_mean[i] = which == 0 ? q_pools : k_pools;
         }
         a.H = BH;
         dim3 grid(N, BH, 1);
-        if (D == 128) {
+        if (block == 64) {
+            if (D == 128) {
+                if (dtype == RSA_BF16) pool_stats_kernel<128, bf16_tag, false, 64><<<grid, 256, 0, s>>>(a);
+                else pool_stats_kernel<128, fp16_tag, false, 64><<<grid, 256, 0, s>>>(a);
+            } else {
+                if (dtype == RSA_BF16) pool_stats_kernel<64, bf16_tag, false, 64><<<grid, 128, 0, s>>>(a);
+                else pool_stats_kernel<64, fp16_tag, false, 64><<<grid, 128, 0, s>>>(a);
+            }
+        } else if (D == 128) {
             if (dtype == RSA_BF16) pool_stats_kernel<128, bf16_tag, false><<<grid, 256, 0, s>>>(a);
             else pool_stats_kernel<128, fp16_tag, false><<<grid, 256, 0, s>>>(a);
         } else {
@@ -1396,6 +1466,13 @@ extern "C" int rsa_estimate_pr_gain(int BH, int NQ, int NK, int D, int dtype, co
     gapr_compare_kernel<<<g, 128, 0, s>>>(q_pools, scratch_aq + (size_t)BH * NQ * D, k_pools,
                                           scratch_ak + (size_t)BH * NK * D, scores, mask_out, NQ, NK, D);
     return rsa_launch_status();
+}
+extern "C" int rsa_estimate_pr_gain(int BH, int NQ, int NK, int D, int dtype, const void* q_blocks,
+                                    const void* k_blocks, const float* q_pools, const float* k_pools,
+                                    const float* scores, float* scratch_aq, float* scratch_ak, uint8_t* mask_out,
+                                    void* stream) {
+    return rsa_estimate_pr_gain_ex(BH, NQ, NK, D, dtype, RSA_BLOCK, q_blocks, k_blocks, q_pools, k_pools, scores, scratch_aq,
+                                   scratch_ak, mask_out, stream);
 }
 
 extern "C" const char* rsa_status_string(int status) {
@@ -1413,7 +1490,8 @@ int g_rsa_last_hip_error = 0;
 extern "C" const char* rsa_last_hip_error(void) { return hipGetErrorString((hipError_t)g_rsa_last_hip_error); }
 
 extern "C" int rsa_abi_check(int header_version, size_t sizeof_rsa_buffers, size_t sizeof_rsa_layout) {
+    // (0.6.1 added entry points only: a host built against the 0.6.0 header passes)
     return (header_version / 100 == RSA_HEADER_VERSION / 100 && sizeof_rsa_buffers == sizeof(rsa_buffers) &&
             sizeof_rsa_layout == sizeof(rsa_layout)) ? RSA_OK : RSA_ERR_UNSUPPORTED;
 }
-extern "C" int rsa_version(void) { return 600; }  // 0.6.0: rsa_abi_check; the pv entry points refuse K spans a 32-bit row offset cannot reach; 0.5.0: rsa_buffers.tpart_bytes (declared capacity of the partial buffer; carve_workspace hands tpart out for every layout), rsa_set_shard_invariant, rsa_comm_count; 0.4.0: rsa_p2p_state_alloc / _free / _timeout (fine-grained exchange state), rsa_dense_masked_fwd; 0.3.1: block-scaled fp8 operands (rsa_fp8_operands.scales = E8M0 words + K mean), K1 writes the images, rsa_fp8_images gone; 0.3.0: rsa_buffers has 15 members, rsa_allgather_heads_p2p is stream-ordered (+ state buffers), rsa_ipc_offset
+extern "C" int rsa_version(void) { return 601; }  // 0.6.1: 64-token blocks through rsa_layout_ex and the _ex entry points (rsa_buffer_bytes_ex, rsa_carve_workspace_ex, rsa_pool_stats_ex, rsa_pooled_scores_ex, rsa_select_mask_ex, rsa_compensation_ex, rsa_block_sparse_fwd_ex, rsa_rectified_attention_ex, rsa_estimate_pr_gain_ex); 0.6.0: rsa_abi_check; the pv entry points refuse K spans a 32-bit row offset cannot reach; 0.5.0: rsa_buffers.tpart_bytes (declared capacity of the partial buffer; carve_workspace hands tpart out for every layout), rsa_set_shard_invariant, rsa_comm_count; 0.4.0: rsa_p2p_state_alloc / _free / _timeout (fine-grained exchange state), rsa_dense_masked_fwd; 0.3.1: block-scaled fp8 operands (rsa_fp8_operands.scales = E8M0 words + K mean), K1 writes the images, rsa_fp8_images gone; 0.3.0: rsa_buffers has 15 members, rsa_allgather_heads_p2p is stream-ordered (+ state buffers), rsa_ipc_offset

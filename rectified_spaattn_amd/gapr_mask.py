@@ -7,7 +7,7 @@ from . import _core, _lib
 
 
 def estimate_pr_gain(Q_blocks, K_blocks, q_pools, k_pools, attention_scores):
-    """Q_blocks/K_blocks [B,H,N,128,d] (bf16/fp16 device tensors), q_pools/k_pools [B,H,N,d], attention_scores
+    """Q_blocks/K_blocks [B,H,N,b,d] with b = 128 or 64 (bf16/fp16 device tensors), q_pools/k_pools [B,H,N,d], attention_scores
     [B,H,NQ,NK] (unscaled pooled scores).  Returns bool [B,H,NQ,NK]: True where the pooled-score gain does NOT
     exceed the pooling error, i.e. ~gapr_mask, exactly what the reference returns.
 
@@ -16,8 +16,8 @@ def estimate_pr_gain(Q_blocks, K_blocks, q_pools, k_pools, attention_scores):
     _core._require_device(Q_blocks, K_blocks, q_pools, k_pools, attention_scores)
     B, H, NQ, IQ, d = Q_blocks.shape
     NK, JK = K_blocks.shape[2], K_blocks.shape[3]
-    if IQ != _lib.BLOCK or JK != _lib.BLOCK:
-        raise NotImplementedError("estimate_pr_gain on the HIP path needs 128-token blocks")
+    if IQ != JK or IQ not in _lib.BLOCKS:
+        raise NotImplementedError("estimate_pr_gain on the HIP path needs 128- or 64-token blocks (IQ == JK)")
     BH = B * H
     qb, kb = Q_blocks.contiguous(), K_blocks.contiguous()
     qp = q_pools.reshape(BH, NQ, d).float().contiguous()
@@ -28,8 +28,14 @@ def estimate_pr_gain(Q_blocks, K_blocks, q_pools, k_pools, attention_scores):
     out = torch.empty(BH, NQ, NK, dtype=torch.uint8, device=qb.device)
     vp = ctypes.c_void_p
     with torch.cuda.device(qb.device):
-        _lib.check(_lib.lib().rsa_estimate_pr_gain(BH, NQ, NK, d, _core.dtype_code(qb.dtype), vp(qb.data_ptr()),
-                                                   vp(kb.data_ptr()), vp(qp.data_ptr()), vp(kp.data_ptr()),
-                                                   vp(sc.data_ptr()), vp(s_q.data_ptr()), vp(s_k.data_ptr()),
-                                                   vp(out.data_ptr()), _core._stream()), "rsa_estimate_pr_gain")
+        if IQ == _lib.BLOCK:
+            _lib.check(_lib.lib().rsa_estimate_pr_gain(BH, NQ, NK, d, _core.dtype_code(qb.dtype), vp(qb.data_ptr()),
+                                                       vp(kb.data_ptr()), vp(qp.data_ptr()), vp(kp.data_ptr()),
+                                                       vp(sc.data_ptr()), vp(s_q.data_ptr()), vp(s_k.data_ptr()),
+                                                       vp(out.data_ptr()), _core._stream()), "rsa_estimate_pr_gain")
+        else:
+            _lib.check(_lib.lib().rsa_estimate_pr_gain_ex(BH, NQ, NK, d, _core.dtype_code(qb.dtype), IQ, vp(qb.data_ptr()),
+                                                          vp(kb.data_ptr()), vp(qp.data_ptr()), vp(kp.data_ptr()),
+                                                          vp(sc.data_ptr()), vp(s_q.data_ptr()), vp(s_k.data_ptr()),
+                                                          vp(out.data_ptr()), _core._stream()), "rsa_estimate_pr_gain_ex")
     return out.view(B, H, NQ, NK).bool()

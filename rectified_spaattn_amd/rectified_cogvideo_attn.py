@@ -31,7 +31,7 @@ def rectified_block_sparse_attention(query, key, value, attn_mask, top_k, block_
 class RectifiedCogVideoXVideoSpaAttnProcessor2_0:
     """Reference :410-523: sparse once the step counter reaches 5; dense otherwise (any mode)."""
 
-    def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0):
+    def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0, block_size=128):
         if not hasattr(F, "scaled_dot_product_attention"):
             raise ImportError("CogVideoXAttnProcessor requires PyTorch 2.0, to use it, please upgrade PyTorch to 2.0.")
         self.mode = mode
@@ -43,6 +43,9 @@ class RectifiedCogVideoXVideoSpaAttnProcessor2_0:
         # K5 / dense-kernel operand precision of THIS processor (None = process default, see set_qkv_fp8 / set_dense_fp8)
         self.qkv_fp8 = None
         self.dense_fp8 = None
+        # tokens per block of the sparse steps (block_size_M = block_size_N; 64 or 128, the default).  The block_neighbor_list
+        # must be built at the same block size (gilbert_block_neighbor_mapping(..., block_size=block_size))
+        self.block_size = op._check_blocks(block_size, block_size)
 
     def __call__(self, attn, hidden_states, encoder_hidden_states, attention_mask=None, image_rotary_emb=None):
         n_txt = encoder_hidden_states.size(1)
@@ -76,7 +79,8 @@ class RectifiedCogVideoXVideoSpaAttnProcessor2_0:
             out = rectified_block_sparse_attention(q, k, v, attn_mask=attention_mask, top_k=self.select_block_num,
                                                    cu_seqlens_q=cu_q, cu_seqlens_kv=cu_kv, max_seqlen_q=S,
                                                    max_seqlen_kv=S_k, block_neighbor_list=self.block_neighbor_list,
-                                                   p_remain_rates=self.p_remain_rates, text_length=n_txt, qkv_fp8=self.qkv_fp8)
+                                                   p_remain_rates=self.p_remain_rates, text_length=n_txt, qkv_fp8=self.qkv_fp8,
+                                                   block_size_M=self.block_size, block_size_N=self.block_size)
         else:
             dense_mode = self.mode if self.mode in ("torch", "vanilla") else "flash"
             out = fullattn(q, k, v, mode=dense_mode, drop_rate=0.0, attn_mask=attention_mask, causal=False,

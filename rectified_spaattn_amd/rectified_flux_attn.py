@@ -35,7 +35,7 @@ class RectifiedFluxSpaAttnProcessor2_0:
     Deviation on purpose: the dense branch honours self.mode ("torch"/"vanilla" run on
     CPU tensors) instead of being hard-wired to "flash"; on device all dense modes are the same HIP kernel."""
 
-    def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0, text_length=256):
+    def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0, text_length=256, block_size=128):
         if not hasattr(F, "scaled_dot_product_attention"):
             raise ImportError("FluxAttnProcessor2_0 requires PyTorch 2.0. To use it, please upgrade PyTorch to 2.0.")
         self.mode = mode
@@ -47,6 +47,9 @@ class RectifiedFluxSpaAttnProcessor2_0:
         # K5 / dense-kernel operand precision of THIS processor (None = process default, see set_qkv_fp8 / set_dense_fp8)
         self.qkv_fp8 = None
         self.dense_fp8 = None
+        # tokens per block of the sparse steps (block_size_M = block_size_N; 64 or 128, the default).  The block_neighbor_list
+        # must be built at the same block size (gilbert_block_neighbor_mapping(..., block_size=block_size))
+        self.block_size = op._check_blocks(block_size, block_size)
         self.text_length = text_length
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, image_rotary_emb=None):
@@ -105,7 +108,8 @@ class RectifiedFluxSpaAttnProcessor2_0:
             out = rectified_block_sparse_attention(q, k, v, attn_mask=attention_mask, top_k=self.select_block_num,
                                                    cu_seqlens_q=cu_q, cu_seqlens_kv=cu_kv, max_seqlen_q=S_q,
                                                    max_seqlen_kv=S_k, block_neighbor_list=self.block_neighbor_list,
-                                                   p_remain_rates=self.p_remain_rates, text_length=self.text_length, qkv_fp8=self.qkv_fp8)
+                                                   p_remain_rates=self.p_remain_rates, text_length=self.text_length, qkv_fp8=self.qkv_fp8,
+                                                   block_size_M=self.block_size, block_size_N=self.block_size)
         else:
             dense_mode = self.mode if self.mode in ("torch", "vanilla") else "flash"
             out = fullattn(q, k, v, mode=dense_mode, drop_rate=0.0, attn_mask=attention_mask, causal=False,

@@ -36,7 +36,7 @@ class RectifiedHunyuanVideoSpaAttnProcessor2_0:
     """Drop-in for the reference processor (:419-545): positional ctor (mode, select_block_num,
     block_neighbor_list, p_remain_rates, processor_id), same __call__ keywords, step counter wrapping at 50."""
 
-    def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0):
+    def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0, block_size=128):
         if not hasattr(F, "scaled_dot_product_attention"):
             raise ImportError("HunyuanVideoAttnProcessor2_0 requires PyTorch 2.0. To use it, please upgrade "
                               "PyTorch to 2.0.")
@@ -49,6 +49,9 @@ class RectifiedHunyuanVideoSpaAttnProcessor2_0:
         # K5 / dense-kernel operand precision of THIS processor (None = process default, see set_qkv_fp8 / set_dense_fp8)
         self.qkv_fp8 = None
         self.dense_fp8 = None
+        # tokens per block of the sparse steps (block_size_M = block_size_N; 64 or 128, the default).  The block_neighbor_list
+        # must be built at the same block size (gilbert_block_neighbor_mapping(..., block_size=block_size))
+        self.block_size = op._check_blocks(block_size, block_size)
 
     def __call__(self, attn, hidden_states: torch.Tensor, encoder_hidden_states: Optional[torch.Tensor] = None,
                  attention_mask: Optional[torch.Tensor] = None, image_rotary_emb=None,
@@ -113,7 +116,8 @@ class RectifiedHunyuanVideoSpaAttnProcessor2_0:
             out = rectified_block_sparse_attention(q, k, v, attn_mask=attention_mask, top_k=self.select_block_num,
                                                    cu_seqlens_q=cu, cu_seqlens_kv=cu, max_seqlen_q=S,
                                                    max_seqlen_kv=S, block_neighbor_list=self.block_neighbor_list,
-                                                   p_remain_rates=self.p_remain_rates, qkv_fp8=self.qkv_fp8)
+                                                   p_remain_rates=self.p_remain_rates, qkv_fp8=self.qkv_fp8,
+                                                   block_size_M=self.block_size, block_size_N=self.block_size)
         elif self.mode in ("flash", "torch", "vanilla"):
             out = fullattn(q, k, v, mode=self.mode, drop_rate=0.0, attn_mask=attention_mask, causal=False,
                            cu_seqlens_q=cu, cu_seqlens_kv=cu, max_seqlen_q=S, max_seqlen_kv=S, batch_size=B, dense_fp8=self.dense_fp8)

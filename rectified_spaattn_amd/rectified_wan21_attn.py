@@ -44,7 +44,7 @@ class _WanProcessorBase:
     _name = "WanAttnProcessor2_0"
 
     def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0,
-                 first_frame_blocks=0):
+                 first_frame_blocks=0, block_size=128):
         if not hasattr(F, "scaled_dot_product_attention"):
             raise ImportError(f"{self._name} requires PyTorch 2.0. To use it, please upgrade PyTorch to 2.0.")
         self.mode = mode
@@ -56,6 +56,9 @@ class _WanProcessorBase:
         # K5 / dense-kernel operand precision of THIS processor (None = process default, see set_qkv_fp8 / set_dense_fp8)
         self.qkv_fp8 = None
         self.dense_fp8 = None
+        # tokens per block of the sparse steps (block_size_M = block_size_N; 64 or 128, the default).  The block_neighbor_list
+        # must be built at the same block size (gilbert_block_neighbor_mapping(..., block_size=block_size))
+        self.block_size = op._check_blocks(block_size, block_size)
         self.first_frame_blocks = first_frame_blocks
 
     def _use_sparse(self) -> bool:
@@ -111,7 +114,8 @@ class _WanProcessorBase:
                                                    cu_seqlens_q=cu_q, cu_seqlens_kv=cu_kv, max_seqlen_q=S_q,
                                                    max_seqlen_kv=S_k, block_neighbor_list=self.block_neighbor_list,
                                                    p_remain_rates=self.p_remain_rates,
-                                                   first_frame_blocks=self.first_frame_blocks, qkv_fp8=self.qkv_fp8)
+                                                   first_frame_blocks=self.first_frame_blocks, qkv_fp8=self.qkv_fp8,
+                                                   block_size_M=self.block_size, block_size_N=self.block_size)
         elif self.mode in ("sparse", "flash", "torch", "vanilla"):
             dense_mode = "flash" if self.mode == "sparse" else self.mode  # warm-up layers/steps run dense
             out = fullattn(q, k, v, mode=dense_mode, drop_rate=0.0, attn_mask=attention_mask, causal=False,

@@ -47,9 +47,9 @@ def _cos_sin_rope(x, freqs_cos, freqs_sin):
 
 class _Wan22Base(_WanProcessorBase):
     def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0,
-                 first_frame_blocks=0, warm_steps=0):
+                 first_frame_blocks=0, warm_steps=0, block_size=128):
         super().__init__(mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id,
-                         first_frame_blocks)
+                         first_frame_blocks, block_size=block_size)
         self.warm_steps = warm_steps
         self._attention_backend = None
 
@@ -82,9 +82,9 @@ class RectifiedWanTI2VSpaAttnProcessor2_0(_Wan22Base):
     """Reference :15-163 (TI2V-5B): no warm_steps argument; sparse from layer 2 and step counter 10, wrap 100."""
 
     def __init__(self, mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id=0,
-                 first_frame_blocks=0):
+                 first_frame_blocks=0, block_size=128):
         super().__init__(mode, select_block_num, block_neighbor_list, p_remain_rates, processor_id,
-                         first_frame_blocks, warm_steps=0)
+                         first_frame_blocks, warm_steps=0, block_size=block_size)
 
     def _use_sparse(self):
         return self.processor_id >= 2 and self.current_step >= 10
