@@ -22,16 +22,17 @@ Two forms are generated per (D, dtype, K/V slot parity, sub-step parity):
     subtractions of a sub-step (-3.7 % time), the row maximum as two chains placed as soon as S_nxt is complete another
     0.7 % (profiles/r03_k5_block.md).  Nothing pads the statement behind its last MFMA: the only vector code that touches O
     outside the blocks (the rare rescale, the epilogue) carries the 12 wait states itself.
-  * RSA_K5_BLOCK_*: the compiled block's arithmetic operation for operation (S, then S - m by v_sub), for the A/B build:
-    bit-identical to the block as hipcc schedules it (tools/check_blk.py).
+  * RSA_K5_BLOCK_*: round 2's compiled block's arithmetic operation for operation (S, then S - m by v_sub): the product at
+    head dim 64, where it measures 4 % faster than the -m form.
 
 Measured and dropped: the sub-step's LDS-DMA pieces spread over the MFMA shadows (16.96 vs 16.42 ms: a piece stalls its wave
 ~70 cycles wherever it is issued, and inside the block that stall stops the wave's MFMA stream), 16x16x32 MFMAs (timing
 probe: +-0 sparse, +3 % dense), packed f32 adds for the row sum (+0.8 % time).
 
+The output depends on nothing but this file.
+
 usage: python3 gen_k5_block.py > rsa_attn_block.h
 """
-import os
 
 AHEAD = 4          # LDS operand buffers per operand kind (K fragments, V^T fragments)
 COST = dict(sub=4, exp=8, cvt=4, cvt8=5, add=4, max=4, mov=4, nop=8, swap=4)
@@ -70,8 +71,7 @@ def rsm_form(D, negm):
     """Head dim 64 (both forms): 8 MFMAs per sub-step against the same softmax make the wave vector-bound
     (profiles/r05_d64_experiments.txt: without the vector work -29 %), so the 16 row-sum additions go to the matrix pipe as two
     v_mfma_f32_16x16x32 (ones . P^T, 4 passes each): l = the row sum of the ROUNDED P, complete over both lane halves."""
-    import os
-    return D == 64 and os.environ.get("RSA_GEN_NORSM", "") == ""     # (env: the A/B twin with the additions, tools/history/r5_d64x_build.sh)
+    return D == 64
 
 
 def vr(a, n=1):
@@ -79,10 +79,7 @@ def vr(a, n=1):
 
 
 def gen_block(D, dt, VS, SUB, negm):
-    """The asm lines of one block variant.  (env RSA_GEN_X: timing experiments of tools/history/r5_d64x_build.sh -- noexp = no exponentials,
-    novalu = no vector work at all, nolds = no LDS operand reads; the results are garbage.)"""
-    import os
-    xf = set(filter(None, os.environ.get("RSA_GEN_X", "").split(",")))
+    """The asm lines of one block variant."""
     m = Map(D, negm)
     KS, DT = m.KS, m.DT
     mf = "v_mfma_f32_32x32x16_bf16" if dt == "bf16" else "v_mfma_f32_32x32x16_f16"
@@ -96,16 +93,10 @@ def gen_block(D, dt, VS, SUB, negm):
     lds_seq = []          # issue order of LDS ops: (tag, count)
 
     def k_read(ks):
-        if "nolds" in xf:
-            lds_seq.append((("K", ks), 0))
-            return
         lines.append(f"ds_read_b128 {vr(m.KF + 4 * (ks % AHEAD), 4)}, {vr(m.KA + ks)} offset:{koff}")
         lds_seq.append((("K", ks), 1))
 
     def v_read(p):
-        if "nolds" in xf:
-            lds_seq.append((("V", p), 0))
-            return
         k2, d = divmod(p, DT)
         off = vbase + (2 * SUB + k2) * 16 * D * 2
         b = m.VF + 4 * (p % AHEAD)
@@ -150,10 +141,6 @@ def gen_block(D, dt, VS, SUB, negm):
              ("swap", f"v_permlane32_swap_b32 {vr(m.T0)}, {vr(m.T1)}"), ("nop", "s_nop 1"),
              ("max", f"v_max_f32 %[mx], {vr(m.T0)}, {vr(m.T1)}")]
 
-    if "noexp" in xf:
-        work = [w for w in work if w[0] != "exp"]
-    if "novalu" in xf:
-        work, maxw = [], [("mov", "v_mov_b32 %[mx], 0")]
     if m.RSM:
         work = [w for w in work if w[0] != "add"]
     mf_rs = "v_mfma_f32_16x16x32_bf16" if dt == "bf16" else "v_mfma_f32_16x16x32_f16"
@@ -195,7 +182,7 @@ def gen_block(D, dt, VS, SUB, negm):
             p = i - KS
             k2, d = divmod(p, DT)
             text = "\n".join(lines)
-            for jj in range(4 if "novalu" not in xf else 0):   # sanity: the half of P this MFMA reads has been packed
+            for jj in range(4):   # sanity: the half of P this MFMA reads has been packed
                 assert f"{cv} {vr(m.P + 4 * k2 + jj)}," in text, (D, dt, VS, SUB, "P not packed before PV", p)
             if m.RSM and d == 0:      # l += ones . P^T over the 16 keys of half k2 (behind the conversions that packed it)
                 lines.append("s_nop 1")
@@ -267,8 +254,7 @@ def main():
 # =====================================================================================================================
 AHEAD8, RING8 = 3, 4
 DMA8_GAPS = [0, 2, 4, 6]      # dma form: K piece 0, K piece 1, V piece 0, V piece 1 behind these MFMAs of the nine
-if os.environ.get("RSA_GEN8_GAPS"):       # (placement A/B: profiles/r05_pv_hand_placed.txt)
-    DMA8_GAPS = [int(x) for x in os.environ["RSA_GEN8_GAPS"].split(",")]
+                              # (placement: profiles/r05_pv_hand_placed.txt)
 
 
 class Map8:
@@ -303,8 +289,6 @@ def gen_block8(TS, codemap=False, D8=128, dma=False):
     V(tile + 2) into (TS + 2) & 3 -- one per MFMA shadow instead of as a burst behind the barrier (there the eight waves' pieces queue
     at the CU's one addresser: profiles/r05_pv_hand_placed.txt).  Scalar operands: %[ksrc] / %[vsrc] = first byte of the wave's
     first piece, %[ldsw] = LDS address of the wave's first piece in slot 0 of the K ring."""
-    import os
-    xf = set(filter(None, os.environ.get("RSA_GEN8_X", "").split(",")))   # timing experiments (tools/history/r5_pvx_build.sh): halfk, nolds
     m = Map8(D8)
     SC_, SN = (m.SA, m.SB) if TS % 2 == 0 else (m.SB, m.SA)
     TILE8 = 64 * D8
@@ -315,13 +299,13 @@ def gen_block8(TS, codemap=False, D8=128, dma=False):
     for sub in range(2):
         for ks in range(m.KS):
             off = kslot * TILE8 + sub * 32 * D8
-            ops.append(("qk", sub, ks, [] if ("halfk" in xf and sub == 1) or "nolds" in xf else [(m.KA + 2 * ks, off), (m.KA + 2 * ks + 1, off)]))
+            ops.append(("qk", sub, ks, [(m.KA + 2 * ks, off), (m.KA + 2 * ks + 1, off)]))
     n_qk = len(ops)
     ones_reg = dma      # (round 5: -3 % at head dim 128, profiles/r05_pv_hand_placed.txt)
-    ops.append(("rs", 0, 0, [] if "nolds" in xf or ones_reg else [(m.ON, 0), (m.ON, 16)]))
+    ops.append(("rs", 0, 0, [] if ones_reg else [(m.ON, 0), (m.ON, 16)]))
     for dt in range(m.DT):
         off = (4 + TS) * TILE8 + dt * 2048
-        ops.append(("pv", dt, 0, [] if "nolds" in xf else [(m.VA, off), (m.VA + 1, off)]))
+        ops.append(("pv", dt, 0, [(m.VA, off), (m.VA + 1, off)]))
 
     def read(i):
         if not ops[i][3]:
@@ -395,7 +379,7 @@ def gen_block8(TS, codemap=False, D8=128, dma=False):
             emit_work(0, False, force_all=True)
         if ops[i][3]:
             wait_for(i)
-        a = vr(m.OP + 8 * ((i if ops[i][3] or "nolds" in xf else i - m.KS) % RING8), 8)
+        a = vr(m.OP + 8 * ((i if ops[i][3] else i - m.KS) % RING8), 8)
         if kind == "qk":
             c = vr(m.MB, 16) if y == 0 else vr(SN + 16 * x, 16)
             lines.append(f"v_mfma_scale_f32_32x32x64_f8f6f4 {vr(SN + 16 * x, 16)}, {a}, {vr(m.Q + 8 * y, 8)}, {c}, "
@@ -519,18 +503,12 @@ NSLOT8H = 6      # 4-register operand slots (256 registers per wave at two waves
 
 DMA8H_GAPS = {128: [1, 4, 7, 10, 13, 16],     # dma form: K pieces 0..3, V pieces 0, 1 behind these MFMAs of the 21
               64: [1, 4, 7]}                  # head dim 64: K pieces 0, 1, V piece 0 of the 11
-if os.environ.get("RSA_GEN8H_GAPS"):
-    DMA8H_GAPS[128] = [int(x) for x in os.environ["RSA_GEN8H_GAPS"].split(",")]
 
 
 def gen_block8h(T6, dt, dma=False, D8=128):
     """dma: the block also issues the wave's six LDS-DMA pieces -- K(tile + 3) into ring slot T6 % 3 (= K(tile)'s), V(tile + 2) into
     (T6 + 2) % 3 -- one per MFMA shadow (see gen_block8).  Scalar operands: %[kb16] = the head's K rows, %[vsrc] = first byte of the
-    wave's first V piece, %[ldsw] = LDS address of the wave's first piece in slot 0 of the K ring.
-    xf (env RSA_GEN8H_X, comma separated; timing experiments of tools/history/r5_pvx.sh, results are garbage): halfk = the second
-    32-key half re-uses the first half's K fragment (8 instead of 16 K reads), nov = no V reads, novalu = no conversions / row max."""
-    import os
-    xf = set(filter(None, os.environ.get("RSA_GEN8H_X", "").split(",")))
+    wave's first V piece, %[ldsw] = LDS address of the wave's first piece in slot 0 of the K ring."""
     m = Map8H(D8)
     KTILE, VTILE = 128 * D8, 64 * D8          # bytes of a K tile (64 keys x 2 D8: 16 / 8 KiB) and of a V tile (D8 x 64: 8 / 4 KiB)
     mf = "v_mfma_f32_32x32x16_bf16" if dt == "bf16" else "v_mfma_f32_32x32x16_f16"
@@ -541,15 +519,12 @@ def gen_block8h(T6, dt, dma=False, D8=128):
     for ks in range(m.KS):       # the two halves' chains alternate: no MFMA waits for the one just before it
         kreg = m.KB if ks == 0 else (m.T0 if ks % 2 == 0 else m.T1)
         for sub in range(2):
-            if ("halfk" in xf and sub == 1) or "nok" in xf:
-                ops.append(("qk", sub, ks, [], 0))
-            else:
-                ops.append(("qk", sub, ks, [(kreg, kslot * KTILE + sub * (KTILE // 2))], 1))
+            ops.append(("qk", sub, ks, [(kreg, kslot * KTILE + sub * (KTILE // 2))], 1))
     n_qk = len(ops)
     ops.append(("rs", 0, 0, [], 0))
     for d in range(m.DT):
         off = vslot * VTILE + d * 2048
-        ops.append(("pv", d, 0, [] if "nov" in xf else [(m.VA, off), (m.VA + 1, off)], 0 if "nov" in xf else 2))
+        ops.append(("pv", d, 0, [(m.VA, off), (m.VA + 1, off)], 2))
     n = len(ops)
     slot_of, consumer = {}, [None] * NSLOT8H     # consumer[s] = index of the op that reads slot s (None: free)
     state = dict(issued=-1)
@@ -569,7 +544,7 @@ def gen_block8h(T6, dt, dma=False, D8=128):
         slot_of[j] = s0
         b = m.OP + 4 * s0
         kind, sub, ks = ops[j][0], ops[j][1], ops[j][2]
-        if kind == "qk" and sub == 0 and ks > 0 and "nok" not in xf:
+        if kind == "qk" and sub == 0 and ks > 0:
             assert state["issued"] < n_qk, "T0 / T1 belong to the row maximum from P . V 0 on"
             lines.append(f"v_xor_b32 {vr(ops[j][3][0][0])}, {hex(ks << 5)}, {vr(m.KB)}")
         for c2, (areg, off) in enumerate(ops[j][3]):
@@ -596,8 +571,6 @@ def gen_block8h(T6, dt, dma=False, D8=128):
              ("nop", "s_nop 1"), ("swap", f"v_permlane32_swap_b32 {vr(m.T0)}, {vr(m.T1)}"), ("nop", "s_nop 1"),
              ("max", f"v_max_f32 %[mx], {vr(m.T0)}, {vr(m.T1)}")]
     wi, mi = 0, 0
-    if "novalu" in xf:
-        work, maxw = [], [("mov", "v_mov_b32 %[mx], 0")]
 
     def emit_work(cycles, allow_max, force_all=False):
         nonlocal wi, mi

@@ -99,9 +99,6 @@ struct AttnArgs {
     int k5_static;                            // 64-row kernel, bf16: the steady state keeps the softmax reference it is entered with (checked, redone if it overflowed)
     int blk;                                  // tokens per block: 128, or 64 (sparse calls through the _ex entry points: the 32-row kernel's pair walk)
     int txt0;                                 // blk 64: first text query row (NBv * 64); text units of 128 rows from there
-#ifdef RSA_K5_DIAG
-    unsigned long long* dbg;                  // diagnostics build only (make diag): per-wave s_memtime sums, see tools/diag_k5.py
-#endif
 };
 
 // ---------------------------------------------------------------------------------------------------------------------

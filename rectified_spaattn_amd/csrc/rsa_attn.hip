@@ -23,13 +23,6 @@ static int g_k5_rows256 = 1;    // dense calls at head dim 128: 256-row tiles (0
 static int g_k5_static = 1;     // 64-row kernel, bf16: optimistic static softmax reference in the steady-state loop (0 = online body only)
 int rsa_k5_static() { return g_k5_static; }
 static int g_k5_gsync = 1;      // aligned starts of the sparse walks (rsa_attn.h): bit 0 = in the 64-row kernel, bit 1 = in the 32-row and e4m3 kernels
-#ifdef RSA_K5_FORMS
-extern int g_rsa_k5_form;
-extern int g_rsa_k5w_form;
-#endif
-#ifdef RSA_K5_DIAG
-static unsigned long long g_dbg_ptr = 0;   // diagnostics build: device buffer for K5's in-kernel time sums
-#endif
 
 void rsa_set_fp8_variant(int v);
 void rsa_set_fp8_smooth_k(int v);
@@ -48,14 +41,6 @@ extern "C" int rsa_set_tuning(const char* key, int value) {
     if (strcmp(key, "k3_long") == 0) { g_rsa_k3_long = value; return RSA_OK; }
     if (strcmp(key, "k4_split") == 0) { g_rsa_k4_split = value; return RSA_OK; }
     if (strcmp(key, "k2_dma") == 0) { g_rsa_k2_dma = value; return RSA_OK; }
-#ifdef RSA_K5_FORMS
-    if (strcmp(key, "k5_form") == 0) { g_rsa_k5_form = value; return RSA_OK; }
-    if (strcmp(key, "k5w_form") == 0) { g_rsa_k5w_form = value; return RSA_OK; }
-#endif
-#ifdef RSA_K5_DIAG
-    if (strcmp(key, "dbg_lo") == 0) { g_dbg_ptr = (g_dbg_ptr & 0xFFFFFFFF00000000ull) | (unsigned)value; return RSA_OK; }
-    if (strcmp(key, "dbg_hi") == 0) { g_dbg_ptr = (g_dbg_ptr & 0xFFFFFFFFull) | ((unsigned long long)(unsigned)value << 32); return RSA_OK; }
-#endif
     if (strcmp(key, "k5_static") == 0) { g_k5_static = value; return RSA_OK; }
     if (strcmp(key, "k5_rows256") == 0) { g_k5_rows256 = value; return RSA_OK; }
     if (strcmp(key, "k5_tsplit") == 0) { g_k5_tsplit = value; return RSA_OK; }
@@ -391,9 +376,6 @@ static int block_sparse_fwd_b(const rsa_layout* l, int blk, rsa_tensor4 q, rsa_t
     a.q_text_end = l->NBv * blk + l->q_text_valid;
     a.q_split = 0; a.kv_split = 0; a.causal = 0; a.rows256 = 0;
     a.qk_scale = (float)((1.0 / sqrt((double)l->D)) * 1.44269504);  // sm_scale * 1.44269504 (hunyuan :145)
-#ifdef RSA_K5_DIAG
-    a.dbg = reinterpret_cast<unsigned long long*>(g_dbg_ptr);
-#endif
     return launch_attn(a, l->B * l->H, l->D, l->dtype, buf->tpart_bytes, static_cast<hipStream_t>(stream));
 }
 extern "C" int rsa_block_sparse_fwd(const rsa_layout* l, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
@@ -424,17 +406,11 @@ static int dense_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_tensor4
     a.blk = RSA_BLOCK; a.txt0 = 0;
     // head dim 128 through the 64-row kernel: 256-row tiles once there are at least two of them (a shorter call keeps 128-row tiles)
     a.rows256 = (((D == 128 && (g_k5_w64 & 1)) || (D == 64 && (g_k5_w64 & 2))) && g_k5_rows256 && Sq > 256) ? 1 : 0;
-#ifdef RSA_K5_FORMS
-    if (g_rsa_k5w_form != 0) a.rows256 = 0;     // (the A/B forms are forms of the 128-row kernel)
-#endif
     const int rw = a.rows256 ? 2 * RSA_BLOCK : RSA_BLOCK;
     a.NQB = (Sq + rw - 1) / rw; a.NBv = a.NQB; a.NB_total = (Sk + RSA_BLOCK - 1) / RSA_BLOCK;
     a.kv_valid = Sk; a.kv_text_valid = Sk; a.q_text_end = 0;
     a.q_split = q_split; a.kv_split = kv_split; a.causal = causal;
     a.qk_scale = (float)((1.0 / sqrt((double)D)) * 1.44269504);
-#ifdef RSA_K5_DIAG
-    a.dbg = nullptr;
-#endif
     return launch_attn(a, B * H, D, dtype, 0, static_cast<hipStream_t>(stream));
 }
 

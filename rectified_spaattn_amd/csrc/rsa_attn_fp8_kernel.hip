@@ -43,9 +43,7 @@ typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef RSA_PV_LIST_WINDOW
-#define RSA_PV_LIST_WINDOW 1024      // entries of the pv form's kept-list window in LDS (a power of two; tests build nothing else)
-#endif
+constexpr int RSA_PV_LIST_WINDOW = 1024;   // entries of the pv form's kept-list window in LDS (a power of two)
 
 struct Attn8Args {
     const uint8_t *q8, *k8, *v8t;  // [BH, S_pad, 128], [BH, S_pad, 128], [BH, S_pad/64, 128, 64]
@@ -583,9 +581,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-#ifndef RSA_PVX_NOBAR
         __syncthreads();
-#endif
         if constexpr (LWIN != 0) {
             // every LWIN / 2 items: entries [item + LWIN / 2, item + LWIN) replace those of [item - LWIN / 2, item), which are behind
             // every reader (the entry of tile + 5 is the furthest read ahead); they are first read LWIN / 2 items -- barriers -- later
@@ -599,15 +595,10 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
         const int t3 = (PIPE_OPT & 1) != 0 ? ts % 3 : tile % 3;
         const int ks_dma = HYB ? t3 : (ts + 3) & (NSLOT - 1), vs_dma = HYB ? (t3 + 2) % 3 : (ts + 2) & (NSLOT - 1);
         const int ks_nxt = HYB ? (t3 + 1) % 3 : (ts + 1) & (NSLOT - 1), vs_cur = HYB ? t3 : ts;
-#if defined(RSA_PVX_HOTDMA)   // (RSA_PVX_*: timing experiments of tools/history/r5_pvx.sh, never defined in the product)
-        if (tile + 3 < n_tiles) dma_k((tile & 1) * 64, ks_dma);   // every piece issued, every line L2-resident
-        if (tile + 2 < n_tiles) dma_v((tile & 1) * 64, vs_dma);
-#elif !defined(RSA_PVX_NODMA)
         if constexpr (!DMAB) {
             if (tile + 3 < n_tiles) dma_k(kq3, ks_dma);
             if (tile + 2 < n_tiles) dma_v(kq2, vs_dma);
         }
-#endif
         // ---- head (rare branches): boundary mask, deferred rescale ----
         if (key0 < lo_max || key0 + 64 > hi_min) {
             apply_mask(S_cur, key0);

@@ -76,7 +76,7 @@ __device__ __forceinline__ void k5_block_nm(f32x16 (&o)[D / 32], const s16x8 (&q
         else RSA_K5_PICK(RSA_K5_BLOCKN, 64, F16, RSA_K5_OPSN_64, RSA_K5_CLOBBERN_64);
     }
 }
-// the classic form (S, then S - m by v_sub: the compiled block's arithmetic, bit-identical to the block as hipcc emits it):
+// the classic form (S, then S - m by v_sub: the arithmetic of round 2's compiled block, bit for bit):
 // the product at head dim 64, where it measures 4 % faster than the -m form (at 128 the -m form wins by 3.7 %)
 // (head dim 64, round 5: the row sums ride the matrix pipe -- l lives in lacc, four registers with the lane's complete row sum of
 // the rounded P, onesv is the ones operand of those products; l itself is not touched.  At 128 it is the other way round.)
@@ -95,20 +95,19 @@ __device__ __forceinline__ void k5_block(f32x16 (&o)[D / 32], const s16x8 (&q)[D
     }
 }
 
-// WIDE: 16-byte output stores after a permlane32_swap regroup (needs 16-byte aligned output rows), else 8-byte stores.
-// FORM: 2 = hand-placed block, score chain started from -m (the product at head dim 128); 1 = hand-placed block with the
-// compiled block's arithmetic (the product at head dim 64); the A/B and diagnostics builds (make ab / make diag,
-// -DRSA_K5_FORMS) carry both at either head dim plus 0 = the block as hipcc schedules it (round 2's kernel).  0 and 1 are
-// bit-identical to each other, 2 differs from them by the rounding order of S - m.
+// The form of the hand-placed block: 2 = score chain started from -m (head dim 128); 1 = the classic arithmetic, S then S - m
+// (head dim 64).  The two differ by the rounding order of S - m.
 constexpr int k5_product_form(int D) { return D == 128 ? 2 : 1; }
+// WIDE: 16-byte output stores after a permlane32_swap regroup (needs 16-byte aligned output rows), else 8-byte stores.
 // BLK: tokens per block.  128: the 128-row query block of the header above, two 64-key tiles per kept block.  64 (the _ex entry
 // points): the workgroup owns the PAIR of query blocks (2 qblk, 2 qblk + 1), waves 0-1 the first, 2-3 the second, and walks the
 // union of their kept lists -- one 64-key tile per entry, staged once for both; the entries carry which of the two kept them
 // (bits 14 / 15 of the LDS list), and a wave pair masks the tiles of the other's list to -inf (exact: they add 0 to O and l, and
 // -inf leaves the running maximum alone), so every row gets the bytes its own list would give.  Dense text rows: 128-row units
 // from row NBv * 64 on (a.txt0).
-template <int D, typename Tag, bool WIDE, int FORM, int BLK = 128>
+template <int D, typename Tag, bool WIDE, int BLK = 128>
 __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
+    constexpr int FORM = k5_product_form(D);
     constexpr int NW = 4;                   // 4 waves x 32 query rows
     constexpr int KS = D / 16;
     constexpr int DT = D / 32;
@@ -358,11 +357,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     // iff (k-block & 1) == ((a >> 2) & 1) -- the B operand is the P . V product's P fragment, whose k-blocks 0 / 2 are the two lane
     // halves of query row n and 1 / 3 those of row n + 16, and the lane that owns C rows 4 (l >> 4) .. + 3 of column l & 15 is the
     // lane of exactly that query row (the construction of the e4m3 kernel's row-sum product).
-#ifdef RSA_K5X_NORSM   // (A/B twin of tools/history/r5_d64x_build.sh: row sums by vector additions, as rounds 3-4)
-    constexpr bool RSM = false;
-#else
     constexpr bool RSM = D == 64;
-#endif
     f32x4 lacc = {0.0f, 0.0f, 0.0f, 0.0f};
     s16x8 onesv;
     {
@@ -374,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     // m_ref = the finite reference the scores are taken against (S_cur, S_nxt hold S - m_ref), nm = its negation in 16
     // registers (C operand of the first QK^T MFMA), thr = how far a new row maximum may exceed it before the rescale (-inf
     // until the row has seen a finite score: the first finite maximum always becomes the reference).  m_run is the running
-    // maximum itself (-inf = nothing seen): what the split-KV partials carry, and the A/B forms' reference.
+    // maximum itself (-inf = nothing seen): what the split-KV partials carry, and form 1's reference.
     float m_ref = 0.0f, thr = -INFINITY;
     f32x16 nm;
 #pragma unroll
@@ -434,21 +429,6 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     };
 
     int kq1 = 0, kq2 = 0;  // first keys of tile+1 / tile+2 (fetched from LDS ahead of use)
-#ifdef RSA_K5_DIAG
-    // diagnostics build: s_memtime at four points of every sub-step, differences summed per wave (scalar registers)
-    unsigned long long tstamp[4] = {0, 0, 0, 0}, tsum[4] = {0, 0, 0, 0}, tkern0;
-    auto stamp_now = [&]() -> unsigned long long {
-        unsigned long long tt;
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt) :: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        return tt;
-    };
-    tkern0 = stamp_now();
-#define RSA_STAMP(i) do { tstamp[i] = stamp_now(); if ((i) > 0) tsum[i] += tstamp[i] - tstamp[(i) > 0 ? (i) - 1 : 0]; } while (0)
-#else
-#define RSA_STAMP(i) do { } while (0)
-#endif
 
     // The part of a sub-step u = 2*tile + SUB behind its staging: rare branches (boundary mask, deferred rescale), then the
     // pipelined block: consumes S_cur (scores of 32 keys, row max in mx_cur), produces S_nxt / mx_nxt for sub-step u+1.
@@ -483,9 +463,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { S_cur[i] -= delta; nm[i] = -m_ref; }
             }
-            RSA_STAMP(2);
             k5_block_nm<D, Tag, vs, sub>(o, qf, S_cur, S_nxt, nm, l_run, lacc, onesv, mx_nxt, ka, va);
-            RSA_STAMP(3);
         }
         else {   // the classic arithmetic (scores S, reference m_run subtracted in the softmax)
             if (__builtin_amdgcn_ballot_w64(mx_cur > m_run + 8.0f) != 0ull) {
@@ -505,54 +483,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
                     for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
             }
             const float m_use = (m_run == -INFINITY) ? 0.0f : m_run;
-            RSA_STAMP(2);
-            if constexpr (FORM == 1) {
-                k5_block<D, Tag, vs, sub>(o, qf, S_cur, S_nxt, m_use, l_run, lacc, onesv, mx_nxt, ka, va);
-            }
-#ifdef RSA_K5_FORMS
-            else {   // A/B build: the block left to hipcc; iglp_opt(0) = LLVM's small-GEMM MFMA/DS interleave
-                __builtin_amdgcn_s_setprio(2);
-                __builtin_amdgcn_iglp_opt(0);
-                if constexpr (sub == 0) qk_sub(std::integral_constant<int, vs>{}, std::integral_constant<int, 1>{}, S_nxt);
-                else qk_sub(std::integral_constant<int, vs ^ 1>{}, std::integral_constant<int, 0>{}, S_nxt);
-                s16x8 pb[2];
-                float ps = 0.0f;
-#pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {
-                    float pv8[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        pv8[i] = __builtin_amdgcn_exp2f(S_cur[8 * hf + i] - m_use);
-                        ps += pv8[i];
-                    }
-                    pb[hf] = E::cvt8(pv8);
-                }
-                if constexpr (RSM) {
-#pragma unroll
-                    for (int hf = 0; hf < 2; ++hf) lacc = E::mfma_rowsum(onesv, pb[hf], lacc);
-                } else {
-                    l_run += ps;
-                }
-                const unsigned char* vt_ = lds + (2 + vs) * TILE_BYTES;
-#pragma unroll
-                for (int k2 = 0; k2 < 2; ++k2) {
-#pragma unroll
-                    for (int dt = 0; dt < DT; ++dt) {
-                        const int offa = vrd[dt][0] + (2 * sub + k2) * 16 * D * 2;
-                        const int offb = vrd[dt][1] + (2 * sub + k2) * 16 * D * 2;
-                        const s16x4 va_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (s16x4 __attribute__((address_space(3)))*)(vt_ + offa));
-                        const s16x4 vb_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (s16x4 __attribute__((address_space(3)))*)(vt_ + offb));
-                        const s16x8 av = __builtin_shufflevector(va_, vb_, 0, 1, 2, 3, 4, 5, 6, 7);
-                        o[dt] = E::mfma(av, pb[k2], o[dt]);
-                    }
-                }
-                rowmax_sub(S_nxt, mx_nxt);
-                __builtin_amdgcn_s_setprio(0);
-            }
-#endif
-            RSA_STAMP(3);
+            k5_block<D, Tag, vs, sub>(o, qf, S_cur, S_nxt, m_use, l_run, lacc, onesv, mx_nxt, ka, va);
         }
     };
 
@@ -561,24 +492,18 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     // tile ago must land.
     auto stage = [&](auto VS, auto SUB, int tile) {
         constexpr int vs = decltype(VS)::value, sub = decltype(SUB)::value;
-        RSA_STAMP(0);
         if (tile + 1 < n_tiles) {
             if constexpr (NPC == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-#ifndef RSA_K5X_NOBAR     // (RSA_K5X_*: timing experiments of tools/history/r5_d64x_build.sh, never defined in the product)
         __syncthreads();
-#endif
-        RSA_STAMP(1);
-#ifndef RSA_K5X_NODMA
         if constexpr (sub == 0) {
             if (tile + 1 < n_tiles) dma(1, kq1, (2 + (vs ^ 1)) * TILE_BYTES);
         } else {
             if (tile + 2 < n_tiles) dma(0, kq2, vs * TILE_BYTES);
         }
-#endif
     };
 
     // ---------------- prologue + main loop ----------------
@@ -732,27 +657,16 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
             }
         }
     }
-#ifdef RSA_K5_DIAG
-    if (a.dbg && lane == 0) {
-        const unsigned long long tend = stamp_now();
-        unsigned long long* o8 = a.dbg + ((long)work * 4 + wv) * 8;
-        o8[0] = tsum[1]; o8[1] = tsum[2]; o8[2] = tsum[3]; o8[3] = tend - tkern0; o8[4] = (unsigned long long)n_tiles;
-        o8[5] = (unsigned long long)qblk; o8[6] = tkern0; o8[7] = tend;
-    }
-#endif
 }
 
 // launch hook used by rsa_attn.hip::launch_attn
-#ifdef RSA_K5_FORMS
-int g_rsa_k5_form = -1;   // A/B and diagnostics builds: tuning key "k5_form" (see the FORM template parameter); -1 = the product's choice
-#endif
 int rsa_launch_bsfwd(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
-    if (a.blk == 64) {   // (64-token blocks: the product form, pair-union walk; no A/B forms)
+    if (a.blk == 64) {   // (64-token blocks: pair-union walk)
         const bool wide64 = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
 #define RSA_K5B(DD, TT) \
         do { \
-            if (wide64) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, k5_product_form(DD), 64>), a, true, grid, 256, lds_bytes, s); \
-            else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false, k5_product_form(DD), 64>), a, true, grid, 256, lds_bytes, s); \
+            if (wide64) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, 64>), a, true, grid, 256, lds_bytes, s); \
+            else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false, 64>), a, true, grid, 256, lds_bytes, s); \
         } while (0)
         if (D == 128) {
             if (dtype == RSA_BF16) RSA_K5B(128, bf16_tag); else RSA_K5B(128, fp16_tag);
@@ -764,22 +678,11 @@ int rsa_launch_bsfwd(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int 
     }
     // the 16-byte output stores need 16-byte aligned rows; anything else takes the 8-byte form
     const bool wide = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
-#ifdef RSA_K5_FORMS
 #define RSA_K5(DD, TT) \
     do { \
-        if (!wide) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false, k5_product_form(DD)>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
-        else if (g_rsa_k5_form == 0) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, 0>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
-        else if (g_rsa_k5_form == 1) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, 1>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
-        else if (g_rsa_k5_form == 2) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, 2>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
-        else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, k5_product_form(DD)>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
+        if (wide) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
+        else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
     } while (0)
-#else
-#define RSA_K5(DD, TT) \
-    do { \
-        if (wide) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, k5_product_form(DD)>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
-        else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false, k5_product_form(DD)>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
-    } while (0)
-#endif
     if (D == 128) {
         if (dtype == RSA_BF16) RSA_K5(128, bf16_tag); else RSA_K5(128, fp16_tag);
     } else {

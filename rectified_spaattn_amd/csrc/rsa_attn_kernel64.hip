@@ -28,9 +28,6 @@
 #include "rsa_attn.h"
 #include <atomic>
 #include "rsa_attn_block64.h"
-#ifdef RSA_K5_FORMS
-#include "rsa_attn_block64_forms.h"
-#endif
 
 // One asm site serves both head dims: RSA_K5W_* (128) / RSA_K5V_* (64) of rsa_attn_block64.h, same arch-register map, different
 // accumulator map (O a[0:32 DT - 1], Q behind it) -- hence the clobber lists by prefix.
@@ -141,7 +138,6 @@ __device__ __forceinline__ bool k5w_map(const AttnArgs& a, int work, int& bh, in
 }
 
 // WIDE: 16-byte output stores after a permlane32_swap regroup (needs 16-byte aligned output rows), else 8-byte stores.
-// XF (A/B build only, -DRSA_K5_FORMS): one of the loop forms of rsa_attn_block64_forms.h instead of the product's loop.
 // NW (round 6): waves per workgroup.  2 = one 128-row query block (every sparse call: the mask's granularity).  4 = a 256-ROW
 // tile of a DENSE call (rsa_dense_fwd / _causal_: all rows walk the same keys): four waves, one per SIMD, ONE workgroup per CU on ONE
 // K/V ring -- every half-tile is staged once per 256 rows instead of once per 128, each wave issues 4 LDS-DMA pieces per sub-step
@@ -149,7 +145,7 @@ __device__ __forceinline__ bool k5w_map(const AttnArgs& a, int work, int& bh, in
 // every second piece dropped (gen_k5_block64.py, RSA_K5W_LOOP_*_R256); `qblk` then counts 256-row tiles (the host sets NQB so).
 // D (round 6): head dim 128 or 64 (CogVideoX).  At 64 a sub-step is 8 + 8 MFMAs against the same softmax, a half-tile 4 KiB = four
 // LDS-DMA pieces of 8 rows (two per wave); same register map in the arch file, O in a[0:63], Q in a[64:95].
-template <typename Tag, bool WIDE, int XF = 0, int NW = 2, int D = 128>
+template <typename Tag, bool WIDE, int NW = 2, int D = 128>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) void bsfwd64_kernel(AttnArgs a) {
     constexpr int RW = 64 * NW;             // query rows per workgroup: NW waves x 64 rows
     constexpr int NPIECE = 32 * D * 2 / 1024;   // 1-KiB pieces of a 32-key half-tile: 8 (4 rows each) / 4 (8 rows each)
@@ -157,7 +153,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     constexpr int RPP = 32 / NPIECE;        // key rows per piece
     constexpr int LPR = 64 / RPP;           // lanes (16-byte chunks) per key row
     static_assert(NW == 2 || NW == 4, "two or four waves");
-    static_assert(D == 128 || (D == 64 && XF == 0), "head dim 64: the product forms only");
     constexpr int KS = D / 16;
     constexpr int DT = D / 32;
     constexpr int HALF = 32 * D * 2;        // bytes of a 32-key half-tile
@@ -339,27 +334,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     // if any wave of the workgroup failed the check, the whole workgroup walks again through the online body and stores again.
     // Same softmax either way (the reference cancels in O / l); which body ran depends only on the rows' own data, never on the
     // launch.  Tuning key k5_static = 0: online body only.
-    constexpr bool MAY_STATIC = std::is_same<Tag, bf16_tag>::value && XF == 0;
-    static_assert(NW == 2 || XF == 0, "the A/B forms are forms of the 128-row kernel");
+    constexpr bool MAY_STATIC = std::is_same<Tag, bf16_tag>::value;
     const bool may_static = MAY_STATIC && a.k5_static != 0;
     // state the epilogue reads (set at the head of a pass)
     float l_run[2], m_ref[2], thr[2];
     int i0 = 0, i1 = 0;
-#ifdef RSA_K5_DIAG
-    // diagnostics build: s_memtime around the phases of the walk, summed per wave (scalar registers)
-    unsigned long long tprev = 0, tsum[4] = {0, 0, 0, 0}, tkern0, tprologue = 0;
-    auto stamp_now = [&]() -> unsigned long long {
-        unsigned long long tt;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt) :: "memory");
-        return tt;
-    };
-    tkern0 = stamp_now();
-#define RSA_STAMP0() do { tprev = stamp_now(); } while (0)
-#define RSA_STAMP(i) do { const unsigned long long tn_ = stamp_now(); tsum[i] += tn_ - tprev; tprev = tn_; } while (0)
-#else
-#define RSA_STAMP0() do { } while (0)
-#define RSA_STAMP(i) do { } while (0)
-#endif
 #pragma nounroll
     for (int pass = 0; pass < 2; ++pass) {
     if constexpr (D == 128) asm volatile(RSA_K5W_OZERO ::: RSA_K5W_CLOBBER_O); else asm volatile(RSA_K5V_OZERO ::: RSA_K5V_CLOBBER_O);
@@ -472,10 +451,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
         if constexpr (std::is_same<Tag, bf16_tag>::value) RSA_K5_ASM(D, QK0_BF16, OPS_QK0, CLOBBER_TMP, , "memory");
         else RSA_K5_ASM(D, QK0_F16, OPS_QK0, CLOBBER_TMP, , "memory");
     }
-    RSA_STAMP0();
-#ifdef RSA_K5_DIAG
-    tprologue = tprev - tkern0;
-#endif
     // Which kept blocks the asm loop takes: [i0, i1) such that no score of block i needs the boundary mask and block i + 1
     // (whose half-tiles the loop stages while it works on i) exists and lies inside the valid keys: i0 = the leading blocks
     // below lo_max (second segment of a two-segment dense call), i1 from the end of the ascending list.
@@ -485,7 +460,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     while (nfull > i0 && blk_of(nfull - 1) * RSA_BLOCK + RSA_BLOCK > hi_min) --nfull;
     i1 = nfull - 1 > i0 ? nfull - 1 : i0;
     run_items(0, i0);
-    RSA_STAMP(0);
     {
         rescale_check(I0{}, mxA, SA, SB, nm);
         const unsigned cnt = (unsigned)(i1 - i0);
@@ -501,29 +475,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
             __builtin_amdgcn_ballot_w64(thr[0] == -INFINITY || thr[1] == -INFINITY) == 0ull) stat = 1;
         stat = __builtin_amdgcn_readfirstlane(stat);
         used_static = stat != 0;
-#ifdef RSA_K5_DIAG
-        unsigned d0 = 0, d1 = 0;   // in-loop stamps: cycles parked on the vmcnt wait / on the barrier (+ rescales taken << 24)
-        if constexpr (std::is_same<Tag, bf16_tag>::value) RSA_K5_ASM(D, LOOP_BF16_DIAG, OPS_LOOP_DIAG, CL_LOOP, , RSA_K5W_CLOBBER_LOOP_DIAG, "memory");
-        else RSA_K5_ASM(D, LOOP_F16_DIAG, OPS_LOOP_DIAG, CL_LOOP, , RSA_K5W_CLOBBER_LOOP_DIAG, "memory");
-        tsum[3] = ((unsigned long long)d1 << 32) | d0;
-#else
-#ifdef RSA_K5_FORMS
-#define RSA_K5W_XFORM(N) else if constexpr (XF == N) \
-            asm volatile(RSA_K5W_LOOP_BF16_X##N RSA_K5W_OPS_LOOP : RSA_K5W_CLOBBER_TMP, RSA_K5W_CLOBBER_O, RSA_K5W_CLOBBER_LOOP, "memory");
-        if constexpr (false) {}
-        RSA_K5W_XFORM(1) RSA_K5W_XFORM(2) RSA_K5W_XFORM(3) RSA_K5W_XFORM(4) RSA_K5W_XFORM(5) RSA_K5W_XFORM(6) RSA_K5W_XFORM(7) RSA_K5W_XFORM(8) RSA_K5W_XFORM(9) RSA_K5W_XFORM(10) RSA_K5W_XFORM(11) RSA_K5W_XFORM(12) RSA_K5W_XFORM(13) RSA_K5W_XFORM(14) RSA_K5W_XFORM(15) RSA_K5W_XFORM(16) RSA_K5W_XFORM(17) RSA_K5W_XFORM(18) RSA_K5W_XFORM(19) RSA_K5W_XFORM(20) RSA_K5W_XFORM(21) RSA_K5W_XFORM(22) RSA_K5W_XFORM(23) RSA_K5W_XFORM(24) RSA_K5W_XFORM(25) RSA_K5W_XFORM(26) RSA_K5W_XFORM(27) RSA_K5W_XFORM(28) RSA_K5W_XFORM(29) RSA_K5W_XFORM(30) RSA_K5W_XFORM(31)
-        else
-#endif
         if constexpr (NW == 4 && std::is_same<Tag, bf16_tag>::value) RSA_K5_ASM(D, LOOP_BF16_R256, OPS_LOOP, CL_LOOP, , "memory");
         else if constexpr (NW == 4) RSA_K5_ASM(D, LOOP_F16_R256, OPS_LOOP, CL_LOOP, , "memory");
         else if constexpr (std::is_same<Tag, bf16_tag>::value) RSA_K5_ASM(D, LOOP_BF16, OPS_LOOP, CL_LOOP, , "memory");
         else RSA_K5_ASM(D, LOOP_F16, OPS_LOOP, CL_LOOP, , "memory");
-#endif
         (void)lv;
     }
-    RSA_STAMP(1);
     run_items(i1, n_items);
-    RSA_STAMP(2);
     if (!may_static) break;                      // (uniform over the launch)
     {
         // the overflow trace of a static walk: l of either half at 2^100 or beyond (or infinite, or NaN), or an O element that is
@@ -673,66 +631,30 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     };
     finish_half(std::integral_constant<int, 0>{});
     finish_half(std::integral_constant<int, 1>{});
-#ifdef RSA_K5_DIAG
-    if (e.dbg && lane == 0) {   // [leading C++ blocks, asm loop, trailing C++ blocks, -, kept blocks, kernel cycles, blocks in the loop]
-        const unsigned long long tend = stamp_now();
-        unsigned long long* o8 = e.dbg + ((long)blockIdx.x * 4 + wv) * 8;
-        o8[0] = tsum[0]; o8[1] = tsum[1]; o8[2] = tsum[2]; o8[3] = tsum[3]; o8[4] = (unsigned long long)n_items;
-        o8[5] = tend - tkern0; o8[6] = (unsigned long long)(i1 - i0); o8[7] = (tprologue << 32) | ((tend - tprev) & 0xFFFFFFFFull);
-    }
-#endif
 }
 
-#ifdef RSA_K5_FORMS
-int g_rsa_k5w_form = 0;   // A/B build: tuning key "k5w_form" (loop forms of rsa_attn_block64_forms.h)
-#endif
-// launch hook used by rsa_attn.hip::launch_attn (head dims 128 and 64)
-int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
-    const bool wide = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
-    lds_bytes += 16;   // the loop reads its list two entries ahead
-    if (D == 64 && a.rows256) {
-        if (a.mode != MODE_DENSE) return RSA_ERR_BAD_ARG;
-        if (dtype == RSA_BF16) {
-            if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, 0, 4, 64>), a, false, grid, 256, lds_bytes, s);
-            else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false, 0, 4, 64>), a, false, grid, 256, lds_bytes, s);
-        } else {
-            if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true, 0, 4, 64>), a, false, grid, 256, lds_bytes, s);
-            else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false, 0, 4, 64>), a, false, grid, 256, lds_bytes, s);
-        }
-        return rsa_launch_status();
-    }
-    if (D == 64) {
-        if (dtype == RSA_BF16) {
-            if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, 0, 2, 64>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s);
-            else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false, 0, 2, 64>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s);
-        } else {
-            if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true, 0, 2, 64>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s);
-            else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false, 0, 2, 64>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s);
-        }
-        return rsa_launch_status();
-    }
-    if (D != 128) return RSA_ERR_UNSUPPORTED;
-#ifdef RSA_K5_FORMS
-#define RSA_K5W_XLAUNCH(N) if (g_rsa_k5w_form == N && dtype == RSA_BF16 && wide) { RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, N>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s); return rsa_launch_status(); }
-    RSA_K5W_XLAUNCH(1) RSA_K5W_XLAUNCH(2) RSA_K5W_XLAUNCH(3) RSA_K5W_XLAUNCH(4) RSA_K5W_XLAUNCH(5) RSA_K5W_XLAUNCH(6) RSA_K5W_XLAUNCH(7) RSA_K5W_XLAUNCH(8) RSA_K5W_XLAUNCH(9) RSA_K5W_XLAUNCH(10) RSA_K5W_XLAUNCH(11) RSA_K5W_XLAUNCH(12) RSA_K5W_XLAUNCH(13) RSA_K5W_XLAUNCH(14) RSA_K5W_XLAUNCH(15) RSA_K5W_XLAUNCH(16) RSA_K5W_XLAUNCH(17) RSA_K5W_XLAUNCH(18) RSA_K5W_XLAUNCH(19) RSA_K5W_XLAUNCH(20) RSA_K5W_XLAUNCH(21) RSA_K5W_XLAUNCH(22) RSA_K5W_XLAUNCH(23) RSA_K5W_XLAUNCH(24) RSA_K5W_XLAUNCH(25) RSA_K5W_XLAUNCH(26) RSA_K5W_XLAUNCH(27) RSA_K5W_XLAUNCH(28) RSA_K5W_XLAUNCH(29) RSA_K5W_XLAUNCH(30) RSA_K5W_XLAUNCH(31)
-#endif
-    if (a.rows256) {     // dense calls: 256-row tiles, four waves on one K/V ring (the host counted the grid in such tiles)
-        if (a.mode != MODE_DENSE) return RSA_ERR_BAD_ARG;
-        if (dtype == RSA_BF16) {
-            if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, 0, 4>), a, false, grid, 256, lds_bytes, s);
-            else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false, 0, 4>), a, false, grid, 256, lds_bytes, s);
-        } else {
-            if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true, 0, 4>), a, false, grid, 256, lds_bytes, s);
-            else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false, 0, 4>), a, false, grid, 256, lds_bytes, s);
-        }
-        return rsa_launch_status();
-    }
+// the four instantiations (dtype x store width) of the NW-wave kernel at head dim D
+template <int NW, int D>
+static int launch_bsfwd64(const AttnArgs& a, bool wide, int dtype, dim3 grid, size_t lds_bytes, hipStream_t s) {
+    const bool sparse = a.mode == MODE_SPARSE;
     if (dtype == RSA_BF16) {
-        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s);
-        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s);
+        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, NW, D>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false, NW, D>), a, sparse, grid, 64 * NW, lds_bytes, s);
     } else {
-        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s);
-        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false>), a, a.mode == MODE_SPARSE, grid, 128, lds_bytes, s);
+        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true, NW, D>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false, NW, D>), a, sparse, grid, 64 * NW, lds_bytes, s);
     }
     return rsa_launch_status();
+}
+
+// launch hook used by rsa_attn.hip::launch_attn (head dims 128 and 64)
+int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
+    if (D != 128 && D != 64) return RSA_ERR_UNSUPPORTED;
+    const bool wide = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
+    lds_bytes += 16;   // the loop reads its list two entries ahead
+    if (a.rows256) {     // dense calls: 256-row tiles, four waves on one K/V ring (the host counted the grid in such tiles)
+        if (a.mode != MODE_DENSE) return RSA_ERR_BAD_ARG;
+        return D == 128 ? launch_bsfwd64<4, 128>(a, wide, dtype, grid, lds_bytes, s) : launch_bsfwd64<4, 64>(a, wide, dtype, grid, lds_bytes, s);
+    }
+    return D == 128 ? launch_bsfwd64<2, 128>(a, wide, dtype, grid, lds_bytes, s) : launch_bsfwd64<2, 64>(a, wide, dtype, grid, lds_bytes, s);
 }

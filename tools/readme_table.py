@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Prints README.md's results table from profiles/r06_bench*.json (the final set of the round: tools/final_run_r5.sh), so that the
+"""Prints README.md's results table from profiles/r06_bench*.json (the final set of the round), so that the
 table and the committed bench lines cannot drift apart.  usage: python tools/readme_table.py"""
 import json
 import os
