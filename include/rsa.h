@@ -226,6 +226,31 @@ int rsa_rectified_attention_ex(const rsa_layout_ex* lay, rsa_tensor4 q, rsa_tens
                                const uint8_t* neighbor, int top_k, float p_remain, void* workspace,
                                size_t workspace_bytes, rsa_out4 out, void* stream);
 
+/* ---- caller-supplied block masks: the reference's _triton_block_sparse_attention_onehot (rectified_hunyuan_attn.py:108-168,
+ * same in the flux / cogvideo / wan21 files) over a mask of the caller's own.  Additive: no struct above changes. ----
+ *
+ * Dense [B, H, NQ, NK] block mask -> the kept lists of rsa_buffers, in K3's format with NBv = NQ and NB_total = NK:
+ * bitmask [BH, NQ, ceil(NK/32)], cols [BH, NQ, NK] (ascending; only the first counts[] entries are written), counts [BH, NQ].
+ * mask: DEVICE uint8, nonzero = kept (a torch bool tensor has these bytes); ELEMENT strides per axis, 0 for a broadcast axis,
+ * the key axis contiguous.  NK <= 8192 (K5's key-block limit).  One wave per row. */
+int rsa_block_mask_to_lists(int B, int H, int NQ, int NK, const uint8_t* mask, int64_t mask_stride_b, int64_t mask_stride_h,
+                            int64_t mask_stride_q, uint32_t* bitmask, int32_t* cols, int32_t* counts, void* stream);
+/* The inverse: bitmask [BH, NQ, ceil(NK/32)] -> contiguous [B, H, NQ, NK] uint8 mask of 0 / 1. */
+int rsa_lists_to_block_mask(int B, int H, int NQ, int NK, const uint32_t* bitmask, uint8_t* mask, void* stream);
+
+/* Plain block-sparse attention (K5 without the rectification epilogue) over such lists:
+ *   O[b, h, i] = softmax over the keys j < kv_valid of the kept blocks of row block i / block of (sm_scale q_i . k_j) applied to V
+ * q [B, H, Sq, D], k / v [B, H, Sk, D] (Sq and Sk may differ; the last query and key blocks may be ragged); cols / counts as
+ * rsa_block_mask_to_lists writes them, with NQ = ceil(Sq / block) rows per head and NK <= ceil(Sk / block) blocks per row (keys
+ * past NK * block are never visited).  1 <= kv_valid <= Sk; sm_scale finite, of either sign.  block: 64 or 128; D: 64 or 128; dtype: RSA_BF16 / RSA_FP16.  Exactly
+ * the rows < Sq of `out` (a [B, Sq, H, D]-strided view as in rsa_block_sparse_fwd) are written; a row without a visible key is 0.
+ * tpart / tpart_bytes: optional partial buffer (NULL / 0: nothing is split); with >= RSA_TAIL_PIECES * 128 * (D + 2) floats, the
+ * walks of a last, partial generation of workgroups are split over its idle slots (head dim 128, 128-token blocks), as in
+ * rsa_block_sparse_fwd. */
+int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, int kv_valid,
+                               double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* cols,
+                               const int32_t* counts, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream);
+
 /* Stand-alone GAPR for callers of estimate_pr_gain (gapr_mask.py:4): blocks are [BH, N, 128, D] contiguous
  * 2-byte elements, pools [BH, N, D] fp32, scores [BH, NQ, NK] fp32 -> mask [BH, NQ, NK] uint8 (1 = ~gapr_mask). */
 int rsa_estimate_pr_gain(int BH, int NQ, int NK, int D, int dtype, const void* q_blocks, const void* k_blocks,

@@ -9,6 +9,9 @@ Module names mirror the reference package `rectified_spaattn`:
     rectified_wan22_attn      RectifiedWan{TI2V,T2V,I2V}SpaAttnProcessor2_0
     rectified_cogvideo_attn   rectified_block_sparse_attention, RectifiedCogVideoXVideoSpaAttnProcessor2_0
     attn_processor            get_attn_processors, set_attn_processor
+    block_sparse              block_sparse_attention over a caller's block mask (also exported here), the mask <-> list
+                              conversions; the four rectified_*_attn modules above also carry the reference's
+                              _build_block_index_with_importance_optimized and _triton_block_sparse_attention_onehot
     teacache                  TeaCache step-skipping controller (scripts' teacache_forward bookkeeping), rel_l1_distance
 Device work goes through librsa_hip.so (C-ABI in include/rsa.h): the attention operators and fullattn never fall back to
 PyTorch kernels for device tensors (they raise).  Two deliberate uses of plain PyTorch expressions remain and are the
@@ -34,6 +37,13 @@ def set_dense_fp8(enabled) -> bool:
     Default off."""
     from . import _operator
     return _operator.set_dense_fp8(enabled)
+
+
+def block_sparse_attention(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128):
+    """Block-sparse attention over a block mask of the caller's own: q [B,H,Sq,D], k / v [B,H,Sk,D], block_mask bool / uint8
+    [B|1, H|1, ceil(Sq/block), NK] -> [B,H,Sq,D].  See rectified_spaattn_amd.block_sparse.block_sparse_attention."""
+    from . import block_sparse
+    return block_sparse.block_sparse_attention(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size)
 
 
 def clear_buffer_cache() -> None:

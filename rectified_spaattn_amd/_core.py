@@ -227,8 +227,10 @@ def cached_buffers(spec: LayoutSpec, B: int, H: int, D: int, device) -> Dict[str
 
 
 def clear_buffer_cache() -> None:
-    """Drops every cached buffer set (they return to PyTorch's allocator)."""
+    """Drops every cached buffer set (they return to PyTorch's allocator), block_sparse's tail buffers included."""
     _BUF_CACHE.clear()
+    from . import block_sparse
+    block_sparse._TAIL_CACHE.clear()
 
 
 def _c_buffers(bufs: Dict[str, torch.Tensor]) -> RsaBuffers:

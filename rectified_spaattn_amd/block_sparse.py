@@ -1,0 +1,265 @@
+"""Block-sparse attention over caller-supplied block masks, and the reference's two building blocks on top of it.
+
+The reference composes its operator from `_build_block_index_with_importance_optimized` (the selection: one-hot block mask,
+implicit full-attention probabilities, GAPR mask) and `_triton_block_sparse_attention_onehot` (plain block-sparse attention over
+any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the flux / cogvideo / wan21 files.  Here:
+
+    block_sparse_attention   K5 without the rectifying epilogue (rsa_block_sparse_plain_fwd) over the lists
+                             rsa_block_mask_to_lists makes from the caller's mask
+    build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
+                             rsa_lists_to_block_mask for the reference's dense one-hot form
+
+Difference from the reference kept on purpose: a query row that sees no key (no kept block, or every kept key at or beyond
+kv_len) is 0 here; the reference's Triton kernel divides 0 by 0 there and returns NaN."""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional
+
+import torch
+
+from . import _core, _lib
+from ._lib import RsaOut4
+
+
+def _check_block_pair(block_size_M: int, block_size_N: int) -> int:
+    if block_size_M != block_size_N or block_size_M not in _lib.BLOCKS:
+        raise NotImplementedError(f"block-sparse attention on the HIP path: block_size_M = block_size_N in {_lib.BLOCKS}, "
+                                  f"got {block_size_M} / {block_size_N}")
+    return int(block_size_M)
+
+
+MAX_KEY_BLOCKS = 8192   # K5's key-block limit (its kept list lives in LDS as u16)
+
+
+def _mask_u8(block_mask: torch.Tensor) -> torch.Tensor:
+    """bool / uint8 mask with a contiguous key axis, as uint8 bytes (a bool tensor is reinterpreted, not copied)."""
+    m = block_mask
+    if m.stride(-1) != 1 and m.shape[-1] > 1:
+        m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def block_mask_to_lists(block_mask: torch.Tensor, B: int, H: int) -> Dict[str, torch.Tensor]:
+    """[B|1, H|1, NQ, NK] bool / uint8 device mask (nonzero = kept) -> K5's kept lists, the rsa_buffers format:
+    bitmask int32 [B*H, NQ, ceil(NK/32)], cols int32 [B*H, NQ, NK] (ascending, first counts entries written), counts [B*H, NQ]."""
+    if block_mask.dtype not in (torch.bool, torch.uint8) or block_mask.dim() != 4:
+        raise ValueError(f"block_mask: a 4-d bool or uint8 tensor, got {block_mask.dtype} {tuple(block_mask.shape)}")
+    if block_mask.shape[0] not in (1, B) or block_mask.shape[1] not in (1, H):
+        raise ValueError(f"block_mask {tuple(block_mask.shape)} does not broadcast over B = {B}, H = {H}")
+    if not 1 <= block_mask.shape[3] <= MAX_KEY_BLOCKS or block_mask.shape[2] < 1:
+        raise ValueError(f"block_mask {tuple(block_mask.shape)}: 1..{MAX_KEY_BLOCKS} key blocks and at least one query block")
+    _core._require_device(block_mask)
+    m = _mask_u8(block_mask)
+    NQ, NK = m.shape[2], m.shape[3]
+    strides = [0 if m.shape[i] == 1 else m.stride(i) for i in range(3)]
+    dev = m.device
+    out = dict(bitmask=torch.empty((B * H, NQ, (NK + 31) // 32), dtype=torch.int32, device=dev),
+               cols=torch.empty((B * H, NQ, NK), dtype=torch.int32, device=dev),
+               counts=torch.empty((B * H, NQ), dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rsa_block_mask_to_lists(B, H, NQ, NK, m.data_ptr(), *strides, out["bitmask"].data_ptr(),
+                                                      out["cols"].data_ptr(), out["counts"].data_ptr(), _core._stream()),
+                   "rsa_block_mask_to_lists")
+    return out
+
+
+def lists_to_block_mask(bitmask: torch.Tensor, B: int, H: int, NQ: int, NK: int) -> torch.Tensor:
+    """bitmask words [B*H, NQ, ceil(NK/32)] -> uint8 [B, H, NQ, NK] of 0 / 1 (view it as bool for the reference's one-hot form)."""
+    _core._require_device(bitmask)
+    if bitmask.numel() != B * H * NQ * ((NK + 31) // 32) or not bitmask.is_contiguous():
+        raise ValueError(f"bitmask {tuple(bitmask.shape)} is not a contiguous [{B * H}, {NQ}, {(NK + 31) // 32}] word array")
+    out = torch.empty((B, H, NQ, NK), dtype=torch.uint8, device=bitmask.device)
+    with torch.cuda.device(bitmask.device):
+        _lib.check(_lib.lib().rsa_lists_to_block_mask(B, H, NQ, NK, bitmask.data_ptr(), out.data_ptr(), _core._stream()),
+                   "rsa_lists_to_block_mask")
+    return out
+
+
+_TAIL_CACHE: "Dict[tuple, torch.Tensor]" = {}
+
+
+def _tail_buffer(device) -> torch.Tensor:
+    """The tail split's partial buffer ([RSA_TAIL_PIECES, 128, 130] fp32, 34 MB), one per (device, stream) and reused in stream
+    order as _core.cached_buffers reuses the rectified call's (and like those, never during a HIP-graph capture)."""
+    dev = torch.device(device)
+    shape = (_lib.TAIL_PIECES, _lib.BLOCK, 128 + 2)
+    if not _core.BUFFER_CACHE or torch.cuda.is_current_stream_capturing():
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    buf = _TAIL_CACHE.get(key)
+    if buf is None:
+        buf = _TAIL_CACHE[key] = torch.empty(shape, dtype=torch.float32, device=dev)
+    return buf
+
+
+def _kv_lens(kv_len, B: int, Sk: int):
+    """None | int | per-batch sequence | tensor (one host read) -> list of B ints in [0, Sk]."""
+    if kv_len is None:
+        lens = [Sk] * B
+    elif isinstance(kv_len, int):
+        lens = [int(kv_len)] * B
+    else:
+        vals = kv_len.reshape(-1).tolist() if isinstance(kv_len, torch.Tensor) else list(kv_len)
+        if len(vals) == 1:
+            vals = vals * B
+        if len(vals) != B:
+            raise ValueError(f"kv_len: {len(vals)} values for a batch of {B}")
+        lens = [int(x) for x in vals]
+    if any(n < 0 or n > Sk for n in lens):
+        raise ValueError(f"kv_len {lens} outside [0, {Sk}]")
+    return lens
+
+
+def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask: torch.Tensor, *, kv_len=None,
+                           sm_scale: Optional[float] = None, block_size: int = 128) -> torch.Tensor:
+    """softmax(sm_scale q k^T) v restricted, per query block i, to the key blocks j with block_mask[b, h, i, j] set and to the
+    keys < kv_len.  q [B,H,Sq,D], k / v [B,H,Sk,D] (any strides with a contiguous head dim: [B,S,H,D] views need no copy);
+    block_mask bool / uint8 [B|1, H|1, ceil(Sq/block), NK] with NK <= ceil(Sk/block) (keys past NK * block are never visited);
+    kv_len None (= Sk), an int, or one value per batch item (a tensor costs one host read; distinct values run one launch per
+    batch item); sm_scale defaults to D ** -0.5.  Returns [B,H,Sq,D] in the input dtype.  A row without a visible key is 0
+    (the reference's kernel gives NaN there).  Asynchronous on the current stream.  Head dims 64 / 128 run natively, 16 / 32
+    zero-padded (exact); bf16 and fp16."""
+    blk = _check_block_pair(block_size, block_size)
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k, v: [B, H, S, D] tensors")
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if k.shape != v.shape or k.shape[0] != B or k.shape[1] != H or k.shape[3] != D:
+        raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"q, k, v: one dtype, bfloat16 or float16 (got {q.dtype}, {k.dtype}, {v.dtype})")
+    if D not in (16, 32, 64, 128):
+        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
+    if Sq <= 0 or Sk <= 0:
+        raise ValueError(f"empty operands (Sq = {Sq}, Sk = {Sk})")
+    NQ, NKmax = -(-Sq // blk), -(-Sk // blk)
+    if block_mask.dim() != 4 or block_mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"block_mask: a 4-d bool or uint8 tensor, got {block_mask.dtype} {tuple(block_mask.shape)}")
+    if (block_mask.shape[0] not in (1, B) or block_mask.shape[1] not in (1, H) or block_mask.shape[2] != NQ
+            or not 1 <= block_mask.shape[3] <= min(NKmax, MAX_KEY_BLOCKS)):
+        raise ValueError(f"block_mask {tuple(block_mask.shape)}: expected [{B}|1, {H}|1, {NQ}, 1..{min(NKmax, MAX_KEY_BLOCKS)}] "
+                         f"for block {blk} (at most {MAX_KEY_BLOCKS} key blocks)")
+    lens = _kv_lens(kv_len, B, Sk)
+    _core._require_device(q, k, v)
+    scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
+    if block_mask.device != q.device:
+        block_mask = block_mask.to(q.device)
+    if D in _core._PAD_HEAD_DIM:   # zero columns add exact zeros to every dot product; the caller's scale is kept
+        pad = (0, _core._PAD_HEAD_DIM[D] - D)
+        F = torch.nn.functional
+        return block_sparse_attention(F.pad(q, pad), F.pad(k, pad), F.pad(v, pad), block_mask, kv_len=lens, sm_scale=scale,
+                                      block_size=blk)[..., :D].contiguous()
+    L = _lib.lib()
+    q, k, v = _core._as_bhsd(q), _core._as_bhsd(k), _core._as_bhsd(v)
+    NK = block_mask.shape[3]
+    lists = block_mask_to_lists(block_mask, B, H)
+    out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=q.device)
+    # the tail split's partial buffer (head dim 128, 128-token blocks: the rectified call's K5 gets the same)
+    tpart = _tail_buffer(q.device) if D == 128 and blk == _lib.BLOCK else None
+    tp, tpb = (tpart.data_ptr(), tpart.numel() * 4) if tpart is not None else (None, 0)
+    dt = _core.dtype_code(q.dtype)
+    # one launch for the whole batch when the key limits agree, else one per batch item
+    groups = [(0, B, lens[0])] if len(set(lens)) == 1 else [(b, b + 1, lens[b]) for b in range(B)]
+    with torch.cuda.device(q.device):
+        for b0, b1, n in groups:
+            if n == 0:   # no visible key at all
+                out[b0:b1].zero_()
+                continue
+            row = H * NQ * b0
+            o4 = RsaOut4(out[b0].data_ptr(), out.stride(0), out.stride(1), out.stride(2))
+            _lib.check(L.rsa_block_sparse_plain_fwd(b1 - b0, H, Sq, Sk, D, dt, blk, NQ, NK, n, scale, _core._t4(q[b0:b1]),
+                                                    _core._t4(k[b0:b1]), _core._t4(v[b0:b1]),
+                                                    lists["cols"].data_ptr() + row * NK * 4, lists["counts"].data_ptr() + row * 4,
+                                                    tp, tpb, o4, _core._stream()), "rsa_block_sparse_plain_fwd")
+    return out
+
+
+def build_block_index(query: torch.Tensor, key: torch.Tensor, top_k: int, block_size_M: int = 128, block_size_N: int = 128,
+                      text_start_block=None, text_end_block=None, num_blocks=None, prob_threshold: float = 0.7,
+                      block_neighbor_list=None, attenable=None, first_frame_blocks=None, text: bool = True):
+    """The reference's _build_block_index_with_importance_optimized on the rectified call's selection pass (K1..K3).
+    query [B,H,NQ*block,D] (the visual rows), key [B,H,S,D] -> (one_hot bool [B,H,NQ,num_blocks], probs fp32 [B,H,NQ,L],
+    nogapr bool [B,H,NQ,NQ]).  text=True: the hunyuan / flux / cogvideo form (`attenable` text tokens after the visual blocks are
+    scored one by one, text blocks [NQ, text_end_block) kept by every row, L = NQ + 1); text=False: the wan21 form (L = NQ,
+    `first_frame_blocks` square kept).  K1 pools V as well: K stands in for it and its pool is dropped.  The inputs are not
+    modified (the reference's callers zero masked K rows themselves beforehand)."""
+    blk = _check_block_pair(block_size_M, block_size_N)
+    if query.dim() != 4 or key.dim() != 4:
+        raise ValueError("query, key: [B, H, S, D] tensors")
+    B, H, Sq, D = query.shape
+    S = key.shape[2]
+    if key.shape[0] != B or key.shape[1] != H or key.shape[3] != D:
+        raise ValueError(f"key {tuple(key.shape)} does not match query {tuple(query.shape)}")
+    if query.dtype not in (torch.bfloat16, torch.float16) or key.dtype != query.dtype:
+        raise ValueError(f"query, key: one dtype, bfloat16 or float16 (got {query.dtype}, {key.dtype})")
+    if D not in (16, 32, 64, 128):
+        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
+    NQ = -(-Sq // blk)
+    NB = -(-S // blk)
+    as_int = lambda x: int(x.reshape(-1)[0].item()) if isinstance(x, torch.Tensor) else int(x)   # noqa: E731
+    if num_blocks is not None and as_int(num_blocks) != NB:
+        raise ValueError(f"num_blocks = {as_int(num_blocks)}, but key has {S} rows = {NB} blocks of {blk}")
+    if text_start_block is not None and as_int(text_start_block) != NQ:
+        raise ValueError(f"text_start_block = {as_int(text_start_block)}: the selection pass starts the text at the end of the "
+                         f"{NQ} query blocks")
+    if Sq % blk and Sq != S:
+        raise ValueError(f"query: {Sq} rows are not whole blocks of {blk} and not the whole key sequence ({S})")
+    if NQ > NB:
+        raise ValueError(f"query has {NQ} blocks, key only {NB}")
+    if text:
+        n_txt = 0 if attenable is None else as_int(attenable)
+        teb = NB if text_end_block is None else min(max(as_int(text_end_block), NQ), NB)
+        ffb = 0
+        if n_txt < 0 or NQ * blk + n_txt > S:
+            raise ValueError(f"attenable = {n_txt} text tokens do not fit behind {NQ} blocks of {blk} in {S} key rows")
+    else:
+        if NQ != NB:
+            raise ValueError(f"wan21 selection: query blocks ({NQ}) and key blocks ({NB}) must agree")
+        n_txt, teb, ffb = 0, NB, 0 if first_frame_blocks is None else as_int(first_frame_blocks)
+    _core._require_device(query, key)
+    if D in _core._PAD_HEAD_DIM:   # (bit-identical selection: see _core._PAD_HEAD_DIM)
+        query, key, _ = _core.pad_small_head_dim(query, key, key)
+        D = query.shape[-1]
+    query, key = _core._as_bhsd(query), _core._as_bhsd(key)
+    spec = _core.LayoutSpec(S, NB, NQ, n_txt, S, S, teb, ffb, 0, S, blk)
+    dev = query.device
+    names = ("qbar", "aq", "kbar", "ak", "vbar", "scores", "unrel", "probs", "w", "R", "bitmask", "cols", "counts")
+    shapes = _core.buffer_shapes(spec, B, H, D)
+    bufs = {n: torch.empty(shapes[n], dtype=_core._BUF_DTYPES[n], device=dev) for n in names}
+    cb = _lib.RsaBuffers(*[bufs[n].data_ptr() if n in bufs and bufs[n].numel() else None for n in _lib.BUFFER_NAMES], 0)
+    nbr = _core.neighbor_on_device(block_neighbor_list, NQ, dev)
+    L = _lib.lib()
+    tq, tk = _core._t4(query), _core._t4(key)
+    ex = blk != _lib.BLOCK
+    lay = spec.to_c_ex(B, H, D, query.dtype) if ex else spec.to_c(B, H, D, query.dtype)
+    sfx = "_ex" if ex else ""
+    st, lp, cbp = _core._stream(), ctypes.byref(lay), ctypes.byref(cb)
+    with torch.cuda.device(dev):
+        _lib.check(getattr(L, "rsa_pool_stats" + sfx)(lp, tq, tk, tk, cbp, st), "rsa_pool_stats")
+        _lib.check(getattr(L, "rsa_pooled_scores" + sfx)(lp, tk, cbp, st), "rsa_pooled_scores")
+        _lib.check(getattr(L, "rsa_select_mask" + sfx)(lp, nbr.data_ptr() if nbr is not None else None, int(top_k),
+                                                       float(prob_threshold), cbp, st), "rsa_select_mask")
+    one_hot = lists_to_block_mask(bufs["bitmask"], B, H, NQ, NB).view(torch.bool)
+    probs = bufs["probs"].view(B, H, NQ, spec.L)
+    nogapr = bufs["unrel"].view(B, H, NQ, NQ).view(torch.bool)
+    return one_hot, probs, nogapr
+
+
+def triton_block_sparse_attention_onehot(q, k, v, seqlens, block_mask, sm_scale, block_size_M=128, block_size_N=128):
+    """The reference's _triton_block_sparse_attention_onehot: [B,H,S,D] x3, seqlens [B] (the key limit per batch item),
+    block_mask [B,H,NQ,NB] -> [B,H,S,D].  Query blocks come from block_mask.shape[-2]: rows past NQ * block are 0, as the
+    reference's zero-initialised output leaves them."""
+    blk = _check_block_pair(block_size_M, block_size_N)
+    Sq = q.shape[2]
+    NQ = block_mask.shape[-2]
+    rows = min(Sq, NQ * blk)
+    nq = -(-rows // blk)
+    if nq < NQ:
+        block_mask = block_mask[:, :, :nq]
+    o = block_sparse_attention(q[:, :, :rows], k, v, block_mask, kv_len=seqlens, sm_scale=sm_scale, block_size=blk)
+    if rows == Sq:
+        return o
+    full = torch.zeros_like(q, memory_format=torch.contiguous_format)
+    full[:, :, :rows] = o
+    return full

@@ -387,6 +387,38 @@ extern "C" int rsa_block_sparse_fwd_ex(const rsa_layout_ex* lx, rsa_tensor4 q, r
     return rsa_layout_ex_ok(lx) ? block_sparse_fwd_b(&lx->base, lx->block, q, k, v, buf, out, stream) : RSA_ERR_BAD_ARG;
 }
 
+// Plain block-sparse attention over caller-supplied lists (rsa_block_mask_to_lists): the sparse walk of the rectified call with
+// no R / comp (the epilogue stores acc / l), the caller's scale, Sq query rows in NQ blocks and no text rows (NQB = NBv = NQ, so
+// nothing is written past row Sq), Sk key rows of which those >= kv_valid are masked.
+extern "C" int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, int kv_valid,
+                                          double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* cols,
+                                          const int32_t* counts, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream) {
+    if (block != 64 && block != RSA_BLOCK) return RSA_ERR_UNSUPPORTED;
+    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return RSA_ERR_BAD_ARG;
+    if (NQ != (Sq + block - 1) / block || NK <= 0 || NK > (Sk + block - 1) / block) return RSA_ERR_BAD_ARG;
+    if (NK > 8192) return RSA_ERR_UNSUPPORTED;
+    if (kv_valid <= 0 || kv_valid > Sk) return RSA_ERR_BAD_ARG;   // (a key row is clamped into [0, kv_valid) before it is staged)
+    if (!std::isfinite(sm_scale)) return RSA_ERR_BAD_ARG;       // (any sign: the online softmax needs none)
+    if (!cols || !counts) return RSA_ERR_BAD_ARG;
+    if (tpart && tpart_bytes == 0) return RSA_ERR_WORKSPACE;
+    int st;
+    if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v)) || (st = check_out(out)))
+        return st;
+    AttnArgs a;
+    fill_qkv(a, q, k, v, out);
+    a.cols = cols; a.counts = counts; a.R = nullptr; a.comp = nullptr;
+    a.tpart = tpart;
+    a.mode = MODE_SPARSE; a.H = H; a.Sq = Sq; a.Sk = Sk;
+    a.NBv = NQ; a.NQB = NQ; a.NB_total = NK;
+    a.blk = block; a.txt0 = NQ * block;
+    a.kv_valid = kv_valid; a.kv_text_valid = 0; a.q_text_end = 0;
+    a.q_split = 0; a.kv_split = 0; a.causal = 0; a.rows256 = 0;
+    a.qk_scale = (float)(sm_scale * 1.44269504);   // (as the reference kernel's launcher: hunyuan :145)
+    return launch_attn(a, B * H, D, dtype, tpart ? tpart_bytes : 0, static_cast<hipStream_t>(stream));
+}
+
 static int dense_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
                      int q_split, int kv_split, int causal, rsa_out4 out, void* stream) {
     if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return RSA_ERR_BAD_ARG;

@@ -5,8 +5,24 @@ import torch
 import torch.nn.functional as F
 
 from . import _operator as op
+from . import block_sparse
 from .attn import fullattn
 from .gapr_mask import estimate_pr_gain  # noqa: F401
+
+
+def _triton_block_sparse_attention_onehot(q, k, v, seqlens, block_mask, sm_scale, block_size_M=128, block_size_N=128):
+    """Plain block-sparse attention over any boolean block mask (reference :107-168) on the HIP kernel: [B,H,S,D] x3,
+    seqlens [B] = key limit per batch item, block_mask [B,H,NQ,NB] -> [B,H,S,D].  Rows without a visible key are 0, not NaN."""
+    return block_sparse.triton_block_sparse_attention_onehot(q, k, v, seqlens, block_mask, sm_scale, block_size_M, block_size_N)
+
+
+def _build_block_index_with_importance_optimized(query, key, top_k, block_size_M=128, block_size_N=128, text_start_block=None,
+                                                 text_end_block=None, num_blocks=None, prob_threshold=0.7,
+                                                 block_neighbor_list=None, attenable=None):
+    """The selection (reference :170-280) -> (one_hot bool [B,H,NQ,num_blocks], probs fp32 [B,H,NQ,NQ+1], nogapr bool
+    [B,H,NQ,NQ]), computed by the rectified call's selection pass.  query: the visual rows; key is not modified."""
+    return block_sparse.build_block_index(query, key, top_k, block_size_M, block_size_N, text_start_block, text_end_block,
+                                          num_blocks, prob_threshold, block_neighbor_list, attenable=attenable, text=True)
 
 
 def block_sparse_attention_combined(query, key, value, attn_mask, top_k, block_size_M=128, block_size_N=128,
