@@ -251,6 +251,30 @@ int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, int dtype, i
                                double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* cols,
                                const int32_t* counts, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream);
 
+/* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
+ * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
+ *
+ * K3 with the caller's mask in place of the sort: per (b, h, visual query block i) row it writes probs (softmax and IPAR of the
+ * contract, bit-identical to what K3 writes), then with kept = mask[b, h, i, :NB_total] (nonzero = kept, nothing added: no
+ * neighbour, text-block or first-frame union) and M_j = kept_j | unrel_j for j < NBv, M_NBv = kept_NBv (the text column):
+ *   R = sum of probs over M (the contract's strided tree),  w_j = M_j ? 0 : probs_j,  bitmask / cols / counts of `kept`.
+ * Call it after K2 and before K4.  mask: DEVICE uint8 [B|1, H|1, NBv, NB_total] with BYTE strides b / h / q (0 = broadcast for b
+ * and h; the query stride is positive) and a contiguous key axis.  A NULL mask or buffer, a negative stride or a query stride of
+ * 0 is RSA_ERR_BAD_ARG; a layout rsa_select_mask refuses gets the code it returns.  A visual row whose kept blocks hold no key below
+ * kv_valid comes out of K5 as comp (the reference's kernel gives NaN there).  One workgroup per row. */
+int rsa_select_from_mask(const rsa_layout* lay, const uint8_t* mask, int64_t mask_stride_b, int64_t mask_stride_h,
+                         int64_t mask_stride_q, const rsa_buffers* buf, void* stream);
+int rsa_select_from_mask_ex(const rsa_layout_ex* lay, const uint8_t* mask, int64_t mask_stride_b, int64_t mask_stride_h,
+                            int64_t mask_stride_q, const rsa_buffers* buf, void* stream);
+/* The whole operator on such a mask: K1, K2, the pass above, K4, K5 on one stream, in the workspace of
+ * rsa_rectified_attention (rsa_buffer_bytes / rsa_carve_workspace).  The mask arguments are checked before the first launch. */
+int rsa_rectified_attention_masked(const rsa_layout* lay, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const uint8_t* mask,
+                                   int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q, void* workspace,
+                                   size_t workspace_bytes, rsa_out4 out, void* stream);
+int rsa_rectified_attention_masked_ex(const rsa_layout_ex* lay, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                                      const uint8_t* mask, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_q,
+                                      void* workspace, size_t workspace_bytes, rsa_out4 out, void* stream);
+
 /* Stand-alone GAPR for callers of estimate_pr_gain (gapr_mask.py:4): blocks are [BH, N, 128, D] contiguous
  * 2-byte elements, pools [BH, N, D] fp32, scores [BH, NQ, NK] fp32 -> mask [BH, NQ, NK] uint8 (1 = ~gapr_mask). */
 int rsa_estimate_pr_gain(int BH, int NQ, int NK, int D, int dtype, const void* q_blocks, const void* k_blocks,

@@ -290,14 +290,37 @@ def fp8_kmean(scales: torch.Tensor, BH: int, NB_total: int, D: int = 128) -> tor
     return scales[BH * NB_total:].view(torch.float32).view(BH, D)
 
 
+def check_block_mask(block_mask: torch.Tensor, B: int, H: int, spec: LayoutSpec, block_neighbor_list=None) -> None:
+    """The checks of a caller's block mask for the rectified call that need no device: bool / uint8 [B|1, H|1, NBv, NB_total]
+    (the shape the selection builder returns), and no selection rule beside it that the mask would silently replace."""
+    want = f"[{B}|1, {H}|1, {spec.NBv}, {spec.NB_total}] ([B|1, H|1, NBv, NB_total] at block {spec.block})"
+    if not isinstance(block_mask, torch.Tensor) or block_mask.dtype not in (torch.bool, torch.uint8) or block_mask.dim() != 4:
+        got = f"{block_mask.dtype} {tuple(block_mask.shape)}" if isinstance(block_mask, torch.Tensor) else type(block_mask).__name__
+        raise ValueError(f"block_mask: a bool or uint8 tensor {want} expected, got {got}")
+    s = block_mask.shape
+    if s[0] not in (1, B) or s[1] not in (1, H) or s[2] != spec.NBv or s[3] != spec.NB_total:
+        raise ValueError(f"block_mask {tuple(s)} does not match {want}")
+    if block_neighbor_list is not None:
+        raise ValueError("block_neighbor_list is not applied when block_mask is given (the mask is the kept set as it "
+                         "stands): OR the neighbour blocks into the mask, block_mask[..., :NBv] |= block_neighbor_list")
+    if spec.first_frame_blocks:
+        raise ValueError("first_frame_blocks is not applied when block_mask is given (the mask is the kept set as it "
+                         "stands): OR the first-frame square into the mask, block_mask[..., :ffb, :ffb] = True")
+
+
 class StagedCall:
     """One rectified-attention call with its buffers: select() runs K1..K4 (mask-selection pass), attend() runs
     K5.  Both are asynchronous on the current stream.  q, k, v: [B, H, S, D] device tensors.
     qkv_fp8: K5 runs on e4m3 images of Q, K, V (written by K1 in its own pass) on the fp8 MFMA; the mask-selection
-    statistics are unchanged, so the kept lists are the 2-byte path's bit for bit."""
+    statistics are unchanged, so the kept lists are the 2-byte path's bit for bit.
+    block_mask: bool / uint8 [B|1, H|1, NBv, NB_total], the kept set of every visual query block as it stands; the selection
+    pass computes probs and the GAPR bit as always and derives R, w and the lists from the mask (rsa_select_from_mask) instead
+    of the sort (top_k and p_remain are then unused)."""
 
     def __init__(self, q, k, v, spec: LayoutSpec, top_k: int, p_remain: float, block_neighbor_list=None,
-                 qkv_fp8: bool = False, reuse_buffers: bool = False):
+                 qkv_fp8: bool = False, reuse_buffers: bool = False, block_mask: Optional[torch.Tensor] = None):
+        if block_mask is not None:
+            check_block_mask(block_mask, q.shape[0], q.shape[1], spec, block_neighbor_list)
         _require_device(q, k, v)
         self.L = _lib.lib()
         B, H, S, D = q.shape
@@ -334,6 +357,15 @@ class StagedCall:
         if qkv_fp8:
             self.fp8 = alloc_fp8_operands(spec, B, H, D, q.device, v_only=self.fp8_pv)
             self.cf = RsaFp8Operands(*[self.fp8[n].data_ptr() if self.fp8[n].numel() else None for n in ("q8", "k8", "v8t", "scales")])
+        self.mask = None
+        if block_mask is not None:
+            from .block_sparse import _mask_u8
+            m = _mask_u8(block_mask.to(q.device) if block_mask.device != q.device else block_mask)
+            if m.shape[2] > 1 and m.stride(2) == 0:   # (the library reads one mask row per query block)
+                m = m.contiguous()
+            self.mask = m   # (held until the call is done with it)
+            self.mask_strides = (0 if m.shape[0] == 1 else m.stride(0), 0 if m.shape[1] == 1 else m.stride(1),
+                                 m.stride(2) if m.shape[2] > 1 else 1)
 
     def quantize(self):
         """The stand-alone producer of the e4m3 images (rsa_quantize_fp8: one pass over Q, K, V).  select() does not need
@@ -363,14 +395,19 @@ class StagedCall:
                 _lib.check(L.rsa_pool_stats(lay, tq, tk, tv, cb, st), "rsa_pool_stats")
 
     def select_rest(self):
-        """K2..K4 (need only K1's statistics)."""
+        """K2..K4 (need only K1's statistics); with a block mask, K2, rsa_select_from_mask, K4."""
         cb, st = ctypes.byref(self.cb), _stream()
         tk = self.t[1]
-        (k2, lay), (k3, _), (k4, _) = self._fn("rsa_pooled_scores"), self._fn("rsa_select_mask"), self._fn("rsa_compensation")
+        (k2, lay), (k4, _) = self._fn("rsa_pooled_scores"), self._fn("rsa_compensation")
         with torch.cuda.device(self.q.device):
             _lib.check(k2(lay, tk, cb, st), "rsa_pooled_scores")
-            _lib.check(k3(lay, self.nbr.data_ptr() if self.nbr is not None else None, self.top_k,
-                          self.p, cb, st), "rsa_select_mask")
+            if self.mask is not None:
+                k3m, _ = self._fn("rsa_select_from_mask")
+                _lib.check(k3m(lay, self.mask.data_ptr(), *self.mask_strides, cb, st), "rsa_select_from_mask")
+            else:
+                k3, _ = self._fn("rsa_select_mask")
+                _lib.check(k3(lay, self.nbr.data_ptr() if self.nbr is not None else None, self.top_k,
+                              self.p, cb, st), "rsa_select_mask")
             _lib.check(k4(lay, cb, st), "rsa_compensation")
 
     def select(self):
@@ -399,22 +436,23 @@ class StagedCall:
 
 def rectified_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, spec: LayoutSpec, top_k: int,
                         p_remain: float, block_neighbor_list=None, return_parts: bool = False,
-                        shape_xfuse: bool = False, qkv_fp8: bool = False):
+                        shape_xfuse: bool = False, qkv_fp8: bool = False, block_mask: Optional[torch.Tensor] = None):
     """q, k, v: [B, H, S, D] device tensors -> [B, S, H*D] (or [B, S, H, D] if shape_xfuse).
 
     K1 pool_stats -> K2 pooled_scores -> K3 select_mask -> K4 compensation -> K5 block_sparse_fwd on the
     current stream; no host synchronisation, no K/V mutation (the reference zeroes masked K/V rows in place,
-    hunyuan :307-308; here they are treated as zero by predication)."""
+    hunyuan :307-308; here they are treated as zero by predication).  block_mask: the caller's kept set in place of K3's
+    selection (StagedCall); a visual row whose kept blocks hold no valid key comes out as comp (the reference: NaN)."""
     if q.shape[-1] in _PAD_HEAD_DIM:   # head dim 16 / 32: served zero-padded (exactly; see _PAD_HEAD_DIM)
         B, H, S, D = q.shape
         r = rectified_attention(*pad_small_head_dim(q, k, v), spec, top_k, p_remain, block_neighbor_list, return_parts,
-                                True, qkv_fp8)
+                                True, qkv_fp8, block_mask)
         o = (r[0] if return_parts else r)[..., :D]
         o = o.contiguous() if shape_xfuse else o.reshape(B, S, H * D)
         return (o, r[1]) if return_parts else o
     # return_parts hands the buffers to the caller, so those calls get their own set
     call = StagedCall(q, k, v, spec, top_k, p_remain, block_neighbor_list, qkv_fp8=qkv_fp8,
-                      reuse_buffers=not return_parts)
+                      reuse_buffers=not return_parts, block_mask=block_mask)
     call.select()
     out = call.attend()
     B, H, S, D = q.shape

@@ -73,8 +73,12 @@ def _fp8_mode(choice, D: int):
 
 def run(variant: str, query, key, value, top_k, prob_threshold, block_neighbor_list, shape_xfuse,
         cu_seqlens_q=None, cu_seqlens_kv=None, text_length: int = 256, first_frame_blocks=None,
-        block_size_M: int = 128, block_size_N: int = 128, qkv_fp8: Optional[bool] = None):
-    """qkv_fp8: per-call choice of the K5 operand precision (None = the process default set_qkv_fp8())."""
+        block_size_M: int = 128, block_size_N: int = 128, qkv_fp8: Optional[bool] = None, block_mask=None):
+    """qkv_fp8: per-call choice of the K5 operand precision (None = the process default set_qkv_fp8()).
+    block_mask: bool / uint8 [B|1, H|1, NBv, NB_total], the kept blocks of every visual query block as they stand (e.g. the
+    one_hot of _build_block_index_with_importance_optimized, reused or edited): the call is rectified over it -- R and the
+    compensation from the implicit full-attention probabilities and the GAPR bit as always --, top_k and prob_threshold are
+    unused, and a block_neighbor_list or first_frame_blocks (selection rules the mask replaces) is refused."""
     blk = _check_blocks(block_size_M, block_size_N)
     B, H, S, D = query.shape
     if variant == "hunyuan":
@@ -87,6 +91,9 @@ def run(variant: str, query, key, value, top_k, prob_threshold, block_neighbor_l
         spec = _core.LayoutSpec.wan(S, first_frame_blocks, block=blk)
     else:
         raise ValueError(variant)
+    if block_mask is not None:
+        _core.check_block_mask(block_mask, B, H, spec, block_neighbor_list)
+        top_k, prob_threshold = 0, 0.0
     if blk != BLOCK:
         # the fp8 K5 is built for 128-token blocks: the process default falls back to the 2-byte kernel (as for head dims
         # without an fp8 kernel), an explicit per-call request is refused rather than silently not honoured
@@ -97,7 +104,7 @@ def run(variant: str, query, key, value, top_k, prob_threshold, block_neighbor_l
     else:
         fp8 = _fp8_mode(QKV_FP8 if qkv_fp8 is None else qkv_fp8, D)
     return _core.rectified_attention(query, key, value, spec, int(top_k), float(prob_threshold),
-                                     block_neighbor_list, shape_xfuse=shape_xfuse, qkv_fp8=fp8)
+                                     block_neighbor_list, shape_xfuse=shape_xfuse, qkv_fp8=fp8, block_mask=block_mask)
 
 
 # ---- small helpers shared by the processors ---------------------------------------------------------

@@ -10,7 +10,8 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
 Difference from the reference kept on purpose: a query row that sees no key (no kept block, or every kept key at or beyond
-kv_len) is 0 here; the reference's Triton kernel divides 0 by 0 there and returns NaN."""
+kv_len) is 0 here; the reference's Triton kernel divides 0 by 0 there and returns NaN.  In the rectified call over a caller's mask
+(the variants' block_mask=) such a visual row therefore comes out as comp alone, 0 * R + comp."""
 from __future__ import annotations
 
 import ctypes

@@ -27,21 +27,21 @@ def _build_block_index_with_importance_optimized(query, key, top_k, block_size_M
 def block_sparse_attention_combined(query, key, value, attn_mask, top_k, block_size_M=128, block_size_N=128,
                                     cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None,
                                     prob_threshold=0.5, block_neighbor_list=None, text_length=256,
-                                    shape_xfuse=False, qkv_fp8=None):
+                                    shape_xfuse=False, qkv_fp8=None, block_mask=None):
     """[B,H,S,D] x3 -> [B,S,H*D] (reference :282-378)."""
     return op.run("cogvideo", query, key, value, top_k, prob_threshold, block_neighbor_list, shape_xfuse,
                   cu_seqlens_q=cu_seqlens_q, cu_seqlens_kv=cu_seqlens_kv, text_length=text_length,
-                  block_size_M=block_size_M, block_size_N=block_size_N, qkv_fp8=qkv_fp8)
+                  block_size_M=block_size_M, block_size_N=block_size_N, qkv_fp8=qkv_fp8, block_mask=block_mask)
 
 
 def rectified_block_sparse_attention(query, key, value, attn_mask, top_k, block_size_M=128, block_size_N=128,
                                      cu_seqlens_q=None, cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None,
                                      block_neighbor_list=None, shape_xfuse=False, p_remain_rates=0.5,
-                                     text_length=256, qkv_fp8=None):
+                                     text_length=256, qkv_fp8=None, block_mask=None):
     return block_sparse_attention_combined(query, key, value, attn_mask, top_k, block_size_M, block_size_N,
                                            cu_seqlens_q, cu_seqlens_kv, max_seqlen_q, max_seqlen_kv,
                                            prob_threshold=p_remain_rates, block_neighbor_list=block_neighbor_list,
-                                           text_length=text_length, shape_xfuse=shape_xfuse, qkv_fp8=qkv_fp8)
+                                           text_length=text_length, shape_xfuse=shape_xfuse, qkv_fp8=qkv_fp8, block_mask=block_mask)
 
 
 class RectifiedCogVideoXVideoSpaAttnProcessor2_0:
