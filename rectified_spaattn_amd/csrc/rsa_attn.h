@@ -1,5 +1,5 @@
-// Shared declarations of the K5 attention kernels (rsa_attn_kernel.hip: bf16 / fp16; rsa_attn_fp8_kernel.hip: e4m3)
-// and their host sides (rsa_attn.hip).
+// Shared declarations of the K5 attention kernels (rsa_attn_kernel64.hip, rsa_attn_kernel.hip: bf16 / fp16;
+// rsa_attn_fp8_kernel.hip: e4m3) and their host sides (rsa_attn.hip): argument structs, the walk plan, aligned starts.
 #pragma once
 #include <string.h>
 
@@ -68,38 +68,189 @@ struct Elem<fp16_tag> {
 
 enum { MODE_SPARSE = 0, MODE_DENSE = 1 };
 
-struct AttnArgs {
-    const unsigned short *q, *k, *v;
-    long qsb, qsh, qss, ksb, ksh, kss, vsb, vsh, vss;
+// What every K5 kernel needs to plan its walk and to store: the output, the kept lists, the shape and the launch's work
+// mapping (filled by rsa_plan_walk, rsa_attn.hip).  AttnArgs below and Attn8Args (rsa_attn_fp8_kernel.hip) add their operands.
+struct WalkArgs {
     unsigned short* out;
     long osb, osh, oss;
     const int32_t* cols;    // [BH, NBv, NB_total]
     const int32_t* counts;  // [BH, NBv]
     const float* R;         // [BH, NBv] or null
     const float* comp;      // [BH, NBv, D] or null
+    float* tpart;           // split-KV partials of the text query blocks (rsa_part_row), or null
+    float* tail_part;       // ... of the tail pieces (below)
+    unsigned* gsync;        // start-alignment counters of this launch (below), or null
     int mode, H, Sq, Sk;
     int NBv, NQB, NB_total;  // sparse: q blocks < NBv use lists; NQB = total q blocks
-    int kv_valid, kv_text_valid, q_text_end;  // sparse mode (q_text_end = NBv*128 + q_text_valid)
+    int kv_valid, kv_text_valid, q_text_end;  // sparse mode (q_text_end = NBv * block + q_text_valid)
     int q_split, kv_split;                    // dense mode
-    int causal;                               // dense mode: key j of a segment visible to its row i iff j <= i + (keys - rows)
-    int n_heavy_pad, NBp, BH;                 // work mapping
-    float* tpart;                             // split-KV partials of the text query blocks, or null
+    int causal;                               // dense mode: rsa_seg_hi
+    int n_heavy_pad, NBp, BH;                 // work mapping (rsa_walk_map)
     int tsplit, tper;                         // workgroups per text block, key blocks per workgroup
-    int heavy_last;                           // 64-row kernel: the (split) text-row pieces are the LAST workgroups of the grid
-    // 64-row kernel, tail split: sparse workgroups [0, tail_first) walk their whole list; the tail_n x tail_p workgroups behind them
-    // are the pieces of the tail_n sparse blocks tail_first .. (piece i = block tail_first + i / tail_p, part i % tail_p of its
-    // list), partials to tail_part; the text pieces follow.  tail_n = 0: no split
+    int heavy_last;                           // the (split) text-row pieces are the LAST workgroups of the grid
+    // Tail split: sparse workgroups [0, tail_first) walk their whole list; the tail_n x tail_p workgroups behind them are the
+    // pieces of the tail_n sparse blocks tail_first .. (piece i = block tail_first + i / tail_p, part i % tail_p of its list),
+    // partials to tail_part; the text pieces follow.  tail_n = 0: no split
     int tail_first, tail_n, tail_p;
-    float* tail_part;
-    float qk_scale;
-    unsigned* gsync;                          // 64-row kernel: start-alignment counters of this launch (rsa_attn_kernel64.hip), or null
-    int gsync_gen;                            // ... workgroups an XCD holds at a time (a generation)
+    int gsync_gen;                            // aligned starts: workgroups an XCD holds at a time (a generation)
     int gsync_ratio;                          // ... walks that keep 1 / gsync_ratio of the keys or more are not held (default 2)
-    int rows256;                              // 64-row kernel, dense calls: NQB / NBv count 256-row tiles (four waves per workgroup, one K/V ring)
     int k5_static;                            // 64-row kernel, bf16: the steady state keeps the softmax reference it is entered with (checked, redone if it overflowed)
+};
+
+struct AttnArgs : WalkArgs {
+    const unsigned short *q, *k, *v;
+    long qsb, qsh, qss, ksb, ksh, kss, vsb, vsh, vss;
+    float qk_scale;
+    int rows256;                              // 64-row kernel, dense calls: NQB / NBv count 256-row tiles (four waves per workgroup, one K/V ring)
     int blk;                                  // tokens per block: 128, or 64 (sparse calls through the _ex entry points: the 32-row kernel's pair walk)
     int txt0;                                 // blk 64: first text query row (NBv * 64); text units of 128 rows from there
 };
+
+// The kernel's own arguments, read in place: the argument struct must be the kernel's ONLY parameter (it then sits at offset 0
+// of the kernarg segment).  The 64-row and 32-row kernels take their arguments this way, not through the by-value parameter: once
+// the dense plan is the shared functions below, every use of that parameter is a plain field read and hipcc loads the whole
+// struct at the head of the kernel; the fields the epilogue needs then stay live across the walk (10 scalar registers spilled
+// in the 32-row instances at head dim 128).  Through the pointer each field is loaded where it is used, as at every use of a
+// by-value parameter hipcc does not take apart.
+template <typename A>
+__device__ __forceinline__ const A& rsa_kernargs() {
+    return *static_cast<const A*>((const void*)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The walk plan of a workgroup, shared by the three K5 kernels (rsa_attn_kernel64.hip, rsa_attn_kernel.hip,
+// rsa_attn_fp8_kernel.hip).  Out-parameters, not returned structs: after inlining the values are the callers' own scalars.
+//
+// Work mapping: grid index -> (batch * head, unit, piece); returns what the workgroup walks (WALK_NONE = padding workgroup).
+// A head's sparse units (query blocks; n_units = NBv, or the (NBv + 1) >> 1 PAIRS of 64-token blocks) are padded to NBp, a
+// multiple of 8: workgroup v of them goes to XCD
+// v & 7, which takes the (v & 7)-th contiguous eighth of the head's units.  The dense text-row blocks (unit = NBv + text block)
+// come FIRST when each is one long walk over every key block (no split-KV buffer: the longest work first), and LAST when they
+// are split into tsplit pieces shorter than a sparse walk (heavy_last; tsp = the piece): with aligned starts the launch advances
+// in generations of 8 x 64 workgroups, and the short pieces then fill the slots the last, partial generation leaves idle instead
+// of adding a generation of their own.  Tail split (tail_n > 0; sparse units first): the units from index tail_first on -- the
+// last, partial generation -- are walked by tail_p workgroups each, which together fill the slots that generation would leave
+// idle; tail >= 0 is such a piece's index (else -1) and tsp its part of the kept list.
+__host__ __device__ __forceinline__ int rsa_walk_unit(int j, int NBp) { return (j & 7) * (NBp >> 3) + (j >> 3); }   // j-th of a head's NBp
+enum { WALK_NONE = 0, WALK_SPARSE = 1, WALK_TEXT = 2 };
+__device__ __forceinline__ int rsa_walk_map(const WalkArgs& a, int work, int n_units, int& bh, int& unit, int& tsp, int& tail) {
+    tsp = 0;
+    tail = -1;
+    const int n_sparse = a.BH * a.NBp;
+    const bool heavy_last = a.heavy_last != 0;
+    int wh = heavy_last ? work - n_sparse : work;                 // index among the text-row pieces
+    int v = heavy_last ? work : work - a.n_heavy_pad;             // index among the sparse units
+    bool text = heavy_last ? work >= n_sparse : work < a.n_heavy_pad;
+    if (a.tail_n > 0) {
+        const int tail_end = a.tail_first + a.tail_n * a.tail_p;
+        text = work >= tail_end;
+        wh = work - tail_end;
+        if (work >= a.tail_first && !text) {
+            tail = work - a.tail_first;
+            v = a.tail_first + tail / a.tail_p;
+            tsp = tail % a.tail_p;
+        }
+    }
+    if (text) {
+        const int ntq = a.NQB - a.NBv;
+        const int per_bh = ntq * a.tsplit;      // text blocks x key-range splits (tsplit = 1: no split)
+        if (ntq <= 0 || wh >= a.BH * per_bh) return WALK_NONE;
+        bh = wh / per_bh;
+        const int rem = wh % per_bh;
+        unit = a.NBv + rem / a.tsplit;
+        tsp = rem % a.tsplit;
+    } else {
+        bh = v / a.NBp;
+        unit = rsa_walk_unit(v % a.NBp, a.NBp);
+        if (unit >= n_units) return WALK_NONE;
+    }
+    return text ? WALK_TEXT : WALK_SPARSE;
+}
+
+// Sparse walk of visual block rowi (= bh * NBv + block): its kept list, or part tsp of it for a tail piece (tail >= 0)
+__device__ __forceinline__ void rsa_walk_list(const WalkArgs& a, long rowi, int tail, int tsp, const int32_t*& list, int& n_items) {
+    list = a.cols + rowi * a.NB_total;
+    n_items = a.counts[rowi];
+    if (tail >= 0) {
+        const int per = (n_items + a.tail_p - 1) / a.tail_p, first = tsp * per;
+        const int left = n_items - first;
+        list += first;
+        n_items = left < 0 ? 0 : (left < per ? left : per);
+    }
+}
+// Walk of a text block over the key blocks (of blk tokens) of the valid text keys, or slice tsp of them (split-KV)
+__device__ __forceinline__ void rsa_walk_text(const WalkArgs& a, int blk, int tsp, int& first_blk, int& n_items) {
+    n_items = (a.kv_text_valid + blk - 1) / blk;
+    if (a.tsplit > 1) {
+        first_blk = tsp * a.tper;
+        n_items = n_items - first_blk < a.tper ? n_items - first_blk : a.tper;
+        if (n_items < 0) n_items = 0;
+    }
+}
+
+// Dense mode: one or two (query rows, key rows) segments -- rows below q_split see keys [0, kv_split), the others
+// [kv_split, Sk) (attn.py:107-120).  causal = bottom-right aligned inside a segment: key j of a segment visible to its row i iff
+// j <= i + (keys - rows) (flash-attn's convention; equal to the top-left form of the reference's "torch" / "vanilla" modes,
+// attn.py:101-106 / :129-133, whenever a segment has as many keys as rows -- the only case the Python side lets through.  The
+// reference's "flash" mode never passes `causal` on, attn.py:107-116, and neither does attn.py here).
+// One past the last key row `row` may see:
+__device__ __forceinline__ int rsa_seg_hi(const WalkArgs& a, int row) {
+    const bool s1 = row >= a.q_split;
+    const int lo = s1 ? a.kv_split : 0, hi = s1 ? a.Sk : a.kv_split;
+    if (!a.causal) return hi;
+    const int rows = s1 ? a.Sq - a.q_split : a.q_split, rin = row - (s1 ? a.q_split : 0);
+    const int lim = lo + rin + 1 + ((hi - lo) - rows);
+    return lim < lo ? lo : (lim < hi ? lim : hi);
+}
+// the key range [lo, hi) of query row grow (rows past the sequence: the last row's)
+__device__ __forceinline__ void rsa_dense_row(const WalkArgs& a, int grow, int& lo, int& hi) {
+    lo = grow < a.q_split ? 0 : a.kv_split;
+    hi = rsa_seg_hi(a, grow < a.Sq ? grow : a.Sq - 1);
+}
+// ... and of the tile of `rows` query rows from row0: the extremes of its rows' ranges and the key blocks it walks
+__device__ __forceinline__ void rsa_dense_tile(const WalkArgs& a, int row0, int rows, int& lo_max, int& hi_min, int& hi_max,
+                                               int& first_blk, int& n_items) {
+    const int row1 = row0 + rows;
+    int lo_min;
+    const int rlast = (row1 <= a.Sq ? row1 : a.Sq) - 1;   // last real row of the tile
+    if (row1 <= a.q_split) { lo_min = 0; lo_max = 0; }
+    else if (row0 >= a.q_split) { lo_min = lo_max = a.kv_split; }
+    else { lo_min = 0; lo_max = a.kv_split; }
+    // rsa_seg_hi grows with the row inside a segment: extremes of the tile sit at its first / last row of each segment
+    hi_min = rsa_seg_hi(a, row0);
+    hi_max = rsa_seg_hi(a, rlast);
+    if (row0 < a.q_split && rlast >= a.q_split) {   // the tile straddles the two segments
+        const int h0 = rsa_seg_hi(a, a.q_split - 1), h1 = rsa_seg_hi(a, a.q_split);
+        hi_min = hi_min < h1 ? hi_min : h1;
+        hi_max = hi_max > h0 ? hi_max : h0;
+    }
+    first_blk = lo_min / RSA_BLOCK;
+    n_items = (hi_max + RSA_BLOCK - 1) / RSA_BLOCK - first_blk;
+    if (hi_max <= lo_min) n_items = 0;
+}
+
+// the partial row a walk stores to: piece `tail` of tail_part, or piece tsp of text block `unit` in tpart (tsplit pieces per block)
+__device__ __forceinline__ float* rsa_part_of(const WalkArgs& a, int bh, int unit, int tsp, int tail, int row, int D) {
+    return tail >= 0 ? a.tail_part + rsa_part_row(tail, row, D)
+                     : a.tpart + rsa_part_row(((long)bh * (a.NQB - a.NBv) + (unit - a.NBv)) * a.tsplit + tsp, row, D);
+}
+
+// Host plan of a launch (rsa_attn.hip): text split, text pieces first or last, padding, tail split and the grid size, from the
+// shape and the policy of the kernel family that asks.
+struct WalkPolicy {
+    int blk;                   // tokens per block; 64: the sparse units are pairs of query blocks
+    int short_grid_text_cap;   // most pieces per text block on grids of fewer than 8 generations (longer grids, shard invariance: 16)
+    bool tail_split;           // the kernel can store a tail piece's partial ...
+    bool tail_beside_text;     // ... and a split tail pays beside text pieces placed last (else only in launches without text rows)
+};
+// *nblocks = workgroups to launch (0: nothing to do).  rsa_combine_walk: the passes behind the kernel, tail pieces then text pieces.
+int rsa_plan_walk(WalkArgs& a, int BH, int D, const WalkPolicy& pol, size_t tpart_bytes, long* nblocks);
+int rsa_combine_walk(const WalkArgs& a, int D, int blk, int dtype, hipStream_t s);
+int rsa_launch_bsfwd(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s);     // rsa_attn_kernel.hip
+int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s);   // rsa_attn_kernel64.hip
+int rsa_check_out(const rsa_out4& o);
+void rsa_set_fp8_variant(int v);      // rsa_attn_fp8_kernel.hip; tuning key "fp8_variant"
+void rsa_set_fp8_smooth_k(int v);     // rsa_fp8.hip; tuning key "fp8_smooth_k"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Aligned starts of the sparse walks (all K5 kernels; host side: rsa_gsync_slot in rsa_attn.hip).

@@ -1,4 +1,5 @@
-// K5 host side: argument checks and launches of the block-sparse attention kernel (rsa_attn_kernel.hip).
+// K5 host side: the plan of a launch (rsa_plan_walk: every K5 kernel's), the combine passes behind it, argument checks and
+// launches of the 2-byte block-sparse attention kernels (rsa_attn_kernel64.hip, rsa_attn_kernel.hip).
 // rsa_block_sparse_fwd, rsa_dense_fwd and rsa_rectified_attention of include/rsa.h live here.
 #include <stdlib.h>
 
@@ -14,8 +15,8 @@ extern int g_rsa_k3_prefix;
 extern int g_rsa_k3_long;
 extern int g_rsa_k4_split;
 extern int g_rsa_k2_dma;
-static int g_k5_tail_split = 1; // 64-row kernel: the last, partial generation's walks split over its idle slots (k5w_map)
-static int g_k5_text_last = 1;  // 64-row kernel: split text-row pieces at the end of the grid (rsa_attn_kernel64.hip::k5w_map)
+static int g_k5_tail_split = 1; // the last, partial generation's walks split over its idle slots (rsa_attn.h::rsa_walk_map)
+static int g_k5_text_last = 1;  // split text-row pieces at the end of the grid (rsa_attn.h::rsa_walk_map)
 static int g_shard_invariant = 0; // rsa_set_shard_invariant: nothing about a row's arithmetic may depend on the size of the launch
 static int g_k5_gsync_ratio = 2; // aligned starts: walks that keep 1 / ratio of the keys or more are not held back
 int rsa_gsync_ratio() { return g_k5_gsync_ratio; }
@@ -24,11 +25,9 @@ static int g_k5_static = 1;     // 64-row kernel, bf16: optimistic static softma
 int rsa_k5_static() { return g_k5_static; }
 static int g_k5_gsync = 1;      // aligned starts of the sparse walks (rsa_attn.h): bit 0 = in the 64-row kernel, bit 1 = in the 32-row and e4m3 kernels
 
-void rsa_set_fp8_variant(int v);
-void rsa_set_fp8_smooth_k(int v);
-int rsa_launch_bsfwd(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s);
-int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s);
 static int g_k5_w64 = 3;        // the 64-rows-per-wave kernel (rsa_attn_kernel64.hip): bit 0 = at head dim 128, bit 1 = at head dim 64 (round 6); a clear bit = the 32-row kernel (A/B)
+// does a call run the 64-row kernel?  (64-token blocks: the 32-row kernel, whose 64-key tiles are exactly one block)
+static bool k5_runs_w64(int D, int blk) { return blk == RSA_BLOCK && ((D == 128 && (g_k5_w64 & 1)) || (D == 64 && (g_k5_w64 & 2))); }
 
 // Tuning / diagnostics hook (not part of the data path).  The switches are process-global, so the hook only works in a
 // process that opted in with the environment variable RSA_TUNING=1 (the A/B tools and the variant tests); a production
@@ -70,8 +69,8 @@ __global__ __launch_bounds__(256) void text_combine_kernel(const float* __restri
     const int tq = (int)(bhq % ntq);
     const int grow = txt0 + tq * RSA_BLOCK + r;   // (txt0 = NBv * block: the text rows, in units of 128)
     if (grow >= Sq) return;
-    const float* base = tpart + (bhq * tsplit * RSA_BLOCK + r) * (long)(D + 2);
-    const long pstride = (long)RSA_BLOCK * (D + 2);
+    const float* base = tpart + rsa_part_row(bhq * tsplit, r, D);
+    const long pstride = rsa_part_row(1, 0, D);
     // (round 6: every load of the row issued up front -- (m, l) of all pieces, then the pieces' values eight at a time -- instead of
     // one dependent round trip per piece; the sums run in the same order, piece 0 first: same bytes)
     constexpr int MAXP = RSA_TEXT_SPLIT;
@@ -120,45 +119,13 @@ __global__ __launch_bounds__(256) void text_combine_kernel(const float* __restri
     }
 }
 
-// (also used by the fp8 kernel's host side, rsa_attn_fp8_kernel.hip)
-static int launch_text_combine_at(const float* tpart, unsigned short* out, long osb, long osh, long oss, int D, int H, int txt0,
-                                  int ntq, int tsplit, int q_text_end, int Sq, int BH, int dtype, hipStream_t s) {
-    const long rows = (long)BH * ntq * RSA_BLOCK;
-    if (rows <= 0) return RSA_OK;
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    if (dtype == RSA_BF16)
-        text_combine_kernel<bf16_tag><<<grid, 256, 0, s>>>(tpart, out, osb, osh, oss, D, H, txt0, ntq, tsplit, q_text_end,
-                                                         Sq, rows);
-    else
-        text_combine_kernel<fp16_tag><<<grid, 256, 0, s>>>(tpart, out, osb, osh, oss, D, H, txt0, ntq, tsplit, q_text_end,
-                                                         Sq, rows);
-    return rsa_launch_status();
-}
-int rsa_launch_text_combine(const float* tpart, unsigned short* out, long osb, long osh, long oss, int D, int H, int NBv,
-                            int ntq, int tsplit, int q_text_end, int Sq, int BH, int dtype, hipStream_t s) {
-    return launch_text_combine_at(tpart, out, osb, osh, oss, D, H, NBv * RSA_BLOCK, ntq, tsplit, q_text_end, Sq, BH, dtype, s);
-}
-int rsa_text_split_enabled() { return g_k5_tsplit; }
-int rsa_shard_invariant() { return g_shard_invariant; }
 extern "C" int rsa_set_shard_invariant(int on) {
     const int prev = g_shard_invariant;
     g_shard_invariant = on != 0;
     return prev;
 }
-// How many pieces the partial buffer has room for per text block (capacity in bytes declared by the caller, rsa_buffers.tpart_bytes)
-int rsa_text_split_capacity(size_t tpart_bytes, int BH, int ntq, int D) {
-    const size_t per = (size_t)BH * (size_t)(ntq > 0 ? ntq : 1) * RSA_BLOCK * (size_t)(D + 2) * sizeof(float);
-    const size_t n = tpart_bytes / per;
-    return n > (size_t)RSA_TEXT_SPLIT ? RSA_TEXT_SPLIT : (int)n;
-}
-// Room for the tail pieces behind the text region (which always starts RSA_TEXT_SPLIT pieces per text block in)
-bool rsa_tail_fits(size_t tpart_bytes, int BH, int ntq, int D, int tail_n, int tail_p) {
-    const size_t blk = (size_t)RSA_BLOCK * (size_t)(D + 2) * sizeof(float);
-    return ((size_t)BH * (size_t)ntq * RSA_TEXT_SPLIT + (size_t)tail_n * (size_t)tail_p) * blk <= tpart_bytes;
-}
-int rsa_text_last_enabled() { return g_k5_text_last; }
 
-// Tail split of the 64-row kernel (rsa_attn_kernel64.hip::k5w_map): merge the tail_p partials of every tail block, then what the
+// Tail split (rsa_attn.h::rsa_walk_map): merge the tail_p partials of every tail block, then what the
 // kernel's own epilogue does -- normalise, rectify (O . R / l + comp as one fma rounded to fp32), convert, store.  One wave per
 // query row, lane = d and d + 64.
 template <typename Tag>
@@ -170,12 +137,12 @@ __global__ __launch_bounds__(256) void tail_combine_kernel(const float* __restri
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (long)tail_n * RSA_BLOCK) return;
     const int t = (int)(row / RSA_BLOCK), r = (int)(row % RSA_BLOCK);
-    const int v = tail_first + t, bh = v / NBp, j = v % NBp;
-    const int qblk = (j & 7) * (NBp >> 3) + (j >> 3);
+    const int v = tail_first + t, bh = v / NBp;
+    const int qblk = rsa_walk_unit(v % NBp, NBp);
     const int grow = qblk * RSA_BLOCK + r;
     if (qblk >= NBv || grow >= Sq) return;
-    const float* base = part + ((long)t * tail_p * RSA_BLOCK + r) * (long)(D + 2);
-    const long pstride = (long)RSA_BLOCK * (D + 2);
+    const float* base = part + rsa_part_row((long)t * tail_p, r, D);
+    const long pstride = rsa_part_row(1, 0, D);
     float M = -INFINITY;
     for (int p = 0; p < tail_p; ++p) M = fmaxf(M, base[p * pstride + D]);
     float L = 0.0f, acc[2] = {0.0f, 0.0f};
@@ -198,37 +165,30 @@ __global__ __launch_bounds__(256) void tail_combine_kernel(const float* __restri
     }
 }
 
-// (also used by the e4m3 kernel's host side, rsa_attn_fp8_kernel.hip)
-int rsa_launch_tail_combine(const float* part, unsigned short* out, long osb, long osh, long oss, int H, int NBv, int NBp,
-                            int tail_first, int tail_n, int tail_p, const float* R, const float* comp, int Sq, int dtype,
-                            hipStream_t s) {
-    const long rows = (long)tail_n * RSA_BLOCK;
+// The passes behind a K5 kernel: the tail pieces' merge, then the text pieces' (blk: tokens per block, the text rows start at NBv * blk)
+int rsa_combine_walk(const WalkArgs& a, int D, int blk, int dtype, hipStream_t s) {
+    if (a.tail_n > 0) {
+        const dim3 grid((unsigned)(((long)a.tail_n * RSA_BLOCK + 3) / 4));
+        if (dtype == RSA_BF16)
+            tail_combine_kernel<bf16_tag><<<grid, 256, 0, s>>>(a.tail_part, a.out, a.osb, a.osh, a.oss, a.H, a.NBv, a.NBp, a.tail_first,
+                                                             a.tail_n, a.tail_p, a.R, a.comp, a.Sq);
+        else
+            tail_combine_kernel<fp16_tag><<<grid, 256, 0, s>>>(a.tail_part, a.out, a.osb, a.osh, a.oss, a.H, a.NBv, a.NBp, a.tail_first,
+                                                             a.tail_n, a.tail_p, a.R, a.comp, a.Sq);
+        const int st = rsa_launch_status();
+        if (st != RSA_OK) return st;
+    }
+    const int ntq = a.NQB - a.NBv;
+    const long rows = (long)a.BH * ntq * RSA_BLOCK;
+    if (a.tsplit <= 1 || rows <= 0) return RSA_OK;
     const dim3 grid((unsigned)((rows + 3) / 4));
     if (dtype == RSA_BF16)
-        tail_combine_kernel<bf16_tag><<<grid, 256, 0, s>>>(part, out, osb, osh, oss, H, NBv, NBp, tail_first, tail_n, tail_p, R, comp, Sq);
+        text_combine_kernel<bf16_tag><<<grid, 256, 0, s>>>(a.tpart, a.out, a.osb, a.osh, a.oss, D, a.H, a.NBv * blk, ntq, a.tsplit,
+                                                         a.q_text_end, a.Sq, rows);
     else
-        tail_combine_kernel<fp16_tag><<<grid, 256, 0, s>>>(part, out, osb, osh, oss, H, NBv, NBp, tail_first, tail_n, tail_p, R, comp, Sq);
+        text_combine_kernel<fp16_tag><<<grid, 256, 0, s>>>(a.tpart, a.out, a.osb, a.osh, a.oss, D, a.H, a.NBv * blk, ntq, a.tsplit,
+                                                         a.q_text_end, a.Sq, rows);
     return rsa_launch_status();
-}
-// the plan of a tail split (see launch_attn): n_sparse = BH x NBp sparse workgroups, n_heavy_pad text pieces behind them
-int rsa_plan_tail_split(long n_sparse, long n_heavy_pad, int* tail_first, int* tail_n, int* tail_p) {
-    *tail_first = *tail_n = *tail_p = 0;
-    if (!g_k5_tail_split || g_shard_invariant) return 0;
-    const long full = n_sparse / 512, T = n_sparse % 512;
-    const long room = 512 - n_heavy_pad;
-    const long P = T > 0 ? (room / T < 4 ? room / T : 4) : 0;
-    if (full < 1 || T <= 0 || P < 2) return 0;
-    *tail_first = (int)(full * 512); *tail_n = (int)T; *tail_p = (int)P;       // T x P <= 512 = RSA_TAIL_PIECES
-    return 1;
-}
-static int launch_tail_combine(const AttnArgs& a, int dtype, hipStream_t s) {
-    return rsa_launch_tail_combine(a.tail_part, a.out, a.osb, a.osh, a.oss, a.H, a.NBv, a.NBp, a.tail_first, a.tail_n, a.tail_p, a.R,
-                                   a.comp, a.Sq, dtype, s);
-}
-
-static int launch_text_combine(const AttnArgs& a, int BH, int D, int dtype, hipStream_t s) {
-    return launch_text_combine_at(a.tpart, a.out, a.osb, a.osh, a.oss, D, a.H, a.txt0, a.NQB - a.NBv, a.tsplit,
-                                  a.q_text_end, a.Sq, BH, dtype, s);
 }
 
 // Aligned starts (rsa_attn.h): the counters are a ring of slots in a __device__ array of the code object (no allocation, nothing
@@ -277,68 +237,79 @@ int rsa_wg_per_cu(const void* kernel, int block, size_t lds_bytes) {
     return n;
 }
 
-static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes, hipStream_t s) {
+int rsa_plan_walk(WalkArgs& a, int BH, int D, const WalkPolicy& pol, size_t tpart_bytes, long* nblocks) {
+    *nblocks = 0;
+    const int blk = pol.blk;
     const int ntq = a.NQB - a.NBv;
     if (a.tpart && tpart_bytes == 0) return RSA_ERR_WORKSPACE;   // capacity not declared (rsa_buffers.tpart_bytes, 0.5.0)
-    a.gsync = nullptr; a.gsync_gen = 64; a.gsync_ratio = 2; a.k5_static = g_k5_static;
+    const size_t piece_bytes = (size_t)rsa_part_row(1, 0, D) * sizeof(float);
+    a.BH = BH;
+    a.NBp = ((blk == 64 ? (a.NBv + 1) >> 1 : a.NBv) + 7) & ~7;   // (blk 64: pairs of query blocks)
     // split-KV for the dense text rows: without it one workgroup walks every key block of a text query block (902 at the
     // HunyuanVideo shape = 10 kept lists) -- hidden among 21 600 sparse blocks on one GPU, the critical path when the
     // heads are sharded over 8
-    const int n_txt_items = (a.kv_text_valid + a.blk - 1) / a.blk;
+    const int n_txt_items = (a.kv_text_valid + blk - 1) / blk;
     a.tsplit = 1; a.tper = n_txt_items;
     if (a.mode == MODE_SPARSE && ntq > 0 && a.tpart && g_k5_tsplit && n_txt_items >= 32) {
-        int sp = n_txt_items / 16;
-        // 16 pieces per text block; 32 (RSA_TEXT_SPLIT, what tpart is sized for) on grids of fewer than 8 generations, where the
-        // pieces of 0.6 of a sparse walk's life would be the last to finish behind a split tail (and the combine pass that
-        // doubles with them is still small)
-        int cap = ((long)BH * (a.blk == 64 ? (((a.NBv + 1) >> 1) + 7) & ~7 : (a.NBv + 7) & ~7) < 8 * 512 && !g_shard_invariant)
-                      ? RSA_TEXT_SPLIT : 16;
-        const int room = rsa_text_split_capacity(tpart_bytes, BH, ntq, D);   // what the caller's buffer holds
-        if (cap > room) cap = room;
+        const int sp = n_txt_items / 16;
+        // 16 pieces per text block; with the 2-byte kernels 32 (RSA_TEXT_SPLIT, what tpart is sized for) on grids of fewer than 8
+        // generations, where the pieces of 0.6 of a sparse walk's life would be the last to finish behind a split tail (and the
+        // combine pass that doubles with them is still small)
+        int cap = ((long)BH * a.NBp < 8 * 512 && !g_shard_invariant) ? pol.short_grid_text_cap : 16;
+        const size_t room = tpart_bytes / ((size_t)BH * (size_t)ntq * piece_bytes);   // what the caller's buffer holds
+        if ((size_t)cap > room) cap = (int)room;
         a.tsplit = sp > cap ? cap : sp;
         if (a.tsplit < 2) a.tsplit = 1;
         a.tper = (n_txt_items + a.tsplit - 1) / a.tsplit;
     }
     const int n_heavy = ntq > 0 ? BH * ntq * a.tsplit : 0;
     a.heavy_last = a.tsplit > 1 && g_k5_text_last;
-    a.BH = BH;
     a.n_heavy_pad = (n_heavy + 7) & ~7;
-    a.NBp = a.blk == 64 ? (((a.NBv + 1) >> 1) + 7) & ~7 : (a.NBv + 7) & ~7;   // (blk 64: pairs of query blocks)
-    long nblocks = (long)a.n_heavy_pad + (long)BH * a.NBp;
-    // Tail split (64-row kernel, sparse lists): 512 workgroups run at a time (2 per CU), each for about as long as the others, so
-    // a launch costs ceil(workgroups / 512) lives; when the last generation of sparse blocks is less than half full, its blocks'
-    // walks are split over the idle slots (tail_p pieces each, partials behind the text region of tpart) and merged by a combine
-    // pass.  Which blocks are split depends on the grid: a sharded and an unsharded run then agree on those blocks within
-    // rounding, not byte for byte (tuning key k5_tail_split = 0 keeps every walk whole).
+    const long n_sparse = (long)BH * a.NBp;
+    *nblocks = (long)a.n_heavy_pad + n_sparse;
+    // Tail split (sparse lists): 512 workgroups run at a time (2 per CU), each for about as long as the others, so a launch costs
+    // ceil(workgroups / 512) lives; when the last generation of sparse blocks is less than half full, its blocks' walks are
+    // split over the idle slots (tail_p pieces each, partials behind the text region of tpart, which always starts RSA_TEXT_SPLIT
+    // pieces per text block in) and merged by a combine pass.  Which blocks are split depends on the grid: a sharded and an
+    // unsharded run then agree on those blocks within rounding, not byte for byte (tuning key k5_tail_split = 0 keeps every
+    // walk whole).  The pieces AND the text-row pieces behind them must fit the 512 slots together: otherwise whatever starts
+    // late (0.6 of a life for a text piece) ends the launch as late as the unsplit tail did (measured: 3 heads of the headline
+    // shape, 456 pieces + 96 text pieces: 1.92 ms against 1.88 unsplit).
+    // (e4m3 kernel, tail_beside_text = false: with its shorter lives and two waves per SIMD the split measured +1.6 % on Wan2.2-TI2V
+    // and -2.3 % at 3 heads of the HunyuanVideo shape, where the text pieces end the launch either way: profiles/r04_k5_tail_split.txt)
     a.tail_first = a.tail_n = a.tail_p = 0; a.tail_part = nullptr;
-    const bool w64 = D == 128 && (g_k5_w64 & 1) && a.blk == RSA_BLOCK;
-    if (w64 && a.mode == MODE_SPARSE && a.tpart && (a.heavy_last || n_heavy == 0)) {
-        // the pieces AND the text-row pieces behind them must fit the 512 slots together: otherwise whatever starts late (0.6 of a
-        // life for a text piece) ends the launch as late as the unsplit tail did (measured: 3 heads of the headline shape, 456
-        // pieces + 96 text pieces: 1.92 ms against 1.88 unsplit)
-        if (rsa_plan_tail_split((long)BH * a.NBp, a.n_heavy_pad, &a.tail_first, &a.tail_n, &a.tail_p) &&
-            !rsa_tail_fits(tpart_bytes, BH, ntq, D, a.tail_n, a.tail_p))
-            a.tail_first = a.tail_n = a.tail_p = 0;
-        if (a.tail_n > 0) {
-            a.tail_part = a.tpart + (long)BH * ntq * RSA_TEXT_SPLIT * RSA_BLOCK * (D + 2);
-            nblocks = (long)a.tail_first + (long)a.tail_n * a.tail_p + a.n_heavy_pad;
+    if (pol.tail_split && a.mode == MODE_SPARSE && a.tpart && (n_heavy == 0 || (pol.tail_beside_text && a.heavy_last)) && g_k5_tail_split &&
+        !g_shard_invariant) {
+        const long full = n_sparse / 512, T = n_sparse % 512;
+        const long room = 512 - a.n_heavy_pad;
+        const long P = T > 0 ? (room / T < 4 ? room / T : 4) : 0;      // T x P <= 512 = RSA_TAIL_PIECES
+        const size_t text_pieces = (size_t)BH * (size_t)ntq * RSA_TEXT_SPLIT;
+        if (full >= 1 && T > 0 && P >= 2 && (text_pieces + (size_t)(T * P)) * piece_bytes <= tpart_bytes) {
+            a.tail_first = (int)(full * 512); a.tail_n = (int)T; a.tail_p = (int)P;
+            a.tail_part = a.tpart + rsa_part_row((long)text_pieces, 0, D);
+            *nblocks = (long)a.tail_first + (long)a.tail_n * a.tail_p + a.n_heavy_pad;
         }
     }
-    if (nblocks <= 0) return RSA_OK;
-    if (nblocks > 0x7FFFFFFF) return RSA_ERR_UNSUPPORTED;
-    if (a.NB_total > 8192) return RSA_ERR_UNSUPPORTED;  // kept list lives in LDS as u16, 16 KiB max
+    if (*nblocks <= 0) { *nblocks = 0; return RSA_OK; }
+    if (*nblocks > 0x7FFFFFFF) return RSA_ERR_UNSUPPORTED;
+    if (a.NB_total > 8192) return RSA_ERR_UNSUPPORTED;  // kept list lives in LDS, 16 KiB (u16) / 32 KiB (e4m3 entries) max
+    return RSA_OK;
+}
+
+static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes, hipStream_t s) {
+    const bool w64 = k5_runs_w64(D, a.blk);
+    long nblocks;
+    WalkPolicy pol;
+    pol.blk = a.blk;
+    pol.short_grid_text_cap = RSA_TEXT_SPLIT;
+    pol.tail_split = w64 && D == 128;       // (only the 64-row kernel stores a tail piece, and only at head dim 128)
+    pol.tail_beside_text = true;
+    int st = rsa_plan_walk(a, BH, D, pol, tpart_bytes, &nblocks);
+    if (st != RSA_OK || nblocks == 0) return st;
     const size_t lds_bytes = (size_t)4 * 64 * D * 2 + (((size_t)a.NB_total * 2 + 15) & ~(size_t)15);
-    // (64-token blocks: the 32-row kernel, whose 64-key tiles are exactly one block)
-    const bool use64 = a.blk == RSA_BLOCK && ((D == 128 && (g_k5_w64 & 1)) || (D == 64 && (g_k5_w64 & 2)));
-    const int st = use64 ? rsa_launch_bsfwd64(a, dim3((unsigned)nblocks), lds_bytes, D, dtype, s)
-                         : rsa_launch_bsfwd(a, dim3((unsigned)nblocks), lds_bytes, D, dtype, s);
-    if (st != RSA_OK) return st;
-    if (a.tail_n > 0) {
-        const int st2 = launch_tail_combine(a, dtype, s);
-        if (st2 != RSA_OK) return st2;
-    }
-    if (a.tsplit <= 1) return st;
-    return launch_text_combine(a, BH, D, dtype, s);
+    st = w64 ? rsa_launch_bsfwd64(a, dim3((unsigned)nblocks), lds_bytes, D, dtype, s)
+             : rsa_launch_bsfwd(a, dim3((unsigned)nblocks), lds_bytes, D, dtype, s);
+    return st != RSA_OK ? st : rsa_combine_walk(a, D, a.blk, dtype, s);
 }
 
 static void fill_qkv(AttnArgs& a, const rsa_tensor4& q, const rsa_tensor4& k, const rsa_tensor4& v,
@@ -349,7 +320,7 @@ static void fill_qkv(AttnArgs& a, const rsa_tensor4& q, const rsa_tensor4& k, co
     a.out = static_cast<unsigned short*>(out.ptr); a.osb = out.stride_b; a.osh = out.stride_h; a.oss = out.stride_s;
 }
 
-static int check_out(const rsa_out4& o) {
+int rsa_check_out(const rsa_out4& o) {
     if (!o.ptr || (reinterpret_cast<uintptr_t>(o.ptr) & 7)) return RSA_ERR_BAD_ARG;
     if ((o.stride_b % 4) || (o.stride_h % 4) || (o.stride_s % 4)) return RSA_ERR_BAD_ARG;  // 8-byte stores
     return RSA_OK;
@@ -360,7 +331,7 @@ static int block_sparse_fwd_b(const rsa_layout* l, int blk, rsa_tensor4 q, rsa_t
     int st = rsa_check_layout_b(l, blk);
     if (st != RSA_OK) return st;
     if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v)) ||
-        (st = check_out(out)))
+        (st = rsa_check_out(out)))
         return st;
     if (!buf || (l->NBv > 0 && (!buf->cols || !buf->counts))) return RSA_ERR_BAD_ARG;
     if ((buf->R == nullptr) != (buf->comp == nullptr)) return RSA_ERR_BAD_ARG;
@@ -404,7 +375,7 @@ extern "C" int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, i
     if (!cols || !counts) return RSA_ERR_BAD_ARG;
     if (tpart && tpart_bytes == 0) return RSA_ERR_WORKSPACE;
     int st;
-    if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v)) || (st = check_out(out)))
+    if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v)) || (st = rsa_check_out(out)))
         return st;
     AttnArgs a;
     fill_qkv(a, q, k, v, out);
@@ -427,7 +398,7 @@ static int dense_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_tensor4
     if (q_split < 0 || q_split > Sq || kv_split < 0 || kv_split > Sk) return RSA_ERR_BAD_ARG;
     int st;
     if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v)) ||
-        (st = check_out(out)))
+        (st = rsa_check_out(out)))
         return st;
     AttnArgs a;
     fill_qkv(a, q, k, v, out);
@@ -437,7 +408,7 @@ static int dense_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_tensor4
     a.mode = MODE_DENSE; a.H = H; a.Sq = Sq; a.Sk = Sk;
     a.blk = RSA_BLOCK; a.txt0 = 0;
     // head dim 128 through the 64-row kernel: 256-row tiles once there are at least two of them (a shorter call keeps 128-row tiles)
-    a.rows256 = (((D == 128 && (g_k5_w64 & 1)) || (D == 64 && (g_k5_w64 & 2))) && g_k5_rows256 && Sq > 256) ? 1 : 0;
+    a.rows256 = (k5_runs_w64(D, a.blk) && g_k5_rows256 && Sq > 256) ? 1 : 0;
     const int rw = a.rows256 ? 2 * RSA_BLOCK : RSA_BLOCK;
     a.NQB = (Sq + rw - 1) / rw; a.NBv = a.NQB; a.NB_total = (Sk + RSA_BLOCK - 1) / RSA_BLOCK;
     a.kv_valid = Sk; a.kv_text_valid = Sk; a.q_text_end = 0;

@@ -1,6 +1,6 @@
 // K5, fp8 operands: block-sparse flash attention forward on v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3 x e4m3 -> f32, twice the
-// bf16 MFMA rate) with the rectification epilogue fused.  Same work mapping, per-row plan, kept lists and epilogue as
-// the 2-byte kernel (rsa_attn_kernel.hip); the operands are the block-scaled images of rsa_fp8_emit.h.
+// bf16 MFMA rate) with the rectification epilogue fused.  The work mapping and walk plan all K5 kernels share (rsa_attn.h), kept
+// lists and epilogue as the 2-byte kernel (rsa_attn_kernel.hip); the operands are the block-scaled images of rsa_fp8_emit.h.
 //
 // One workgroup (4 waves, two workgroups per CU) owns one 128-row query block, wave w rows 32w..32w+31, "key on the
 // register, query row on the lane":
@@ -45,46 +45,17 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RSA_PV_LIST_WINDOW = 1024;   // entries of the pv form's kept-list window in LDS (a power of two)
 
-struct Attn8Args {
+struct Attn8Args : WalkArgs {
     const uint8_t *q8, *k8, *v8t;  // [BH, S_pad, 128], [BH, S_pad, 128], [BH, S_pad/64, 128, 64]
     const uint32_t* exps;          // [BH, exps_stride] E8M0 block exponents: byte 0 Q, byte 1 K, byte 2 V (rsa_fp8_emit.h)
     int exps_stride;
-    unsigned short* out;
-    long osb, osh, oss;
-    const int32_t* cols;
-    const int32_t* counts;
-    const float* R;
-    const float* comp;
-    int mode, H, Sq, Sk, Sq_pad, Sk_pad;  // padded rows of q8 and of k8 / v8t
-    int NBv, NQB, NB_total;
-    int kv_valid, kv_text_valid, q_text_end;
-    int q_split, kv_split, causal;
-    int n_heavy_pad, NBp, BH;
+    int Sq_pad, Sk_pad;            // padded rows of q8 and of k8 / v8t
     int out_fp16;
-    float* tpart;        // split-KV partials of the text query blocks (layout of rsa_attn.hip's combine kernel) or null
-    int tsplit, tper;
-    unsigned* gsync;     // aligned starts (rsa_attn.h): this launch's counters or null
-    int gsync_gen, gsync_ratio, k5_static;   // (k5_static: set by RSA_LAUNCH_GSYNC for every K5 args struct; only the 64-row 2-byte kernel reads it)
-    int heavy_last;      // the split text-row pieces behind the sparse blocks in the grid
-    int tail_first, tail_n, tail_p;   // tail split (rsa_attn.hip::launch_attn, rsa_attn_kernel64.hip::k5w_map): head dim 128 only
-    float* tail_part;
     // "pv" form (round 5, HYB instances): Q . K^T on the 2-byte operands as they are, only P . V on e4m3
     const unsigned short *q16, *k16;
     long qsb, qsh, qss, ksb, ksh, kss;
     float qk_scale;                   // sm_scale * log2(e) * PMap::U, folded into Q
 };
-
-// rsa_attn.hip: merge of the split-KV partials of the text blocks, and the switch for the split
-int rsa_launch_text_combine(const float* tpart, unsigned short* out, long osb, long osh, long oss, int D, int H, int NBv,
-                            int ntq, int tsplit, int q_text_end, int Sq, int BH, int dtype, hipStream_t s);
-int rsa_text_split_enabled();
-int rsa_text_last_enabled();
-int rsa_text_split_capacity(size_t tpart_bytes, int BH, int ntq, int D);
-bool rsa_tail_fits(size_t tpart_bytes, int BH, int ntq, int D, int tail_n, int tail_p);
-int rsa_plan_tail_split(long n_sparse, long n_heavy_pad, int* tail_first, int* tail_n, int* tail_p);
-int rsa_launch_tail_combine(const float* part, unsigned short* out, long osb, long osh, long oss, int H, int NBv, int NBp,
-                            int tail_first, int tail_n, int tail_p, const float* R, const float* comp, int Sq, int dtype,
-                            hipStream_t s);
 
 namespace {
 
@@ -232,42 +203,9 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
     unsigned* lds_list = reinterpret_cast<unsigned*>(lds + ONES + 64);
 
     const GsyncTicket gs_tk = rsa_gsync_announce(a.gsync, a.gsync_gen);   // aligned starts (rsa_attn.h)
-    // ---------------- work mapping (as rsa_attn_kernel.hip) ----------------
-    int bh, qblk, tsp = 0, tail = -1;
-    {
-        // (the split text-row pieces are the LAST workgroups of the grid -- heavy_last, as in rsa_attn_kernel64.hip: they fill the
-        // slots the last generation of sparse blocks leaves idle; an unsplit text row, one long walk, still comes first)
-        const int n_sparse = a.BH * a.NBp;
-        bool text = a.heavy_last ? (int)blockIdx.x >= n_sparse : (int)blockIdx.x < a.n_heavy_pad;
-        int bid = a.heavy_last ? (int)blockIdx.x - n_sparse : (int)blockIdx.x;        // index among the text pieces
-        int vtail = -1;
-        if (a.tail_n > 0) {    // (sparse blocks first: the tail's pieces sit between the whole walks and the text pieces)
-            const int tail_end = a.tail_first + a.tail_n * a.tail_p;
-            text = (int)blockIdx.x >= tail_end;
-            bid = (int)blockIdx.x - tail_end;
-            if ((int)blockIdx.x >= a.tail_first && !text) {
-                tail = (int)blockIdx.x - a.tail_first;
-                vtail = a.tail_first + tail / a.tail_p;
-                tsp = tail % a.tail_p;
-            }
-        }
-        if (text) {
-            const int ntq = a.NQB - a.NBv;
-            const int per_bh = ntq * a.tsplit;
-            if (ntq <= 0 || bid >= a.BH * per_bh) return;
-            bh = bid / per_bh;
-            const int rem = bid % per_bh;
-            qblk = a.NBv + rem / a.tsplit;
-            tsp = rem % a.tsplit;
-        } else {
-            const int v = vtail >= 0 ? vtail : (a.heavy_last ? (int)blockIdx.x : (int)blockIdx.x - a.n_heavy_pad);
-            bh = v / a.NBp;
-            const int j = v % a.NBp;
-            const int chunk = a.NBp >> 3;
-            qblk = (j & 7) * chunk + (j >> 3);
-            if (qblk >= a.NBv) return;
-        }
-    }
+    // ---------------- work mapping (rsa_attn.h); a text block is a qblk >= NBv ----------------
+    int bh, qblk, tsp, tail;
+    if (rsa_walk_map(a, blockIdx.x, a.NBv, bh, qblk, tsp, tail) == WALK_NONE) return;
     const int b = bh / a.H, h = bh % a.H;
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -282,33 +220,22 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
     bool rectify = false;
     if (a.mode == MODE_SPARSE) {
         if (qblk < a.NBv) {
-            const long rowi = (long)bh * a.NBv + qblk;
-            list = a.cols + rowi * a.NB_total;
-            n_items = a.counts[rowi];
-            if (tail >= 0) {   // this workgroup's part of the kept list (tail split)
-                const int per = (n_items + a.tail_p - 1) / a.tail_p, first = tsp * per;
-                const int left = n_items - first;
-                list += first;
-                n_items = left < 0 ? 0 : (left < per ? left : per);
-            }
+            rsa_walk_list(a, (long)bh * a.NBv + qblk, tail, tsp, list, n_items);
             lo_max = 0; hi_min = hi_max = a.kv_valid;
             rectify = a.R != nullptr;
             hi_r = a.kv_valid; store_r = grow < a.Sq;
         } else {
-            n_items = (a.kv_text_valid + RSA_BLOCK - 1) / RSA_BLOCK;
-            if (a.tsplit > 1) {   // split-KV: this workgroup's slice of the key blocks
-                first_blk = tsp * a.tper;
-                n_items = n_items - first_blk < a.tper ? n_items - first_blk : a.tper;
-                if (n_items < 0) n_items = 0;
-            }
+            rsa_walk_text(a, RSA_BLOCK, tsp, first_blk, n_items);
             lo_max = 0; hi_min = hi_max = a.kv_text_valid;
             hi_r = a.kv_text_valid;
             store_r = grow < a.q_text_end;
             zero_r = !store_r && grow < a.Sq;
         }
     } else {
-        // dense mode: one or two (query rows, key rows) segments; causal = bottom-right aligned inside a segment (as
-        // rsa_attn_kernel.hip: the flash-attn convention of the reference's "flash" mode, attn.py:108-116)
+        // dense mode: rsa_seg_hi / rsa_dense_row / rsa_dense_tile of rsa_attn.h (which states the conventions), written out.  With
+        // the shared functions hipcc loads this kernel's whole argument struct at entry and keeps the epilogue's fields in scalar
+        // registers across the walk (+24 everywhere, 8 to 54 spilled in the pv instances); read in place instead
+        // (rsa_kernargs) it still costs 4 to 9 registers and 0.3 % of the e4m3 K5 (profiles/walk_plan_ab.txt)
         const int row0 = qblk * RSA_BLOCK, row1 = row0 + RSA_BLOCK;
         auto seg_hi = [&](int row) -> int {   // one past the last key row `row` may see
             const bool s1 = row >= a.q_split;
@@ -796,10 +723,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
     const float l_tot = lacc[0];
     if ((a.mode == MODE_SPARSE && a.tsplit > 1 && qblk >= a.NBv) || tail >= 0) {
         // split-KV partial of a text block or of a tail piece (merged by rsa_attn.hip's combine kernels): O in V's units, m, l
-        const int ntq = a.NQB - a.NBv;
-        const int rowb = 32 * wv + r;
-        float* pp = tail >= 0 ? a.tail_part + ((long)tail * RSA_BLOCK + rowb) * (D8 + 2)
-                              : a.tpart + ((((long)bh * ntq + (qblk - a.NBv)) * a.tsplit + tsp) * RSA_BLOCK + rowb) * (D8 + 2);
+        float* pp = rsa_part_of(a, bh, qblk, tsp, tail, 32 * wv + r, D8);
 #pragma unroll
         for (int dt = 0; dt < DT8; ++dt)
 #pragma unroll
@@ -861,39 +785,14 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
 
 int g_fp8_variant = 0;
 int launch_attn8(Attn8Args& a, int BH, int D8, size_t tpart_bytes, hipStream_t s, int hyb = 0) {
-    const int ntq = a.NQB - a.NBv;
-    if (a.tpart && tpart_bytes == 0) return RSA_ERR_WORKSPACE;   // capacity not declared (rsa_buffers.tpart_bytes, 0.5.0)
-    const int n_txt_items = (a.kv_text_valid + RSA_BLOCK - 1) / RSA_BLOCK;
-    a.tsplit = 1; a.tper = n_txt_items;
-    if (a.mode == MODE_SPARSE && ntq > 0 && a.tpart && rsa_text_split_enabled() && n_txt_items >= 32) {
-        const int sp = n_txt_items / 16;
-        int cap = rsa_text_split_capacity(tpart_bytes, BH, ntq, D8);   // (sized for RSA_TEXT_SPLIT = 32 by rsa_buffer_bytes; the 2-byte kernel uses them on short grids)
-        if (cap > 16) cap = 16;
-        a.tsplit = sp > cap ? cap : sp;
-        if (a.tsplit < 2) a.tsplit = 1;
-        a.tper = (n_txt_items + a.tsplit - 1) / a.tsplit;
-    }
-    const int n_heavy = ntq > 0 ? BH * ntq * a.tsplit : 0;
-    a.heavy_last = a.tsplit > 1 && rsa_text_last_enabled();
-    a.BH = BH;
-    a.n_heavy_pad = (n_heavy + 7) & ~7;
-    a.NBp = (a.NBv + 7) & ~7;
-    long nblocks = (long)a.n_heavy_pad + (long)BH * a.NBp;
-    a.tail_first = a.tail_n = a.tail_p = 0; a.tail_part = nullptr;
-    // (as rsa_attn.hip::launch_attn, but only for layouts without text rows: with this kernel's shorter lives and two waves per
-    // SIMD the split measured +1.6 % on Wan2.2-TI2V and -2.3 % at 3 heads of the HunyuanVideo shape, where the text pieces end the
-    // launch either way: profiles/r04_k5_tail_split.txt)
-    if (D8 == 128 && a.mode == MODE_SPARSE && a.tpart && n_heavy == 0 &&
-        rsa_plan_tail_split((long)BH * a.NBp, a.n_heavy_pad, &a.tail_first, &a.tail_n, &a.tail_p) &&
-        !rsa_tail_fits(tpart_bytes, BH, ntq, D8, a.tail_n, a.tail_p))
-        a.tail_first = a.tail_n = a.tail_p = 0;
-    if (a.tail_n > 0) {
-        a.tail_part = a.tpart + (long)BH * ntq * RSA_TEXT_SPLIT * RSA_BLOCK * (D8 + 2);
-        nblocks = (long)a.tail_first + (long)a.tail_n * a.tail_p + a.n_heavy_pad;
-    }
-    if (nblocks <= 0) return RSA_OK;
-    if (nblocks > 0x7FFFFFFF) return RSA_ERR_UNSUPPORTED;
-    if (a.NB_total > 8192) return RSA_ERR_UNSUPPORTED;
+    long nblocks;
+    WalkPolicy pol;
+    pol.blk = RSA_BLOCK;
+    pol.short_grid_text_cap = 16;
+    pol.tail_split = D8 == 128;
+    pol.tail_beside_text = false;           // (measured: rsa_plan_walk)
+    int st = rsa_plan_walk(a, BH, D8, pol, tpart_bytes, &nblocks);
+    if (st != RSA_OK || nblocks == 0) return st;
     // pv form: a K row is addressed as a 32-bit byte offset from its head's base (the LDS-DMA's vector offset): refuse spans the
     // offset cannot reach instead of reading wrapped addresses (a [B,S,H,D]-strided K at 6 144 B per row wraps near 700 k keys;
     // a head-contiguous K at 256 B per row reaches 16 M).  The 2-byte and e4m3 kernels walk a 64-bit scalar base instead.
@@ -940,22 +839,8 @@ int launch_attn8(Attn8Args& a, int BH, int D8, size_t tpart_bytes, hipStream_t s
             default: RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<15>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_bytes, s);
         }
     }
-    const int st = rsa_launch_status();
-    if (st != RSA_OK) return st;
-    if (a.tail_n > 0) {
-        const int st2 = rsa_launch_tail_combine(a.tail_part, a.out, a.osb, a.osh, a.oss, a.H, a.NBv, a.NBp, a.tail_first, a.tail_n,
-                                                a.tail_p, a.R, a.comp, a.Sq, a.out_fp16 ? RSA_FP16 : RSA_BF16, s);
-        if (st2 != RSA_OK) return st2;
-    }
-    if (a.tsplit <= 1) return st;
-    return rsa_launch_text_combine(a.tpart, a.out, a.osb, a.osh, a.oss, D8, a.H, a.NBv, ntq, a.tsplit, a.q_text_end, a.Sq,
-                                   BH, a.out_fp16 ? RSA_FP16 : RSA_BF16, s);
-}
-
-int check_out8(const rsa_out4& o) {
-    if (!o.ptr || (reinterpret_cast<uintptr_t>(o.ptr) & 7)) return RSA_ERR_BAD_ARG;
-    if ((o.stride_b % 4) || (o.stride_h % 4) || (o.stride_s % 4)) return RSA_ERR_BAD_ARG;
-    return RSA_OK;
+    st = rsa_launch_status();
+    return st != RSA_OK ? st : rsa_combine_walk(a, D8, RSA_BLOCK, a.out_fp16 ? RSA_FP16 : RSA_BF16, s);
 }
 
 }  // namespace
@@ -968,7 +853,7 @@ extern "C" int rsa_block_sparse_fwd_fp8(const rsa_layout* l, const rsa_fp8_opera
     if (st != RSA_OK) return st;
     if (l->D != 128 && l->D != 64) return RSA_ERR_UNSUPPORTED;
     if (!ops || !ops->q8 || !ops->k8 || !ops->v8t || !ops->scales) return RSA_ERR_BAD_ARG;
-    if ((st = check_out8(out))) return st;
+    if ((st = rsa_check_out(out))) return st;
     if (!buf || (l->NBv > 0 && (!buf->cols || !buf->counts))) return RSA_ERR_BAD_ARG;
     if ((buf->R == nullptr) != (buf->comp == nullptr)) return RSA_ERR_BAD_ARG;
     Attn8Args a;
@@ -994,7 +879,7 @@ extern "C" int rsa_block_sparse_fwd_fp8pv(const rsa_layout* l, rsa_tensor4 q, rs
     if (st != RSA_OK) return st;
     if (l->D != 128 && l->D != 64) return RSA_ERR_UNSUPPORTED;
     if (!ops || !ops->v8t || !ops->scales) return RSA_ERR_BAD_ARG;
-    if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = check_out8(out))) return st;
+    if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_out(out))) return st;
     if (!buf || (l->NBv > 0 && (!buf->cols || !buf->counts))) return RSA_ERR_BAD_ARG;
     if ((buf->R == nullptr) != (buf->comp == nullptr)) return RSA_ERR_BAD_ARG;
     Attn8Args a;
@@ -1059,7 +944,7 @@ static int dense_fwd_fp8(int B, int H, int Sq, int Sk, int D, int dtype, rsa_ten
     if (q_split < 0 || q_split > Sq || kv_split < 0 || kv_split > Sk) return RSA_ERR_BAD_ARG;
     int st;
     if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v)) ||
-        (st = check_out8(out)))
+        (st = rsa_check_out(out)))
         return st;
     rsa_fp8_operands ops;
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -106,7 +106,8 @@ constexpr int k5_product_form(int D) { return D == 128 ? 2 : 1; }
 // -inf leaves the running maximum alone), so every row gets the bytes its own list would give.  Dense text rows: 128-row units
 // from row NBv * 64 on (a.txt0).
 template <int D, typename Tag, bool WIDE, int BLK = 128>
-__global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
+    const AttnArgs& a = rsa_kernargs<AttnArgs>();
     constexpr int FORM = k5_product_form(D);
     constexpr int NW = 4;                   // 4 waves x 32 query rows
     constexpr int KS = D / 16;
@@ -121,28 +122,13 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
 
     const int work = blockIdx.x;
     const GsyncTicket gs_tk = rsa_gsync_announce(a.gsync, a.gsync_gen);   // aligned starts (rsa_attn.h)
-    // ---------------- work mapping: dense text-row blocks first, then the sparse blocks chunked per XCD ----------------
-    int bh, qblk, tsp = 0;   // tsp: which part of a text block's key range this workgroup walks
-    // (the split text-row pieces are the LAST workgroups of the grid -- a.heavy_last, as in rsa_attn_kernel64.hip)
-    const int n_sparse = a.BH * a.NBp;
-    const bool text = a.heavy_last ? work >= n_sparse : work < a.n_heavy_pad;
-    if (text) {
-        const int wh = a.heavy_last ? work - n_sparse : work;
-        const int ntq = a.NQB - a.NBv;
-        const int per_bh = ntq * a.tsplit;      // text blocks x key-range splits (tsplit = 1: no split)
-        if (ntq <= 0 || wh >= a.BH * per_bh) return;
-        bh = wh / per_bh;
-        const int rem = wh % per_bh;
-        qblk = a.NBv + rem / a.tsplit;
-        tsp = rem % a.tsplit;
-    } else {
-        const int v = a.heavy_last ? work : work - a.n_heavy_pad;
-        bh = v / a.NBp;
-        const int j = v % a.NBp;
-        const int chunk = a.NBp >> 3;
-        qblk = (j & 7) * chunk + (j >> 3);
-        if (qblk >= (BLK == 64 ? (a.NBv + 1) >> 1 : a.NBv)) return;
-    }
+    // ---------------- work mapping (rsa_attn.h) ----------------
+    // qblk: the query block, at BLK 64 the PAIR of query blocks; tsp: which part of a text block's key range this workgroup walks.
+    // `tail` is ignored: this kernel has no partial store for a tail piece, and the host plans a tail split for the kernels that have
+    int bh, qblk, tsp, tail;
+    const int walk = rsa_walk_map(a, work, BLK == 64 ? (a.NBv + 1) >> 1 : a.NBv, bh, qblk, tsp, tail);
+    if (walk == WALK_NONE) return;
+    const bool text = walk == WALK_TEXT;
     const int b = bh / a.H, h = bh % a.H;
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -159,57 +145,21 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     bool rectify = false;
     if (a.mode == MODE_SPARSE) {
         if (BLK == 64 ? !text : qblk < a.NBv) {
-            const long rowi = (long)bh * a.NBv + (BLK == 64 ? 2 * qblk : qblk);
-            list = a.cols + rowi * a.NB_total;
-            n_items = a.counts[rowi];
+            rsa_walk_list(a, (long)bh * a.NBv + (BLK == 64 ? 2 * qblk : qblk), -1, 0, list, n_items);
             lo_max = 0; hi_min = hi_max = a.kv_valid;
             rectify = a.R != nullptr;
             hi_r = a.kv_valid; store_r = grow < a.Sq && (BLK == 128 || qw < a.NBv);
         } else {
-            n_items = (a.kv_text_valid + BLK - 1) / BLK;
-            if (a.tsplit > 1) {   // split-KV: this workgroup's slice of the key blocks
-                first_blk = tsp * a.tper;
-                n_items = n_items - first_blk < a.tper ? n_items - first_blk : a.tper;
-                if (n_items < 0) n_items = 0;
-            }
+            rsa_walk_text(a, BLK, tsp, first_blk, n_items);
             lo_max = 0; hi_min = hi_max = a.kv_text_valid;
             hi_r = a.kv_text_valid;
             store_r = grow < a.q_text_end;
             zero_r = !store_r && grow < a.Sq;
         }
     } else {
-        // dense mode: one or two (query rows, key rows) segments (attn.py:107-120); causal = bottom-right aligned inside a
-        // segment (flash-attn's convention; equal to the top-left form of the reference's "torch" / "vanilla" modes,
-        // attn.py:101-106 / :129-133, whenever a segment has as many keys as rows -- the only case the Python side lets
-        // through.  The reference's "flash" mode never passes `causal` on, attn.py:107-116, and neither does attn.py here)
-        const int row0 = qblk * 128, row1 = row0 + 128;
-        auto seg_hi = [&](int row) -> int {   // one past the last key row `row` may see
-            const bool s1 = row >= a.q_split;
-            const int lo = s1 ? a.kv_split : 0, hi = s1 ? a.Sk : a.kv_split;
-            if (!a.causal) return hi;
-            const int rows = s1 ? a.Sq - a.q_split : a.q_split, rin = row - (s1 ? a.q_split : 0);
-            const int lim = lo + rin + 1 + ((hi - lo) - rows);
-            return lim < lo ? lo : (lim < hi ? lim : hi);
-        };
-        lo_r = grow < a.q_split ? 0 : a.kv_split;
-        hi_r = seg_hi(grow < a.Sq ? grow : a.Sq - 1);
+        rsa_dense_row(a, grow, lo_r, hi_r);
         store_r = grow < a.Sq;
-        int lo_min;
-        const int rlast = (row1 <= a.Sq ? row1 : a.Sq) - 1;   // last real row of the block
-        if (row1 <= a.q_split) { lo_min = 0; lo_max = 0; }
-        else if (row0 >= a.q_split) { lo_min = lo_max = a.kv_split; }
-        else { lo_min = 0; lo_max = a.kv_split; }
-        // seg_hi grows with the row inside a segment: extremes of the block sit at its first / last row of each segment
-        hi_min = seg_hi(row0);
-        hi_max = seg_hi(rlast);
-        if (row0 < a.q_split && rlast >= a.q_split) {   // the block straddles the two segments
-            const int h0 = seg_hi(a.q_split - 1), h1 = seg_hi(a.q_split);
-            hi_min = hi_min < h1 ? hi_min : h1;
-            hi_max = hi_max > h0 ? hi_max : h0;
-        }
-        first_blk = lo_min / RSA_BLOCK;
-        n_items = (hi_max + RSA_BLOCK - 1) / RSA_BLOCK - first_blk;
-        if (hi_max <= lo_min) n_items = 0;
+        rsa_dense_tile(a, qblk * 128, 128, lo_max, hi_min, hi_max, first_blk, n_items);
     }
     n_items = __builtin_amdgcn_readfirstlane(n_items);
     const bool use_list = list != nullptr;
@@ -566,9 +516,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs a) {
     if (a.mode == MODE_SPARSE && a.tsplit > 1 && (BLK == 64 ? text : qblk >= a.NBv)) {
         // split-KV partial of a text block: unnormalised O (fp32), m (log2 domain) and l per row; the combine
         // kernel (rsa_attn.hip) merges the tsplit parts
-        const int ntq = a.NQB - a.NBv;
-        const int rowb = 32 * wv + r;
-        float* pp = a.tpart + ((((long)bh * ntq + (qblk - a.NBv)) * a.tsplit + tsp) * RSA_BLOCK + rowb) * (D + 2);
+        float* pp = rsa_part_of(a, bh, qblk, tsp, -1, 32 * wv + r, D);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
 #pragma unroll

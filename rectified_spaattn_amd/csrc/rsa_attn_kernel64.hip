@@ -1,6 +1,6 @@
 // K5, 64-rows-per-wave form: block-sparse flash attention forward for gfx950 with the rectification
-// epilogue fused -- same semantics, work mapping, per-row plan and epilogue as bsfwd_kernel (rsa_attn_kernel.hip; the
-// reference kernel it follows: rectified_hunyuan_attn.py:15-105), different occupancy model:
+// epilogue fused -- same semantics and epilogue as bsfwd_kernel (rsa_attn_kernel.hip; the reference kernel it follows:
+// rectified_hunyuan_attn.py:15-105), the work mapping and walk plan all K5 kernels share (rsa_attn.h), different occupancy model:
 //
 //   one workgroup = 2 waves = one 128-row query block, wave w owns rows 64w .. 64w+63 as two 32-row halves and the WHOLE
 //   512-entry register file of its SIMD (one wave per SIMD; two workgroups per CU).  O (128 registers) and the Q
@@ -92,51 +92,6 @@ __device__ __forceinline__ f32x16 k5w_oread() {
     return t;
 }
 
-// blockIdx -> (batch*head, query block, key-range part of a split text block); false = padding workgroup
-// Work mapping.  Sparse query blocks: workgroup v of a head's NBp (a multiple of 8) goes to XCD v & 7, which takes the
-// (v & 7)-th contiguous eighth of the head's query blocks.  The dense text-row blocks come FIRST when each is one long walk
-// over every key block (no split-KV buffer: the longest work first), and LAST when they are split into pieces shorter than a
-// sparse walk (tsplit > 1): with aligned starts the launch advances in generations of 8 x 64 workgroups, and the short
-// pieces then fill the slots the last, partial generation leaves idle instead of adding a generation of their own.
-// Tail split (a.tail_n > 0; sparse blocks first): the sparse blocks from index tail_first on -- the last, partial generation --
-// are walked by tail_p workgroups each (piece i of the region = block tail_first + i / tail_p, part i % tail_p of its kept
-// list), which together fill the slots that generation would leave idle; tail >= 0 tells the caller (the piece's index).
-__device__ __forceinline__ bool k5w_map(const AttnArgs& a, int work, int& bh, int& qblk, int& tsp, int& tail) {
-    tsp = 0;
-    tail = -1;
-    const int n_sparse = a.BH * a.NBp;
-    const bool heavy_last = a.heavy_last != 0;
-    int wh = heavy_last ? work - n_sparse : work;                 // index among the text-row pieces
-    int v = heavy_last ? work : work - a.n_heavy_pad;             // index among the sparse blocks
-    bool text = heavy_last ? work >= n_sparse : work < a.n_heavy_pad;
-    if (a.tail_n > 0) {
-        const int tail_end = a.tail_first + a.tail_n * a.tail_p;
-        text = work >= tail_end;
-        wh = work - tail_end;
-        if (work >= a.tail_first && !text) {
-            tail = work - a.tail_first;
-            v = a.tail_first + tail / a.tail_p;
-            tsp = tail % a.tail_p;
-        }
-    }
-    if (text) {
-        const int ntq = a.NQB - a.NBv;
-        const int per_bh = ntq * a.tsplit;      // text blocks x key-range splits (tsplit = 1: no split)
-        if (ntq <= 0 || wh >= a.BH * per_bh) return false;
-        bh = wh / per_bh;
-        const int rem = wh % per_bh;
-        qblk = a.NBv + rem / a.tsplit;
-        tsp = rem % a.tsplit;
-    } else {
-        bh = v / a.NBp;
-        const int j = v % a.NBp;
-        const int chunk = a.NBp >> 3;
-        qblk = (j & 7) * chunk + (j >> 3);
-        if (qblk >= a.NBv) return false;
-    }
-    return true;
-}
-
 // WIDE: 16-byte output stores after a permlane32_swap regroup (needs 16-byte aligned output rows), else 8-byte stores.
 // NW (round 6): waves per workgroup.  2 = one 128-row query block (every sparse call: the mask's granularity).  4 = a 256-ROW
 // tile of a DENSE call (rsa_dense_fwd / _causal_: all rows walk the same keys): four waves, one per SIMD, ONE workgroup per CU on ONE
@@ -146,7 +101,8 @@ __device__ __forceinline__ bool k5w_map(const AttnArgs& a, int work, int& bh, in
 // D (round 6): head dim 128 or 64 (CogVideoX).  At 64 a sub-step is 8 + 8 MFMAs against the same softmax, a half-tile 4 KiB = four
 // LDS-DMA pieces of 8 rows (two per wave); same register map in the arch file, O in a[0:63], Q in a[64:95].
 template <typename Tag, bool WIDE, int NW = 2, int D = 128>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) void bsfwd64_kernel(AttnArgs a) {
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) void bsfwd64_kernel(AttnArgs) {
+    const AttnArgs& a = rsa_kernargs<AttnArgs>();
     constexpr int RW = 64 * NW;             // query rows per workgroup: NW waves x 64 rows
     constexpr int NPIECE = 32 * D * 2 / 1024;   // 1-KiB pieces of a 32-key half-tile: 8 (4 rows each) / 4 (8 rows each)
     constexpr int NPW = NPIECE / NW;        // ... of them each wave stages
@@ -164,9 +120,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
 
     const GsyncTicket gs_tk = rsa_gsync_announce(a.gsync, a.gsync_gen);   // aligned starts (rsa_attn.h)
 
-    // ---------------- work mapping: dense text-row blocks first, then the sparse blocks chunked per XCD ----------------
+    // ---------------- work mapping (rsa_attn.h); a text block is a qblk >= NBv ----------------
     int bh, qblk, tsp, tail;
-    if (!k5w_map(a, blockIdx.x, bh, qblk, tsp, tail)) return;
+    if (rsa_walk_map(a, blockIdx.x, a.NBv, bh, qblk, tsp, tail) == WALK_NONE) return;
     const int b = bh / a.H, h = bh % a.H;
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -181,59 +137,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     const int32_t* list = nullptr;
     if (a.mode == MODE_SPARSE) {
         if (qblk < a.NBv) {
-            const long rowi = (long)bh * a.NBv + qblk;
-            list = a.cols + rowi * a.NB_total;
-            n_items = a.counts[rowi];
-            if (tail >= 0) {   // this workgroup's part of the kept list (tail split)
-                const int per = (n_items + a.tail_p - 1) / a.tail_p, first = tsp * per;
-                const int left = n_items - first;
-                list += first;
-                n_items = left < 0 ? 0 : (left < per ? left : per);
-            }
+            rsa_walk_list(a, (long)bh * a.NBv + qblk, tail, tsp, list, n_items);
             lo_max = 0; hi_min = hi_max = a.kv_valid;
             hi_r[0] = hi_r[1] = a.kv_valid;
         } else {
-            n_items = (a.kv_text_valid + RSA_BLOCK - 1) / RSA_BLOCK;
-            if (a.tsplit > 1) {   // split-KV: this workgroup's slice of the key blocks
-                first_blk = tsp * a.tper;
-                n_items = n_items - first_blk < a.tper ? n_items - first_blk : a.tper;
-                if (n_items < 0) n_items = 0;
-            }
+            rsa_walk_text(a, RSA_BLOCK, tsp, first_blk, n_items);
             lo_max = 0; hi_min = hi_max = a.kv_text_valid;
             hi_r[0] = hi_r[1] = a.kv_text_valid;
         }
     } else {
-        // dense mode: one or two (query rows, key rows) segments; causal = bottom-right aligned inside a segment (see
-        // rsa_attn_kernel.hip for the conventions)
-        const int row0 = qblk * RW, row1 = row0 + RW;
-        auto seg_hi = [&](int row) -> int {
-            const bool s1 = row >= a.q_split;
-            const int lo = s1 ? a.kv_split : 0, hi = s1 ? a.Sk : a.kv_split;
-            if (!a.causal) return hi;
-            const int rows = s1 ? a.Sq - a.q_split : a.q_split, rin = row - (s1 ? a.q_split : 0);
-            const int lim = lo + rin + 1 + ((hi - lo) - rows);
-            return lim < lo ? lo : (lim < hi ? lim : hi);
-        };
 #pragma unroll
-        for (int x = 0; x < 2; ++x) {
-            lo_r[x] = grow[x] < a.q_split ? 0 : a.kv_split;
-            hi_r[x] = seg_hi(grow[x] < a.Sq ? grow[x] : a.Sq - 1);
-        }
-        int lo_min;
-        const int rlast = (row1 <= a.Sq ? row1 : a.Sq) - 1;
-        if (row1 <= a.q_split) { lo_min = 0; lo_max = 0; }
-        else if (row0 >= a.q_split) { lo_min = lo_max = a.kv_split; }
-        else { lo_min = 0; lo_max = a.kv_split; }
-        hi_min = seg_hi(row0);
-        hi_max = seg_hi(rlast);
-        if (row0 < a.q_split && rlast >= a.q_split) {
-            const int h0 = seg_hi(a.q_split - 1), h1 = seg_hi(a.q_split);
-            hi_min = hi_min < h1 ? hi_min : h1;
-            hi_max = hi_max > h0 ? hi_max : h0;
-        }
-        first_blk = lo_min / RSA_BLOCK;
-        n_items = (hi_max + RSA_BLOCK - 1) / RSA_BLOCK - first_blk;
-        if (hi_max <= lo_min) n_items = 0;
+        for (int x = 0; x < 2; ++x) rsa_dense_row(a, grow[x], lo_r[x], hi_r[x]);
+        rsa_dense_tile(a, qblk * RW, RW, lo_max, hi_min, hi_max, first_blk, n_items);
     }
     n_items = __builtin_amdgcn_readfirstlane(n_items);
     // the kept list (sparse visual blocks) or the plain block range (text rows, dense mode) as u16 entries in LDS: the walk
@@ -514,14 +429,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     asm volatile("s_nop 11" ::: "memory");   // (the last block's last MFMA -> the reads of O below)
     // Everything the epilogue needs from the arguments is read AGAIN here, through a pointer the compiler cannot see through
     // (kept live in scalar registers across the walk it costs 25 of them).
-    const AttnArgs* ep = (const AttnArgs*)(const void*)__builtin_amdgcn_kernarg_segment_ptr();
+    const AttnArgs* ep = &rsa_kernargs<AttnArgs>();
     asm volatile("" : "+s"(ep));
     const AttnArgs& e = *ep;
     int bh2, qblk2, tsp2, tail2;
     {
         int work2 = blockIdx.x;
         asm volatile("" : "+s"(work2));
-        k5w_map(e, work2, bh2, qblk2, tsp2, tail2);
+        rsa_walk_map(e, work2, e.NBv, bh2, qblk2, tsp2, tail2);
     }
     const int b2 = bh2 / e.H, h2 = bh2 % e.H;
     const bool partial = (e.mode == MODE_SPARSE && e.tsplit > 1 && qblk2 >= e.NBv) || tail2 >= 0;
@@ -553,10 +468,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
         if (partial) {
             // split-KV partial of a text block or of a tail piece: unnormalised O (fp32), m (log2 domain) and l per row (merged by
             // text_combine_kernel / tail_combine_kernel, rsa_attn.hip)
-            const int ntq = e.NQB - e.NBv;
-            const int rowb = 64 * wv + 32 * x + r;
-            float* pp = tail2 >= 0 ? e.tail_part + ((long)tail2 * RSA_BLOCK + rowb) * (D + 2)
-                                   : e.tpart + ((((long)bh2 * ntq + (qblk2 - e.NBv)) * e.tsplit + tsp2) * RSA_BLOCK + rowb) * (D + 2);
+            float* pp = rsa_part_of(e, bh2, qblk2, tsp2, tail2, 64 * wv + 32 * x + r, D);
             auto put = [&](int dt, const f32x16& o) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {

@@ -64,6 +64,10 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// Split-KV partials (tpart, tail_part): piece after piece of 128 rows, a row = D unnormalised O values (fp32), then the running
+// maximum m (log2 domain) and the row sum l.  Offset of row `row` of piece `piece`, in floats:
+__host__ __device__ __forceinline__ long rsa_part_row(long piece, int row, int D) { return (piece * RSA_BLOCK + row) * (D + 2); }
+
 // blk: tokens per block (RSA_BLOCK, or 64 through the _ex entry points of 0.6.1)
 static inline int rsa_check_layout_b(const rsa_layout* l, int blk) {
     if (blk != 64 && blk != 128) return RSA_ERR_UNSUPPORTED;

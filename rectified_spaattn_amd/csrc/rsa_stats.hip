@@ -1153,7 +1153,7 @@ __global__ void gapr_compare_kernel(const float* qbar, const float* aq, const fl
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // (blk = 64: the text / tail partials keep their 128-row pieces; NB_total - NBv counts 64-token blocks, at least as many
-// pieces as the 128-row text units K5 walks at that block size -- rsa_attn.hip::launch_attn)
+// pieces as the 128-row text units K5 walks at that block size -- rsa_attn.hip::rsa_plan_walk)
 static int buffer_bytes_b(const rsa_layout* l, int blk, size_t sizes[RSA_NUM_BUFFERS], size_t* total) {
     int st = rsa_check_layout_b(l, blk);
     if (st != RSA_OK) return st;
@@ -1164,7 +1164,7 @@ static int buffer_bytes_b(const rsa_layout* l, int blk, size_t sizes[RSA_NUM_BUF
         BH * NBv * D * 4, BH * NBv * D * 4, BH * NBv * D * 4, BH * NBv * D * 4, BH * NB * D * 4,
         BH * NBv * NS * 4, BH * NBv * NBv,  BH * NBv * L * 4, BH * NBv * L * 4, BH * NBv * 4,
         BH * NBv * D * 4,  BH * NBv * NW * 4, BH * NBv * NB * 4, BH * NBv * 4,
-        (BH * (NB - NBv) * RSA_TEXT_SPLIT + RSA_TAIL_PIECES) * 128 * (D + 2) * 4};
+        (size_t)rsa_part_row((long)(BH * (NB - NBv) * RSA_TEXT_SPLIT + RSA_TAIL_PIECES), 0, (int)D) * sizeof(float)};
     size_t tot = 0;
     for (int i = 0; i < RSA_NUM_BUFFERS; ++i) {
         sizes[i] = s[i];

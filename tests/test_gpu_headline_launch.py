@@ -1,7 +1,7 @@
 """K5 at the SIZE OF THE HEADLINE LAUNCH (round 6; VERDICT r5 "Missing 2").  The bench times one launch over all 24 heads x 902
 blocks of the HunyuanVideo 720p shape, while every other full-size parity test runs 2-4 heads -- and the 64-row kernel plans
-its work mapping, its aligned starts and its tail split from the size of the launch (rsa_attn_kernel64.hip::k5w_map,
-rsa_attn.hip::launch_attn).  Here the launch itself is checked:
+its work mapping, its aligned starts and its tail split from the size of the launch (rsa_attn.h::rsa_walk_map,
+rsa_attn.hip::rsa_plan_walk).  Here the launch itself is checked:
 
   * 24 heads, regime R2 (top_k 90, no neighbours): aligned starts on / off give the same BYTES; sampled query blocks and text
     rows of three heads agree with the oracle (fp64 dense-masked attention over the device's own kept rows, x R + comp) and

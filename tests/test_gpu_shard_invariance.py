@@ -1,7 +1,7 @@
 """Head sharding: a rank that holds heads [h0, h0+n) computes, for those heads, exactly the unsharded call's
 bitmask, kept lists, R and compensation -- always (no statistic crosses heads: softmax, sort and the cumulative rule are per
 (b, h, query block); top_k, p and the neighbour matrix are head-independent) -- and exactly its O wherever K5 planned the row's
-walk the same way in both launches.  Two plans depend on the size of the launch (rsa_attn.hip::launch_attn): the tail split
+walk the same way in both launches.  Two plans depend on the size of the launch (rsa_attn.hip::rsa_plan_walk): the tail split
 (which query blocks of the last, partial generation are walked in pieces) and the piece count of the dense text rows (32 on
 short grids, 16 otherwise); the rows they touch agree within rounding.  `parallel.set_shard_invariant(True)` (C:
 rsa_set_shard_invariant) plans both per head: byte-identical O everywhere, which the second test pins at a shape where one
@@ -40,7 +40,7 @@ def test_head_shard_equals_full_run(layout):
 
 
 def _tail_blocks(H, spec):
-    """[H, NBv] bool: the query blocks a launch of H heads walks in pieces (the plan of rsa_plan_tail_split)."""
+    """[H, NBv] bool: the query blocks a launch of H heads walks in pieces (the tail split of rsa_attn.hip::rsa_plan_walk)."""
     NBp = (spec.NBv + 7) // 8 * 8
     n_sparse = H * NBp
     full, T = divmod(n_sparse, 512)

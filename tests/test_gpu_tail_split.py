@@ -1,4 +1,4 @@
-"""Tail split of the 64-row K5 (rsa_attn.hip::launch_attn, tuning key k5_tail_split; round 4): when the last generation of 512
+"""Tail split of the 64-row K5 (rsa_attn.hip::rsa_plan_walk, tuning key k5_tail_split; round 4): when the last generation of 512
 workgroups is less than half full, the walks of its query blocks are split over the idle slots (split-KV partials + a combine pass
 that also rectifies).  The split blocks' accumulation order changes, so they agree with the unsplit kernel within rounding, not
 byte for byte; every other block stays byte-identical; everything agrees with the oracle within the operator's tolerance."""
