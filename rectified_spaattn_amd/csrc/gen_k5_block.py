@@ -16,14 +16,14 @@ MFMA behind counted lgkmcnt waits, and the softmax's vector instructions are dea
 Registers are pinned through physical-register constraints ("{v[96:111]}"); the operand lists are generated with the
 streams (RSA_K5_OPS*), so the C++ side cannot drift from the register map.
 
-Two forms are generated per (D, dtype, K/V slot parity, sub-step parity):
-  * RSA_K5_BLOCKN_*: the product.  The kernel runs at the board's power cap (1.39 kW, 1.72 GHz under this loop,
+One block is generated per (D, dtype, K/V slot parity, sub-step parity); its form is a function of the head dim (negm_form):
+  * RSA_K5_BLOCKN_128_*: head dim 128.  The kernel runs at the board's power cap (1.39 kW, 1.72 GHz under this loop,
     tools/clock_probe.py), so what it saves is instructions, not stalls: starting the score chain from -m removes the 16
     subtractions of a sub-step (-3.7 % time), the row maximum as two chains placed as soon as S_nxt is complete another
     0.7 % (profiles/r03_k5_block.md).  Nothing pads the statement behind its last MFMA: the only vector code that touches O
     outside the blocks (the rare rescale, the epilogue) carries the 12 wait states itself.
-  * RSA_K5_BLOCK_*: round 2's compiled block's arithmetic operation for operation (S, then S - m by v_sub): the product at
-    head dim 64, where it measures 4 % faster than the -m form.
+  * RSA_K5_BLOCK_64_*: head dim 64.  Round 2's compiled block's arithmetic operation for operation (S, then S - m by v_sub),
+    which measures 4 % faster there than the -m form, with the row sums on the matrix pipe (rsm_form).
 
 Measured and dropped: the sub-step's LDS-DMA pieces spread over the MFMA shadows (16.96 vs 16.42 ms: a piece stalls its wave
 ~70 cycles wherever it is issued, and inside the block that stall stops the wave's MFMA stream), 16x16x32 MFMAs (timing
@@ -39,7 +39,7 @@ COST = dict(sub=4, exp=8, cvt=4, cvt8=5, add=4, max=4, mov=4, nop=8, swap=4)
 
 
 class Map:
-    def __init__(self, D, negm):
+    def __init__(self, D):
         self.D, self.KS, self.DT = D, D // 16, D // 32
         r = 0
         self.O = r; r += 16 * self.DT
@@ -47,7 +47,7 @@ class Map:
         self.SA = r; r += 16
         self.SB = r; r += 16
         self.NM = r
-        if negm: r += 16         # the reference maximum, negated, in all 16 registers: C operand of the first QK^T MFMA
+        if negm_form(D): r += 16         # the reference maximum, negated, in all 16 registers: C operand of the first QK^T MFMA
         self.tmp0 = r
         self.P = r; r += 8
         self.KF = r; r += 4 * AHEAD
@@ -59,7 +59,7 @@ class Map:
         r = (r + 3) & ~3
         self.KA = r; r += self.KS
         self.VA = r; r += 2 * self.DT
-        self.RSM = rsm_form(D, negm)
+        self.RSM = rsm_form(D)
         if self.RSM:             # row sums on the matrix pipe (head dim 64, round 5): l in four registers, the ones operand
             r = (r + 3) & ~3
             self.LACC = r; r += 4
@@ -67,8 +67,13 @@ class Map:
         self.end = r
 
 
-def rsm_form(D, negm):
-    """Head dim 64 (both forms): 8 MFMAs per sub-step against the same softmax make the wave vector-bound
+def negm_form(D):
+    """Head dim 128: the score chain starts from -m (no subtraction in the softmax).  Head dim 64: the classic form, S then S - m."""
+    return D == 128
+
+
+def rsm_form(D):
+    """Head dim 64: 8 MFMAs per sub-step against the same softmax make the wave vector-bound
     (profiles/r05_d64_experiments.txt: without the vector work -29 %), so the 16 row-sum additions go to the matrix pipe as two
     v_mfma_f32_16x16x32 (ones . P^T, 4 passes each): l = the row sum of the ROUNDED P, complete over both lane halves."""
     return D == 64
@@ -78,9 +83,10 @@ def vr(a, n=1):
     return f"v{a}" if n == 1 else f"v[{a}:{a + n - 1}]"
 
 
-def gen_block(D, dt, VS, SUB, negm):
+def gen_block(D, dt, VS, SUB):
     """The asm lines of one block variant."""
-    m = Map(D, negm)
+    m = Map(D)
+    negm = negm_form(D)
     KS, DT = m.KS, m.DT
     mf = "v_mfma_f32_32x32x16_bf16" if dt == "bf16" else "v_mfma_f32_32x32x16_f16"
     cv = "v_cvt_pk_bf16_f32" if dt == "bf16" else "v_cvt_pk_f16_f32"
@@ -211,30 +217,28 @@ def main():
     out = ["// GENERATED by gen_k5_block.py -- do not edit; edit the generator (its docstring says what this is).", "#pragma once", ""]
     for D in (128, 64):
         for dt in ("bf16", "f16"):
-            for negm in (False, True):
-                for VS in (0, 1):
-                    for SUB in (0, 1):
-                        lines, m = gen_block(D, dt, VS, SUB, negm)
-                        out.append(f"#define RSA_K5_BLOCK{'N' if negm else ''}_{D}_{dt.upper()}_V{VS}_S{SUB} \\")
-                        out.append(" \\\n".join(c_string(lines).split("\n")))
-                        out.append("")
+            for VS in (0, 1):
+                for SUB in (0, 1):
+                    lines, m = gen_block(D, dt, VS, SUB)
+                    out.append(f"#define RSA_K5_BLOCK{'N' if negm_form(D) else ''}_{D}_{dt.upper()}_V{VS}_S{SUB} \\")
+                    out.append(" \\\n".join(c_string(lines).split("\n")))
+                    out.append("")
     # operand lists (the constraint strings carry the register map) and the clobbered temporaries
     for D in (128, 64):
-        for negm in (False, True):
-            m = Map(D, negm)
-            outs = [f'"+{{{vr(m.O + 16 * d, 16)}}}"(o[{d}])' for d in range(m.DT)]
-            outs += [f'"+{{{vr(m.SA, 16)}}}"(SA)', f'"+{{{vr(m.SB, 16)}}}"(SB)',
-                     f'"+{{{vr(m.LACC, 4)}}}"(lacc)' if m.RSM else '[l] "+v"(l)', '[mx] "=&v"(mx)']
-            ins = [f'"{{{vr(m.Q + 4 * k, 4)}}}"(q[{k}])' for k in range(m.KS)]
-            ins += [f'"{{{vr(m.NM, 16)}}}"(nm)'] if negm else ['[m] "v"(m)']
-            ins += [f'"{{{vr(m.KA, m.KS)}}}"(ka)', f'"{{{vr(m.VA, 2 * m.DT)}}}"(va)']
-            if m.RSM: ins += [f'"{{{vr(m.ONES, 4)}}}"(onesv)']
-            tag = f"{'N' if negm else ''}_{D}"
-            out.append(f"#define RSA_K5_OPS{tag} : {', '.join(outs)} : {', '.join(ins)}")
-            out.append(f"#define RSA_K5_CLOBBER{tag} " + ", ".join(f'"v{r}"' for r in range(m.tmp0, m.tmp1)))
-            out.append(f"// D = {D}{' (-m form)' if negm else ''}: O v[{m.O}:{m.Q - 1}], Q v[{m.Q}:{m.SA - 1}], SA v[{m.SA}:{m.SA + 15}], "
-                       f"SB v[{m.SB}:{m.SB + 15}], " + (f"-m v[{m.NM}:{m.NM + 15}], " if negm else "")
-                       + f"temporaries v[{m.tmp0}:{m.tmp1 - 1}], K addresses v[{m.KA}:{m.KA + m.KS - 1}], V addresses v[{m.VA}:{m.end - 1}]")
+        m, negm = Map(D), negm_form(D)
+        outs = [f'"+{{{vr(m.O + 16 * d, 16)}}}"(o[{d}])' for d in range(m.DT)]
+        outs += [f'"+{{{vr(m.SA, 16)}}}"(SA)', f'"+{{{vr(m.SB, 16)}}}"(SB)',
+                 f'"+{{{vr(m.LACC, 4)}}}"(lacc)' if m.RSM else '[l] "+v"(l)', '[mx] "=&v"(mx)']
+        ins = [f'"{{{vr(m.Q + 4 * k, 4)}}}"(q[{k}])' for k in range(m.KS)]
+        ins += [f'"{{{vr(m.NM, 16)}}}"(nm)'] if negm else ['[m] "v"(m)']
+        ins += [f'"{{{vr(m.KA, m.KS)}}}"(ka)', f'"{{{vr(m.VA, 2 * m.DT)}}}"(va)']
+        if m.RSM: ins += [f'"{{{vr(m.ONES, 4)}}}"(onesv)']
+        tag = f"{'N' if negm else ''}_{D}"
+        out.append(f"#define RSA_K5_OPS{tag} : {', '.join(outs)} : {', '.join(ins)}")
+        out.append(f"#define RSA_K5_CLOBBER{tag} " + ", ".join(f'"v{r}"' for r in range(m.tmp0, m.tmp1)))
+        out.append(f"// D = {D}{' (-m form)' if negm else ''}: O v[{m.O}:{m.Q - 1}], Q v[{m.Q}:{m.SA - 1}], SA v[{m.SA}:{m.SA + 15}], "
+                   f"SB v[{m.SB}:{m.SB + 15}], " + (f"-m v[{m.NM}:{m.NM + 15}], " if negm else "")
+                   + f"temporaries v[{m.tmp0}:{m.tmp1 - 1}], K addresses v[{m.KA}:{m.KA + m.KS - 1}], V addresses v[{m.VA}:{m.end - 1}]")
     main8(out)
     main8h(out)
     print("\n".join(out))

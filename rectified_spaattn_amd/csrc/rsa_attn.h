@@ -22,15 +22,6 @@ struct Elem<bf16_tag> {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
                                                        c, 0, 0, 0);
     }
-    // D = A.B + C with D and C in DIFFERENT registers (hipcc ties them and copies C first when given the builtin)
-    static __device__ __forceinline__ f32x4 mfma_rowsum(s16x8 a, s16x8 b, f32x4 c) {   // 16 x 16 x 32 (row sums: rsa_attn_kernel.hip)
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x16 mfma_from(s16x8 a, s16x8 b, const f32x16& c) {
-        f32x16 d;
-        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
-        return d;
-    }
     static __device__ __forceinline__ unsigned short from_f32(float f) {
         return __builtin_bit_cast(unsigned short, (__bf16)f);
     }
@@ -46,14 +37,6 @@ struct Elem<fp16_tag> {
     static __device__ __forceinline__ f32x16 mfma(s16x8 a, s16x8 b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
                                                       0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x4 mfma_rowsum(s16x8 a, s16x8 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ f32x16 mfma_from(s16x8 a, s16x8 b, const f32x16& c) {
-        f32x16 d;
-        asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
-        return d;
     }
     static __device__ __forceinline__ unsigned short from_f32(float f) {
         return __builtin_bit_cast(unsigned short, (_Float16)f);
@@ -102,16 +85,16 @@ struct AttnArgs : WalkArgs {
     long qsb, qsh, qss, ksb, ksh, kss, vsb, vsh, vss;
     float qk_scale;
     int rows256;                              // 64-row kernel, dense calls: NQB / NBv count 256-row tiles (four waves per workgroup, one K/V ring)
-    int blk;                                  // tokens per block: 128, or 64 (sparse calls through the _ex entry points: the 32-row kernel's pair walk)
+    int blk;                                  // tokens per block: 128 (the 64-row kernel), or 64 (sparse calls through the _ex entry points: the 32-row kernel)
     int txt0;                                 // blk 64: first text query row (NBv * 64); text units of 128 rows from there
 };
 
 // The kernel's own arguments, read in place: the argument struct must be the kernel's ONLY parameter (it then sits at offset 0
 // of the kernarg segment).  The 64-row and 32-row kernels take their arguments this way, not through the by-value parameter: once
-// the dense plan is the shared functions below, every use of that parameter is a plain field read and hipcc loads the whole
-// struct at the head of the kernel; the fields the epilogue needs then stay live across the walk (10 scalar registers spilled
-// in the 32-row instances at head dim 128).  Through the pointer each field is loaded where it is used, as at every use of a
-// by-value parameter hipcc does not take apart.
+// the walk plan is the shared functions below, every use of that parameter is a plain field read and hipcc loads the whole
+// struct at the head of the kernel; the fields the epilogue needs then stay live across the walk (scalar registers spilled at
+// head dim 128).  Through the pointer each field is loaded where it is used, as at every use of a by-value parameter hipcc
+// does not take apart.
 template <typename A>
 __device__ __forceinline__ const A& rsa_kernargs() {
     return *static_cast<const A*>((const void*)__builtin_amdgcn_kernarg_segment_ptr());
@@ -302,8 +285,8 @@ __device__ __forceinline__ void rsa_gsync_wait(unsigned* gsync, GsyncTicket tk, 
     __syncthreads();
 }
 // host: the counters of one launch (cleared in stream order in front of it) or null.  which: 1 = the 64-row kernel (on by
-// default), 2 = the 32-row and the e4m3 kernels (off by default: with two waves per SIMD they gain nothing from it and lose the
-// wait, profiles/r04_k5_gsync.md) -- bits of the tuning key "k5_gsync"; wg_per_cu = what the runtime says fits
+// default), 2 = the 32-row kernel (64-token blocks) and the e4m3 kernels (off by default: with two waves per SIMD they gain
+// nothing from it and lose the wait, profiles/r04_k5_gsync.md) -- bits of the tuning key "k5_gsync"; wg_per_cu = what the runtime says fits
 // (hipOccupancyMaxActiveBlocksPerMultiprocessor); *gen = workgroups per XCD generation
 unsigned* rsa_gsync_slot(int which, unsigned grid, int wg_per_cu, hipStream_t s, int* gen);
 int rsa_k5_static();      // tuning key "k5_static" (default 1): rsa_attn_kernel64.hip, optimistic static reference

@@ -23,11 +23,7 @@ int rsa_gsync_ratio() { return g_k5_gsync_ratio; }
 static int g_k5_rows256 = 1;    // dense calls at head dim 128: 256-row tiles (0 = 128-row tiles, the sparse calls' form)
 static int g_k5_static = 1;     // 64-row kernel, bf16: optimistic static softmax reference in the steady-state loop (0 = online body only)
 int rsa_k5_static() { return g_k5_static; }
-static int g_k5_gsync = 1;      // aligned starts of the sparse walks (rsa_attn.h): bit 0 = in the 64-row kernel, bit 1 = in the 32-row and e4m3 kernels
-
-static int g_k5_w64 = 3;        // the 64-rows-per-wave kernel (rsa_attn_kernel64.hip): bit 0 = at head dim 128, bit 1 = at head dim 64 (round 6); a clear bit = the 32-row kernel (A/B)
-// does a call run the 64-row kernel?  (64-token blocks: the 32-row kernel, whose 64-key tiles are exactly one block)
-static bool k5_runs_w64(int D, int blk) { return blk == RSA_BLOCK && ((D == 128 && (g_k5_w64 & 1)) || (D == 64 && (g_k5_w64 & 2))); }
+static int g_k5_gsync = 1;      // aligned starts of the sparse walks (rsa_attn.h): bit 0 = in the 64-row kernel, bit 1 = in the 32-row (64-token blocks) and e4m3 kernels
 
 // Tuning / diagnostics hook (not part of the data path).  The switches are process-global, so the hook only works in a
 // process that opted in with the environment variable RSA_TUNING=1 (the A/B tools and the variant tests); a production
@@ -43,7 +39,6 @@ extern "C" int rsa_set_tuning(const char* key, int value) {
     if (strcmp(key, "k5_static") == 0) { g_k5_static = value; return RSA_OK; }
     if (strcmp(key, "k5_rows256") == 0) { g_k5_rows256 = value; return RSA_OK; }
     if (strcmp(key, "k5_tsplit") == 0) { g_k5_tsplit = value; return RSA_OK; }
-    if (strcmp(key, "k5_w64") == 0) { g_k5_w64 = value; return RSA_OK; }
     if (strcmp(key, "k5_gsync") == 0) { g_k5_gsync = value; return RSA_OK; }
     if (strcmp(key, "k5_gsync_ratio") == 0) { g_k5_gsync_ratio = value; return RSA_OK; }
     if (strcmp(key, "k5_text_last") == 0) { g_k5_text_last = value; return RSA_OK; }
@@ -297,7 +292,8 @@ int rsa_plan_walk(WalkArgs& a, int BH, int D, const WalkPolicy& pol, size_t tpar
 }
 
 static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes, hipStream_t s) {
-    const bool w64 = k5_runs_w64(D, a.blk);
+    // 128-token blocks and dense calls run the 64-row kernel; 64-token blocks the 32-row kernel, whose 64-key tiles are one block
+    const bool w64 = a.blk == RSA_BLOCK;
     long nblocks;
     WalkPolicy pol;
     pol.blk = a.blk;
@@ -407,8 +403,8 @@ static int dense_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_tensor4
     a.tsplit = 1; a.tper = 0;
     a.mode = MODE_DENSE; a.H = H; a.Sq = Sq; a.Sk = Sk;
     a.blk = RSA_BLOCK; a.txt0 = 0;
-    // head dim 128 through the 64-row kernel: 256-row tiles once there are at least two of them (a shorter call keeps 128-row tiles)
-    a.rows256 = (k5_runs_w64(D, a.blk) && g_k5_rows256 && Sq > 256) ? 1 : 0;
+    // 256-row tiles once there are at least two of them (a shorter call keeps 128-row tiles)
+    a.rows256 = (g_k5_rows256 && Sq > 256) ? 1 : 0;
     const int rw = a.rows256 ? 2 * RSA_BLOCK : RSA_BLOCK;
     a.NQB = (Sq + rw - 1) / rw; a.NBv = a.NQB; a.NB_total = (Sk + RSA_BLOCK - 1) / RSA_BLOCK;
     a.kv_valid = Sk; a.kv_text_valid = Sk; a.q_text_end = 0;

@@ -1,8 +1,14 @@
-// K5: block-sparse flash attention forward for gfx950 (MI355X) with the rectification epilogue fused.
+// K5 at 64-token blocks: block-sparse flash attention forward for gfx950 (MI355X) with the rectification epilogue fused, 32
+// query rows per wave.  (128-token blocks and dense calls run the 64-rows-per-wave kernel, rsa_attn_kernel64.hip.)
 //
-// One workgroup (4 waves, 256 threads, two workgroups per CU) owns one 128-row query block; wave w owns rows
-// 32w..32w+31.  Both GEMMs run on v_mfma_f32_32x32x16_{bf16,f16} in the "key on the register, query row on
-// the lane" orientation:
+// One workgroup (4 waves, 256 threads, two workgroups per CU) owns the PAIR of 64-row query blocks (2 qblk, 2 qblk + 1): waves
+// 0-1 the first, waves 2-3 the second, wave w rows 32w..32w+31 of the pair's 128.  It walks the UNION of the two blocks' kept
+// lists -- one 64-key tile per entry, staged once for both; the entries carry which of the two kept them (bits 14 / 15 of the LDS
+// list), and a wave pair masks the tiles of the other's list to -inf (exact: they add 0 to O and l, and -inf leaves the running
+// maximum alone), so every row gets the bytes its own list would give.  Dense text rows: 128-row units from row
+// NBv * 64 on (a.txt0), every key block theirs, optionally split over the key range (split-KV partials, rsa_attn.hip).
+//
+// Both GEMMs run on v_mfma_f32_32x32x16_{bf16,f16} in the "key on the register, query row on the lane" orientation:
 //      S^T[key][q]  = K . Q^T      A = K rows (ds_read_b128 from an XOR-swizzled row-major tile), B = Q (registers)
 //      O^T[d][q]   += V^T . P^T    A = V^T (ds_read_b64_tr_b16 transposing reads), B = P^T = the S^T accumulator
 //                                      converted in place (no LDS round trip, no cross-lane traffic)
@@ -18,10 +24,11 @@
 // happens to emit (profiles/r03_k5_r1_vs_head.md: the same source went from read-ahead operand reads to one
 // lgkmcnt(0) per MFMA between two rounds, -8 %).  The running max is deferred: the reference max only moves when some
 // row's max grew by more than 2^8 since it was set (P <= 2^8: same relative precision in bf16/fp16 P, fp32
-// accumulators); that rare rescale and the boundary-tile mask sit in branches in front of the block.
+// accumulators); that rare rescale and the mask (boundary tiles, tiles of the other wave pair's list) sit in branches in front
+// of the block.
 //
 // Staging: K/V tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction) issued
-// from inline asm so that hipcc neither counts nor drains them; LDS = [K0 K1 V0 V1 | kept list (u16)], 64-key tiles.  At the
+// from inline asm so that hipcc neither counts nor drains them; LDS = [K0 K1 V0 V1 | union list (u16)], 64-key tiles.  At the
 // head of sub-step (t,0) V(t+1) is issued into V(t-1)'s slot, at the head of (t,1) K(t+2) into K(t)'s slot, each behind a
 // counted vmcnt (the group issued half a tile ago stays in flight) + barrier; every tile has a full tile time to land.
 // (One wait + barrier + issue point per 64-key TILE -- half the barriers, 8 pieces per issue point -- measured the same:
@@ -29,15 +36,16 @@
 // the per-lane SOURCE chunk (same involution as tile_off on the read side); per-lane source offsets are tile-invariant
 // 32-bit values and the tile only moves a scalar base.
 //
-// The chip runs this loop at its board power cap (1.39 kW at 1.72 GHz, tools/clock_probe.py), so cycles saved from stalls
-// come back as a lower clock; what pays is fewer instructions per MFMA: the score chain starts from -m (a 16-register
-// block, C operand of the first QK^T MFMA), so the accumulator is S - m and the softmax needs no subtraction.
+// The chip runs this loop at its board power cap (tools/clock_probe.py), so cycles saved from stalls come back as a lower
+// clock; what pays is fewer instructions per MFMA.  Head dim 128: the score chain starts from -m (a 16-register block, C
+// operand of the first QK^T MFMA), so the accumulator is S - m and the softmax needs no subtraction; the row sums are added
+// into l.  Head dim 64: the classic arithmetic (S, then S - m by v_sub), which measures faster there, with the row sums on the
+// matrix pipe (lacc).
 //
 // Semantics kept from the reference kernel (rectified_hunyuan_attn.py:15-105): Q is pre-multiplied by
 // sm_scale*log2(e) and rounded to the input dtype (:61-62), P is rounded to the input dtype before PV (:97),
-// fp32 softmax statistics and accumulators, kv columns outside the row's range are -inf (:86-87), rows
-// beyond the sequence are not stored (:105).  Added: per-row kv ranges (the two-segment varlen semantics of
-// the flash call, attn.py:107-120), a NaN-free fully-masked path, the fused O*R+comp epilogue (hunyuan :365)
+// fp32 softmax statistics and accumulators, kv columns beyond the valid keys are -inf (:86-87), rows
+// beyond the sequence are not stored (:105).  Added: a NaN-free fully-masked path, the fused O*R+comp epilogue (hunyuan :365)
 // and a strided [B,S,H,D] store (hunyuan :383-387).
 //
 // (Forms measured and NOT kept in this library -- a ping-pong 8-wave kernel, paired 256-row workgroups over union lists,
@@ -60,55 +68,34 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
         else asm volatile(NAME##_##DD##_##TT##_V1_S1 OPS : CLOB, "memory"); \
     } while (0)
 
-// the product's block: S_cur / S_nxt hold S - m (nm = -m in 16 registers), no subtraction in the softmax
-template <int D, typename Tag, int VS, int SUB, typename KA, typename VA>
-__device__ __forceinline__ void k5_block_nm(f32x16 (&o)[D / 32], const s16x8 (&q)[D / 16], f32x16& S_cur, f32x16& S_nxt,
-                                            const f32x16& nm, float& l, f32x4& lacc, const s16x8& onesv, float& mx, const KA& ka,
-                                            const VA& va) {
+// head dim 128: S_cur / S_nxt hold S - m (nm = -m in 16 registers), no subtraction in the softmax; the row sums go into l
+template <typename Tag, int VS, int SUB>
+__device__ __forceinline__ void k5_block_nm(f32x16 (&o)[4], const s16x8 (&q)[8], f32x16& S_cur, f32x16& S_nxt, const f32x16& nm,
+                                            float& l, float& mx, const i32x8& ka, const i32x8& va) {
     f32x16& SA = SUB == 0 ? S_cur : S_nxt;
     f32x16& SB = SUB == 0 ? S_nxt : S_cur;
-    constexpr bool BF = std::is_same<Tag, bf16_tag>::value;
-    if constexpr (D == 128) {
-        if constexpr (BF) RSA_K5_PICK(RSA_K5_BLOCKN, 128, BF16, RSA_K5_OPSN_128, RSA_K5_CLOBBERN_128);
-        else RSA_K5_PICK(RSA_K5_BLOCKN, 128, F16, RSA_K5_OPSN_128, RSA_K5_CLOBBERN_128);
-    } else {
-        if constexpr (BF) RSA_K5_PICK(RSA_K5_BLOCKN, 64, BF16, RSA_K5_OPSN_64, RSA_K5_CLOBBERN_64);
-        else RSA_K5_PICK(RSA_K5_BLOCKN, 64, F16, RSA_K5_OPSN_64, RSA_K5_CLOBBERN_64);
-    }
+    if constexpr (std::is_same<Tag, bf16_tag>::value) RSA_K5_PICK(RSA_K5_BLOCKN, 128, BF16, RSA_K5_OPSN_128, RSA_K5_CLOBBERN_128);
+    else RSA_K5_PICK(RSA_K5_BLOCKN, 128, F16, RSA_K5_OPSN_128, RSA_K5_CLOBBERN_128);
 }
-// the classic form (S, then S - m by v_sub: the arithmetic of round 2's compiled block, bit for bit):
-// the product at head dim 64, where it measures 4 % faster than the -m form (at 128 the -m form wins by 3.7 %)
-// (head dim 64, round 5: the row sums ride the matrix pipe -- l lives in lacc, four registers with the lane's complete row sum of
-// the rounded P, onesv is the ones operand of those products; l itself is not touched.  At 128 it is the other way round.)
-template <int D, typename Tag, int VS, int SUB, typename KA, typename VA>
-__device__ __forceinline__ void k5_block(f32x16 (&o)[D / 32], const s16x8 (&q)[D / 16], f32x16& S_cur, f32x16& S_nxt, float m,
-                                         float& l, f32x4& lacc, const s16x8& onesv, float& mx, const KA& ka, const VA& va) {
+// head dim 64: the classic form (S, then S - m by v_sub: the arithmetic of round 2's compiled block, bit for bit), which measures
+// 4 % faster there than the -m form (at 128 the -m form wins by 3.7 %).  The row sums ride the matrix pipe: lacc = four registers
+// with the lane's complete row sum of the rounded P, onesv the ones operand of those products.
+template <typename Tag, int VS, int SUB>
+__device__ __forceinline__ void k5_block(f32x16 (&o)[2], const s16x8 (&q)[4], f32x16& S_cur, f32x16& S_nxt, float m, f32x4& lacc,
+                                         const s16x8& onesv, float& mx, const i32x4& ka, const i32x4& va) {
     f32x16& SA = SUB == 0 ? S_cur : S_nxt;
     f32x16& SB = SUB == 0 ? S_nxt : S_cur;
-    constexpr bool BF = std::is_same<Tag, bf16_tag>::value;
-    if constexpr (D == 128) {
-        if constexpr (BF) RSA_K5_PICK(RSA_K5_BLOCK, 128, BF16, RSA_K5_OPS_128, RSA_K5_CLOBBER_128);
-        else RSA_K5_PICK(RSA_K5_BLOCK, 128, F16, RSA_K5_OPS_128, RSA_K5_CLOBBER_128);
-    } else {
-        if constexpr (BF) RSA_K5_PICK(RSA_K5_BLOCK, 64, BF16, RSA_K5_OPS_64, RSA_K5_CLOBBER_64);
-        else RSA_K5_PICK(RSA_K5_BLOCK, 64, F16, RSA_K5_OPS_64, RSA_K5_CLOBBER_64);
-    }
+    if constexpr (std::is_same<Tag, bf16_tag>::value) RSA_K5_PICK(RSA_K5_BLOCK, 64, BF16, RSA_K5_OPS_64, RSA_K5_CLOBBER_64);
+    else RSA_K5_PICK(RSA_K5_BLOCK, 64, F16, RSA_K5_OPS_64, RSA_K5_CLOBBER_64);
 }
 
-// The form of the hand-placed block: 2 = score chain started from -m (head dim 128); 1 = the classic arithmetic, S then S - m
-// (head dim 64).  The two differ by the rounding order of S - m.
-constexpr int k5_product_form(int D) { return D == 128 ? 2 : 1; }
+// NEGM (head dim 128): the score chain starts from -m and the row sums are added into l_run.  Head dim 64: the classic
+// arithmetic with the row sums in lacc.  The two differ by the rounding order of S - m.
 // WIDE: 16-byte output stores after a permlane32_swap regroup (needs 16-byte aligned output rows), else 8-byte stores.
-// BLK: tokens per block.  128: the 128-row query block of the header above, two 64-key tiles per kept block.  64 (the _ex entry
-// points): the workgroup owns the PAIR of query blocks (2 qblk, 2 qblk + 1), waves 0-1 the first, 2-3 the second, and walks the
-// union of their kept lists -- one 64-key tile per entry, staged once for both; the entries carry which of the two kept them
-// (bits 14 / 15 of the LDS list), and a wave pair masks the tiles of the other's list to -inf (exact: they add 0 to O and l, and
-// -inf leaves the running maximum alone), so every row gets the bytes its own list would give.  Dense text rows: 128-row units
-// from row NBv * 64 on (a.txt0).
-template <int D, typename Tag, bool WIDE, int BLK = 128>
+template <int D, typename Tag, bool WIDE>
 __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     const AttnArgs& a = rsa_kernargs<AttnArgs>();
-    constexpr int FORM = k5_product_form(D);
+    constexpr bool NEGM = D == 128;
     constexpr int NW = 4;                   // 4 waves x 32 query rows
     constexpr int KS = D / 16;
     constexpr int DT = D / 32;
@@ -123,119 +110,92 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     const int work = blockIdx.x;
     const GsyncTicket gs_tk = rsa_gsync_announce(a.gsync, a.gsync_gen);   // aligned starts (rsa_attn.h)
     // ---------------- work mapping (rsa_attn.h) ----------------
-    // qblk: the query block, at BLK 64 the PAIR of query blocks; tsp: which part of a text block's key range this workgroup walks.
+    // qblk: the PAIR of query blocks, or the 128-row text unit; tsp: which part of a text unit's key range this workgroup walks.
     // `tail` is ignored: this kernel has no partial store for a tail piece, and the host plans a tail split for the kernels that have
     int bh, qblk, tsp, tail;
-    const int walk = rsa_walk_map(a, work, BLK == 64 ? (a.NBv + 1) >> 1 : a.NBv, bh, qblk, tsp, tail);
+    const int walk = rsa_walk_map(a, work, (a.NBv + 1) >> 1, bh, qblk, tsp, tail);
     if (walk == WALK_NONE) return;
     const bool text = walk == WALK_TEXT;
     const int b = bh / a.H, h = bh % a.H;
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    // BLK 64: qblk is the pair (sparse) or the 128-row text unit (text); qw = this wave's own query block
-    const int grow = (BLK == 64 && text ? a.txt0 + (qblk - a.NBv) * 128 : qblk * 128) + 32 * wv + r;
-    const int qw = BLK == 64 ? 2 * qblk + (wv >> 1) : qblk;
+    const int grow = (text ? a.txt0 + (qblk - a.NBv) * 128 : qblk * 128) + 32 * wv + r;
+    const int qw = 2 * qblk + (wv >> 1);   // this wave's own query block (sparse walks)
 
     // ---------------- per-row plan ----------------
-    int lo_r = 0, hi_r = 0;
+    // hi: one past the last key the rows may see; a list (sparse pair) or the key blocks first_blk .. + n_items - 1 (text unit)
     bool store_r = false, zero_r = false;
-    int n_items, first_blk = 0, lo_max, hi_min, hi_max;
+    int n_items, first_blk = 0, hi;
     const int32_t* list = nullptr;
     bool rectify = false;
-    if (a.mode == MODE_SPARSE) {
-        if (BLK == 64 ? !text : qblk < a.NBv) {
-            rsa_walk_list(a, (long)bh * a.NBv + (BLK == 64 ? 2 * qblk : qblk), -1, 0, list, n_items);
-            lo_max = 0; hi_min = hi_max = a.kv_valid;
-            rectify = a.R != nullptr;
-            hi_r = a.kv_valid; store_r = grow < a.Sq && (BLK == 128 || qw < a.NBv);
-        } else {
-            rsa_walk_text(a, BLK, tsp, first_blk, n_items);
-            lo_max = 0; hi_min = hi_max = a.kv_text_valid;
-            hi_r = a.kv_text_valid;
-            store_r = grow < a.q_text_end;
-            zero_r = !store_r && grow < a.Sq;
-        }
+    if (!text) {
+        rsa_walk_list(a, (long)bh * a.NBv + 2 * qblk, -1, 0, list, n_items);
+        hi = a.kv_valid;
+        rectify = a.R != nullptr;
+        store_r = grow < a.Sq && qw < a.NBv;
     } else {
-        rsa_dense_row(a, grow, lo_r, hi_r);
-        store_r = grow < a.Sq;
-        rsa_dense_tile(a, qblk * 128, 128, lo_max, hi_min, hi_max, first_blk, n_items);
+        rsa_walk_text(a, 64, tsp, first_blk, n_items);
+        hi = a.kv_text_valid;
+        store_r = grow < a.q_text_end;
+        zero_r = !store_r && grow < a.Sq;
     }
     n_items = __builtin_amdgcn_readfirstlane(n_items);
     const bool use_list = list != nullptr;
-    if constexpr (BLK == 64) {
-        if (use_list) {
-            // union of the pair's lists: both scattered into two bitmaps (in the K/V tile area, free until the first staging),
-            // one word per thread (NB_total <= 8 192: <= 256 words), a workgroup prefix sum of the popcounts, then each thread
-            // writes its word's entries in ascending order: block | kept by 2 qblk << 14 | kept by 2 qblk + 1 << 15
-            unsigned* bm = reinterpret_cast<unsigned*>(lds);
-            int* wsum = reinterpret_cast<int*>(lds + 2 * 256 * 4);
-            const int nw = (a.NB_total + 31) >> 5;
-            for (int i = t; i < 2 * nw; i += 64 * NW) bm[i] = 0u;
-            __syncthreads();
+    if (use_list) {
+        // union of the pair's lists: both scattered into two bitmaps (in the K/V tile area, free until the first staging),
+        // one word per thread (NB_total <= 8 192: <= 256 words), a workgroup prefix sum of the popcounts, then each thread
+        // writes its word's entries in ascending order: block | kept by 2 qblk << 14 | kept by 2 qblk + 1 << 15
+        unsigned* bm = reinterpret_cast<unsigned*>(lds);
+        int* wsum = reinterpret_cast<int*>(lds + 2 * 256 * 4);
+        const int nw = (a.NB_total + 31) >> 5;
+        for (int i = t; i < 2 * nw; i += 64 * NW) bm[i] = 0u;
+        __syncthreads();
 #pragma unroll
-            for (int hb = 0; hb < 2; ++hb) {
-                const int qb = 2 * qblk + hb;
-                if (qb < a.NBv) {
-                    const long ri = (long)bh * a.NBv + qb;
-                    const int32_t* li = a.cols + ri * a.NB_total;
-                    const int n = a.counts[ri];
-                    for (int i = t; i < n; i += 64 * NW) {
-                        const int c = li[i];
-                        atomicOr(&bm[hb * nw + (c >> 5)], 1u << (c & 31));
-                    }
+        for (int hb = 0; hb < 2; ++hb) {
+            const int qb = 2 * qblk + hb;
+            if (qb < a.NBv) {
+                const long ri = (long)bh * a.NBv + qb;
+                const int32_t* li = a.cols + ri * a.NB_total;
+                const int n = a.counts[ri];
+                for (int i = t; i < n; i += 64 * NW) {
+                    const int c = li[i];
+                    atomicOr(&bm[hb * nw + (c >> 5)], 1u << (c & 31));
                 }
             }
-            __syncthreads();
-            const unsigned w0 = t < nw ? bm[t] : 0u, w1 = t < nw ? bm[nw + t] : 0u;
-            unsigned u = w0 | w1;
-            const int c = __popc(u);
-            int x = c;
+        }
+        __syncthreads();
+        const unsigned w0 = t < nw ? bm[t] : 0u, w1 = t < nw ? bm[nw + t] : 0u;
+        unsigned u = w0 | w1;
+        const int c = __popc(u);
+        int x = c;
 #pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int y = __shfl_up(x, d, 64);
-                if (lane >= d) x += y;
-            }
-            if (lane == 63) wsum[t >> 6] = x;
-            __syncthreads();
-            int off = x - c;
-            for (int ww = 0; ww < (t >> 6); ++ww) off += wsum[ww];
-            n_items = __builtin_amdgcn_readfirstlane(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
-            while (u) {
-                const int bit = __ffs(u) - 1;
-                u &= u - 1;
-                lds_list[off++] = (unsigned short)((32 * t + bit) | (((w0 >> bit) & 1u) << 14) | (((w1 >> bit) & 1u) << 15));
-            }
-            __syncthreads();
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y = __shfl_up(x, d, 64);
+            if (lane >= d) x += y;
         }
-    } else {
-        if (use_list) {
-            for (int i = t; i < n_items; i += 64 * NW) lds_list[i] = (unsigned short)list[i];
-            __syncthreads();
+        if (lane == 63) wsum[t >> 6] = x;
+        __syncthreads();
+        int off = x - c;
+        for (int ww = 0; ww < (t >> 6); ++ww) off += wsum[ww];
+        n_items = __builtin_amdgcn_readfirstlane(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+        while (u) {
+            const int bit = __ffs(u) - 1;
+            u &= u - 1;
+            lds_list[off++] = (unsigned short)((32 * t + bit) | (((w0 >> bit) & 1u) << 14) | (((w1 >> bit) & 1u) << 15));
         }
+        __syncthreads();
     }
-    auto blk_of = [&](int item) -> int { return use_list ? (int)lds_list[item] : first_blk + item; };
-    // BLK 64: the raw list entry (block | owner bits; text walks: both owners) and the KEY WORD the tile queue carries: first key
-    // | owner bits << 28 (kkey / kmine take it apart).  BLK 128: the key itself.
-    auto raw64 = [&](int item) -> int { return use_list ? (int)lds_list[item] : (first_blk + item) | (3 << 14); };
-    auto kword = [&](int raw) -> int { return ((raw & 0x3FFF) * 64) | ((raw >> 14) << 28); };
-    auto kkey = [&](int kw) -> int { return BLK == 64 ? (kw & 0x0FFFFFFF) : kw; };
-    int n_tiles = BLK == 64 ? n_items : 2 * n_items;
-    if (BLK == 128 && n_items > 0) {
-        const int last_blk = blk_of(n_items - 1);
-        if (last_blk * RSA_BLOCK + 64 >= hi_max) n_tiles -= 1;
-    }
-    n_tiles = __builtin_amdgcn_readfirstlane(n_tiles);
-    const int kv_limit = hi_max < a.Sk ? hi_max : a.Sk;
-    auto key0_of = [&](int tile) -> int {  // first key of tile `tile` (clamped index: callers guard tile < n_tiles)
-        if constexpr (BLK == 64) {
-            return kword(__builtin_amdgcn_readfirstlane(raw64(tile < n_items ? tile : (n_items > 0 ? n_items - 1 : 0))));
-        } else {
-            const int it = tile >> 1;
-            const int blk = __builtin_amdgcn_readfirstlane(blk_of(it < n_items ? it : (n_items > 0 ? n_items - 1 : 0)));
-            return blk * RSA_BLOCK + (tile & 1) * 64;
-        }
+    // One 64-key tile per item.  The raw entry of tile `tile` (block | owner bits; text walks: both owners), still per lane, index
+    // clamped (callers guard tile < n_items), and the KEY WORD the tile queue carries: first key | owner bits << 28
+    auto raw_item = [&](int tile) -> int {
+        const int it = tile < n_items ? tile : (n_items > 0 ? n_items - 1 : 0);
+        return use_list ? (int)lds_list[it] : (first_blk + it) | (3 << 14);
     };
+    auto kword = [&](int raw) -> int { return ((raw & 0x3FFF) * 64) | ((raw >> 14) << 28); };
+    auto kkey = [&](int kw) -> int { return kw & 0x0FFFFFFF; };
+    const int kv_limit = hi < a.Sk ? hi : a.Sk;
+    auto key0_of = [&](int tile) -> int { return kword(__builtin_amdgcn_readfirstlane(raw_item(tile))); };
 
     // ---------------- Q fragments (B operand) ----------------
     s16x8 qf[KS];
@@ -302,12 +262,11 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) o[dt][i] = 0.0f;
     float m_run = -INFINITY, l_run = 0.0f;
-    // Row sums on the matrix pipe (RSM: head dim 64, gen_k5_block.py::rsm_form): lacc = the lane's complete
+    // Row sums on the matrix pipe (head dim 64, gen_k5_block.py::rsm_form): lacc = the lane's complete
     // row sum of the rounded P in all four registers.  A operand of v_mfma_f32_16x16x32 (lane: row a = l & 15, k-block l >> 4): ones
     // iff (k-block & 1) == ((a >> 2) & 1) -- the B operand is the P . V product's P fragment, whose k-blocks 0 / 2 are the two lane
     // halves of query row n and 1 / 3 those of row n + 16, and the lane that owns C rows 4 (l >> 4) .. + 3 of column l & 15 is the
     // lane of exactly that query row (the construction of the e4m3 kernel's row-sum product).
-    constexpr bool RSM = D == 64;
     f32x4 lacc = {0.0f, 0.0f, 0.0f, 0.0f};
     s16x8 onesv;
     {
@@ -319,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     // m_ref = the finite reference the scores are taken against (S_cur, S_nxt hold S - m_ref), nm = its negation in 16
     // registers (C operand of the first QK^T MFMA), thr = how far a new row maximum may exceed it before the rescale (-inf
     // until the row has seen a finite score: the first finite maximum always becomes the reference).  m_run is the running
-    // maximum itself (-inf = nothing seen): what the split-KV partials carry, and form 1's reference.
+    // maximum itself (-inf = nothing seen): what the split-KV partials carry, and the classic form's reference.
     float m_ref = 0.0f, thr = -INFINITY;
     f32x16 nm;
 #pragma unroll
@@ -340,10 +299,8 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
         else return tile_off<D>(32 * sub + r, 2 * ks + hh);
     };
     // read addresses of the hand-placed block: LDS byte addresses of sub-tile 0 / slot 0; slot, sub-tile and k-step are immediates
-    using KAv = typename std::conditional<D == 128, i32x8, i32x4>::type;
-    using VAv = typename std::conditional<D == 128, i32x8, i32x4>::type;
-    KAv ka;
-    VAv va;
+    using AddrV = typename std::conditional<D == 128, i32x8, i32x4>::type;   // KS K addresses, 2 DT V addresses
+    AddrV ka, va;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) ka[ks] = (int)lds_base + k_off(ks, 0);
 #pragma unroll
@@ -374,7 +331,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int kk = kbase + (i & 3) + 8 * (i >> 2);
-            if (kk < lo_r || kk >= hi_r || !mine) S[i] = -INFINITY;
+            if (kk >= hi || !mine) S[i] = -INFINITY;
         }
     };
 
@@ -386,12 +343,12 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     auto half = [&](auto VS, auto SUB, int key0, f32x16& S_cur, float& mx_cur, f32x16& S_nxt, float& mx_nxt) {
         constexpr int vs = decltype(VS)::value, sub = decltype(SUB)::value;
         const int kfirst = kkey(key0) + 32 * sub;
-        const bool mine = BLK == 128 || ((key0 >> (28 + (wv >> 1))) & 1);   // (BLK 64: the tile is in this wave pair's list)
-        if (kfirst < lo_max || kfirst + 32 > hi_min || !mine) {
+        const bool mine = (key0 >> (28 + (wv >> 1))) & 1;   // the tile is in this wave pair's list
+        if (kfirst + 32 > hi || !mine) {
             apply_mask_sub(S_cur, kfirst, mine);
             rowmax_sub(S_cur, mx_cur);
         }
-        if constexpr (FORM == 2) {
+        if constexpr (NEGM) {
             // S_cur, mx_cur are relative to m_ref as it was when they were computed, and that is still m_ref
             if (__builtin_amdgcn_ballot_w64(mx_cur > thr) != 0ull) {
                 asm volatile("s_nop 11" ::: "memory");   // the block's last MFMA wrote O: 12 wait states before a VALU touches it
@@ -402,10 +359,6 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
                 const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);   // (first: O and l are still zero)
                 m_ref += delta;
                 l_run *= alpha;
-                if constexpr (RSM) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) lacc[i] *= alpha;
-                }
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -413,7 +366,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { S_cur[i] -= delta; nm[i] = -m_ref; }
             }
-            k5_block_nm<D, Tag, vs, sub>(o, qf, S_cur, S_nxt, nm, l_run, lacc, onesv, mx_nxt, ka, va);
+            k5_block_nm<Tag, vs, sub>(o, qf, S_cur, S_nxt, nm, l_run, mx_nxt, ka, va);
         }
         else {   // the classic arithmetic (scores S, reference m_run subtracted in the softmax)
             if (__builtin_amdgcn_ballot_w64(mx_cur > m_run + 8.0f) != 0ull) {
@@ -422,18 +375,15 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
                 const float mu = (m_new == -INFINITY) ? 0.0f : m_new;
                 const float alpha = __builtin_amdgcn_exp2f(m_run - mu);
                 m_run = m_new;
-                l_run *= alpha;
-                if constexpr (RSM) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) lacc[i] *= alpha;
-                }
+                for (int i = 0; i < 4; ++i) lacc[i] *= alpha;
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
             }
             const float m_use = (m_run == -INFINITY) ? 0.0f : m_run;
-            k5_block<D, Tag, vs, sub>(o, qf, S_cur, S_nxt, m_use, l_run, lacc, onesv, mx_nxt, ka, va);
+            k5_block<Tag, vs, sub>(o, qf, S_cur, S_nxt, m_use, lacc, onesv, mx_nxt, ka, va);
         }
     };
 
@@ -442,7 +392,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     // tile ago must land.
     auto stage = [&](auto VS, auto SUB, int tile) {
         constexpr int vs = decltype(VS)::value, sub = decltype(SUB)::value;
-        if (tile + 1 < n_tiles) {
+        if (tile + 1 < n_items) {
             if constexpr (NPC == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         } else {
@@ -450,24 +400,24 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
         }
         __syncthreads();
         if constexpr (sub == 0) {
-            if (tile + 1 < n_tiles) dma(1, kq1, (2 + (vs ^ 1)) * TILE_BYTES);
+            if (tile + 1 < n_items) dma(1, kq1, (2 + (vs ^ 1)) * TILE_BYTES);
         } else {
-            if (tile + 2 < n_tiles) dma(0, kq2, vs * TILE_BYTES);
+            if (tile + 2 < n_items) dma(0, kq2, vs * TILE_BYTES);
         }
     };
 
     // ---------------- prologue + main loop ----------------
-    if ((BLK == 64 ? !text : qblk < a.NBv) || a.mode != MODE_SPARSE) rsa_gsync_wait(a.gsync, gs_tk, n_items, a.NB_total, a.gsync_ratio);   // aligned starts: in front of the first staging instruction (text-row pieces do not wait, as in the 64-row and e4m3 kernels)
+    if (!text) rsa_gsync_wait(a.gsync, gs_tk, n_items, a.NB_total, a.gsync_ratio);   // aligned starts: in front of the first staging instruction (text-row pieces do not wait, as in the 64-row and e4m3 kernels)
     f32x16 SA, SB;
     float mxA = -INFINITY, mxB = -INFINITY;
     int key0 = 0;
-    if (n_tiles > 0) {
+    if (n_items > 0) {
         key0 = key0_of(0);
         kq1 = key0_of(1);
         kq2 = key0_of(2);
         dma(0, key0, 0);
         dma(1, key0, 2 * TILE_BYTES);
-        if (n_tiles > 1) dma(0, kq1, TILE_BYTES);
+        if (n_items > 1) dma(0, kq1, TILE_BYTES);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         qk_sub(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, SA);
@@ -475,17 +425,11 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     }
     // The kept-list entry of tile+3 is read from LDS one advance() EARLY into a register (pref_raw) and only made scalar
     // here: the LDS round trip (~100 cycles, once per tile and wave) is off the wave's critical path.
-    auto raw_item = [&](int tile) -> int {   // block index of `tile`'s list entry, still per lane (index clamped)
-        if constexpr (BLK == 64) return raw64(tile < n_items ? tile : (n_items > 0 ? n_items - 1 : 0));
-        const int it = tile >> 1;
-        return blk_of(it < n_items ? it : (n_items > 0 ? n_items - 1 : 0));
-    };
-    int pref_raw = n_tiles > 0 ? raw_item(3) : 0;
+    int pref_raw = n_items > 0 ? raw_item(3) : 0;
     auto advance = [&](int tile) {  // after finishing `tile`: shift the key queue, tile+3's first key from the prefetched entry
         key0 = kq1;
         kq1 = kq2;
-        if constexpr (BLK == 64) kq2 = kword(__builtin_amdgcn_readfirstlane(pref_raw));
-        else kq2 = __builtin_amdgcn_readfirstlane(pref_raw) * RSA_BLOCK + ((tile + 3) & 1) * 64;
+        kq2 = kword(__builtin_amdgcn_readfirstlane(pref_raw));
         pref_raw = raw_item(tile + 4);
     };
     {
@@ -498,22 +442,22 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
             half(VS, I1{}, key0, SB, mxB, SA, mxA);
         };
         int tile = 0;
-        for (; tile + 1 < n_tiles; tile += 2) {
+        for (; tile + 1 < n_items; tile += 2) {
             tile_step(I0{}, tile);
             advance(tile);
             tile_step(I1{}, tile + 1);
             advance(tile + 1);
         }
-        if (tile < n_tiles) tile_step(I0{}, tile);
+        if (tile < n_items) tile_step(I0{}, tile);
     }
 
     // ---------------- epilogue ----------------
     asm volatile("s_nop 11" ::: "memory");   // (the last block's last MFMA -> the reads of O below)
-    if constexpr (FORM == 2) m_run = thr == -INFINITY ? -INFINITY : m_ref;
+    if constexpr (NEGM) m_run = thr == -INFINITY ? -INFINITY : m_ref;
     const auto swl = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
-    const float l_tot = RSM ? lacc[0] : __uint_as_float(swl[0]) + __uint_as_float(swl[1]);   // (RSM: already complete over both lane halves)
+    const float l_tot = !NEGM ? lacc[0] : __uint_as_float(swl[0]) + __uint_as_float(swl[1]);   // (lacc: already complete over both lane halves)
     bool done = false;
-    if (a.mode == MODE_SPARSE && a.tsplit > 1 && (BLK == 64 ? text : qblk >= a.NBv)) {
+    if (a.tsplit > 1 && text) {
         // split-KV partial of a text block: unnormalised O (fp32), m (log2 domain) and l per row; the combine
         // kernel (rsa_attn.hip) merges the tsplit parts
         float* pp = rsa_part_of(a, bh, qblk, tsp, -1, 32 * wv + r, D);
@@ -607,29 +551,15 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     }
 }
 
-// launch hook used by rsa_attn.hip::launch_attn
+// launch hook used by rsa_attn.hip::launch_attn (64-token blocks only)
 int rsa_launch_bsfwd(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
-    if (a.blk == 64) {   // (64-token blocks: pair-union walk)
-        const bool wide64 = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
-#define RSA_K5B(DD, TT) \
-        do { \
-            if (wide64) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, 64>), a, true, grid, 256, lds_bytes, s); \
-            else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false, 64>), a, true, grid, 256, lds_bytes, s); \
-        } while (0)
-        if (D == 128) {
-            if (dtype == RSA_BF16) RSA_K5B(128, bf16_tag); else RSA_K5B(128, fp16_tag);
-        } else {
-            if (dtype == RSA_BF16) RSA_K5B(64, bf16_tag); else RSA_K5B(64, fp16_tag);
-        }
-#undef RSA_K5B
-        return rsa_launch_status();
-    }
+    if (a.blk != 64 || a.mode != MODE_SPARSE) return RSA_ERR_UNSUPPORTED;
     // the 16-byte output stores need 16-byte aligned rows; anything else takes the 8-byte form
     const bool wide = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
 #define RSA_K5(DD, TT) \
     do { \
-        if (wide) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
-        else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false>), a, a.mode == MODE_SPARSE, grid, 256, lds_bytes, s); \
+        if (wide) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true>), a, true, grid, 256, lds_bytes, s); \
+        else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false>), a, true, grid, 256, lds_bytes, s); \
     } while (0)
     if (D == 128) {
         if (dtype == RSA_BF16) RSA_K5(128, bf16_tag); else RSA_K5(128, fp16_tag);

@@ -242,6 +242,29 @@ def test_plain_attention_against_fp64(case):
         assert float(out.float()[:, :, :blk].abs().max()) == 0.0, "an empty mask row must give 0"
 
 
+@pytest.mark.parametrize("dt,D", [(torch.bfloat16, 128), (torch.float16, 128), (torch.bfloat16, 64), (torch.float16, 64)])
+def test_64_token_blocks_agree_with_the_same_mask_in_128_token_blocks(dt, D):
+    """A 128-token-block mask runs the 64-rows-per-wave kernel; the same mask with every entry repeated into 2 x 2 blocks of 64
+    tokens has the same visibility and runs the 32-rows-per-wave kernel's pair walk.  Both against fp64 attention, and against
+    each other within one output ulp at head dim 128 and two at head dim 64 (the two kernels add the row sums in a different
+    order).  48 sparse workgroups: no tail split, so no block's summation order depends on the grid."""
+    from rectified_spaattn_amd import block_sparse_attention
+    B, H, Sq, Sk, kv_len = 2, 3, 900, 1000, [1000, 777]
+    q, k, v, m = _plain_inputs(dt, D, 128, B, H, Sq, Sk, 0.3, {}, 64 + D)
+    m64 = m.repeat_interleave(2, -2)[..., :-(-Sq // 64), :].repeat_interleave(2, -1)[..., :-(-Sk // 64)]
+    ref = _reference(q.float(), k.float(), v.float(), m, kv_len, D ** -0.5, 128)
+    outs = [block_sparse_attention(q, k, v, m, kv_len=kv_len, block_size=128),
+            block_sparse_attention(q, k, v, m64, kv_len=kv_len, block_size=64)]
+    mx, mean = TOL[dt]
+    for blk, out in zip((128, 64), outs):
+        err = (out.double().cpu() - ref).abs()
+        assert err.max() <= mx and err.mean() <= mean, f"block {blk}: max {err.max():.3e} mean {err.mean():.3e}"
+    ulp = 2.0 ** -7 if dt == torch.bfloat16 else 2.0 ** -10
+    dist = float((outs[0].double() - outs[1].double()).abs().max())
+    bound = (1 if D == 128 else 2) * ulp * max(1.0, float(ref.abs().max()))
+    assert dist <= bound, f"between the kernels: {dist:.3e}, bound {bound:.3e}"
+
+
 @pytest.mark.parametrize("blk", [64, 128])
 def test_rows_without_a_visible_key_are_exactly_zero(blk):
     from rectified_spaattn_amd import block_sparse_attention

@@ -1,7 +1,7 @@
 """Aligned starts of the sparse walks (rsa_attn.h, tuning key k5_gsync; round 4).  The workgroups of an XCD wait for their
 generation before they stage their first tile, so that their ascending walks meet in the XCD's L2.  It is a scheduling aid:
 the arithmetic and its order are untouched, so every kernel must give the same BYTES with it on and off -- in the 64-row kernel
-(where it is on by default), in the 32-row kernel and in the e4m3 kernel (bit 1 of the key)."""
+(128-token blocks, where it is on by default), in the 32-row kernel (64-token blocks) and in the e4m3 kernel (bit 1 of the key)."""
 import numpy as np
 import pytest
 import torch
@@ -19,24 +19,25 @@ def _inputs(H, nb, D, seed, dt):
     return mk(), mk(), torch.randn(1, H, S, D, generator=g, device="cuda:0").to(dt)
 
 
-@pytest.mark.parametrize("w64,D,dt", [(1, 128, torch.bfloat16), (1, 128, torch.float16), (0, 128, torch.bfloat16), (0, 64, torch.bfloat16),
-                                       (3, 64, torch.bfloat16), (3, 64, torch.float16)])
-def test_aligned_starts_do_not_change_a_byte(w64, D, dt):
+@pytest.mark.parametrize("blk,D,dt", [(128, 128, torch.bfloat16), (128, 128, torch.float16), (128, 64, torch.bfloat16),
+                                       (128, 64, torch.float16), (64, 128, torch.bfloat16), (64, 64, torch.bfloat16)])
+def test_aligned_starts_do_not_change_a_byte(blk, D, dt):
     from rectified_spaattn_amd import _core, _lib
-    H, nb, top_k = 8, 168, 14          # 1 344 workgroups (more than two generations of 8 x 64), 8 % of the keys kept: the walks wait
+    # 128-token blocks: 168 key blocks, 1 344 workgroups of the 64-row kernel; 64-token blocks: 336 key blocks, 1 344 pair walks of
+    # the 32-row kernel (bit 1 of the key).  More than two generations of 8 x 64, 8 % of the keys kept: the walks wait
+    H, nb = 8, 168
+    top_k = 14 if blk == 128 else 28
     q, k, v = _inputs(H, nb, D, 11, dt)
-    spec = _core.LayoutSpec.wan(nb * 128, 0)
+    spec = _core.LayoutSpec.wan(nb * 128, 0, block=blk)
     L = _lib.lib()
     outs = []
     try:
-        assert L.rsa_set_tuning(b"k5_w64", w64) == 0
         for gs in (0, 3, 0, 3):
             assert L.rsa_set_tuning(b"k5_gsync", gs) == 0
             out = _core.rectified_attention(q, k, v, spec, top_k, 0.05, None)
             torch.cuda.synchronize()
             outs.append(out.view(torch.int16).cpu().numpy().copy())
     finally:
-        L.rsa_set_tuning(b"k5_w64", 3)
         L.rsa_set_tuning(b"k5_gsync", 1)
     assert np.isfinite(out.float().cpu().numpy()).all()
     for o in outs[1:]:

@@ -199,6 +199,8 @@ def test_cabi_fp8_entry_points_validate_on_the_host():
     assert lib.rsa_dense_fp8_bytes(0, 2, 300, 500, 128, ctypes.byref(d)) == -1
     # the tuning hook is inert unless the process opted in with RSA_TUNING=1 (then unknown keys are bad arguments)
     assert lib.rsa_set_tuning(b"no_such_key", 1) == (-1 if os.environ.get("RSA_TUNING") == "1" else -2)
+    # (the key that once chose between the two 2-byte K5 kernels is gone: the block size alone decides)
+    assert lib.rsa_set_tuning(b"k5_w64", 1) == lib.rsa_set_tuning(b"no_such_key", 1)
 
 
 # ---- round 2: Wan2.2 processors and B = 2 against reference vectors (tests/golden/processors_r2.npz) ------------------

@@ -1,6 +1,6 @@
 #!/bin/bash
 # the two SQ counter passes of tools/pmc_passes.sh only (issue / wait / instruction mix), sparse call only
-# usage: bash tools/pmc_sq.sh <out-subdir-of-gpurun_out>     (env RSA_K5_W64=1 RSA_TUNING=1: the 64-row K5)
+# usage: bash tools/pmc_sq.sh <out-subdir>     (a subdirectory of $OUT below)
 R=$PWD; OUT=$R/gpurun_out/$1; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp; export RSA_PERF_NODENSE=1
 N=0
