@@ -251,6 +251,23 @@ int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, int dtype, i
                                double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* cols,
                                const int32_t* counts, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream);
 
+/* The same call with a key range per query row (found by symbol: the header version stays 6.1).  Query row r of batch item b and
+ * head h sees key j iff its block is in the lists  and  lo <= j < hi  and  j < kv_valid  and  j < NK * block, with
+ *     lo = row_lo[b * range_stride_b + r]  (row_lo NULL: 0),   hi = row_hi[b * range_stride_b + r],
+ * DEVICE int32 arrays of Sq entries per batch item (range_stride_b = 0: one array for every batch item), clamped into
+ * [0, kv_valid] on the device -- any int32 may be passed; hi <= lo is the empty range, and a row without a visible key is 0.
+ * Ranges need not grow with the row.  Causal, sliding-window and chunk-causal masks at token granularity and per-batch key
+ * limits that live on the device are all such ranges (block_sparse_attention(causal= / window= / row_range=) builds them).
+ * The kernel drops the listed blocks no row of a query block can see before it stages anything; blocks that some rows see only
+ * in part (the diagonal of a causal mask) run masked, block by block, as the last blocks of every walk do.
+ * Everything rsa_block_sparse_plain_fwd refuses is refused here; besides: block != 128 is RSA_ERR_UNSUPPORTED (64-token blocks
+ * run the 32-rows-per-wave kernel, which has one scalar key limit and no per-row range); row_hi NULL, a negative stride or an
+ * array that is not 4-byte aligned is RSA_ERR_BAD_ARG. */
+int rsa_block_sparse_ranged_fwd(int B, int H, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, int kv_valid,
+                                double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* cols,
+                                const int32_t* counts, const int32_t* row_lo, const int32_t* row_hi, int64_t range_stride_b,
+                                float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

@@ -39,11 +39,14 @@ def set_dense_fp8(enabled) -> bool:
     return _operator.set_dense_fp8(enabled)
 
 
-def block_sparse_attention(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128):
+def block_sparse_attention(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, window=None,
+                           row_range=None):
     """Block-sparse attention over a block mask of the caller's own: q [B,H,Sq,D], k / v [B,H,Sk,D], block_mask bool / uint8
-    [B|1, H|1, ceil(Sq/block), NK] -> [B,H,Sq,D].  See rectified_spaattn_amd.block_sparse.block_sparse_attention."""
+    [B|1, H|1, ceil(Sq/block), NK] -> [B,H,Sq,D]; causal / window=(left, right) / row_range=(lo, hi) add a key range per query
+    row.  See rectified_spaattn_amd.block_sparse.block_sparse_attention."""
     from . import block_sparse
-    return block_sparse.block_sparse_attention(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size)
+    return block_sparse.block_sparse_attention(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
+                                               causal=causal, window=window, row_range=row_range)
 
 
 def clear_buffer_cache() -> None:

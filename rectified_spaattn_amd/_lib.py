@@ -126,6 +126,9 @@ def lib():
     L.rsa_lists_to_block_mask.argtypes = [i32] * 4 + [vp, vp, vp]
     L.rsa_block_sparse_plain_fwd.argtypes = ([i32] * 10 + [ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, vp, vp, sz,
                                              RsaOut4, vp])
+    L.rsa_block_sparse_ranged_fwd.argtypes = ([i32] * 10 + [ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, vp, vp, vp, i64,
+                                              vp, sz, RsaOut4, vp])
+    L.rsa_block_sparse_ranged_fwd.restype = i32
     L.rsa_select_from_mask.argtypes = [P(RsaLayout), vp, i64, i64, i64, P(RsaBuffers), vp]
     L.rsa_select_from_mask_ex.argtypes = [P(RsaLayoutEx), vp, i64, i64, i64, P(RsaBuffers), vp]
     L.rsa_rectified_attention_masked.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, vp, i64, i64, i64, vp, sz,
@@ -210,8 +213,8 @@ EXPORTED = ("rsa_version", "rsa_abi_check", "rsa_buffer_bytes", "rsa_carve_works
             "rsa_allgather_heads_p2p", "rsa_p2p_state_bytes", "rsa_p2p_state_alloc", "rsa_p2p_state_free", "rsa_p2p_state_timeout", "rsa_ipc_export", "rsa_ipc_open", "rsa_ipc_close",
             "rsa_ipc_offset", "rsa_buffer_bytes_ex", "rsa_carve_workspace_ex", "rsa_pool_stats_ex", "rsa_pooled_scores_ex",
             "rsa_select_mask_ex", "rsa_compensation_ex", "rsa_block_sparse_fwd_ex", "rsa_rectified_attention_ex", "rsa_estimate_pr_gain_ex",
-            "rsa_block_mask_to_lists", "rsa_lists_to_block_mask", "rsa_block_sparse_plain_fwd", "rsa_select_from_mask",
-            "rsa_select_from_mask_ex", "rsa_rectified_attention_masked", "rsa_rectified_attention_masked_ex")
+            "rsa_block_mask_to_lists", "rsa_lists_to_block_mask", "rsa_block_sparse_plain_fwd", "rsa_block_sparse_ranged_fwd",
+            "rsa_select_from_mask", "rsa_select_from_mask_ex", "rsa_rectified_attention_masked", "rsa_rectified_attention_masked_ex")
 
 
 def check(status: int, what: str):

@@ -5,7 +5,8 @@ implicit full-attention probabilities, GAPR mask) and `_triton_block_sparse_atte
 any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the flux / cogvideo / wan21 files.  Here:
 
     block_sparse_attention   K5 without the rectifying epilogue (rsa_block_sparse_plain_fwd) over the lists
-                             rsa_block_mask_to_lists makes from the caller's mask
+                             rsa_block_mask_to_lists makes from the caller's mask; with causal= / window= / row_range= a key
+                             range per query row on top of the mask (rsa_block_sparse_ranged_fwd, one launch per batch)
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
@@ -112,16 +113,129 @@ def _kv_lens(kv_len, B: int, Sk: int):
     return lens
 
 
+_RANGE_CACHE: "Dict[tuple, tuple]" = {}
+_RANGE_CACHE_MAX = 64
+
+
+def _check_window(window):
+    if not isinstance(window, (tuple, list)) or len(window) != 2 or not all(isinstance(w, int) and w >= -1 for w in window):
+        raise ValueError(f"window: (left, right), ints >= 0 or -1 for unbounded, got {window!r}")
+    return int(window[0]), int(window[1])
+
+
+def _check_row_range(row_range, B: int, Sq: int, device):
+    """(lo | None, hi): int32 tensors [B|1, Sq] on q's device."""
+    if not isinstance(row_range, (tuple, list)) or len(row_range) != 2:
+        raise ValueError("row_range: a pair (lo | None, hi) of int32 tensors [B|1, Sq]")
+    lo, hi = row_range
+    if hi is None:
+        raise ValueError("row_range: hi is required (lo may be None = 0)")
+    for name, t in (("lo", lo), ("hi", hi)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise ValueError(f"row_range {name}: an int32 tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 2 or t.shape[0] not in (1, B) or t.shape[1] != Sq:
+            raise ValueError(f"row_range {name} {tuple(t.shape)}: expected [{B}|1, {Sq}]")
+        if t.device != device:
+            raise ValueError(f"row_range {name} is on {t.device}, q on {device}")
+    return lo, hi
+
+
+def _window_ranges(device, B: int, Sq: int, Sk: int, lens, left: int, right: int):
+    """lo (None: 0) and hi, int32 [B|1, Sq] on the device, of window (left, right) aligned bottom-right per batch item:
+    lo = r + off_b - left, hi = r + off_b + right + 1 with off_b = kv_len[b] - Sq, hi folded with kv_len[b]; clipped into [0, Sk]
+    (the kernel clamps into [0, kv_valid] anyway).  lens: a list of B host ints -- cached per (device, stream, Sq, lens, window)
+    as _tail_buffer caches, never during a graph capture -- or an integer device tensor [B|1], which is never read on the host."""
+    dev = torch.device(device)
+    r = torch.arange(Sq, dtype=torch.int64, device=dev)
+
+    def rows(off):    # off = kv_len - Sq: a host int (-> [Sq]) or a device tensor [n, 1] (-> [n, Sq])
+        lo = None if left < 0 else (r + (off - left)).clamp(0, Sk).to(torch.int32)
+        hi = r + (off + right + 1) if right >= 0 else r * 0 + (off + Sq)
+        hi = hi.clamp(max=off + Sq) if isinstance(off, int) else torch.minimum(hi, off + Sq)
+        return lo, hi.clamp(0, Sk).to(torch.int32)
+    if isinstance(lens, torch.Tensor):
+        return rows(lens.reshape(-1, 1).to(torch.int64) - Sq)
+    capturing = torch.cuda.is_current_stream_capturing()
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, Sq, Sk, tuple(lens), left, right)
+    if _core.BUFFER_CACHE and not capturing and key in _RANGE_CACHE:
+        return _RANGE_CACHE[key]
+    per = [rows(n - Sq) for n in (lens if len(set(lens)) > 1 else lens[:1])]
+    lo = None if left < 0 else torch.stack([p[0] for p in per])
+    out = (lo, torch.stack([p[1] for p in per]))
+    if _core.BUFFER_CACHE and not capturing:
+        if len(_RANGE_CACHE) >= _RANGE_CACHE_MAX:
+            _RANGE_CACHE.pop(next(iter(_RANGE_CACHE)))
+        _RANGE_CACHE[key] = out
+    return out
+
+
+def _ranged_attention(q, k, v, block_mask, lens, scale: float, lo, hi) -> torch.Tensor:
+    """One launch of rsa_block_sparse_ranged_fwd for the whole batch.  lens: B host ints, or a device tensor [B|1] (not read)."""
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if isinstance(lens, torch.Tensor):
+        kv_valid = Sk
+    else:
+        kv_valid = max(lens)
+        if kv_valid == 0:   # no visible key at all
+            return torch.zeros((B, H, Sq, D), dtype=q.dtype, device=q.device)
+    if D in _core._PAD_HEAD_DIM:   # zero columns add exact zeros to every dot product; the caller's scale is kept
+        pad = (0, _core._PAD_HEAD_DIM[D] - D)
+        F = torch.nn.functional
+        return _ranged_attention(F.pad(q, pad), F.pad(k, pad), F.pad(v, pad), block_mask, lens, scale, lo, hi)[..., :D].contiguous()
+    if lo is not None and lo.shape[0] != hi.shape[0]:
+        lo = lo.expand(hi.shape[0], Sq) if lo.shape[0] == 1 else lo
+        hi = hi.expand(lo.shape[0], Sq) if hi.shape[0] == 1 else hi
+    lo = None if lo is None else lo.contiguous()
+    hi = hi.contiguous()
+    L = _lib.lib()
+    q, k, v = _core._as_bhsd(q), _core._as_bhsd(k), _core._as_bhsd(v)
+    NQ, NK = -(-Sq // _lib.BLOCK), block_mask.shape[3]
+    lists = block_mask_to_lists(block_mask, B, H)
+    out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=q.device)
+    tpart = _tail_buffer(q.device) if D == 128 else None
+    tp, tpb = (tpart.data_ptr(), tpart.numel() * 4) if tpart is not None else (None, 0)
+    with torch.cuda.device(q.device):
+        _lib.check(L.rsa_block_sparse_ranged_fwd(B, H, Sq, Sk, D, _core.dtype_code(q.dtype), _lib.BLOCK, NQ, NK, kv_valid, scale,
+                                                 _core._t4(q), _core._t4(k), _core._t4(v), lists["cols"].data_ptr(),
+                                                 lists["counts"].data_ptr(), lo.data_ptr() if lo is not None else None, hi.data_ptr(),
+                                                 0 if hi.shape[0] == 1 else Sq, tp, tpb,
+                                                 RsaOut4(out.data_ptr(), out.stride(0), out.stride(1), out.stride(2)), _core._stream()),
+                   "rsa_block_sparse_ranged_fwd")
+    return out
+
+
 def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask: torch.Tensor, *, kv_len=None,
-                           sm_scale: Optional[float] = None, block_size: int = 128) -> torch.Tensor:
+                           sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, window=None,
+                           row_range=None) -> torch.Tensor:
     """softmax(sm_scale q k^T) v restricted, per query block i, to the key blocks j with block_mask[b, h, i, j] set and to the
     keys < kv_len.  q [B,H,Sq,D], k / v [B,H,Sk,D] (any strides with a contiguous head dim: [B,S,H,D] views need no copy);
     block_mask bool / uint8 [B|1, H|1, ceil(Sq/block), NK] with NK <= ceil(Sk/block) (keys past NK * block are never visited);
     kv_len None (= Sk), an int, or one value per batch item (a tensor costs one host read; distinct values run one launch per
     batch item); sm_scale defaults to D ** -0.5.  Returns [B,H,Sq,D] in the input dtype.  A row without a visible key is 0
     (the reference's kernel gives NaN there).  Asynchronous on the current stream.  Head dims 64 / 128 run natively, 16 / 32
-    zero-padded (exact); bf16 and fp16."""
+    zero-padded (exact); bf16 and fp16.
+
+    Per-row key ranges (at most one of the three; 128-token blocks only): row r of batch item b then sees key j iff
+    block_mask[b, h, r // 128, j // 128] and lo[b, r] <= j < hi[b, r] and j < kv_len[b] and j < NK * 128.
+      row_range=(lo | None, hi)   int32 device tensors [B|1, Sq]; any values (clamped into [0, kv_len[b]] on the device), hi <= lo
+                                  is an empty row (0), the same ranges for every head, no order along the rows required
+      window=(left, right)        flash-attn's sliding window, -1 = unbounded, aligned bottom-right per batch item:
+                                  lo = r + off_b - left, hi = r + off_b + right + 1 with off_b = kv_len[b] - Sq
+      causal=True                 window=(-1, 0)
+    With a range the call is ONE launch for the whole batch whatever kv_len holds: host values are folded into hi, and a kv_len
+    that is a device tensor is folded on the device and never read on the host.  Without one nothing changes."""
     blk = _check_block_pair(block_size, block_size)
+    if int(bool(causal)) + (window is not None) + (row_range is not None) > 1:
+        raise ValueError("causal, window and row_range exclude one another: give at most one")
+    ranged = bool(causal) or window is not None or row_range is not None
+    if ranged and blk != _lib.BLOCK:
+        raise NotImplementedError(f"causal / window / row_range need block_size = {_lib.BLOCK}: 64-token blocks run the "
+                                  "32-rows-per-wave kernel, which has one key limit per launch and no per-row range")
+    if window is not None:
+        window = _check_window(window)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError("q, k, v: [B, H, S, D] tensors")
     B, H, Sq, D = q.shape
@@ -141,11 +255,29 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
             or not 1 <= block_mask.shape[3] <= min(NKmax, MAX_KEY_BLOCKS)):
         raise ValueError(f"block_mask {tuple(block_mask.shape)}: expected [{B}|1, {H}|1, {NQ}, 1..{min(NKmax, MAX_KEY_BLOCKS)}] "
                          f"for block {blk} (at most {MAX_KEY_BLOCKS} key blocks)")
-    lens = _kv_lens(kv_len, B, Sk)
+    if row_range is not None:
+        row_range = _check_row_range(row_range, B, Sq, q.device)
+    on_device = ranged and isinstance(kv_len, torch.Tensor) and kv_len.is_cuda   # (then it is folded on the device, not read)
+    if on_device:
+        if kv_len.numel() not in (1, B) or kv_len.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"kv_len: an int32 / int64 tensor of 1 or {B} values, got {kv_len.dtype} {tuple(kv_len.shape)}")
+        lens = kv_len.to(q.device).reshape(-1)
+    else:
+        lens = _kv_lens(kv_len, B, Sk)
     _core._require_device(q, k, v)
     scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
     if block_mask.device != q.device:
         block_mask = block_mask.to(q.device)
+    if ranged:
+        if row_range is None:
+            lo, hi = _window_ranges(q.device, B, Sq, Sk, lens, *((-1, 0) if causal else window))
+        else:
+            lo, hi = row_range
+            if on_device:
+                hi = torch.minimum(hi, lens.reshape(-1, 1).clamp(0, Sk).to(torch.int32))
+            elif any(n != Sk for n in lens):     # fold the host limits: one small device op per distinct limit, no host read
+                hi = torch.stack([hi[b if hi.shape[0] > 1 else 0].clamp(max=lens[b]) for b in range(B)])
+        return _ranged_attention(q, k, v, block_mask, lens, scale, lo, hi)
     if D in _core._PAD_HEAD_DIM:   # zero columns add exact zeros to every dot product; the caller's scale is kept
         pad = (0, _core._PAD_HEAD_DIM[D] - D)
         F = torch.nn.functional

@@ -87,6 +87,13 @@ struct AttnArgs : WalkArgs {
     int rows256;                              // 64-row kernel, dense calls: NQB / NBv count 256-row tiles (four waves per workgroup, one K/V ring)
     int blk;                                  // tokens per block: 128 (the 64-row kernel), or 64 (sparse calls through the _ex entry points: the 32-row kernel)
     int txt0;                                 // blk 64: first text query row (NBv * 64); text units of 128 rows from there
+    // Per-row key ranges of a sparse call (rsa_block_sparse_ranged_fwd; the RANGED instantiations of the 64-row kernel): query
+    // row r of batch item b sees the keys [row_lo[b * range_sb + r], row_hi[b * range_sb + r]) of its kept blocks, clamped into
+    // [0, kv_valid].  row_hi NULL = no ranges (every other kernel and call); row_lo NULL = 0; range_sb 0 = one array for the batch.
+    // LAST members: every field above keeps the kernarg offset the kernels without ranges read it at.
+    const int32_t* row_lo;
+    const int32_t* row_hi;
+    long range_sb;
 };
 
 // The kernel's own arguments, read in place: the argument struct must be the kernel's ONLY parameter (it then sits at offset 0

@@ -314,6 +314,7 @@ static void fill_qkv(AttnArgs& a, const rsa_tensor4& q, const rsa_tensor4& k, co
     a.k = static_cast<const unsigned short*>(k.ptr); a.ksb = k.stride_b; a.ksh = k.stride_h; a.kss = k.stride_s;
     a.v = static_cast<const unsigned short*>(v.ptr); a.vsb = v.stride_b; a.vsh = v.stride_h; a.vss = v.stride_s;
     a.out = static_cast<unsigned short*>(out.ptr); a.osb = out.stride_b; a.osh = out.stride_h; a.oss = out.stride_s;
+    a.row_lo = nullptr; a.row_hi = nullptr; a.range_sb = 0;     // no per-row key ranges (rsa_block_sparse_ranged_fwd sets them)
 }
 
 int rsa_check_out(const rsa_out4& o) {
@@ -357,9 +358,10 @@ extern "C" int rsa_block_sparse_fwd_ex(const rsa_layout_ex* lx, rsa_tensor4 q, r
 // Plain block-sparse attention over caller-supplied lists (rsa_block_mask_to_lists): the sparse walk of the rectified call with
 // no R / comp (the epilogue stores acc / l), the caller's scale, Sq query rows in NQ blocks and no text rows (NQB = NBv = NQ, so
 // nothing is written past row Sq), Sk key rows of which those >= kv_valid are masked.
-extern "C" int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, int kv_valid,
-                                          double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* cols,
-                                          const int32_t* counts, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream) {
+// (the checks and the arguments rsa_block_sparse_plain_fwd and rsa_block_sparse_ranged_fwd share)
+static int plain_args(AttnArgs& a, int B, int H, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, int kv_valid,
+                      double sm_scale, const rsa_tensor4& q, const rsa_tensor4& k, const rsa_tensor4& v, const int32_t* cols,
+                      const int32_t* counts, float* tpart, size_t tpart_bytes, const rsa_out4& out) {
     if (block != 64 && block != RSA_BLOCK) return RSA_ERR_UNSUPPORTED;
     if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
     if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
@@ -373,7 +375,6 @@ extern "C" int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, i
     int st;
     if ((st = rsa_check_tensor(q)) || (st = rsa_check_tensor(k)) || (st = rsa_check_tensor(v)) || (st = rsa_check_out(out)))
         return st;
-    AttnArgs a;
     fill_qkv(a, q, k, v, out);
     a.cols = cols; a.counts = counts; a.R = nullptr; a.comp = nullptr;
     a.tpart = tpart;
@@ -383,6 +384,30 @@ extern "C" int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, i
     a.kv_valid = kv_valid; a.kv_text_valid = 0; a.q_text_end = 0;
     a.q_split = 0; a.kv_split = 0; a.causal = 0; a.rows256 = 0;
     a.qk_scale = (float)(sm_scale * 1.44269504);   // (as the reference kernel's launcher: hunyuan :145)
+    return RSA_OK;
+}
+extern "C" int rsa_block_sparse_plain_fwd(int B, int H, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, int kv_valid,
+                                          double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* cols,
+                                          const int32_t* counts, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream) {
+    AttnArgs a;
+    const int st = plain_args(a, B, H, Sq, Sk, D, dtype, block, NQ, NK, kv_valid, sm_scale, q, k, v, cols, counts, tpart, tpart_bytes, out);
+    if (st != RSA_OK) return st;
+    return launch_attn(a, B * H, D, dtype, tpart ? tpart_bytes : 0, static_cast<hipStream_t>(stream));
+}
+
+// ... with a key range per query row (rsa.h): the same walk through the RANGED instantiations of the 64-row kernel.  128-token
+// blocks only: the 32-row kernel, which walks 64-token blocks, masks against ONE scalar key limit per launch, not a range per row.
+extern "C" int rsa_block_sparse_ranged_fwd(int B, int H, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, int kv_valid,
+                                           double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* cols,
+                                           const int32_t* counts, const int32_t* row_lo, const int32_t* row_hi,
+                                           int64_t range_stride_b, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream) {
+    if (block != RSA_BLOCK) return RSA_ERR_UNSUPPORTED;
+    if (!row_hi || range_stride_b < 0) return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(row_lo) | reinterpret_cast<uintptr_t>(row_hi)) & 3) return RSA_ERR_BAD_ARG;
+    AttnArgs a;
+    const int st = plain_args(a, B, H, Sq, Sk, D, dtype, block, NQ, NK, kv_valid, sm_scale, q, k, v, cols, counts, tpart, tpart_bytes, out);
+    if (st != RSA_OK) return st;
+    a.row_lo = row_lo; a.row_hi = row_hi; a.range_sb = (long)range_stride_b;
     return launch_attn(a, B * H, D, dtype, tpart ? tpart_bytes : 0, static_cast<hipStream_t>(stream));
 }
 

@@ -44,6 +44,14 @@
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+// (the RANGED plan's reductions)
+__device__ __forceinline__ int k5w_max(int x, int y) { return x > y ? x : y; }
+__device__ __forceinline__ int k5w_wave_max(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = k5w_max(v, __shfl_xor(v, m, 64));
+    return v;
+}
+
 // block U without LDS-DMA (the C++-driven sub-steps)
 template <typename Tag, int U, int D>
 __device__ __forceinline__ void k5w_block(f32x16 (&SA)[2], f32x16 (&SB)[2], const f32x16 (&nm)[2], float (&l)[2], float (&mx)[2],
@@ -100,8 +108,12 @@ __device__ __forceinline__ f32x16 k5w_oread() {
 // every second piece dropped (gen_k5_block64.py, RSA_K5W_LOOP_*_R256); `qblk` then counts 256-row tiles (the host sets NQB so).
 // D (round 6): head dim 128 or 64 (CogVideoX).  At 64 a sub-step is 8 + 8 MFMAs against the same softmax, a half-tile 4 KiB = four
 // LDS-DMA pieces of 8 rows (two per wave); same register map in the arch file, O in a[0:63], Q in a[64:95].
-template <typename Tag, bool WIDE, int NW = 2, int D = 128>
+// RANGED: per-row key ranges of a sparse call (AttnArgs::row_lo / row_hi; rsa_block_sparse_ranged_fwd).  Two waves only; everything it
+// adds sits in the plan, under `if constexpr (RANGED)`: the rows' ranges take the place of [0, kv_valid), the tile's extremes steer
+// the walk as they do in a causal or two-segment dense call, and the kept list is trimmed to the blocks some row of the tile can see.
+template <typename Tag, bool WIDE, int NW = 2, int D = 128, bool RANGED = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) void bsfwd64_kernel(AttnArgs) {
+    static_assert(!RANGED || NW == 2, "per-row ranges: sparse calls only (128-row query blocks)");
     const AttnArgs& a = rsa_kernargs<AttnArgs>();
     constexpr int RW = 64 * NW;             // query rows per workgroup: NW waves x 64 rows
     constexpr int NPIECE = 32 * D * 2 / 1024;   // 1-KiB pieces of a 32-key half-tile: 8 (4 rows each) / 4 (8 rows each)
@@ -138,8 +150,64 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     if (a.mode == MODE_SPARSE) {
         if (qblk < a.NBv) {
             rsa_walk_list(a, (long)bh * a.NBv + qblk, tail, tsp, list, n_items);
-            lo_max = 0; hi_min = hi_max = a.kv_valid;
-            hi_r[0] = hi_r[1] = a.kv_valid;
+            if constexpr (RANGED) {
+                // The rows' own ranges, clamped into [0, kv_valid]; rows past the sequence take the last row's (as rsa_dense_row), so
+                // the extremes below are those of the tile's real rows.  An empty range (hi <= lo) becomes [0, 0): it pulls hi_min to
+                // 0, so every sub-step of the tile is masked, and it does not count for lo_min.
+                const int32_t* lo_p = a.row_lo ? a.row_lo + (long)b * a.range_sb : nullptr;
+                const int32_t* hi_p = a.row_hi + (long)b * a.range_sb;
+                const int kvv = a.kv_valid;
+                int red4[4] = {-kvv, 0, -kvv, 0};     // -lo_min, lo_max, -hi_min, hi_max of this lane's two rows
+#pragma unroll
+                for (int x = 0; x < 2; ++x) {
+                    const int row = grow[x] < a.Sq ? grow[x] : a.Sq - 1;
+                    int lo = lo_p ? lo_p[row] : 0, hi = hi_p[row];
+                    lo = lo < 0 ? 0 : (lo < kvv ? lo : kvv);
+                    hi = hi < 0 ? 0 : (hi < kvv ? hi : kvv);
+                    const bool none = hi <= lo;
+                    lo_r[x] = none ? 0 : lo;
+                    hi_r[x] = none ? 0 : hi;
+                    red4[0] = k5w_max(red4[0], none ? -kvv : -lo);
+                    red4[1] = k5w_max(red4[1], lo_r[x]);
+                    red4[2] = k5w_max(red4[2], -hi_r[x]);
+                    red4[3] = k5w_max(red4[3], hi_r[x]);
+                }
+                // The extremes steer i0 / nfull / i1 and the barriers inside `step`: they must be the same in both waves.  Each wave
+                // reduces its 64 lanes, then the two meet in LDS -- the head of the K ring, which nothing touches before the first staging.
+                int* red = reinterpret_cast<int*>(lds);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int m = k5w_wave_max(red4[i]);
+                    if (lane == 0) red[4 * wv + i] = m;
+                }
+                __syncthreads();
+                const int lo_min = -__builtin_amdgcn_readfirstlane(k5w_max(red[0], red[4]));
+                lo_max = __builtin_amdgcn_readfirstlane(k5w_max(red[1], red[5]));
+                hi_min = -__builtin_amdgcn_readfirstlane(k5w_max(red[2], red[6]));
+                hi_max = __builtin_amdgcn_readfirstlane(k5w_max(red[3], red[7]));
+                // Trim the (ascending) list -- a tail piece's own part of it -- to the blocks some row of the tile can see: entries
+                // with blk * 128 >= hi_max go from its end, entries with blk * 128 + 128 <= lo_min from its front, 64 entries per step
+                // (every wave counts for itself: same list, same result).  A piece may end up with nothing: its partial is then
+                // m = -inf, l = 0, which the combine pass gives weight 0.
+                // INVARIANT the staging relies on: n_items > 0 implies hi_max >= 1 (a kept entry has blk * 128 < hi_max), so the key
+                // rows dma_half clamps to kv_limit - 1 = min(hi_max, Sk) - 1 are never clamped to row -1.
+                const int bhi = (hi_max + RSA_BLOCK - 1) / RSA_BLOCK, blo = lo_min / RSA_BLOCK;
+                int keep = 0, skip = 0;
+                for (int base = 0; base < n_items; base += 64) {
+                    const int i = base + lane;
+                    const int e = i < n_items ? list[i] : 0x7FFFFFFF;
+                    const int c = __builtin_popcountll(__builtin_amdgcn_ballot_w64(e < bhi));
+                    keep += c;
+                    skip += __builtin_popcountll(__builtin_amdgcn_ballot_w64(e < blo));
+                    if (c < 64) break;
+                }
+                skip = skip < keep ? skip : keep;
+                list += skip;
+                n_items = keep - skip;
+            } else {
+                lo_max = 0; hi_min = hi_max = a.kv_valid;
+                hi_r[0] = hi_r[1] = a.kv_valid;
+            }
         } else {
             rsa_walk_text(a, RSA_BLOCK, tsp, first_blk, n_items);
             lo_max = 0; hi_min = hi_max = a.kv_text_valid;
@@ -545,16 +613,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     finish_half(std::integral_constant<int, 1>{});
 }
 
-// the four instantiations (dtype x store width) of the NW-wave kernel at head dim D
-template <int NW, int D>
+// the four instantiations (dtype x store width) of the NW-wave kernel at head dim D (RANGED: with per-row key ranges)
+template <int NW, int D, bool RANGED = false>
 static int launch_bsfwd64(const AttnArgs& a, bool wide, int dtype, dim3 grid, size_t lds_bytes, hipStream_t s) {
     const bool sparse = a.mode == MODE_SPARSE;
     if (dtype == RSA_BF16) {
-        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, NW, D>), a, sparse, grid, 64 * NW, lds_bytes, s);
-        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false, NW, D>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, NW, D, RANGED>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false, NW, D, RANGED>), a, sparse, grid, 64 * NW, lds_bytes, s);
     } else {
-        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true, NW, D>), a, sparse, grid, 64 * NW, lds_bytes, s);
-        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false, NW, D>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true, NW, D, RANGED>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false, NW, D, RANGED>), a, sparse, grid, 64 * NW, lds_bytes, s);
     }
     return rsa_launch_status();
 }
@@ -567,6 +635,11 @@ int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, in
     if (a.rows256) {     // dense calls: 256-row tiles, four waves on one K/V ring (the host counted the grid in such tiles)
         if (a.mode != MODE_DENSE) return RSA_ERR_BAD_ARG;
         return D == 128 ? launch_bsfwd64<4, 128>(a, wide, dtype, grid, lds_bytes, s) : launch_bsfwd64<4, 64>(a, wide, dtype, grid, lds_bytes, s);
+    }
+    if (a.row_hi) {      // per-row key ranges: the sparse walk's RANGED instantiations (the host checked the rest)
+        if (a.mode != MODE_SPARSE) return RSA_ERR_BAD_ARG;
+        return D == 128 ? launch_bsfwd64<2, 128, true>(a, wide, dtype, grid, lds_bytes, s)
+                        : launch_bsfwd64<2, 64, true>(a, wide, dtype, grid, lds_bytes, s);
     }
     return D == 128 ? launch_bsfwd64<2, 128>(a, wide, dtype, grid, lds_bytes, s) : launch_bsfwd64<2, 64>(a, wide, dtype, grid, lds_bytes, s);
 }
