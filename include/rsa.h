@@ -268,6 +268,25 @@ int rsa_block_sparse_ranged_fwd(int B, int H, int Sq, int Sk, int D, int dtype, 
                                 const int32_t* counts, const int32_t* row_lo, const int32_t* row_hi, int64_t range_stride_b,
                                 float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream);
 
+/* The same two calls with grouped-query K/V heads (GQA; Hkv = 1: MQA; found by symbol: the header version stays 6.1).  q and out
+ * hold H heads, k and v Hkv, H a multiple of Hkv; query head h reads K/V head h / (H / Hkv) -- the convention of flash-attn and of
+ * torch's enable_gqa, the result of repeating every K/V head H / Hkv times along the head axis, without the copies.  cols / counts
+ * hold Hl list heads per batch item ([B * Hl, NQ, NK] / [B * Hl, NQ], H a multiple of Hl): head h walks list row
+ * (b * Hl + h / (H / Hl)) * NQ + query block.  Hl = Hkv is one selection per K/V head (NSA- and MoBA-style), Hl = 1 one for all heads,
+ * Hl = H one per query head.  row_hi NULL (then row_lo NULL too): no ranges, else as rsa_block_sparse_ranged_fwd.
+ * Two forms, same softmax: (a) every query head a walk of its own -- the launch of the MHA call, byte for byte what that call gives
+ * on repeated K/V and lists; (b) two query heads of one K/V head and one list row as the four waves of one workgroup on ONE K/V
+ * ring, where block = 128 and H / Hkv and H / Hl are even (no tail split then).  (b) equals (a) byte for byte unless a bf16 walk's
+ * optimistic softmax reference overflowed: the workgroup then redoes BOTH heads' walks through the online body.  The library takes
+ * (a) unless the tuning key k5_gqa_pair is 1.  Hkv = Hl = H launches what the two entries above launch.
+ * H, Hkv or Hl non-positive or not dividing H: RSA_ERR_BAD_ARG; ranges with block 64: RSA_ERR_UNSUPPORTED; row_lo without row_hi, a
+ * negative stride, a misaligned range array: RSA_ERR_BAD_ARG; besides, everything rsa_block_sparse_plain_fwd refuses.  The
+ * rectified calls, the selection pass and the e4m3 forms have no grouped form: they pool K per head. */
+int rsa_block_sparse_gqa_fwd(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK,
+                             int kv_valid, double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                             const int32_t* cols, const int32_t* counts, const int32_t* row_lo, const int32_t* row_hi,
+                             int64_t range_stride_b, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

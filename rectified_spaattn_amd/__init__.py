@@ -43,7 +43,8 @@ def block_sparse_attention(q, k, v, block_mask, *, kv_len=None, sm_scale=None, b
                            row_range=None):
     """Block-sparse attention over a block mask of the caller's own: q [B,H,Sq,D], k / v [B,H,Sk,D], block_mask bool / uint8
     [B|1, H|1, ceil(Sq/block), NK] -> [B,H,Sq,D]; causal / window=(left, right) / row_range=(lo, hi) add a key range per query
-    row.  See rectified_spaattn_amd.block_sparse.block_sparse_attention."""
+    row; k / v may hold Hkv < H heads (GQA / MQA: query head h reads K/V head h // (H // Hkv); mask head axis H, Hkv or 1).
+    See rectified_spaattn_amd.block_sparse.block_sparse_attention."""
     from . import block_sparse
     return block_sparse.block_sparse_attention(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                                causal=causal, window=window, row_range=row_range)

@@ -20,6 +20,7 @@ RSA_BF16, RSA_FP16 = 0, 1
 BLOCK = 128
 BLOCKS = (64, 128)     # block sizes the library serves (64 through the _ex entry points, rsa.h 0.6.1)
 HEADER_VERSION = 601   # RSA_HEADER_VERSION of include/rsa.h this ctypes mirror follows (rsa_abi_check)
+GQA_PAIR_DEFAULT = 0   # the library's default of the tuning key k5_gqa_pair (grouped-query calls: 0 = one walk per query head)
 
 
 class RsaError(RuntimeError):
@@ -129,6 +130,9 @@ def lib():
     L.rsa_block_sparse_ranged_fwd.argtypes = ([i32] * 10 + [ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, vp, vp, vp, i64,
                                               vp, sz, RsaOut4, vp])
     L.rsa_block_sparse_ranged_fwd.restype = i32
+    L.rsa_block_sparse_gqa_fwd.argtypes = ([i32] * 12 + [ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, vp, vp, vp, i64,
+                                           vp, sz, RsaOut4, vp])
+    L.rsa_block_sparse_gqa_fwd.restype = i32
     L.rsa_select_from_mask.argtypes = [P(RsaLayout), vp, i64, i64, i64, P(RsaBuffers), vp]
     L.rsa_select_from_mask_ex.argtypes = [P(RsaLayoutEx), vp, i64, i64, i64, P(RsaBuffers), vp]
     L.rsa_rectified_attention_masked.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, vp, i64, i64, i64, vp, sz,
@@ -193,7 +197,7 @@ def lib():
                  "rsa_rectified_attention_ex", "rsa_estimate_pr_gain_ex"):
         getattr(L, name).restype = i32
     # kernel-variant switches for A/B runs and the variant tests; rsa_set_tuning works only under RSA_TUNING=1
-    for key in ("k5_tsplit", "k3_prefix", "k3_long", "k4_split", "k5_rows256", "k5_static", "k5_gsync", "k5_gsync_ratio", "k5_text_last", "k5_tail_split"):
+    for key in ("k5_tsplit", "k3_prefix", "k3_long", "k4_split", "k5_rows256", "k5_static", "k5_gsync", "k5_gsync_ratio", "k5_text_last", "k5_tail_split", "k5_gqa_pair"):
         val = os.environ.get("RSA_" + key.upper())
         if val is not None:
             check_rc = L.rsa_set_tuning(key.encode(), int(val))
@@ -214,6 +218,7 @@ EXPORTED = ("rsa_version", "rsa_abi_check", "rsa_buffer_bytes", "rsa_carve_works
             "rsa_ipc_offset", "rsa_buffer_bytes_ex", "rsa_carve_workspace_ex", "rsa_pool_stats_ex", "rsa_pooled_scores_ex",
             "rsa_select_mask_ex", "rsa_compensation_ex", "rsa_block_sparse_fwd_ex", "rsa_rectified_attention_ex", "rsa_estimate_pr_gain_ex",
             "rsa_block_mask_to_lists", "rsa_lists_to_block_mask", "rsa_block_sparse_plain_fwd", "rsa_block_sparse_ranged_fwd",
+            "rsa_block_sparse_gqa_fwd",
             "rsa_select_from_mask", "rsa_select_from_mask_ex", "rsa_rectified_attention_masked", "rsa_rectified_attention_masked_ex")
 
 

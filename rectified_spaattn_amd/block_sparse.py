@@ -7,6 +7,8 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
     block_sparse_attention   K5 without the rectifying epilogue (rsa_block_sparse_plain_fwd) over the lists
                              rsa_block_mask_to_lists makes from the caller's mask; with causal= / window= / row_range= a key
                              range per query row on top of the mask (rsa_block_sparse_ranged_fwd, one launch per batch)
+                             k / v may hold fewer heads than q (GQA / MQA: query head h reads K/V head h // (H // Hkv)) and
+                             the mask one row per K/V head: rsa_block_sparse_gqa_fwd, no repeated K/V and no repeated lists
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
@@ -78,6 +80,24 @@ def lists_to_block_mask(bitmask: torch.Tensor, B: int, H: int, NQ: int, NK: int)
     return out
 
 
+def gqa_kv_head(h: int, H: int, Hkv: int) -> int:
+    """The K/V head query head h reads when k / v hold Hkv heads for H query heads: h // (H // Hkv), flash-attn's and torch's
+    enable_gqa convention -- what k.repeat_interleave(H // Hkv, dim=1)[:, h] holds.  The same map takes h to its list head."""
+    if H <= 0 or Hkv <= 0 or H % Hkv or not 0 <= h < H:
+        raise ValueError(f"head {h} of H = {H} query heads over Hkv = {Hkv} heads: Hkv must divide H")
+    return h // (H // Hkv)
+
+
+def gqa_pairable(H: int, Hkv: int, Hl: int, block: int) -> bool:
+    """Whether a grouped-query call can run two query heads per workgroup on one K/V ring (form (b)):
+    128-token blocks, and heads 2p and 2p + 1 share both their K/V head (H // Hkv even) and their list row (H // Hl even, Hl = the
+    mask's head axis).  Everything else runs one walk per query head (form (a)); so does every call unless the tuning key
+    k5_gqa_pair is 1."""
+    if min(H, Hkv, Hl) <= 0 or H % Hkv or H % Hl:
+        raise ValueError(f"H = {H} query heads over Hkv = {Hkv} K/V heads and Hl = {Hl} list heads: both must divide H")
+    return block == _lib.BLOCK and (H // Hkv) % 2 == 0 and (H // Hl) % 2 == 0
+
+
 _TAIL_CACHE: "Dict[tuple, torch.Tensor]" = {}
 
 
@@ -111,6 +131,12 @@ def _kv_lens(kv_len, B: int, Sk: int):
     if any(n < 0 or n > Sk for n in lens):
         raise ValueError(f"kv_len {lens} outside [0, {Sk}]")
     return lens
+
+
+def _list_heads(block_mask: torch.Tensor, H: int, Hkv: int) -> int:
+    """List heads per batch item of a call: with as many K/V heads as query heads H, as ever (a mask head axis of 1 is expanded);
+    with fewer, the mask's own head axis -- 1, Hkv or H -- so that shared lists are built and kept once."""
+    return H if Hkv == H else int(block_mask.shape[1])
 
 
 _RANGE_CACHE: "Dict[tuple, tuple]" = {}
@@ -174,7 +200,7 @@ def _window_ranges(device, B: int, Sq: int, Sk: int, lens, left: int, right: int
 def _ranged_attention(q, k, v, block_mask, lens, scale: float, lo, hi) -> torch.Tensor:
     """One launch of rsa_block_sparse_ranged_fwd for the whole batch.  lens: B host ints, or a device tensor [B|1] (not read)."""
     B, H, Sq, D = q.shape
-    Sk = k.shape[2]
+    Hkv, Sk = k.shape[1], k.shape[2]
     if isinstance(lens, torch.Tensor):
         kv_valid = Sk
     else:
@@ -193,10 +219,20 @@ def _ranged_attention(q, k, v, block_mask, lens, scale: float, lo, hi) -> torch.
     L = _lib.lib()
     q, k, v = _core._as_bhsd(q), _core._as_bhsd(k), _core._as_bhsd(v)
     NQ, NK = -(-Sq // _lib.BLOCK), block_mask.shape[3]
-    lists = block_mask_to_lists(block_mask, B, H)
+    Hl = _list_heads(block_mask, H, Hkv)
+    lists = block_mask_to_lists(block_mask, B, Hl)
     out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=q.device)
     tpart = _tail_buffer(q.device) if D == 128 else None
     tp, tpb = (tpart.data_ptr(), tpart.numel() * 4) if tpart is not None else (None, 0)
+    if Hkv != H:
+        with torch.cuda.device(q.device):
+            _lib.check(L.rsa_block_sparse_gqa_fwd(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), _lib.BLOCK, NQ, NK, kv_valid,
+                                                  scale, _core._t4(q), _core._t4(k), _core._t4(v), lists["cols"].data_ptr(),
+                                                  lists["counts"].data_ptr(), lo.data_ptr() if lo is not None else None,
+                                                  hi.data_ptr(), 0 if hi.shape[0] == 1 else Sq, tp, tpb,
+                                                  RsaOut4(out.data_ptr(), out.stride(0), out.stride(1), out.stride(2)),
+                                                  _core._stream()), "rsa_block_sparse_gqa_fwd")
+        return out
     with torch.cuda.device(q.device):
         _lib.check(L.rsa_block_sparse_ranged_fwd(B, H, Sq, Sk, D, _core.dtype_code(q.dtype), _lib.BLOCK, NQ, NK, kv_valid, scale,
                                                  _core._t4(q), _core._t4(k), _core._t4(v), lists["cols"].data_ptr(),
@@ -211,7 +247,8 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
                            sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, window=None,
                            row_range=None) -> torch.Tensor:
     """softmax(sm_scale q k^T) v restricted, per query block i, to the key blocks j with block_mask[b, h, i, j] set and to the
-    keys < kv_len.  q [B,H,Sq,D], k / v [B,H,Sk,D] (any strides with a contiguous head dim: [B,S,H,D] views need no copy);
+    keys < kv_len.  q [B,H,Sq,D], k / v [B,H,Sk,D] or with fewer K/V heads (last paragraph); any strides with a contiguous head
+    dim: [B,S,H,D] views need no copy;
     block_mask bool / uint8 [B|1, H|1, ceil(Sq/block), NK] with NK <= ceil(Sk/block) (keys past NK * block are never visited);
     kv_len None (= Sk), an int, or one value per batch item (a tensor costs one host read; distinct values run one launch per
     batch item); sm_scale defaults to D ** -0.5.  Returns [B,H,Sq,D] in the input dtype.  A row without a visible key is 0
@@ -226,7 +263,15 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
                                   lo = r + off_b - left, hi = r + off_b + right + 1 with off_b = kv_len[b] - Sq
       causal=True                 window=(-1, 0)
     With a range the call is ONE launch for the whole batch whatever kv_len holds: host values are folded into hi, and a kv_len
-    that is a device tensor is folded on the device and never read on the host.  Without one nothing changes."""
+    that is a device tensor is folded on the device and never read on the host.  Without one nothing changes.
+
+    Grouped-query K/V heads (GQA; MQA with one): k / v [B,Hkv,Sk,D] with H % Hkv == 0.  Query head h reads K/V head
+    h // (H // Hkv) -- flash-attn's and torch's enable_gqa convention, the result of k.repeat_interleave(H // Hkv, dim=1) without
+    the g-fold K/V memory and traffic; q, k, v as head-strided views of one fused projection [B, S, (H + 2 Hkv) D] need no copy.
+    The mask's head axis is then H (one row per query head), Hkv (one per K/V head, shared by its H // Hkv query heads: the lists
+    are built once per K/V head) or 1.  Both block sizes; ranges with 128-token blocks as above.  With Hkv == H nothing changes.
+    Only this call is grouped: triton_block_sparse_attention_onehot, build_block_index, the rectified_* calls and the fp8
+    switches stay MHA-only (the selection statistics pool K per head, and the reference has no grouped form)."""
     blk = _check_block_pair(block_size, block_size)
     if int(bool(causal)) + (window is not None) + (row_range is not None) > 1:
         raise ValueError("causal, window and row_range exclude one another: give at most one")
@@ -240,7 +285,12 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
         raise ValueError("q, k, v: [B, H, S, D] tensors")
     B, H, Sq, D = q.shape
     Sk = k.shape[2]
-    if k.shape != v.shape or k.shape[0] != B or k.shape[1] != H or k.shape[3] != D:
+    Hkv = k.shape[1]
+    if v.shape[1] != Hkv:
+        raise ValueError(f"k has Hkv = {Hkv} heads, v {v.shape[1]}: k and v must hold the same K/V heads")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h reads K/V head h // (H // Hkv))")
+    if k.shape != v.shape or k.shape[0] != B or k.shape[3] != D:
         raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
     if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
         raise ValueError(f"q, k, v: one dtype, bfloat16 or float16 (got {q.dtype}, {k.dtype}, {v.dtype})")
@@ -251,7 +301,10 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
     NQ, NKmax = -(-Sq // blk), -(-Sk // blk)
     if block_mask.dim() != 4 or block_mask.dtype not in (torch.bool, torch.uint8):
         raise ValueError(f"block_mask: a 4-d bool or uint8 tensor, got {block_mask.dtype} {tuple(block_mask.shape)}")
-    if (block_mask.shape[0] not in (1, B) or block_mask.shape[1] not in (1, H) or block_mask.shape[2] != NQ
+    if Hkv != H and block_mask.shape[1] not in (1, Hkv, H):
+        raise ValueError(f"block_mask {tuple(block_mask.shape)}: a head axis of {H} (per query head), Hkv = {Hkv} (per K/V head) "
+                         "or 1")
+    if (block_mask.shape[0] not in (1, B) or block_mask.shape[1] not in (1, Hkv, H) or block_mask.shape[2] != NQ
             or not 1 <= block_mask.shape[3] <= min(NKmax, MAX_KEY_BLOCKS)):
         raise ValueError(f"block_mask {tuple(block_mask.shape)}: expected [{B}|1, {H}|1, {NQ}, 1..{min(NKmax, MAX_KEY_BLOCKS)}] "
                          f"for block {blk} (at most {MAX_KEY_BLOCKS} key blocks)")
@@ -286,7 +339,8 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
     L = _lib.lib()
     q, k, v = _core._as_bhsd(q), _core._as_bhsd(k), _core._as_bhsd(v)
     NK = block_mask.shape[3]
-    lists = block_mask_to_lists(block_mask, B, H)
+    Hl = _list_heads(block_mask, H, Hkv)
+    lists = block_mask_to_lists(block_mask, B, Hl)
     out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=q.device)
     # the tail split's partial buffer (head dim 128, 128-token blocks: the rectified call's K5 gets the same)
     tpart = _tail_buffer(q.device) if D == 128 and blk == _lib.BLOCK else None
@@ -299,8 +353,14 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
             if n == 0:   # no visible key at all
                 out[b0:b1].zero_()
                 continue
-            row = H * NQ * b0
+            row = Hl * NQ * b0
             o4 = RsaOut4(out[b0].data_ptr(), out.stride(0), out.stride(1), out.stride(2))
+            if Hkv != H:
+                _lib.check(L.rsa_block_sparse_gqa_fwd(b1 - b0, H, Hkv, Hl, Sq, Sk, D, dt, blk, NQ, NK, n, scale, _core._t4(q[b0:b1]),
+                                                      _core._t4(k[b0:b1]), _core._t4(v[b0:b1]),
+                                                      lists["cols"].data_ptr() + row * NK * 4, lists["counts"].data_ptr() + row * 4,
+                                                      None, None, 0, tp, tpb, o4, _core._stream()), "rsa_block_sparse_gqa_fwd")
+                continue
             _lib.check(L.rsa_block_sparse_plain_fwd(b1 - b0, H, Sq, Sk, D, dt, blk, NQ, NK, n, scale, _core._t4(q[b0:b1]),
                                                     _core._t4(k[b0:b1]), _core._t4(v[b0:b1]),
                                                     lists["cols"].data_ptr() + row * NK * 4, lists["counts"].data_ptr() + row * 4,

@@ -94,7 +94,13 @@ struct AttnArgs : WalkArgs {
     const int32_t* row_lo;
     const int32_t* row_hi;
     long range_sb;
+    // Grouped-query K/V heads (rsa_block_sparse_gqa_fwd; the GQA instantiations): query head h reads K/V head h / kv_group and
+    // walks the lists of list head h / list_group (H / list_group list heads per batch item).  gqa: 0 = none (1 / 1: every other
+    // call, whose kernels read none of the three), RSA_GQA_HEAD = each query head a walk of its own, RSA_GQA_PAIR = two query
+    // heads of one K/V head and one list per workgroup (BH then counts head PAIRS).  Behind the ranges for the same reason.
+    int kv_group, list_group, gqa;
 };
+enum { RSA_GQA_NONE = 0, RSA_GQA_HEAD = 1, RSA_GQA_PAIR = 2 };
 
 // The kernel's own arguments, read in place: the argument struct must be the kernel's ONLY parameter (it then sits at offset 0
 // of the kernarg segment).  The 64-row and 32-row kernels take their arguments this way, not through the by-value parameter: once
@@ -238,6 +244,9 @@ int rsa_plan_walk(WalkArgs& a, int BH, int D, const WalkPolicy& pol, size_t tpar
 int rsa_combine_walk(const WalkArgs& a, int D, int blk, int dtype, hipStream_t s);
 int rsa_launch_bsfwd(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s);     // rsa_attn_kernel.hip
 int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s);   // rsa_attn_kernel64.hip
+// ... its grouped-query instantiations (a.gqa != RSA_GQA_NONE; wide / lds_bytes as rsa_launch_bsfwd64 worked them out): rsa_attn_kernel64_gqa.hip, _gqa_pair.hip
+int rsa_launch_bsfwd64_gqa(const AttnArgs& a, bool wide, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s);
+int rsa_launch_bsfwd64_gqa_pair(const AttnArgs& a, bool wide, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s);
 int rsa_check_out(const rsa_out4& o);
 void rsa_set_fp8_variant(int v);      // rsa_attn_fp8_kernel.hip; tuning key "fp8_variant"
 void rsa_set_fp8_smooth_k(int v);     // rsa_fp8.hip; tuning key "fp8_smooth_k"

@@ -23,6 +23,7 @@ int rsa_gsync_ratio() { return g_k5_gsync_ratio; }
 static int g_k5_rows256 = 1;    // dense calls at head dim 128: 256-row tiles (0 = 128-row tiles, the sparse calls' form)
 static int g_k5_static = 1;     // 64-row kernel, bf16: optimistic static softmax reference in the steady-state loop (0 = online body only)
 int rsa_k5_static() { return g_k5_static; }
+static int g_k5_gqa_pair = 0;   // grouped-query calls: 1 = two query heads of one K/V head and one list share a workgroup's K/V ring where they can (rsa_gqa_form)
 static int g_k5_gsync = 1;      // aligned starts of the sparse walks (rsa_attn.h): bit 0 = in the 64-row kernel, bit 1 = in the 32-row (64-token blocks) and e4m3 kernels
 
 // Tuning / diagnostics hook (not part of the data path).  The switches are process-global, so the hook only works in a
@@ -43,6 +44,7 @@ extern "C" int rsa_set_tuning(const char* key, int value) {
     if (strcmp(key, "k5_gsync_ratio") == 0) { g_k5_gsync_ratio = value; return RSA_OK; }
     if (strcmp(key, "k5_text_last") == 0) { g_k5_text_last = value; return RSA_OK; }
     if (strcmp(key, "k5_tail_split") == 0) { g_k5_tail_split = value; return RSA_OK; }
+    if (strcmp(key, "k5_gqa_pair") == 0) { g_k5_gqa_pair = value; return RSA_OK; }
     if (strcmp(key, "fp8_variant") == 0) { rsa_set_fp8_variant(value); return RSA_OK; }
     if (strcmp(key, "fp8_smooth_k") == 0) { rsa_set_fp8_smooth_k(value); return RSA_OK; }
     return RSA_ERR_BAD_ARG;
@@ -298,7 +300,8 @@ static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes
     WalkPolicy pol;
     pol.blk = a.blk;
     pol.short_grid_text_cap = RSA_TEXT_SPLIT;
-    pol.tail_split = w64 && D == 128;       // (only the 64-row kernel stores a tail piece, and only at head dim 128)
+    // (only the 64-row kernel stores a tail piece, and only at head dim 128; a piece's partial holds 128 rows, a head pair has 256)
+    pol.tail_split = w64 && D == 128 && a.gqa != RSA_GQA_PAIR;
     pol.tail_beside_text = true;
     int st = rsa_plan_walk(a, BH, D, pol, tpart_bytes, &nblocks);
     if (st != RSA_OK || nblocks == 0) return st;
@@ -315,6 +318,7 @@ static void fill_qkv(AttnArgs& a, const rsa_tensor4& q, const rsa_tensor4& k, co
     a.v = static_cast<const unsigned short*>(v.ptr); a.vsb = v.stride_b; a.vsh = v.stride_h; a.vss = v.stride_s;
     a.out = static_cast<unsigned short*>(out.ptr); a.osb = out.stride_b; a.osh = out.stride_h; a.oss = out.stride_s;
     a.row_lo = nullptr; a.row_hi = nullptr; a.range_sb = 0;     // no per-row key ranges (rsa_block_sparse_ranged_fwd sets them)
+    a.kv_group = 1; a.list_group = 1; a.gqa = RSA_GQA_NONE;     // every head its own K/V head and lists (rsa_block_sparse_gqa_fwd sets them)
 }
 
 int rsa_check_out(const rsa_out4& o) {
@@ -409,6 +413,34 @@ extern "C" int rsa_block_sparse_ranged_fwd(int B, int H, int Sq, int Sk, int D, 
     if (st != RSA_OK) return st;
     a.row_lo = row_lo; a.row_hi = row_hi; a.range_sb = (long)range_stride_b;
     return launch_attn(a, B * H, D, dtype, tpart ? tpart_bytes : 0, static_cast<hipStream_t>(stream));
+}
+
+// ... with grouped-query K/V heads (rsa.h): k / v hold Hkv heads, the lists Hl per batch item.  Form (b), a head pair per workgroup,
+// where two neighbouring query heads share both their K/V head and their list row and the kernel is the 64-row one; else form (a),
+// the MHA launch with two divisions in its address arithmetic.  Hkv = Hl = H is the MHA call itself: the kernels of the two
+// entries above.
+static int rsa_gqa_form(int H, int Hkv, int Hl, int block, int pair_enabled) {
+    if (Hkv == H && Hl == H) return RSA_GQA_NONE;
+    const bool pair = pair_enabled && block == RSA_BLOCK && (H / Hkv) % 2 == 0 && (H / Hl) % 2 == 0;
+    return pair ? RSA_GQA_PAIR : RSA_GQA_HEAD;
+}
+extern "C" int rsa_block_sparse_gqa_fwd(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK,
+                                        int kv_valid, double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                                        const int32_t* cols, const int32_t* counts, const int32_t* row_lo, const int32_t* row_hi,
+                                        int64_t range_stride_b, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream) {
+    if (H <= 0 || Hkv <= 0 || Hl <= 0 || H % Hkv || H % Hl) return RSA_ERR_BAD_ARG;
+    if (row_hi && block == 64) return RSA_ERR_UNSUPPORTED;     // (the 32-row kernel has no per-row range)
+    if ((!row_hi && row_lo) || range_stride_b < 0) return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(row_lo) | reinterpret_cast<uintptr_t>(row_hi)) & 3) return RSA_ERR_BAD_ARG;
+    AttnArgs a;
+    const int st = plain_args(a, B, H, Sq, Sk, D, dtype, block, NQ, NK, kv_valid, sm_scale, q, k, v, cols, counts, tpart, tpart_bytes, out);
+    if (st != RSA_OK) return st;
+    a.row_lo = row_lo; a.row_hi = row_hi; a.range_sb = row_hi ? (long)range_stride_b : 0;
+    a.kv_group = H / Hkv; a.list_group = H / Hl;
+    a.gqa = rsa_gqa_form(H, Hkv, Hl, block, g_k5_gqa_pair);
+    // a head pair per workgroup: the walk plan counts pairs (rsa_walk_map itself is the MHA call's)
+    const int BH = a.gqa == RSA_GQA_PAIR ? B * (H / 2) : B * H;
+    return launch_attn(a, BH, D, dtype, tpart ? tpart_bytes : 0, static_cast<hipStream_t>(stream));
 }
 
 static int dense_fwd(int B, int H, int Sq, int Sk, int D, int dtype, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,

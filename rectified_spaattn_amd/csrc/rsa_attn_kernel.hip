@@ -92,7 +92,9 @@ __device__ __forceinline__ void k5_block(f32x16 (&o)[2], const s16x8 (&q)[4], f3
 // NEGM (head dim 128): the score chain starts from -m and the row sums are added into l_run.  Head dim 64: the classic
 // arithmetic with the row sums in lacc.  The two differ by the rounding order of S - m.
 // WIDE: 16-byte output stores after a permlane32_swap regroup (needs 16-byte aligned output rows), else 8-byte stores.
-template <int D, typename Tag, bool WIDE>
+// GQA: grouped-query K/V heads of a sparse call (AttnArgs::kv_group / list_group; rsa_block_sparse_gqa_fwd): the walk of query head
+// h with the K/V head h / kv_group and the lists of list head h / list_group; nothing else changes.
+template <int D, typename Tag, bool WIDE, bool GQA = false>
 __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     const AttnArgs& a = rsa_kernargs<AttnArgs>();
     constexpr bool NEGM = D == 128;
@@ -117,6 +119,8 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     if (walk == WALK_NONE) return;
     const bool text = walk == WALK_TEXT;
     const int b = bh / a.H, h = bh % a.H;
+    long lbh = bh;                          // list head of this head: its own, or the one it shares (h / list_group)
+    if constexpr (GQA) lbh = (long)b * (a.H / a.list_group) + h / a.list_group;
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int r = lane & 31, hh = lane >> 5;
@@ -130,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     const int32_t* list = nullptr;
     bool rectify = false;
     if (!text) {
-        rsa_walk_list(a, (long)bh * a.NBv + 2 * qblk, -1, 0, list, n_items);
+        rsa_walk_list(a, lbh * a.NBv + 2 * qblk, -1, 0, list, n_items);
         hi = a.kv_valid;
         rectify = a.R != nullptr;
         store_r = grow < a.Sq && qw < a.NBv;
@@ -155,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
         for (int hb = 0; hb < 2; ++hb) {
             const int qb = 2 * qblk + hb;
             if (qb < a.NBv) {
-                const long ri = (long)bh * a.NBv + qb;
+                const long ri = lbh * a.NBv + qb;
                 const int32_t* li = a.cols + ri * a.NB_total;
                 const int n = a.counts[ri];
                 for (int i = t; i < n; i += 64 * NW) {
@@ -218,8 +222,10 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     }
 
     // ---------------- LDS-DMA staging ----------------
-    const unsigned char* kbase = reinterpret_cast<const unsigned char*>(a.k + (long)b * a.ksb + (long)h * a.ksh);
-    const unsigned char* vbase = reinterpret_cast<const unsigned char*>(a.v + (long)b * a.vsb + (long)h * a.vsh);
+    int hkv = h;                            // the K/V head
+    if constexpr (GQA) hkv = h / a.kv_group;
+    const unsigned char* kbase = reinterpret_cast<const unsigned char*>(a.k + (long)b * a.ksb + (long)hkv * a.ksh);
+    const unsigned char* vbase = reinterpret_cast<const unsigned char*>(a.v + (long)b * a.vsb + (long)hkv * a.vsh);
     // A region of keys is staged in groups of 4 pieces (4 KiB = 4*RPI rows); in every group wave w moves piece w: rows
     // w*RPI .. +RPI-1 of the group.  The source-chunk swizzle depends on the row inside the group only.
     const int rsub = lane / CHR, cl = lane % CHR;
@@ -556,9 +562,13 @@ int rsa_launch_bsfwd(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int 
     if (a.blk != 64 || a.mode != MODE_SPARSE) return RSA_ERR_UNSUPPORTED;
     // the 16-byte output stores need 16-byte aligned rows; anything else takes the 8-byte form
     const bool wide = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
+    if (a.gqa != RSA_GQA_NONE && (a.gqa != RSA_GQA_HEAD || a.kv_group <= 0 || a.list_group <= 0)) return RSA_ERR_BAD_ARG;   // (no head pairs here)
 #define RSA_K5(DD, TT) \
     do { \
-        if (wide) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true>), a, true, grid, 256, lds_bytes, s); \
+        if (a.gqa) { \
+            if (wide) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true, true>), a, true, grid, 256, lds_bytes, s); \
+            else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false, true>), a, true, grid, 256, lds_bytes, s); \
+        } else if (wide) RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, true>), a, true, grid, 256, lds_bytes, s); \
         else RSA_LAUNCH_GSYNC(2, (bsfwd_kernel<DD, TT, false>), a, true, grid, 256, lds_bytes, s); \
     } while (0)
     if (D == 128) {

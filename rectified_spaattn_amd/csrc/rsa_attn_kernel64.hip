@@ -108,14 +108,21 @@ __device__ __forceinline__ f32x16 k5w_oread() {
 // every second piece dropped (gen_k5_block64.py, RSA_K5W_LOOP_*_R256); `qblk` then counts 256-row tiles (the host sets NQB so).
 // D (round 6): head dim 128 or 64 (CogVideoX).  At 64 a sub-step is 8 + 8 MFMAs against the same softmax, a half-tile 4 KiB = four
 // LDS-DMA pieces of 8 rows (two per wave); same register map in the arch file, O in a[0:63], Q in a[64:95].
-// RANGED: per-row key ranges of a sparse call (AttnArgs::row_lo / row_hi; rsa_block_sparse_ranged_fwd).  Two waves only; everything it
+// RANGED: per-row key ranges of a sparse call (AttnArgs::row_lo / row_hi; rsa_block_sparse_ranged_fwd).  Two waves (or a head pair's four: GQA); everything it
 // adds sits in the plan, under `if constexpr (RANGED)`: the rows' ranges take the place of [0, kv_valid), the tile's extremes steer
 // the walk as they do in a causal or two-segment dense call, and the kept list is trimmed to the blocks some row of the tile can see.
-template <typename Tag, bool WIDE, int NW = 2, int D = 128, bool RANGED = false>
+// GQA: grouped-query K/V heads of a sparse call (AttnArgs::kv_group / list_group; rsa_block_sparse_gqa_fwd).  RSA_GQA_HEAD (two
+// waves): the MHA walk of query head h with the K/V head h / kv_group and the lists of list head h / list_group -- two divisions
+// in the address arithmetic, nothing else.  RSA_GQA_PAIR (four waves): waves 0-1 are query block qblk of head 2p, waves 2-3 the
+// same query block of head 2p + 1, both of one K/V head and one list row: ONE list, ONE K/V ring and the 256-row tile's loop
+// statement (every half-tile staged once for both heads); the grid counts head pairs, `qblk` still counts 128-row query blocks.
+template <typename Tag, bool WIDE, int NW = 2, int D = 128, bool RANGED = false, int GQA = RSA_GQA_NONE>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) void bsfwd64_kernel(AttnArgs) {
-    static_assert(!RANGED || NW == 2, "per-row ranges: sparse calls only (128-row query blocks)");
+    constexpr bool PAIR = GQA == RSA_GQA_PAIR;
+    static_assert(!RANGED || NW == 2 || PAIR, "per-row ranges: sparse calls only (128-row query blocks)");
+    static_assert(PAIR ? NW == 4 : (GQA == RSA_GQA_NONE || NW == 2), "a head pair is four waves, a head of its own two");
     const AttnArgs& a = rsa_kernargs<AttnArgs>();
-    constexpr int RW = 64 * NW;             // query rows per workgroup: NW waves x 64 rows
+    constexpr int RW = PAIR ? 128 : 64 * NW;    // query rows per workgroup and head: NW waves x 64 rows (a pair: two waves per head)
     constexpr int NPIECE = 32 * D * 2 / 1024;   // 1-KiB pieces of a 32-key half-tile: 8 (4 rows each) / 4 (8 rows each)
     constexpr int NPW = NPIECE / NW;        // ... of them each wave stages
     constexpr int RPP = 32 / NPIECE;        // key rows per piece
@@ -135,12 +142,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     // ---------------- work mapping (rsa_attn.h); a text block is a qblk >= NBv ----------------
     int bh, qblk, tsp, tail;
     if (rsa_walk_map(a, blockIdx.x, a.NBv, bh, qblk, tsp, tail) == WALK_NONE) return;
-    const int b = bh / a.H, h = bh % a.H;
+    int b = bh / a.H, h = bh % a.H;         // batch item and query head (a head pair: below)
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    int wq = wv;                            // the 64-row slice of the query block this wave owns
+    if constexpr (PAIR) {                   // bh counts head pairs: waves 0-1 are head 2p, waves 2-3 head 2p + 1
+        const int hp = a.H >> 1;
+        b = bh / hp; h = 2 * (bh % hp) + (wv >> 1); wq = wv & 1;
+    }
     const int r = lane & 31, hh = lane >> 5;
     int grow[2];
-    grow[0] = qblk * RW + 64 * wv + r;
+    grow[0] = qblk * RW + 64 * wq + r;
     grow[1] = grow[0] + 32;
 
     // ---------------- per-row plan (per row half) ----------------
@@ -149,7 +161,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     const int32_t* list = nullptr;
     if (a.mode == MODE_SPARSE) {
         if (qblk < a.NBv) {
-            rsa_walk_list(a, (long)bh * a.NBv + qblk, tail, tsp, list, n_items);
+            long lrow = bh;                 // list row of this head: its own, or its list head's (the same for a pair's two heads)
+            if constexpr (GQA != RSA_GQA_NONE) lrow = (long)b * (a.H / a.list_group) + h / a.list_group;
+            rsa_walk_list(a, lrow * a.NBv + qblk, tail, tsp, list, n_items);
             if constexpr (RANGED) {
                 // The rows' own ranges, clamped into [0, kv_valid]; rows past the sequence take the last row's (as rsa_dense_row), so
                 // the extremes below are those of the tile's real rows.  An empty range (hi <= lo) becomes [0, 0): it pulls hi_min to
@@ -174,6 +188,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
                 }
                 // The extremes steer i0 / nfull / i1 and the barriers inside `step`: they must be the same in both waves.  Each wave
                 // reduces its 64 lanes, then the two meet in LDS -- the head of the K ring, which nothing touches before the first staging.
+                // (a head pair: four slots; the ranges are per row, so waves 2-3 bring what waves 0-1 brought)
                 int* red = reinterpret_cast<int*>(lds);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -181,10 +196,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
                     if (lane == 0) red[4 * wv + i] = m;
                 }
                 __syncthreads();
-                const int lo_min = -__builtin_amdgcn_readfirstlane(k5w_max(red[0], red[4]));
-                lo_max = __builtin_amdgcn_readfirstlane(k5w_max(red[1], red[5]));
-                hi_min = -__builtin_amdgcn_readfirstlane(k5w_max(red[2], red[6]));
-                hi_max = __builtin_amdgcn_readfirstlane(k5w_max(red[3], red[7]));
+                int lo_min;
+                if constexpr (NW == 2) {
+                    lo_min = -__builtin_amdgcn_readfirstlane(k5w_max(red[0], red[4]));
+                    lo_max = __builtin_amdgcn_readfirstlane(k5w_max(red[1], red[5]));
+                    hi_min = -__builtin_amdgcn_readfirstlane(k5w_max(red[2], red[6]));
+                    hi_max = __builtin_amdgcn_readfirstlane(k5w_max(red[3], red[7]));
+                } else {
+                    lo_min = -__builtin_amdgcn_readfirstlane(k5w_max(k5w_max(red[0], red[4]), k5w_max(red[8], red[12])));
+                    lo_max = __builtin_amdgcn_readfirstlane(k5w_max(k5w_max(red[1], red[5]), k5w_max(red[9], red[13])));
+                    hi_min = -__builtin_amdgcn_readfirstlane(k5w_max(k5w_max(red[2], red[6]), k5w_max(red[10], red[14])));
+                    hi_max = __builtin_amdgcn_readfirstlane(k5w_max(k5w_max(red[3], red[7]), k5w_max(red[11], red[15])));
+                }
                 // Trim the (ascending) list -- a tail piece's own part of it -- to the blocks some row of the tile can see: entries
                 // with blk * 128 >= hi_max go from its end, entries with blk * 128 + 128 <= lo_min from its front, 64 entries per step
                 // (every wave counts for itself: same list, same result).  A piece may end up with nothing: its partial is then
@@ -259,8 +282,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
         const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)p >> 32));
         return reinterpret_cast<const unsigned char*>(((unsigned long)hi << 32) | lo);
     };
-    const unsigned char* kbase = uni64(reinterpret_cast<const unsigned char*>(a.k + (long)b * a.ksb + (long)h * a.ksh));
-    const unsigned char* vbase = uni64(reinterpret_cast<const unsigned char*>(a.v + (long)b * a.vsb + (long)h * a.vsh));
+    int hkv = h;                            // the K/V head (a pair's two heads share it: kv_group is even there)
+    if constexpr (GQA != RSA_GQA_NONE) hkv = h / a.kv_group;
+    const unsigned char* kbase = uni64(reinterpret_cast<const unsigned char*>(a.k + (long)b * a.ksb + (long)hkv * a.ksh));
+    const unsigned char* vbase = uni64(reinterpret_cast<const unsigned char*>(a.v + (long)b * a.vsb + (long)hkv * a.vsh));
     // A 32-key half-tile = NPIECE one-KiB pieces of RPP rows (8 x 4 rows at head dim 128, 4 x 8 rows at 64); wave w moves pieces
     // NW j + w, j = 0 .. NPW - 1.  The XOR swizzle of a row's source chunk (rsa_attn.h::tile_off) depends on the row: at head dim 128
     // on (row & 3) and ((row >> 2) & 3) = piece & 3 -- two per-lane offsets (even / odd j) with two waves, one with four --, at head
@@ -506,7 +531,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
         asm volatile("" : "+s"(work2));
         rsa_walk_map(e, work2, e.NBv, bh2, qblk2, tsp2, tail2);
     }
-    const int b2 = bh2 / e.H, h2 = bh2 % e.H;
+    int b2, h2;
+    if constexpr (PAIR) {
+        const int hp2 = e.H >> 1;
+        b2 = bh2 / hp2; h2 = 2 * (bh2 % hp2) + (wv >> 1);
+    } else {
+        b2 = bh2 / e.H; h2 = bh2 % e.H;
+    }
     const bool partial = (e.mode == MODE_SPARSE && e.tsplit > 1 && qblk2 >= e.NBv) || tail2 >= 0;
     const bool rectify = e.mode == MODE_SPARSE && qblk2 < e.NBv && e.R != nullptr && tail2 < 0;   // (a tail piece is rectified by its combine pass)
     // the compensation row of this query block, the 64 values this lane adds (d = 32 dt + 8 g + 4 hh + 0..3), and R: ALL loads
@@ -529,14 +560,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     }
     auto finish_half = [&](auto HX) {
         constexpr int x = decltype(HX)::value;
-        const int grow2 = qblk2 * RW + 64 * wv + 32 * x + r;
+        const int grow2 = qblk2 * RW + 64 * wq + 32 * x + r;
         const float mrun = thr[x] == -INFINITY ? -INFINITY : m_ref[x];
         const auto swl = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run[x]), __float_as_uint(l_run[x]), false, false);
         const float l_tot = __uint_as_float(swl[0]) + __uint_as_float(swl[1]);
         if (partial) {
             // split-KV partial of a text block or of a tail piece: unnormalised O (fp32), m (log2 domain) and l per row (merged by
             // text_combine_kernel / tail_combine_kernel, rsa_attn.hip)
-            float* pp = rsa_part_of(e, bh2, qblk2, tsp2, tail2, 64 * wv + 32 * x + r, D);
+            float* pp = rsa_part_of(e, bh2, qblk2, tsp2, tail2, 64 * wq + 32 * x + r, D);
             auto put = [&](int dt, const f32x16& o) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -613,25 +644,28 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     finish_half(std::integral_constant<int, 1>{});
 }
 
-// the four instantiations (dtype x store width) of the NW-wave kernel at head dim D (RANGED: with per-row key ranges)
-template <int NW, int D, bool RANGED = false>
+// the four instantiations (dtype x store width) of the NW-wave kernel at head dim D (RANGED: with per-row key ranges; GQA: grouped
+// K/V heads, per head or per head pair)
+template <int NW, int D, bool RANGED = false, int GQA = RSA_GQA_NONE>
 static int launch_bsfwd64(const AttnArgs& a, bool wide, int dtype, dim3 grid, size_t lds_bytes, hipStream_t s) {
     const bool sparse = a.mode == MODE_SPARSE;
     if (dtype == RSA_BF16) {
-        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, NW, D, RANGED>), a, sparse, grid, 64 * NW, lds_bytes, s);
-        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false, NW, D, RANGED>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, true, NW, D, RANGED, GQA>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<bf16_tag, false, NW, D, RANGED, GQA>), a, sparse, grid, 64 * NW, lds_bytes, s);
     } else {
-        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true, NW, D, RANGED>), a, sparse, grid, 64 * NW, lds_bytes, s);
-        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false, NW, D, RANGED>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        if (wide) RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, true, NW, D, RANGED, GQA>), a, sparse, grid, 64 * NW, lds_bytes, s);
+        else RSA_LAUNCH_GSYNC(1, (bsfwd64_kernel<fp16_tag, false, NW, D, RANGED, GQA>), a, sparse, grid, 64 * NW, lds_bytes, s);
     }
     return rsa_launch_status();
 }
 
+#ifndef RSA_K64_GQA_UNIT
 // launch hook used by rsa_attn.hip::launch_attn (head dims 128 and 64)
 int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
     if (D != 128 && D != 64) return RSA_ERR_UNSUPPORTED;
     const bool wide = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
     lds_bytes += 16;   // the loop reads its list two entries ahead
+    if (a.gqa != RSA_GQA_NONE) return rsa_launch_bsfwd64_gqa(a, wide, grid, lds_bytes, D, dtype, s);
     if (a.rows256) {     // dense calls: 256-row tiles, four waves on one K/V ring (the host counted the grid in such tiles)
         if (a.mode != MODE_DENSE) return RSA_ERR_BAD_ARG;
         return D == 128 ? launch_bsfwd64<4, 128>(a, wide, dtype, grid, lds_bytes, s) : launch_bsfwd64<4, 64>(a, wide, dtype, grid, lds_bytes, s);
@@ -643,3 +677,30 @@ int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, in
     }
     return D == 128 ? launch_bsfwd64<2, 128>(a, wide, dtype, grid, lds_bytes, s) : launch_bsfwd64<2, 64>(a, wide, dtype, grid, lds_bytes, s);
 }
+#else
+// The grouped-query instantiations, two translation units of their own (rsa_attn_kernel64_gqa.hip: RSA_K64_GQA_UNIT = RSA_GQA_HEAD,
+// rsa_attn_kernel64_gqa_pair.hip: = RSA_GQA_PAIR; each includes this file), so that the 64-row kernel's instantiations compile side
+// by side and the build's longest compilation stays the one it was.
+template <int NW, int GQA>
+static int launch_gqa(const AttnArgs& a, bool wide, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
+    if (a.row_hi)
+        return D == 128 ? launch_bsfwd64<NW, 128, true, GQA>(a, wide, dtype, grid, lds_bytes, s)
+                        : launch_bsfwd64<NW, 64, true, GQA>(a, wide, dtype, grid, lds_bytes, s);
+    return D == 128 ? launch_bsfwd64<NW, 128, false, GQA>(a, wide, dtype, grid, lds_bytes, s)
+                    : launch_bsfwd64<NW, 64, false, GQA>(a, wide, dtype, grid, lds_bytes, s);
+}
+#if RSA_K64_GQA_UNIT == 1
+static_assert(RSA_GQA_HEAD == 1, "RSA_K64_GQA_UNIT names the form");
+int rsa_launch_bsfwd64_gqa(const AttnArgs& a, bool wide, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
+    if (a.mode != MODE_SPARSE || a.rows256 || a.kv_group <= 0 || a.list_group <= 0) return RSA_ERR_BAD_ARG;
+    if (a.gqa == RSA_GQA_PAIR) return rsa_launch_bsfwd64_gqa_pair(a, wide, grid, lds_bytes, D, dtype, s);
+    return launch_gqa<2, RSA_GQA_HEAD>(a, wide, grid, lds_bytes, D, dtype, s);
+}
+#else
+static_assert(RSA_K64_GQA_UNIT == RSA_GQA_PAIR, "RSA_K64_GQA_UNIT names the form");
+int rsa_launch_bsfwd64_gqa_pair(const AttnArgs& a, bool wide, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
+    if ((a.kv_group | a.list_group | a.H) & 1) return RSA_ERR_BAD_ARG;   // both heads of a pair: one K/V head, one list row
+    return launch_gqa<4, RSA_GQA_PAIR>(a, wide, grid, lds_bytes, D, dtype, s);
+}
+#endif
+#endif
