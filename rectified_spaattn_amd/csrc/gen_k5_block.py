@@ -29,13 +29,15 @@ Measured and dropped: the sub-step's LDS-DMA pieces spread over the MFMA shadows
 ~70 cycles wherever it is issued, and inside the block that stall stops the wave's MFMA stream), 16x16x32 MFMAs (timing
 probe: +-0 sparse, +3 % dense), packed f32 adds for the row sum (+0.8 % time).
 
-The output depends on nothing but this file.
+The output depends on nothing but this file and the generators' shared core, k5gen.py.
 
 usage: python3 gen_k5_block.py > rsa_attn_block.h
 """
+from k5gen import CVT_PK, MFMA16, Stream, clobbers, codemap_work, lds_dma, macro, ops_macro, pin, row_max1, vr
 
 AHEAD = 4          # LDS operand buffers per operand kind (K fragments, V^T fragments)
-COST = dict(sub=4, exp=8, cvt=4, cvt8=5, add=4, max=4, mov=4, nop=8, swap=4)
+# issue cycles of the 32-row kernels' vector work: the 2-byte kernel, the e4m3 kernel and its pv form (the 64-row table differs)
+COST32 = dict(sub=4, exp=8, cvt=4, cvt8=5, add=4, max=4, mov=4, nop=8, swap=4)
 
 
 class Map:
@@ -79,41 +81,29 @@ def rsm_form(D):
     return D == 64
 
 
-def vr(a, n=1):
-    return f"v{a}" if n == 1 else f"v[{a}:{a + n - 1}]"
-
-
 def gen_block(D, dt, VS, SUB):
     """The asm lines of one block variant."""
     m = Map(D)
     negm = negm_form(D)
     KS, DT = m.KS, m.DT
-    mf = "v_mfma_f32_32x32x16_bf16" if dt == "bf16" else "v_mfma_f32_32x32x16_f16"
-    cv = "v_cvt_pk_bf16_f32" if dt == "bf16" else "v_cvt_pk_f16_f32"
+    mf, cv = MFMA16[dt], CVT_PK[dt]
     TILE = 64 * D * 2
     SC, SN = (m.SA, m.SB) if SUB == 0 else (m.SB, m.SA)
     kslot, ksub = (VS, 1) if SUB == 0 else (VS ^ 1, 0)
     koff = kslot * TILE + ksub * 32 * D * 2
     vbase = (2 + VS) * TILE
-    lines = []
-    lds_seq = []          # issue order of LDS ops: (tag, count)
+    s = Stream(COST32)
+    lines = s.lines
 
     def k_read(ks):
-        lines.append(f"ds_read_b128 {vr(m.KF + 4 * (ks % AHEAD), 4)}, {vr(m.KA + ks)} offset:{koff}")
-        lds_seq.append((("K", ks), 1))
+        s.read(("K", ks), [f"ds_read_b128 {vr(m.KF + 4 * (ks % AHEAD), 4)}, {vr(m.KA + ks)} offset:{koff}"])
 
     def v_read(p):
         k2, d = divmod(p, DT)
         off = vbase + (2 * SUB + k2) * 16 * D * 2
         b = m.VF + 4 * (p % AHEAD)
-        lines.append(f"ds_read_b64_tr_b16 {vr(b, 2)}, {vr(m.VA + 2 * d)} offset:{off}")
-        lines.append(f"ds_read_b64_tr_b16 {vr(b + 2, 2)}, {vr(m.VA + 2 * d + 1)} offset:{off}")
-        lds_seq.append((("V", p), 2))
-
-    def wait_for(tag):
-        idx = [i for i, (t, _) in enumerate(lds_seq) if t == tag][-1]
-        after = sum(c for _, c in lds_seq[idx + 1:])
-        lines.append(f"s_waitcnt lgkmcnt({after})")
+        s.read(("V", p), [f"ds_read_b64_tr_b16 {vr(b, 2)}, {vr(m.VA + 2 * d)} offset:{off}",
+                          f"ds_read_b64_tr_b16 {vr(b + 2, 2)}, {vr(m.VA + 2 * d + 1)} offset:{off}"])
 
     # ---- the vector work, in issue order ----
     def pair(i):   # two scores interleaved so that no instruction reads its predecessor's result
@@ -134,49 +124,23 @@ def gen_block(D, dt, VS, SUB):
     for j in range(4, 8): work += C(j)
     for i in range(8, 16): work += [("add", f"v_add_f32 {vr(m.PS)}, {vr(m.PS)}, {vr(SC + i)}")]
     work += [("add", f"v_add_f32 %[l], %[l], {vr(m.PS)}")]
-    if negm:   # two chains, merged by a v_max
-        maxw = [("max", f"v_max_f32 {vr(m.T0)}, {vr(SN)}, {vr(SN + 1)}"), ("max", f"v_max_f32 {vr(m.T1)}, {vr(SN + 2)}, {vr(SN + 3)}")]
-        for i in range(2, 8):
-            t = m.T0 if i % 2 == 0 else m.T1
-            maxw += [("max", f"v_max3_f32 {vr(t)}, {vr(t)}, {vr(SN + 2 * i)}, {vr(SN + 2 * i + 1)}")]
-        maxw += [("max", f"v_max_f32 {vr(m.T0)}, {vr(m.T0)}, {vr(m.T1)}")]
-    else:
-        maxw = [("max", f"v_max_f32 {vr(m.T0)}, {vr(SN)}, {vr(SN + 1)}")]
-        for i in range(1, 8): maxw += [("max", f"v_max3_f32 {vr(m.T0)}, {vr(m.T0)}, {vr(SN + 2 * i)}, {vr(SN + 2 * i + 1)}")]
-    maxw += [("mov", f"v_mov_b32 {vr(m.T1)}, {vr(m.T0)}"), ("nop", "s_nop 1"),
-             ("swap", f"v_permlane32_swap_b32 {vr(m.T0)}, {vr(m.T1)}"), ("nop", "s_nop 1"),
-             ("max", f"v_max_f32 %[mx], {vr(m.T0)}, {vr(m.T1)}")]
-
     if m.RSM:
         work = [w for w in work if w[0] != "add"]
+    s.work, s.maxw = work, row_max1(m.T0, m.T1, SN, 8, 2 if negm else 1)     # (-m form: two chains, merged by a v_max)
     mf_rs = "v_mfma_f32_16x16x32_bf16" if dt == "bf16" else "v_mfma_f32_16x16x32_f16"
     nm = KS + 2 * DT                      # MFMAs of the block
-    total = sum(COST[k] for k, _ in work + maxw)
+    total = sum(COST32[k] for k, _ in s.work + s.maxw)
     pre = 72 if D == 128 else 48          # vector work issued while the first K fragments are in flight
     budget = max(24, -(-(total - pre) // nm) + 2)
-    wi, mi = 0, 0
-
-    def emit_work(cycles, allow_max):
-        nonlocal wi, mi
-        used = 0
-        while used < cycles:
-            if wi < len(work):
-                k, t = work[wi]; wi += 1
-            elif allow_max and mi < len(maxw):
-                k, t = maxw[mi]; mi += 1
-            else:
-                break
-            lines.append(t)
-            used += COST[k]
 
     # (head dim 64: 8 MFMAs per sub-step against the same softmax, the wave is bound by vector issue, and raising its
     # priority over its partner on the SIMD costs 3-5 %: tools/perf_d64.py, profiles/r03_k5_block.md)
     if D == 128: lines.append("s_setprio 2")
     for ks in range(min(AHEAD, KS)): k_read(ks)
-    emit_work(pre, False)
+    s.emit_work(pre, False)
     for i in range(nm):
         if i < KS:
-            wait_for(("K", i))
+            s.wait_for(("K", i))
             c = (vr(m.NM, 16) if negm else "0") if i == 0 else vr(SN, 16)
             lines.append(f"{mf} {vr(SN, 16)}, {vr(m.KF + 4 * (i % AHEAD), 4)}, {vr(m.Q + 4 * i, 4)}, {c}")
             if i + AHEAD < KS: k_read(i + AHEAD)
@@ -193,24 +157,20 @@ def gen_block(D, dt, VS, SUB):
             if m.RSM and d == 0:      # l += ones . P^T over the 16 keys of half k2 (behind the conversions that packed it)
                 lines.append("s_nop 1")
                 lines.append(f"{mf_rs} {vr(m.LACC, 4)}, {vr(m.ONES, 4)}, {vr(m.P + 4 * k2, 4)}, {vr(m.LACC, 4)}")
-            wait_for(("V", p))
+            s.wait_for(("V", p))
             lines.append(f"{mf} {vr(m.O + 16 * d, 16)}, {vr(m.VF + 4 * (p % AHEAD), 4)}, {vr(m.P + 4 * k2, 4)}, {vr(m.O + 16 * d, 16)}")
             if p + AHEAD < 2 * DT: v_read(p + AHEAD)
         last = i == nm - 1
         # The row max reads S_nxt: two or more MFMAs behind the last QK MFMA (its 8 passes are over).  Classic form: it fills
         # the last two shadows and the tail, padded to the 12 wait states between the last PV MFMA and any VALU touching O.
         n0 = len(lines)
-        emit_work(10 ** 6 if last else budget, i >= (KS + 1 if negm else max(KS + 1, nm - 2)))
+        s.emit_work(10 ** 6 if last else budget, i >= (KS + 1 if negm else max(KS + 1, nm - 2)))
         if last and not negm:
             tail = sum(int(l.split()[1]) + 1 if l.startswith("s_nop") else 1 for l in lines[n0:])
             if tail < 12: lines.append(f"s_nop {11 - tail}")
-    assert wi == len(work) and mi == len(maxw)
+    assert not s.work and not s.maxw
     if D == 128: lines.append("s_setprio 0")
-    return lines, m
-
-
-def c_string(lines):
-    return "\n".join(f'    "{l}\\n\\t"' for l in lines)
+    return lines
 
 
 def main():
@@ -219,30 +179,25 @@ def main():
         for dt in ("bf16", "f16"):
             for VS in (0, 1):
                 for SUB in (0, 1):
-                    lines, m = gen_block(D, dt, VS, SUB)
-                    out.append(f"#define RSA_K5_BLOCK{'N' if negm_form(D) else ''}_{D}_{dt.upper()}_V{VS}_S{SUB} \\")
-                    out.append(" \\\n".join(c_string(lines).split("\n")))
-                    out.append("")
+                    out.append(macro(f"RSA_K5_BLOCK{'N' if negm_form(D) else ''}_{D}_{dt.upper()}_V{VS}_S{SUB}", gen_block(D, dt, VS, SUB)))
     # operand lists (the constraint strings carry the register map) and the clobbered temporaries
     for D in (128, 64):
         m, negm = Map(D), negm_form(D)
-        outs = [f'"+{{{vr(m.O + 16 * d, 16)}}}"(o[{d}])' for d in range(m.DT)]
-        outs += [f'"+{{{vr(m.SA, 16)}}}"(SA)', f'"+{{{vr(m.SB, 16)}}}"(SB)',
-                 f'"+{{{vr(m.LACC, 4)}}}"(lacc)' if m.RSM else '[l] "+v"(l)', '[mx] "=&v"(mx)']
-        ins = [f'"{{{vr(m.Q + 4 * k, 4)}}}"(q[{k}])' for k in range(m.KS)]
-        ins += [f'"{{{vr(m.NM, 16)}}}"(nm)'] if negm else ['[m] "v"(m)']
-        ins += [f'"{{{vr(m.KA, m.KS)}}}"(ka)', f'"{{{vr(m.VA, 2 * m.DT)}}}"(va)']
-        if m.RSM: ins += [f'"{{{vr(m.ONES, 4)}}}"(onesv)']
+        outs = [pin("+", m.O + 16 * d, 16, f"o[{d}]") for d in range(m.DT)]
+        outs += [pin("+", m.SA, 16, "SA"), pin("+", m.SB, 16, "SB"), pin("+", m.LACC, 4, "lacc") if m.RSM else '[l] "+v"(l)', '[mx] "=&v"(mx)']
+        ins = [pin("", m.Q + 4 * k, 4, f"q[{k}]") for k in range(m.KS)]
+        ins += [pin("", m.NM, 16, "nm")] if negm else ['[m] "v"(m)']
+        ins += [pin("", m.KA, m.KS, "ka"), pin("", m.VA, 2 * m.DT, "va")]
+        if m.RSM: ins += [pin("", m.ONES, 4, "onesv")]
         tag = f"{'N' if negm else ''}_{D}"
-        out.append(f"#define RSA_K5_OPS{tag} : {', '.join(outs)} : {', '.join(ins)}")
-        out.append(f"#define RSA_K5_CLOBBER{tag} " + ", ".join(f'"v{r}"' for r in range(m.tmp0, m.tmp1)))
+        out.append(ops_macro(f"RSA_K5_OPS{tag}", outs, ins))
+        out.append(f"#define RSA_K5_CLOBBER{tag} " + clobbers("v", range(m.tmp0, m.tmp1)))
         out.append(f"// D = {D}{' (-m form)' if negm else ''}: O v[{m.O}:{m.Q - 1}], Q v[{m.Q}:{m.SA - 1}], SA v[{m.SA}:{m.SA + 15}], "
                    f"SB v[{m.SB}:{m.SB + 15}], " + (f"-m v[{m.NM}:{m.NM + 15}], " if negm else "")
                    + f"temporaries v[{m.tmp0}:{m.tmp1 - 1}], K addresses v[{m.KA}:{m.KA + m.KS - 1}], V addresses v[{m.VA}:{m.end - 1}]")
     main8(out)
     main8h(out)
     print("\n".join(out))
-
 
 
 # =====================================================================================================================
@@ -257,6 +212,11 @@ def main():
 # loop-invariant VGPR plus an immediate (the compiled block spent ~16 v_add_u32 per tile on them).
 # =====================================================================================================================
 AHEAD8, RING8 = 3, 4
+
+
+def operand_reads(b, reads):
+    """ds_read_b128 of an A operand into v[b:...]: four registers per (address register, immediate) pair"""
+    return [f"ds_read_b128 {vr(b + 4 * c2, 4)}, {vr(areg)}" + (f" offset:{off}" if off else "") for c2, (areg, off) in enumerate(reads)]
 DMA8_GAPS = [0, 2, 4, 6]      # dma form: K piece 0, K piece 1, V piece 0, V piece 1 behind these MFMAs of the nine
                               # (placement: profiles/r05_pv_hand_placed.txt)
 
@@ -297,7 +257,8 @@ def gen_block8(TS, codemap=False, D8=128, dma=False):
     SC_, SN = (m.SA, m.SB) if TS % 2 == 0 else (m.SB, m.SA)
     TILE8 = 64 * D8
     kslot = (TS + 1) & 3
-    lines, lds_seq = [], []
+    s = Stream(COST32)
+    lines = s.lines
     # the A operands, in MFMA order (nine at head dim 128, five at 64): (kind, LDS reads as (address register, immediate) pairs)
     ops = []
     for sub in range(2):
@@ -312,16 +273,8 @@ def gen_block8(TS, codemap=False, D8=128, dma=False):
         ops.append(("pv", dt, 0, [(m.VA, off), (m.VA + 1, off)]))
 
     def read(i):
-        if not ops[i][3]:
-            return
-        b = m.OP + 8 * (i % RING8)
-        for c2, (areg, off) in enumerate(ops[i][3]):
-            lines.append(f"ds_read_b128 {vr(b + 4 * c2, 4)}, {vr(areg)}" + (f" offset:{off}" if off else ""))
-        lds_seq.append((i, 2))
-
-    def wait_for(i):
-        idx = [k for k, (t, _) in enumerate(lds_seq) if t == i][-1]
-        lines.append(f"s_waitcnt lgkmcnt({sum(c for _, c in lds_seq[idx + 1:])})")
+        if ops[i][3]:
+            s.read(i, operand_reads(m.OP + 8 * (i % RING8), ops[i][3]))
 
     # vector work: exponentials in place, the e4m3 words of P built in place in S_cur[0][0:7]
     work = []
@@ -341,48 +294,18 @@ def gen_block8(TS, codemap=False, D8=128, dma=False):
             if g >= 1: work += pack(g - 1)
         work += pack(7)
     else:
-        # code-map form: the accumulator holds 8 log2(P) + 56, the e4m3 CODE of P up to rounding: one v_cvt_pk_u8_f32 per score
-        # (round to nearest even, saturating at 0: tools/probes/cvt_pk_u8_probe.hip), no exponential, no fp8 conversion.
-        # Word j = register j of S_cur[0]; registers 0..7 are all sources of words 0 and 1, so those two go first (word 1
-        # starts once word 0 has read register 1), the rest in interleaved pairs (no back-to-back dependent conversions).
-        def byte(j, e):
-            sub, w4 = divmod(j, 4)
-            return ("cvt8", f"v_cvt_pk_u8_f32 {vr(SC_ + j)}, {vr(SC_ + 16 * sub + 4 * w4 + e)}, {e}, {vr(SC_ + j)}")
-        work += [byte(0, 0), byte(0, 1), byte(1, 0), byte(0, 2), byte(1, 1), byte(0, 3), byte(1, 2), byte(1, 3)]
-        for j in (2, 4, 6):
-            for e in range(4):
-                work += [byte(j, e), byte(j + 1, e)]
-    maxw = [("max", f"v_max_f32 {vr(m.T0)}, {vr(SN)}, {vr(SN + 1)}"), ("max", f"v_max_f32 {vr(m.T1)}, {vr(SN + 2)}, {vr(SN + 3)}")]
-    for i in range(2, 16):
-        t = m.T0 if i % 2 == 0 else m.T1
-        maxw += [("max", f"v_max3_f32 {vr(t)}, {vr(t)}, {vr(SN + 2 * i)}, {vr(SN + 2 * i + 1)}")]
-    maxw += [("max", f"v_max_f32 {vr(m.T0)}, {vr(m.T0)}, {vr(m.T1)}"), ("mov", f"v_mov_b32 {vr(m.T1)}, {vr(m.T0)}"),
-             ("nop", "s_nop 1"), ("swap", f"v_permlane32_swap_b32 {vr(m.T0)}, {vr(m.T1)}"), ("nop", "s_nop 1"),
-             ("max", f"v_max_f32 %[mx], {vr(m.T0)}, {vr(m.T1)}")]
-    wi, mi = 0, 0
-
-    def emit_work(cycles, allow_max, force_all=False):
-        nonlocal wi, mi
-        used = 0
-        while used < cycles or force_all:
-            if wi < len(work):
-                k, t = work[wi]; wi += 1
-            elif allow_max and mi < len(maxw):
-                k, t = maxw[mi]; mi += 1
-            else:
-                break
-            lines.append(t)
-            used += COST[k]
+        work = codemap_work(SC_)      # (k5gen.py says what the code-map form is)
+    s.work, s.maxw = work, row_max1(m.T0, m.T1, SN, 16, 2)
 
     lines.append("s_setprio 2")
     for i in range(AHEAD8): read(i)
-    emit_work(64, False)
+    s.emit_work(64, False)
     n = len(ops)
     for i, (kind, x, y, _) in enumerate(ops):
-        if kind != "qk" and wi < len(work):   # the row sum and PV read the whole packed P
-            emit_work(0, False, force_all=True)
+        if kind != "qk" and s.work:   # the row sum and PV read the whole packed P
+            s.emit_work(0, False, force_all=True)
         if ops[i][3]:
-            wait_for(i)
+            s.wait_for(i)
         a = vr(m.OP + 8 * ((i if ops[i][3] else i - m.KS) % RING8), 8)
         if kind == "qk":
             c = vr(m.MB, 16) if y == 0 else vr(SN + 16 * x, 16)
@@ -401,62 +324,43 @@ def gen_block8(TS, codemap=False, D8=128, dma=False):
             j = gaps.index(i)
             isv, hi = divmod(j, TILE8 // 4096)
             dst = (4 + ((TS + 2) & 3)) * TILE8 + hi * 4096 if isv else ((TS + 3) & 3) * TILE8 + hi * 4096
-            lines.append(f"s_add_u32 m0, %[ldsw], {dst}")
-            lines.append("s_nop 0")      # (M0 write -> LDS-DMA: one wait state)
-            lines.append(f"global_load_lds_dwordx4 {vr((m.DV if isv else m.DK) + hi)}, " + ("%[vsrc]" if isv else "%[ksrc]"))
+            lines += lds_dma((m.DV if isv else m.DK) + hi, "%[vsrc]" if isv else "%[ksrc]", m0=("%[ldsw]", dst))
         # row max of S_nxt: two MFMAs behind the last QK^T MFMA (index n_qk - 1): from the shadow of PV 0 (index n_qk + 1) on
-        emit_work(10 ** 6 if i == n - 1 else 48, i >= n_qk + 1)
-    assert wi == len(work) and mi == len(maxw)
+        s.emit_work(10 ** 6 if i == n - 1 else 48, i >= n_qk + 1)
+    assert not s.work and not s.maxw
     lines.append("s_setprio 0")
-    return lines, m
+    return lines
+
+
+def outs8(m):
+    """the outputs every e4m3 / pv statement shares: O, both score tiles (two 32-key halves each), l, the row maximum"""
+    return ([pin("+", m.O + 16 * d, 16, f"o[{d}]") for d in range(m.DT)]
+            + [pin("+", S + 16 * h, 16, f"{n}[{h}]") for n, S in (("SA", m.SA), ("SB", m.SB)) for h in (0, 1)]
+            + [pin("+", m.LACC, 4, "lacc"), '[mx] "=&v"(mx)'])
 
 
 def main8(out):
     for codemap in (False, True):
         for TS in range(4):
-            lines, m = gen_block8(TS, codemap)
-            out.append(f"#define RSA_K5F8_BLOCK{'C' if codemap else ''}_T{TS} \\")
-            out.append(" \\\n".join(c_string(lines).split("\n")))
-            out.append("")
+            out.append(macro(f"RSA_K5F8_BLOCK{'C' if codemap else ''}_T{TS}", gen_block8(TS, codemap)))
     for TS in range(4):   # the product at head dim 128: code map + the wave's LDS-DMA pieces inside the block
-        lines, m = gen_block8(TS, True, 128, dma=True)
-        out.append(f"#define RSA_K5F8_BLOCKCD_T{TS} \\")
-        out.append(" \\\n".join(c_string(lines).split("\n")))
-        out.append("")
+        out.append(macro(f"RSA_K5F8_BLOCKCD_T{TS}", gen_block8(TS, True, 128, dma=True)))
     for TS in range(4):   # head dim 64 (CogVideoX): the code-map form, staging behind the barrier / inside the block (product)
         for dma in (False, True):
-            lines, m = gen_block8(TS, True, 64, dma=dma)
-            out.append(f"#define RSA_K5F8_BLOCKC{'D' if dma else ''}64_T{TS} \\")
-            out.append(" \\\n".join(c_string(lines).split("\n")))
-            out.append("")
-    m = Map8(64)
-    outs = [f'"+{{{vr(m.O + 16 * d, 16)}}}"(o[{d}])' for d in range(2)]
-    outs += [f'"+{{{vr(m.SA, 16)}}}"(SA[0])', f'"+{{{vr(m.SA + 16, 16)}}}"(SA[1])', f'"+{{{vr(m.SB, 16)}}}"(SB[0])',
-             f'"+{{{vr(m.SB + 16, 16)}}}"(SB[1])', f'"+{{{vr(m.LACC, 4)}}}"(lacc)', '[mx] "=&v"(mx)']
-    ins = [f'"{{{vr(m.Q, 8)}}}"(q[0])', f'"{{{vr(m.MB, 16)}}}"(mblk)',
-           f'"{{{vr(m.SC)}}}"(sca)', f'"{{{vr(m.SC + 1)}}}"(scb)', f'"{{{vr(m.KA, 2)}}}"(ka)', f'"{{{vr(m.VA, 2)}}}"(va)',
-           f'"{{{vr(m.ON)}}}"(ona)']
-    out.append(f"#define RSA_K5F8_OPS64 : {', '.join(outs)} : {', '.join(ins)}")
-    insd = ins[:-1] + [f'"{{{vr(m.ONES, 8)}}}"(onesv)', f'"{{{vr(m.DK)}}}"(dk)', f'"{{{vr(m.DV)}}}"(dv)', '[ksrc] "s"(ksrc)', '[vsrc] "s"(vsrc)', '[ldsw] "s"(ldsw)']
-    out.append(f"#define RSA_K5F8_OPS64D : {', '.join(outs)} : {', '.join(insd)}")
-    out.append("#define RSA_K5F8_CLOBBER64 " + ", ".join(f'"v{r}"' for r in range(m.tmp0, m.tmp1)))
-    out.append(f"// e4m3 kernel, head dim 64: O v[0:{m.Q - 1}], Q v[{m.Q}:{m.SA - 1}], SA v[{m.SA}:{m.SB - 1}], SB v[{m.SB}:{m.MB - 1}], "
-               f"reference block v[{m.MB}:{m.LACC - 1}], l v[{m.LACC}:{m.LACC + 3}], temporaries v[{m.tmp0}:{m.tmp1 - 1}], "
-               f"scales v[{m.SC}:{m.SC + 1}], K / V / ones addresses v[{m.KA}:{m.end - 1}]")
-    m = Map8()
-    outs = [f'"+{{{vr(m.O + 16 * d, 16)}}}"(o[{d}])' for d in range(4)]
-    outs += [f'"+{{{vr(m.SA, 16)}}}"(SA[0])', f'"+{{{vr(m.SA + 16, 16)}}}"(SA[1])', f'"+{{{vr(m.SB, 16)}}}"(SB[0])',
-             f'"+{{{vr(m.SB + 16, 16)}}}"(SB[1])', f'"+{{{vr(m.LACC, 4)}}}"(lacc)', '[mx] "=&v"(mx)']
-    ins = [f'"{{{vr(m.Q, 8)}}}"(q[0])', f'"{{{vr(m.Q + 8, 8)}}}"(q[1])', f'"{{{vr(m.MB, 16)}}}"(mblk)',
-           f'"{{{vr(m.SC)}}}"(sca)', f'"{{{vr(m.SC + 1)}}}"(scb)', f'"{{{vr(m.KA, 4)}}}"(ka)', f'"{{{vr(m.VA, 2)}}}"(va)',
-           f'"{{{vr(m.ON)}}}"(ona)']
-    out.append(f"#define RSA_K5F8_OPS : {', '.join(outs)} : {', '.join(ins)}")
-    insd = ins[:-1] + [f'"{{{vr(m.ONES, 8)}}}"(onesv)', f'"{{{vr(m.DK, 2)}}}"(dk)', f'"{{{vr(m.DV, 2)}}}"(dv)', '[ksrc] "s"(ksrc)', '[vsrc] "s"(vsrc)', '[ldsw] "s"(ldsw)']
-    out.append(f"#define RSA_K5F8_OPSD : {', '.join(outs)} : {', '.join(insd)}")
-    out.append("#define RSA_K5F8_CLOBBER " + ", ".join(f'"v{r}"' for r in range(m.tmp0, m.tmp1)))
-    out.append(f"// e4m3 kernel: O v[0:63], Q v[{m.Q}:{m.SA - 1}], SA v[{m.SA}:{m.SB - 1}], SB v[{m.SB}:{m.MB - 1}], 4 - m v[{m.MB}:{m.LACC - 1}], "
-               f"l v[{m.LACC}:{m.LACC + 3}], temporaries v[{m.tmp0}:{m.tmp1 - 1}], scales v[{m.SC}:{m.SC + 1}], "
-               f"K / V / ones addresses v[{m.KA}:{m.end - 1}]")
+            out.append(macro(f"RSA_K5F8_BLOCKC{'D' if dma else ''}64_T{TS}", gen_block8(TS, True, 64, dma=dma)))
+    for D8, tag in ((64, "64"), (128, "")):
+        m = Map8(D8)
+        ins = [pin("", m.Q + 8 * ks, 8, f"q[{ks}]") for ks in range(m.KS)]
+        ins += [pin("", m.MB, 16, "mblk"), pin("", m.SC, 1, "sca"), pin("", m.SC + 1, 1, "scb"), pin("", m.KA, 2 * m.KS, "ka"),
+                pin("", m.VA, 2, "va")]
+        out.append(ops_macro(f"RSA_K5F8_OPS{tag}", outs8(m), ins + [pin("", m.ON, 1, "ona")]))
+        insd = ins + [pin("", m.ONES, 8, "onesv"), pin("", m.DK, m.KS, "dk"), pin("", m.DV, m.KS, "dv"),
+                      '[ksrc] "s"(ksrc)', '[vsrc] "s"(vsrc)', '[ldsw] "s"(ldsw)']
+        out.append(ops_macro(f"RSA_K5F8_OPS{tag}D", outs8(m), insd))
+        out.append(f"#define RSA_K5F8_CLOBBER{tag} " + clobbers("v", range(m.tmp0, m.tmp1)))
+        out.append(f"// e4m3 kernel{', head dim 64' if D8 == 64 else ''}: O v[0:{m.Q - 1}], Q v[{m.Q}:{m.SA - 1}], SA v[{m.SA}:{m.SB - 1}], SB v[{m.SB}:{m.MB - 1}], "
+                   f"{'reference block' if D8 == 64 else '4 - m'} v[{m.MB}:{m.LACC - 1}], l v[{m.LACC}:{m.LACC + 3}], temporaries v[{m.tmp0}:{m.tmp1 - 1}], "
+                   f"scales v[{m.SC}:{m.SC + 1}], K / V / ones addresses v[{m.KA}:{m.end - 1}]")
 
 
 # =====================================================================================================================
@@ -515,10 +419,11 @@ def gen_block8h(T6, dt, dma=False, D8=128):
     wave's first V piece, %[ldsw] = LDS address of the wave's first piece in slot 0 of the K ring."""
     m = Map8H(D8)
     KTILE, VTILE = 128 * D8, 64 * D8          # bytes of a K tile (64 keys x 2 D8: 16 / 8 KiB) and of a V tile (D8 x 64: 8 / 4 KiB)
-    mf = "v_mfma_f32_32x32x16_bf16" if dt == "bf16" else "v_mfma_f32_32x32x16_f16"
+    mf = MFMA16[dt]
     SC_, SN = (m.SA, m.SB) if T6 % 2 == 0 else (m.SB, m.SA)
     kslot, vslot = (T6 + 1) % 3, T6 % 3
-    lines, lds_seq = [], []
+    s = Stream(COST32)
+    lines = s.lines
     ops = []      # (kind, x, y, reads [(address register, offset)], slots)
     for ks in range(m.KS):       # the two halves' chains alternate: no MFMA waits for the one just before it
         kreg = m.KB if ks == 0 else (m.T0 if ks % 2 == 0 else m.T1)
@@ -551,44 +456,10 @@ def gen_block8h(T6, dt, dma=False, D8=128):
         if kind == "qk" and sub == 0 and ks > 0:
             assert state["issued"] < n_qk, "T0 / T1 belong to the row maximum from P . V 0 on"
             lines.append(f"v_xor_b32 {vr(ops[j][3][0][0])}, {hex(ks << 5)}, {vr(m.KB)}")
-        for c2, (areg, off) in enumerate(ops[j][3]):
-            lines.append(f"ds_read_b128 {vr(b + 4 * c2, 4)}, {vr(areg)}" + (f" offset:{off}" if off else ""))
-        lds_seq.append((j, len(ops[j][3])))
-
-    def wait_for(i):
-        idx = [k for k, (t, _) in enumerate(lds_seq) if t == i][-1]
-        lines.append(f"s_waitcnt lgkmcnt({sum(c for _, c in lds_seq[idx + 1:])})")
+        s.read(j, operand_reads(b, ops[j][3]))
 
     # vector work: the code-map conversions of S_cur in place (as gen_block8), then the row maximum of S_nxt
-    def byte(j, e):
-        sub, w4 = divmod(j, 4)
-        return ("cvt8", f"v_cvt_pk_u8_f32 {vr(SC_ + j)}, {vr(SC_ + 16 * sub + 4 * w4 + e)}, {e}, {vr(SC_ + j)}")
-    work = [byte(0, 0), byte(0, 1), byte(1, 0), byte(0, 2), byte(1, 1), byte(0, 3), byte(1, 2), byte(1, 3)]
-    for j in (2, 4, 6):
-        for e in range(4):
-            work += [byte(j, e), byte(j + 1, e)]
-    maxw = [("max", f"v_max_f32 {vr(m.T0)}, {vr(SN)}, {vr(SN + 1)}"), ("max", f"v_max_f32 {vr(m.T1)}, {vr(SN + 2)}, {vr(SN + 3)}")]
-    for i in range(2, 16):
-        t = m.T0 if i % 2 == 0 else m.T1
-        maxw += [("max", f"v_max3_f32 {vr(t)}, {vr(t)}, {vr(SN + 2 * i)}, {vr(SN + 2 * i + 1)}")]
-    maxw += [("max", f"v_max_f32 {vr(m.T0)}, {vr(m.T0)}, {vr(m.T1)}"), ("mov", f"v_mov_b32 {vr(m.T1)}, {vr(m.T0)}"),
-             ("nop", "s_nop 1"), ("swap", f"v_permlane32_swap_b32 {vr(m.T0)}, {vr(m.T1)}"), ("nop", "s_nop 1"),
-             ("max", f"v_max_f32 %[mx], {vr(m.T0)}, {vr(m.T1)}")]
-    wi, mi = 0, 0
-
-    def emit_work(cycles, allow_max, force_all=False):
-        nonlocal wi, mi
-        used = 0
-        while used < cycles or force_all:
-            if wi < len(work):
-                k, t = work[wi]; wi += 1
-            elif allow_max and mi < len(maxw):
-                k, t = maxw[mi]; mi += 1
-            else:
-                break
-            lines.append(t)
-            used += COST[k]
-
+    s.work, s.maxw = codemap_work(SC_), row_max1(m.T0, m.T1, SN, 16, 2)
     nxt = 0           # next op whose operand read has not been issued
 
     def top_up(cur):
@@ -603,13 +474,13 @@ def gen_block8h(T6, dt, dma=False, D8=128):
 
     lines.append("s_setprio 2")
     top_up(0)
-    emit_work(48, False)
+    s.emit_work(48, False)
     for i, (kind, x, y, _, _) in enumerate(ops):
-        if kind != "qk" and wi < len(work):   # the row sum and P . V read the whole packed P
-            emit_work(0, False, force_all=True)
+        if kind != "qk" and s.work:   # the row sum and P . V read the whole packed P
+            s.emit_work(0, False, force_all=True)
         assert i < nxt, ("operand never read", T6, i)
         if ops[i][4]:
-            wait_for(i)
+            s.wait_for(i)
         b = m.OP + 4 * slot_of.get(i, slot_of.get(i - 1, 0))
         if kind == "qk":
             c = vr(m.MB, 16) if y == 0 else vr(SN + 16 * x, 16)
@@ -628,14 +499,12 @@ def gen_block8h(T6, dt, dma=False, D8=128):
                 dst, vo, src = (T6 % 3) * KTILE + j * 4096, m.DK + j, "%[kb16]"
             else:
                 dst, vo, src = 3 * KTILE + ((T6 + 2) % 3) * VTILE + (j - m.NPK) * 4096, m.DV + j - m.NPK, "%[vsrc]"
-            lines.append(f"s_add_u32 m0, %[ldsw], {dst}")
-            lines.append("s_nop 0")      # (M0 write -> LDS-DMA: one wait state)
-            lines.append(f"global_load_lds_dwordx4 {vr(vo)}, {src}")
+            lines += lds_dma(vo, src, m0=("%[ldsw]", dst))
         # row max of S_nxt: two MFMAs behind the last QK^T MFMA
-        emit_work(10 ** 6 if i == n - 1 else (20 if kind == "qk" else 48), i >= n_qk + 1)
-    assert wi == len(work) and mi == len(maxw) and nxt == n
+        s.emit_work(10 ** 6 if i == n - 1 else (20 if kind == "qk" else 48), i >= n_qk + 1)
+    assert not s.work and not s.maxw and nxt == n
     lines.append("s_setprio 0")
-    return lines, m
+    return lines
 
 
 def main8h(out):
@@ -644,21 +513,15 @@ def main8h(out):
         for dt in ("bf16", "f16"):
             for dma in (False, True):
                 for T6 in range(6):
-                    lines, m = gen_block8h(T6, dt, dma, D8)
-                    out.append(f"#define RSA_K5F8H{tag}_BLOCK{'D' if dma else ''}_{dt.upper()}_T{T6} \\")
-                    out.append(" \\\n".join(c_string(lines).split("\n")))
-                    out.append("")
+                    out.append(macro(f"RSA_K5F8H{tag}_BLOCK{'D' if dma else ''}_{dt.upper()}_T{T6}", gen_block8h(T6, dt, dma, D8)))
         m = Map8H(D8)
-        outs = [f'"+{{{vr(m.O + 16 * d, 16)}}}"(o[{d}])' for d in range(m.DT)]
-        outs += [f'"+{{{vr(m.SA, 16)}}}"(SA[0])', f'"+{{{vr(m.SA + 16, 16)}}}"(SA[1])', f'"+{{{vr(m.SB, 16)}}}"(SB[0])',
-                 f'"+{{{vr(m.SB + 16, 16)}}}"(SB[1])', f'"+{{{vr(m.LACC, 4)}}}"(lacc)', '[mx] "=&v"(mx)']
-        ins = [f'"{{{vr(m.Q + 16 * i, 16)}}}"(qv[{i}])' for i in range(m.KS // 4)]     # Q fragments of four k-steps per 16-register value
-        ins += [f'"{{{vr(m.MB, 16)}}}"(mblk)', f'"{{{vr(m.SC)}}}"(sca)', f'"{{{vr(m.SC + 1)}}}"(scb)', f'"{{{vr(m.VA, 2)}}}"(vah)',
-                f'"{{{vr(m.KB)}}}"(kah)', f'"{{{vr(m.ONES, 8)}}}"(onesv)']
-        out.append(f"#define RSA_K5F8H{tag}_OPS : {', '.join(outs)} : {', '.join(ins)}")
-        insd = ins + [f'"{{{vr(m.DK, m.NPK)}}}"(dk)', f'"{{{vr(m.DV, m.NPV)}}}"(dv)', '[kb16] "s"(kb16)', '[vsrc] "s"(vsrc)', '[ldsw] "s"(ldsw)']
-        out.append(f"#define RSA_K5F8H{tag}_OPSD : {', '.join(outs)} : {', '.join(insd)}")
-        out.append(f"#define RSA_K5F8H{tag}_CLOBBER " + ", ".join(f'"v{r}"' for r in range(m.tmp0, m.tmp1)))
+        ins = [pin("", m.Q + 16 * i, 16, f"qv[{i}]") for i in range(m.KS // 4)]     # Q fragments of four k-steps per 16-register value
+        ins += [pin("", m.MB, 16, "mblk"), pin("", m.SC, 1, "sca"), pin("", m.SC + 1, 1, "scb"), pin("", m.VA, 2, "vah"),
+                pin("", m.KB, 1, "kah"), pin("", m.ONES, 8, "onesv")]
+        out.append(ops_macro(f"RSA_K5F8H{tag}_OPS", outs8(m), ins))
+        insd = ins + [pin("", m.DK, m.NPK, "dk"), pin("", m.DV, m.NPV, "dv"), '[kb16] "s"(kb16)', '[vsrc] "s"(vsrc)', '[ldsw] "s"(ldsw)']
+        out.append(ops_macro(f"RSA_K5F8H{tag}_OPSD", outs8(m), insd))
+        out.append(f"#define RSA_K5F8H{tag}_CLOBBER " + clobbers("v", range(m.tmp0, m.tmp1)))
         out.append(f"// pv form, head dim {D8}: O v[0:{m.Q - 1}], Q v[{m.Q}:{m.SA - 1}], SA v[{m.SA}:{m.SB - 1}], SB v[{m.SB}:{m.MB - 1}], reference block "
                    f"v[{m.MB}:{m.LACC - 1}], l v[{m.LACC}:{m.LACC + 3}], temporaries v[{m.tmp0}:{m.tmp1 - 1}], scales v[{m.SC}:{m.SC + 1}], "
                    f"V / K addresses v[{m.VA}:{m.KB}], ones v[{m.ONES}:{m.ONES + 7}], DMA lane offsets v[{m.DK}:{m.end - 1}]")

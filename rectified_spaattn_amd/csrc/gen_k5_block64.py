@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-# (round 6: head dim 64 beside 128 -- RSA_K5V_* beside RSA_K5W_*, configure(d) below; the docstring describes head dim 128)
-"""Generator of the 64-rows-per-wave form of K5's main loop (rsa_attn_block64.h), head dim 128.
+"""Generator of the 64-rows-per-wave form of K5's main loop (rsa_attn_block64.h): RSA_K5W_* = head dim 128, RSA_K5V_* = head dim 64.
+
+The text below describes head dim 128.  Head dim 64 (round 6) is the same streams on 8 + 8 MFMAs per 32-key sub-step; everything
+that differs is a field of HeadDim, one immutable object per head dim, which every function here takes as its first argument.
 
 One wave owns 64 query rows (two 32-row halves h = 0, 1) and the WHOLE register file of its SIMD (one wave per SIMD, 512
 registers): every K fragment and every V^T fragment read from LDS feeds TWO MFMAs (one per row half), so the LDS operand
@@ -52,39 +54,47 @@ Two products:
     and the accumulator-file housekeeping.  One statement per U: alternative statements that define the same pinned tiles make
     hipcc copy the tiles around every one of them.
 
-The output depends on nothing but this file.
+The output depends on nothing but this file and the generators' shared core, k5gen.py.
 
 usage: python3 gen_k5_block64.py > rsa_attn_block64.h        (python3 gen_k5_block64.py stats: per-gap issue costs)
 """
 import sys
+from dataclasses import dataclass
+from types import MappingProxyType
+
+from k5gen import CVT_PK, MFMA16, Stream, ar, clobbers, lds_dma, macro, ops_macro, pin, row_max, sr, vr
 
 AHEAD = 4
-COST = dict(exp=8, cvt=5, add=4, max=4, mov=4, swap=4, lds=4, wait=1, dma=24)   # (dma: the piece keeps its gap to itself at head dim 128;
+# issue cycles of the 64-row kernel's vector work and of what rides in its gaps (the 32-row kernels' table differs)
+COST64 = dict(exp=8, cvt=5, add=4, max=4, mov=4, swap=4, lds=4, wait=1, dma=24)   # (dma: the piece keeps its gap to itself at head dim 128;
                                                                                  # pricing it at 4 changes nothing measurable: r06_k5_forms.txt form 7)
-D, KS, DT = 128, 8, 4
-HALF = 32 * D * 2             # bytes of a 32-key half-tile
-VRING = 4 * HALF              # LDS offset of the V ring
-NQK, NPV, NMF = 2 * KS, 4 * DT, 2 * KS + 4 * DT      # MFMAs of a block: scores, P . V, all
-PFX = "K5W"                   # macro prefix: K5W = head dim 128, K5V = head dim 64
 
 
-def configure(d):
-    """Head dim of the streams generated from here on (round 6: 64 beside 128).  Head dim 64: 8 + 8 MFMAs per 32-key sub-step against
-    the same softmax; a half-tile is 4 KiB = 4 LDS-DMA pieces (2 per wave), so the loop issues 2 + 2 pieces per sub-step."""
-    global D, KS, DT, HALF, VRING, NQK, NPV, NMF, PFX, DMA_GAPS, SALU_AT, VMC, GAPC, NEXP
-    D, KS, DT = d, d // 16, d // 32
-    HALF = 32 * D * 2
-    VRING = 4 * HALF
-    NQK, NPV, NMF = 2 * KS, 4 * DT, 2 * KS + 4 * DT
-    PFX = "K5W" if d == 128 else "K5V"
-    if d == 128:
-        DMA_GAPS = [4 * j + 1 for j in range(8)]
-        SALU_AT = dict(k=22, k3=(22, 23, 24), v=30, h1=(2, 3))
-        VMC, GAPC, NEXP = 16, 24, 2
-    else:
-        DMA_GAPS = [1, 3, 9, 11]        # K0 K1 | V0 V1: the wave's 2 + 2 pieces of the sub-step
-        SALU_AT = dict(k=4, k3=(4, 5, 6), v=12, h1=(2, 3))
-        VMC, GAPC, NEXP = 8, 36, 4
+@dataclass(frozen=True)
+class HeadDim:
+    """What depends on the head dim.  Head dim 64 (round 6): 8 + 8 MFMAs per 32-key sub-step against the same softmax; a half-tile is
+    4 KiB = 4 LDS-DMA pieces (2 per wave), so the loop issues 2 + 2 pieces per sub-step."""
+    D: int
+    PFX: str                  # macro prefix: K5W = head dim 128, K5V = head dim 64
+    DMA_GAPS: tuple           # the gaps that carry the wave's LDS-DMA pieces
+    SALU_AT: MappingProxyType  # gaps of the loop's scalar bookkeeping (gen_loop)
+    VMC: int                  # LDS-DMA pieces of the last two sub-steps that may still fly at a sub-step boundary
+    GAPC: int                 # issue cycles of vector work dealt into one MFMA gap (head dim 64: 36 -- 16 MFMAs per sub-step cannot hide
+                              # the softmax of 64 x 32 scores, the stream is paced by the vector port there)
+    NEXP: int                 # exponentials per MFMA gap while there are any
+    KS = property(lambda c: c.D // 16)
+    DT = property(lambda c: c.D // 32)
+    HALF = property(lambda c: 32 * c.D * 2)              # bytes of a 32-key half-tile
+    VRING = property(lambda c: 4 * c.HALF)               # LDS offset of the V ring
+    NQK = property(lambda c: 2 * c.KS)                   # MFMAs of a block: scores,
+    NPV = property(lambda c: 4 * c.DT)                   # P . V,
+    NMF = property(lambda c: c.NQK + c.NPV)              # all
+
+
+HEAD_DIMS = (HeadDim(128, "K5W", tuple(4 * j + 1 for j in range(8)),       # every fourth gap
+                     MappingProxyType(dict(k=22, k3=(22, 23, 24), v=30, h1=(2, 3))), VMC=16, GAPC=24, NEXP=2),
+             HeadDim(64, "K5V", (1, 3, 9, 11),                             # K0 K1 | V0 V1: the wave's 2 + 2 pieces of the sub-step
+                     MappingProxyType(dict(k=4, k3=(4, 5, 6), v=12, h1=(2, 3))), VMC=8, GAPC=36, NEXP=4))
 
 # ---- register map ----
 SA = [0, 16]
@@ -94,6 +104,7 @@ P = [96, 104]
 KF, VF = 112, 128
 PS = [144, 145]
 T = [146, 147, 148, 149]
+TH, MX = [T[0:2], T[2:4]], ["%[mx0]", "%[mx1]"]      # per row half: the row maximum's temporaries, its result
 TMP0, TMP1 = 96, 150          # clobbered temporaries [TMP0, TMP1)
 KA, VA = 152, 160
 VOK, VOV = 168, 172           # per-lane DMA source offsets of the wave's four K pieces / four V pieces of a half-tile
@@ -101,66 +112,41 @@ VOK, VOV = 168, 172           # per-lane DMA source offsets of the wave's four K
 S_KB, S_KL, S_VB, S_VL, S_BLK, S_CNT, S_T0, S_T2, S_K128, S_V128, S_KST, S_VST = 80, 82, 84, 86, 87, 88, 90, 92, 94, 95, 96, 97
 S_CLOB = list(range(80, 98))
 LOOP_PRE = 24                 # issue cycles of vector work the loop's blocks put in front of their first MFMA (the boundary blocks: 64)
-DMA_GAPS = [4 * j + 1 for j in range(8)]      # the 8 gaps that carry the wave's LDS-DMA pieces: every fourth gap
-SALU_AT = dict(k=22, k3=(22, 23, 24), v=30, h1=(2, 3))     # gaps of the loop's scalar bookkeeping (gen_loop)
-VMC = 16                      # LDS-DMA pieces of the last two sub-steps that may still fly at a sub-step boundary
-GAPC = 24                     # issue cycles of vector work dealt into one MFMA gap (head dim 64: 36 -- 16 MFMAs per sub-step cannot hide
-                              # the softmax of 64 x 32 scores, the stream is paced by the vector port there)
-NEXP = 2                      # exponentials per MFMA gap while there are any (head dim 64: 4)
-STATS = None
 
 
-def AO(h, dt):
-    return 16 * (DT * h + dt)
+def AO(c, h, dt):
+    return 16 * (c.DT * h + dt)
 
 
-def AQ(h, ks):
-    return 32 * DT + 4 * (KS * h + ks)
+def AQ(c, h, ks):
+    return 32 * c.DT + 4 * (c.KS * h + ks)
 
 
-def vr(a, n=1):
-    return f"v{a}" if n == 1 else f"v[{a}:{a + n - 1}]"
-
-
-def ar(a, n=1):
-    return f"a{a}" if n == 1 else f"a[{a}:{a + n - 1}]"
-
-
-def sr(a, n=1):
-    return f"s{a}" if n == 1 else f"s[{a}:{a + n - 1}]"
-
-
-def gen_block(dt, U, dma, chain=None, pre=64, salu=None, loop=False, rowmax=True, halfdma=False):
+def gen_block(c, dt, U, dma, chain=None, pre=64, salu=None, loop=False, rowmax=True, halfdma=False, stats=None):
     """Block U.  dma: issue the wave's pieces from the scalar walkers (halfdma: only every second one, the 256-row form).  chain
     (the loop): the block does not open with its K reads -- the previous block issued them in its tail -- and issues the NEXT
     block's first four K reads itself, behind the lines of `chain` (the sub-step boundary: vmcnt wait, barrier, ...), which sit
     in front of MFMA 30: behind the wait for the last V^T fragment, so every LDS read of this sub-step has returned when the
     barrier releases the slots.  pre: issue cycles of vector work in front of the first MFMA.  salu: scalar lines per gap.
     loop: the row maxima go ahead of the row sums, followed by the deferred-rescale test's two compares (the loop keeps the
-    branch).  rowmax=False: no row maxima at all (the static body)."""
-    mf = "v_mfma_f32_32x32x16_bf16" if dt == "bf16" else "v_mfma_f32_32x32x16_f16"
-    cv = "v_cvt_pk_bf16_f32" if dt == "bf16" else "v_cvt_pk_f16_f32"
+    branch).  rowmax=False: no row maxima at all (the static body).  stats: a list that receives the per-gap issue costs."""
+    D, KS, DT, HALF, NQK, NMF = c.D, c.KS, c.DT, c.HALF, c.NQK, c.NMF
+    mf, cv = MFMA16[dt], CVT_PK[dt]
     SC, SN = (SA, SB) if U % 2 == 0 else (SB, SA)
     koff = ((U + 1) & 3) * HALF
-    voff = VRING + U * HALF
-    lines, lds_seq = [], []
+    voff = c.VRING + U * HALF
+    s = Stream()
+    lines = s.lines
 
     def k_read(ks):
-        lines.append(f"ds_read_b128 {vr(KF + 4 * (ks % AHEAD), 4)}, {vr(KA + ks)} offset:{koff}")
-        lds_seq.append((("K", ks), 1))
+        s.read(("K", ks), [f"ds_read_b128 {vr(KF + 4 * (ks % AHEAD), 4)}, {vr(KA + ks)} offset:{koff}"])
 
     def v_read(p):
         k2, d = divmod(p, DT)
         off = voff + k2 * 16 * D * 2
         b = VF + 4 * (p % AHEAD)
-        lines.append(f"ds_read_b64_tr_b16 {vr(b, 2)}, {vr(VA + 2 * d)} offset:{off}")
-        lines.append(f"ds_read_b64_tr_b16 {vr(b + 2, 2)}, {vr(VA + 2 * d + 1)} offset:{off}")
-        lds_seq.append((("V", p), 2))
-
-    def wait_for(tag):
-        idx = [i for i, (t, _) in enumerate(lds_seq) if t == tag][-1]
-        after = sum(c for _, c in lds_seq[idx + 1:])
-        lines.append(f"s_waitcnt lgkmcnt({after})")
+        s.read(("V", p), [f"ds_read_b64_tr_b16 {vr(b, 2)}, {vr(VA + 2 * d)} offset:{off}",
+                          f"ds_read_b64_tr_b16 {vr(b + 2, 2)}, {vr(VA + 2 * d + 1)} offset:{off}"])
 
     # ---- vector work: an exponential stream and a stream of everything else, each item with what it waits for ----
     # exponentials in groups of four (both halves of two adjacent scores): after group g the packing of P word (g & 3) of
@@ -183,28 +169,17 @@ def gen_block(dt, U, dma, chain=None, pre=64, salu=None, loop=False, rowmax=True
                     + [("add", f"v_add_f32 %[l{h}], %[l{h}], {vr(PS[h])}", 32)])
     addq = [x for pair in zip(*adds) for x in pair]      # the two halves' chains interleaved
     E = NQK + 1        # S_nxt[1]'s last MFMA is MFMA NQK - 1: its readers sit two or more MFMAs behind it
-    maxq = []
-    for h in (0, 1):
-        maxq += [("max", f"v_max_f32 {vr(T[2 * h])}, {vr(SN[h])}, {vr(SN[h] + 1)}")]
-    for h in (0, 1):
-        maxq += [("max", f"v_max_f32 {vr(T[2 * h + 1])}, {vr(SN[h] + 2)}, {vr(SN[h] + 3)}")]
-    for i in range(2, 8):
-        for h in (0, 1):
-            t = T[2 * h + (i & 1)]
-            maxq += [("max", f"v_max3_f32 {vr(t)}, {vr(t)}, {vr(SN[h] + 2 * i)}, {vr(SN[h] + 2 * i + 1)}")]
-    maxq += [("max", f"v_max_f32 {vr(T[2 * h])}, {vr(T[2 * h])}, {vr(T[2 * h + 1])}") for h in (0, 1)]
-    maxq += [("mov", f"v_mov_b32 {vr(T[2 * h + 1])}, {vr(T[2 * h])}") for h in (0, 1)]
     # v_permlane32_swap: 2 wait states behind the VALU write of either operand and in front of a reader of its results: the
     # other half's mov / swap and one s_nop each way ("tail": emitted as one unit, never split by other vector work)
-    tail = ["s_nop 0", f"v_permlane32_swap_b32 {vr(T[0])}, {vr(T[1])}", f"v_permlane32_swap_b32 {vr(T[2])}, {vr(T[3])}", "s_nop 0",
-            f"v_max_f32 %[mx0], {vr(T[0])}, {vr(T[1])}", f"v_max_f32 %[mx1], {vr(T[2])}, {vr(T[3])}"]
+    maxq, tail = row_max(TH, SN, MX, nop=0)
+    tail = [t for _, t in tail]
 
     if loop:
         tail = tail + ["v_cmp_gt_f32 vcc, %[mx0], %[th0]", f"v_cmp_gt_f32 {sr(S_T2, 2)}, %[mx1], %[th1]"]
     if not rowmax:
         maxq, tail = [], []
-    dcost = COST["dma"] if D == 128 else 4
-    dgaps = DMA_GAPS if dma else []
+    dcost = COST64["dma"] if D == 128 else 4
+    dgaps = c.DMA_GAPS if dma else ()
     salu = salu or {}
     ei = 0             # exponentials issued
     last_exp_line = -10
@@ -219,28 +194,28 @@ def gen_block(dt, U, dma, chain=None, pre=64, salu=None, loop=False, rowmax=True
             progress = False
             if cvq and cvq[0][2] <= ei and len(lines) - last_exp_line >= 1 + (1 if cvq[0][2] == ei else 0):
                 k, t, need = cvq.pop(0)
-                lines.append(t); used += COST[k]; progress = True
+                lines.append(t); used += COST64[k]; progress = True
                 continue
-            if ei < len(EXP) and (nexp < NEXP or gap < 0 or final):
+            if ei < len(EXP) and (nexp < c.NEXP or gap < 0 or final):
                 h, i = EXP[ei]
                 lines.append(f"v_exp_f32 {vr(SC[h] + i)}, {vr(SC[h] + i)}")
                 last_exp_line = len(lines) - 1
-                ei += 1; nexp += 1; used += COST["exp"]; progress = True
+                ei += 1; nexp += 1; used += COST64["exp"]; progress = True
                 continue
             if loop and maxq and gap >= E:
                 k, t = maxq.pop(0)
-                lines.append(t); used += COST[k]; progress = True
+                lines.append(t); used += COST64[k]; progress = True
                 continue
             if loop and not maxq and tail and gap >= E:
                 lines.extend(tail); used += len(tail) * 4; tail.clear(); progress = True
                 continue
             if addq and addq[0][2] <= ei and len(lines) - last_exp_line >= 2:
                 k, t, need = addq.pop(0)
-                lines.append(t); used += COST[k]; progress = True
+                lines.append(t); used += COST64[k]; progress = True
                 continue
             if maxq and gap >= E:
                 k, t = maxq.pop(0)
-                lines.append(t); used += COST[k]; progress = True
+                lines.append(t); used += COST64[k]; progress = True
                 continue
             if not maxq and not addq and not cvq and ei == len(EXP) and tail and gap >= E:
                 lines.extend(tail); used += 6 * 4; tail.clear(); progress = True
@@ -261,31 +236,29 @@ def gen_block(dt, U, dma, chain=None, pre=64, salu=None, loop=False, rowmax=True
         isv, hi = pair & 1, pair >> 1
         base, ldsw, vo = (S_VB, S_VL, VOV) if isv else (S_KB, S_KL, VOK)
         j = 2 * hi + sub
-        if sub == 0:
-            lines.append(f"s_add_u32 m0, {sr(ldsw)}, {4096 * hi}")
-            lines.append("s_nop 0")      # (M0 write -> LDS-DMA: one wait state)
-        lines.append(f"global_load_lds_dwordx4 {vr(vo + j)}, {sr(base, 2)}" + (" offset:2048" if sub else ""))
+        lines.extend(lds_dma(vo + j, sr(base, 2) + (" offset:2048" if sub else ""), m0=None if sub else (sr(ldsw), 4096 * hi)))
         dma_j += 1
 
     if chain is None:
         for ks in range(AHEAD):
             k_read(ks)
     else:
-        lds_seq.extend(((("K", ks), 1)) for ks in range(AHEAD))      # in flight since the previous block's tail
+        for ks in range(AHEAD):
+            s.in_flight(("K", ks), 1)      # in flight since the previous block's tail
     emit_slot(pre, -1)
     usage = []
     for i in range(NMF):
         if i < NQK:
             ks, h = divmod(i, 2)
             if h == 0:
-                wait_for(("K", ks))
-            c = vr(NM[h], 16) if ks == 0 else vr(SN[h], 16)
-            lines.append(f"{mf} {vr(SN[h], 16)}, {vr(KF + 4 * (ks % AHEAD), 4)}, {ar(AQ(h, ks), 4)}, {c}")
+                s.wait_for(("K", ks))
+            acc = vr(NM[h], 16) if ks == 0 else vr(SN[h], 16)
+            lines.append(f"{mf} {vr(SN[h], 16)}, {vr(KF + 4 * (ks % AHEAD), 4)}, {ar(AQ(c, h, ks), 4)}, {acc}")
             fixed = 0
             if h == 1 and ks + AHEAD < KS:
-                k_read(ks + AHEAD); fixed += COST["lds"]
+                k_read(ks + AHEAD); fixed += COST64["lds"]
             if h == 0 and ks >= KS - AHEAD:   # V^T fragments 0..3 ride the last QK^T shadows (head dim 128: gaps 8, 10, 12, 14)
-                v_read(ks - (KS - AHEAD)); fixed += 2 * COST["lds"]
+                v_read(ks - (KS - AHEAD)); fixed += 2 * COST64["lds"]
         else:
             p, h = divmod(i - NQK, 2)
             k2, d = divmod(p, DT)
@@ -294,70 +267,57 @@ def gen_block(dt, U, dma, chain=None, pre=64, salu=None, loop=False, rowmax=True
                 for hh in (0, 1):
                     for jj in range(4):
                         assert f"{cv} {vr(P[hh] + 4 * k2 + jj)}," in text, (dt, U, "P not packed before PV", p)
-                wait_for(("V", p))
+                s.wait_for(("V", p))
             if chain is not None and i == NMF - 2:
                 lines.extend(chain)
                 nk = ((U + 2) & 3) * HALF
                 lines.extend(f"ds_read_b128 {vr(KF + 4 * ks, 4)}, {vr(KA + ks)} offset:{nk}" for ks in range(AHEAD))
-            lines.append(f"{mf} {ar(AO(h, d), 16)}, {vr(VF + 4 * (p % AHEAD), 4)}, {vr(P[h] + 4 * k2, 4)}, {ar(AO(h, d), 16)}")
+            lines.append(f"{mf} {ar(AO(c, h, d), 16)}, {vr(VF + 4 * (p % AHEAD), 4)}, {vr(P[h] + 4 * k2, 4)}, {ar(AO(c, h, d), 16)}")
             fixed = 0
             if h == 1 and p + AHEAD < 2 * DT:
-                v_read(p + AHEAD); fixed += 2 * COST["lds"]
+                v_read(p + AHEAD); fixed += 2 * COST64["lds"]
         lines.extend(salu.get(i, []))      # scalar bookkeeping of the loop riding in this gap (free beside an MFMA)
         if i in dgaps:
             dma_piece(); fixed += dcost
-        usage.append(fixed + emit_slot(GAPC - fixed, i, final=(i == NMF - 1)))
+        usage.append(fixed + emit_slot(c.GAPC - fixed, i, final=(i == NMF - 1)))
     assert ei == len(EXP) and not cvq and not addq and not maxq and not tail, (dt, U, "vector work left over")
     assert dma_j == len(dgaps)
-    if STATS is not None:
-        STATS.append((dt, U, dma, usage))
+    if stats is not None:
+        stats.append((dt, U, dma, usage))
     return lines
 
 
 def rowmax_lines(S):
     """mx[h] = row maximum of the 32 x 32 score tile S[h] (both halves), out of the pipelined block."""
-    lines = []
-    for h in (0, 1):
-        lines.append(f"v_max_f32 {vr(T[2 * h])}, {vr(S[h])}, {vr(S[h] + 1)}")
-    for i in range(1, 8):
-        for h in (0, 1):
-            lines.append(f"v_max3_f32 {vr(T[2 * h])}, {vr(T[2 * h])}, {vr(S[h] + 2 * i)}, {vr(S[h] + 2 * i + 1)}")
-    for h in (0, 1):
-        lines.append(f"v_mov_b32 {vr(T[2 * h + 1])}, {vr(T[2 * h])}")
-    lines.append("s_nop 1")
-    lines.append(f"v_permlane32_swap_b32 {vr(T[0])}, {vr(T[1])}")
-    lines.append(f"v_permlane32_swap_b32 {vr(T[2])}, {vr(T[3])}")
-    lines.append("s_nop 1")
-    lines.append(f"v_max_f32 %[mx0], {vr(T[0])}, {vr(T[1])}")
-    lines.append(f"v_max_f32 %[mx1], {vr(T[2])}, {vr(T[3])}")
-    return lines
+    chain, tail = row_max(TH, S, MX, chains=1)
+    return [t for _, t in chain + tail]
 
 
-def gen_qk0(dt):
+def gen_qk0(c, dt):
     """Prologue: S_A[h] = K(half-tile 0, slot 0) . Q[h]^T - m[h], row maxima -- the block's first half without a softmax."""
-    mf = "v_mfma_f32_32x32x16_bf16" if dt == "bf16" else "v_mfma_f32_32x32x16_f16"
-    SN = SA
-    lines = [f"ds_read_b128 {vr(KF + 4 * (ks % AHEAD), 4)}, {vr(KA + ks)}" for ks in range(AHEAD)]
-    for ks in range(KS):
-        # reads outstanding behind fragment ks when it is needed: those issued after it so far
-        lines.append(f"s_waitcnt lgkmcnt({min(AHEAD - 1, KS - 1 - ks)})")
+    SN, s = SA, Stream()
+
+    def k_read(ks):
+        s.read(ks, [f"ds_read_b128 {vr(KF + 4 * (ks % AHEAD), 4)}, {vr(KA + ks)}"])
+
+    for ks in range(AHEAD): k_read(ks)
+    for ks in range(c.KS):
+        s.wait_for(ks)
         for h in (0, 1):
-            c = vr(NM[h], 16) if ks == 0 else vr(SN[h], 16)
-            lines.append(f"{mf} {vr(SN[h], 16)}, {vr(KF + 4 * (ks % AHEAD), 4)}, {ar(AQ(h, ks), 4)}, {c}")
-        if ks + AHEAD < KS:
-            lines.append(f"ds_read_b128 {vr(KF + 4 * (ks % AHEAD), 4)}, {vr(KA + ks + AHEAD)}")
-    lines.append("s_nop 15")     # the last MFMA's passes (8 + margin) before the maxima read S
-    lines.append("s_nop 3")
-    lines += rowmax_lines(SN)
-    return lines
+            acc = vr(NM[h], 16) if ks == 0 else vr(SN[h], 16)
+            s.lines.append(f"{MFMA16[dt]} {vr(SN[h], 16)}, {vr(KF + 4 * (ks % AHEAD), 4)}, {ar(AQ(c, h, ks), 4)}, {acc}")
+        if ks + AHEAD < c.KS: k_read(ks + AHEAD)
+    s.lines.append("s_nop 15")     # the last MFMA's passes (8 + margin) before the maxima read S
+    s.lines.append("s_nop 3")
+    return s.lines + rowmax_lines(SN)
 
 
-def rescale_core(S, al, de, ng):
+def rescale_core(c, S, al, de, ng):
     """O[h] *= al[h], S[h] -= de[h], -m[h] = ng[h] for both halves (operand names given per half)."""
     lines = ["s_nop 11"]     # the last PV MFMA of the preceding block wrote O: 12 wait states before it is read
     for h in (0, 1):
-        for g in range(0, 16 * DT, 8):
-            base = AO(h, 0) + g
+        for g in range(0, 16 * c.DT, 8):
+            base = AO(c, h, 0) + g
             lines += [f"v_accvgpr_read_b32 {vr(TMP0 + j)}, {ar(base + j)}" for j in range(8)]
             lines += [f"v_mul_f32 {vr(TMP0 + j)}, {vr(TMP0 + j)}, {al[h]}" for j in range(8)]
             lines += [f"v_accvgpr_write_b32 {ar(base + j)}, {vr(TMP0 + j)}" for j in range(8)]
@@ -402,7 +362,7 @@ def gen_loop_head0(t0, t1):
             f"s_mov_b32 {sr(S_KL)}, %[ldsk]"]
 
 
-def gen_loop(dt, static=False, halfdma=False):
+def gen_loop(c, dt, static=False, halfdma=False, stats=None):
     """The steady-state loop, one asm statement (see the file docstring).  Operands: cnt (kept blocks to process, >= 0),
     blk0 / blk1 (block index of the first one and of its successor), la (VGPR: LDS byte address of the list entry two blocks
     ahead), kb / vb (64-bit bases of this head's K / V), krow / vrow (bytes per key row), ldsk / ldsv (LDS address of the wave's
@@ -412,8 +372,9 @@ def gen_loop(dt, static=False, halfdma=False):
     loop with (rsa_attn_kernel64.hip: "optimistic static reference"; the kernel checks l and O afterwards and redoes the walk
     through the first body if anything overflowed).
     halfdma: every second LDS-DMA piece dropped, vmcnt(VMC / 2) at the sub-step boundary (the 256-row dense form)."""
+    HALF, SALU_AT = c.HALF, c.SALU_AT
     t0, t1 = sr(S_T0), sr(S_T0 + 1)
-    vmc = VMC // 2 if halfdma else VMC
+    vmc = c.VMC // 2 if halfdma else c.VMC
     L = [f"s_mov_b32 {sr(S_CNT)}, %[cnt]",
          f"s_cmp_eq_u32 {sr(S_CNT)}, 0",
          "s_cbranch_scc1 .Lk5w_done_%=",
@@ -471,7 +432,7 @@ def gen_loop(dt, static=False, halfdma=False):
             if U == 1:
                 salu[gh[0]] = head[:3]
                 salu[gh[1]] = head[3:]
-            L += gen_block(dt, U, True, chain=tail, pre=LOOP_PRE, salu=salu, loop=online, rowmax=online, halfdma=halfdma)
+            L += gen_block(c, dt, U, True, chain=tail, pre=LOOP_PRE, salu=salu, loop=online, rowmax=online, halfdma=halfdma, stats=stats)
             if online:    # deferred-rescale test on the scores the NEXT block consumes (S_nxt of this block; compares in the block)
                 L += [f"s_or_b64 vcc, vcc, {sr(S_T2, 2)}", f"s_cbranch_vccnz .Lk5w_resc{U}_%=", f".Lk5w_back{U}_%=:"]
         L += [f"s_sub_u32 {sr(S_CNT)}, {sr(S_CNT)}, 1", f"s_cmp_lg_u32 {sr(S_CNT)}, 0", f"s_cbranch_scc1 .Lk5w_{lname}_%=",
@@ -480,49 +441,33 @@ def gen_loop(dt, static=False, halfdma=False):
     for U in range(4):
         S = SB if U % 2 == 0 else SA          # S_nxt of block U
         L += [f".Lk5w_resc{U}_%=:"] + rescale_decide()
-        L += rescale_core(S, [vr(144), vr(145)], [vr(146), vr(147)], [vr(148), vr(149)])
+        L += rescale_core(c, S, [vr(144), vr(145)], [vr(146), vr(147)], [vr(148), vr(149)])
         L += [f"s_branch .Lk5w_back{U}_%="]
     L += [".Lk5w_done_%=:"]
     return L
 
 
-def c_string(lines):
-    return " \\\n".join(f'    "{l}\\n\\t"' for l in lines)
+def header(stats=None):
+    """The text of rsa_attn_block64.h: the streams of head dim 128 (RSA_K5W_*), then those of head dim 64 (RSA_K5V_*)."""
+    return "\n".join(["// GENERATED by gen_k5_block64.py -- do not edit; edit the generator (its docstring says what this is).", "#pragma once", ""]
+                     + [main_one(c, stats) for c in HEAD_DIMS])
 
 
-def main():
-    print("// GENERATED by gen_k5_block64.py -- do not edit; edit the generator (its docstring says what this is).\n#pragma once\n")
-    for d in (128, 64):      # RSA_K5W_* = head dim 128, RSA_K5V_* = head dim 64 (the same streams on 8 + 8 MFMAs per sub-step)
-        configure(d)
-        text = main_one()
-        print(text if d == 128 else text.replace("RSA_K5W_", "RSA_K5V_"))
-    configure(128)
-
-
-def main_one():
+def main_one(c, stats=None):
+    KS, DT, R = c.KS, c.DT, f"RSA_{c.PFX}_"
     out = []
     for dt in ("bf16", "f16"):
         for U in range(4):
-            out.append(f"#define RSA_K5W_BLOCK_{dt.upper()}_U{U} \\")
-            out.append(c_string(gen_block(dt, U, False)))
-            out.append("")
-        out.append(f"#define RSA_K5W_LOOP_{dt.upper()} \\")
-        out.append(c_string(gen_loop(dt, static=(dt == "bf16"))))   # (fp16 P overflows at 2^16: no static body)
-        out.append("")
+            out.append(macro(f"{R}BLOCK_{dt.upper()}_U{U}", gen_block(c, dt, U, False, stats=stats)))
+        out.append(macro(f"{R}LOOP_{dt.upper()}", gen_loop(c, dt, static=(dt == "bf16"), stats=stats)))   # (fp16 P overflows at 2^16: no static body)
         # the 256-row dense form (four waves on one K/V ring): the same loop with every second LDS-DMA piece dropped -- each wave stages
         # 2 + 2 of a half-tile's 8 + 8 pieces (lane offset registers 0 and 2), vmcnt(8) at the sub-step boundary
-        out.append(f"#define RSA_K5W_LOOP_{dt.upper()}_R256 \\")
-        out.append(c_string(gen_loop(dt, static=(dt == "bf16"), halfdma=True)))
-        out.append("")
-        out.append(f"#define RSA_K5W_QK0_{dt.upper()} \\")
-        out.append(c_string(gen_qk0(dt)))
-        out.append("")
+        out.append(macro(f"{R}LOOP_{dt.upper()}_R256", gen_loop(c, dt, static=(dt == "bf16"), halfdma=True, stats=stats)))
+        out.append(macro(f"{R}QK0_{dt.upper()}", gen_qk0(c, dt)))
     # rare paths on the pinned arch registers, as asm as well (the compiler never computes on S / -m: it then keeps every
     # pinned tile in place between statements instead of shuffling 16-register tuples around the blocks)
     for nmx, S in (("A", SA), ("B", SB)):
-        out.append(f"#define RSA_K5W_ROWMAX_{nmx} \\")
-        out.append(c_string(rowmax_lines(S)))
-        out.append("")
+        out.append(macro(f"{R}ROWMAX_{nmx}", rowmax_lines(S)))
         # boundary mask: score i of lane half hh is key kfirst + 4 hh + (i & 3) + 8 (i >> 2); kept iff lo <= key < hi, tested
         # as (key - lo) <u (hi - lo): %[kb0/1] = kfirst + 4 hh - lo[h], %[sp0/1] = hi[h] - lo[h] (0 when the range is empty)
         lines = []
@@ -532,63 +477,49 @@ def main_one():
                 lines.append(f"v_add_u32 {vr(T[0])}, {off}, %[kb{h}]")
                 lines.append(f"v_cmp_gt_u32 vcc, %[sp{h}], {vr(T[0])}")
                 lines.append(f"v_cndmask_b32 {vr(S[h] + i)}, %[ninf], {vr(S[h] + i)}, vcc")
-        out.append(f"#define RSA_K5W_MASK_{nmx} \\")
-        out.append(c_string(lines))
-        out.append("")
+        out.append(macro(f"{R}MASK_{nmx}", lines))
         # deferred rescale of both halves: O[h] *= al[h], S[h] -= de[h], -m[h] = ng[h] (a half that does not move gets 1, 0
         # and its old -m: exact no-ops)
-        out.append(f"#define RSA_K5W_RESCALE_{nmx} \\")
-        out.append(c_string(rescale_core(S, ["%[al0]", "%[al1]"], ["%[de0]", "%[de1]"], ["%[ng0]", "%[ng1]"])))
-        out.append("")
-    out.append("#define RSA_K5W_NMZERO \\")
-    out.append(c_string([f"v_mov_b32 {vr(NM[0] + i)}, 0" for i in range(32)]))
-    out.append("")
+        out.append(macro(f"{R}RESCALE_{nmx}", rescale_core(c, S, ["%[al0]", "%[al1]"], ["%[de0]", "%[de1]"], ["%[ng0]", "%[ng1]"])))
+    out.append(macro(f"{R}NMZERO", [f"v_mov_b32 {vr(NM[0] + i)}, 0" for i in range(32)]))
     # accumulator-file housekeeping: zero O, write one Q fragment, read one O tile
-    out.append("#define RSA_K5W_OZERO \\")
-    out.append(c_string([f"v_accvgpr_write_b32 {ar(i)}, 0" for i in range(32 * DT)]))
-    out.append("")
+    out.append(macro(f"{R}OZERO", [f"v_accvgpr_write_b32 {ar(i)}, 0" for i in range(32 * DT)]))
     # (k-steps / d tiles a head dim does not have get an empty body: the C++ side names all of them and discards by `if constexpr`)
     for h in (0, 1):
         for ks in range(8):
-            out.append(f"#define RSA_K5W_QWRITE_H{h}_K{ks} \\")
-            out.append(c_string([f"v_accvgpr_write_b32 {ar(AQ(h, ks) + j)}, {vr(TMP0 + j)}" for j in range(4)] if ks < KS else ["s_nop 0"]))
-            out.append("")
+            out.append(macro(f"{R}QWRITE_H{h}_K{ks}",
+                             [f"v_accvgpr_write_b32 {ar(AQ(c, h, ks) + j)}, {vr(TMP0 + j)}" for j in range(4)] if ks < KS else ["s_nop 0"]))
     for h in (0, 1):
         for d in range(4):
-            out.append(f"#define RSA_K5W_OREAD_H{h}_D{d} \\")
-            out.append(c_string([f"v_accvgpr_read_b32 {vr(TMP0 + j)}, {ar(AO(h, d) + j)}" for j in range(16)] if d < DT else ["s_nop 0"]))
-            out.append("")
+            out.append(macro(f"{R}OREAD_H{h}_D{d}",
+                             [f"v_accvgpr_read_b32 {vr(TMP0 + j)}, {ar(AO(c, h, d) + j)}" for j in range(16)] if d < DT else ["s_nop 0"]))
     # operand lists
-    souts = [f'"+{{{vr(SA[h], 16)}}}"(SA[{h}])' for h in (0, 1)] + [f'"+{{{vr(SB[h], 16)}}}"(SB[{h}])' for h in (0, 1)]
-    outs = souts + ['[l0] "+v"(l[0])', '[l1] "+v"(l[1])', '[mx0] "=&v"(mx[0])', '[mx1] "=&v"(mx[1])']
-    ins = [f'"{{{vr(NM[h], 16)}}}"(nm[{h}])' for h in (0, 1)] + [f'"{{{vr(KA, 8)}}}"(ka)', f'"{{{vr(VA, 8)}}}"(va)']
-    out.append(f"#define RSA_K5W_OPS : {', '.join(outs)} : {', '.join(ins)}")
-    nmio = [f'"+{{{vr(NM[h], 16)}}}"(nm[{h}])' for h in (0, 1)]
-    louts = souts + nmio + ['[l0] "+v"(l[0])', '[l1] "+v"(l[1])', '[mx0] "+v"(mx[0])', '[mx1] "+v"(mx[1])',
-                            '[th0] "+v"(thr[0])', '[th1] "+v"(thr[1])', '[mr0] "+v"(m_ref[0])', '[mr1] "+v"(m_ref[1])',
-                            '[la] "+v"(la)', '[lv] "=&v"(lv)']
-    lins = [f'"{{{vr(KA, 8)}}}"(ka)', f'"{{{vr(VA, 8)}}}"(va)', f'"{{{vr(VOK, 4)}}}"(vok)', f'"{{{vr(VOV, 4)}}}"(vov)',
+    def tiles(mod, S, name):
+        return [pin(mod, S[h], 16, f"{name}[{h}]") for h in (0, 1)]
+    souts = tiles("+", SA, "SA") + tiles("+", SB, "SB")
+    lsum, mxo = ['[l0] "+v"(l[0])', '[l1] "+v"(l[1])'], ['[mx0] "=&v"(mx[0])', '[mx1] "=&v"(mx[1])']
+    ins = tiles("", NM, "nm") + [pin("", KA, 8, "ka"), pin("", VA, 8, "va")]
+    out.append(ops_macro(f"{R}OPS", souts + lsum + mxo, ins))
+    nmio = tiles("+", NM, "nm")
+    louts = souts + nmio + lsum + ['[mx0] "+v"(mx[0])', '[mx1] "+v"(mx[1])',
+                                   '[th0] "+v"(thr[0])', '[th1] "+v"(thr[1])', '[mr0] "+v"(m_ref[0])', '[mr1] "+v"(m_ref[1])',
+                                   '[la] "+v"(la)', '[lv] "=&v"(lv)']
+    lins = [pin("", KA, 8, "ka"), pin("", VA, 8, "va"), pin("", VOK, 4, "vok"), pin("", VOV, 4, "vov"),
             '[cnt] "s"(cnt)', '[blk0] "s"(blk0)', '[blk1] "s"(blk1)', '[kb] "s"(kb)', '[vb] "s"(vb)', '[krow] "s"(krow)',
             '[vrow] "s"(vrow)', '[ldsk] "s"(ldsk)', '[ldsv] "s"(ldsv)', '[ninf] "v"(ninf)', '[eight] "v"(eight)', '[stat] "s"(stat)']
-    out.append(f"#define RSA_K5W_OPS_LOOP : {', '.join(louts)} : {', '.join(lins)}")
-    outs0 = [f'"+{{{vr(SA[h], 16)}}}"(SA[{h}])' for h in (0, 1)] + ['[mx0] "=&v"(mx[0])', '[mx1] "=&v"(mx[1])']
-    out.append(f"#define RSA_K5W_OPS_QK0 : {', '.join(outs0)} : {', '.join(ins[:3])}")
+    out.append(ops_macro(f"{R}OPS_LOOP", louts, lins))
+    out.append(ops_macro(f"{R}OPS_QK0", tiles("+", SA, "SA") + mxo, ins[:3]))
     for nmx, S in (("A", SA), ("B", SB)):
-        so = [f'"+{{{vr(S[h], 16)}}}"(S{nmx}[{h}])' for h in (0, 1)]
-        out.append(f"#define RSA_K5W_OPS_ROWMAX_{nmx} : {', '.join(so)}, [mx0] \"=&v\"(mx[0]), [mx1] \"=&v\"(mx[1]) :")
-        out.append(f"#define RSA_K5W_OPS_MASK_{nmx} : {', '.join(so)} : [kb0] \"v\"(kb0), [kb1] \"v\"(kb1), [sp0] \"v\"(sp0), "
-                   f"[sp1] \"v\"(sp1), [ninf] \"v\"(ninf)")
-        out.append(f"#define RSA_K5W_OPS_RESCALE_{nmx} : {', '.join(so + nmio)} : [al0] \"v\"(al0), [al1] \"v\"(al1), "
-                   f"[de0] \"v\"(de0), [de1] \"v\"(de1), [ng0] \"v\"(ng0), [ng1] \"v\"(ng1)")
-    out.append(f"#define RSA_K5W_OPS_NMZERO : \"={{{vr(NM[0], 16)}}}\"(nm[0]), \"={{{vr(NM[1], 16)}}}\"(nm[1])")
-    tmp = ", ".join(f'"v{r}"' for r in range(TMP0, TMP1))
-    acc_o = ", ".join(f'"a{r}"' for r in range(32 * DT))
-    acc_q = ", ".join(f'"a{r}"' for r in range(32 * DT, 32 * DT + 8 * KS))
-    out.append(f"#define RSA_K5W_CLOBBER_TMP {tmp}")
-    out.append(f"#define RSA_K5W_CLOBBER_O {acc_o}")
-    out.append(f"#define RSA_K5W_CLOBBER_Q {acc_q}")
-    out.append("#define RSA_K5W_CLOBBER_LOOP " + ", ".join(f'"s{r}"' for r in S_CLOB) + ', "vcc", "scc"')
-    out.append(f"// head dim {D}: O a[0:{32 * DT - 1}], Q a[{32 * DT}:{32 * DT + 8 * KS - 1}]; SA v[0:31], SB v[32:63], -m v[64:95], temporaries v[{TMP0}:{TMP1 - 1}] "
+        so = tiles("+", S, f"S{nmx}")
+        out.append(ops_macro(f"{R}OPS_ROWMAX_{nmx}", so + mxo, []))
+        out.append(ops_macro(f"{R}OPS_MASK_{nmx}", so, ['[kb0] "v"(kb0)', '[kb1] "v"(kb1)', '[sp0] "v"(sp0)', '[sp1] "v"(sp1)', '[ninf] "v"(ninf)']))
+        out.append(ops_macro(f"{R}OPS_RESCALE_{nmx}", so + nmio, [f'[{n}{h}] "v"({n}{h})' for n in ("al", "de", "ng") for h in (0, 1)]))
+    out.append(ops_macro(f"{R}OPS_NMZERO", tiles("=", NM, "nm")))
+    out.append(f"#define {R}CLOBBER_TMP " + clobbers("v", range(TMP0, TMP1)))
+    out.append(f"#define {R}CLOBBER_O " + clobbers("a", range(32 * DT)))
+    out.append(f"#define {R}CLOBBER_Q " + clobbers("a", range(32 * DT, 32 * DT + 8 * KS)))
+    out.append(f"#define {R}CLOBBER_LOOP " + clobbers("s", S_CLOB) + ', "vcc", "scc"')
+    out.append(f"// head dim {c.D}: O a[0:{32 * DT - 1}], Q a[{32 * DT}:{32 * DT + 8 * KS - 1}]; SA v[0:31], SB v[32:63], -m v[64:95], temporaries v[{TMP0}:{TMP1 - 1}] "
                f"(P v[96:111], K ring v[112:127], V ring v[128:143]), K addresses v[{KA}:{KA + 7}], V addresses v[{VA}:{VA + 7}], "
                f"DMA lane offsets v[{VOK}:{VOV + 1}]; the loop statement owns s[{S_CLOB[0]}:{S_CLOB[-1]}]")
     return "\n".join(out)
@@ -596,13 +527,10 @@ def main_one():
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "stats":
-        STATS = []
-        import contextlib
-        import io
-        with contextlib.redirect_stdout(io.StringIO()):
-            main()
-        for dt, U, dma, usage in STATS:
+        stats = []
+        header(stats)
+        for dt, U, dma, usage in stats:
             if dt == "bf16" and U == 0:
                 print(f"U{U} dma={dma}: per-gap issue cost {usage}  total {sum(usage)}")
     else:
-        main()
+        print(header())
