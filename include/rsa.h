@@ -287,6 +287,34 @@ int rsa_block_sparse_gqa_fwd(int B, int H, int Hkv, int Hl, int Sq, int Sk, int 
                              const int32_t* cols, const int32_t* counts, const int32_t* row_lo, const int32_t* row_hi,
                              int64_t range_stride_b, float* tpart, size_t tpart_bytes, rsa_out4 out, void* stream);
 
+/* ---- top-k block selection per list head, written straight into the list contract above (MoBA-style; found by symbol: the
+ * header version stays 6.1).  q [B, H, Sq, D], k [B, Hkv, Sk, D], H a multiple of Hkv, query head h
+ * belongs to K/V head h / (H / Hkv); Hl list heads per batch item, Hl = Hkv (one selection per K/V head, scored with the sum of
+ * its query heads' pooled queries) or Hl = H (one per query head).  len_b = kv_len_dev[b] clamped into [0, Sk] (DEVICE int32, B
+ * values, read on the device only) or, with kv_len_dev NULL, kv_valid in [0, Sk]; off_b = len_b - Sq.
+ *   pooling   qbar[b, h, i] = fp32 sum of the rows < Sq of query block i / their count; kbar[b, hk, j] the same over the keys
+ *             < len_b of key block j
+ *   score     t[b, hl, i, j] = sum over the list head's query heads, ascending, of <qbar[b, h, i], kbar[b, hk, j]> (fp32, no scale)
+ *   visible   j * block < len_b, and with causal j * block <= r1 + off_b, r0 .. r1 the rows of query block i: the blocks in which
+ *             the causal attention call lets some row of the block see some key
+ *   forced    the visible j < keep_first, and with keep_local >= 1 those in [jd_lo - (keep_local - 1), jd_hi] (without causal up
+ *             to jd_hi + (keep_local - 1)), jd_lo = max(r0 + off_b, 0) / block, jd_hi = min(max(r1 + off_b, 0), len_b - 1) / block
+ *   kept      forced and the best max(top_k - |forced|, 0) visible unforced blocks by t, the lower j first among equals:
+ *             |kept| = min(max(top_k, |forced|), |visible|)
+ * Output: bitmask [B * Hl, NQ, ceil(NK/32)], cols [B * Hl, NQ, NK], counts [B * Hl, NQ] exactly as rsa_block_mask_to_lists
+ * writes them (row (b * Hl + hl) * NQ + i), and, unless scores is NULL, t as fp32 [B, Hl, NQ, NK] with -inf at invisible blocks.
+ * NQ = ceil(Sq / block), NK = ceil(Sk / block) <= 8192; block 64 or 128; D 16, 32, 64 or 128, all native.  ws: DEVICE scratch of
+ * at least rsa_block_select_bytes(...) bytes, 16-byte aligned (the pooled vectors).  Two launches, no atomics on floats: the same
+ * inputs give the same bytes.  With non-finite scores which blocks win is unspecified; the lists stay well formed.
+ * Non-positive sizes, Hkv not dividing H, Hl other than Hkv or H, NQ / NK not matching Sq / Sk, a negative top_k / keep_first /
+ * keep_local, kv_valid outside [0, Sk], a NULL or misaligned pointer or stride: RSA_ERR_BAD_ARG; block, D, dtype or NK outside
+ * the above: RSA_ERR_UNSUPPORTED; ws_bytes too small: RSA_ERR_WORKSPACE.  Every check runs before the first HIP call. */
+int rsa_block_select_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes);
+int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q,
+                     rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k, int keep_first,
+                     int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores,
+                     void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

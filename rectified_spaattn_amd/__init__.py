@@ -9,8 +9,8 @@ Module names mirror the reference package `rectified_spaattn`:
     rectified_wan22_attn      RectifiedWan{TI2V,T2V,I2V}SpaAttnProcessor2_0
     rectified_cogvideo_attn   rectified_block_sparse_attention, RectifiedCogVideoXVideoSpaAttnProcessor2_0
     attn_processor            get_attn_processors, set_attn_processor
-    block_sparse              block_sparse_attention over a caller's block mask (also exported here), the mask <-> list
-                              conversions; the four rectified_*_attn modules above also carry the reference's
+    block_sparse              block_sparse_attention over a caller's block mask and select_blocks, the top-k block selection
+                              per K/V head that makes one (both also exported here), the mask <-> list conversions; the four rectified_*_attn modules above also carry the reference's
                               _build_block_index_with_importance_optimized and _triton_block_sparse_attention_onehot
     teacache                  TeaCache step-skipping controller (scripts' teacache_forward bookkeeping), rel_l1_distance
 Device work goes through librsa_hip.so (C-ABI in include/rsa.h): the attention operators and fullattn never fall back to
@@ -48,6 +48,18 @@ def block_sparse_attention(q, k, v, block_mask, *, kv_len=None, sm_scale=None, b
     from . import block_sparse
     return block_sparse.block_sparse_attention(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                                causal=causal, window=window, row_range=row_range)
+
+
+def select_blocks(q, k, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0, mask_heads="kv",
+                  return_scores=False, as_lists=False):
+    """Top-k key blocks per query block by pooled scores, per K/V head (mask_heads="q": per query head), on the device: q
+    [B,H,Sq,D], k [B,Hkv,Sk,D] -> bool block mask [B, Hkv|H, ceil(Sq/block), ceil(Sk/block)] for block_sparse_attention with
+    the same kv_len / causal / block_size; keep_first / keep_local force the first blocks and the diagonal band.
+    See rectified_spaattn_amd.block_sparse.select_blocks."""
+    from . import block_sparse
+    return block_sparse.select_blocks(q, k, top_k, block_size=block_size, kv_len=kv_len, causal=causal, keep_first=keep_first,
+                                      keep_local=keep_local, mask_heads=mask_heads, return_scores=return_scores,
+                                      as_lists=as_lists)
 
 
 def clear_buffer_cache() -> None:

@@ -9,6 +9,8 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              range per query row on top of the mask (rsa_block_sparse_ranged_fwd, one launch per batch)
                              k / v may hold fewer heads than q (GQA / MQA: query head h reads K/V head h // (H // Hkv)) and
                              the mask one row per K/V head: rsa_block_sparse_gqa_fwd, no repeated K/V and no repeated lists
+    select_blocks            a selection of the library's own for that call: pooled scores and a plain top-k per K/V head, with
+                             the call's kv_len and causal alignment, written as lists on the device (rsa_block_select)
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
@@ -366,6 +368,89 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
                                                     lists["cols"].data_ptr() + row * NK * 4, lists["counts"].data_ptr() + row * 4,
                                                     tp, tpb, o4, _core._stream()), "rsa_block_sparse_plain_fwd")
     return out
+
+
+def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None, causal: bool = False,
+                  keep_first: int = 0, keep_local: int = 0, mask_heads: str = "kv", return_scores: bool = False,
+                  as_lists: bool = False):
+    """Top-k key blocks per query block by pooled scores, per K/V head, on the device (MoBA-style): the
+    block_mask of a following block_sparse_attention(q, k, v, mask, kv_len=..., causal=..., block_size=...).
+    q [B,H,Sq,D], k [B,Hkv,Sk,D] with H % Hkv == 0 (query head h belongs to K/V head h // (H // Hkv)), bf16 or fp16, head dim 16,
+    32, 64 or 128 (all native, nothing is padded), any strides block_sparse_attention accepts; block_size 64 or 128;
+    NK = ceil(Sk/block) <= 8192.  kv_len as in block_sparse_attention (None, int, one value per batch item, or an int32 / int64
+    device tensor of 1 or B values, which is read on the device only); off_b = kv_len[b] - Sq.
+      pooling   qbar / kbar: the fp32 mean of a block's rows < Sq / of its keys < kv_len[b]
+      score     t[b, hl, i, j] = sum over the list head's query heads, ascending, of <qbar[b, h, i], kbar[b, h // g, j]>, fp32, no
+                sm_scale.  mask_heads="kv": one list head per K/V head (its H // Hkv query heads summed); "q": one per query head
+      visible   j * block < kv_len[b]; with causal also j * block <= r1 + off_b (r0 .. r1 = the rows of query block i): the blocks
+                in which block_sparse_attention(causal=True) lets some row of the block see some key
+      forced    the visible j < keep_first, and with keep_local >= 1 the visible j in [jd_lo - (keep_local - 1), jd_hi] (without
+                causal: up to jd_hi + (keep_local - 1)), jd_lo = max(r0 + off_b, 0) // block,
+                jd_hi = min(max(r1 + off_b, 0), kv_len[b] - 1) // block
+      kept      forced and the best max(top_k - |forced|, 0) visible unforced blocks, by t descending, the lower j on equal t:
+                |kept| = min(max(top_k, |forced|), |visible|); top_k = 0 keeps the forced blocks alone
+    Returns the bool mask [B, Hl, NQ, NK] (Hl = Hkv or H), or with as_lists=True the dict block_mask_to_lists returns for it
+    (bitmask, cols, counts; row (b * Hl + hl) * NQ + i); with return_scores=True a pair, the second the fp32 scores
+    [B, Hl, NQ, NK] with -inf at invisible blocks.  Two calls on the same inputs give the same bytes.  With non-finite scores
+    which blocks win is unspecified; the rows stay well formed.  Asynchronous on the current stream."""
+    if block_size not in _lib.BLOCKS:
+        raise NotImplementedError(f"select_blocks on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
+    blk = int(block_size)
+    if mask_heads not in ("kv", "q"):
+        raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
+    for name, val in (("top_k", top_k), ("keep_first", keep_first), ("keep_local", keep_local)):
+        if not isinstance(val, int) or isinstance(val, bool) or val < 0:
+            raise ValueError(f"{name}: an int >= 0, got {val!r}")
+    if q.dim() != 4 or k.dim() != 4:
+        raise ValueError("q, k: [B, H, S, D] tensors")
+    B, H, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h belongs to K/V head h // (H // Hkv))")
+    if k.shape[0] != B or k.shape[3] != D:
+        raise ValueError(f"k {tuple(k.shape)} does not match q {tuple(q.shape)}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype:
+        raise ValueError(f"q, k: one dtype, bfloat16 or float16 (got {q.dtype}, {k.dtype})")
+    if D not in (16, 32, 64, 128):
+        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
+    if Sq <= 0 or Sk <= 0:
+        raise ValueError(f"empty operands (Sq = {Sq}, Sk = {Sk})")
+    NQ, NK = -(-Sq // blk), -(-Sk // blk)
+    if NK > MAX_KEY_BLOCKS:
+        raise ValueError(f"Sk = {Sk} is {NK} key blocks of {blk}: at most {MAX_KEY_BLOCKS}")
+    Hl = Hkv if mask_heads == "kv" else H
+    on_device = isinstance(kv_len, torch.Tensor) and kv_len.is_cuda      # (then it is read on the device only)
+    if on_device:
+        if kv_len.numel() not in (1, B) or kv_len.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"kv_len: an int32 / int64 tensor of 1 or {B} values, got {kv_len.dtype} {tuple(kv_len.shape)}")
+        lens = None
+    else:
+        lens = _kv_lens(kv_len, B, Sk)
+    _core._require_device(q, k)
+    dev = q.device
+    if on_device:
+        kv_dev, kv_valid = kv_len.to(dev).reshape(-1).clamp(0, Sk).to(torch.int32).expand(B).contiguous(), Sk
+    elif len(set(lens)) == 1:
+        kv_dev, kv_valid = None, lens[0]
+    else:
+        kv_dev, kv_valid = torch.tensor(lens, dtype=torch.int32, device=dev), Sk
+    L = _lib.lib()
+    q, k = _core._as_bhsd(q), _core._as_bhsd(k)
+    need = ctypes.c_size_t(0)
+    _lib.check(L.rsa_block_select_bytes(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), "rsa_block_select_bytes")
+    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+    out = dict(bitmask=torch.empty((B * Hl, NQ, (NK + 31) // 32), dtype=torch.int32, device=dev),
+               cols=torch.empty((B * Hl, NQ, NK), dtype=torch.int32, device=dev),
+               counts=torch.empty((B * Hl, NQ), dtype=torch.int32, device=dev))
+    scores = torch.empty((B, Hl, NQ, NK), dtype=torch.float32, device=dev) if return_scores else None
+    with torch.cuda.device(dev):
+        _lib.check(L.rsa_block_select(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NQ, NK, _core._t4(q), _core._t4(k),
+                                      kv_dev.data_ptr() if kv_dev is not None else None, kv_valid, int(bool(causal)),
+                                      min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), ws.data_ptr(), need.value,
+                                      out["bitmask"].data_ptr(), out["cols"].data_ptr(), out["counts"].data_ptr(),
+                                      scores.data_ptr() if scores is not None else None, _core._stream()), "rsa_block_select")
+    sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
+    return (sel, scores) if return_scores else sel
 
 
 def build_block_index(query: torch.Tensor, key: torch.Tensor, top_k: int, block_size_M: int = 128, block_size_N: int = 128,

@@ -1,0 +1,353 @@
+// Top-k block selection per list head on the device (include/rsa.h: rsa_block_select_bytes, rsa_block_select; DESIGN.md
+// section 5.11).  Two kernels, both plain HIP C++ for wave64:
+//
+//   block_select_pool_kernel   one workgroup per (b, list head, query block) and per (b, K/V head, key block): the fp32 mean of
+//                              the block's rows per channel.  q and k are read exactly once, 16 bytes per lane and load.  The
+//                              query side adds the means of the list head's query heads in ascending order (H / Hl of them).
+//   block_select_kernel        one 256-thread workgroup per list row (b, list head, query block): the pooled scores of the
+//                              visible key blocks into LDS as order-preserving 32-bit keys, the k-th best by a radix select over
+//                              LDS histograms (8 bits a pass), ties to the lower block index by ballot / prefix popcount, and the
+//                              list contract of rsa_block_mask.hip (bitmask, ascending cols, counts) in 64-block ballot steps.
+//
+// Every sum has a fixed order (no floating-point atomics; the histograms count integers): two calls give the same bytes.
+#include "rsa_common.h"
+
+#include <math.h>
+
+#define SEL_NT 256
+#define SEL_MAX_NK 8192
+#define SEL_MAX_STEPS (SEL_MAX_NK / 64)
+
+// ---- pooling ---------------------------------------------------------------------------------------------------------------------
+template <typename Tag>
+__device__ __forceinline__ void sel_add8(float (&a)[8], const uint4 v) {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        a[2 * i] += rsa_to_f32<Tag>((unsigned short)(w[i] & 0xFFFFu));
+        a[2 * i + 1] += rsa_to_f32<Tag>((unsigned short)(w[i] >> 16));
+    }
+}
+
+// Sum over `rows` rows (>= 1, uniform over the workgroup) of D channels: thread t < D returns channel t's sum.  Thread t reads the
+// 16-byte chunk t % (D / 8) of rows t / (D / 8), + 2048 / D, ...; the partials meet over xor strides D / 8 .. 32 inside the wave
+// and as (w0 + w1) + (w2 + w3) through LDS.
+template <typename Tag>
+__device__ __forceinline__ float sel_pool_block(const unsigned short* __restrict__ base, long stride_s, int rows, int D,
+                                                float (*red)[128]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int C = D >> 3, RP = SEL_NT / C;
+    const int c = tid % C;
+    const unsigned short* p = base + c * 8;
+    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int r = tid / C;
+    for (; r + 3 * RP < rows; r += 4 * RP) {
+        uint4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const uint4*>(p + (long)(r + u * RP) * stride_s);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sel_add8<Tag>(a, v[u]);
+    }
+    for (; r < rows; r += RP) sel_add8<Tag>(a, *reinterpret_cast<const uint4*>(p + (long)r * stride_s));
+    for (int m = C; m < 64; m <<= 1) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] += __shfl_xor(a[e], m, 64);
+    }
+    __syncthreads();   // (red may still be read from the previous head)
+    if (lane < C) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) red[wave][lane * 8 + e] = a[e];
+    }
+    __syncthreads();
+    return tid < D ? (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]) : 0.f;
+}
+
+__device__ __forceinline__ int sel_key_limit(const int32_t* __restrict__ kv_len, int b, int kv_valid, int Sk) {
+    return kv_len ? min(max(kv_len[b], 0), Sk) : kv_valid;
+}
+
+template <typename Tag>
+__global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q, rsa_tensor4 k, int H, int Hkv, int Hl, int Sq,
+                                                                   int Sk, int D, int blk, int NQ, int NK, long q_jobs,
+                                                                   const int32_t* __restrict__ kv_len, int kv_valid,
+                                                                   float* __restrict__ kbar, float* __restrict__ qsum) {
+    __shared__ float red[4][128];
+    const int tid = threadIdx.x;
+    long job = blockIdx.x;
+    if (job < q_jobs) {
+        const int i = (int)(job % NQ);
+        const long bh = job / NQ;
+        const int hl = (int)(bh % Hl), gl = H / Hl;
+        const long b = bh / Hl;
+        const long r0 = (long)i * blk;
+        const int rows = (int)min((long)blk, (long)Sq - r0);
+        const float cnt = (float)rows;
+        float tot = 0.f;
+        for (int u = 0; u < gl; ++u) {      // the list head's query heads, ascending: each head's own mean, then the sum
+            const unsigned short* base = static_cast<const unsigned short*>(q.ptr) + b * q.stride_b +
+                                         (long)(hl * gl + u) * q.stride_h + r0 * q.stride_s;
+            tot += sel_pool_block<Tag>(base, q.stride_s, rows, D, red) / cnt;
+        }
+        if (tid < D) qsum[job * D + tid] = tot;
+        return;
+    }
+    job -= q_jobs;
+    const int j = (int)(job % NK);
+    const long bh = job / NK;
+    const int hk = (int)(bh % Hkv);
+    const long b = bh / Hkv;
+    const int len = sel_key_limit(kv_len, (int)b, kv_valid, Sk);
+    const int rows = min(blk, len - j * blk);       // keys of block j below the limit (uniform over the workgroup)
+    float mean = 0.f;
+    if (rows > 0) {
+        const unsigned short* base = static_cast<const unsigned short*>(k.ptr) + b * k.stride_b + (long)hk * k.stride_h +
+                                     (long)j * blk * k.stride_s;
+        mean = sel_pool_block<Tag>(base, k.stride_s, rows, D, red) / (float)rows;
+    }
+    if (tid < D) kbar[job * D + tid] = mean;
+}
+
+// ---- score and select ------------------------------------------------------------------------------------------------------------
+// fp32 -> u32 with the order of the floats (-0 counts as +0); and back.
+__device__ __forceinline__ unsigned sel_key(float x) {
+    unsigned u = __float_as_uint(x);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sel_unkey(unsigned key) {
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+// Exclusive prefix sums of cnt[0 .. n) in place (n <= SEL_MAX_STEPS) by one wave; returns the total (in every lane).
+__device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
+    int run = 0;
+    for (int s0 = 0; s0 < n; s0 += 64) {
+        const int s = s0 + lane;
+        const int c = s < n ? cnt[s] : 0;
+        int inc = c;
+        for (int m = 1; m < 64; m <<= 1) {
+            const int o = __shfl_up(inc, m, 64);
+            if (lane >= m) inc += o;
+        }
+        if (s < n) cnt[s] = run + inc - c;
+        run += __shfl(inc, 63, 64);
+    }
+    return run;
+}
+
+// L = D / 4 lanes share one pooled key row (a float4 each); a wave scores 64 / L key blocks per step.
+template <int L>
+__global__ __launch_bounds__(SEL_NT) void block_select_kernel(const float* __restrict__ kbar, const float* __restrict__ qsum,
+                                                              int Hkv, int Hl, int Sq, int Sk, int blk, int NQ, int NK,
+                                                              const int32_t* __restrict__ kv_len, int kv_valid, int causal,
+                                                              int top_k, int keep_first, int keep_local,
+                                                              uint32_t* __restrict__ bitmask, int32_t* __restrict__ cols,
+                                                              int32_t* __restrict__ counts, float* __restrict__ scores) {
+    extern __shared__ unsigned keys[];              // [NK]: the scores of the visible blocks as ordered keys
+    __shared__ int hist[256];
+    __shared__ int wsum[4];
+    __shared__ unsigned pick[2];
+    __shared__ int step_eq[SEL_MAX_STEPS], step_kept[SEL_MAX_STEPS];
+    __shared__ unsigned long long step_mask[SEL_MAX_STEPS];
+    constexpr int D = 4 * L, RW = 64 / L, U = 4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long row = blockIdx.x;
+    const int i = (int)(row % NQ);
+    const long bh = row / NQ;
+    const int hl = (int)(bh % Hl);
+    const long b = bh / Hl;
+    const int hk = hl / (Hl / Hkv);
+    const int len = sel_key_limit(kv_len, (int)b, kv_valid, Sk);
+
+    // visible blocks: a prefix [0, nvis) of the row; forced blocks: [0, kf) and [flo, fhi] within it
+    const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
+    int nvis = min(NK, (len + blk - 1) / blk);
+    if (causal) nvis = r1 + off < 0 ? 0 : (int)min((long)nvis, (r1 + off) / blk + 1);
+    const int kf = min(keep_first, nvis);
+    int flo = 1, fhi = 0;
+    if (keep_local >= 1 && nvis > 0) {
+        const long jd_lo = max(r0 + off, 0L) / blk, jd_hi = min(max(r1 + off, 0L), (long)len - 1) / blk;
+        const long ext = min(keep_local - 1, SEL_MAX_NK);
+        flo = (int)max(jd_lo - ext, 0L);
+        fhi = (int)min(causal ? jd_hi : jd_hi + ext, (long)nvis - 1);
+    }
+    const int nf = kf + max(0, fhi - max(flo, kf) + 1);
+    auto forced = [&](int j) { return j < kf || (j >= flo && j <= fhi); };
+
+    // scores of the visible blocks
+    {
+        const int cl = lane % L, sub = lane / L;
+        const float4 qv = *reinterpret_cast<const float4*>(qsum + row * D + cl * 4);
+        const float* kb = kbar + ((b * Hkv + hk) * NK) * D + cl * 4;
+        for (int j0 = wave * RW; j0 < nvis; j0 += 4 * RW * U) {
+            float4 kv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + u * 4 * RW + sub;
+                kv[u] = j < nvis ? *reinterpret_cast<const float4*>(kb + (long)j * D) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + u * 4 * RW + sub;
+                float p = fmaf(qv.w, kv[u].w, fmaf(qv.z, kv[u].z, fmaf(qv.y, kv[u].y, qv.x * kv[u].x)));
+#pragma unroll
+                for (int m = 1; m < L; m <<= 1) p += __shfl_xor(p, m, 64);
+                if (cl == 0 && j < nvis) keys[j] = sel_key(p);
+            }
+        }
+    }
+    __syncthreads();
+    if (scores) {
+        float* sr = scores + row * NK;
+        for (int j = tid; j < NK; j += SEL_NT) sr[j] = j < nvis ? sel_unkey(keys[j]) : -INFINITY;
+    }
+
+    // the key of the need-th best unforced visible block
+    const int nunf = nvis - nf, need = max(top_k - nf, 0);
+    const bool take_all = need >= nunf;
+    const bool radix = !take_all && need > 0;
+    unsigned T = 0u;
+    int need_eq = 0;
+    if (radix) {    // (uniform over the workgroup)
+        unsigned prefix = 0u;
+        int rem = need;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();
+            const unsigned himask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+            for (int j = tid; j < nvis; j += SEL_NT) {
+                const unsigned key = keys[j];
+                if (!forced(j) && (key & himask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
+            }
+            __syncthreads();
+            // thread t owns digit 255 - t: its inclusive prefix over t counts the keys with that digit or a higher one
+            const int h = hist[255 - tid];
+            int inc = h;
+            for (int m = 1; m < 64; m <<= 1) {
+                const int o = __shfl_up(inc, m, 64);
+                if (lane >= m) inc += o;
+            }
+            if (lane == 63) wsum[wave] = inc;
+            __syncthreads();
+            for (int w = 0; w < wave; ++w) inc += wsum[w];
+            if (inc - h < rem && rem <= inc) {      // exactly one thread: the digit that holds the rem-th best
+                pick[0] = prefix | ((unsigned)(255 - tid) << shift);
+                pick[1] = (unsigned)(rem - (inc - h));
+            }
+            __syncthreads();
+            prefix = pick[0];
+            rem = (int)pick[1];
+        }
+        T = prefix;
+        need_eq = rem;      // of the blocks that tie at T, the need_eq lowest are kept
+    }
+
+    // the lists, in 64-block ballot steps: wave w takes steps w, w + 4, ...
+    const int nsteps = (NK + 63) >> 6, NW = (NK + 31) >> 5;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int s = wave; s < nsteps; s += 4) {
+        const int j = s * 64 + lane;
+        const bool eq = radix && j < nvis && !forced(j) && keys[j] == T;
+        const unsigned long long m = __ballot(eq);
+        if (lane == 0) step_eq[s] = __popcll(m);
+    }
+    __syncthreads();
+    if (wave == 0) sel_wave_scan(step_eq, nsteps, lane);
+    __syncthreads();
+    uint32_t* wr = bitmask + row * NW;
+    for (int s = wave; s < nsteps; s += 4) {
+        const int j = s * 64 + lane;
+        const bool vis = j < nvis, f = vis && forced(j);
+        const unsigned key = vis ? keys[j] : 0u;
+        const bool eq = radix && vis && !f && key == T;
+        const unsigned long long me = __ballot(eq);
+        const bool kept = f || (vis && (take_all || (radix && key > T))) || (eq && step_eq[s] + __popcll(me & below) < need_eq);
+        const unsigned long long m = __ballot(kept);
+        if (lane < 2 && 2 * s + lane < NW) wr[2 * s + lane] = lane ? (unsigned)(m >> 32) : (unsigned)m;
+        if (lane == 0) {
+            step_mask[s] = m;
+            step_kept[s] = __popcll(m);
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int total = sel_wave_scan(step_kept, nsteps, lane);
+        if (lane == 0) counts[row] = total;
+    }
+    __syncthreads();
+    int32_t* cr = cols + row * NK;
+    for (int s = wave; s < nsteps; s += 4) {
+        const unsigned long long m = step_mask[s];
+        if ((m >> lane) & 1ull) cr[step_kept[s] + __popcll(m & below)] = s * 64 + lane;
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------
+static int sel_check_sizes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
+    if (B <= 0 || Hkv <= 0 || Hl <= 0 || NQ <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (NK > SEL_MAX_NK) return RSA_ERR_UNSUPPORTED;     // K5's key-block limit
+    const size_t q_jobs = (size_t)B * Hl * NQ, k_jobs = (size_t)B * Hkv * NK;
+    if (q_jobs + k_jobs > 0x7FFFFFFFull) return RSA_ERR_UNSUPPORTED;     // one workgroup each
+    if (bytes) *bytes = (q_jobs + k_jobs) * (size_t)D * sizeof(float);
+    return RSA_OK;
+}
+
+extern "C" int rsa_block_select_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
+    if (!bytes) return RSA_ERR_BAD_ARG;
+    return sel_check_sizes(B, Hkv, Hl, D, NQ, NK, bytes);
+}
+
+extern "C" int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK,
+                                rsa_tensor4 q, rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k,
+                                int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                                int32_t* counts, float* scores, void* stream) {
+    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || Sk <= 0) return RSA_ERR_BAD_ARG;
+    if (H % Hkv || (Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
+    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
+    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (NQ != (int)(((long)Sq + block - 1) / block) || NK != (int)(((long)Sk + block - 1) / block)) return RSA_ERR_BAD_ARG;
+    size_t need = 0;
+    const int st = sel_check_sizes(B, Hkv, Hl, D, NQ, NK, &need);
+    if (st != RSA_OK) return st;
+    if (top_k < 0 || keep_first < 0 || keep_local < 0) return RSA_ERR_BAD_ARG;
+    if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
+    if (!ws || !bitmask || !cols || !counts) return RSA_ERR_BAD_ARG;
+    if (rsa_check_tensor(q) != RSA_OK || rsa_check_tensor(k) != RSA_OK) return RSA_ERR_BAD_ARG;
+    if (q.stride_b < 0 || q.stride_h < 0 || q.stride_s < 0 || k.stride_b < 0 || k.stride_h < 0 || k.stride_s < 0)
+        return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(bitmask) | reinterpret_cast<uintptr_t>(cols) | reinterpret_cast<uintptr_t>(counts) |
+         reinterpret_cast<uintptr_t>(scores) | reinterpret_cast<uintptr_t>(kv_len_dev)) & 3)
+        return RSA_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return RSA_ERR_BAD_ARG;
+    if (ws_bytes < need) return RSA_ERR_WORKSPACE;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long q_jobs = (long)B * Hl * NQ, k_jobs = (long)B * Hkv * NK;
+    float* qsum = static_cast<float*>(ws);              // [B, Hl, NQ, D]
+    float* kbar = qsum + q_jobs * D;                    // [B, Hkv, NK, D]
+    const dim3 pool_grid((unsigned)(q_jobs + k_jobs));
+    if (dtype == RSA_BF16)
+        block_select_pool_kernel<bf16_tag><<<pool_grid, SEL_NT, 0, s>>>(q, k, H, Hkv, Hl, Sq, Sk, D, block, NQ, NK, q_jobs,
+                                                                        kv_len_dev, kv_valid, kbar, qsum);
+    else
+        block_select_pool_kernel<fp16_tag><<<pool_grid, SEL_NT, 0, s>>>(q, k, H, Hkv, Hl, Sq, Sk, D, block, NQ, NK, q_jobs,
+                                                                        kv_len_dev, kv_valid, kbar, qsum);
+    int rc = rsa_launch_status();
+    if (rc != RSA_OK) return rc;
+    const dim3 grid((unsigned)q_jobs);
+    const size_t lds = (size_t)NK * sizeof(unsigned);
+#define SEL_LAUNCH(LANES)                                                                                                       \
+    block_select_kernel<LANES><<<grid, SEL_NT, lds, s>>>(kbar, qsum, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid,      \
+                                                         causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts,    \
+                                                         scores)
+    switch (D) {
+        case 16: SEL_LAUNCH(4); break;
+        case 32: SEL_LAUNCH(8); break;
+        case 64: SEL_LAUNCH(16); break;
+        default: SEL_LAUNCH(32); break;
+    }
+#undef SEL_LAUNCH
+    return rsa_launch_status();
+}
