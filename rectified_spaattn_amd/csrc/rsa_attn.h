@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "rsa_common.h"
+#include "rsa_walk_order.h"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -78,6 +79,10 @@ struct WalkArgs {
     int gsync_gen;                            // aligned starts: workgroups an XCD holds at a time (a generation)
     int gsync_ratio;                          // ... walks that keep 1 / gsync_ratio of the keys or more are not held (default 2)
     int k5_static;                            // 64-row kernel, bf16: the steady state keeps the softmax reference it is entered with (checked, redone if it overflowed)
+    // Walk order of the sparse units (rsa_walk_order.h): u16 [BH, NBp], rank -> unit, written by the walk_order kernels (rsa_attn.hip) in
+    // front of this launch into the end of the caller's tpart; null = the eighth map (every kernel but the 64-row kernel's plain sparse
+    // calls; no room; tuning key k5_walk_order = 0)
+    const unsigned short* order;
 };
 
 struct AttnArgs : WalkArgs {
@@ -127,40 +132,12 @@ __device__ __forceinline__ const A& rsa_kernargs() {
 // of adding a generation of their own.  Tail split (tail_n > 0; sparse units first): the units from index tail_first on -- the
 // last, partial generation -- are walked by tail_p workgroups each, which together fill the slots that generation would leave
 // idle; tail >= 0 is such a piece's index (else -1) and tsp its part of the kept list.
-__host__ __device__ __forceinline__ int rsa_walk_unit(int j, int NBp) { return (j & 7) * (NBp >> 3) + (j >> 3); }   // j-th of a head's NBp
-enum { WALK_NONE = 0, WALK_SPARSE = 1, WALK_TEXT = 2 };
+// With an order table (WalkArgs::order; the 64-row kernel's plain sparse calls) the whole walks are dealt in RUNS instead: the
+// workgroups an XCD holds together walk consecutive units of ONE head in the table's order; the pieces of a split tail stay the
+// units of the map above (rsa_walk_order.h: the arithmetic of both maps lives there, in plain C++).
+template <bool ORDERED = false>
 __device__ __forceinline__ int rsa_walk_map(const WalkArgs& a, int work, int n_units, int& bh, int& unit, int& tsp, int& tail) {
-    tsp = 0;
-    tail = -1;
-    const int n_sparse = a.BH * a.NBp;
-    const bool heavy_last = a.heavy_last != 0;
-    int wh = heavy_last ? work - n_sparse : work;                 // index among the text-row pieces
-    int v = heavy_last ? work : work - a.n_heavy_pad;             // index among the sparse units
-    bool text = heavy_last ? work >= n_sparse : work < a.n_heavy_pad;
-    if (a.tail_n > 0) {
-        const int tail_end = a.tail_first + a.tail_n * a.tail_p;
-        text = work >= tail_end;
-        wh = work - tail_end;
-        if (work >= a.tail_first && !text) {
-            tail = work - a.tail_first;
-            v = a.tail_first + tail / a.tail_p;
-            tsp = tail % a.tail_p;
-        }
-    }
-    if (text) {
-        const int ntq = a.NQB - a.NBv;
-        const int per_bh = ntq * a.tsplit;      // text blocks x key-range splits (tsplit = 1: no split)
-        if (ntq <= 0 || wh >= a.BH * per_bh) return WALK_NONE;
-        bh = wh / per_bh;
-        const int rem = wh % per_bh;
-        unit = a.NBv + rem / a.tsplit;
-        tsp = rem % a.tsplit;
-    } else {
-        bh = v / a.NBp;
-        unit = rsa_walk_unit(v % a.NBp, a.NBp);
-        if (unit >= n_units) return WALK_NONE;
-    }
-    return text ? WALK_TEXT : WALK_SPARSE;
+    return rsa_walk_map_t<ORDERED>(a, work, n_units, bh, unit, tsp, tail);
 }
 
 // Sparse walk of visual block rowi (= bh * NBv + block): its kept list, or part tsp of it for a tail piece (tail >= 0)
@@ -257,9 +234,11 @@ void rsa_set_fp8_smooth_k(int v);     // rsa_fp8.hip; tuning key "fp8_smooth_k"
 // (its 32 CUs x the kernel's workgroups per CU, asked of the runtime by the launcher: 64 for the kernels at head dim 128),
 // so "generation" g = (b >> 3) / gen can only be resident once generation g - 1 has left.  Every workgroup announces itself in the counter of (g, XCD) when it starts and, in front of its first
 // staging instruction, waits until its whole generation has: the 64 walks of an XCD then start their ascending key lists
-// TOGETHER and meet in the XCD's L2 (4 MiB = the K, V of ~60 key blocks) instead of each finding the other 63 at unrelated
-// positions (HunyuanVideo R2, 10 % of the keys kept at random: L2 hit rate 15 % -> 41 %, 116 -> 79 GB over the fabric,
-// which is what bounded that launch: profiles/r04_k5_gsync.md).  Advisory only -- the results do not depend on it: a
+// TOGETHER and meet in the XCD's L2 (4 MiB = the K, V of 64 key blocks of ONE head) instead of each finding the other 63 at unrelated
+// positions (HunyuanVideo R2, 10 % of the keys kept at random: L2 hit rate 15 % -> 41 %, 116 -> 79 GB over the fabric:
+// profiles/r04_k5_gsync.md).  How often they meet then depends on WHICH 64 walks a generation holds: with the order table
+// (rsa_walk_order.h) they are one head's, neighbours by mean kept key block -- 41.5 % -> 62.9 % hits, 79.3 -> 50.1 GB at the same
+// shape, for about 3 % of the launch's time: the fabric was not what bounded it (profiles/k5_walk_order.md).  Advisory only -- the results do not depend on it: a
 // bounded wait, switched off for the rest of the launch by the first workgroup that runs into the bound (word 0), so
 // kernels of other processes sharing the device cannot stall this one.  Walks that keep half of the keys or more are not held
 // back (round 4 drew that line at a fifth; measured at the reference scripts' operating points in round 5 --

@@ -24,6 +24,8 @@ static int g_k5_rows256 = 1;    // dense calls at head dim 128: 256-row tiles (0
 static int g_k5_static = 1;     // 64-row kernel, bf16: optimistic static softmax reference in the steady-state loop (0 = online body only)
 int rsa_k5_static() { return g_k5_static; }
 static int g_k5_gqa_pair = 0;   // grouped-query calls: 1 = two query heads of one K/V head and one list share a workgroup's K/V ring where they can (rsa_gqa_form)
+static int g_k5_walk_order = 1; // 64-row kernel, plain sparse calls: runs of one head's walks per XCD generation, in the order of the walk_order kernels (0 = the eighth map, no order kernels)
+static int g_k5_order_overlap = 50; // ... a head whose adjacent kept lists share this percentage of their entries or more keeps its units in index order
 static int g_k5_gsync = 1;      // aligned starts of the sparse walks (rsa_attn.h): bit 0 = in the 64-row kernel, bit 1 = in the 32-row (64-token blocks) and e4m3 kernels
 
 // Tuning / diagnostics hook (not part of the data path).  The switches are process-global, so the hook only works in a
@@ -44,6 +46,8 @@ extern "C" int rsa_set_tuning(const char* key, int value) {
     if (strcmp(key, "k5_gsync_ratio") == 0) { g_k5_gsync_ratio = value; return RSA_OK; }
     if (strcmp(key, "k5_text_last") == 0) { g_k5_text_last = value; return RSA_OK; }
     if (strcmp(key, "k5_tail_split") == 0) { g_k5_tail_split = value; return RSA_OK; }
+    if (strcmp(key, "k5_walk_order") == 0) { g_k5_walk_order = value; return RSA_OK; }
+    if (strcmp(key, "k5_order_overlap") == 0) { g_k5_order_overlap = value; return RSA_OK; }
     if (strcmp(key, "k5_gqa_pair") == 0) { g_k5_gqa_pair = value; return RSA_OK; }
     if (strcmp(key, "fp8_variant") == 0) { rsa_set_fp8_variant(value); return RSA_OK; }
     if (strcmp(key, "fp8_smooth_k") == 0) { rsa_set_fp8_smooth_k(value); return RSA_OK; }
@@ -135,7 +139,7 @@ __global__ __launch_bounds__(256) void tail_combine_kernel(const float* __restri
     if (row >= (long)tail_n * RSA_BLOCK) return;
     const int t = (int)(row / RSA_BLOCK), r = (int)(row % RSA_BLOCK);
     const int v = tail_first + t, bh = v / NBp;
-    const int qblk = rsa_walk_unit(v % NBp, NBp);
+    const int qblk = rsa_walk_unit(v % NBp, NBp);     // (a tail piece's unit is the eighth map's, with and without an order table: rsa_walk_order.h)
     const int grow = qblk * RSA_BLOCK + r;
     if (qblk >= NBv || grow >= Sq) return;
     const float* base = part + rsa_part_row((long)t * tail_p, r, D);
@@ -241,6 +245,7 @@ int rsa_plan_walk(WalkArgs& a, int BH, int D, const WalkPolicy& pol, size_t tpar
     if (a.tpart && tpart_bytes == 0) return RSA_ERR_WORKSPACE;   // capacity not declared (rsa_buffers.tpart_bytes, 0.5.0)
     const size_t piece_bytes = (size_t)rsa_part_row(1, 0, D) * sizeof(float);
     a.BH = BH;
+    a.order = nullptr;                       // (launch_attn: the order table of the 64-row kernel's plain sparse calls)
     a.NBp = ((blk == 64 ? (a.NBv + 1) >> 1 : a.NBv) + 7) & ~7;   // (blk 64: pairs of query blocks)
     // split-KV for the dense text rows: without it one workgroup walks every key block of a text query block (902 at the
     // HunyuanVideo shape = 10 kept lists) -- hidden among 21 600 sparse blocks on one GPU, the critical path when the
@@ -293,6 +298,149 @@ int rsa_plan_walk(WalkArgs& a, int BH, int D, const WalkPolicy& pol, size_t tpar
     return RSA_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Walk order of the sparse units (rsa_walk_order.h): order[bh][rank] = unit, u16 [BH, NBp], built by two small kernels.
+// Key of a unit = the mean of its kept block indices in 1/64 block (19 bits; an empty list sorts last), ties to the lower unit
+// index.  Walks with nearby means stay nearby for their whole lives (a walk's position at step j is an order statistic of its
+// list), so the runs of `gen` consecutive ranks that an XCD holds together meet in its L2 far more often than `gen` walks taken in
+// index order do (profiles/k5_walk_order.md).  Where adjacent query blocks keep nearly the same lists, index order IS the better
+// order (neighbours share their keys, sorting by mean pulls them apart): a head whose mean adjacent overlap,
+// |list_i & list_i+1| / |list_i| over its units with a non-empty list, is thr_pct per cent or more keeps index order.
+//
+// Pass 1, walk_order_unit_kernel: one WAVE per unit over the whole device.  Unit i's key and its overlap with unit i + 1 (list
+// i + 1 as a bitmap in the wave's own 1 KiB of LDS, list i tested against it) -> ukey / uovl [BH, NBp].
+// Pass 2, walk_order_sort_kernel: one workgroup per head.  Sums the overlaps in a fixed order, then sorts (key << 13 | unit) -- or
+// the unit indices alone, for a head that keeps index order -- in LDS, NBv <= 8192.  The units of a split tail (the eighth map's units
+// behind work index n_whole, which stay what they are) are left out of the sort and written at their own ranks.
+constexpr int ORD_NT = 1024, ORD_BM_WORDS = 8192 / 32, ORD_UNIT_NT = 256;
+constexpr unsigned ORD_KEY_EMPTY = 0x7FFFEu;     // (below the all-ones word that marks a pad or a tail unit in the sort)
+__device__ __forceinline__ int ord_wave_sum(int x) {      // sum over the 64 lanes, in a scalar
+    x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);     // quad_perm [1,0,3,2]
+    x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);     // quad_perm [2,3,0,1]
+    x += __builtin_amdgcn_update_dpp(0, x, 0x124, 0xF, 0xF, false);    // row_ror:4
+    x += __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false);    // row_ror:8
+    return __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) +
+           __builtin_amdgcn_readlane(x, 48);
+}
+// a wave's bitmap is its own: its LDS traffic only has to be complete and in order inside the wave (no workgroup barrier)
+__device__ __forceinline__ void ord_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+__global__ __launch_bounds__(ORD_UNIT_NT) void walk_order_unit_kernel(const int32_t* __restrict__ cols, const int32_t* __restrict__ counts,
+                                                                      unsigned* __restrict__ ukey, float* __restrict__ uovl, int BH,
+                                                                      int NBv, int NBp, int NB_total) {
+    __shared__ unsigned ord_bm[ORD_UNIT_NT / 64][ORD_BM_WORDS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long w = (long)blockIdx.x * (ORD_UNIT_NT / 64) + wv;      // wave = (bh, unit)
+    if (w >= (long)BH * NBv) return;
+    const int bh = (int)(w / NBv), i = (int)(w % NBv);
+    unsigned* bm = ord_bm[wv];
+    const long row = (long)bh * NBv + i;
+    const bool has_next = i + 1 < NBv;
+    const int32_t* la = cols + row * NB_total;
+    const int32_t* lb = la + (has_next ? NB_total : 0);
+    // (the first 128 entries of both lists are in flight together with the counts: entries past a count are read -- a row has NB_total
+    // slots -- and not used)
+    const int a0 = lane < NB_total ? la[lane] : -1, a1 = lane + 64 < NB_total ? la[lane + 64] : -1;
+    const int b0 = lane < NB_total ? lb[lane] : -1, b1 = lane + 64 < NB_total ? lb[lane + 64] : -1;
+    int na = counts[row], nb = has_next ? counts[row + 1] : 0;
+    na = na < 0 ? 0 : (na < NB_total ? na : NB_total);
+    nb = nb < 0 ? 0 : (nb < NB_total ? nb : NB_total);
+    for (int x = lane; x < ORD_BM_WORDS; x += 64) bm[x] = 0u;
+    ord_wave_sync();
+    for (int x = lane; x < nb; x += 64) {
+        const int e = x < 64 ? b0 : (x < 128 ? b1 : lb[x]);
+        if ((unsigned)e < (unsigned)NB_total) atomicOr(&bm[e >> 5], 1u << (e & 31));
+    }
+    ord_wave_sync();
+    int sum = 0, hit = 0;
+    for (int x = lane; x < na; x += 64) {
+        const int e = x < 64 ? a0 : (x < 128 ? a1 : la[x]);
+        if ((unsigned)e < (unsigned)NB_total) {
+            sum += e;
+            hit += (int)((bm[e >> 5] >> (e & 31)) & 1u);
+        }
+    }
+    sum = ord_wave_sum(sum);
+    hit = ord_wave_sum(hit);
+    if (lane == 0) {
+        const unsigned key = na > 0 ? ((unsigned)sum << 6) / (unsigned)na : ORD_KEY_EMPTY;     // (sum < 2^25: at most 8192 distinct blocks < 8192)
+        ukey[(long)bh * NBp + i] = (key << 13) | (unsigned)i;
+        uovl[(long)bh * NBp + i] = (has_next && na > 0) ? (float)hit / (float)na : -1.0f;      // -1: no pair
+    }
+}
+__global__ __launch_bounds__(ORD_NT) void walk_order_sort_kernel(const unsigned* __restrict__ ukey, const float* __restrict__ uovl,
+                                                                 unsigned short* __restrict__ order, int NBv, int NBp, int P2,
+                                                                 int n_whole, int thr_pct) {
+    extern __shared__ unsigned ord_keys[];                // [P2]: P2 = the power of two >= NBv
+    __shared__ float ord_ov[ORD_NT / 64];
+    __shared__ int ord_np[ORD_NT / 64];
+    __shared__ int ord_identity;
+    const int bh = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    // ranks [0, r0) are whole walks; the ranks from r0 on are the head's share of a split tail
+    const long left = (long)n_whole - (long)bh * NBp;
+    const int r0 = left < 0 ? 0 : (left < NBp ? (int)left : NBp);
+    const unsigned key_t = t < NBv ? ukey[(long)bh * NBp + t] : 0u;      // (in flight with the overlaps: not behind the decision they lead to)
+    float ov = 0.0f;
+    int np = 0;
+    for (int i = t; i < NBv; i += ORD_NT) {
+        const float o = uovl[(long)bh * NBp + i];
+        if (o >= 0.0f) { ov += o; ++np; }
+    }
+    for (int m = 1; m < 64; m <<= 1) { ov += __shfl_xor(ov, m, 64); np += __shfl_xor(np, m, 64); }
+    if (lane == 0) { ord_ov[wv] = ov; ord_np[wv] = np; }
+    __syncthreads();
+    if (t == 0) {
+        float so = 0.0f;
+        int sp = 0;
+        for (int w = 0; w < ORD_NT / 64; ++w) { so += ord_ov[w]; sp += ord_np[w]; }
+        ord_identity = so * 100.0f >= (float)thr_pct * (float)sp;
+    }
+    __syncthreads();
+    const bool identity = ord_identity != 0;
+    for (int i = t; i < P2; i += ORD_NT) {
+        unsigned key = 0xFFFFFFFFu;                        // pads, and the units of the tail: behind every whole walk
+        if (i < NBv && rsa_walk_unit_inv(i, NBp) < r0) key = identity ? (unsigned)i : (i == t ? key_t : ukey[(long)bh * NBp + i]);
+        ord_keys[i] = key;
+    }
+    __syncthreads();
+    // bitonic sort, ascending.  A step with j < 64 pairs keys of one wave: those steps run on registers (key i sits in lane i & 63
+    // of the wave that owns index i), only the steps with j >= 64 go through LDS and a workgroup barrier.
+    for (int k = 2; k <= P2; k <<= 1) {
+        for (int j = k >> 1; j >= 64; j >>= 1) {
+            for (int i = t; i < P2; i += ORD_NT) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const unsigned ka = ord_keys[i], kb = ord_keys[x];
+                    if ((ka > kb) == ((i & k) == 0)) { ord_keys[i] = kb; ord_keys[x] = ka; }
+                }
+            }
+            __syncthreads();
+        }
+        for (int i0 = 0; i0 < P2; i0 += ORD_NT) {          // (uniform trip count: every lane of a wave takes part in the shuffles)
+            const int i = i0 + t;
+            unsigned key = i < P2 ? ord_keys[i] : 0xFFFFFFFFu;
+            for (int j = k >> 1 < 32 ? k >> 1 : 32; j > 0; j >>= 1) {
+                const unsigned other = (unsigned)__shfl_xor((int)key, j, 64);
+                const bool low = (i & j) == 0, up = (i & k) == 0;       // this lane keeps the smaller key iff low == up
+                const unsigned mn = key < other ? key : other, mx = key < other ? other : key;
+                key = (low == up) ? mn : mx;
+            }
+            if (i < P2) ord_keys[i] = key;
+        }
+        __syncthreads();
+    }
+    unsigned short* o = order + (long)bh * NBp;
+    for (int r = t; r < NBp; r += ORD_NT) {
+        int u;
+        if (r < r0) u = (r < P2 && ord_keys[r] != 0xFFFFFFFFu) ? (int)(ord_keys[r] & 0x1FFFu) : RSA_ORDER_PAD;
+        else u = rsa_walk_unit(r, NBp);                    // (the tail piece's unit; never read through the table)
+        o[r] = (unsigned short)(u < NBv ? u : RSA_ORDER_PAD);
+    }
+}
+
 static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes, hipStream_t s) {
     // 128-token blocks and dense calls run the 64-row kernel; 64-token blocks the 32-row kernel, whose 64-key tiles are one block
     const bool w64 = a.blk == RSA_BLOCK;
@@ -305,6 +453,33 @@ static int launch_attn(AttnArgs& a, int BH, int D, int dtype, size_t tpart_bytes
     pol.tail_beside_text = true;
     int st = rsa_plan_walk(a, BH, D, pol, tpart_bytes, &nblocks);
     if (st != RSA_OK || nblocks == 0) return st;
+    // The order table of the sparse units (rsa_walk_order.h), for the plain sparse calls of the 64-row kernel whose sparse units start
+    // at work index 0: built on this stream in front of the kernel, in what the caller's tpart has left behind the text pieces' and the
+    // tail pieces' regions (the caller's own buffer, ordered by the caller's stream: never a slot another launch could recycle):
+    // the table, then the per-unit keys and overlaps of its first pass.  No tpart or no room: the eighth map.
+    if (g_k5_walk_order && w64 && a.mode == MODE_SPARSE && a.gqa == RSA_GQA_NONE && !a.row_hi && a.tpart && a.NBv > 0 &&
+        a.NBv <= 8192 && (a.heavy_last || a.n_heavy_pad == 0)) {
+        const int ntq = a.NQB - a.NBv;
+        const size_t piece_bytes = (size_t)rsa_part_row(1, 0, D) * sizeof(float);
+        const size_t used = ((size_t)BH * (size_t)(ntq > 0 ? ntq : 0) * RSA_TEXT_SPLIT + (size_t)a.tail_n * (size_t)a.tail_p) * piece_bytes;
+        const size_t n_ent = (size_t)BH * (size_t)a.NBp;         // (NBp is a multiple of 8: the three arrays stay 4-byte aligned)
+        const size_t need = n_ent * (sizeof(unsigned short) + sizeof(unsigned) + sizeof(float));
+        if (used <= tpart_bytes && need <= tpart_bytes - used) {
+            char* base = reinterpret_cast<char*>(a.tpart) + used;
+            unsigned short* order = reinterpret_cast<unsigned short*>(base);
+            unsigned* ukey = reinterpret_cast<unsigned*>(base + n_ent * sizeof(unsigned short));
+            float* uovl = reinterpret_cast<float*>(ukey + n_ent);
+            int P2 = 1;
+            while (P2 < a.NBv) P2 <<= 1;
+            const long waves = (long)BH * a.NBv, per_wg = ORD_UNIT_NT / 64;
+            walk_order_unit_kernel<<<dim3((unsigned)((waves + per_wg - 1) / per_wg)), ORD_UNIT_NT, 0, s>>>(a.cols, a.counts, ukey, uovl, BH, a.NBv,
+                                                                                                        a.NBp, a.NB_total);
+            walk_order_sort_kernel<<<dim3((unsigned)BH), ORD_NT, (size_t)P2 * sizeof(unsigned), s>>>(
+                ukey, uovl, order, a.NBv, a.NBp, P2, a.tail_n > 0 ? a.tail_first : (int)n_ent, g_k5_order_overlap);
+            if ((st = rsa_launch_status()) != RSA_OK) return st;
+            a.order = order;
+        }
+    }
     const size_t lds_bytes = (size_t)4 * 64 * D * 2 + (((size_t)a.NB_total * 2 + 15) & ~(size_t)15);
     st = w64 ? rsa_launch_bsfwd64(a, dim3((unsigned)nblocks), lds_bytes, D, dtype, s)
              : rsa_launch_bsfwd(a, dim3((unsigned)nblocks), lds_bytes, D, dtype, s);

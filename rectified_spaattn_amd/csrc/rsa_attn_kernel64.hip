@@ -119,6 +119,7 @@ __device__ __forceinline__ f32x16 k5w_oread() {
 template <typename Tag, bool WIDE, int NW = 2, int D = 128, bool RANGED = false, int GQA = RSA_GQA_NONE>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) void bsfwd64_kernel(AttnArgs) {
     constexpr bool PAIR = GQA == RSA_GQA_PAIR;
+    constexpr bool ORDERED = NW == 2 && !RANGED && GQA == RSA_GQA_NONE;   // the instantiations that may be given an order table (rsa_walk_order.h)
     static_assert(!RANGED || NW == 2 || PAIR, "per-row ranges: sparse calls only (128-row query blocks)");
     static_assert(PAIR ? NW == 4 : (GQA == RSA_GQA_NONE || NW == 2), "a head pair is four waves, a head of its own two");
     const AttnArgs& a = rsa_kernargs<AttnArgs>();
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
 
     // ---------------- work mapping (rsa_attn.h); a text block is a qblk >= NBv ----------------
     int bh, qblk, tsp, tail;
-    if (rsa_walk_map(a, blockIdx.x, a.NBv, bh, qblk, tsp, tail) == WALK_NONE) return;
+    if (rsa_walk_map<ORDERED>(a, blockIdx.x, a.NBv, bh, qblk, tsp, tail) == WALK_NONE) return;
     int b = bh / a.H, h = bh % a.H;         // batch item and query head (a head pair: below)
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -529,7 +530,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     {
         int work2 = blockIdx.x;
         asm volatile("" : "+s"(work2));
-        rsa_walk_map(e, work2, e.NBv, bh2, qblk2, tsp2, tail2);
+        rsa_walk_map<ORDERED>(e, work2, e.NBv, bh2, qblk2, tsp2, tail2);
     }
     int b2, h2;
     if constexpr (PAIR) {
@@ -663,6 +664,7 @@ static int launch_bsfwd64(const AttnArgs& a, bool wide, int dtype, dim3 grid, si
 // launch hook used by rsa_attn.hip::launch_attn (head dims 128 and 64)
 int rsa_launch_bsfwd64(const AttnArgs& a, dim3 grid, size_t lds_bytes, int D, int dtype, hipStream_t s) {
     if (D != 128 && D != 64) return RSA_ERR_UNSUPPORTED;
+    if (a.order && (a.gqa != RSA_GQA_NONE || a.rows256 || a.row_hi)) return RSA_ERR_BAD_ARG;   // only the plain sparse instantiations read the table
     const bool wide = !(((uintptr_t)a.out & 15) || ((a.osb | a.osh | a.oss) & 7));
     lds_bytes += 16;   // the loop reads its list two entries ahead
     if (a.gqa != RSA_GQA_NONE) return rsa_launch_bsfwd64_gqa(a, wide, grid, lds_bytes, D, dtype, s);

@@ -71,6 +71,36 @@ def main():
             del call
             torch.cuda.empty_cache()
         return
+    if "walkorder" in what:  # same-binary A/B of the walk order (tuning key k5_walk_order), alternating in one process
+        from rectified_spaattn_amd import _lib
+        L = _lib.lib()
+        H = int(os.environ.get("RSA_PERF_H", "24"))
+        rounds = int(os.environ.get("RSA_PERF_ROUNDS", "6"))
+        thr = os.environ.get("RSA_PERF_OVERLAP")
+        if thr is not None:
+            assert L.rsa_set_tuning(b"k5_order_overlap", int(thr)) == 0
+        for regime in os.environ.get("RSA_PERF_REGIMES", "r2").split(","):
+            call, spec = regime_call(regime, H, dev)
+            call.select()
+            torch.cuda.synchronize()
+            ts = {0: [], 1: []}
+            ref = None
+            for rnd in range(rounds):
+                for order in ((0, 1) if rnd % 2 == 0 else (1, 0)):
+                    assert L.rsa_set_tuning(b"k5_walk_order", order) == 0
+                    med, mn = timeit(call.attend, n=5, warm=1)
+                    same = True if ref is None else torch.equal(call.out, ref)
+                    if ref is None:
+                        ref = call.out.clone()
+                    ts[order].append(med)
+                    print(f"regime {regime} round {rnd} k5_walk_order {order}: K5 median {med:.3f} ms (min {mn:.3f}) same bytes {same}", flush=True)
+            L.rsa_set_tuning(b"k5_walk_order", 1)
+            for order in (0, 1):
+                t = sorted(ts[order])
+                print(f"regime {regime} k5_walk_order {order}: median {t[len(t) // 2]:.3f} ms, min {t[0]:.3f}, max {t[-1]:.3f}, spread {t[-1] - t[0]:.3f}")
+            del call
+            torch.cuda.empty_cache()
+        return
     if "sparse" in what:
         H = int(os.environ.get("RSA_PERF_H", "24"))
         wl = WORKLOADS["hunyuan_720p_128f"]

@@ -13,7 +13,16 @@ Scheduling policies compared:
 Prints hit rate, time per step relative to an unconstrained walk (1.0 = no stall) and the stall share.  The result the round-5
 write-up quotes (profiles/r05_k5_walk_sim.md): every window that raises the hit rate noticeably costs more in stalls than the
 aligned-start change gained per hit-rate point, because the work per key range is uneven across independent walks (a window of
-w positions holds w K / NB +- sqrt(..) blocks of a walk)."""
+w positions holds w K / NB +- sqrt(..) blocks of a walk).
+
+`python tools/sim_walks.py product` models the PRODUCT's work mapping instead (profiles/k5_walk_order.md): the policies above put 64
+walks of ONE head in every generation, the product's rsa_walk_map gave XCD x the x-th contiguous eighth of every head's units --
+113 per head and XCD at the HunyuanVideo shape, cut into generations of 64, so about every second generation holds walks of two
+heads, which share nothing.  Three mappings of the (XCD, generation) slots, aligned starts, LRU of C blocks, 8 heads:
+  eighth    the contiguous eighth per head and XCD (the map without an order table)
+  runs      runs of 64 consecutive units of one head dealt to the XCDs, units in index order
+  sorted    the same runs, the head's units sorted by mean kept key block (rsa_walk_order.h + the walk_order kernels)
+each on independent lists (R2) and on lists that share 60 % / 90 % of their entries with the previous query block's."""
 import heapq
 import sys
 from collections import OrderedDict
@@ -81,7 +90,77 @@ def run(rng, C, W, jitter=0.03, gens=6, aligned=True, sort_first=False, nb=NB, k
     return hits / acc, tot_time / (gens * k), stall / (gens * k * NW)
 
 
+def make_lists(rng, n, nb, k, share):
+    """n ascending lists of k of nb blocks; share > 0: list i + 1 keeps that fraction of list i's entries and redraws the rest"""
+    out = [np.sort(rng.choice(nb, k, replace=False))]
+    for _ in range(n - 1):
+        if share <= 0:
+            out.append(np.sort(rng.choice(nb, k, replace=False)))
+            continue
+        keep = rng.choice(out[-1], int(round(share * k)), replace=False)
+        rest = np.setdiff1d(np.arange(nb), keep)
+        out.append(np.sort(np.concatenate([keep, rng.choice(rest, k - len(keep), replace=False)])))
+    return out
+
+
+def run_product(rng, C, mapping, nb=NB, k=K, heads=8, share=0.0, gen=NW, jitter=0.03, xcd=0):
+    """Hit rate of ONE XCD's L2 (LRU of C key blocks, keyed by (head, block)) over a launch of `heads` heads of nb query blocks."""
+    nbp = (nb + 7) & ~7
+    lists = [make_lists(rng, nb, nb, k, share) for _ in range(heads)]
+    order = [sorted(range(nb), key=lambda u, h=h: (lists[h][u].mean(), u)) if mapping == "sorted" else list(range(nb)) for h in range(heads)]
+    walks = []                                   # the walks this XCD receives, in the order it receives them
+    if mapping == "eighth":
+        for h in range(heads):
+            walks += [(h, u) for u in range(xcd * (nbp >> 3), (xcd + 1) * (nbp >> 3)) if u < nb]
+    else:
+        n_sparse = heads * nbp
+        for run0 in range(xcd * gen, n_sparse, 8 * gen):          # run r = p // gen goes to XCD r % 8
+            for p in range(run0, min(run0 + gen, n_sparse)):
+                h, r = divmod(p, nbp)
+                if r < nb:
+                    walks.append((h, order[h][r]))
+    hits = acc = 0
+    cache = OrderedDict()
+    t0 = 0.0
+    for g0 in range(0, len(walks), gen):
+        grp = walks[g0:g0 + gen]
+        ev = [(t0, i, 0) for i in range(len(grp))]
+        heapq.heapify(ev)
+        while ev:
+            t, i, j = heapq.heappop(ev)
+            t0 = max(t0, t)
+            if j >= k:
+                continue
+            h, u = grp[i]
+            key = (h, int(lists[h][u][j]))
+            acc += 1
+            if key in cache:
+                hits += 1
+                cache.move_to_end(key)
+            else:
+                cache[key] = 1
+                if len(cache) > C:
+                    cache.popitem(last=False)
+            heapq.heappush(ev, (t + max(1.0 + rng.normal(0, jitter), 0.5), i, j + 1))
+    return hits / acc
+
+
+def main_product():
+    print("product mapping, R2 shape (90 of 900 key blocks kept, 8 heads, generations of 64 per XCD); hit rate of one XCD's L2")
+    for share, name in ((0.0, "independent lists (R2)"), (0.6, "adjacent lists share 60 %"), (0.9, "adjacent lists share 90 %")):
+        print(f"== {name}")
+        for mapping in ("eighth", "runs", "sorted"):
+            row = []
+            for C in (64, 48):
+                rng = np.random.default_rng(1)
+                row.append(np.mean([run_product(rng, C, mapping, share=share) for _ in range(3)]))
+            print(f"  {mapping:7s}: hits C = 64 {row[0]:.3f} | C = 48 {row[1]:.3f}")
+        sys.stdout.flush()
+
+
 def main():
+    if "product" in sys.argv[1:]:
+        return main_product()
     rng = np.random.default_rng(0)
     dens = [(900, 90, "R2: 10 % of 900 key blocks"), (900, 180, "script: 20 %"), (591, 147, "Wan2.1 script: 25 % of 591")]
     for nb, k, name in dens:
