@@ -1,13 +1,15 @@
-"""The softmax weights of the 2-byte attention kernels, pinned exactly on the MI355X (tests/weights.py has the construction, the
+"""The softmax weights of the 2-byte, e4m3 and pv attention kernels, pinned exactly on the MI355X (tests/weights.py has the construction, the
 weighted-count reference and the case tables; tests/test_weights_cpu.py shows that a weight on the wrong key of a sub-step, a row
 with another row's scores, a rescale that skips O, l, a d-tile or a 32-row half, pieces merged without their weights or a query
 head on the wrong K/V head would break the bound these tests hold the kernels to).  Every score is a small integer in binary
 units, so every softmax weight, rescale factor and merge weight is a power of two and the sums are exact in fp32: the output must
 equal sum 2^n v / sum 2^n over the visible keys within ONE output ulp -- visibility's bound, ULP and FLOOR imported from there --
-and be exactly 0 where that is.  bf16 cases run with the static softmax reference on and off (tuning key k5_static).
+and be exactly 0 where that is.  bf16 cases run with the static softmax reference on and off (tuning key k5_static).  The e4m3 and
+pv forms (qkv_fp8=) run the rectified and the dense cases under the same bound: there every P is the e4m3 code of 1.5 times a power
+of two, K minus its sampled mean and V times its block gain are exact in their images, and the "smooth K" of the product stays on.
 
-Out of scope: the e4m3 and pv forms, rsa_attn_masked.hip (its scale is applied in fp32, so integer scores cannot be reached)
-and the selection pass."""
+Out of scope: Q's block exponent (one value by construction), rsa_attn_masked.hip (its scale is applied in fp32, so integer scores
+cannot be reached) and the selection pass."""
 import contextlib
 
 import numpy as np
@@ -33,9 +35,9 @@ def _tuning(key: bytes, value: int, default: int = 1):
         L.rsa_set_tuning(key, default)
 
 
-def _statics(dt):
-    """The settings of k5_static a case runs under: the static reference is a bf16 form."""
-    return (1, 0) if dt == "bf16" else (1,)
+def _statics(dt, fp8=False):
+    """The settings of k5_static a case runs under: the static reference is a form of the 2-byte bf16 kernels."""
+    return (1, 0) if dt == "bf16" and not fp8 else (1,)
 
 
 def _inputs(m: w.Model):
@@ -90,28 +92,29 @@ def test_plain_block_sparse_attention_weighs_every_key_exactly(cid):
 
 
 # ---- 2. dense attention --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("cid", [c["id"] for c in w.DENSE_CASES])
+@pytest.mark.parametrize("cid", [c["id"] for c in w.DENSE_CASES + w.DENSE_FP8_CASES])
 def test_dense_attention_weighs_every_key_exactly(cid):
+    """The 2-byte cases with the static reference and the 256-row form on and off; the e4m3 and pv cases (qkv_fp8=) as they are."""
     from rectified_spaattn_amd import _core
     c = w.CASES[cid]
     m = w.model(c)
     want = w.reference(m)
     print(f"{cid}: {w.exercised(m)}")
     q, k, v = _inputs(m)
-    for static in _statics(m.dt):
-        for rows256 in ((1, 0) if m.Sq > 256 else (1,)):
+    for static in _statics(m.dt, m.fp8):
+        for rows256 in ((1, 0) if m.Sq > 256 and not m.fp8 else (1,)):
             with _tuning(b"k5_static", static), _tuning(b"k5_rows256", rows256):
-                out = _core.dense_attention(q, k, v, q_split=c["q_split"], kv_split=c["kv_split"], causal=c["causal"])
+                out = _core.dense_attention(q, k, v, q_split=c["q_split"], kv_split=c["kv_split"], causal=c["causal"], qkv_fp8=m.fp8)
                 torch.cuda.synchronize()
             _check(out.permute(0, 2, 1, 3), want, m.dt, f"{cid} k5_static={static} k5_rows256={rows256}")
 
 
 # ---- 3. the rectified call over a caller's mask -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("cid", [c["id"] for c in w.RECT_CASES])
+@pytest.mark.parametrize("cid", [c["id"] for c in w.RECT_CASES + w.RECT_FP8_CASES])
 def test_rectified_attention_over_a_mask_weighs_every_key_exactly(cid):
     """Visual rows: R * weighted census + comp with the call's own R and comp, as tests/test_gpu_visibility.py does; text rows
     through the text split where the layout has one, visual walks through the tail split (on and off) in the 104-block layout.
-    The sensitivity condition is checked again with the call's parts."""
+    The sensitivity condition is checked again with the call's parts.  The e4m3 and pv cases go in as qkv_fp8=."""
     from rectified_spaattn_amd import _core
     c = w.CASES[cid]
     spec = vis.rect_spec(c)
@@ -122,10 +125,11 @@ def test_rectified_attention_over_a_mask_weighs_every_key_exactly(cid):
     mask = torch.from_numpy(m0.mask).to(DEV)
     m = None
     big = c["layout"] in ("hunyuan_tsplit", "hunyuan_tail")
-    for static in _statics(m0.dt):
+    for static in _statics(m0.dt, m0.fp8):
         for split in c.get("tail_split", (1,)):
             with _tuning(b"k5_static", static), _tuning(b"k5_tail_split", split):
-                out, parts = _core.rectified_attention(q, k, v, spec, 0, 0.0, None, return_parts=True, block_mask=mask)
+                out, parts = _core.rectified_attention(q, k, v, spec, 0, 0.0, None, return_parts=True, block_mask=mask,
+                                                       qkv_fp8=m0.fp8)
                 torch.cuda.synchronize()
             if m is None:       # (R and comp come from the selection statistics, which neither tuning key touches)
                 dev_parts = (parts["R"].cpu().numpy().reshape(B * H, sp.NBv),

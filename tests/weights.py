@@ -1,4 +1,4 @@
-"""Exact softmax-weight tests of the 2-byte attention kernels: inputs whose softmax WEIGHTS are known exactly.
+"""Exact softmax-weight tests of the 2-byte, e4m3 and pv attention kernels: inputs whose softmax WEIGHTS are known exactly.
 
 The counterpart of tests/visibility.py.  There every score is 0, which pins which keys a row sums and nothing about the weight
 each key gets.  Here every score is a small non-negative integer in the kernels' own binary units, so every exp2(S - m), every
@@ -27,8 +27,27 @@ The reference is a weighted count, sum 2^n v / sum 2^n over the keys visibility'
 dense_ref, rect_ref and tests/test_ranged_cpu.py's rule are used as they are; only the weights are new).  The model mutants of
 insensitive() live here too, all in numpy: no kernel is built in a mutated form.
 
-Out of scope: the e4m3 and pv forms, rsa_attn_masked.hip (its scale is applied in fp32, so integer scores cannot be reached)
-and the selection pass."""
+The fp8 forms (a case's "fp8": True = e4m3 Q, K, V and P; "pv" = 2-byte Q . K^T, e4m3 P and V; rsa_attn_fp8_kernel.hip).  Integer
+scores stay exact there under conditions that tests/test_weights_cpu.py checks for every case:
+    P   the code map (PMap<true>, pmap()): a score at integer distance d from the row's reference arrives as the code 108 + 8 d,
+        mantissa field 4, the value 1.5 * 2^(d + 6); the 96 cancels between P . V and the row sum.  d <= THRESH by the move rule;
+        below, the last normal code is 12: every visible key of a row must lie within max_spread() = 12 of the row's maximum.  Both
+        forms use the fp16 amplitudes (spread <= 10, <= 11 after balance_mu()), and the budget is 3 * 2^max(V_GAINS) * sum < 2^24.
+    pv  the kernel multiplies Q by (float)(sm_scale * 1.44269504 * 8) and rounds it to the 2-byte type: a is the value that rounds
+        to 1 (Model.q_target), K = 8 n as before.
+    Q   e4m3: the image of a * qk_const is 2^-3 in every block (the MFMA's scale operand adds the 8).  Q's exponent is therefore
+        the same in every block: NOT witnessed.
+    K   e4m3: the kernel subtracts mu, the mean of up to 8 sampled full blocks of K ("smooth K", on in every case: the product's
+        path).  K - mu = 8 (n - mu / 8) is exact in e4m3 only for an integral mu / 8: balance_mu() puts +-1 on base-only keys of
+        the sampled rows until it is.  The key blocks QUIET_BLOCKS hold no n above QUIET, which makes their K exponent differ.
+    V   0 / 2^g per 128-key block, g hashed from V_GAINS: exact, and V's block exponents differ between blocks.
+fp8_image_faults() checks all of it on the images the oracle's byte-exact contract makes (fp8_kmean, fp8_block_images), among it
+that two distinct K and two distinct V exponents occur among the blocks some row sees.  What is left is what is left above, and
+the bound is the same.  A second assumption is not derived: that v_cvt_pk_u8_f32 of an exact integer is that integer (the fp8
+cases meeting the bound on the device shows it).
+
+Out of scope: Q's block exponent, rsa_attn_masked.hip (its scale is applied in fp32, so integer scores cannot be reached) and the
+selection pass."""
 from __future__ import annotations
 
 import dataclasses
@@ -62,6 +81,29 @@ FOCUS_EVERY = 4
 AMP = {"bf16": dict(base=4, step=(9, 10, 12), edge=8, stairs=(3, 4), spike=12, focus=12, fall=9),
        "fp16": dict(base=2, step=(9, 9, 9), edge=8, stairs=(3, 3), spike=9, focus=9, fall=9)}
 STEP_KINDS = ("step", "stairs")
+# the e4m3 and pv forms (module docstring, "The fp8 forms"): the fp16 amplitudes whatever the storage type
+FP8_AMP = "fp16"
+QUIET, QUIET_BLOCKS = 8, (1, 4, 7)     # e4m3 form: these key blocks hold no n above QUIET: |n - mu / 8| <= 7 there, 8 and more in a
+                            # block with a full-height profile, and the K exponents of the two differ
+V_GAINS = (0, 1)            # fp8 forms: V of key block b of K/V head kvh is 0 / 2^g, g hashed from this set
+
+
+def form_of(c: dict):
+    """False, True (e4m3) or "pv": the case's operand form."""
+    return c.get("fp8", False)
+
+
+def pmap():
+    """(U, BIAS, OFFSET, THRESH) of the kernels' code-map P (rsa_attn_fp8_kernel.hip PMap<true>, as oracle.py restates it)."""
+    from oracle import oracle as orc
+    return orc.PCODE_U, orc.PCODE_BIAS, orc.PCODE_OFFSET, orc.PCODE_THRESH
+
+
+def max_spread() -> int:
+    """The largest S - m for which the code of P is still mantissa field 4 of a NORMAL e4m3 value: a score at distance d below the
+    reference arrives as U (OFFSET - d) + BIAS = 108 - 8 d, and the smallest normal code is 8."""
+    U, BIAS, OFFSET, _ = pmap()
+    return int((U * OFFSET + BIAS - 8) // U)
 
 
 # ---- the value of Q ------------------------------------------------------------------------------------------------------
@@ -115,17 +157,19 @@ def cls(r, h, Dq):
 
 # ---- K: the integer scores -----------------------------------------------------------------------------------------------
 def scores_n(dt: str, Hkv: int, Sk: int, Dq: int, key_block: int, outside=(), outside_keys=(), head_of_kv=1,
-             forced=None) -> np.ndarray:
+             forced=None, fp8=False, kvalid: Optional[int] = None) -> np.ndarray:
     """int8 [Hkv, Sk, Dq]: n[kvh, j, c] = base + profile_c(j) (module docstring).  outside: pairs (o, side) such that key r + o
     lies just outside a limit of row r, to the right (side = 1) or to the left (-1): the spike classes put +spike on the keys j
     with cls(j - o, h) == c, h = kvh * head_of_kv (the first query head of the K/V head).  outside_keys: keys just outside a limit
     of every row (kv_len, a chunk's end).  forced: {kvh: {c: (residue, period)}}, the classes forced_classes() turns into focus
-    classes with ONE heavy key (the first) in the sub-steps s with s % period == residue."""
-    amp = AMP[dt]
+    classes with ONE heavy key (the first) in the sub-steps s with s % period == residue.  fp8: the operand form (the fp16
+    amplitudes; e4m3 form: quiet key blocks and the balance of balance_mu() over the kvalid rows the K mean is sampled from)."""
+    amp = AMP[FP8_AMP if fp8 else dt]
     kvh = np.arange(Hkv)[:, None, None]
     j = np.arange(Sk)[None, :, None]
     c = np.arange(Dq)[None, None, :]
     n = (_mix(kvh, j, c, 1) % np.uint64(amp["base"])).astype(np.int64)
+    n_base = n
     kind = np.broadcast_to(np.where(c % 8 == 7, 6, c % 8), (Hkv, 1, Dq)).copy()     # the index into KINDS (both focus classes: 6)
     res = np.broadcast_to((2 * (c // 8) + (c % 8 - 6)) % FOCUS_EVERY, (Hkv, 1, Dq)).copy()
     period = np.full((Hkv, 1, Dq), FOCUS_EVERY)
@@ -165,8 +209,43 @@ def scores_n(dt: str, Hkv: int, Sk: int, Dq: int, key_block: int, outside=(), ou
     for o, side in outside:
         inside |= cls(j - o + side, kvh * head_of_kv, Dq) == c
     n = np.where((kind >= 5) & inside, np.maximum(n, amp["focus"] + n % amp["base"]), n)
+    if fp8 is True:
+        n = np.where(np.isin(j // 128, QUIET_BLOCKS), np.minimum(n, QUIET), n)
+        n = balance_mu(n, n == n_base, Sk if kvalid is None else kvalid)
     assert n.min() >= 0 and n.max() <= 15
     return n.astype(np.int8)
+
+
+def sampled_rows(valid: int) -> np.ndarray:
+    """The rows of K that the e4m3 producer's "smooth K" mean is taken over (oracle.fp8_kmean, rsa_fp8.hip::kmean_sample_kernel):
+    up to 8 evenly spaced full 128-row blocks of the first `valid` rows."""
+    assert valid >= 128, "the model has no case whose only block of K is a partial one"
+    nb = valid // 128
+    ns = min(nb, 8)
+    return np.concatenate([np.arange(128) + 128 * ((i * nb) // ns) for i in range(ns)])
+
+
+def balance_mu(n: np.ndarray, base_only: np.ndarray, valid: int) -> np.ndarray:
+    """n with +1 (or -1) on as many base-only keys (by a hash) of the sampled rows as it takes to make every (K/V head, channel) sum
+    over those rows a multiple of their number (the nearest that the base-only keys can reach): the e4m3 kernel subtracts mu, the mean of K = 8 n over these rows, from
+    K, and K - mu = 8 (n - u) is exact in e4m3 (|n - u| <= 15 has four significant bits) with an integer u = mu / 8 only then.  A
+    base-only key goes from 0 / 1 to at most 2 (-1 only from 1 to 0), so a row's spread grows by at most 1."""
+    rows = sampled_rows(valid)
+    sub = n[:, rows, :]
+    tot = sub.sum(1)                                                     # [Hkv, D]
+    N = len(rows)
+    near = np.maximum(np.rint(tot / N), 1).astype(np.int64) * N - tot             # to the nearest multiple, to the next one up
+    above = -(-tot // N) * N - tot                                                 # where the keys that may go down are too few
+    need = np.where((near < 0) & ((base_only[:, rows, :] & (sub >= 1)).sum(1) < -near), above, near)
+    up = need >= 0
+    cand = base_only[:, rows, :] & (up[:, None, :] | (sub >= 1))
+    assert (cand.sum(1) >= np.abs(need)).all(), "too few base-only keys among the sampled rows to balance a channel's mean"
+    hk, jj, cc = np.meshgrid(np.arange(n.shape[0]), rows, np.arange(n.shape[2]), indexing="ij")
+    order = np.where(cand, _mix(hk, jj, cc, 6) >> np.uint64(1), np.uint64(2 ** 63))     # (candidates first, by hash)
+    rank = np.argsort(np.argsort(order, axis=1, kind="stable"), axis=1, kind="stable")
+    out = n.copy()
+    out[:, rows, :] = sub + np.where(up, 1, -1)[:, None, :] * (rank < np.abs(need)[:, None, :])
+    return out
 
 
 # ---- V -------------------------------------------------------------------------------------------------------------------
@@ -197,6 +276,17 @@ def witness_v(Hkv: int, Sk: int, D: int) -> np.ndarray:
     return v
 
 
+def v_gains(Hkv: int, Sk: int) -> np.ndarray:
+    """int [Hkv, ceil(Sk / 128)]: g of each 128-key block of V in the fp8 forms (V = 0 / 2^g: exact, and the block's E8M0 exponent
+    is g - 8, so that a wrong V exponent shows; the first two blocks of a head always differ)."""
+    nb = -(-Sk // 128)
+    hk, b = np.arange(Hkv)[:, None], np.arange(nb)[None, :]
+    g = np.asarray(V_GAINS)[(_mix(hk, b, 5) % np.uint64(len(V_GAINS))).astype(np.int64)]
+    if nb > 1:
+        g[:, 1] = np.where(g[:, 1] == g[:, 0], np.asarray(V_GAINS)[(np.searchsorted(V_GAINS, g[:, 0]) + 1) % len(V_GAINS)], g[:, 1])
+    return g
+
+
 # ---- the model of a case -------------------------------------------------------------------------------------------------
 @dataclasses.dataclass
 class Model:
@@ -218,15 +308,24 @@ class Model:
     mask: Optional[np.ndarray] = None
     pieces: Optional[dict] = None        # (bh, query block) -> list of arrays of key blocks: the pieces of a split walk
     extra: dict = dataclasses.field(default_factory=dict)
+    fp8: object = False       # False | True (e4m3 Q, K, V and P) | "pv" (2-byte Q . K^T, e4m3 P and V)
 
     @property
     def scale(self) -> float:
         return float(self.D) ** -0.5 if self.sm_scale is None else self.sm_scale
 
     @property
+    def q_target(self):
+        """(the scale find_a() is asked for, the value the scaled Q must round to).  The pv kernel multiplies Q by
+        (float)(sm_scale * 1.44269504 * 8) before it rounds it to the 2-byte type (rsa_attn_fp8_kernel.hip, a.qk_scale), so Q
+        rounds to 1 and a score arrives as 8 n, the code map's unit; the e4m3 image holds Q * (float)(sm_scale * 1.44269504), and
+        the MFMA's scale operand carries the 8."""
+        return (8.0 * self.scale, 1.0) if self.fp8 == "pv" else (self.scale, TARGET)
+
+    @property
     def a(self) -> float:
-        vals, _ = find_a(self.dt, self.scale)
-        assert len(vals) >= 1, f"no value of {self.dt} gives round(a * qk_scale) == {TARGET} at sm_scale {self.scale}"
+        vals, _ = find_a(self.dt, *self.q_target)
+        assert len(vals) >= 1, f"no value of {self.dt} gives round(a * qk_scale) == {self.q_target[1]} at sm_scale {self.scale}"
         return float(vals[0])
 
     def q(self) -> np.ndarray:
@@ -264,6 +363,117 @@ class Model:
         """The (b, h) pairs as flat indices b * H + h, restricted to the first H heads, or to a list of heads (None: all)."""
         hs = range(self.H) if H is None else range(min(H, self.H)) if isinstance(H, int) else H
         return [b * self.H + h for b in range(self.B) for h in hs]
+
+
+# ---- the fp8 forms: the operands as the kernels read them ------------------------------------------------------------------------
+def fp8_images(m: Model) -> dict:
+    """The block-scaled e4m3 images of the case's operands through the oracle's byte-exact contract (fp8_kmean, fp8_block_images),
+    dequantised, made once: mu [Hkv, D] and kd [Hkv, Sk, D] = K - mu as the kernel multiplies it (e4m3 form; pv: K itself, mu = 0),
+    vd [Hkv, Sk, D], qd [H, Sq, D] = the scaled Q (e4m3: the image of Q * qk_const, without the 8 the MFMA's scale operand adds; pv:
+    Q * qk_scale rounded to the 2-byte type), the E8M0 exponents eq [H, .], ek, ev [Hkv, .] (minus 127) and qunit, the one
+    non-zero value of a row of qd: 2^-3 (e4m3: the MFMA's scale operand adds the code map's 8) or 1 (pv: Q carries the 8), so that
+    qd . kd / (8 qunit) is the score in binary units."""
+    if "images" in m.extra:
+        return m.extra["images"]
+    from oracle import oracle as orc
+    assert m.fp8 and m.Hkv == m.H
+    pad = lambda x: -(-x // 128) * 128
+    kvalid = m.extra["kvalid"]
+    k, v, q = m.k(), m.v, m.q()[0]
+
+    def deq(img, ex, rows):
+        return (orc.dequantize_e4m3(img) * np.exp2(np.repeat(ex.astype(np.int64) - 127, 128))[:, None].astype(np.float32))[:rows]
+    out = dict(mu=np.zeros((m.Hkv, m.D), np.float32), kd=[], vd=[], qd=[], ek=[], ev=[], eq=[])
+    for hk in range(m.Hkv):
+        img, ex = orc.fp8_block_images(v[hk], kvalid, pad(m.Sk), "v")
+        out["vd"].append(deq(img, ex, m.Sk))
+        out["ev"].append(ex.astype(np.int64) - 127)
+        if m.fp8 is True:
+            out["mu"][hk] = orc.fp8_kmean(k[hk], kvalid) if m.extra.get("smooth_k", True) else 0
+            img, ex = orc.fp8_block_images(k[hk], kvalid, pad(m.Sk), "k", out["mu"][hk])
+            out["kd"].append(deq(img, ex, m.Sk))
+            out["ek"].append(ex.astype(np.int64) - 127)
+            img, ex = orc.fp8_block_images(q[hk], m.Sq, pad(m.Sq), "q")
+            out["qd"].append(deq(img, ex, m.Sq))
+            out["eq"].append(ex.astype(np.int64) - 127)
+        else:
+            out["kd"].append(k[hk])
+            out["qd"].append(round_dt(q[hk] * qk_scale(m.q_target[0]), m.dt))
+    out = {key: np.stack(val) if isinstance(val, list) and len(val) else val for key, val in out.items()}
+    out["qunit"] = TARGET if m.fp8 is True else 1.0
+    m.extra["images"] = out
+    return out
+
+
+def seen_blocks(m: Model) -> np.ndarray:
+    """bool [ceil(Sk / 128)]: the 128-key blocks that hold a key some row of the case sees."""
+    groups = np.unique(m.ref.r2g[m.ref.r2g >= 0])
+    keys = m.ref.vis[:, groups].any((0, 1))
+    return _pad(keys, 0, -(-m.Sk // 128) * 128).reshape(-1, 128).any(1)
+
+
+def fp8_image_faults(m: Model) -> List[str]:
+    """What keeps the integer scores from being exact in the case's fp8 form (empty = nothing): the conditions of the module
+    docstring, checked on the images."""
+    im = fp8_images(m)
+    bad = []
+    kvalid = m.extra["kvalid"]
+    if m.ref.vis[..., kvalid:].any():
+        bad.append("a row sees a key the producer does not count")
+    r = np.arange(m.Sq)
+    for h in range(m.H):
+        want = np.zeros((m.Sq, m.D), np.float32)
+        want[r, cls(r, h, m.D)] = im["qunit"]
+        if not np.array_equal(im["qd"][h], want):
+            bad.append(f"head {h}: the scaled Q is not one-hot with the power of two {im['qunit']}")
+    u = im["mu"].astype(np.float64) / KSCALE
+    if not np.array_equal(u, np.round(u)):
+        bad.append(f"mu / 8 is not integral: {u[u != np.round(u)][:4]}")
+    # dequantised q . k: between any two keys of a channel it differs by exactly the difference of their n
+    want_k = (KSCALE * (m.n[:, :kvalid].astype(np.float64) - u[:, None, :])).astype(np.float32)
+    if not np.array_equal(im["kd"][:, :kvalid], want_k):
+        bad.append("K - mu is not 8 (n - mu / 8) in the image")
+    if not np.array_equal(im["vd"][:, :kvalid], m.v[:, :kvalid]):
+        bad.append("V is not exact in its image")
+    seen = seen_blocks(m)
+    if seen.sum() == 1 and len(seen) > 1:          # (one row that sees one block: that block and its neighbour must differ)
+        b = int(np.nonzero(seen)[0][0])
+        seen[b + 1 if b + 1 < len(seen) else b - 1] = True
+    for name in ("ev",) + (("ek",) if m.fp8 is True else ()):
+        for hk in range(m.Hkv):
+            if len(set(im[name][hk][:len(seen)][seen].tolist())) < 2:
+                bad.append(f"K/V head {hk}: one {name[1].upper()} exponent in every block a row sees: {im[name][hk].tolist()}")
+    if m.fp8 is True and len({int(e) for e in np.unique(im["eq"])}) != 1:
+        bad.append(f"Q's exponent differs between blocks (the construction says it does not): {np.unique(im['eq']).tolist()}")
+    return bad
+
+
+def tile_walk(m: Model, t: "Terms"):
+    """The walk of Terms t in the fp8 kernels' 64-key tiles, and the moves of their deferred reference (rsa_attn_fp8_kernel.hip, as
+    oracle.attention_rows_pcode restates it): a row's reference starts at its first finite tile maximum and moves to the running
+    maximum whenever some row of its wave (32 consecutive rows) sees a tile maximum more than THRESH above its own reference.
+    -> (index of each sub-step's tile [S], num [T, R, D], den [T, R], J [T, R]: by how much the reference moves BEFORE tile t's
+    P is formed, 0 at a row's first tile).  A split walk is walked as one (its pieces restart the reference; the mutants that use
+    the moves are model mutants either way)."""
+    tiles, idx = np.unique(t.subs // 2, return_inverse=True)
+    T, R = len(tiles), len(t.rows)
+    numT, denT, mxT = np.zeros((T, R, m.D)), np.zeros((T, R)), np.full((T, R), -np.inf)
+    np.add.at(numT, idx, t.num)
+    np.add.at(denT, idx, t.den)
+    np.maximum.at(mxT, idx, t.mx)
+    wave = (t.rows % 128) // 32
+    thresh = pmap()[3]
+    ref = np.full(R, -np.inf)
+    J = np.zeros((T, R))
+    with np.errstate(invalid="ignore"):
+        for ti in range(T):
+            grow = np.where(np.isneginf(ref), mxT[ti] > -np.inf, mxT[ti] > ref + thresh)
+            gw = np.zeros(4, bool)
+            np.logical_or.at(gw, wave, grow)
+            new = np.where(gw[wave], np.maximum(ref, mxT[ti]), ref)
+            J[ti] = np.where(np.isfinite(ref) & (new > ref), new - ref, 0.0)
+            ref = new
+    return idx, numT, denT, J
 
 
 @dataclasses.dataclass
@@ -405,14 +615,28 @@ def insensitive(m: Model, H=None, vis_mutants=(), every: int = 1):
       pieces    split walks: the pieces merged without their 2^(m_i - m)
       heads     GQA: query head h reads K, or V, of K/V head h // g +- 1
       limits    visibility's own mutants that let a row see a key beyond a limit (the spike just outside it), now with weights
-    Exempt: a sub-step without a key visible to the block (it is in no walk of the model), a rectified row with R = 0, and a limit
-    another limit hides.  Limit mutants that hide a key or move a row are not weights' to show (visibility's probes pin them): they
+    and in the fp8 forms (the walk in 64-key tiles, the reference deferred per wave of 32 rows: tile_walk())
+      slots     for each 64-key tile of each walk, the k-slot of the V image (oracle.fp8_kslot_key) that holds the tile's heaviest key
+                (the largest share of a row of the block) swapped with the slot of the same row's lightest key; and the whole tile
+                stored in key order instead of k-slot order
+      exponents each key block's V exponent, and in the e4m3 form its K exponent, replaced by the next block's
+      moves     at each tile before which some row's deferred reference moves by >= 3: the rescale skips O, l or one 32-channel
+                d-tile of O; the tile's own scores, computed a step ahead, are not shifted; every row rescales by the move of
+                the row 32 further on or back (its neighbour wave's)
+    Exempt: a sub-step without a key visible to the block (it is in no walk of the model), a rectified row with R = 0, a limit
+    another limit hides, k-slots whose keys no row of the block sees, the key order in a tile of which the block sees fewer than 24 keys (keys
+    0 .. 3 are their own k-slots, and the hashed heavy key of a focused sub-step is one of 8 .. 23), and a neighbouring block that has the same exponent.  Limit mutants that hide a key or move a row are not weights' to show (visibility's probes pin them): they
     are counted in the returned table under their own heading.
     """
     base = reference(m, H, every=every)
     tol = vis.tolerance(base, ULP[m.dt])
     missed: List[str] = []
     exempt = {"sub-step without a visible key": 0, "rectified row with R = 0": 0, "limit hidden by another limit": 0}
+    if m.fp8:
+        exempt.update({"swapped k-slots without a visible key": 0, "neighbouring block with the same exponent": 0,
+                       "key order in a tile of which the block sees fewer than 24 keys": 0})
+        from oracle import oracle as orc
+        im = fp8_images(m)
     skipped = {"limit mutant that hides a key or moves a row (visibility's probes pin those)": 0}
 
     def moved(bh, t, out):
@@ -502,6 +726,9 @@ def insensitive(m: Model, H=None, vis_mutants=(), every: int = 1):
                         for what, kw in (("K", dict(kn=other)), ("V", dict(kv=other))):
                             if not moved(bh, t, block_rows(m, bh, qb, **kw)):
                                 missed.append(f"{where}: head {h} reads {what} of K/V head {other}")
+            if m.fp8:
+                missed += [f"{where}: {x}" for x in _fp8_insensitive(m, bh, t, num, den, live, im, exempt, orc,
+                                                                      lambda out, bh=bh, t=t: moved(bh, t, out))]
     # limits
     for name, mref in vis_mutants:
         if np.array_equal(mref.r2g, m.ref.r2g) and np.array_equal(mref.vis, m.ref.vis):
@@ -513,6 +740,89 @@ def insensitive(m: Model, H=None, vis_mutants=(), every: int = 1):
         if not (np.abs(reference(m, H, mref, every) - base) >= SENSITIVITY * tol).any():
             missed.append(f"limit: {name}")
     return missed, dict(exempt, **skipped)
+
+
+def _fp8_insensitive(m: Model, bh: int, t: Terms, num, den, live, im, exempt, orc, moved) -> List[str]:
+    """The fp8 forms' own model mutants of one walk (insensitive() has the list)."""
+    out = []
+    kvh = m.kvh(bh % m.H)
+    idx, numT, denT, J = tile_walk(m, t)
+    # slots
+    vp = _pad(m.padded("v", kvh), 0, -(-m.Sk // vis.TILE) * vis.TILE)
+    at = {int(s): i for i, s in enumerate(t.subs)}
+
+    def weight(key):
+        return t.W[:, at[key // SUB], key % SUB] if key // SUB in at else np.zeros(len(t.rows))
+    slot_key = orc.fp8_kslot_key(np.arange(vis.TILE))
+    slot_of = np.argsort(slot_key)
+    share = t.W / np.where(live & (den > 0), den, np.inf)[:, None, None]
+    for tile in np.unique(t.subs // 2):
+        key0 = int(tile) * vis.TILE
+        wt = np.stack([weight(key0 + x) for x in range(vis.TILE)], 1)                        # [R, 64]
+        sh = np.stack([share[:, at[s_]] if s_ in at else np.zeros((len(t.rows), SUB)) for s_ in (2 * int(tile), 2 * int(tile) + 1)], 1)
+        if not (sh > 0).any():
+            exempt["swapped k-slots without a visible key"] += 2
+            continue
+        # (a) two slots: the tile's heaviest key (the largest share of a row of the block: where a weight on the wrong key shows) and
+        #     the lightest key of the same row, an invisible one (weight 0) where the row sees only a part of the tile
+        r1, k1 = np.unravel_index(np.argmax(sh.reshape(len(t.rows), -1)), (len(t.rows), vis.TILE))
+        k2 = int(np.argmin(np.where(np.arange(vis.TILE) % SUB == k1 % SUB, np.inf, wt[r1])))       # (not its twin in the other sub-step)
+        dn = (wt[:, k1] - wt[:, k2])[:, None] * (vp[key0 + k2] - vp[key0 + k1])[None, :]
+        if not moved(finish(m, bh, t, num + dn, den)):
+            out.append(f"k-slots {int(slot_of[k1])} and {int(slot_of[k2])} of the V tile {int(tile)} swapped")
+        # (b) the tile stored in key order: slot p, which the MFMA takes for key fp8_kslot_key(p), holds key p
+        dn = wt[:, slot_key] @ vp[key0:key0 + vis.TILE] - wt @ vp[key0:key0 + vis.TILE]
+        if (wt > 0).any(0).sum() < 24:       # (keys 0 .. 3 are their own slots, and the hashed heavy key of a sub-step is one of 8 .. 23)
+            exempt["key order in a tile of which the block sees fewer than 24 keys"] += 1
+        elif not moved(finish(m, bh, t, num + dn, den)):
+            out.append(f"the V tile {int(tile)} stored in key order, not in k-slot order")
+    # exponents
+    blocks = t.subs * SUB // 128
+    nblk = -(-m.Sk // 128)
+    for kb in np.unique(blocks):
+        on = blocks == kb
+        nb = int(kb) + 1 if kb + 1 < nblk else int(kb) - 1
+        if nb < 0:
+            continue
+        d = int(m.extra["gains"][kvh, nb] - m.extra["gains"][kvh, kb])
+        if d == 0:
+            exempt["neighbouring block with the same exponent"] += 1
+        elif not moved(finish(m, bh, t, num + t.num[on].sum(0) * (2.0 ** d - 1.0), den)):
+            out.append(f"key block {int(kb)} takes the V exponent of block {nb}")
+        if m.fp8 is True:
+            d = int(im["ek"][kvh, nb] - im["ek"][kvh, kb])
+            if d == 0:
+                exempt["neighbouring block with the same exponent"] += 1
+                continue
+            u = (im["mu"][kvh].astype(np.float64) / KSCALE)[cls(t.rows, bh % m.H, m.D)][:, None, None]
+            W0 = t.W[:, on]
+            W1 = np.where(W0 > 0, np.exp2((np.log2(np.where(W0 > 0, W0, 1.0)) - u) * 2.0 ** d + u), 0.0)
+            n1 = num + np.einsum("rst,std->rd", W1 - W0, t.vs[on])
+            if not moved(finish(m, bh, t, n1, den + (W1 - W0).sum((1, 2)))):
+                out.append(f"key block {int(kb)} takes the K exponent of block {nb}")
+    # moves of the deferred reference
+    cn, cd = np.cumsum(numT, 0), np.cumsum(denT, 0)
+    pos = t.rows - t.rows[0]
+    nbr = np.where((pos ^ 32) < len(pos), pos ^ 32, -1)
+    for ti in range(1, len(J)):
+        if not ((J[ti] >= 3) & live).any():
+            continue
+        f = np.exp2(J[ti]) - 1.0
+        bn, bd = cn[ti - 1] * f[:, None], cd[ti - 1] * f
+        variants = [("the rescale skips O", num + bn, den), ("the rescale skips l", num, den + bd),
+                    ("the scores computed ahead are not shifted", num + numT[ti] * f[:, None], den + denT[ti] * f)]
+        for dtile in range(m.D // 32):
+            sel = np.zeros(m.D, bool)
+            sel[32 * dtile:32 * dtile + 32] = True
+            variants.append((f"the rescale skips d-tile {dtile} of O", num + bn * sel, den))
+        Jn = np.where(nbr >= 0, J[ti][np.maximum(nbr, 0)], 0.0)
+        if ((J[ti] != Jn) & live & (cd[ti - 1] > 0)).any():
+            fw = np.exp2(J[ti] - Jn) - 1.0
+            variants.append(("the waves rescale by their neighbour wave's move", num + cn[ti - 1] * fw[:, None], den + cd[ti - 1] * fw))
+        for name, n1, d1 in variants:
+            if not moved(finish(m, bh, t, n1, d1)):
+                out.append(f"reference move at tile {ti} of the walk: {name}")
+    return out
 
 
 # ---- the cases -----------------------------------------------------------------------------------------------------------
@@ -572,13 +882,38 @@ def _rect_cases() -> List[dict]:
     return [c for c in vis.RECT_CASES if not c["fp8"]]
 
 
+def _rect_fp8_cases() -> List[dict]:
+    """visibility's rectified cases of the e4m3 and pv forms (128-token blocks: the fp8 K5 is built for no other): the four
+    layouts at head dims 128 and 64, the text split (hunyuan_tsplit) in both forms, the tail split on and off (hunyuan_tail, e4m3).
+    Every one runs with "smooth K" on (tuning key fp8_smooth_k = 1, the product's setting): balance_mu() found a balance in each."""
+    return [c for c in vis.RECT_CASES if c["fp8"]]
+
+
+def _dense_fp8_cases() -> List[dict]:
+    """Every shape of visibility.DENSE_SHAPES at both head dims in both forms, with the four settings of _dense_cases()."""
+    cases = []
+    for fp8, form in ((True, "e4m3"), ("pv", "pv")):
+        for D in (128, 64):
+            for Sq, Sk in vis.DENSE_SHAPES:
+                qs, ks = vis.dense_splits(Sq, Sk)[1]
+                for name, q_split, kv_split, causal in (("whole", None, None, False), ("causal", None, None, True),
+                                                        (f"q{qs}_kv{ks}", qs, ks, False), (f"q{qs}_kv{ks}-causal", qs, ks, True)):
+                    cases.append(dict(id=f"dense-{form}-D{D}-{Sq}x{Sk}-{name}", family="dense", dt="bf16", fp8=fp8, D=D, B=2, H=2,
+                                      Sq=Sq, Sk=Sk, q_split=q_split, kv_split=kv_split, causal=causal))
+    return cases
+
+
 PLAIN_CASES = _plain_cases()
 DENSE_CASES = _dense_cases()
 RANGED_CASES = _ranged_cases()
 GQA_CASES = _gqa_cases()
 RECT_CASES = _rect_cases()
-CASES: Dict[str, dict] = {c["id"]: c for c in PLAIN_CASES + DENSE_CASES + RANGED_CASES + GQA_CASES + RECT_CASES}
-assert len(CASES) == len(PLAIN_CASES) + len(DENSE_CASES) + len(RANGED_CASES) + len(GQA_CASES) + len(RECT_CASES)
+RECT_FP8_CASES = _rect_fp8_cases()
+DENSE_FP8_CASES = _dense_fp8_cases()
+FP8_CASES = RECT_FP8_CASES + DENSE_FP8_CASES
+_ALL_CASES = PLAIN_CASES + DENSE_CASES + RANGED_CASES + GQA_CASES + RECT_CASES + FP8_CASES
+CASES: Dict[str, dict] = {c["id"]: c for c in _ALL_CASES}
+assert len(CASES) == len(_ALL_CASES)
 
 
 def _tail_pieces(mask: np.ndarray, H: int, NBp: int, valid_blocks: int) -> dict:
@@ -676,6 +1011,8 @@ def model(c: dict, parts=None) -> Model:
     fam, dt, D = c["family"], c["dt"], c["D"]
     B, H = c["B"], c["H"]
     Hkv = c.get("Hkv", H)
+    fp8 = form_of(c)
+    kvalid = None             # the rows of K and V the fp8 producer counts
     pieces = None
     mask = None
     outside, outside_keys = [], []
@@ -692,8 +1029,10 @@ def model(c: dict, parts=None) -> Model:
             qs = Sq if c["q_split"] is None else c["q_split"]
             ks = Sk if c["kv_split"] is None else c["kv_split"]
             outside = [(ks - qs + 1, 1)] + ([(Sk - Sq + 1, 1)] if qs < Sq and ks - qs != Sk - Sq else [])     # (per segment)
-        if c["kv_split"] is not None:
-            outside_keys = [c["kv_split"], c["kv_split"] - 1]
+            outside = [(o, sd) for o, sd in outside if o < Sk and o + Sq > 0]       # (a diagonal that leaves the keys has no key outside it)
+        if c["kv_split"] is not None:          # (the key before the split is outside a limit only where the second segment has rows)
+            outside_keys = [c["kv_split"]] + ([c["kv_split"] - 1] if c["q_split"] < Sq else [])
+        kvalid = Sk
     elif fam in ("ranged", "gqa"):
         import test_ranged_cpu as rule
         Sq, Sk, qrows, kb = c["Sq"], c["Sk"], 128, 128
@@ -720,17 +1059,24 @@ def model(c: dict, parts=None) -> Model:
         ref, mask = vis.rect_ref(c, sp, None, R, comp)
         Sq = Sk = sp.S
         qrows = kb = c["blk"]
+        kvalid = sp.pool_valid
         outside_keys = [sp.kv_valid, sp.kv_text_valid]
         pieces = _text_pieces(sp, B * H)
         if c.get("tail_split"):
             pieces = {**(pieces or {}), **_tail_pieces(mask, H, sp.NB_total, -(-sp.kv_valid // sp.block))}
-        if parts is None:          # visibility's model of R and comp, on THIS V (head 0's) and no pooled-score model: R as there
-            R, comp = vis.rect_model_parts(sp, mask, witness_v(1, Sk, D)[0])
-            ref.R[:, :sp.NBv], ref.comp[:, :sp.NBv] = R, comp
+    assert not fp8 or (kvalid is not None and Hkv == H and kb == 128 and "sm_scale" not in c), "the fp8 forms: MHA, 128-token blocks"
+    v = witness_v(Hkv, Sk, D)
+    gains = None
+    if fp8:
+        gains = v_gains(Hkv, Sk)
+        v = v * np.exp2(np.repeat(gains, 128, axis=1)[:, :Sk, None]).astype(np.float32)
+    if fam == "rect" and parts is None:    # visibility's model of R and comp, on THIS V (head 0's) and no pooled-score model: R as there
+        R, comp = vis.rect_model_parts(sp, mask, v[0])
+        ref.R[:, :sp.NBv], ref.comp[:, :sp.NBv] = R, comp
     forced = forced_classes(ref, B, H, Sq, Sk, qrows, D) if Hkv == H else None
-    n = scores_n(dt, Hkv, Sk, D, kb, tuple(outside), tuple(outside_keys), H // Hkv, forced)
-    return Model(dt, B, H, Hkv, Sq, Sk, D, c.get("sm_scale"), ref, n, witness_v(Hkv, Sk, D), qrows, kb, mask, pieces,
-                 dict(outside=tuple(outside), outside_keys=tuple(outside_keys)))
+    n = scores_n(dt, Hkv, Sk, D, kb, tuple(outside), tuple(outside_keys), H // Hkv, forced, fp8, kvalid)
+    return Model(dt, B, H, Hkv, Sq, Sk, D, c.get("sm_scale"), ref, n, v, qrows, kb, mask, pieces,
+                 dict(outside=tuple(outside), outside_keys=tuple(outside_keys), kvalid=kvalid, gains=gains), fp8)
 
 
 def misplaced_outside_keys(m: Model) -> List[str]:
