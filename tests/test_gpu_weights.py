@@ -8,8 +8,8 @@ and be exactly 0 where that is.  bf16 cases run with the static softmax referenc
 pv forms (qkv_fp8=) run the rectified and the dense cases under the same bound: there every P is the e4m3 code of 1.5 times a power
 of two, K minus its sampled mean and V times its block gain are exact in their images, and the "smooth K" of the product stays on.
 
-Out of scope: Q's block exponent (one value by construction), rsa_attn_masked.hip (its scale is applied in fp32, so integer scores
-cannot be reached) and the selection pass."""
+Out of scope: Q's block exponent (one value by construction), the selection pass, and rsa_attn_masked.hip (its scale is applied in
+fp32, so integer scores cannot be reached: tests/test_gpu_masked_witness.py witnesses it through integer biases instead)."""
 import contextlib
 
 import numpy as np

@@ -46,8 +46,8 @@ that two distinct K and two distinct V exponents occur among the blocks some row
 the bound is the same.  A second assumption is not derived: that v_cvt_pk_u8_f32 of an exact integer is that integer (the fp8
 cases meeting the bound on the device shows it).
 
-Out of scope: Q's block exponent, rsa_attn_masked.hip (its scale is applied in fp32, so integer scores cannot be reached) and the
-selection pass."""
+Out of scope: Q's block exponent, the selection pass, and rsa_attn_masked.hip: its scale is applied in fp32, so integer SCORES cannot
+be reached -- tests/masked_witness.py reaches integer weights there through the bias instead."""
 from __future__ import annotations
 
 import dataclasses
