@@ -208,6 +208,98 @@ __device__ __forceinline__ float* rsa_part_of(const WalkArgs& a, int bh, int uni
                      : a.tpart + rsa_part_row(((long)bh * (a.NQB - a.NBv) + (unit - a.NBv)) * a.tsplit + tsp, row, D);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The fragment layer: what knows how the operands and the accumulator of a 32 x 32 MFMA lie across the lanes, once for the K5
+// kernels.  Lane (r = lane & 31, hh = lane >> 5) owns query row r; register 4 g + i of an O^T tile of 32 d (d tile dt) is
+// d = 32 dt + 8 g + 4 hh + i: four consecutive d per register quad.
+//
+// Scaled 2-byte Q fragment of one k-step (B operand of v_mfma_f32_32x32x16: the lane's k = 16 ks + 8 hh .. + 7, qp points at
+// them): q * scale rounded to the input type (scale = sm_scale * log2(e), times PMap's unit in the pv form); zeros for a row
+// past the sequence (!ok)
+template <typename Tag>
+__device__ __forceinline__ s16x8 rsa_q_frag(const unsigned short* qp, bool ok, float scale) {
+    uint4 raw = make_uint4(0, 0, 0, 0);
+    if (ok) raw = *reinterpret_cast<const uint4*>(qp);
+    const unsigned w4[4] = {raw.x, raw.y, raw.z, raw.w};
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f[2 * e] = rsa_to_f32<Tag>((unsigned short)(w4[e] & 0xFFFF)) * scale;
+        f[2 * e + 1] = rsa_to_f32<Tag>((unsigned short)(w4[e] >> 16)) * scale;
+    }
+    return Elem<Tag>::cvt8(f);
+}
+
+// Split-KV partial of a row (pp = rsa_part_of: rows are 8-byte aligned): d tile dt of the unnormalised O, then the running
+// maximum (log2 domain) and the row sum behind the row's D values, from lane half 0
+__device__ __forceinline__ void rsa_part_tile(float* pp, int dt, int hh, const f32x16& o) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int i = 0; i < 4; i += 2)
+            *reinterpret_cast<float2*>(pp + 32 * dt + 8 * g + 4 * hh + i) = make_float2(o[4 * g + i], o[4 * g + i + 1]);
+}
+__device__ __forceinline__ void rsa_part_ml(float* pp, int D, int hh, float m, float l) {
+    if (hh == 0) *reinterpret_cast<float2*>(pp + D) = make_float2(m, l);
+}
+
+// The compensation values the lane adds to its row, cv[dt][g] = cp[32 dt + 8 g + 4 hh .. + 3], or zeros (cp null: a row that
+// is not rectified).  ALL loads are issued here, back to back, one wait: loaded per (dt, g) inside the store loop each load's
+// latency (L2 / HBM: 1-2 k cycles) is exposed in turn -- 30 k of a 64-row wave's 535 k cycles with nothing else on the SIMD to
+// cover it (stamps: profiles/r04_k5_w64.md)
+template <int DT>
+__device__ __forceinline__ void rsa_comp_row(float4 (&cv)[DT][4], const float* cp, int hh) {
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) cv[dt][g] = make_float4(0, 0, 0, 0);
+    if (cp) {
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) cv[dt][g] = *reinterpret_cast<const float4*>(cp + 32 * dt + 8 * g + 4 * hh);
+    }
+}
+
+// The rectified store of d tile dt of a row (op = the row's first output element): O * sc + comp, one fma rounded to fp32, THEN
+// the conversion to the storage type (what the oracle does).  Left alone, hipcc folds fma + conversion into v_fma_mixlo_f16
+// (one rounding, straight to fp16) in one store form and not in the other; the empty asm keeps the fp32 value, so both store
+// forms write the same bytes (tests/test_gpu_store_forms.py).
+// WIDE (needs 16-byte aligned output rows): lane (r, 0) holds d = 8g .. 8g+3 and lane (r, 1) d = 8g+4 .. 8g+7 of the tile; one
+// v_permlane32_swap per packed register pair regroups two g's so that each lane owns 8 consecutive d: 2 stores of 16 B per lane
+// and tile instead of 4 of 8 B (the store tail of a row-per-lane epilogue is issue-bound).
+template <typename Tag, bool WIDE>
+__device__ __forceinline__ void rsa_out_tile(unsigned short* op, int dt, int hh, const f32x16& o, float sc, const float4 (&cv)[4]) {
+    uint2 pk[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float c[4] = {cv[g].x, cv[g].y, cv[g].z, cv[g].w};
+        unsigned short w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float rr = __builtin_fmaf(o[4 * g + i], sc, c[i]);
+            asm volatile("" : "+v"(rr));
+            w[i] = Elem<Tag>::from_f32(rr);
+        }
+        pk[g].x = (unsigned)w[0] | ((unsigned)w[1] << 16);
+        pk[g].y = (unsigned)w[2] | ((unsigned)w[3] << 16);
+    }
+    if constexpr (WIDE) {
+#pragma unroll
+        for (int gp = 0; gp < 2; ++gp) {
+            // X' = [X.lower, Y.lower], Y' = [X.upper, Y.upper]  (X = pk[2 gp], Y = pk[2 gp + 1])
+            const auto sx = __builtin_amdgcn_permlane32_swap(pk[2 * gp].x, pk[2 * gp + 1].x, false, false);
+            const auto sy = __builtin_amdgcn_permlane32_swap(pk[2 * gp].y, pk[2 * gp + 1].y, false, false);
+            uint4 w4;
+            w4.x = sx[0]; w4.y = sy[0]; w4.z = sx[1]; w4.w = sy[1];
+            *reinterpret_cast<uint4*>(op + 32 * dt + 8 * (2 * gp + hh)) = w4;
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) *reinterpret_cast<uint2*>(op + 32 * dt + 8 * g + 4 * hh) = pk[g];
+    }
+}
+
 // Host plan of a launch (rsa_attn.hip): text split, text pieces first or last, padding, tail split and the grid size, from the
 // shape and the policy of the kernel family that asks.
 struct WalkPolicy {

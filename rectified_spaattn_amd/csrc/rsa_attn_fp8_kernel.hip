@@ -317,18 +317,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
     if constexpr (HYB != 0) {
         const unsigned short* qp16 = a.q16 + (long)b * a.qsb + (long)h * a.qsh + (long)grow * a.qss + 8 * hh;
 #pragma unroll
-        for (int ks = 0; ks < KSH; ++ks) {
-            uint4 raw = make_uint4(0, 0, 0, 0);
-            if (grow < a.Sq) raw = *reinterpret_cast<const uint4*>(qp16 + 16 * ks);
-            const unsigned w4[4] = {raw.x, raw.y, raw.z, raw.w};
-            float f[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                f[2 * e] = rsa_to_f32<HT>((unsigned short)(w4[e] & 0xFFFF)) * a.qk_scale;
-                f[2 * e + 1] = rsa_to_f32<HT>((unsigned short)(w4[e] >> 16)) * a.qk_scale;
-            }
-            qh[ks] = Elem<HT>::cvt8(f);
-        }
+        for (int ks = 0; ks < KSH; ++ks) qh[ks] = rsa_q_frag<HT>(qp16 + 16 * ks, grow < a.Sq, a.qk_scale);
     }
 
     // ---------------- LDS-DMA staging ----------------
@@ -343,11 +332,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     auto dma2 = [&](const unsigned char* tile_src, unsigned lds_dst, unsigned voff) {
 #pragma unroll
-        for (int j = 0; j < NPC8; ++j) {
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                         :: "v"(voff), "s"(tile_src + (wv + 4 * j) * 1024), "s"(lds_dst + (wv + 4 * j) * 1024)
-                         : "memory");
-        }
+        for (int j = 0; j < NPC8; ++j) rsa_lds_dma16(voff, tile_src + (wv + 4 * j) * 1024, lds_dst + (wv + 4 * j) * 1024);
     };
     // "pv" form: the 64-key K tile from the 2-byte tensor, image and swizzle of rsa_attn_kernel.hip (groups of 4 pieces = 16 rows at
     // head dim 128, 32 rows at 64; wave w moves piece w of every group; source chunk XOR-swizzled, rows past the last valid key clamped)
@@ -365,9 +350,7 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
             for (int j = 0; j < NPK_H; ++j) {
                 int krow = key0 + 4 * RPI_H * j + rowl_h;
                 krow = krow < kv_limit_h ? krow : kv_limit_h - 1;
-                const unsigned vo = (unsigned)(((long)krow * a.kss + gsw_h * 8) * 2);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                             :: "v"(vo), "s"(kb16), "s"(ld0 + j * 4096) : "memory");
+                rsa_lds_dma16((unsigned)(((long)krow * a.kss + gsw_h * 8) * 2), kb16, ld0 + j * 4096);
             }
         }
     };
@@ -725,40 +708,24 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
         // split-KV partial of a text block or of a tail piece (merged by rsa_attn.hip's combine kernels): O in V's units, m, l
         float* pp = rsa_part_of(a, bh, qblk, tsp, tail, 32 * wv + r, D8);
 #pragma unroll
-        for (int dt = 0; dt < DT8; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d0 = 32 * dt + 8 * g + 4 * hh;
-                *reinterpret_cast<float2*>(pp + d0) = make_float2(o[dt][4 * g + 0], o[dt][4 * g + 1]);
-                *reinterpret_cast<float2*>(pp + d0 + 2) = make_float2(o[dt][4 * g + 2], o[dt][4 * g + 3]);
-            }
-        if (hh == 0) *reinterpret_cast<float2*>(pp + D8) = make_float2(m_run, l_tot);
+        for (int dt = 0; dt < DT8; ++dt) rsa_part_tile(pp, dt, hh, o[dt]);
+        rsa_part_ml(pp, D8, hh, m_run, l_tot);
         return;
     }
     if (!(store_r || zero_r)) return;
     float inv = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
     float Rv = 1.0f;
-    // the compensation values this lane adds and R: all loads issued here, back to back, one wait (loaded per (dt, g) inside the
-    // store loop each load's latency is exposed in turn: round 4, profiles/r04_k5_w64.md)
+    // the compensation values this lane adds (rsa_attn.h) and R; only sparse walks are rectified, so the compensation values of a
+    // padded text row (zero_r) are zeros already
     float4 cv[DT8][4];
-#pragma unroll
-    for (int dt = 0; dt < DT8; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) cv[dt][g] = make_float4(0, 0, 0, 0);
-    if (rectify) {
-        const long rowi = (long)bh * a.NBv + qblk;
-        if (!zero_r) {
-            const float* cp = a.comp + rowi * D8;
-#pragma unroll
-            for (int dt = 0; dt < DT8; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) cv[dt][g] = *reinterpret_cast<const float4*>(cp + 32 * dt + 8 * g + 4 * hh);
-        }
-        Rv = a.R[rowi];
-    }
+    const long rowi = (long)bh * a.NBv + qblk;
+    rsa_comp_row<DT8>(cv, rectify ? a.comp + rowi * D8 : nullptr, hh);
+    if (rectify) Rv = a.R[rowi];
     if (zero_r) inv = 0.0f;
     const float sc = inv * Rv;
     unsigned short* op = a.out + (long)b * a.osb + (long)h * a.osh + (long)grow * a.oss;
+    // This store is not rsa_out_tile: o * sc + c is left to hipcc's contraction (no pinned fp32 value), the output type is picked
+    // at run time, and there is only the 8-byte form
     // (16-byte stores after a v_permlane32_swap regroup, the 2-byte kernel's default, measured neutral here: 9.60 vs 9.60 ms)
 #pragma unroll
     for (int dt = 0; dt < DT8; ++dt) {
@@ -784,6 +751,31 @@ __global__ __launch_bounds__(256, 2) void bsfwd_fp8_kernel(Attn8Args a) {
 }
 
 int g_fp8_variant = 0;
+// e4m3 scores: no 2-byte operands.  pv form: scores from the 2-byte q and k themselves
+void no_scores_16(Attn8Args& a) {
+    a.q16 = a.k16 = nullptr; a.qsb = a.qsh = a.qss = a.ksb = a.ksh = a.kss = 0; a.qk_scale = 0.0f;
+}
+void scores_from_16(Attn8Args& a, const rsa_tensor4& q, const rsa_tensor4& k, int D) {
+    a.q16 = static_cast<const unsigned short*>(q.ptr); a.qsb = q.stride_b; a.qsh = q.stride_h; a.qss = q.stride_s;
+    a.k16 = static_cast<const unsigned short*>(k.ptr); a.ksb = k.stride_b; a.ksh = k.stride_h; a.kss = k.stride_s;
+    a.qk_scale = (float)((1.0 / sqrt((double)D)) * 1.44269504 * 8.0);      // sm_scale * log2(e) * PMap<true>::U
+}
+// The instantiation of one (head dim, operand form) the tuning key fp8_variant asks for: 0 = the product (the hand-placed code-map
+// block with the wave's LDS-DMA pieces inside); 1 = its compiled twin (same arithmetic, hipcc's schedule); 2 = exact-exponential P,
+// hand-placed (e4m3 at head dim 128 only); 3 = the product's block with the staging behind the barrier, as rounds 3-4 had it (not the
+// pv form at head dim 64).  1 and 2 are the verification forms the tests compare the product with; a variant a form lacks runs the product
+template <int D8, int HYB>
+void launch_fp8_variant(const Attn8Args& a, dim3 grid, size_t lds_bytes, hipStream_t s) {
+    const bool sparse = a.mode == MODE_SPARSE;
+    const int v = g_fp8_variant;
+    if constexpr (HYB == 0 && D8 == 128)
+        if (v == 2) { RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<3, D8, HYB>), a, sparse, grid, 256, lds_bytes, s); return; }
+    if constexpr (HYB == 0 || D8 == 128)
+        if (v == 3) { RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<7, D8, HYB>), a, sparse, grid, 256, lds_bytes, s); return; }
+    if (v == 1) RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<6, D8, HYB>), a, sparse, grid, 256, lds_bytes, s);
+    else RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<15, D8, HYB>), a, sparse, grid, 256, lds_bytes, s);
+}
+
 int launch_attn8(Attn8Args& a, int BH, int D8, size_t tpart_bytes, hipStream_t s, int hyb = 0) {
     long nblocks;
     WalkPolicy pol;
@@ -798,49 +790,32 @@ int launch_attn8(Attn8Args& a, int BH, int D8, size_t tpart_bytes, hipStream_t s
     // a head-contiguous K at 256 B per row reaches 16 M).  The 2-byte and e4m3 kernels walk a 64-bit scalar base instead.
     if (hyb != 0 && (unsigned long long)a.Sk * (unsigned long long)(a.kss < 0 ? -a.kss : a.kss) * 2ull >= (1ull << 32))
         return RSA_ERR_UNSUPPORTED;
-    const size_t lds_bytes = (size_t)2 * NSLOT * 64 * D8 + 64 + (((size_t)a.NB_total * 4 + 15) & ~(size_t)15);
-    if (hyb != 0 && D8 == 64) {   // the pv form at head dim 64 (K 3 x 8 KiB, V 3 x 4 KiB): product and compiled twin
-        const size_t n_list = a.NB_total < RSA_PV_LIST_WINDOW ? a.NB_total : RSA_PV_LIST_WINDOW;
-        const size_t lds_h = (size_t)3 * 8192 + (size_t)3 * 4096 + 64 + ((n_list * 4 + 15) & ~(size_t)15);
-        if (g_fp8_variant == 1) {
-            if (hyb == 2) RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<6, 64, 2>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-            else RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<6, 64, 1>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-        } else {
-            if (hyb == 2) RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<15, 64, 2>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-            else RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<15, 64, 1>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-        }
-    } else
-    if (hyb != 0) {   // the pv form: 2-byte Q . K^T, e4m3 P . V (three-slot rings: K 3 x 16 KiB, V 3 x 8 KiB)
-        if (D8 != 128) return RSA_ERR_UNSUPPORTED;
-        const size_t n_list = a.NB_total < RSA_PV_LIST_WINDOW ? a.NB_total : RSA_PV_LIST_WINDOW;     // (the kernel's LWIN)
-        const size_t lds_h = (size_t)3 * 16384 + (size_t)3 * 8192 + 64 + ((n_list * 4 + 15) & ~(size_t)15);
-        // (tuning key fp8_variant 1 = the compiled twin of the hand-placed block: same arithmetic, hipcc's schedule)
-        // and 3 = the hand-placed block with the staging behind the barrier, as the other forms have it)
-        if (g_fp8_variant == 1) {
-            if (hyb == 2) RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<6, 128, 2>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-            else RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<6, 128, 1>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-        } else if (g_fp8_variant == 3) {
-            if (hyb == 2) RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<7, 128, 2>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-            else RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<7, 128, 1>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-        } else {
-            if (hyb == 2) RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<15, 128, 2>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-            else RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<15, 128, 1>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_h, s);
-        }
-    } else
-    if (D8 == 64) {   // head dim 64: the product form, its compiled twin (1), the hand-placed block with the staging behind the barrier (3)
-        if (g_fp8_variant == 1) RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<6, 64>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_bytes, s);
-        else if (g_fp8_variant == 3) RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<7, 64>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_bytes, s);
-        else RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<15, 64>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_bytes, s);
-    } else {
-        switch (g_fp8_variant) {   // tuning key fp8_variant: 0 = product; 1, 2 = the two verification forms the tests compare it with
-            case 1: RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<6>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_bytes, s); break;   // product arithmetic, hipcc's schedule
-            case 2: RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<3>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_bytes, s); break;   // exact-exponential P, hand-placed
-            case 3: RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<7>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_bytes, s); break;   // the product's block, staging behind the barrier (rounds 3-4)
-            default: RSA_LAUNCH_GSYNC(2, (bsfwd_fp8_kernel<15>), a, a.mode == MODE_SPARSE, dim3((unsigned)nblocks), 256, lds_bytes, s);
-        }
-    }
+    if (hyb != 0 && D8 != 128 && D8 != 64) return RSA_ERR_UNSUPPORTED;
+    // LDS: the two rings, the row-sum product's 64-byte ones table, the walk's entries.  e4m3: four slots of 64 D8 bytes each, the
+    // whole list.  pv form: three slots (K tiles of 2-byte rows: 3 x 16 KiB + 3 x 8 KiB at head dim 128) and the kernel's LWIN window
+    const size_t n_list = hyb != 0 && a.NB_total > RSA_PV_LIST_WINDOW ? RSA_PV_LIST_WINDOW : a.NB_total;
+    const size_t lds_bytes = (hyb != 0 ? (size_t)3 * (2 * 64 * D8 + 64 * D8) : (size_t)2 * NSLOT * 64 * D8) + 64 + ((n_list * 4 + 15) & ~(size_t)15);
+    const dim3 grid((unsigned)nblocks);
+    if (hyb == 0) D8 == 64 ? launch_fp8_variant<64, 0>(a, grid, lds_bytes, s) : launch_fp8_variant<128, 0>(a, grid, lds_bytes, s);
+    else if (hyb == 2) D8 == 64 ? launch_fp8_variant<64, 2>(a, grid, lds_bytes, s) : launch_fp8_variant<128, 2>(a, grid, lds_bytes, s);
+    else D8 == 64 ? launch_fp8_variant<64, 1>(a, grid, lds_bytes, s) : launch_fp8_variant<128, 1>(a, grid, lds_bytes, s);
     st = rsa_launch_status();
     return st != RSA_OK ? st : rsa_combine_walk(a, D8, RSA_BLOCK, a.out_fp16 ? RSA_FP16 : RSA_BF16, s);
+}
+
+// The operands of a sparse call on the e4m3 images (the pv form then adds its scores' operands: scores_from_16)
+void fill_sparse8(Attn8Args& a, const rsa_layout* l, const rsa_fp8_operands* ops, const rsa_buffers* buf, const rsa_out4& out) {
+    a.q8 = ops->q8; a.k8 = ops->k8; a.v8t = ops->v8t; a.exps = ops->scales; a.exps_stride = l->NB_total;
+    a.out = static_cast<unsigned short*>(out.ptr); a.osb = out.stride_b; a.osh = out.stride_h; a.oss = out.stride_s;
+    a.cols = buf->cols; a.counts = buf->counts; a.R = buf->R; a.comp = buf->comp; a.tpart = buf->tpart;
+    a.mode = MODE_SPARSE; a.H = l->H; a.Sq = l->S; a.Sk = l->S;
+    a.Sq_pad = a.Sk_pad = l->NB_total * RSA_BLOCK;
+    a.NBv = l->NBv; a.NQB = l->NB_total; a.NB_total = l->NB_total;
+    a.kv_valid = l->kv_valid; a.kv_text_valid = l->kv_text_valid;
+    a.q_text_end = l->NBv * RSA_BLOCK + l->q_text_valid;
+    a.q_split = 0; a.kv_split = 0; a.causal = 0;
+    a.out_fp16 = l->dtype == RSA_FP16;
+    no_scores_16(a);
 }
 
 }  // namespace
@@ -857,17 +832,7 @@ extern "C" int rsa_block_sparse_fwd_fp8(const rsa_layout* l, const rsa_fp8_opera
     if (!buf || (l->NBv > 0 && (!buf->cols || !buf->counts))) return RSA_ERR_BAD_ARG;
     if ((buf->R == nullptr) != (buf->comp == nullptr)) return RSA_ERR_BAD_ARG;
     Attn8Args a;
-    a.q8 = ops->q8; a.k8 = ops->k8; a.v8t = ops->v8t; a.exps = ops->scales; a.exps_stride = l->NB_total;
-    a.out = static_cast<unsigned short*>(out.ptr); a.osb = out.stride_b; a.osh = out.stride_h; a.oss = out.stride_s;
-    a.cols = buf->cols; a.counts = buf->counts; a.R = buf->R; a.comp = buf->comp; a.tpart = buf->tpart;
-    a.mode = MODE_SPARSE; a.H = l->H; a.Sq = l->S; a.Sk = l->S;
-    a.Sq_pad = a.Sk_pad = l->NB_total * RSA_BLOCK;
-    a.NBv = l->NBv; a.NQB = l->NB_total; a.NB_total = l->NB_total;
-    a.kv_valid = l->kv_valid; a.kv_text_valid = l->kv_text_valid;
-    a.q_text_end = l->NBv * RSA_BLOCK + l->q_text_valid;
-    a.q_split = 0; a.kv_split = 0; a.causal = 0;
-    a.out_fp16 = l->dtype == RSA_FP16;
-    a.q16 = a.k16 = nullptr; a.qsb = a.qsh = a.qss = a.ksb = a.ksh = a.kss = 0; a.qk_scale = 0.0f;
+    fill_sparse8(a, l, ops, buf, out);
     return launch_attn8(a, l->B * l->H, l->D, buf->tpart_bytes, static_cast<hipStream_t>(stream));
 }
 
@@ -883,19 +848,8 @@ extern "C" int rsa_block_sparse_fwd_fp8pv(const rsa_layout* l, rsa_tensor4 q, rs
     if (!buf || (l->NBv > 0 && (!buf->cols || !buf->counts))) return RSA_ERR_BAD_ARG;
     if ((buf->R == nullptr) != (buf->comp == nullptr)) return RSA_ERR_BAD_ARG;
     Attn8Args a;
-    a.q8 = ops->q8; a.k8 = ops->k8; a.v8t = ops->v8t; a.exps = ops->scales; a.exps_stride = l->NB_total;
-    a.out = static_cast<unsigned short*>(out.ptr); a.osb = out.stride_b; a.osh = out.stride_h; a.oss = out.stride_s;
-    a.cols = buf->cols; a.counts = buf->counts; a.R = buf->R; a.comp = buf->comp; a.tpart = buf->tpart;
-    a.mode = MODE_SPARSE; a.H = l->H; a.Sq = l->S; a.Sk = l->S;
-    a.Sq_pad = a.Sk_pad = l->NB_total * RSA_BLOCK;
-    a.NBv = l->NBv; a.NQB = l->NB_total; a.NB_total = l->NB_total;
-    a.kv_valid = l->kv_valid; a.kv_text_valid = l->kv_text_valid;
-    a.q_text_end = l->NBv * RSA_BLOCK + l->q_text_valid;
-    a.q_split = 0; a.kv_split = 0; a.causal = 0;
-    a.out_fp16 = l->dtype == RSA_FP16;
-    a.q16 = static_cast<const unsigned short*>(q.ptr); a.qsb = q.stride_b; a.qsh = q.stride_h; a.qss = q.stride_s;
-    a.k16 = static_cast<const unsigned short*>(k.ptr); a.ksb = k.stride_b; a.ksh = k.stride_h; a.kss = k.stride_s;
-    a.qk_scale = (float)((1.0 / sqrt((double)l->D)) * 1.44269504 * 8.0);      // sm_scale * log2(e) * PMap<true>::U
+    fill_sparse8(a, l, ops, buf, out);
+    scores_from_16(a, q, k, l->D);
     return launch_attn8(a, l->B * l->H, l->D, buf->tpart_bytes, static_cast<hipStream_t>(stream), l->dtype == RSA_FP16 ? 2 : 1);
 }
 
@@ -963,12 +917,8 @@ static int dense_fwd_fp8(int B, int H, int Sq, int Sk, int D, int dtype, rsa_ten
     a.kv_valid = Sk; a.kv_text_valid = Sk; a.q_text_end = 0;
     a.q_split = q_split; a.kv_split = kv_split; a.causal = causal;
     a.out_fp16 = dtype == RSA_FP16;
-    a.q16 = a.k16 = nullptr; a.qsb = a.qsh = a.qss = a.ksb = a.ksh = a.kss = 0; a.qk_scale = 0.0f;
-    if (pv) {   // scores from the 2-byte q and k themselves (rsa_block_sparse_fwd_fp8pv's operands)
-        a.q16 = static_cast<const unsigned short*>(q.ptr); a.qsb = q.stride_b; a.qsh = q.stride_h; a.qss = q.stride_s;
-        a.k16 = static_cast<const unsigned short*>(k.ptr); a.ksb = k.stride_b; a.ksh = k.stride_h; a.kss = k.stride_s;
-        a.qk_scale = (float)((1.0 / sqrt((double)D)) * 1.44269504 * 8.0);
-    }
+    no_scores_16(a);
+    if (pv) scores_from_16(a, q, k, D);
     return launch_attn8(a, B * H, D, 0, s, pv ? (dtype == RSA_FP16 ? 2 : 1) : 0);
 }
 

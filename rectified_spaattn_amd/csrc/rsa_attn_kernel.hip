@@ -205,20 +205,8 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     s16x8 qf[KS];
     {
         const unsigned short* qp = a.q + (long)b * a.qsb + (long)h * a.qsh + (long)grow * a.qss + 8 * hh;
-        const bool qok = grow < a.Sq;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            uint4 raw = make_uint4(0, 0, 0, 0);
-            if (qok) raw = *reinterpret_cast<const uint4*>(qp + 16 * ks);
-            const unsigned w4[4] = {raw.x, raw.y, raw.z, raw.w};
-            float f[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                f[2 * e] = rsa_to_f32<Tag>((unsigned short)(w4[e] & 0xFFFF)) * a.qk_scale;
-                f[2 * e + 1] = rsa_to_f32<Tag>((unsigned short)(w4[e] >> 16)) * a.qk_scale;
-            }
-            qf[ks] = E::cvt8(f);
-        }
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = rsa_q_frag<Tag>(qp + 16 * ks, grow < a.Sq, a.qk_scale);
     }
 
     // ---------------- LDS-DMA staging ----------------
@@ -246,17 +234,13 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
             const long step = is_v ? vstep : kstep;
             const unsigned vo = is_v ? voffv : voffk;
 #pragma unroll
-            for (int j = 0; j < NPC; ++j)
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                             :: "v"(vo), "s"(tb + j * step), "s"(ld0 + j * 4096) : "memory");
+            for (int j = 0; j < NPC; ++j) rsa_lds_dma16(vo, tb + j * step, ld0 + j * 4096);
         } else {   // the tile runs past the last valid key: rows clamped (their scores are masked)
 #pragma unroll
             for (int j = 0; j < NPC; ++j) {
                 int krow = key_first + j * 4 * RPI + rowl;
                 krow = krow < kv_limit ? krow : kv_limit - 1;
-                const unsigned vo = (unsigned)(((long)krow * ss + gsw * 8) * 2);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                             :: "v"(vo), "s"(base), "s"(ld0 + j * 4096) : "memory");
+                rsa_lds_dma16((unsigned)(((long)krow * ss + gsw * 8) * 2), base, ld0 + j * 4096);
             }
         }
     };
@@ -462,98 +446,26 @@ __global__ __launch_bounds__(256, 2) void bsfwd_kernel(AttnArgs) {
     if constexpr (NEGM) m_run = thr == -INFINITY ? -INFINITY : m_ref;
     const auto swl = __builtin_amdgcn_permlane32_swap(__float_as_uint(l_run), __float_as_uint(l_run), false, false);
     const float l_tot = !NEGM ? lacc[0] : __uint_as_float(swl[0]) + __uint_as_float(swl[1]);   // (lacc: already complete over both lane halves)
-    bool done = false;
     if (a.tsplit > 1 && text) {
         // split-KV partial of a text block: unnormalised O (fp32), m (log2 domain) and l per row; the combine
         // kernel (rsa_attn.hip) merges the tsplit parts
         float* pp = rsa_part_of(a, bh, qblk, tsp, -1, 32 * wv + r, D);
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d0 = 32 * dt + 8 * g + 4 * hh;
-                *reinterpret_cast<float2*>(pp + d0) = make_float2(o[dt][4 * g + 0], o[dt][4 * g + 1]);
-                *reinterpret_cast<float2*>(pp + d0 + 2) = make_float2(o[dt][4 * g + 2], o[dt][4 * g + 3]);
-            }
-        if (hh == 0) *reinterpret_cast<float2*>(pp + D) = make_float2(m_run, l_tot);
-        done = true;
-    }
-    if (!done && (store_r || zero_r)) {
-        float inv = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
-        float Rv = 1.0f;
-        // the compensation values this lane adds (d = 32 dt + 8 g + 4 hh + 0..3) and R: all loads issued here, back to back,
-        // one wait (loaded per (dt, g) inside the store loop each load's latency is exposed in turn: round 4, profiles/r04_k5_w64.md)
+        for (int dt = 0; dt < DT; ++dt) rsa_part_tile(pp, dt, hh, o[dt]);
+        rsa_part_ml(pp, D, hh, m_run, l_tot);
+    } else if (store_r || zero_r) {
+        // the fused O * R / l + comp store (rsa_attn.h); padded text rows (zero_r) are stored as zeros.  Only sparse walks are
+        // rectified, so a text row's compensation values are zeros already
         float4 cv[DT][4];
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) cv[dt][g] = make_float4(0, 0, 0, 0);
-        if (rectify && !zero_r) {
-            const long rowi = (long)bh * a.NBv + qw;
-            const float* cp = a.comp + rowi * D;
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) cv[dt][g] = *reinterpret_cast<const float4*>(cp + 32 * dt + 8 * g + 4 * hh);
-        }
-        if (rectify) Rv = a.R[(long)bh * a.NBv + qw];
-        if (zero_r) inv = 0.0f;
+        float Rv = 1.0f;
+        const long rowi = (long)bh * a.NBv + qw;
+        rsa_comp_row<DT>(cv, rectify ? a.comp + rowi * D : nullptr, hh);
+        if (rectify) Rv = a.R[rowi];
+        const float inv = l_tot > 0.0f && !zero_r ? 1.0f / l_tot : 0.0f;
         const float sc = inv * Rv;
         unsigned short* op = a.out + (long)b * a.osb + (long)h * a.osh + (long)grow * a.oss;
-        // O * sc + comp: one fma rounded to fp32, THEN the conversion to the storage type (what the oracle does).  Left alone,
-        // hipcc folds fma + conversion into v_fma_mixlo_f16 (one rounding, straight to fp16) in one store form and not in the
-        // other; the empty asm keeps the fp32 value, so both store forms write the same bytes.
-        auto fin = [&](float acc, float c) -> float {
-            float rr = __builtin_fmaf(acc, sc, c);
-            asm volatile("" : "+v"(rr));
-            return rr;
-        };
-        if constexpr (WIDE) {
-            // wide stores: lane (r, 0) holds d = 8g .. 8g+3 and lane (r, 1) d = 8g+4 .. 8g+7 of a 32-wide d tile; one
-            // v_permlane32_swap per packed register pair regroups two g's so that each lane owns 8 consecutive d:
-            // 8 stores of 16 B per lane instead of 16 of 8 B (the store tail of a row-per-lane epilogue is issue-bound)
 #pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-#pragma unroll
-                for (int gp = 0; gp < 2; ++gp) {
-                    uint2 pk[2];
-#pragma unroll
-                    for (int gi = 0; gi < 2; ++gi) {
-                        const int g = 2 * gp + gi;
-                        const float4 c4 = cv[dt][g];
-                        const float v0 = fin(o[dt][4 * g + 0], c4.x);
-                        const float v1 = fin(o[dt][4 * g + 1], c4.y);
-                        const float v2 = fin(o[dt][4 * g + 2], c4.z);
-                        const float v3 = fin(o[dt][4 * g + 3], c4.w);
-                        pk[gi].x = (unsigned)E::from_f32(v0) | ((unsigned)E::from_f32(v1) << 16);
-                        pk[gi].y = (unsigned)E::from_f32(v2) | ((unsigned)E::from_f32(v3) << 16);
-                    }
-                    // X' = [X.lower, Y.lower], Y' = [X.upper, Y.upper]  (X = pk[0], Y = pk[1])
-                    const auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
-                    const auto sy = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
-                    uint4 w4;
-                    w4.x = sx[0]; w4.y = sy[0]; w4.z = sx[1]; w4.w = sy[1];
-                    *reinterpret_cast<uint4*>(op + 32 * dt + 8 * (2 * gp + hh)) = w4;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d0 = 32 * dt + 8 * g + 4 * hh;
-                    const float4 c4 = cv[dt][g];
-                    const float v0 = fin(o[dt][4 * g + 0], c4.x);
-                    const float v1 = fin(o[dt][4 * g + 1], c4.y);
-                    const float v2 = fin(o[dt][4 * g + 2], c4.z);
-                    const float v3 = fin(o[dt][4 * g + 3], c4.w);
-                    uint2 pk;
-                    pk.x = (unsigned)E::from_f32(v0) | ((unsigned)E::from_f32(v1) << 16);
-                    pk.y = (unsigned)E::from_f32(v2) | ((unsigned)E::from_f32(v3) << 16);
-                    *reinterpret_cast<uint2*>(op + d0) = pk;
-                }
-            }
-        }
+        for (int dt = 0; dt < DT; ++dt) rsa_out_tile<Tag, WIDE>(op, dt, hh, o[dt], sc, cv[dt]);
     }
 }
 

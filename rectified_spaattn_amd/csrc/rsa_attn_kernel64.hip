@@ -133,7 +133,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     constexpr int DT = D / 32;
     constexpr int HALF = 32 * D * 2;        // bytes of a 32-key half-tile
     constexpr int VRING = 4 * HALF;
-    using E = Elem<Tag>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned short* lds_list = reinterpret_cast<unsigned short*>(lds + 8 * HALF);
     __shared__ int redo_flag;               // optimistic static reference (below): a wave whose walk overflowed asks the workgroup for a second pass
@@ -258,16 +257,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     {
         auto load_frag = [&](int x, int ks) -> s16x8 {
             const unsigned short* qp = a.q + (long)b * a.qsb + (long)h * a.qsh + (long)grow[x] * a.qss + 8 * hh;
-            uint4 raw = make_uint4(0, 0, 0, 0);
-            if (grow[x] < a.Sq) raw = *reinterpret_cast<const uint4*>(qp + 16 * ks);
-            const unsigned w4[4] = {raw.x, raw.y, raw.z, raw.w};
-            float f[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                f[2 * e] = rsa_to_f32<Tag>((unsigned short)(w4[e] & 0xFFFF)) * a.qk_scale;
-                f[2 * e + 1] = rsa_to_f32<Tag>((unsigned short)(w4[e] >> 16)) * a.qk_scale;
-            }
-            return E::cvt8(f);
+            return rsa_q_frag<Tag>(qp + 16 * ks, grow[x] < a.Sq, a.qk_scale);
         };
 #define RSA_QF(HH, KK) do { if constexpr (KK < KS) k5w_qwrite<HH, KK, D>(load_frag(HH, KK)); } while (0)
         RSA_QF(0, 0); RSA_QF(0, 1); RSA_QF(0, 2); RSA_QF(0, 3); RSA_QF(0, 4); RSA_QF(0, 5); RSA_QF(0, 6); RSA_QF(0, 7);
@@ -276,17 +266,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     }
 
     // ---------------- LDS-DMA staging ----------------
-    // (hipcc does 64-bit address arithmetic on the vector unit even when it is wave-uniform and then hands the VGPR pair to an
-    // "s" operand as is: every base that reaches the staging asm is made scalar explicitly, half by half)
-    auto uni64 = [](const unsigned char* p) -> const unsigned char* {
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)p);
-        const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)p >> 32));
-        return reinterpret_cast<const unsigned char*>(((unsigned long)hi << 32) | lo);
-    };
     int hkv = h;                            // the K/V head (a pair's two heads share it: kv_group is even there)
     if constexpr (GQA != RSA_GQA_NONE) hkv = h / a.kv_group;
-    const unsigned char* kbase = uni64(reinterpret_cast<const unsigned char*>(a.k + (long)b * a.ksb + (long)hkv * a.ksh));
-    const unsigned char* vbase = uni64(reinterpret_cast<const unsigned char*>(a.v + (long)b * a.vsb + (long)hkv * a.vsh));
+    // (every base that reaches the staging asm is made scalar explicitly: rsa_common.h)
+    const unsigned char* kbase = rsa_uniform64(a.k + (long)b * a.ksb + (long)hkv * a.ksh);
+    const unsigned char* vbase = rsa_uniform64(a.v + (long)b * a.vsb + (long)hkv * a.vsh);
     // A 32-key half-tile = NPIECE one-KiB pieces of RPP rows (8 x 4 rows at head dim 128, 4 x 8 rows at 64); wave w moves pieces
     // NW j + w, j = 0 .. NPW - 1.  The XOR swizzle of a row's source chunk (rsa_attn.h::tile_off) depends on the row: at head dim 128
     // on (row & 3) and ((row >> 2) & 3) = piece & 3 -- two per-lane offsets (even / odd j) with two waves, one with four --, at head
@@ -325,9 +309,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
         for (int j = 0; j < NPW; ++j) {
             int krow_ = key_first + RPP * NW * j + rowl;
             krow_ = krow_ < kv_limit ? krow_ : kv_limit - 1;
-            const unsigned vo = (unsigned)krow_ * rowb + ((j & 1) ? gsw1 : gsw0) * 16;
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                         :: "v"(vo), "s"(base), "s"(ld0 + j * NW * 1024) : "memory");
+            rsa_lds_dma16((unsigned)krow_ * rowb + ((j & 1) ? gsw1 : gsw0) * 16, base, ld0 + j * NW * 1024);
         }
     };
 
@@ -541,24 +523,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     }
     const bool partial = (e.mode == MODE_SPARSE && e.tsplit > 1 && qblk2 >= e.NBv) || tail2 >= 0;
     const bool rectify = e.mode == MODE_SPARSE && qblk2 < e.NBv && e.R != nullptr && tail2 < 0;   // (a tail piece is rectified by its combine pass)
-    // the compensation row of this query block, the 64 values this lane adds (d = 32 dt + 8 g + 4 hh + 0..3), and R: ALL loads
-    // issued here, back to back, one wait -- per (dt, g) inside the store loop each load's latency (L2 / HBM: 1-2 k cycles)
-    // is exposed in turn: 30 k of a wave's 535 k cycles with nothing else on the SIMD to cover it (stamps: profiles/r04_k5_w64.md)
+    // the compensation row of this query block (all loads issued here, ahead of both halves: rsa_attn.h) and R
     float4 cv[DT][4];
     float Rv = 1.0f;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) cv[dt][g] = make_float4(0, 0, 0, 0);
-    if (rectify) {
-        const long rowi = (long)bh2 * e.NBv + qblk2;
-        const float* cp = e.comp + rowi * D;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) cv[dt][g] = *reinterpret_cast<const float4*>(cp + 32 * dt + 8 * g + 4 * hh);
-        Rv = e.R[rowi];
-    }
+    const long rowi = (long)bh2 * e.NBv + qblk2;
+    rsa_comp_row<DT>(cv, rectify ? e.comp + rowi * D : nullptr, hh);
+    if (rectify) Rv = e.R[rowi];
     auto finish_half = [&](auto HX) {
         constexpr int x = decltype(HX)::value;
         const int grow2 = qblk2 * RW + 64 * wq + 32 * x + r;
@@ -569,17 +539,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
             // split-KV partial of a text block or of a tail piece: unnormalised O (fp32), m (log2 domain) and l per row (merged by
             // text_combine_kernel / tail_combine_kernel, rsa_attn.hip)
             float* pp = rsa_part_of(e, bh2, qblk2, tsp2, tail2, 64 * wq + 32 * x + r, D);
-            auto put = [&](int dt, const f32x16& o) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d0 = 32 * dt + 8 * g + 4 * hh;
-                    *reinterpret_cast<float2*>(pp + d0) = make_float2(o[4 * g + 0], o[4 * g + 1]);
-                    *reinterpret_cast<float2*>(pp + d0 + 2) = make_float2(o[4 * g + 2], o[4 * g + 3]);
-                }
-            };
+            auto put = [&](int dt, const f32x16& o) { rsa_part_tile(pp, dt, hh, o); };
             put(0, k5w_oread<x, 0, D>()); put(1, k5w_oread<x, 1, D>());
             if constexpr (DT == 4) { put(2, k5w_oread<x, 2, D>()); put(3, k5w_oread<x, 3, D>()); }
-            if (hh == 0) *reinterpret_cast<float2*>(pp + D) = make_float2(mrun, l_tot);
+            rsa_part_ml(pp, D, hh, mrun, l_tot);
             return;
         }
         // rows that are stored / written as zeros (padded text rows), from the row index (not kept live across the main loop)
@@ -591,53 +554,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
         if (zr) inv = 0.0f;
         const float sc = inv * Rv;
         unsigned short* op = e.out + (long)b2 * e.osb + (long)h2 * e.osh + (long)grow2 * e.oss;
-        // O * sc + comp: one fma rounded to fp32, THEN the conversion to the storage type (what the oracle does); the empty asm
-        // keeps hipcc from folding fma + conversion into v_fma_mixlo_f16 in one store form and not in the other
-        auto fin = [&](float acc, float c) -> float {
-            float rr = __builtin_fmaf(acc, sc, c);
-            asm volatile("" : "+v"(rr));
-            return rr;
-        };
-        auto put = [&](int dt, const f32x16& o) {
-            if constexpr (WIDE) {
-#pragma unroll
-                for (int gp = 0; gp < 2; ++gp) {
-                    uint2 pk[2];
-#pragma unroll
-                    for (int gi = 0; gi < 2; ++gi) {
-                        const int g = 2 * gp + gi;
-                        float4 c4 = cv[dt][g];
-                        if (zr) c4 = make_float4(0, 0, 0, 0);
-                        const float v0 = fin(o[4 * g + 0], c4.x);
-                        const float v1 = fin(o[4 * g + 1], c4.y);
-                        const float v2 = fin(o[4 * g + 2], c4.z);
-                        const float v3 = fin(o[4 * g + 3], c4.w);
-                        pk[gi].x = (unsigned)E::from_f32(v0) | ((unsigned)E::from_f32(v1) << 16);
-                        pk[gi].y = (unsigned)E::from_f32(v2) | ((unsigned)E::from_f32(v3) << 16);
-                    }
-                    const auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
-                    const auto sy = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
-                    uint4 w4;
-                    w4.x = sx[0]; w4.y = sy[0]; w4.z = sx[1]; w4.w = sy[1];
-                    *reinterpret_cast<uint4*>(op + 32 * dt + 8 * (2 * gp + hh)) = w4;
-                }
-            } else {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d0 = 32 * dt + 8 * g + 4 * hh;
-                    float4 c4 = cv[dt][g];
-                    if (zr) c4 = make_float4(0, 0, 0, 0);
-                    const float v0 = fin(o[4 * g + 0], c4.x);
-                    const float v1 = fin(o[4 * g + 1], c4.y);
-                    const float v2 = fin(o[4 * g + 2], c4.z);
-                    const float v3 = fin(o[4 * g + 3], c4.w);
-                    uint2 pk;
-                    pk.x = (unsigned)E::from_f32(v0) | ((unsigned)E::from_f32(v1) << 16);
-                    pk.y = (unsigned)E::from_f32(v2) | ((unsigned)E::from_f32(v3) << 16);
-                    *reinterpret_cast<uint2*>(op + d0) = pk;
-                }
-            }
-        };
+        // (a padded row is a text row, and only sparse walks are rectified: its compensation values are zeros already)
+        auto put = [&](int dt, const f32x16& o) { rsa_out_tile<Tag, WIDE>(op, dt, hh, o, sc, cv[dt]); };
         put(0, k5w_oread<x, 0, D>()); put(1, k5w_oread<x, 1, D>());
         if constexpr (DT == 4) { put(2, k5w_oread<x, 2, D>()); put(3, k5w_oread<x, 3, D>()); }
     };

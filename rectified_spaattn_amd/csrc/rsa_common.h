@@ -64,6 +64,21 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// LDS-DMA staging (K2's score tiles, the K/V tiles of every K5 kernel).
+// hipcc does 64-bit address arithmetic on the vector unit even when it is wave-uniform and then hands the VGPR pair to an "s"
+// operand as is: a base that reaches the staging asm from such arithmetic is made scalar explicitly, half by half.
+__device__ __forceinline__ const unsigned char* rsa_uniform64(const void* p) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)p);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)p >> 32));
+    return reinterpret_cast<const unsigned char*>(((unsigned long)hi << 32) | lo);
+}
+// One 1-KiB piece: every lane's 16 bytes at sbase + voff -> LDS byte address lds_dst + 16 * lane (lane-linear image: a bank swizzle
+// goes into the lane's SOURCE offset).  Issued from inline asm so that hipcc neither counts nor drains it: the caller waits with
+// an s_waitcnt vmcnt of its own.
+__device__ __forceinline__ void rsa_lds_dma16(unsigned voff, const unsigned char* sbase, unsigned lds_dst) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
+}
+
 // Split-KV partials (tpart, tail_part): piece after piece of 128 rows, a row = D unnormalised O values (fp32), then the running
 // maximum m (log2 domain) and the row sum l.  Offset of row `row` of piece `piece`, in floats:
 __host__ __device__ __forceinline__ long rsa_part_row(long piece, int row, int D) { return (piece * RSA_BLOCK + row) * (D + 2); }

@@ -317,10 +317,7 @@ __device__ __forceinline__ void pooled_scores_tile_dma(const ScoreArgs& a, int b
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float*)smem;
     auto swz = [](int row) -> int { return DK == 32 ? (row >> 1) & 7 : (row >> 2) & 3; };
     // ---- staging: wave w moves operand w; piece p = rows RPP p .. of the tile, lane (rr = lane / LPR, c = lane % LPR) ----
-    const float* opbase = (wv == 0 ? a.qbar : wv == 1 ? a.kbar : wv == 2 ? a.aq : a.ak) + (long)bh * NBv * D;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)opbase);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)opbase >> 32));
-    const unsigned char* base = reinterpret_cast<const unsigned char*>(((unsigned long)hi << 32) | lo);
+    const unsigned char* base = rsa_uniform64((wv == 0 ? a.qbar : wv == 1 ? a.kbar : wv == 2 ? a.aq : a.ak) + (long)bh * NBv * D);
     const int row0 = (wv & 1) ? j0 : i0;                          // q / aq rows follow i, k / ak rows follow j
     const int rr = lane / LPR, c = lane % LPR;
     unsigned voff[NPC];
@@ -333,9 +330,7 @@ __device__ __forceinline__ void pooled_scores_tile_dma(const ScoreArgs& a, int b
     auto stage = [&](int d0, int buf) {
         const unsigned dst = lds0 + buf * BUFB + wv * OPB;
 #pragma unroll
-        for (int p = 0; p < NPC; ++p)
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                         :: "v"(voff[p] + (unsigned)(d0 * 4)), "s"(base), "s"(dst + p * 1024) : "memory");
+        for (int p = 0; p < NPC; ++p) rsa_lds_dma16(voff[p] + (unsigned)(d0 * 4), base, dst + p * 1024);
     };
     const bool live = i0 + 32 * wi < NBv && j0 + 32 * wj < NBv;   // wave-uniform: a dead wave only stages
     k2_f32x16 s, eq, ek;

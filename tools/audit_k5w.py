@@ -1,6 +1,6 @@
 import re,sys
 lines=open(sys.argv[1]).read().split('\n')
-kname=sys.argv[2] if len(sys.argv)>2 else '_Z14bsfwd64_kernelI8bf16_tagLb1ELi2ELi128EEv8AttnArgs'   # bsfwd64_kernel<bf16_tag, true, 2, 128>
+kname=sys.argv[2] if len(sys.argv)>2 else '_Z14bsfwd64_kernelI8bf16_tagLb1ELi2ELi128ELb0ELi0EEv8AttnArgs'   # bsfwd64_kernel<bf16_tag, true, 2, 128, false, 0>
 start=[i for i,l in enumerate(lines) if l.startswith(kname+':')][0]
 end=[i for i,l in enumerate(lines) if i>start and l.strip().startswith('.end_amdhsa_kernel')][0]
 inasm=False; cnt={}; asm_idx=0; asm_first={}
