@@ -315,6 +315,42 @@ int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int d
                      int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores,
                      void* stream);
 
+/* ---- block-sparse DECODE attention: a few query rows over a (paged) K/V cache (found by symbol: the header version stays 6.1;
+ * DESIGN.md section 5.12).  q [B, H, Sq, D] with Sq <= block (ONE query block), k / v [B, Hkv, Sk, D], H a multiple of Hkv, query
+ * head h reads K/V head h / (H / Hkv); Hl list heads per batch item, Hl in {1, Hkv, H}; cols [B * Hl, NK] / counts [B * Hl] as
+ * rsa_block_mask_to_lists or rsa_block_select write them for NQ = 1.  A unit = the H / max(Hl, Hkv) query heads that share a K/V
+ * head and a list row; its Sq * H / max(Hl, Hkv) rows must not exceed 64 (four 16-row MFMA tiles: RSA_ERR_UNSUPPORTED beyond).
+ * len_b = kv_len_dev[b] clamped into [0, Sk] (DEVICE int32, B values, never read on the host) or, with kv_len_dev NULL, kv_valid.
+ *   visible   row r of (b, h) sees key j iff block j / block is in the list row of (b, list head of h), j < len_b,
+ *             j < NK * block, and with causal j <= r + len_b - Sq (bottom-right aligned; both block sizes).  A row without a
+ *             visible key is 0 and its log-sum-exp -inf.
+ *   cache     keys at or beyond len_b may hold anything (NaN, Inf): they are never multiplied.  block_table NULL: k / v are the
+ *             [B, Hkv, Sk, D] views.  Otherwise block_table is DEVICE int32 [B, >= NK] with row stride table_stride_b, k / v are
+ *             page pools [num_pages, Hkv, block, D] (stride_b = the page stride), Sk = the logical capacity, and key j of batch
+ *             item b is row j % block of page block_table[b][j / block].  The table is read only for listed blocks that hold a
+ *             key below len_b; a listed block whose page lies outside [0, num_pages), like a list entry outside [0, NK),
+ *             contributes no key and is not read.
+ *   numerics  those of the 2-byte rsa_block_sparse_plain_fwd: Q * (float)(sm_scale * 1.44269504) rounded to the input type,
+ *             log2-domain scores, P rounded to the input type for P.V, fp32 accumulation, one division and one conversion.
+ *   splits    one workgroup per (unit, split); split s takes list entries [s C, (s + 1) C), C = blocks_per_split (0: the
+ *             library's choice, min(8, NK): measured, profiles/decode_perf.txt).  The grid's split extent is ceil(NK / C);
+ *             workgroups past a list's end leave at once.  ws holds the partials (fp32 O, m, l per unit, split and row):
+ *             rsa_block_sparse_decode_bytes(...) bytes, 16-byte aligned.  A second small launch merges them in ascending s.  The
+ *             result may depend on blocks_per_split through the summation order; for one value two calls give the same bytes
+ *             (no atomics on floats).
+ *   outputs   out [B, H, Sq, D] through any strides that are multiples of 4 elements (pointer 8-byte aligned); lse NULL or fp32
+ *             [B, H, Sq] contiguous: ln sum_j exp(sm_scale q . k_j) over the visible keys, (m + log2 l) ln 2.
+ * Non-positive sizes, Hkv not dividing H, Hl not in {1, Hkv, H}, NK outside 1 .. min(ceil(Sk / block), 8192), kv_valid outside
+ * [0, Sk], Sq > block, a NULL or misaligned pointer, a negative stride, a table with num_pages <= 0, a negative
+ * blocks_per_split: RSA_ERR_BAD_ARG; D outside {64, 128}, block outside {64, 128}, an unknown dtype, more than 64 rows per unit:
+ * RSA_ERR_UNSUPPORTED; ws_bytes too small: RSA_ERR_WORKSPACE.  Every check runs before the first HIP call. */
+int rsa_block_sparse_decode_bytes(int B, int H, int Hkv, int Hl, int Sq, int D, int NK, int blocks_per_split, size_t* bytes);
+int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                            const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
+                            rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* cols,
+                            const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
+                            void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

@@ -9,7 +9,8 @@ Module names mirror the reference package `rectified_spaattn`:
     rectified_wan22_attn      RectifiedWan{TI2V,T2V,I2V}SpaAttnProcessor2_0
     rectified_cogvideo_attn   rectified_block_sparse_attention, RectifiedCogVideoXVideoSpaAttnProcessor2_0
     attn_processor            get_attn_processors, set_attn_processor
-    block_sparse              block_sparse_attention over a caller's block mask and select_blocks, the top-k block selection
+    block_sparse              block_sparse_attention over a caller's block mask, block_sparse_decode (its decode half: few query rows over a
+                              (paged) K/V cache, with log-sum-exp) and select_blocks, the top-k block selection
                               per K/V head that makes one (both also exported here), the mask <-> list conversions; the four rectified_*_attn modules above also carry the reference's
                               _build_block_index_with_importance_optimized and _triton_block_sparse_attention_onehot
     teacache                  TeaCache step-skipping controller (scripts' teacache_forward bookkeeping), rel_l1_distance
@@ -60,6 +61,17 @@ def select_blocks(q, k, top_k, *, block_size=128, kv_len=None, causal=False, kee
     return block_sparse.select_blocks(q, k, top_k, block_size=block_size, kv_len=kv_len, causal=causal, keep_first=keep_first,
                                       keep_local=keep_local, mask_heads=mask_heads, return_scores=return_scores,
                                       as_lists=as_lists)
+
+
+def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
+                        return_lse=False, blocks_per_split=None):
+    """Block-sparse decode attention: q [B,H,Sq,D] with Sq <= block over a K/V cache [B,Hkv,Sk,D], or over page pools
+    [P,Hkv,block,D] behind block_table int32 [B,NKt]; block_mask bool / uint8 [B|1, Hl, 1, NK] or select_blocks' lists;
+    return_lse=True adds the fp32 log-sum-exp [B,H,Sq].  See rectified_spaattn_amd.block_sparse.block_sparse_decode."""
+    from . import block_sparse
+    return block_sparse.block_sparse_decode(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
+                                            causal=causal, block_table=block_table, return_lse=return_lse,
+                                            blocks_per_split=blocks_per_split)
 
 
 def clear_buffer_cache() -> None:

@@ -137,6 +137,11 @@ def lib():
     L.rsa_block_select_bytes.restype = i32
     L.rsa_block_select.argtypes = [i32] * 11 + [RsaTensor4, RsaTensor4, vp] + [i32] * 5 + [vp, sz, vp, vp, vp, vp, vp]
     L.rsa_block_select.restype = i32
+    L.rsa_block_sparse_decode_bytes.argtypes = [i32] * 8 + [P(sz)]
+    L.rsa_block_sparse_decode_bytes.restype = i32
+    L.rsa_block_sparse_decode.argtypes = ([i32] * 10 + [vp, i32, i32, ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, i64,
+                                          i32, vp, vp, i32, vp, sz, RsaOut4, vp, vp])
+    L.rsa_block_sparse_decode.restype = i32
     L.rsa_select_from_mask.argtypes = [P(RsaLayout), vp, i64, i64, i64, P(RsaBuffers), vp]
     L.rsa_select_from_mask_ex.argtypes = [P(RsaLayoutEx), vp, i64, i64, i64, P(RsaBuffers), vp]
     L.rsa_rectified_attention_masked.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, vp, i64, i64, i64, vp, sz,
@@ -223,6 +228,7 @@ EXPORTED = ("rsa_version", "rsa_abi_check", "rsa_buffer_bytes", "rsa_carve_works
             "rsa_select_mask_ex", "rsa_compensation_ex", "rsa_block_sparse_fwd_ex", "rsa_rectified_attention_ex", "rsa_estimate_pr_gain_ex",
             "rsa_block_mask_to_lists", "rsa_lists_to_block_mask", "rsa_block_sparse_plain_fwd", "rsa_block_sparse_ranged_fwd",
             "rsa_block_sparse_gqa_fwd", "rsa_block_select_bytes", "rsa_block_select",
+            "rsa_block_sparse_decode_bytes", "rsa_block_sparse_decode",
             "rsa_select_from_mask", "rsa_select_from_mask_ex", "rsa_rectified_attention_masked", "rsa_rectified_attention_masked_ex")
 
 

@@ -9,6 +9,8 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              range per query row on top of the mask (rsa_block_sparse_ranged_fwd, one launch per batch)
                              k / v may hold fewer heads than q (GQA / MQA: query head h reads K/V head h // (H // Hkv)) and
                              the mask one row per K/V head: rsa_block_sparse_gqa_fwd, no repeated K/V and no repeated lists
+    block_sparse_decode      the decode half: a few query rows (one query block) over a contiguous or PAGED K/V cache, split over
+                             the kept list and merged, with an optional log-sum-exp (rsa_block_sparse_decode, kernels of its own)
     select_blocks            a selection of the library's own for that call: pooled scores and a plain top-k per K/V head, with
                              the call's kv_len and causal alignment, written as lists on the device (rsa_block_select)
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
@@ -451,6 +453,150 @@ def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: i
                                       scores.data_ptr() if scores is not None else None, _core._stream()), "rsa_block_select")
     sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
     return (sel, scores) if return_scores else sel
+
+
+DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_decode.hip)
+
+
+def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask, *, kv_len=None,
+                        sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, block_table=None,
+                        return_lse: bool = False, blocks_per_split: Optional[int] = None):
+    """Block-sparse attention of a few query rows (decode: one token, or a handful of speculative ones) over a long K/V cache:
+    block_sparse_attention's result at one query block, from kernels built for it.
+    q [B,H,Sq,D] with Sq <= block_size; k / v [B,Hkv,Sk,D], H % Hkv == 0, query head h reads K/V head h // (H // Hkv); any strides
+    with a contiguous head dim and 16-byte aligned rows (a cache is never copied: other strides are refused); bf16 / fp16; head
+    dim 64 or 128 (16 / 32 are refused: padding a cache would copy it); block_size 64 or 128.
+    block_mask: bool / uint8 [B|1, Hl, 1, NK], Hl in {1, Hkv, H}, NK <= min(ceil(Sk/block), 8192) -- what
+    select_blocks(q, k, top_k, causal=True, kv_len=...) returns for Sq <= block -- or the dict select_blocks(..., as_lists=True)
+    returns with one query block (Hl = cols.shape[0] // B; used as it is, no conversion launch).
+    A unit is the H // max(Hl, Hkv) query heads that share a K/V head and a list row; its Sq * H // max(Hl, Hkv) rows share every
+    K / V block read, and more than 64 of them are refused (use block_sparse_attention).
+    Row r of (b, h) sees key j iff mask[b, hl(h), 0, j // block] and j < kv_len[b] and j < NK * block and, with causal=True,
+    j <= r + kv_len[b] - Sq (bottom-right aligned; both block sizes).  A row without a visible key is 0, its log-sum-exp -inf.
+    kv_len: None (= Sk), an int, one value per batch item, or an int32 / int64 device tensor of 1 or B values, which is clamped
+    into [0, Sk] on the device and never read on the host.  Keys at or beyond kv_len[b] may hold anything, NaN included.
+    block_table: int32 device tensor [B, NKt], NKt >= NK; k / v are then page pools [P, Hkv, block_size, D], the capacity is
+    Sk = NKt * block_size and key j of batch item b is row j % block of page block_table[b, j // block].  The table is read only
+    for kept blocks that hold a key below kv_len[b]; a kept block whose entry lies outside [0, P) contributes no key, as if its
+    mask bit were clear (and so does an entry of a caller's lists outside [0, NK)).
+    return_lse=True: (out, lse), lse fp32 [B,H,Sq] = ln sum over the visible keys of exp(sm_scale q . k).
+    blocks_per_split: kept-list entries per workgroup; None = the library's choice, min(8, NK) (measured: DESIGN.md 5.12).  The result may
+    depend on it through the summation order of the merge; for one value two calls give the same bytes.  Asynchronous on the
+    current stream, no host synchronisation, capturable in a HIP graph (the workspace comes from torch inside the capture)."""
+    if block_size not in _lib.BLOCKS:
+        raise NotImplementedError(f"block-sparse decode on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
+    blk = int(block_size)
+    if blocks_per_split is not None and (not isinstance(blocks_per_split, int) or isinstance(blocks_per_split, bool)
+                                         or blocks_per_split < 1):
+        raise ValueError(f"blocks_per_split: None or an int >= 1, got {blocks_per_split!r}")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("q, k, v: [B, H, S, D] tensors")
+    B, H, Sq, D = q.shape
+    Hkv = k.shape[1]
+    if v.shape[1] != Hkv:
+        raise ValueError(f"k has Hkv = {Hkv} heads, v {v.shape[1]}: k and v must hold the same K/V heads")
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h reads K/V head h // (H // Hkv))")
+    paged = block_table is not None
+    if paged:
+        if (not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
+                or block_table.shape[0] != B or block_table.shape[1] < 1):
+            raise ValueError(f"block_table: an int32 tensor [{B}, NKt], got {getattr(block_table, 'dtype', type(block_table))} "
+                             f"{tuple(getattr(block_table, 'shape', ()))}")
+        if k.shape != v.shape or k.shape[2] != blk or k.shape[3] != D:
+            raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}: with a block_table they are "
+                             f"page pools [P, Hkv, {blk}, {D}]")
+        Sk = block_table.shape[1] * blk
+    else:
+        if k.shape != v.shape or k.shape[0] != B or k.shape[3] != D:
+            raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+        Sk = k.shape[2]
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"q, k, v: one dtype, bfloat16 or float16 (got {q.dtype}, {k.dtype}, {v.dtype})")
+    if D in (16, 32):
+        raise NotImplementedError(f"head dim {D}: block_sparse_decode serves 64 and 128 (padding a cache would copy it)")
+    if D not in (64, 128):
+        raise ValueError(f"head dim {D}: 64 or 128")
+    if Sq <= 0 or Sk <= 0:
+        raise ValueError(f"empty operands (Sq = {Sq}, Sk = {Sk})")
+    if Sq > blk:
+        raise ValueError(f"Sq = {Sq}: block_sparse_decode serves one query block, Sq <= block_size = {blk}")
+    NKmax = min(-(-Sk // blk), MAX_KEY_BLOCKS)
+    if isinstance(block_mask, dict):
+        cols, counts = block_mask.get("cols"), block_mask.get("counts")
+        if (not isinstance(cols, torch.Tensor) or not isinstance(counts, torch.Tensor) or cols.dtype != torch.int32
+                or counts.dtype != torch.int32 or cols.dim() != 3 or cols.shape[1] != 1 or cols.shape[0] % B
+                or counts.numel() != cols.shape[0] or not cols.is_contiguous() or not counts.is_contiguous()):
+            raise ValueError("block_mask: a bool / uint8 tensor, or the lists of one query block: cols int32 [B * Hl, 1, NK] and "
+                             "counts int32 [B * Hl, 1], contiguous (select_blocks(..., as_lists=True))")
+        Hl, NK = cols.shape[0] // B, cols.shape[2]
+        mask = None
+    else:
+        mask = block_mask
+        if not isinstance(mask, torch.Tensor) or mask.dim() != 4 or mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"block_mask: a 4-d bool or uint8 tensor, got {getattr(mask, 'dtype', type(mask))} "
+                             f"{tuple(getattr(mask, 'shape', ()))}")
+        Hl, NK = mask.shape[1], mask.shape[3]
+        if mask.shape[0] not in (1, B) or mask.shape[2] != 1:
+            raise ValueError(f"block_mask {tuple(mask.shape)}: expected [{B}|1, Hl, 1, 1..{NKmax}] for block {blk} (one query block)")
+    if Hl not in (1, Hkv, H):
+        raise ValueError(f"block_mask: a head axis of {H} (per query head), Hkv = {Hkv} (per K/V head) or 1, got {Hl}")
+    if not 1 <= NK <= NKmax:
+        raise ValueError(f"block_mask: {NK} key blocks, expected 1..{NKmax} for block {blk} (at most {MAX_KEY_BLOCKS} key blocks)")
+    rows = Sq * (H // max(Hl, Hkv))
+    if rows > DECODE_MAX_ROWS:
+        raise NotImplementedError(f"Sq * H // max(Hl, Hkv) = {rows} rows share a K/V head and a list row: block_sparse_decode "
+                                  f"serves at most {DECODE_MAX_ROWS}; use block_sparse_attention")
+    on_device = isinstance(kv_len, torch.Tensor) and kv_len.is_cuda      # (then it is read on the device only)
+    if on_device:
+        if kv_len.numel() not in (1, B) or kv_len.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"kv_len: an int32 / int64 tensor of 1 or {B} values, got {kv_len.dtype} {tuple(kv_len.shape)}")
+        lens = None
+    else:
+        lens = _kv_lens(kv_len, B, Sk)
+    for name, t in (("k", k), ("v", v)):
+        if t.stride(-1) != 1 or any(st % 8 for st in t.stride()[:-1]) or any(st < 0 for st in t.stride()):
+            raise ValueError(f"{name}: a contiguous head dim and strides that are multiples of 8 elements (a cache is not copied), "
+                             f"got strides {tuple(t.stride())}")
+    _core._require_device(q, k, v)
+    if k.data_ptr() % 16 or v.data_ptr() % 16:
+        raise ValueError("k, v: 16-byte aligned (a cache is not copied)")
+    dev = q.device
+    if on_device:
+        kv_dev, kv_valid = kv_len.to(dev).reshape(-1).clamp(0, Sk).to(torch.int32).expand(B).contiguous(), Sk
+    elif len(set(lens)) == 1:
+        kv_dev, kv_valid = None, lens[0]
+    else:
+        kv_dev, kv_valid = torch.tensor(lens, dtype=torch.int32, device=dev), Sk
+    scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
+    if mask is not None:
+        lists = block_mask_to_lists(mask.to(dev) if mask.device != dev else mask, B, Hl)
+        cols, counts = lists["cols"], lists["counts"]
+    else:
+        _core._require_device(cols, counts)
+    table = None
+    if paged:
+        _core._require_device(block_table)
+        table = block_table if block_table.stride(1) == 1 else block_table.contiguous()
+    L = _lib.lib()
+    q = _core._as_bhsd(q)
+    bps = 0 if blocks_per_split is None else int(blocks_per_split)
+    need = ctypes.c_size_t(0)
+    _lib.check(L.rsa_block_sparse_decode_bytes(B, H, Hkv, Hl, Sq, D, NK, bps, ctypes.byref(need)), "rsa_block_sparse_decode_bytes")
+    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+    out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=dev)
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+    with torch.cuda.device(dev):
+        _lib.check(L.rsa_block_sparse_decode(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK,
+                                             kv_dev.data_ptr() if kv_dev is not None else None, kv_valid, int(bool(causal)), scale,
+                                             _core._t4(q), _core._t4(k), _core._t4(v),
+                                             table.data_ptr() if table is not None else None,
+                                             table.stride(0) if table is not None else 0, k.shape[0] if paged else 0,
+                                             cols.data_ptr(), counts.data_ptr(), bps, ws.data_ptr(), need.value,
+                                             RsaOut4(out.data_ptr(), out.stride(0), out.stride(1), out.stride(2)),
+                                             lse.data_ptr() if lse is not None else None, _core._stream()),
+                   "rsa_block_sparse_decode")
+    return (out, lse) if return_lse else out
 
 
 def build_block_index(query: torch.Tensor, key: torch.Tensor, top_k: int, block_size_M: int = 128, block_size_N: int = 128,

@@ -1,0 +1,489 @@
+// Block-sparse decode attention: a few query rows over a (paged) K/V cache (include/rsa.h: rsa_block_sparse_decode_bytes,
+// rsa_block_sparse_decode).  Two kernels, plain HIP C++ for wave64:
+//
+//   decode_split_kernel   one 4-wave workgroup per (unit, split).  A unit = the query heads that share a K/V head AND a list row:
+//                         its rows (head-major: row = head_in_unit * Sq + query row, at most 64) are the columns of 16x16x32 MFMA
+//                         tiles.  Split s walks entries [s C, (s + 1) C) of the unit's kept list in chunks of 32 keys; chunk c of
+//                         the slice goes to wave c & 3, so the four waves share the keys of every kept block.  Per chunk and wave:
+//                             S^T[key][row]  = K . Q^T        A = K straight from global memory (16 B per lane), B = the scaled Q
+//                             P^T            = exp2(S^T - m)  the accumulator IS the next B operand (its k order: key_of below)
+//                             O^T[d][row]   += V^T . P^T      A = V^T by ds_read_b64_tr_b16 from the wave's own [32][D] LDS image
+//                         A lane owns ONE query row (lane & 15) of each row tile, so the running maximum, the row sum and the
+//                         rescale of O^T are lane-local; only the chunk maximum crosses lanes (two xor steps).  K and V of the next
+//                         chunk are loaded into a second register set while this one is computed.  The waves' (m, l, O) meet
+//                         through LDS in ascending wave order at the end and wave 0 stores the split's partial.
+//   decode_merge_kernel   per row: m* = max m_s, O = sum 2^(m_s - m*) O_s / sum 2^(m_s - m*) l_s over the splits in ascending
+//                         order, one division, one conversion; optionally the log-sum-exp (m* + log2 l) ln 2.  The grid's split
+//                         extent comes from NK (the host never reads a list's count); the workgroups past a list's end leave at
+//                         once and the merge stops at ceil(count / C).
+//
+// Numeric contract of the 2-byte K5 kernels: Q * (float)(sm_scale * 1.44269504) rounded to the input type (rsa_q_frag), scores
+// in the log2 domain, P rounded to the input type for P.V, fp32 accumulation.  Keys at or beyond the limit are never multiplied:
+// their scores are replaced by selection, their V rows are zeroed on the way into LDS, and blocks without a key below the limit
+// (or with a list / table entry out of range) are not read at all.  No atomics: the same inputs give the same bytes.
+#include "rsa_attn.h"
+
+#include <math.h>
+
+#define DEC_NT 256
+#define DEC_MAX_NK 8192
+#define DEC_MAX_ROWS 64
+#define DEC_CHUNK 32            // keys per wave step
+#define DEC_SPLIT 8             // default list entries per split: within a fifth of the best split size at every measured shape
+                                // (profiles/decode_perf.txt), and the partials it costs stay below a tenth of the K/V it reads
+
+struct DecArgs {
+    const unsigned short *q, *k, *v;
+    long qsb, qsh, qss, ksb, ksh, kss, vsb, vsh, vss;
+    const int32_t* table;       // [B, >= NK] page of every key block, or null: contiguous cache
+    long tsb;
+    int num_pages;
+    const int32_t *cols, *counts;
+    const int32_t* kv_len;      // device limits (clamped here) or null: kv_valid
+    int kv_valid;
+    int H, Hkv, Hl, U, Sq, Sk, NK, blk, causal;
+    int C, nsplit, R16;         // list entries per split, splits, rows of a partial (16 x row tiles)
+    float qk_scale;
+    float* ws_o;                // [B * U * nsplit, R16, D] unnormalised O
+    float2* ws_ml;              // [B * U * nsplit, R16] (m in the log2 domain, l)
+};
+
+template <typename Tag>
+struct Mfma16;
+template <>
+struct Mfma16<bf16_tag> {
+    static __device__ __forceinline__ f32x4 mfma(s16x8 a, s16x8 b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+};
+template <>
+struct Mfma16<fp16_tag> {
+    static __device__ __forceinline__ f32x4 mfma(s16x8 a, s16x8 b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+};
+
+// A chunk's operands as they come from global memory: K as the A fragments of S^T (key = 16 t + (lane & 15), d = 32 ks +
+// 8 (lane >> 4) ..), V as 16-byte pieces of its [32][D] row image.  key0 < 0: nothing to do (the block is not visited).
+template <int D>
+struct DecRaw {
+    uint4 kf[2][D / 32];
+    uint4 vf[D / 16];
+    const unsigned short* vb;   // the V rows of the chunk's batch item or page, and the offset of its row numbers
+    long roff;
+    int key0;
+};
+
+__device__ __forceinline__ s16x4 dec_tr_read(const unsigned char* p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+}
+
+template <typename Tag, int D, int MT>
+__global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(DecArgs a) {
+    constexpr int KS = D / 32, DT = D / 16, CH = D / 8, VL = D / 16;
+    // At head dim 128 with four row tiles Q (64 registers) and O^T (128) do not fit beside two sets of K and V: the scaled Q
+    // fragments then live in LDS (one image for the four waves) and are read again in every chunk.
+    constexpr bool QLDS = D == 128 && MT == 4;
+    constexpr int QROW = 2 * D + 16;        // bytes per row of that image
+    constexpr int VROW = 2 * D + 32;        // bytes per key row of the V image: rows 0 .. 7 start 8 banks apart (transposed reads
+                                            // of a 32-lane half touch 8 rows x 32 B: conflict-free)
+    // one array: the waves' V images (behind the last barrier of the walk: the O^T tiles of waves 1 .. 3), the Q image, (m, l)
+    constexpr int VIMG = 4 * DEC_CHUNK * VROW, QIMG = QLDS ? 16 * MT * QROW : 0;
+    static_assert(3 * 16 * D * 4 <= VIMG, "the O^T tiles of three waves fit the V images");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[VIMG + QIMG + 4 * 16 * MT * 8];
+    unsigned char* const vimg = lds;
+    unsigned char* const qimg = lds + VIMG;
+    float (*const red)[16 * D] = reinterpret_cast<float (*)[16 * D]>(lds);
+    float2 (*const ml)[16 * MT] = reinterpret_cast<float2 (*)[16 * MT]>(lds + VIMG + QIMG);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lh = lane >> 4;
+    const int unit = blockIdx.x % a.U, b = blockIdx.x / a.U, split = blockIdx.y;
+    const int gu = a.H / a.U, R = a.Sq * gu;
+    const int hk = unit / (a.U / a.Hkv), hl = unit / (a.U / a.Hl);
+    const int kvlen = a.kv_len ? min(max(a.kv_len[b], 0), a.Sk) : a.kv_valid;
+    const long lrow = (long)b * a.Hl + hl;
+    const long part = ((long)blockIdx.x * a.nsplit + split) * a.R16;
+    const int count = min(max(a.counts[lrow], 0), a.NK);
+    const int first = split * a.C;
+    const int n_items = max(0, min(a.C, count - first));
+    if (n_items == 0) return;               // (uniform) past the list's end: the merge stops at the list's count
+    if (kvlen == 0) {                       // (uniform) no key at all: m = -inf, l = 0; the merge never reads its O
+        if (tid < 16 * MT) a.ws_ml[part + tid] = make_float2(-INFINITY, 0.f);
+        return;
+    }
+    const int32_t* list = a.cols + lrow * a.NK + first;
+    const int cshift = a.blk == 128 ? 2 : 1;        // chunks per block: 4 or 2
+
+    // the unit's rows: scaled Q fragments (B operand of S^T: column = row tile's row lane & 15) and each row's key limit
+    s16x8 qf[QLDS ? 1 : MT][QLDS ? 1 : KS];
+    int lim[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int rr = 16 * mt + lr;
+        const bool ok = rr < R;
+        const int hu = ok ? rr / a.Sq : 0, qrow = ok ? rr - hu * a.Sq : 0;
+        const unsigned short* qp = a.q + (long)b * a.qsb + (long)(unit * gu + hu) * a.qsh + (long)qrow * a.qss + 8 * lh;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const s16x8 f = rsa_q_frag<Tag>(qp + 32 * ks, ok, a.qk_scale);
+            if constexpr (QLDS) {
+                if (wave == 0) *reinterpret_cast<s16x8*>(qimg + rr * QROW + 64 * ks + 16 * lh) = f;
+            } else {
+                qf[mt][ks] = f;
+            }
+        }
+        lim[mt] = !ok ? 0 : (a.causal ? min(kvlen, max(0, qrow + kvlen - a.Sq + 1)) : kvlen);
+    }
+
+    f32x4 o[DT][MT];
+    float m[MT], l[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        m[mt] = -INFINITY;
+        l[mt] = 0.f;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[dt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    unsigned char* vst = vimg + wave * (DEC_CHUNK * VROW);
+    if constexpr (QLDS) __syncthreads();
+    const unsigned short* kbase = a.k + (long)hk * a.ksh;
+    const unsigned short* vbase = a.v + (long)hk * a.vsh;
+
+    for (int e0 = 0; e0 < n_items; e0 += 64) {
+        // this lane's list entry: the key block and where it lives, or -1 (out of range, no key below the limit, no page).  No
+        // address is formed from an unchecked index.
+        int jv = -1, pv = -1;
+        if (e0 + lane < n_items) {
+            const int j = list[e0 + lane];
+            if (j >= 0 && j < a.NK && (long)j * a.blk < kvlen) {
+                jv = j;
+                pv = j;
+                if (a.table) {
+                    pv = a.table[(long)b * a.tsb + j];
+                    if (pv < 0 || pv >= a.num_pages) jv = -1;
+                }
+            }
+        }
+        const int nch = min(64, n_items - e0) << cshift;
+
+        auto load_v = [&](uint4 (&vf)[VL], const DecRaw<D>& r) {
+#pragma unroll
+            for (int i = 0; i < VL; ++i) {
+                const int idx = i * 64 + lane, vr = idx / CH, ch = idx % CH;
+                const long row = min(r.key0 + vr, kvlen - 1) + r.roff;
+                vf[i] = *reinterpret_cast<const uint4*>(r.vb + row * a.vss + 8 * ch);
+            }
+        };
+        auto load = [&](DecRaw<D>& r, int c) {
+            const int entry = c >> cshift, sub = c & ((1 << cshift) - 1);
+            const int j = __shfl(jv, entry, 64), pg = __shfl(pv, entry, 64);
+            const int key0 = j * a.blk + sub * DEC_CHUNK;
+            r.key0 = -1;
+            if (j < 0 || key0 >= kvlen) return;         // (uniform)
+            r.key0 = key0;
+            // rows at or beyond the limit are read as the last row below it: in bounds, masked (K) or zeroed (V) later
+            const long roff = a.table ? -(long)j * a.blk : 0;     // paged: rows count from the page's first
+            const unsigned short* kb = kbase + (a.table ? (long)pg * a.ksb : (long)b * a.ksb);
+            r.vb = vbase + (a.table ? (long)pg * a.vsb : (long)b * a.vsb);
+            r.roff = roff;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const long row = min(key0 + 16 * t + lr, kvlen - 1) + roff;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+                    r.kf[t][ks] = *reinterpret_cast<const uint4*>(kb + row * a.kss + 32 * ks + 8 * lh);
+            }
+            load_v(r.vf, r);
+        };
+
+        auto qfrag = [&](int mt, int ks, int qoff) {
+            if constexpr (QLDS) return *reinterpret_cast<const s16x8*>(qimg + qoff + 16 * mt * QROW + 64 * ks);
+            else return qf[mt][ks];
+        };
+        auto compute = [&](const DecRaw<D>& r) {
+            if (r.key0 < 0) return;                     // (uniform: the transposed reads below need every lane)
+            const int key0 = r.key0;
+            int qoff = lr * QROW + 16 * lh;
+            if constexpr (QLDS) asm volatile("" : "+v"(qoff));      // (read in every chunk, not hoisted back into registers)
+            // S^T = K . Q^T: lane (lr, lh) gets keys key0 + 16 t + 4 lh + i of query row lr of each row tile
+            s16x8 pf[MT];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                float x[8];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks)
+                        s = Mfma16<Tag>::mfma(__builtin_bit_cast(s16x8, r.kf[t][ks]), qfrag(mt, ks, qoff), s);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) x[4 * t + i] = key0 + 16 * t + 4 * lh + i < lim[mt] ? s[i] : -INFINITY;
+                }
+                float mx = x[0];
+#pragma unroll
+                for (int e = 1; e < 8; ++e) mx = fmaxf(mx, x[e]);
+                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                const float mn = fmaxf(m[mt], mx);
+                const float mref = mn == -INFINITY ? 0.f : mn;
+                const float alpha = __builtin_amdgcn_exp2f(m[mt] - mref);
+                float ps = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    x[e] = __builtin_amdgcn_exp2f(x[e] - mref);
+                    ps += x[e];
+                }
+                l[mt] = l[mt] * alpha + ps;     // the lane's share of the row sum: the four lanes of a row meet at the end
+                m[mt] = mn;
+                // element e of the fragment is key_of(lh, e) = 16 (e >> 2) + 4 lh + (e & 3): the V^T fragments below follow it
+                pf[mt] = Elem<Tag>::cvt8(x);
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt) o[dt][mt] *= alpha;
+            }
+            // V image: a key at or beyond the limit becomes a zero row (0 * NaN inside an MFMA would be NaN)
+#pragma unroll
+            for (int i = 0; i < VL; ++i) {
+                const int idx = i * 64 + lane, vr = idx / CH, ch = idx % CH;
+                const uint4 x = key0 + vr < kvlen ? r.vf[i] : make_uint4(0, 0, 0, 0);
+                *reinterpret_cast<uint4*>(vst + vr * VROW + 16 * ch) = x;
+            }
+            // O^T += V^T . P^T: lane 4 q + p of a 16-lane group addresses key row (4 lh + q), d = 16 dt + 4 p .. + 3, and receives
+            // d = 16 dt + lr of the rows' four keys
+            const unsigned char* vp = vst + (4 * lh + (lr >> 2)) * VROW + 8 * (lr & 3);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                const s16x4 lo = dec_tr_read(vp + 32 * dt), hi = dec_tr_read(vp + 16 * VROW + 32 * dt);
+                const s16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) o[dt][mt] = Mfma16<Tag>::mfma(vf, pf[mt], o[dt][mt]);
+            }
+        };
+
+        DecRaw<D> ra, rb;
+        int c = wave;
+        if (c < nch) load(ra, c);
+        while (c < nch) {
+            if (c + 4 < nch) load(rb, c + 4);
+            compute(ra);
+            c += 4;
+            if (c >= nch) break;
+            if (c + 4 < nch) load(ra, c + 4);
+            compute(rb);
+            c += 4;
+        }
+    }
+
+    // the waves meet: one (m, l) per row and wave, then O in ascending wave order
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        l[mt] += __shfl_xor(l[mt], 16, 64);
+        l[mt] += __shfl_xor(l[mt], 32, 64);
+        if (lh == 0) ml[wave][16 * mt + lr] = make_float2(m[mt], l[mt]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        float ms = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) ms = fmaxf(ms, ml[w][16 * mt + lr].x);
+        const float mref = ms == -INFINITY ? 0.f : ms;
+        float lt = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) lt += __builtin_amdgcn_exp2f(ml[w][16 * mt + lr].x - mref) * ml[w][16 * mt + lr].y;
+        const float f = __builtin_amdgcn_exp2f(m[mt] - mref);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[dt][mt] *= f;
+        m[mt] = ms;
+        l[mt] = lt;
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        if (wave > 0) {
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt)
+                *reinterpret_cast<f32x4*>(&red[wave - 1][lr * D + 16 * dt + 4 * lh]) = o[dt][mt];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+#pragma unroll
+                for (int w = 0; w < 3; ++w) o[dt][mt] += *reinterpret_cast<const f32x4*>(&red[w][lr * D + 16 * dt + 4 * lh]);
+                *reinterpret_cast<f32x4*>(a.ws_o + (part + 16 * mt + lr) * D + 16 * dt + 4 * lh) = o[dt][mt];
+            }
+            if (lh == 0) a.ws_ml[part + 16 * mt + lr] = make_float2(m[mt], l[mt]);
+        }
+        __syncthreads();
+    }
+}
+
+struct DecMergeArgs {
+    const float* ws_o;
+    const float2* ws_ml;
+    unsigned short* out;
+    long osb, osh, oss;
+    float* lse;                 // [B, H, Sq] or null
+    const int32_t* counts;      // [B * Hl]: splits past a list's end were never written and are not read
+    int Hl, NK, C;
+    int H, U, Sq, nsplit, R16;
+    long rows;                  // B * H * Sq
+};
+
+// D / 4 threads per output row, four channels each; the splits in ascending order.
+template <typename Tag, int D>
+__global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(DecMergeArgs a) {
+    constexpr int TPR = D / 4;
+    const long g = (long)blockIdx.x * DEC_NT + threadIdx.x;
+    const long row = g / TPR;
+    const int c = (int)(g % TPR);
+    if (row >= a.rows) return;
+    const int qrow = (int)(row % a.Sq), h = (int)((row / a.Sq) % a.H);
+    const long b = row / ((long)a.Sq * a.H);
+    const int gu = a.H / a.U, unit = h / gu, rr = (h % gu) * a.Sq + qrow;
+    const long p0 = ((b * a.U + unit) * a.nsplit) * a.R16 + rr;
+    const int count = min(max(a.counts[b * a.Hl + unit / (a.U / a.Hl)], 0), a.NK);
+    const int nlive = min(a.nsplit, (count + a.C - 1) / a.C);
+    float ms = -INFINITY;
+    for (int s = 0; s < nlive; ++s) {
+        const float2 v = a.ws_ml[p0 + (long)s * a.R16];
+        if (v.y > 0.f) ms = fmaxf(ms, v.x);
+    }
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float lt = 0.f;
+    for (int s = 0; s < nlive; ++s) {
+        const float2 v = a.ws_ml[p0 + (long)s * a.R16];
+        if (!(v.y > 0.f)) continue;         // an empty partial: skipped, not multiplied (its O was never written)
+        const float f = __builtin_amdgcn_exp2f(v.x - ms);
+        const float4 x = *reinterpret_cast<const float4*>(a.ws_o + (p0 + (long)s * a.R16) * D + 4 * c);
+        acc.x += f * x.x;
+        acc.y += f * x.y;
+        acc.z += f * x.z;
+        acc.w += f * x.w;
+        lt += f * v.y;
+    }
+    const bool any = lt > 0.f;
+    const float r[4] = {any ? acc.x / lt : 0.f, any ? acc.y / lt : 0.f, any ? acc.z / lt : 0.f, any ? acc.w / lt : 0.f};
+    uint2 pk;
+    pk.x = (unsigned)Elem<Tag>::from_f32(r[0]) | ((unsigned)Elem<Tag>::from_f32(r[1]) << 16);
+    pk.y = (unsigned)Elem<Tag>::from_f32(r[2]) | ((unsigned)Elem<Tag>::from_f32(r[3]) << 16);
+    *reinterpret_cast<uint2*>(a.out + b * a.osb + (long)h * a.osh + (long)qrow * a.oss + 4 * c) = pk;
+    if (a.lse && c == 0) a.lse[row] = any ? (ms + __builtin_amdgcn_logf(lt)) * 0.69314718055994530942f : -INFINITY;
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------
+struct DecPlan {
+    int U, MT, C, nsplit;
+    size_t bytes;
+};
+
+// Shapes only: units, rows per unit, split size (0 = the library's choice) and the workspace.
+static int dec_plan(int B, int H, int Hkv, int Hl, int Sq, int D, int NK, int blocks_per_split, DecPlan* p) {
+    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+    if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
+    if (NK > DEC_MAX_NK || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
+    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    p->U = Hl > Hkv ? Hl : Hkv;
+    const long rows = (long)Sq * (H / p->U);
+    if (rows > DEC_MAX_ROWS) return RSA_ERR_UNSUPPORTED;
+    p->MT = rows <= 16 ? 1 : (rows <= 32 ? 2 : 4);
+    const long units = (long)B * p->U;
+    if (units > 0x7FFFFFFFl) return RSA_ERR_UNSUPPORTED;
+    if (blocks_per_split > 0) {
+        p->C = blocks_per_split < NK ? blocks_per_split : NK;
+    } else {
+        p->C = DEC_SPLIT < NK ? DEC_SPLIT : NK;
+    }
+    p->nsplit = (NK + p->C - 1) / p->C;
+    p->bytes = (size_t)units * p->nsplit * (16 * p->MT) * ((size_t)D + 2) * sizeof(float);
+    return RSA_OK;
+}
+
+extern "C" int rsa_block_sparse_decode_bytes(int B, int H, int Hkv, int Hl, int Sq, int D, int NK, int blocks_per_split,
+                                             size_t* bytes) {
+    if (!bytes) return RSA_ERR_BAD_ARG;
+    DecPlan p;
+    const int st = dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
+    if (st == RSA_OK) *bytes = p.bytes;
+    return st;
+}
+
+template <typename Tag, int D>
+static void dec_launch(const DecArgs& a, const DecMergeArgs& g, int MT, dim3 grid, hipStream_t s) {
+    if (MT == 1) decode_split_kernel<Tag, D, 1><<<grid, DEC_NT, 0, s>>>(a);
+    else if (MT == 2) decode_split_kernel<Tag, D, 2><<<grid, DEC_NT, 0, s>>>(a);
+    else decode_split_kernel<Tag, D, 4><<<grid, DEC_NT, 0, s>>>(a);
+    const long threads = g.rows * (D / 4);
+    decode_merge_kernel<Tag, D><<<dim3((unsigned)((threads + DEC_NT - 1) / DEC_NT)), DEC_NT, 0, s>>>(g);
+}
+
+extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                       const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                       rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                       int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
+                                       size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
+    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || Sk <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+    if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
+    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
+    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    const long nkmax = ((long)Sk + block - 1) / block;
+    if (NK > (nkmax < DEC_MAX_NK ? nkmax : DEC_MAX_NK)) return RSA_ERR_BAD_ARG;
+    if (Sq > block || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
+    if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
+    DecPlan p;
+    const int st = dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
+    if (st != RSA_OK) return st;
+    if (!cols || !counts || !ws || !out.ptr) return RSA_ERR_BAD_ARG;
+    if (rsa_check_tensor(q) != RSA_OK || rsa_check_tensor(k) != RSA_OK || rsa_check_tensor(v) != RSA_OK) return RSA_ERR_BAD_ARG;
+    if (q.stride_b < 0 || q.stride_h < 0 || q.stride_s < 0 || k.stride_b < 0 || k.stride_h < 0 || k.stride_s < 0 ||
+        v.stride_b < 0 || v.stride_h < 0 || v.stride_s < 0 || out.stride_b < 0 || out.stride_h < 0 || out.stride_s < 0)
+        return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(out.ptr) & 7) || (out.stride_b % 4) || (out.stride_h % 4) || (out.stride_s % 4))
+        return RSA_ERR_BAD_ARG;         // 8-byte stores of four channels
+    if ((reinterpret_cast<uintptr_t>(cols) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(kv_len_dev) |
+         reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(lse)) & 3)
+        return RSA_ERR_BAD_ARG;
+    if (block_table && (num_pages <= 0 || table_stride_b < 0)) return RSA_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return RSA_ERR_BAD_ARG;
+    if (ws_bytes < p.bytes) return RSA_ERR_WORKSPACE;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long parts = (long)B * p.U * p.nsplit;
+    DecArgs a;
+    a.q = static_cast<const unsigned short*>(q.ptr);
+    a.k = static_cast<const unsigned short*>(k.ptr);
+    a.v = static_cast<const unsigned short*>(v.ptr);
+    a.qsb = q.stride_b; a.qsh = q.stride_h; a.qss = q.stride_s;
+    a.ksb = k.stride_b; a.ksh = k.stride_h; a.kss = k.stride_s;
+    a.vsb = v.stride_b; a.vsh = v.stride_h; a.vss = v.stride_s;
+    a.table = block_table;
+    a.tsb = table_stride_b;
+    a.num_pages = num_pages;
+    a.cols = cols;
+    a.counts = counts;
+    a.kv_len = kv_len_dev;
+    a.kv_valid = kv_valid;
+    a.H = H; a.Hkv = Hkv; a.Hl = Hl; a.U = p.U; a.Sq = Sq; a.Sk = Sk; a.NK = NK; a.blk = block; a.causal = causal != 0;
+    a.C = p.C; a.nsplit = p.nsplit; a.R16 = 16 * p.MT;
+    a.qk_scale = (float)(sm_scale * 1.44269504);    // (as rsa_block_sparse_plain_fwd)
+    a.ws_o = static_cast<float*>(ws);
+    a.ws_ml = reinterpret_cast<float2*>(a.ws_o + parts * a.R16 * D);
+    DecMergeArgs g;
+    g.ws_o = a.ws_o;
+    g.ws_ml = a.ws_ml;
+    g.out = static_cast<unsigned short*>(out.ptr);
+    g.osb = out.stride_b; g.osh = out.stride_h; g.oss = out.stride_s;
+    g.lse = lse;
+    g.counts = counts;
+    g.Hl = Hl; g.NK = NK; g.C = p.C;
+    g.H = H; g.U = p.U; g.Sq = Sq; g.nsplit = p.nsplit; g.R16 = a.R16;
+    g.rows = (long)B * H * Sq;
+    const dim3 grid((unsigned)((long)B * p.U), (unsigned)p.nsplit);
+    if (dtype == RSA_BF16) {
+        if (D == 128) dec_launch<bf16_tag, 128>(a, g, p.MT, grid, s);
+        else dec_launch<bf16_tag, 64>(a, g, p.MT, grid, s);
+    } else {
+        if (D == 128) dec_launch<fp16_tag, 128>(a, g, p.MT, grid, s);
+        else dec_launch<fp16_tag, 64>(a, g, p.MT, grid, s);
+    }
+    return rsa_launch_status();
+}
