@@ -351,6 +351,41 @@ int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D
                             const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
                             void* stream);
 
+/* ---- a cache of pooled keys for the selection, and the selection from it (found by symbol: the header version stays 6.1;
+ * DESIGN.md section 5.13).  One decode step is rsa_pool_keys (the blocks the step touched) -> rsa_block_select_pooled ->
+ * rsa_block_sparse_decode: all on the device, no host read, capturable in one graph.
+ *
+ * rsa_pool_keys writes out[b, hk, j, :] (fp32 [B, Hkv, NK, D] contiguous, 16-byte aligned) = the kbar of rsa_block_select above,
+ * with its summation order, for exactly the blocks j with start_b / block <= j < ceil(len_b / block), and no other byte of out;
+ * start_b > len_b writes nothing.  len_b = kv_len_dev[b] clamped into [0, Sk] (DEVICE int32, B values, never read on the host) or,
+ * with kv_len_dev NULL, kv_valid in [0, Sk]; start_b likewise from start_dev or start.  Keys at or beyond len_b are never loaded.
+ * k: [B, Hkv, Sk, D] through any strides that are multiples of 8 elements, NK = ceil(Sk / block) <= 8192; or, with block_table
+ * (DEVICE int32 [B, >= NK], row stride table_stride_b), a page pool [num_pages, Hkv, block, D] (stride_b = the page stride) with
+ * Sk = NK * block: block j of batch item b is page block_table[b][j].  The table is read for written blocks only; an entry
+ * outside [0, num_pages) gives a block of zeros and no address is formed from it.  workgroups_per_head workgroups per (b, K/V
+ * head) stride over the block range (a device limit does not size the grid); any count >= 1 gives the same bytes; 0 = the exact
+ * count when both limits are host values, NK when start is the host value 0, else 2.  One launch.
+ *
+ * rsa_block_select_pooled is rsa_block_select with kbar read from pooled_k (fp32 [B, Hkv, NK, D] contiguous, 16-byte aligned) and
+ * Sk = NK * block: on inputs both accept, and pooled_k = rsa_pool_keys of the same k and limit, it writes the same bytes (lists
+ * and scores).  Only the visible prefix of pooled_k is read; the rest may hold anything.  score_splits workgroups per list row
+ * compute the row's scores (1: inside the select workgroup; 0: the library's choice, a function of B * Hl * NQ, NK and D alone; at
+ * most 256); every value gives the same bytes.  ws: rsa_block_select_pooled_bytes(...) bytes, 16-byte aligned.  Two launches
+ * with one split, three with more.
+ * Refusals as rsa_block_select's and rsa_block_sparse_decode's: non-positive sizes, Hkv not dividing H, Hl other than Hkv or H,
+ * NQ / NK not matching Sq / Sk, a negative top_k / keep_first / keep_local / workgroups_per_head / score_splits (or one above
+ * 256), kv_valid or start outside [0, Sk], a NULL or misaligned pointer or stride, a negative stride, a table with num_pages <= 0:
+ * RSA_ERR_BAD_ARG; block, D, dtype or NK outside the above: RSA_ERR_UNSUPPORTED; ws_bytes too small: RSA_ERR_WORKSPACE.  Every
+ * check runs before the first HIP call. */
+int rsa_pool_keys(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                  int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid, const int32_t* start_dev,
+                  int start, int workgroups_per_head, float* out, void* stream);
+int rsa_block_select_pooled_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes);
+int rsa_block_select_pooled(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q,
+                            const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k, int keep_first,
+                            int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                            int32_t* counts, float* scores, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

@@ -74,6 +74,25 @@ def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, bloc
                                             blocks_per_split=blocks_per_split)
 
 
+def pool_keys(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None):
+    """The cache of pooled keys for select_blocks_pooled: k [B,Hkv,Sk,D] (or a page pool behind block_table) -> fp32
+    [B, Hkv, ceil(Sk/block), D]; with start= and out= only the blocks from start // block up to kv_len are written again.
+    See rectified_spaattn_amd.block_sparse.pool_keys."""
+    from . import block_sparse
+    return block_sparse.pool_keys(k, block_size=block_size, kv_len=kv_len, block_table=block_table, out=out, start=start,
+                                  workgroups_per_head=workgroups_per_head)
+
+
+def select_blocks_pooled(q, pooled_k, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0,
+                         mask_heads="kv", return_scores=False, as_lists=False, score_splits=None):
+    """select_blocks from a cache of pooled keys (pool_keys) in place of k: the same bytes without a pass over K.
+    See rectified_spaattn_amd.block_sparse.select_blocks_pooled."""
+    from . import block_sparse
+    return block_sparse.select_blocks_pooled(q, pooled_k, top_k, block_size=block_size, kv_len=kv_len, causal=causal,
+                                             keep_first=keep_first, keep_local=keep_local, mask_heads=mask_heads,
+                                             return_scores=return_scores, as_lists=as_lists, score_splits=score_splits)
+
+
 def clear_buffer_cache() -> None:
     """Drops the intermediate buffers the operators keep per (geometry, device, stream) between calls (about 0.45 GB per
     set at the HunyuanVideo shape; `_core.BUFFER_CACHE_MAX_BYTES` bounds the total, `_core.BUFFER_CACHE = False` turns the

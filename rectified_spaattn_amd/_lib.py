@@ -137,6 +137,12 @@ def lib():
     L.rsa_block_select_bytes.restype = i32
     L.rsa_block_select.argtypes = [i32] * 11 + [RsaTensor4, RsaTensor4, vp] + [i32] * 5 + [vp, sz, vp, vp, vp, vp, vp]
     L.rsa_block_select.restype = i32
+    L.rsa_pool_keys.argtypes = [i32] * 7 + [RsaTensor4, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp]
+    L.rsa_pool_keys.restype = i32
+    L.rsa_block_select_pooled_bytes.argtypes = [i32] * 6 + [P(sz)]
+    L.rsa_block_select_pooled_bytes.restype = i32
+    L.rsa_block_select_pooled.argtypes = [i32] * 10 + [RsaTensor4, vp, vp] + [i32] * 6 + [vp, sz, vp, vp, vp, vp, vp]
+    L.rsa_block_select_pooled.restype = i32
     L.rsa_block_sparse_decode_bytes.argtypes = [i32] * 8 + [P(sz)]
     L.rsa_block_sparse_decode_bytes.restype = i32
     L.rsa_block_sparse_decode.argtypes = ([i32] * 10 + [vp, i32, i32, ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, i64,
@@ -229,6 +235,7 @@ EXPORTED = ("rsa_version", "rsa_abi_check", "rsa_buffer_bytes", "rsa_carve_works
             "rsa_block_mask_to_lists", "rsa_lists_to_block_mask", "rsa_block_sparse_plain_fwd", "rsa_block_sparse_ranged_fwd",
             "rsa_block_sparse_gqa_fwd", "rsa_block_select_bytes", "rsa_block_select",
             "rsa_block_sparse_decode_bytes", "rsa_block_sparse_decode",
+            "rsa_pool_keys", "rsa_block_select_pooled_bytes", "rsa_block_select_pooled",
             "rsa_select_from_mask", "rsa_select_from_mask_ex", "rsa_rectified_attention_masked", "rsa_rectified_attention_masked_ex")
 
 

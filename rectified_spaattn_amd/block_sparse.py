@@ -13,6 +13,10 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              the kept list and merged, with an optional log-sum-exp (rsa_block_sparse_decode, kernels of its own)
     select_blocks            a selection of the library's own for that call: pooled scores and a plain top-k per K/V head, with
                              the call's kv_len and causal alignment, written as lists on the device (rsa_block_select)
+    pool_keys                the cache of pooled keys of that selection, made once and updated block by block as the K/V cache
+                             grows, directly or through a block table (rsa_pool_keys)
+    select_blocks_pooled     select_blocks from that cache instead of K: the same bytes without a pass over K
+                             (rsa_block_select_pooled)
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
@@ -451,6 +455,197 @@ def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: i
                                       min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), ws.data_ptr(), need.value,
                                       out["bitmask"].data_ptr(), out["cols"].data_ptr(), out["counts"].data_ptr(),
                                       scores.data_ptr() if scores is not None else None, _core._stream()), "rsa_block_select")
+    sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
+    return (sel, scores) if return_scores else sel
+
+
+MAX_SCORE_SPLITS = 256  # score workgroups per list row of select_blocks_pooled, at most (rsa_block_select.hip)
+
+
+def _device_limit(val, B: int, Sk: int, dev):
+    """What _check_limit returned, for the C entries: (device int32 [B] | None, host int, host list | None).  A device tensor is
+    clamped into [0, Sk] on the device and never read on the host."""
+    if isinstance(val, torch.Tensor):
+        return val.to(dev).reshape(-1).clamp(0, Sk).to(torch.int32).expand(B).contiguous(), Sk, None
+    if len(set(val)) == 1:
+        return None, val[0], val
+    return torch.tensor(val, dtype=torch.int32, device=dev), Sk, val
+
+
+def _check_limit(name: str, val, B: int, Sk: int, default: int):
+    """None | int | per-batch sequence | host tensor -> list of B ints in [0, Sk]; a device tensor is checked and passed on."""
+    if isinstance(val, torch.Tensor) and val.is_cuda:
+        if val.numel() not in (1, B) or val.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{name}: an int32 / int64 tensor of 1 or {B} values, got {val.dtype} {tuple(val.shape)}")
+        return val
+    try:
+        return _kv_lens(default if val is None else val, B, Sk)
+    except ValueError as e:
+        raise ValueError(str(e).replace("kv_len", name, 1)) from None
+
+
+def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_table=None, out: Optional[torch.Tensor] = None,
+              start=None, workgroups_per_head: Optional[int] = None) -> torch.Tensor:
+    """The cache of pooled keys select_blocks_pooled reads: per key block the kbar of select_blocks, the
+    fp32 sum of the block's keys below kv_len[b] divided once by their count, in select_blocks' summation order.
+    k [B,Hkv,Sk,D], any strides block_sparse_decode accepts (a cache is never copied), or with block_table int32 [B, NKt] a page
+    pool [P, Hkv, block_size, D] (one page = one key block, as in block_sparse_decode); bf16 / fp16; head dim 16, 32, 64 or 128;
+    block_size 64 or 128; NKt = ceil(Sk/block) or the table's width, at most 8192.  Returns (and fills) out, fp32
+    [B, Hkv, NKt, D] contiguous: 1/64 of K's bytes at 128-token blocks.
+    kv_len, start: None (= Sk / 0), an int, one value per batch item, or an int32 / int64 device tensor of 1 or B values, which is
+    clamped into [0, Sk] on the device and never read on the host.  The call writes exactly the blocks j with
+    start[b] // block <= j < ceil(kv_len[b] / block) and leaves every other element of out untouched:
+      start=None             everything below kv_len (prefill); out may be None, the result is then new (and unwritten beyond)
+      start=the old length   after an append: the tail block again and every block the append opened
+      start=kv_len           the ragged tail block alone (after a rollback of rejected speculative tokens)
+      start > kv_len         nothing
+    out is required when start is given.  Keys at or beyond kv_len[b] are never loaded and may hold NaN.  The table is read only
+    for blocks the call writes; an entry outside [0, P) gives a block of zeros.
+    workgroups_per_head: workgroups per (b, K/V head) that stride over the block range -- a performance hint, any count >= 1
+    gives the same bytes.  None: the exact count when both limits are host values, NKt with start=None, else 2 (an append of
+    at most block tokens touches at most two blocks).  Asynchronous on the current stream, no host synchronisation, capturable."""
+    if block_size not in _lib.BLOCKS:
+        raise NotImplementedError(f"pool_keys on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
+    blk = int(block_size)
+    if workgroups_per_head is not None and (not isinstance(workgroups_per_head, int) or isinstance(workgroups_per_head, bool)
+                                            or workgroups_per_head < 1):
+        raise ValueError(f"workgroups_per_head: None or an int >= 1, got {workgroups_per_head!r}")
+    if not isinstance(k, torch.Tensor) or k.dim() != 4:
+        raise ValueError("k: a [B, Hkv, Sk, D] tensor, or a page pool [P, Hkv, block_size, D] with block_table")
+    Hkv, D = k.shape[1], k.shape[3]
+    paged = block_table is not None
+    if paged:
+        if (not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
+                or block_table.shape[0] < 1 or block_table.shape[1] < 1):
+            raise ValueError(f"block_table: an int32 tensor [B, NKt], got {getattr(block_table, 'dtype', type(block_table))} "
+                             f"{tuple(getattr(block_table, 'shape', ()))}")
+        if k.shape[2] != blk:
+            raise ValueError(f"k {tuple(k.shape)}: with a block_table it is a page pool [P, Hkv, {blk}, D]")
+        B, NK = block_table.shape
+        Sk = NK * blk
+    else:
+        B, Sk = k.shape[0], k.shape[2]
+        NK = -(-Sk // blk)
+    if k.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"k: bfloat16 or float16, got dtype {k.dtype}")
+    if D not in (16, 32, 64, 128):
+        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
+    if B <= 0 or Hkv <= 0 or Sk <= 0:
+        raise ValueError(f"empty operands (B = {B}, Hkv = {Hkv}, Sk = {Sk})")
+    if NK > MAX_KEY_BLOCKS:
+        raise ValueError(f"Sk = {Sk} is {NK} key blocks of {blk}: at most {MAX_KEY_BLOCKS}")
+    if start is not None and out is None:
+        raise ValueError("out: required when start is given (an update writes into the cache it is given)")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, Hkv, NK, D)
+                            or not out.is_contiguous()):
+        raise ValueError(f"out: a contiguous float32 tensor [{B}, {Hkv}, {NK}, {D}], got {getattr(out, 'dtype', type(out))} "
+                         f"{tuple(getattr(out, 'shape', ()))}")
+    lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
+    starts = _check_limit("start", start, B, Sk, 0)
+    if k.stride(-1) != 1 or any(st % 8 for st in k.stride()[:-1]) or any(st < 0 for st in k.stride()):
+        raise ValueError(f"k: a contiguous head dim and strides that are multiples of 8 elements (a cache is not copied), "
+                         f"got strides {tuple(k.stride())}")
+    _core._require_device(k)
+    if k.data_ptr() % 16:
+        raise ValueError("k: 16-byte aligned (a cache is not copied)")
+    dev = k.device
+    if out is None:
+        out = torch.empty((B, Hkv, NK, D), dtype=torch.float32, device=dev)
+    else:
+        _core._require_device(out)
+    if out.data_ptr() % 16:
+        raise ValueError("out: 16-byte aligned")
+    table = None
+    if paged:
+        _core._require_device(block_table)
+        table = block_table if block_table.stride(1) == 1 else block_table.contiguous()
+    kv_dev, kv_valid, lens = _device_limit(lens, B, Sk, dev)
+    st_dev, st_host, starts = _device_limit(starts, B, Sk, dev)
+    if workgroups_per_head is not None:
+        wph = int(workgroups_per_head)
+    elif lens is not None and starts is not None:     # the exact count: the grid is sized from host values alone
+        wph = max([1] + [-(-n // blk) - s // blk for n, s in zip(lens, starts) if s <= n])
+    else:
+        wph = NK if start is None else 2
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rsa_pool_keys(B, Hkv, Sk, D, _core.dtype_code(k.dtype), blk, NK, _core._t4(k),
+                                            table.data_ptr() if table is not None else None,
+                                            table.stride(0) if table is not None else 0, k.shape[0] if paged else 0,
+                                            kv_dev.data_ptr() if kv_dev is not None else None, kv_valid,
+                                            st_dev.data_ptr() if st_dev is not None else None, st_host, wph, out.data_ptr(),
+                                            _core._stream()), "rsa_pool_keys")
+    return out
+
+
+def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None,
+                         causal: bool = False, keep_first: int = 0, keep_local: int = 0, mask_heads: str = "kv",
+                         return_scores: bool = False, as_lists: bool = False, score_splits: Optional[int] = None):
+    """select_blocks from a cache of pooled keys: q [B,H,Sq,D] (any Sq), pooled_k fp32 [B, Hkv, NK, D]
+    contiguous as pool_keys returns it, Sk taken as NK * block_size.  Visible set, forced blocks, top-k, ties and the returned
+    mask / lists / scores are select_blocks' contract word for word, and on inputs both calls accept
+        select_blocks_pooled(q, pool_keys(k, kv_len=L, ...), top_k, kv_len=L, ...)
+    gives the bytes of select_blocks(q, k, top_k, kv_len=L, ...): the query pooling, the score arithmetic and the select body are
+    one device code.  Only the visible prefix of pooled_k is read: entries at or beyond ceil(kv_len[b] / block) may hold anything,
+    NaN included.  kv_len: None (= NK * block), an int, one value per batch item, or an int32 / int64 device tensor (read on the
+    device only).
+    score_splits: workgroups per list row that compute the row's scores before the select workgroup ranks them (few list rows,
+    many key blocks: a decode step); 1 = inside the select workgroup; None = the library's choice, a function of the shapes alone
+    (measured: DESIGN.md 5.13).  Every value gives the same bytes.  Asynchronous on the current stream, capturable."""
+    if block_size not in _lib.BLOCKS:
+        raise NotImplementedError(f"select_blocks_pooled on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
+    blk = int(block_size)
+    if mask_heads not in ("kv", "q"):
+        raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
+    for name, val in (("top_k", top_k), ("keep_first", keep_first), ("keep_local", keep_local)):
+        if not isinstance(val, int) or isinstance(val, bool) or val < 0:
+            raise ValueError(f"{name}: an int >= 0, got {val!r}")
+    if score_splits is not None and (not isinstance(score_splits, int) or isinstance(score_splits, bool)
+                                     or not 1 <= score_splits <= MAX_SCORE_SPLITS):
+        raise ValueError(f"score_splits: None or an int in 1..{MAX_SCORE_SPLITS}, got {score_splits!r}")
+    if not isinstance(q, torch.Tensor) or not isinstance(pooled_k, torch.Tensor) or q.dim() != 4 or pooled_k.dim() != 4:
+        raise ValueError("q: a [B, H, Sq, D] tensor, pooled_k: a [B, Hkv, NK, D] tensor")
+    B, H, Sq, D = q.shape
+    Hkv, NK = pooled_k.shape[1], pooled_k.shape[2]
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h belongs to K/V head h // (H // Hkv))")
+    if pooled_k.shape[0] != B or pooled_k.shape[3] != D:
+        raise ValueError(f"pooled_k {tuple(pooled_k.shape)} does not match q {tuple(q.shape)}")
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"q: bfloat16 or float16, got dtype {q.dtype}")
+    if pooled_k.dtype != torch.float32 or not pooled_k.is_contiguous():
+        raise ValueError(f"pooled_k: a contiguous float32 tensor (pool_keys' result), got dtype {pooled_k.dtype}, "
+                         f"strides {tuple(pooled_k.stride())}")
+    if D not in (16, 32, 64, 128):
+        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
+    if Sq <= 0 or NK <= 0:
+        raise ValueError(f"empty operands (Sq = {Sq}, NK = {NK})")
+    if NK > MAX_KEY_BLOCKS:
+        raise ValueError(f"pooled_k holds {NK} key blocks: at most {MAX_KEY_BLOCKS}")
+    NQ, Sk = -(-Sq // blk), NK * blk
+    Hl = Hkv if mask_heads == "kv" else H
+    lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
+    _core._require_device(q, pooled_k)
+    dev = q.device
+    if pooled_k.data_ptr() % 16:
+        raise ValueError("pooled_k: 16-byte aligned")
+    kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
+    L = _lib.lib()
+    q = _core._as_bhsd(q)
+    need = ctypes.c_size_t(0)
+    _lib.check(L.rsa_block_select_pooled_bytes(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), "rsa_block_select_pooled_bytes")
+    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+    out = dict(bitmask=torch.empty((B * Hl, NQ, (NK + 31) // 32), dtype=torch.int32, device=dev),
+               cols=torch.empty((B * Hl, NQ, NK), dtype=torch.int32, device=dev),
+               counts=torch.empty((B * Hl, NQ), dtype=torch.int32, device=dev))
+    scores = torch.empty((B, Hl, NQ, NK), dtype=torch.float32, device=dev) if return_scores else None
+    with torch.cuda.device(dev):
+        _lib.check(L.rsa_block_select_pooled(B, H, Hkv, Hl, Sq, D, _core.dtype_code(q.dtype), blk, NQ, NK, _core._t4(q),
+                                             pooled_k.data_ptr(), kv_dev.data_ptr() if kv_dev is not None else None, kv_valid,
+                                             int(bool(causal)), min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1),
+                                             0 if score_splits is None else int(score_splits), ws.data_ptr(), need.value,
+                                             out["bitmask"].data_ptr(), out["cols"].data_ptr(), out["counts"].data_ptr(),
+                                             scores.data_ptr() if scores is not None else None, _core._stream()),
+                   "rsa_block_select_pooled")
     sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
     return (sel, scores) if return_scores else sel
 

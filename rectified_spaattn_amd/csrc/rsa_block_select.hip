@@ -9,6 +9,15 @@
 //                              LDS histograms (8 bits a pass), ties to the lower block index by ballot / prefix popcount, and the
 //                              list contract of rsa_block_mask.hip (bitmask, ascending cols, counts) in 64-block ballot steps.
 //
+// The pooled-key cache (rsa_pool_keys, rsa_block_select_pooled_bytes, rsa_block_select_pooled) runs the
+// same device code: sel_pool_mean, sel_score_blocks and the select body below exist once.
+//
+//   pool_keys_kernel           W workgroups per (b, K/V head) stride over the key blocks [start / block, ceil(len / block)) and
+//                              write sel_pool_mean of each, read directly or through a block table, into the fp32 cache
+//   block_score_kernel         `splits` workgroups per list row: each writes its slice of the row's ordered keys to the workspace
+//                              (a lane group computes a whole score: nothing is summed across workgroups)
+//   block_select_kernel<L, 1>  the select body over keys loaded from that workspace instead of computed
+//
 // Every sum has a fixed order (no floating-point atomics; the histograms count integers): two calls give the same bytes.
 #include "rsa_common.h"
 
@@ -17,6 +26,7 @@
 #define SEL_NT 256
 #define SEL_MAX_NK 8192
 #define SEL_MAX_STEPS (SEL_MAX_NK / 64)
+#define SEL_MAX_SPLITS 256      // score workgroups per list row of the pooled selection, at most
 
 // ---- pooling ---------------------------------------------------------------------------------------------------------------------
 template <typename Tag>
@@ -62,6 +72,13 @@ __device__ __forceinline__ float sel_pool_block(const unsigned short* __restrict
     return tid < D ? (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]) : 0.f;
 }
 
+// The value of a key block in the selection: the fp32 sum of its `rows` (>= 1) keys below the limit, divided once by their count.
+template <typename Tag>
+__device__ __forceinline__ float sel_pool_mean(const unsigned short* __restrict__ base, long stride_s, int rows, int D,
+                                               float (*red)[128]) {
+    return sel_pool_block<Tag>(base, stride_s, rows, D, red) / (float)rows;
+}
+
 __device__ __forceinline__ int sel_key_limit(const int32_t* __restrict__ kv_len, int b, int kv_valid, int Sk) {
     return kv_len ? min(max(kv_len[b], 0), Sk) : kv_valid;
 }
@@ -102,9 +119,45 @@ __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q
     if (rows > 0) {
         const unsigned short* base = static_cast<const unsigned short*>(k.ptr) + b * k.stride_b + (long)hk * k.stride_h +
                                      (long)j * blk * k.stride_s;
-        mean = sel_pool_block<Tag>(base, k.stride_s, rows, D, red) / (float)rows;
+        mean = sel_pool_mean<Tag>(base, k.stride_s, rows, D, red);
     }
     if (tid < D) kbar[job * D + tid] = mean;
+}
+
+// The pooled-key cache: workgroup w of the W of (b, K/V head) writes the blocks start / blk + w, + W, ... below ceil(len / blk) and
+// nothing else.  Both limits are uniform over the workgroup, so every barrier of sel_pool_block is met by all of it.  With a table
+// the page of a block is read for written blocks only, and an entry outside [0, num_pages) gives zeros: no address is formed
+// from it.
+template <typename Tag>
+__global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hkv, int Sk, int D, int blk, int NK, int W,
+                                                           const int32_t* __restrict__ kv_len, int kv_valid,
+                                                           const int32_t* __restrict__ start_dev, int start_host,
+                                                           const int32_t* __restrict__ table, long table_stride_b,
+                                                           int num_pages, float* __restrict__ out) {
+    __shared__ float red[4][128];
+    const int tid = threadIdx.x;
+    const int w = (int)(blockIdx.x % (unsigned)W);
+    const long bh = blockIdx.x / (unsigned)W;
+    const int hk = (int)(bh % Hkv);
+    const long b = bh / Hkv;
+    const int len = sel_key_limit(kv_len, (int)b, kv_valid, Sk);
+    const int st = sel_key_limit(start_dev, (int)b, start_host, Sk);
+    if (st > len) return;
+    const int j_hi = min(NK, (len + blk - 1) / blk);
+    for (int j = st / blk + w; j < j_hi; j += W) {
+        const int rows = min(blk, len - j * blk);       // >= 1 below j_hi
+        const unsigned short* base;
+        bool have = true;
+        if (table) {
+            const int page = table[b * table_stride_b + j];
+            have = page >= 0 && page < num_pages;
+            base = static_cast<const unsigned short*>(k.ptr) + (long)(have ? page : 0) * k.stride_b + (long)hk * k.stride_h;
+        } else {
+            base = static_cast<const unsigned short*>(k.ptr) + b * k.stride_b + (long)hk * k.stride_h + (long)j * blk * k.stride_s;
+        }
+        const float mean = have ? sel_pool_mean<Tag>(base, k.stride_s, rows, D, red) : 0.f;
+        if (tid < D) out[(bh * NK + j) * D + tid] = mean;
+    }
 }
 
 // ---- score and select ------------------------------------------------------------------------------------------------------------
@@ -135,9 +188,68 @@ __device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
     return run;
 }
 
-// L = D / 4 lanes share one pooled key row (a float4 each); a wave scores 64 / L key blocks per step.
+// Visible blocks of list row (b, i): a prefix [0, nvis) of the row.
+__device__ __forceinline__ int sel_visible(int len, int Sq, int blk, int NK, int i, int causal) {
+    const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
+    int nvis = min(NK, (len + blk - 1) / blk);
+    if (causal) nvis = r1 + off < 0 ? 0 : (int)min((long)nvis, (r1 + off) / blk + 1);
+    return nvis;
+}
+
+// Scores of the key blocks [lo, hi) of one list row as ordered keys into dst[j], by one workgroup.  L = D / 4 lanes share one
+// pooled key row (a float4 each); a wave scores 64 / L key blocks per step.  kb: the pooled rows of (b, K/V head); qrow: the row's
+// pooled query.
 template <int L>
+__device__ __forceinline__ void sel_score_blocks(const float* __restrict__ kb, const float* __restrict__ qrow, int lo, int hi,
+                                                 unsigned* dst) {
+    constexpr int D = 4 * L, RW = 64 / L, U = 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cl = lane % L, sub = lane / L;
+    const float4 qv = *reinterpret_cast<const float4*>(qrow + cl * 4);
+    kb += cl * 4;
+    for (int j0 = lo + wave * RW; j0 < hi; j0 += 4 * RW * U) {
+        float4 kv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * 4 * RW + sub;
+            kv[u] = j < hi ? *reinterpret_cast<const float4*>(kb + (long)j * D) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * 4 * RW + sub;
+            float p = fmaf(qv.w, kv[u].w, fmaf(qv.z, kv[u].z, fmaf(qv.y, kv[u].y, qv.x * kv[u].x)));
+#pragma unroll
+            for (int m = 1; m < L; m <<= 1) p += __shfl_xor(p, m, 64);
+            if (cl == 0 && j < hi) dst[j] = sel_key(p);
+        }
+    }
+}
+
+// The score pass of the pooled selection spread over `splits` workgroups per list row: workgroup (row, part) writes the keys of
+// its slice of the visible blocks to wkeys[row, :].
+template <int L>
+__global__ __launch_bounds__(SEL_NT) void block_score_kernel(const float* __restrict__ kbar, const float* __restrict__ qsum, int Hkv,
+                                                             int Hl, int Sq, int Sk, int blk, int NQ, int NK, int splits,
+                                                             const int32_t* __restrict__ kv_len, int kv_valid, int causal,
+                                                             unsigned* __restrict__ wkeys) {
+    constexpr int D = 4 * L;
+    const int part = (int)(blockIdx.x % (unsigned)splits);
+    const long row = blockIdx.x / (unsigned)splits;
+    const int i = (int)(row % NQ);
+    const long bh = row / NQ;
+    const int hl = (int)(bh % Hl);
+    const long b = bh / Hl;
+    const int hk = hl / (Hl / Hkv);
+    const int nvis = sel_visible(sel_key_limit(kv_len, (int)b, kv_valid, Sk), Sq, blk, NK, i, causal);
+    const int chunk = (NK + splits - 1) / splits;
+    const int lo = part * chunk, hi = min(lo + chunk, nvis);
+    sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, lo, hi, wkeys + row * NK);
+}
+
+// LOADED = 0: the scores are computed here (kbar, qsum); LOADED = 1: their keys are loaded from wkeys [rows, NK] (block_score_kernel).
+template <int L, int LOADED>
 __global__ __launch_bounds__(SEL_NT) void block_select_kernel(const float* __restrict__ kbar, const float* __restrict__ qsum,
+                                                              const unsigned* __restrict__ wkeys,
                                                               int Hkv, int Hl, int Sq, int Sk, int blk, int NQ, int NK,
                                                               const int32_t* __restrict__ kv_len, int kv_valid, int causal,
                                                               int top_k, int keep_first, int keep_local,
@@ -149,7 +261,7 @@ __global__ __launch_bounds__(SEL_NT) void block_select_kernel(const float* __res
     __shared__ unsigned pick[2];
     __shared__ int step_eq[SEL_MAX_STEPS], step_kept[SEL_MAX_STEPS];
     __shared__ unsigned long long step_mask[SEL_MAX_STEPS];
-    constexpr int D = 4 * L, RW = 64 / L, U = 4;
+    constexpr int D = 4 * L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long row = blockIdx.x;
     const int i = (int)(row % NQ);
@@ -161,8 +273,7 @@ __global__ __launch_bounds__(SEL_NT) void block_select_kernel(const float* __res
 
     // visible blocks: a prefix [0, nvis) of the row; forced blocks: [0, kf) and [flo, fhi] within it
     const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
-    int nvis = min(NK, (len + blk - 1) / blk);
-    if (causal) nvis = r1 + off < 0 ? 0 : (int)min((long)nvis, (r1 + off) / blk + 1);
+    const int nvis = sel_visible(len, Sq, blk, NK, i, causal);
     const int kf = min(keep_first, nvis);
     int flo = 1, fhi = 0;
     if (keep_local >= 1 && nvis > 0) {
@@ -175,26 +286,11 @@ __global__ __launch_bounds__(SEL_NT) void block_select_kernel(const float* __res
     auto forced = [&](int j) { return j < kf || (j >= flo && j <= fhi); };
 
     // scores of the visible blocks
-    {
-        const int cl = lane % L, sub = lane / L;
-        const float4 qv = *reinterpret_cast<const float4*>(qsum + row * D + cl * 4);
-        const float* kb = kbar + ((b * Hkv + hk) * NK) * D + cl * 4;
-        for (int j0 = wave * RW; j0 < nvis; j0 += 4 * RW * U) {
-            float4 kv[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = j0 + u * 4 * RW + sub;
-                kv[u] = j < nvis ? *reinterpret_cast<const float4*>(kb + (long)j * D) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int j = j0 + u * 4 * RW + sub;
-                float p = fmaf(qv.w, kv[u].w, fmaf(qv.z, kv[u].z, fmaf(qv.y, kv[u].y, qv.x * kv[u].x)));
-#pragma unroll
-                for (int m = 1; m < L; m <<= 1) p += __shfl_xor(p, m, 64);
-                if (cl == 0 && j < nvis) keys[j] = sel_key(p);
-            }
-        }
+    if (LOADED) {
+        const unsigned* wr = wkeys + row * NK;
+        for (int j = tid; j < nvis; j += SEL_NT) keys[j] = wr[j];
+    } else {
+        sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, 0, nvis, keys);
     }
     __syncthreads();
     if (scores) {
@@ -339,9 +435,139 @@ extern "C" int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, i
     const dim3 grid((unsigned)q_jobs);
     const size_t lds = (size_t)NK * sizeof(unsigned);
 #define SEL_LAUNCH(LANES)                                                                                                       \
-    block_select_kernel<LANES><<<grid, SEL_NT, lds, s>>>(kbar, qsum, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid,      \
-                                                         causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts,    \
-                                                         scores)
+    block_select_kernel<LANES, 0><<<grid, SEL_NT, lds, s>>>(kbar, qsum, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev,    \
+                                                            kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask,     \
+                                                            cols, counts, scores)
+    switch (D) {
+        case 16: SEL_LAUNCH(4); break;
+        case 32: SEL_LAUNCH(8); break;
+        case 64: SEL_LAUNCH(16); break;
+        default: SEL_LAUNCH(32); break;
+    }
+#undef SEL_LAUNCH
+    return rsa_launch_status();
+}
+
+// ---- the pooled-key cache ----------------------------------------------------------------------------------
+extern "C" int rsa_pool_keys(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                             int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
+                             const int32_t* start_dev, int start, int workgroups_per_head, float* out, void* stream) {
+    if (B <= 0 || Hkv <= 0 || Sk <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
+    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (NK != (int)(((long)Sk + block - 1) / block)) return RSA_ERR_BAD_ARG;
+    if (NK > SEL_MAX_NK) return RSA_ERR_UNSUPPORTED;
+    if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
+    if (!start_dev && (start < 0 || start > Sk)) return RSA_ERR_BAD_ARG;
+    if (workgroups_per_head < 0) return RSA_ERR_BAD_ARG;
+    if (!out || rsa_check_tensor(k) != RSA_OK) return RSA_ERR_BAD_ARG;
+    if (k.stride_b < 0 || k.stride_h < 0 || k.stride_s < 0) return RSA_ERR_BAD_ARG;
+    if (block_table && (num_pages <= 0 || table_stride_b < 0)) return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_len_dev) | reinterpret_cast<uintptr_t>(start_dev)) & 3)
+        return RSA_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(out) & 15) return RSA_ERR_BAD_ARG;       // (the selection reads the cache 16 bytes a lane)
+    int W = workgroups_per_head;
+    if (W == 0) {   // the exact count with two host limits; every block with start 0; else the two an append of <= block keys touches
+        if (!kv_len_dev && !start_dev) W = start > kv_valid ? 1 : max(1, (kv_valid + block - 1) / block - start / block);
+        else W = (!start_dev && start == 0) ? NK : 2;
+    }
+    W = min(W, NK);
+    if ((size_t)B * Hkv * W > 0x7FFFFFFFull) return RSA_ERR_UNSUPPORTED;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((size_t)B * Hkv * W));
+    if (dtype == RSA_BF16)
+        pool_keys_kernel<bf16_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start,
+                                                           block_table, (long)table_stride_b, num_pages, out);
+    else
+        pool_keys_kernel<fp16_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start,
+                                                           block_table, (long)table_stride_b, num_pages, out);
+    return rsa_launch_status();
+}
+
+static int sel_pooled_check_sizes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
+    if (B <= 0 || Hkv <= 0 || Hl <= 0 || NQ <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (NK > SEL_MAX_NK) return RSA_ERR_UNSUPPORTED;
+    const size_t q_jobs = (size_t)B * Hl * NQ;
+    if (q_jobs * SEL_MAX_SPLITS > 0x7FFFFFFFull) return RSA_ERR_UNSUPPORTED;    // one workgroup per row and split
+    if (bytes) *bytes = q_jobs * ((size_t)D * sizeof(float) + (size_t)NK * sizeof(unsigned));   // the pooled queries, the keys
+    return RSA_OK;
+}
+
+// The library's choice of score_splits, a function of the shapes alone (measured: profiles/pooled_select_perf.txt).
+// One pass of sel_score_blocks' loop per score workgroup (4096 / D key blocks: 32 at D = 128), which is the best or within the
+// baseline's spread of the best at both measured row counts (8 rows x 1024 blocks: 32 splits; 64 rows x 256 blocks: 8); at most 64
+// splits and about 1024 workgroups, and none where the list rows alone give two workgroups per compute unit (not measured there).
+static int sel_default_splits(size_t rows, int NK, int D) {
+    if (rows >= 512) return 1;
+    const int pass = 4096 / D;
+    const int by_blocks = (NK + pass - 1) / pass, by_rows = (int)((1024 + rows - 1) / rows);
+    return max(1, min(min(by_blocks, by_rows), 64));
+}
+
+extern "C" int rsa_block_select_pooled_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
+    if (!bytes) return RSA_ERR_BAD_ARG;
+    return sel_pooled_check_sizes(B, Hkv, Hl, D, NQ, NK, bytes);
+}
+
+extern "C" int rsa_block_select_pooled(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK,
+                                       rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal,
+                                       int top_k, int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes,
+                                       uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, void* stream) {
+    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+    if (H % Hkv || (Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
+    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
+    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (NQ != (int)(((long)Sq + block - 1) / block)) return RSA_ERR_BAD_ARG;
+    size_t need = 0;
+    const int st = sel_pooled_check_sizes(B, Hkv, Hl, D, NQ, NK, &need);
+    if (st != RSA_OK) return st;
+    const int Sk = NK * block;      // the capacity of the cache
+    if (top_k < 0 || keep_first < 0 || keep_local < 0) return RSA_ERR_BAD_ARG;
+    if (score_splits < 0 || score_splits > SEL_MAX_SPLITS) return RSA_ERR_BAD_ARG;
+    if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
+    if (!ws || !pooled_k || !bitmask || !cols || !counts) return RSA_ERR_BAD_ARG;
+    if (rsa_check_tensor(q) != RSA_OK) return RSA_ERR_BAD_ARG;
+    if (q.stride_b < 0 || q.stride_h < 0 || q.stride_s < 0) return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(bitmask) | reinterpret_cast<uintptr_t>(cols) | reinterpret_cast<uintptr_t>(counts) |
+         reinterpret_cast<uintptr_t>(scores) | reinterpret_cast<uintptr_t>(kv_len_dev)) & 3)
+        return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(pooled_k)) & 15) return RSA_ERR_BAD_ARG;
+    if (ws_bytes < need) return RSA_ERR_WORKSPACE;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long q_jobs = (long)B * Hl * NQ;
+    const int splits = min(score_splits ? score_splits : sel_default_splits((size_t)q_jobs, NK, D), NK);
+    float* qsum = static_cast<float*>(ws);                              // [B, Hl, NQ, D]
+    unsigned* wkeys = reinterpret_cast<unsigned*>(qsum + q_jobs * D);   // [B, Hl, NQ, NK]
+    // the pooled queries: the query jobs of the pool kernel alone (no key job in the grid: k and kbar are not touched)
+    if (dtype == RSA_BF16)
+        block_select_pool_kernel<bf16_tag><<<dim3((unsigned)q_jobs), SEL_NT, 0, s>>>(q, q, H, Hkv, Hl, Sq, Sk, D, block, NQ, NK, q_jobs,
+                                                                                     kv_len_dev, kv_valid, nullptr, qsum);
+    else
+        block_select_pool_kernel<fp16_tag><<<dim3((unsigned)q_jobs), SEL_NT, 0, s>>>(q, q, H, Hkv, Hl, Sq, Sk, D, block, NQ, NK, q_jobs,
+                                                                                     kv_len_dev, kv_valid, nullptr, qsum);
+    int rc = rsa_launch_status();
+    if (rc != RSA_OK) return rc;
+    const dim3 grid((unsigned)q_jobs), sgrid((unsigned)(q_jobs * splits));
+    const size_t lds = (size_t)NK * sizeof(unsigned);
+#define SEL_LAUNCH(LANES)                                                                                                       \
+    if (splits > 1) {                                                                                                           \
+        block_score_kernel<LANES><<<sgrid, SEL_NT, 0, s>>>(pooled_k, qsum, Hkv, Hl, Sq, Sk, block, NQ, NK, splits, kv_len_dev,  \
+                                                           kv_valid, causal != 0, wkeys);                                       \
+        rc = rsa_launch_status();                                                                                               \
+        if (rc != RSA_OK) return rc;                                                                                            \
+        block_select_kernel<LANES, 1><<<grid, SEL_NT, lds, s>>>(pooled_k, qsum, wkeys, Hkv, Hl, Sq, Sk, block, NQ, NK,          \
+                                                                kv_len_dev, kv_valid, causal != 0, top_k, keep_first,           \
+                                                                keep_local, bitmask, cols, counts, scores);                     \
+    } else {                                                                                                                    \
+        block_select_kernel<LANES, 0><<<grid, SEL_NT, lds, s>>>(pooled_k, qsum, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK,        \
+                                                                kv_len_dev, kv_valid, causal != 0, top_k, keep_first,           \
+                                                                keep_local, bitmask, cols, counts, scores);                     \
+    }
     switch (D) {
         case 16: SEL_LAUNCH(4); break;
         case 32: SEL_LAUNCH(8); break;
