@@ -49,6 +49,8 @@ def _lib():
         L.orc_select_row.restype = None
         L.orc_select_row.argtypes = [f32p, f32p, f32p, f32p, u8p] + [ctypes.c_int] * 7 + [
             ctypes.c_float, ctypes.c_float, u8p, u8p, f32p, f32p, ctypes.POINTER(ctypes.c_int), f32p]
+        L.orc_select_row_blk.restype = None
+        L.orc_select_row_blk.argtypes = L.orc_select_row.argtypes + [ctypes.c_float]
         _LIB = L
     return _LIB
 
@@ -241,6 +243,48 @@ def select_head(q, k, v, lay: Layout, top_k: int, p: float, neighbor: Optional[n
     comp = (w.astype(np.float64) @ st.vbar[:L].astype(np.float64)).astype(np.float32)
     return dict(kept=kept, unrel=unrel, probs=probs, w=w, n_needed=n_needed, R=R, comp=comp, rows=rows,
                 s_vis=s_vis, s_txt=s_txt, eq=eq, ek=ek, stats=st)
+
+
+def select_rows_from_scores(s_vis, s_txt, unrel, lay: Layout, top_k: int, p: float, neighbor: Optional[np.ndarray],
+                            D: int = 128, block: int = BLOCK):
+    """The selection of select_head from given UNSCALED scores and GAPR bytes, for tests that write K3's input themselves
+    (tests/select_rows.py): s_vis [R, NBv] fp32, s_txt [R, n_txt] (ignored without text), unrel [R, NBv] 0/1; row r is query
+    block r % NBv (several heads are stacked).  One orc_select_row per row; the wanted GAPR byte is handed over as eq = 0 and
+    ek = inf (byte 1: nothing exceeds inf) or ek = 0 (byte 0: needs s != 0, asserted -- the contract gives !(0 > 0) = 1).
+    D sets the scale (D ** -0.5 as fp32), block IPAR's weight of a visual block (orc_select_row_blk; 128 is orc_select_row).
+    Returns select_head's dict without comp and the statistics."""
+    s_vis = np.ascontiguousarray(s_vis, np.float32)
+    nr = s_vis.shape[0]
+    assert s_vis.shape[1] == lay.NBv
+    s_txt = np.ascontiguousarray(s_txt, np.float32) if lay.n_txt > 0 else np.zeros((nr, 1), np.float32)
+    want = np.ascontiguousarray(unrel, np.uint8) != 0
+    assert (want | (s_vis != 0)).all(), "a GAPR byte of 0 on a score of 0: the contract gives 1 there"
+    eq = np.zeros((nr, lay.NBv), np.float32)
+    ek = np.where(want, np.float32(np.inf), np.float32(0)).astype(np.float32)
+    L = lay.L
+    kept = np.zeros((nr, lay.NB_total), np.uint8)
+    unrel_o = np.zeros((nr, lay.NBv), np.uint8)
+    probs = np.zeros((nr, L), np.float32)
+    w = np.zeros((nr, L), np.float32)
+    n_needed = np.zeros(nr, np.int32)
+    R = np.zeros(nr, np.float32)
+    nbr_u8 = None
+    if neighbor is not None:
+        nbr_u8 = np.ascontiguousarray(np.asarray(neighbor)[: lay.NBv, : lay.NBv], np.uint8)
+    lib = _lib()
+    nn, rr = ctypes.c_int(0), ctypes.c_float(0)
+    scale, thr = softmax_scale(D), np.float32(p)
+    for a in range(nr):
+        i = a % lay.NBv
+        lib.orc_select_row_blk(_f32p(s_vis[a]), _f32p(s_txt[a]), _f32p(eq[a]), _f32p(ek[a]),
+                               _u8p(nbr_u8[i]) if nbr_u8 is not None else None,
+                               lay.NBv, lay.n_txt, lay.NB_total, lay.text_end_block, int(i), lay.ffb, int(top_k),
+                               ctypes.c_float(thr), ctypes.c_float(scale), _u8p(kept[a]), _u8p(unrel_o[a]),
+                               _f32p(probs[a]), _f32p(w[a]), ctypes.byref(nn), ctypes.byref(rr), ctypes.c_float(block))
+        n_needed[a] = nn.value
+        R[a] = rr.value
+    assert np.array_equal(unrel_o != 0, want)
+    return dict(kept=kept, unrel=unrel_o, probs=probs, w=w, n_needed=n_needed, R=R)
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -152,11 +152,12 @@ static int cmp_desc(const void* a, const void* b) {
  *  nbr[NBv]     neighbour row (0/1) or NULL
  *  outputs: kept[NB_total] (0/1), unrel[NBv] (0/1), probs[L] (L = NBv + (n_txt>0)), w[L] compensation
  *           weights, *n_needed, *R
+ *  blk          tokens per block: IPAR's weight of a visual block (128; 64 for the 64-token-block layouts)
  */
-void orc_select_row(const float* s_vis, const float* s_txt, const float* eq, const float* ek,
-                    const uint8_t* nbr, int NBv, int n_txt, int NB_total, int text_end_block, int qblk,
-                    int first_frame_blocks, int top_k, float thr, float scale, uint8_t* kept,
-                    uint8_t* unrel, float* probs, float* w, int* n_needed, float* R) {
+void orc_select_row_blk(const float* s_vis, const float* s_txt, const float* eq, const float* ek,
+                        const uint8_t* nbr, int NBv, int n_txt, int NB_total, int text_end_block, int qblk,
+                        int first_frame_blocks, int top_k, float thr, float scale, uint8_t* kept,
+                        uint8_t* unrel, float* probs, float* w, int* n_needed, float* R, float blk) {
     const int has_txt = n_txt > 0;
     const int L = NBv + (has_txt ? 1 : 0);
     const int NS = NBv + n_txt;
@@ -178,8 +179,8 @@ void orc_select_row(const float* s_vis, const float* s_txt, const float* eq, con
     if (has_txt) {
         float normal_sum = strided_tree_sum(x, NBv, NULL, 0);
         float text_sum = strided_tree_sum(x + NBv, n_txt, NULL, 0);
-        float denom = normal_sum * 128.0f + text_sum;
-        for (int j = 0; j < NBv; ++j) probs[j] = (x[j] * 128.0f) / denom;
+        float denom = normal_sum * blk + text_sum;
+        for (int j = 0; j < NBv; ++j) probs[j] = (x[j] * blk) / denom;
         probs[NBv] = text_sum / denom;
     } else {
         for (int j = 0; j < NBv; ++j) probs[j] = x[j];
@@ -220,4 +221,13 @@ void orc_select_row(const float* s_vis, const float* s_txt, const float* eq, con
     free(M);
     free(kv);
     free(x);
+}
+
+/* The 128-token-block form every golden vector pins (blk = 128.0f: the same operations on the same values as before). */
+void orc_select_row(const float* s_vis, const float* s_txt, const float* eq, const float* ek,
+                    const uint8_t* nbr, int NBv, int n_txt, int NB_total, int text_end_block, int qblk,
+                    int first_frame_blocks, int top_k, float thr, float scale, uint8_t* kept,
+                    uint8_t* unrel, float* probs, float* w, int* n_needed, float* R) {
+    orc_select_row_blk(s_vis, s_txt, eq, ek, nbr, NBv, n_txt, NB_total, text_end_block, qblk, first_frame_blocks, top_k,
+                       thr, scale, kept, unrel, probs, w, n_needed, R, 128.0f);
 }
