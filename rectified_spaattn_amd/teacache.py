@@ -49,10 +49,10 @@ COEFFICIENTS = {
 def rel_l1_distance(x: torch.Tensor, prev: torch.Tensor) -> float:
     """mean|x - prev| / mean|prev| as a python float (one host sync, like the reference's `.cpu().item()`).
     Device bf16 / fp16 tensors go through the one-pass HIP reduction; anything else (CPU plumbing runs, fp32 timestep
-    embeddings of a few KB) uses the reference's own expression."""
+    embeddings of a few KB, an empty tensor, which has no address to hand to the kernel) uses the reference's own expression."""
     if x.shape != prev.shape:
         raise ValueError(f"shape mismatch {tuple(x.shape)} vs {tuple(prev.shape)}")
-    if x.is_cuda and prev.is_cuda and x.dtype == prev.dtype and x.dtype in (torch.bfloat16, torch.float16):
+    if x.is_cuda and prev.is_cuda and x.dtype == prev.dtype and x.dtype in (torch.bfloat16, torch.float16) and x.numel():
         a, b = x.contiguous(), prev.contiguous()
         if a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0:
             out = torch.empty(2 + 2048, dtype=torch.float32, device=x.device)
