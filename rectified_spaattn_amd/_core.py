@@ -152,11 +152,16 @@ def _require_device(*ts):
                                 "CPU tensors are supported by fullattn(mode='torch'|'vanilla') alone")
 
 
+def _read_in_place(t: torch.Tensor) -> bool:
+    """Whether the kernels read the [B,H,S,D] view t of 2-byte elements as it is: a contiguous head dim, strides that keep
+    16-byte row chunks, a 16-byte aligned pointer.  Operands that fail it are copied (_as_bhsd); a K/V cache is refused."""
+    *outer, inner = t.stride()
+    return inner == 1 and not any(s % 8 for s in outer) and t.data_ptr() % 16 == 0
+
+
 def _as_bhsd(t: torch.Tensor) -> torch.Tensor:
     """Accept any [B,H,S,D] view whose head dim is contiguous and whose strides keep 16-byte row chunks."""
-    if t.stride(-1) != 1 or any(s % 8 for s in t.stride()[:-1]) or t.data_ptr() % 16:
-        t = t.contiguous()
-    return t
+    return t if _read_in_place(t) else t.contiguous()
 
 
 def _k_for_pv(k: torch.Tensor) -> torch.Tensor:
@@ -227,10 +232,12 @@ def cached_buffers(spec: LayoutSpec, B: int, H: int, D: int, device) -> Dict[str
 
 
 def clear_buffer_cache() -> None:
-    """Drops every cached buffer set (they return to PyTorch's allocator), block_sparse's tail buffers included."""
+    """Drops every cached buffer set (they return to PyTorch's allocator), block_sparse's tail buffers and window ranges
+    included."""
     _BUF_CACHE.clear()
     from . import block_sparse
     block_sparse._TAIL_CACHE.clear()
+    block_sparse._RANGE_CACHE.clear()
 
 
 def _c_buffers(bufs: Dict[str, torch.Tensor]) -> RsaBuffers:

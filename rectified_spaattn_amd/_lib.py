@@ -62,6 +62,103 @@ class RsaFp8Operands(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("q8", "k8", "v8t", "scales")]
 
 
+# Every prototype of include/rsa.h as name: (restype, argtypes), in the header's order, one type per parameter and no counted
+# runs: an entry reads against its prototype parameter by parameter.  lib() applies the table in one loop.  int -> i32,
+# int64_t -> i64, uint64_t -> u64, size_t -> sz, float -> f32, double -> f64, const char* -> cstr, rsa_tensor4 / rsa_out4 by value
+# -> T4 / O4, a pointer to a struct or to a host size_t / int / int64_t / void* -> P(its mirror), every other pointer -> vp.
+# tests/test_abi_cpu.py holds the table to the header, types included: one int for an int64_t shifts every later argument.
+P = ctypes.POINTER
+i32, i64, u64, sz = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t
+f32, f64, cstr, vp = ctypes.c_float, ctypes.c_double, ctypes.c_char_p, ctypes.c_void_p
+T4, O4 = RsaTensor4, RsaOut4
+PROTOTYPES = {
+    "rsa_version": (i32, []),
+    "rsa_abi_check": (i32, [i32, sz, sz]),
+    "rsa_set_shard_invariant": (i32, [i32]),
+    "rsa_buffer_bytes": (i32, [P(RsaLayout), P(sz * NUM_BUFFERS), P(sz)]),
+    "rsa_carve_workspace": (i32, [P(RsaLayout), vp, sz, P(RsaBuffers)]),
+    "rsa_pool_stats": (i32, [P(RsaLayout), T4, T4, T4, P(RsaBuffers), vp]),
+    "rsa_pooled_scores": (i32, [P(RsaLayout), T4, P(RsaBuffers), vp]),
+    "rsa_select_mask": (i32, [P(RsaLayout), vp, i32, f32, P(RsaBuffers), vp]),
+    "rsa_compensation": (i32, [P(RsaLayout), P(RsaBuffers), vp]),
+    "rsa_block_sparse_fwd": (i32, [P(RsaLayout), T4, T4, T4, P(RsaBuffers), O4, vp]),
+    "rsa_rectified_attention": (i32, [P(RsaLayout), T4, T4, T4, vp, i32, f32, vp, sz, O4, vp]),
+    "rsa_dense_fwd": (i32, [i32, i32, i32, i32, i32, i32, T4, T4, T4, i32, i32, O4, vp]),
+    "rsa_dense_causal_fwd": (i32, [i32, i32, i32, i32, i32, i32, T4, T4, T4, i32, i32, O4, vp]),
+    "rsa_dense_masked_fwd": (i32, [i32, i32, i32, i32, i32, i32, T4, T4, T4, vp, i32, i64, i64, i64, i64, i32, O4, vp]),
+    "rsa_dense_dropout_fwd": (i32, [i32, i32, i32, i32, i32, i32, T4, T4, T4, vp, i32, i64, i64, i64, i64, i32, i32, f32, u64, O4,
+                                    vp]),
+    "rsa_buffer_bytes_ex": (i32, [P(RsaLayoutEx), P(sz * NUM_BUFFERS), P(sz)]),
+    "rsa_carve_workspace_ex": (i32, [P(RsaLayoutEx), vp, sz, P(RsaBuffers)]),
+    "rsa_pool_stats_ex": (i32, [P(RsaLayoutEx), T4, T4, T4, P(RsaBuffers), vp]),
+    "rsa_pooled_scores_ex": (i32, [P(RsaLayoutEx), T4, P(RsaBuffers), vp]),
+    "rsa_select_mask_ex": (i32, [P(RsaLayoutEx), vp, i32, f32, P(RsaBuffers), vp]),
+    "rsa_compensation_ex": (i32, [P(RsaLayoutEx), P(RsaBuffers), vp]),
+    "rsa_block_sparse_fwd_ex": (i32, [P(RsaLayoutEx), T4, T4, T4, P(RsaBuffers), O4, vp]),
+    "rsa_rectified_attention_ex": (i32, [P(RsaLayoutEx), T4, T4, T4, vp, i32, f32, vp, sz, O4, vp]),
+    "rsa_block_mask_to_lists": (i32, [i32, i32, i32, i32, vp, i64, i64, i64, vp, vp, vp, vp]),
+    "rsa_lists_to_block_mask": (i32, [i32, i32, i32, i32, vp, vp, vp]),
+    "rsa_block_sparse_plain_fwd": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f64, T4, T4, T4, vp, vp, vp, sz, O4,
+                                         vp]),
+    "rsa_block_sparse_ranged_fwd": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f64, T4, T4, T4, vp, vp, vp, vp, i64,
+                                          vp, sz, O4, vp]),
+    "rsa_block_sparse_gqa_fwd": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f64, T4, T4, T4, vp, vp, vp,
+                                       vp, i64, vp, sz, O4, vp]),
+    "rsa_block_select_bytes": (i32, [i32, i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_block_select": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, T4, vp, i32, i32, i32, i32, i32, vp,
+                               sz, vp, vp, vp, vp, vp]),
+    "rsa_block_sparse_decode_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_block_sparse_decode": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp, i64,
+                                      i32, vp, vp, i32, vp, sz, O4, vp, vp]),
+    "rsa_pool_keys": (i32, [i32, i32, i32, i32, i32, i32, i32, T4, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp]),
+    "rsa_block_select_pooled_bytes": (i32, [i32, i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_block_select_pooled": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, vp, vp, i32, i32, i32, i32, i32, i32,
+                                      vp, sz, vp, vp, vp, vp, vp]),
+    "rsa_select_from_mask": (i32, [P(RsaLayout), vp, i64, i64, i64, P(RsaBuffers), vp]),
+    "rsa_select_from_mask_ex": (i32, [P(RsaLayoutEx), vp, i64, i64, i64, P(RsaBuffers), vp]),
+    "rsa_rectified_attention_masked": (i32, [P(RsaLayout), T4, T4, T4, vp, i64, i64, i64, vp, sz, O4, vp]),
+    "rsa_rectified_attention_masked_ex": (i32, [P(RsaLayoutEx), T4, T4, T4, vp, i64, i64, i64, vp, sz, O4, vp]),
+    "rsa_estimate_pr_gain": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "rsa_estimate_pr_gain_ex": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "rsa_gilbert_mapping": (i32, [i32, i32, i32, cstr, vp, vp]),
+    "rsa_gilbert_block_neighbors": (i32, [i32, i32, i32, i32, cstr, vp]),
+    "rsa_permute_tokens": (i32, [i32, i32, i32, vp, i64, i64, vp, vp, i64, i64, vp]),
+    "rsa_qk_norm_rope": (i32, [i32, i32, i32, i32, i32, T4, vp, f32, i32, vp, vp, i32, O4, vp]),
+    "rsa_qk_layernorm_rope": (i32, [i32, i32, i32, i32, i32, T4, vp, vp, f32, vp, vp, i32, O4, vp]),
+    "rsa_norm_rope_heads": (i32, [i32, i32, i32, i32, i32, vp, i64, i64, vp, f32, i32, i32, vp, vp, O4, vp]),
+    "rsa_fp8_operand_bytes": (i32, [P(RsaLayout), P(sz * 4), P(sz)]),
+    "rsa_carve_fp8_operands": (i32, [P(RsaLayout), vp, sz, P(RsaFp8Operands)]),
+    "rsa_quantize_fp8": (i32, [P(RsaLayout), T4, T4, T4, P(RsaFp8Operands), vp]),
+    "rsa_pool_stats_fp8": (i32, [P(RsaLayout), T4, T4, T4, P(RsaBuffers), P(RsaFp8Operands), vp]),
+    "rsa_block_sparse_fwd_fp8": (i32, [P(RsaLayout), P(RsaFp8Operands), P(RsaBuffers), O4, vp]),
+    "rsa_block_sparse_fwd_fp8pv": (i32, [P(RsaLayout), T4, T4, P(RsaFp8Operands), P(RsaBuffers), O4, vp]),
+    "rsa_rectified_attention_fp8": (i32, [P(RsaLayout), T4, T4, T4, vp, i32, f32, vp, sz, vp, sz, O4, vp]),
+    "rsa_rectified_attention_fp8pv": (i32, [P(RsaLayout), T4, T4, T4, vp, i32, f32, vp, sz, vp, sz, O4, vp]),
+    "rsa_rel_l1": (i32, [vp, vp, i64, i32, vp, vp, vp]),
+    "rsa_dense_fp8_bytes": (i32, [i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_dense_fwd_fp8": (i32, [i32, i32, i32, i32, i32, i32, T4, T4, T4, i32, i32, vp, sz, O4, vp]),
+    "rsa_dense_causal_fwd_fp8": (i32, [i32, i32, i32, i32, i32, i32, T4, T4, T4, i32, i32, vp, sz, O4, vp]),
+    "rsa_dense_fwd_fp8pv": (i32, [i32, i32, i32, i32, i32, i32, T4, T4, T4, i32, i32, i32, vp, sz, O4, vp]),
+    "rsa_comm_unique_id": (i32, [vp]),
+    "rsa_comm_create": (i32, [i32, i32, vp, P(vp)]),
+    "rsa_comm_destroy": (i32, [vp]),
+    "rsa_comm_count": (i32, [vp, P(i32)]),
+    "rsa_allgather_heads": (i32, [vp, i32, vp, vp, vp, i64, i64, vp]),
+    "rsa_p2p_state_bytes": (i32, []),
+    "rsa_p2p_state_alloc": (i32, [P(vp)]),
+    "rsa_p2p_state_free": (i32, [vp]),
+    "rsa_p2p_state_timeout": (i32, [vp, P(i32)]),
+    "rsa_allgather_heads_p2p": (i32, [i32, i32, vp, P(vp), P(vp), i64, i64, vp]),
+    "rsa_ipc_export": (i32, [vp, vp]),
+    "rsa_ipc_open": (i32, [vp, i32, P(vp)]),
+    "rsa_ipc_close": (i32, [vp]),
+    "rsa_ipc_offset": (i32, [vp, P(i64)]),
+    "rsa_set_tuning": (i32, [cstr, i32]),
+    "rsa_status_string": (cstr, [i32]),
+    "rsa_last_hip_error": (cstr, []),
+}
+EXPORTED = tuple(PROTOTYPES)
+
 _lib = None
 
 
@@ -74,143 +171,14 @@ def lib():
         raise RsaError(f"{LIB_PATH} not found: the HIP extension is not built "
                        f"(python -c 'import __graft_entry__ as g; g.build()'); there is no fallback path")
     L = ctypes.CDLL(LIB_PATH)
-    P = ctypes.POINTER
-    vp, i32, f32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-    L.rsa_version.restype = i32
-    L.rsa_abi_check.argtypes = [i32, sz, sz]
-    L.rsa_abi_check.restype = i32
+    for name in ("rsa_version", "rsa_abi_check"):
+        getattr(L, name).restype, getattr(L, name).argtypes = PROTOTYPES[name]
     if L.rsa_abi_check(HEADER_VERSION, ctypes.sizeof(RsaBuffers), ctypes.sizeof(RsaLayout)) != 0:
         raise RsaError(f"{LIB_PATH} (version {L.rsa_version()}) was built from another include/rsa.h than this package's "
                        f"ctypes mirror (header {HEADER_VERSION}, rsa_buffers {ctypes.sizeof(RsaBuffers)} B): rebuild it")
-    L.rsa_status_string.restype = ctypes.c_char_p
-    L.rsa_status_string.argtypes = [i32]
-    L.rsa_last_hip_error.restype = ctypes.c_char_p
-    L.rsa_gilbert_mapping.argtypes = [i32, i32, i32, ctypes.c_char_p, vp, vp]
-    L.rsa_gilbert_mapping.restype = i32
-    L.rsa_gilbert_block_neighbors.argtypes = [i32, i32, i32, i32, ctypes.c_char_p, vp]
-    L.rsa_gilbert_block_neighbors.restype = i32
-    i64 = ctypes.c_int64
-    L.rsa_permute_tokens.argtypes = [i32, i32, i32, vp, i64, i64, vp, vp, i64, i64, vp]
-    L.rsa_permute_tokens.restype = i32
-    L.rsa_qk_norm_rope.argtypes = [i32, i32, i32, i32, i32, RsaTensor4, vp, f32, i32, vp, vp, i32, RsaOut4, vp]
-    L.rsa_qk_norm_rope.restype = i32
-    L.rsa_qk_layernorm_rope.argtypes = [i32, i32, i32, i32, i32, RsaTensor4, vp, vp, f32, vp, vp, i32, RsaOut4, vp]
-    L.rsa_qk_layernorm_rope.restype = i32
-    L.rsa_norm_rope_heads.argtypes = [i32, i32, i32, i32, i32, vp, i64, i64, vp, f32, i32, i32, vp, vp, RsaOut4, vp]
-    L.rsa_norm_rope_heads.restype = i32
-    L.rsa_rel_l1.argtypes = [vp, vp, i64, i32, vp, vp, vp]
-    L.rsa_rel_l1.restype = i32
-    L.rsa_set_tuning.argtypes = [ctypes.c_char_p, i32]
-    L.rsa_set_tuning.restype = i32
-    L.rsa_set_shard_invariant.argtypes = [i32]
-    L.rsa_set_shard_invariant.restype = i32
-    L.rsa_buffer_bytes.argtypes = [P(RsaLayout), P(sz * NUM_BUFFERS), P(sz)]
-    L.rsa_carve_workspace.argtypes = [P(RsaLayout), vp, sz, P(RsaBuffers)]
-    L.rsa_pool_stats.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaBuffers), vp]
-    L.rsa_pooled_scores.argtypes = [P(RsaLayout), RsaTensor4, P(RsaBuffers), vp]
-    L.rsa_select_mask.argtypes = [P(RsaLayout), vp, i32, f32, P(RsaBuffers), vp]
-    L.rsa_compensation.argtypes = [P(RsaLayout), P(RsaBuffers), vp]
-    L.rsa_block_sparse_fwd.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaBuffers), RsaOut4, vp]
-    L.rsa_rectified_attention.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, vp, i32, f32, vp, sz,
-                                          RsaOut4, vp]
-    L.rsa_buffer_bytes_ex.argtypes = [P(RsaLayoutEx), P(sz * NUM_BUFFERS), P(sz)]
-    L.rsa_carve_workspace_ex.argtypes = [P(RsaLayoutEx), vp, sz, P(RsaBuffers)]
-    L.rsa_pool_stats_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaBuffers), vp]
-    L.rsa_pooled_scores_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, P(RsaBuffers), vp]
-    L.rsa_select_mask_ex.argtypes = [P(RsaLayoutEx), vp, i32, f32, P(RsaBuffers), vp]
-    L.rsa_compensation_ex.argtypes = [P(RsaLayoutEx), P(RsaBuffers), vp]
-    L.rsa_block_sparse_fwd_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaBuffers), RsaOut4, vp]
-    L.rsa_rectified_attention_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, RsaTensor4, RsaTensor4, vp, i32, f32, vp, sz,
-                                             RsaOut4, vp]
-    L.rsa_estimate_pr_gain_ex.argtypes = [i32] * 6 + [vp] * 9
-    L.rsa_block_mask_to_lists.argtypes = [i32] * 4 + [vp, i64, i64, i64, vp, vp, vp, vp]
-    L.rsa_lists_to_block_mask.argtypes = [i32] * 4 + [vp, vp, vp]
-    L.rsa_block_sparse_plain_fwd.argtypes = ([i32] * 10 + [ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, vp, vp, sz,
-                                             RsaOut4, vp])
-    L.rsa_block_sparse_ranged_fwd.argtypes = ([i32] * 10 + [ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, vp, vp, vp, i64,
-                                              vp, sz, RsaOut4, vp])
-    L.rsa_block_sparse_ranged_fwd.restype = i32
-    L.rsa_block_sparse_gqa_fwd.argtypes = ([i32] * 12 + [ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, vp, vp, vp, i64,
-                                           vp, sz, RsaOut4, vp])
-    L.rsa_block_sparse_gqa_fwd.restype = i32
-    L.rsa_block_select_bytes.argtypes = [i32] * 6 + [P(sz)]
-    L.rsa_block_select_bytes.restype = i32
-    L.rsa_block_select.argtypes = [i32] * 11 + [RsaTensor4, RsaTensor4, vp] + [i32] * 5 + [vp, sz, vp, vp, vp, vp, vp]
-    L.rsa_block_select.restype = i32
-    L.rsa_pool_keys.argtypes = [i32] * 7 + [RsaTensor4, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp]
-    L.rsa_pool_keys.restype = i32
-    L.rsa_block_select_pooled_bytes.argtypes = [i32] * 6 + [P(sz)]
-    L.rsa_block_select_pooled_bytes.restype = i32
-    L.rsa_block_select_pooled.argtypes = [i32] * 10 + [RsaTensor4, vp, vp] + [i32] * 6 + [vp, sz, vp, vp, vp, vp, vp]
-    L.rsa_block_select_pooled.restype = i32
-    L.rsa_block_sparse_decode_bytes.argtypes = [i32] * 8 + [P(sz)]
-    L.rsa_block_sparse_decode_bytes.restype = i32
-    L.rsa_block_sparse_decode.argtypes = ([i32] * 10 + [vp, i32, i32, ctypes.c_double, RsaTensor4, RsaTensor4, RsaTensor4, vp, i64,
-                                          i32, vp, vp, i32, vp, sz, RsaOut4, vp, vp])
-    L.rsa_block_sparse_decode.restype = i32
-    L.rsa_select_from_mask.argtypes = [P(RsaLayout), vp, i64, i64, i64, P(RsaBuffers), vp]
-    L.rsa_select_from_mask_ex.argtypes = [P(RsaLayoutEx), vp, i64, i64, i64, P(RsaBuffers), vp]
-    L.rsa_rectified_attention_masked.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, vp, i64, i64, i64, vp, sz,
-                                                 RsaOut4, vp]
-    L.rsa_rectified_attention_masked_ex.argtypes = [P(RsaLayoutEx), RsaTensor4, RsaTensor4, RsaTensor4, vp, i64, i64, i64, vp,
-                                                    sz, RsaOut4, vp]
-    for name in ("rsa_block_mask_to_lists", "rsa_lists_to_block_mask", "rsa_block_sparse_plain_fwd", "rsa_select_from_mask",
-                 "rsa_select_from_mask_ex", "rsa_rectified_attention_masked", "rsa_rectified_attention_masked_ex"):
-        getattr(L, name).restype = i32
-    L.rsa_dense_fwd.argtypes = [i32] * 6 + [RsaTensor4, RsaTensor4, RsaTensor4, i32, i32, RsaOut4, vp]
-    L.rsa_dense_causal_fwd.argtypes = L.rsa_dense_fwd.argtypes
-    L.rsa_dense_causal_fwd.restype = i32
-    L.rsa_dense_masked_fwd.argtypes = [i32] * 6 + [RsaTensor4, RsaTensor4, RsaTensor4, vp, i32] + [ctypes.c_int64] * 4 + [i32, RsaOut4, vp]
-    L.rsa_dense_dropout_fwd.argtypes = ([i32] * 6 + [RsaTensor4, RsaTensor4, RsaTensor4, vp, i32] + [ctypes.c_int64] * 4 +
-                                        [i32, i32, f32, ctypes.c_uint64, RsaOut4, vp])
-    L.rsa_dense_dropout_fwd.restype = i32
-    L.rsa_estimate_pr_gain.argtypes = [i32] * 5 + [vp] * 9
-    L.rsa_fp8_operand_bytes.argtypes = [P(RsaLayout), P(sz * 4), P(sz)]
-    L.rsa_carve_fp8_operands.argtypes = [P(RsaLayout), vp, sz, P(RsaFp8Operands)]
-    L.rsa_quantize_fp8.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaFp8Operands), vp]
-    L.rsa_pool_stats_fp8.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, P(RsaBuffers), P(RsaFp8Operands),
-                                     vp]
-    L.rsa_dense_fp8_bytes.argtypes = [i32] * 5 + [P(sz)]
-    L.rsa_dense_fwd_fp8.argtypes = [i32] * 6 + [RsaTensor4, RsaTensor4, RsaTensor4, i32, i32, vp, sz, RsaOut4, vp]
-    L.rsa_dense_causal_fwd_fp8.argtypes = L.rsa_dense_fwd_fp8.argtypes
-    L.rsa_dense_causal_fwd_fp8.restype = i32
-    L.rsa_dense_fwd_fp8pv.argtypes = [i32] * 6 + [RsaTensor4, RsaTensor4, RsaTensor4, i32, i32, i32, vp, sz, RsaOut4, vp]
-    L.rsa_dense_fwd_fp8pv.restype = i32
-    L.rsa_block_sparse_fwd_fp8.argtypes = [P(RsaLayout), P(RsaFp8Operands), P(RsaBuffers), RsaOut4, vp]
-    L.rsa_block_sparse_fwd_fp8pv.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, P(RsaFp8Operands), P(RsaBuffers), RsaOut4, vp]
-    L.rsa_block_sparse_fwd_fp8pv.restype = i32
-    L.rsa_rectified_attention_fp8.argtypes = [P(RsaLayout), RsaTensor4, RsaTensor4, RsaTensor4, vp, i32, f32, vp, sz,
-                                              vp, sz, RsaOut4, vp]
-    L.rsa_rectified_attention_fp8pv.argtypes = L.rsa_rectified_attention_fp8.argtypes
-    L.rsa_rectified_attention_fp8pv.restype = i32
-    L.rsa_comm_unique_id.argtypes = [vp]
-    L.rsa_comm_create.argtypes = [i32, i32, vp, P(vp)]
-    L.rsa_comm_destroy.argtypes = [vp]
-    L.rsa_comm_count.argtypes = [vp, P(i32)]
-    L.rsa_allgather_heads.argtypes = [vp, i32, vp, vp, vp, i64, i64, vp]
-    L.rsa_allgather_heads_p2p.argtypes = [i32, i32, vp, P(vp), P(vp), i64, i64, vp]
-    L.rsa_p2p_state_bytes.restype = i32
-    L.rsa_p2p_state_alloc.argtypes = [P(vp)]
-    L.rsa_p2p_state_free.argtypes = [vp]
-    L.rsa_p2p_state_timeout.argtypes = [vp, P(i32)]
-    L.rsa_ipc_offset.argtypes = [vp, P(i64)]
-    L.rsa_ipc_export.argtypes = [vp, vp]
-    L.rsa_ipc_open.argtypes = [vp, i32, P(vp)]
-    L.rsa_ipc_close.argtypes = [vp]
-    for name in ("rsa_comm_unique_id", "rsa_comm_create", "rsa_comm_destroy", "rsa_comm_count", "rsa_allgather_heads",
-                 "rsa_allgather_heads_p2p", "rsa_ipc_export", "rsa_ipc_open", "rsa_ipc_close", "rsa_ipc_offset",
-                 "rsa_p2p_state_alloc", "rsa_p2p_state_free", "rsa_p2p_state_timeout"):
-        getattr(L, name).restype = i32
-    for name in ("rsa_fp8_operand_bytes", "rsa_carve_fp8_operands", "rsa_quantize_fp8", "rsa_block_sparse_fwd_fp8",
-                 "rsa_rectified_attention_fp8", "rsa_rectified_attention_fp8pv", "rsa_pool_stats_fp8", "rsa_dense_fp8_bytes",
-                 "rsa_dense_fwd_fp8"):
-        getattr(L, name).restype = i32
-    for name in ("rsa_buffer_bytes", "rsa_carve_workspace", "rsa_pool_stats", "rsa_pooled_scores",
-                 "rsa_select_mask", "rsa_compensation", "rsa_block_sparse_fwd", "rsa_rectified_attention",
-                 "rsa_dense_fwd", "rsa_dense_masked_fwd", "rsa_estimate_pr_gain", "rsa_buffer_bytes_ex", "rsa_carve_workspace_ex",
-                 "rsa_pool_stats_ex", "rsa_pooled_scores_ex", "rsa_select_mask_ex", "rsa_compensation_ex", "rsa_block_sparse_fwd_ex",
-                 "rsa_rectified_attention_ex", "rsa_estimate_pr_gain_ex"):
-        getattr(L, name).restype = i32
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     # kernel-variant switches for A/B runs and the variant tests; rsa_set_tuning works only under RSA_TUNING=1
     for key in ("k5_tsplit", "k3_prefix", "k3_long", "k4_split", "k5_rows256", "k5_static", "k5_gsync", "k5_gsync_ratio", "k5_text_last", "k5_tail_split", "k5_gqa_pair"):
         val = os.environ.get("RSA_" + key.upper())
@@ -220,23 +188,6 @@ def lib():
                 raise RsaError(f"RSA_{key.upper()} is set but rsa_set_tuning refused it (export RSA_TUNING=1)")
     _lib = L
     return L
-
-
-EXPORTED = ("rsa_version", "rsa_abi_check", "rsa_buffer_bytes", "rsa_carve_workspace", "rsa_pool_stats", "rsa_pooled_scores",
-            "rsa_select_mask", "rsa_compensation", "rsa_block_sparse_fwd", "rsa_rectified_attention",
-            "rsa_dense_fwd", "rsa_dense_causal_fwd", "rsa_dense_masked_fwd", "rsa_dense_dropout_fwd", "rsa_estimate_pr_gain", "rsa_status_string", "rsa_last_hip_error", "rsa_set_tuning", "rsa_set_shard_invariant", "rsa_gilbert_mapping",
-            "rsa_gilbert_block_neighbors", "rsa_permute_tokens", "rsa_qk_norm_rope", "rsa_qk_layernorm_rope", "rsa_norm_rope_heads", "rsa_fp8_operand_bytes",
-            "rsa_carve_fp8_operands", "rsa_quantize_fp8", "rsa_block_sparse_fwd_fp8", "rsa_block_sparse_fwd_fp8pv", "rsa_rectified_attention_fp8", "rsa_rectified_attention_fp8pv",
-            "rsa_pool_stats_fp8", "rsa_dense_fp8_bytes", "rsa_dense_fwd_fp8", "rsa_dense_causal_fwd_fp8", "rsa_dense_fwd_fp8pv", "rsa_rel_l1",
-            "rsa_comm_unique_id", "rsa_comm_create", "rsa_comm_destroy", "rsa_comm_count", "rsa_allgather_heads",
-            "rsa_allgather_heads_p2p", "rsa_p2p_state_bytes", "rsa_p2p_state_alloc", "rsa_p2p_state_free", "rsa_p2p_state_timeout", "rsa_ipc_export", "rsa_ipc_open", "rsa_ipc_close",
-            "rsa_ipc_offset", "rsa_buffer_bytes_ex", "rsa_carve_workspace_ex", "rsa_pool_stats_ex", "rsa_pooled_scores_ex",
-            "rsa_select_mask_ex", "rsa_compensation_ex", "rsa_block_sparse_fwd_ex", "rsa_rectified_attention_ex", "rsa_estimate_pr_gain_ex",
-            "rsa_block_mask_to_lists", "rsa_lists_to_block_mask", "rsa_block_sparse_plain_fwd", "rsa_block_sparse_ranged_fwd",
-            "rsa_block_sparse_gqa_fwd", "rsa_block_select_bytes", "rsa_block_select",
-            "rsa_block_sparse_decode_bytes", "rsa_block_sparse_decode",
-            "rsa_pool_keys", "rsa_block_select_pooled_bytes", "rsa_block_select_pooled",
-            "rsa_select_from_mask", "rsa_select_from_mask_ex", "rsa_rectified_attention_masked", "rsa_rectified_attention_masked_ex")
 
 
 def check(status: int, what: str):

@@ -20,6 +20,13 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
+The five calls above build_block_index share one argument layer, below _mask_u8: _check_operands (ranks, head counts, shapes, the
+one 2-byte dtype, the head dims a call serves), _check_limit / _device_limit (kv_len and start: host ints, or a device tensor that
+is never read on the host), _check_block_table / _table_args, _check_cache (a cache is not copied: the negation of what
+_core._as_bhsd copies), _empty_lists and _out4.  Every check runs on CPU tensors, before _core._require_device.  select_blocks and
+select_blocks_pooled are one body (_select); every K5 launch of block_sparse_attention, with ranges or without, grouped or not,
+leaves from _k5_launch.
+
 Difference from the reference kept on purpose: a query row that sees no key (no kept block, or every kept key at or beyond
 kv_len) is 0 here; the reference's Triton kernel divides 0 by 0 there and returns NaN.  In the rectified call over a caller's mask
 (the variants' block_mask=) such a visual row therefore comes out as comp alone, 0 * R + comp."""
@@ -52,6 +59,154 @@ def _mask_u8(block_mask: torch.Tensor) -> torch.Tensor:
     return m.view(torch.uint8) if m.dtype == torch.bool else m
 
 
+# ---- the argument layer of the five public calls: every check below runs on CPU tensors, before the device is asked for ----------
+HEAD_DIMS = (16, 32, 64, 128)
+
+
+def _check_block(what: str, block_size) -> int:
+    if block_size not in _lib.BLOCKS:
+        raise NotImplementedError(f"{what} on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
+    return int(block_size)
+
+
+def _check_count(name: str, val, lo: int, hi: Optional[int] = None, optional: bool = False):
+    """An int option in [lo, hi] (bool is refused); with optional, None passes."""
+    if val is None and optional:
+        return
+    if not isinstance(val, int) or isinstance(val, bool) or val < lo or (hi is not None and val > hi):
+        raise ValueError(f"{name}: {'None or ' if optional else ''}an int {f'in {lo}..{hi}' if hi is not None else f'>= {lo}'}, "
+                         f"got {val!r}")
+
+
+def _key_blocks(Sk: int, blk: int) -> int:
+    NK = -(-Sk // blk)
+    if NK > MAX_KEY_BLOCKS:
+        raise ValueError(f"Sk = {Sk} is {NK} key blocks of {blk}: at most {MAX_KEY_BLOCKS}")
+    return NK
+
+
+def _check_block_table(block_table, B: Optional[int] = None):
+    """int32 [B, NKt] (B: q's batch; None: the table gives it) -> its shape."""
+    ok = isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32 and block_table.dim() == 2
+    if not ok or block_table.shape[1] < 1 or (block_table.shape[0] < 1 if B is None else block_table.shape[0] != B):
+        raise ValueError(f"block_table: an int32 tensor [{'B' if B is None else B}, NKt], got "
+                         f"{getattr(block_table, 'dtype', type(block_table))} {tuple(getattr(block_table, 'shape', ()))}")
+    return block_table.shape
+
+
+def _table_args(block_table, pool):
+    """The C entries' (block_table, table_stride_b, num_pages) of a device table over the page pool, or of no table; and the
+    table they point into, for the caller to hold until the launch."""
+    if block_table is None:
+        return (None, 0, 0), None
+    _core._require_device(block_table)
+    table = block_table if block_table.stride(1) == 1 else block_table.contiguous()
+    return (table.data_ptr(), table.stride(0), pool.shape[0]), table
+
+
+def _check_operands(q, k, v=None, *, dims=HEAD_DIMS, block_table=None, blk: int = 0, pooled: bool = False):
+    """The tensor operands a call takes -> (B, H, Hkv, Sq, Sk, D).  q [B,H,Sq,D] or None (pool_keys: B from k, H = Hkv, Sq = 1);
+    k [B,Hkv,Sk,D], or with a block_table [B, NKt] a page pool [P,Hkv,blk,D] of capacity Sk = NKt * blk, or with pooled the
+    fp32 cache [B,Hkv,NK,D] of pool_keys (Sk is then NK); v like k, or None.  One 2-byte dtype; D among dims, the head dims the
+    call serves (another of HEAD_DIMS is NotImplementedError); nothing empty."""
+    kname = "pooled_k" if pooled else "k"
+    for t in (q, k, v):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 4):
+            raise ValueError(f"{_names(q, kname, v)}: 4-d tensors -- q [B, H, Sq, D], k / v [B, Hkv, Sk, D] or with block_table "
+                             "page pools [P, Hkv, block_size, D], pooled_k [B, Hkv, NK, D]")
+    kB, Hkv, Sk, kD = k.shape
+    B, H, Sq, D = (kB, Hkv, 1, kD) if q is None else q.shape
+    if v is not None and v.shape[1] != Hkv:
+        raise ValueError(f"k has Hkv = {Hkv} heads, v {v.shape[1]}: k and v must hold the same K/V heads")
+    if q is not None and (Hkv <= 0 or H % Hkv):
+        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h uses K/V head h // (H // Hkv))")
+    if block_table is not None:
+        fits = Sk == blk
+        B, NKt = _check_block_table(block_table, None if q is None else B)
+        Sk = NKt * blk
+    else:
+        fits = kB == B
+    if not fits or kD != D or (v is not None and v.shape != k.shape):
+        raise ValueError(f"{kname} {tuple(k.shape)}{'' if v is None else f' / v {tuple(v.shape)}'} does not match"
+                         f"{'' if q is None else f' q {tuple(q.shape)}'}"
+                         + (f": with a block_table k / v are page pools [P, Hkv, {blk}, {D}]" if block_table is not None else ""))
+    dt = k.dtype if q is None else q.dtype
+    if dt not in (torch.bfloat16, torch.float16) or (not pooled and k.dtype != dt) or (v is not None and v.dtype != dt):
+        raise ValueError(f"{_names(q, kname, v)}: one dtype, bfloat16 or float16 (pooled_k apart), got "
+                         f"{', '.join(str(t.dtype) for t in (q, k, v) if t is not None)}")
+    if pooled and (k.dtype != torch.float32 or not k.is_contiguous()):
+        raise ValueError(f"pooled_k: a contiguous float32 tensor (pool_keys' result), got dtype {k.dtype}, "
+                         f"strides {tuple(k.stride())}")
+    if D not in dims:
+        if D in HEAD_DIMS:
+            raise NotImplementedError(f"head dim {D}: this call serves {dims} (padding a cache would copy it)")
+        raise ValueError(f"head dim {D}: one of {dims}")
+    if B <= 0 or Hkv <= 0 or Sq <= 0 or Sk <= 0:
+        raise ValueError(f"empty operands (B = {B}, Hkv = {Hkv}, Sq = {Sq}, {'NK' if pooled else 'Sk'} = {Sk})")
+    return B, H, Hkv, Sq, Sk, D
+
+
+def _names(q, kname: str, v) -> str:
+    return ", ".join(n for n, t in (("q", q), (kname, True), ("v", v)) if t is not None)
+
+
+def _check_cache(k, v=None):
+    """A K/V cache is read where it lies: what _core._as_bhsd would copy is refused."""
+    for name, t in (("k", k), ("v", v)):
+        if t is not None and not _core._read_in_place(t):
+            raise ValueError(f"{name}: a contiguous head dim, strides that are multiples of 8 elements and a 16-byte aligned "
+                             f"pointer (a cache is not copied), got strides {tuple(t.stride())}, pointer % 16 = {t.data_ptr() % 16}")
+
+
+def _check_limit(name: str, val, B: int, Sk: int, default: int, device_ok: bool = True):
+    """A key limit (kv_len, start): None (= default) | int | per-batch sequence | host tensor (one host read) -> list of B ints
+    in [0, Sk].  A device tensor is checked and passed on unread -- or, where the call has no device form (device_ok False),
+    read like a host tensor."""
+    if device_ok and isinstance(val, torch.Tensor) and val.is_cuda:
+        if val.numel() not in (1, B) or val.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{name}: an int32 / int64 tensor of 1 or {B} values, got {val.dtype} {tuple(val.shape)}")
+        return val
+    if val is None:
+        lens = [default] * B
+    elif isinstance(val, int):
+        lens = [int(val)] * B
+    else:
+        vals = val.reshape(-1).tolist() if isinstance(val, torch.Tensor) else list(val)
+        if len(vals) == 1:
+            vals = vals * B
+        if len(vals) != B:
+            raise ValueError(f"{name}: {len(vals)} values for a batch of {B}")
+        lens = [int(x) for x in vals]
+    if any(n < 0 or n > Sk for n in lens):
+        raise ValueError(f"{name} {lens} outside [0, {Sk}]")
+    return lens
+
+
+def _device_limit(val, B: int, Sk: int, dev):
+    """What _check_limit returned, for the C entries: (device int32 [B] | None, host int, host list | None).  A device tensor is
+    clamped into [0, Sk] on the device and never read on the host."""
+    if isinstance(val, torch.Tensor):
+        return val.to(dev).reshape(-1).clamp(0, Sk).to(torch.int32).expand(B).contiguous(), Sk, None
+    if len(set(val)) == 1:
+        return None, val[0], val
+    return torch.tensor(val, dtype=torch.int32, device=dev), Sk, val
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _out4(t: torch.Tensor) -> RsaOut4:
+    return RsaOut4(t.data_ptr(), t.stride(0), t.stride(1), t.stride(2))
+
+
+def _empty_lists(rows: int, NQ: int, NK: int, dev) -> Dict[str, torch.Tensor]:
+    """Unwritten kept lists of rows list heads (the rsa_buffers format block_mask_to_lists describes)."""
+    return dict(bitmask=torch.empty((rows, NQ, (NK + 31) // 32), dtype=torch.int32, device=dev),
+                cols=torch.empty((rows, NQ, NK), dtype=torch.int32, device=dev),
+                counts=torch.empty((rows, NQ), dtype=torch.int32, device=dev))
+
+
 def block_mask_to_lists(block_mask: torch.Tensor, B: int, H: int) -> Dict[str, torch.Tensor]:
     """[B|1, H|1, NQ, NK] bool / uint8 device mask (nonzero = kept) -> K5's kept lists, the rsa_buffers format:
     bitmask int32 [B*H, NQ, ceil(NK/32)], cols int32 [B*H, NQ, NK] (ascending, first counts entries written), counts [B*H, NQ]."""
@@ -66,9 +221,7 @@ def block_mask_to_lists(block_mask: torch.Tensor, B: int, H: int) -> Dict[str, t
     NQ, NK = m.shape[2], m.shape[3]
     strides = [0 if m.shape[i] == 1 else m.stride(i) for i in range(3)]
     dev = m.device
-    out = dict(bitmask=torch.empty((B * H, NQ, (NK + 31) // 32), dtype=torch.int32, device=dev),
-               cols=torch.empty((B * H, NQ, NK), dtype=torch.int32, device=dev),
-               counts=torch.empty((B * H, NQ), dtype=torch.int32, device=dev))
+    out = _empty_lists(B * H, NQ, NK, dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().rsa_block_mask_to_lists(B, H, NQ, NK, m.data_ptr(), *strides, out["bitmask"].data_ptr(),
                                                       out["cols"].data_ptr(), out["counts"].data_ptr(), _core._stream()),
@@ -121,30 +274,6 @@ def _tail_buffer(device) -> torch.Tensor:
     if buf is None:
         buf = _TAIL_CACHE[key] = torch.empty(shape, dtype=torch.float32, device=dev)
     return buf
-
-
-def _kv_lens(kv_len, B: int, Sk: int):
-    """None | int | per-batch sequence | tensor (one host read) -> list of B ints in [0, Sk]."""
-    if kv_len is None:
-        lens = [Sk] * B
-    elif isinstance(kv_len, int):
-        lens = [int(kv_len)] * B
-    else:
-        vals = kv_len.reshape(-1).tolist() if isinstance(kv_len, torch.Tensor) else list(kv_len)
-        if len(vals) == 1:
-            vals = vals * B
-        if len(vals) != B:
-            raise ValueError(f"kv_len: {len(vals)} values for a batch of {B}")
-        lens = [int(x) for x in vals]
-    if any(n < 0 or n > Sk for n in lens):
-        raise ValueError(f"kv_len {lens} outside [0, {Sk}]")
-    return lens
-
-
-def _list_heads(block_mask: torch.Tensor, H: int, Hkv: int) -> int:
-    """List heads per batch item of a call: with as many K/V heads as query heads H, as ever (a mask head axis of 1 is expanded);
-    with fewer, the mask's own head axis -- 1, Hkv or H -- so that shared lists are built and kept once."""
-    return H if Hkv == H else int(block_mask.shape[1])
 
 
 _RANGE_CACHE: "Dict[tuple, tuple]" = {}
@@ -205,49 +334,49 @@ def _window_ranges(device, B: int, Sq: int, Sk: int, lens, left: int, right: int
     return out
 
 
-def _ranged_attention(q, k, v, block_mask, lens, scale: float, lo, hi) -> torch.Tensor:
-    """One launch of rsa_block_sparse_ranged_fwd for the whole batch.  lens: B host ints, or a device tensor [B|1] (not read)."""
+def _k5_launch(q, k, v, block_mask, blk: int, scale: float, groups, lo=None, hi=None) -> torch.Tensor:
+    """block_sparse_attention's launches.  groups: (b0, b1, key limit) runs of batch items, one launch each -- a call with
+    ranges (hi given; lo None = 0; int32 [B|1, Sq]) has one for the whole batch.  The C entry: rsa_block_sparse_gqa_fwd iff k / v
+    hold fewer heads than q, else rsa_block_sparse_ranged_fwd iff there are ranges, else rsa_block_sparse_plain_fwd."""
     B, H, Sq, D = q.shape
-    Hkv, Sk = k.shape[1], k.shape[2]
-    if isinstance(lens, torch.Tensor):
-        kv_valid = Sk
-    else:
-        kv_valid = max(lens)
-        if kv_valid == 0:   # no visible key at all
-            return torch.zeros((B, H, Sq, D), dtype=q.dtype, device=q.device)
     if D in _core._PAD_HEAD_DIM:   # zero columns add exact zeros to every dot product; the caller's scale is kept
         pad = (0, _core._PAD_HEAD_DIM[D] - D)
         F = torch.nn.functional
-        return _ranged_attention(F.pad(q, pad), F.pad(k, pad), F.pad(v, pad), block_mask, lens, scale, lo, hi)[..., :D].contiguous()
-    if lo is not None and lo.shape[0] != hi.shape[0]:
-        lo = lo.expand(hi.shape[0], Sq) if lo.shape[0] == 1 else lo
-        hi = hi.expand(lo.shape[0], Sq) if hi.shape[0] == 1 else hi
-    lo = None if lo is None else lo.contiguous()
-    hi = hi.contiguous()
+        return _k5_launch(F.pad(q, pad), F.pad(k, pad), F.pad(v, pad), block_mask, blk, scale, groups, lo, hi)[..., :D].contiguous()
+    Hkv, Sk = k.shape[1], k.shape[2]
+    ranges = ()
+    if hi is not None:
+        if lo is not None and lo.shape[0] != hi.shape[0]:
+            lo = lo.expand(hi.shape[0], Sq) if lo.shape[0] == 1 else lo
+            hi = hi.expand(lo.shape[0], Sq) if hi.shape[0] == 1 else hi
+        lo, hi = None if lo is None else lo.contiguous(), hi.contiguous()
+        ranges = (_ptr(lo), hi.data_ptr(), 0 if hi.shape[0] == 1 else Sq)
     L = _lib.lib()
     q, k, v = _core._as_bhsd(q), _core._as_bhsd(k), _core._as_bhsd(v)
-    NQ, NK = -(-Sq // _lib.BLOCK), block_mask.shape[3]
-    Hl = _list_heads(block_mask, H, Hkv)
+    NQ, NK = -(-Sq // blk), block_mask.shape[3]
+    # list heads per batch item: H with as many K/V heads as query heads (a mask head axis of 1 is expanded); with fewer, the
+    # mask's own head axis -- 1, Hkv or H -- so that shared lists are built and kept once
+    Hl = H if Hkv == H else int(block_mask.shape[1])
     lists = block_mask_to_lists(block_mask, B, Hl)
     out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=q.device)
-    tpart = _tail_buffer(q.device) if D == 128 else None
+    # the tail split's partial buffer (head dim 128, 128-token blocks: the rectified call's K5 gets the same)
+    tpart = _tail_buffer(q.device) if D == 128 and blk == _lib.BLOCK else None
     tp, tpb = (tpart.data_ptr(), tpart.numel() * 4) if tpart is not None else (None, 0)
+    dt = _core.dtype_code(q.dtype)
     if Hkv != H:
-        with torch.cuda.device(q.device):
-            _lib.check(L.rsa_block_sparse_gqa_fwd(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), _lib.BLOCK, NQ, NK, kv_valid,
-                                                  scale, _core._t4(q), _core._t4(k), _core._t4(v), lists["cols"].data_ptr(),
-                                                  lists["counts"].data_ptr(), lo.data_ptr() if lo is not None else None,
-                                                  hi.data_ptr(), 0 if hi.shape[0] == 1 else Sq, tp, tpb,
-                                                  RsaOut4(out.data_ptr(), out.stride(0), out.stride(1), out.stride(2)),
-                                                  _core._stream()), "rsa_block_sparse_gqa_fwd")
-        return out
+        entry, heads, ranges = "rsa_block_sparse_gqa_fwd", (H, Hkv, Hl), ranges or (None, None, 0)
+    else:
+        entry, heads = "rsa_block_sparse_ranged_fwd" if ranges else "rsa_block_sparse_plain_fwd", (H,)
     with torch.cuda.device(q.device):
-        _lib.check(L.rsa_block_sparse_ranged_fwd(B, H, Sq, Sk, D, _core.dtype_code(q.dtype), _lib.BLOCK, NQ, NK, kv_valid, scale,
-                                                 _core._t4(q), _core._t4(k), _core._t4(v), lists["cols"].data_ptr(),
-                                                 lists["counts"].data_ptr(), lo.data_ptr() if lo is not None else None, hi.data_ptr(),
-                                                 0 if hi.shape[0] == 1 else Sq, tp, tpb,
-                                                 RsaOut4(out.data_ptr(), out.stride(0), out.stride(1), out.stride(2)), _core._stream()),
-                   "rsa_block_sparse_ranged_fwd")
+        for b0, b1, n in groups:
+            if n == 0:   # no visible key at all
+                out[b0:b1].zero_()
+                continue
+            row = Hl * NQ * b0
+            _lib.check(getattr(L, entry)(b1 - b0, *heads, Sq, Sk, D, dt, blk, NQ, NK, n, scale, _core._t4(q[b0:b1]),
+                                         _core._t4(k[b0:b1]), _core._t4(v[b0:b1]), lists["cols"].data_ptr() + row * NK * 4,
+                                         lists["counts"].data_ptr() + row * 4, *ranges, tp, tpb, _out4(out[b0:b1]),
+                                         _core._stream()), entry)
     return out
 
 
@@ -289,23 +418,7 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
                                   "32-rows-per-wave kernel, which has one key limit per launch and no per-row range")
     if window is not None:
         window = _check_window(window)
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("q, k, v: [B, H, S, D] tensors")
-    B, H, Sq, D = q.shape
-    Sk = k.shape[2]
-    Hkv = k.shape[1]
-    if v.shape[1] != Hkv:
-        raise ValueError(f"k has Hkv = {Hkv} heads, v {v.shape[1]}: k and v must hold the same K/V heads")
-    if Hkv <= 0 or H % Hkv:
-        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h reads K/V head h // (H // Hkv))")
-    if k.shape != v.shape or k.shape[0] != B or k.shape[3] != D:
-        raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError(f"q, k, v: one dtype, bfloat16 or float16 (got {q.dtype}, {k.dtype}, {v.dtype})")
-    if D not in (16, 32, 64, 128):
-        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
-    if Sq <= 0 or Sk <= 0:
-        raise ValueError(f"empty operands (Sq = {Sq}, Sk = {Sk})")
+    B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v)
     NQ, NKmax = -(-Sq // blk), -(-Sk // blk)
     if block_mask.dim() != 4 or block_mask.dtype not in (torch.bool, torch.uint8):
         raise ValueError(f"block_mask: a 4-d bool or uint8 tensor, got {block_mask.dtype} {tuple(block_mask.shape)}")
@@ -318,62 +431,30 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
                          f"for block {blk} (at most {MAX_KEY_BLOCKS} key blocks)")
     if row_range is not None:
         row_range = _check_row_range(row_range, B, Sq, q.device)
-    on_device = ranged and isinstance(kv_len, torch.Tensor) and kv_len.is_cuda   # (then it is folded on the device, not read)
-    if on_device:
-        if kv_len.numel() not in (1, B) or kv_len.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"kv_len: an int32 / int64 tensor of 1 or {B} values, got {kv_len.dtype} {tuple(kv_len.shape)}")
-        lens = kv_len.to(q.device).reshape(-1)
-    else:
-        lens = _kv_lens(kv_len, B, Sk)
+    # with a range a device kv_len is folded on the device and not read; without one every kv_len becomes host ints
+    lens = _check_limit("kv_len", kv_len, B, Sk, Sk, device_ok=ranged)
     _core._require_device(q, k, v)
     scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
     if block_mask.device != q.device:
         block_mask = block_mask.to(q.device)
-    if ranged:
-        if row_range is None:
-            lo, hi = _window_ranges(q.device, B, Sq, Sk, lens, *((-1, 0) if causal else window))
-        else:
-            lo, hi = row_range
-            if on_device:
-                hi = torch.minimum(hi, lens.reshape(-1, 1).clamp(0, Sk).to(torch.int32))
-            elif any(n != Sk for n in lens):     # fold the host limits: one small device op per distinct limit, no host read
-                hi = torch.stack([hi[b if hi.shape[0] > 1 else 0].clamp(max=lens[b]) for b in range(B)])
-        return _ranged_attention(q, k, v, block_mask, lens, scale, lo, hi)
-    if D in _core._PAD_HEAD_DIM:   # zero columns add exact zeros to every dot product; the caller's scale is kept
-        pad = (0, _core._PAD_HEAD_DIM[D] - D)
-        F = torch.nn.functional
-        return block_sparse_attention(F.pad(q, pad), F.pad(k, pad), F.pad(v, pad), block_mask, kv_len=lens, sm_scale=scale,
-                                      block_size=blk)[..., :D].contiguous()
-    L = _lib.lib()
-    q, k, v = _core._as_bhsd(q), _core._as_bhsd(k), _core._as_bhsd(v)
-    NK = block_mask.shape[3]
-    Hl = _list_heads(block_mask, H, Hkv)
-    lists = block_mask_to_lists(block_mask, B, Hl)
-    out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=q.device)
-    # the tail split's partial buffer (head dim 128, 128-token blocks: the rectified call's K5 gets the same)
-    tpart = _tail_buffer(q.device) if D == 128 and blk == _lib.BLOCK else None
-    tp, tpb = (tpart.data_ptr(), tpart.numel() * 4) if tpart is not None else (None, 0)
-    dt = _core.dtype_code(q.dtype)
-    # one launch for the whole batch when the key limits agree, else one per batch item
-    groups = [(0, B, lens[0])] if len(set(lens)) == 1 else [(b, b + 1, lens[b]) for b in range(B)]
-    with torch.cuda.device(q.device):
-        for b0, b1, n in groups:
-            if n == 0:   # no visible key at all
-                out[b0:b1].zero_()
-                continue
-            row = Hl * NQ * b0
-            o4 = RsaOut4(out[b0].data_ptr(), out.stride(0), out.stride(1), out.stride(2))
-            if Hkv != H:
-                _lib.check(L.rsa_block_sparse_gqa_fwd(b1 - b0, H, Hkv, Hl, Sq, Sk, D, dt, blk, NQ, NK, n, scale, _core._t4(q[b0:b1]),
-                                                      _core._t4(k[b0:b1]), _core._t4(v[b0:b1]),
-                                                      lists["cols"].data_ptr() + row * NK * 4, lists["counts"].data_ptr() + row * 4,
-                                                      None, None, 0, tp, tpb, o4, _core._stream()), "rsa_block_sparse_gqa_fwd")
-                continue
-            _lib.check(L.rsa_block_sparse_plain_fwd(b1 - b0, H, Sq, Sk, D, dt, blk, NQ, NK, n, scale, _core._t4(q[b0:b1]),
-                                                    _core._t4(k[b0:b1]), _core._t4(v[b0:b1]),
-                                                    lists["cols"].data_ptr() + row * NK * 4, lists["counts"].data_ptr() + row * 4,
-                                                    tp, tpb, o4, _core._stream()), "rsa_block_sparse_plain_fwd")
-    return out
+    if not ranged:   # one launch for the whole batch when the key limits agree, else one per batch item
+        groups = [(0, B, lens[0])] if len(set(lens)) == 1 else [(b, b + 1, lens[b]) for b in range(B)]
+        return _k5_launch(q, k, v, block_mask, blk, scale, groups)
+    on_device = isinstance(lens, torch.Tensor)
+    if on_device:
+        lens = lens.to(q.device).reshape(-1)
+    if row_range is None:
+        lo, hi = _window_ranges(q.device, B, Sq, Sk, lens, *((-1, 0) if causal else window))
+    else:
+        lo, hi = row_range
+        if on_device:
+            hi = torch.minimum(hi, lens.reshape(-1, 1).clamp(0, Sk).to(torch.int32))
+        elif any(n != Sk for n in lens):     # fold the host limits: one small device op per distinct limit, no host read
+            hi = torch.stack([hi[b if hi.shape[0] > 1 else 0].clamp(max=lens[b]) for b in range(B)])
+    kv_valid = Sk if on_device else max(lens)
+    if kv_valid == 0:   # no visible key at all
+        return torch.zeros((B, H, Sq, D), dtype=q.dtype, device=q.device)
+    return _k5_launch(q, k, v, block_mask, blk, scale, [(0, B, kv_valid)], lo, hi)
 
 
 def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None, causal: bool = False,
@@ -399,89 +480,54 @@ def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: i
     (bitmask, cols, counts; row (b * Hl + hl) * NQ + i); with return_scores=True a pair, the second the fp32 scores
     [B, Hl, NQ, NK] with -inf at invisible blocks.  Two calls on the same inputs give the same bytes.  With non-finite scores
     which blocks win is unspecified; the rows stay well formed.  Asynchronous on the current stream."""
-    if block_size not in _lib.BLOCKS:
-        raise NotImplementedError(f"select_blocks on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
-    blk = int(block_size)
-    if mask_heads not in ("kv", "q"):
-        raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
-    for name, val in (("top_k", top_k), ("keep_first", keep_first), ("keep_local", keep_local)):
-        if not isinstance(val, int) or isinstance(val, bool) or val < 0:
-            raise ValueError(f"{name}: an int >= 0, got {val!r}")
-    if q.dim() != 4 or k.dim() != 4:
-        raise ValueError("q, k: [B, H, S, D] tensors")
-    B, H, Sq, D = q.shape
-    Hkv, Sk = k.shape[1], k.shape[2]
-    if Hkv <= 0 or H % Hkv:
-        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h belongs to K/V head h // (H // Hkv))")
-    if k.shape[0] != B or k.shape[3] != D:
-        raise ValueError(f"k {tuple(k.shape)} does not match q {tuple(q.shape)}")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype:
-        raise ValueError(f"q, k: one dtype, bfloat16 or float16 (got {q.dtype}, {k.dtype})")
-    if D not in (16, 32, 64, 128):
-        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
-    if Sq <= 0 or Sk <= 0:
-        raise ValueError(f"empty operands (Sq = {Sq}, Sk = {Sk})")
-    NQ, NK = -(-Sq // blk), -(-Sk // blk)
-    if NK > MAX_KEY_BLOCKS:
-        raise ValueError(f"Sk = {Sk} is {NK} key blocks of {blk}: at most {MAX_KEY_BLOCKS}")
-    Hl = Hkv if mask_heads == "kv" else H
-    on_device = isinstance(kv_len, torch.Tensor) and kv_len.is_cuda      # (then it is read on the device only)
-    if on_device:
-        if kv_len.numel() not in (1, B) or kv_len.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"kv_len: an int32 / int64 tensor of 1 or {B} values, got {kv_len.dtype} {tuple(kv_len.shape)}")
-        lens = None
-    else:
-        lens = _kv_lens(kv_len, B, Sk)
-    _core._require_device(q, k)
-    dev = q.device
-    if on_device:
-        kv_dev, kv_valid = kv_len.to(dev).reshape(-1).clamp(0, Sk).to(torch.int32).expand(B).contiguous(), Sk
-    elif len(set(lens)) == 1:
-        kv_dev, kv_valid = None, lens[0]
-    else:
-        kv_dev, kv_valid = torch.tensor(lens, dtype=torch.int32, device=dev), Sk
-    L = _lib.lib()
-    q, k = _core._as_bhsd(q), _core._as_bhsd(k)
-    need = ctypes.c_size_t(0)
-    _lib.check(L.rsa_block_select_bytes(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), "rsa_block_select_bytes")
-    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
-    out = dict(bitmask=torch.empty((B * Hl, NQ, (NK + 31) // 32), dtype=torch.int32, device=dev),
-               cols=torch.empty((B * Hl, NQ, NK), dtype=torch.int32, device=dev),
-               counts=torch.empty((B * Hl, NQ), dtype=torch.int32, device=dev))
-    scores = torch.empty((B, Hl, NQ, NK), dtype=torch.float32, device=dev) if return_scores else None
-    with torch.cuda.device(dev):
-        _lib.check(L.rsa_block_select(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NQ, NK, _core._t4(q), _core._t4(k),
-                                      kv_dev.data_ptr() if kv_dev is not None else None, kv_valid, int(bool(causal)),
-                                      min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), ws.data_ptr(), need.value,
-                                      out["bitmask"].data_ptr(), out["cols"].data_ptr(), out["counts"].data_ptr(),
-                                      scores.data_ptr() if scores is not None else None, _core._stream()), "rsa_block_select")
-    sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
-    return (sel, scores) if return_scores else sel
+    return _select("select_blocks", q, k, False, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
+                   return_scores, as_lists)
 
 
 MAX_SCORE_SPLITS = 256  # score workgroups per list row of select_blocks_pooled, at most (rsa_block_select.hip)
 
 
-def _device_limit(val, B: int, Sk: int, dev):
-    """What _check_limit returned, for the C entries: (device int32 [B] | None, host int, host list | None).  A device tensor is
-    clamped into [0, Sk] on the device and never read on the host."""
-    if isinstance(val, torch.Tensor):
-        return val.to(dev).reshape(-1).clamp(0, Sk).to(torch.int32).expand(B).contiguous(), Sk, None
-    if len(set(val)) == 1:
-        return None, val[0], val
-    return torch.tensor(val, dtype=torch.int32, device=dev), Sk, val
-
-
-def _check_limit(name: str, val, B: int, Sk: int, default: int):
-    """None | int | per-batch sequence | host tensor -> list of B ints in [0, Sk]; a device tensor is checked and passed on."""
-    if isinstance(val, torch.Tensor) and val.is_cuda:
-        if val.numel() not in (1, B) or val.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"{name}: an int32 / int64 tensor of 1 or {B} values, got {val.dtype} {tuple(val.shape)}")
-        return val
-    try:
-        return _kv_lens(default if val is None else val, B, Sk)
-    except ValueError as e:
-        raise ValueError(str(e).replace("kv_len", name, 1)) from None
+def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
+            return_scores, as_lists, score_splits=None):
+    """select_blocks (keys = k, rsa_block_select) and select_blocks_pooled (keys = pool_keys' cache, rsa_block_select_pooled,
+    with its score_splits): the two differ in where kbar comes from and in nothing else."""
+    blk = _check_block(what, block_size)
+    if mask_heads not in ("kv", "q"):
+        raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
+    for name, val in (("top_k", top_k), ("keep_first", keep_first), ("keep_local", keep_local)):
+        _check_count(name, val, 0)
+    _check_count("score_splits", score_splits, 1, MAX_SCORE_SPLITS, optional=True)
+    B, H, Hkv, Sq, Sk, D = _check_operands(q, keys, pooled=pooled)
+    if pooled:      # the cache holds NK blocks: the capacity is taken as NK * block
+        Sk *= blk
+    NQ, NK = -(-Sq // blk), _key_blocks(Sk, blk)
+    Hl = Hkv if mask_heads == "kv" else H
+    lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
+    _core._require_device(q, keys)
+    dev = q.device
+    if pooled and keys.data_ptr() % 16:
+        raise ValueError("pooled_k: 16-byte aligned")
+    kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
+    L = _lib.lib()
+    q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
+    entry = "rsa_block_select_pooled" if pooled else "rsa_block_select"
+    need = ctypes.c_size_t(0)
+    _lib.check(getattr(L, entry + "_bytes")(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), entry + "_bytes")
+    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+    out = _empty_lists(B * Hl, NQ, NK, dev)
+    scores = torch.empty((B, Hl, NQ, NK), dtype=torch.float32, device=dev) if return_scores else None
+    if pooled:
+        shape, source = (B, H, Hkv, Hl, Sq, D), keys.data_ptr()
+        splits = (0 if score_splits is None else int(score_splits),)
+    else:
+        shape, source, splits = (B, H, Hkv, Hl, Sq, Sk, D), _core._t4(keys), ()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, NQ, NK, _core._t4(q), source, _ptr(kv_dev), kv_valid,
+                                     int(bool(causal)), min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), *splits,
+                                     ws.data_ptr(), need.value, out["bitmask"].data_ptr(), out["cols"].data_ptr(),
+                                     out["counts"].data_ptr(), _ptr(scores), _core._stream()), entry)
+    sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
+    return (sel, scores) if return_scores else sel
 
 
 def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_table=None, out: Optional[torch.Tensor] = None,
@@ -504,36 +550,10 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
     workgroups_per_head: workgroups per (b, K/V head) that stride over the block range -- a performance hint, any count >= 1
     gives the same bytes.  None: the exact count when both limits are host values, NKt with start=None, else 2 (an append of
     at most block tokens touches at most two blocks).  Asynchronous on the current stream, no host synchronisation, capturable."""
-    if block_size not in _lib.BLOCKS:
-        raise NotImplementedError(f"pool_keys on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
-    blk = int(block_size)
-    if workgroups_per_head is not None and (not isinstance(workgroups_per_head, int) or isinstance(workgroups_per_head, bool)
-                                            or workgroups_per_head < 1):
-        raise ValueError(f"workgroups_per_head: None or an int >= 1, got {workgroups_per_head!r}")
-    if not isinstance(k, torch.Tensor) or k.dim() != 4:
-        raise ValueError("k: a [B, Hkv, Sk, D] tensor, or a page pool [P, Hkv, block_size, D] with block_table")
-    Hkv, D = k.shape[1], k.shape[3]
-    paged = block_table is not None
-    if paged:
-        if (not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
-                or block_table.shape[0] < 1 or block_table.shape[1] < 1):
-            raise ValueError(f"block_table: an int32 tensor [B, NKt], got {getattr(block_table, 'dtype', type(block_table))} "
-                             f"{tuple(getattr(block_table, 'shape', ()))}")
-        if k.shape[2] != blk:
-            raise ValueError(f"k {tuple(k.shape)}: with a block_table it is a page pool [P, Hkv, {blk}, D]")
-        B, NK = block_table.shape
-        Sk = NK * blk
-    else:
-        B, Sk = k.shape[0], k.shape[2]
-        NK = -(-Sk // blk)
-    if k.dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError(f"k: bfloat16 or float16, got dtype {k.dtype}")
-    if D not in (16, 32, 64, 128):
-        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
-    if B <= 0 or Hkv <= 0 or Sk <= 0:
-        raise ValueError(f"empty operands (B = {B}, Hkv = {Hkv}, Sk = {Sk})")
-    if NK > MAX_KEY_BLOCKS:
-        raise ValueError(f"Sk = {Sk} is {NK} key blocks of {blk}: at most {MAX_KEY_BLOCKS}")
+    blk = _check_block("pool_keys", block_size)
+    _check_count("workgroups_per_head", workgroups_per_head, 1, optional=True)
+    B, _, Hkv, _, Sk, D = _check_operands(None, k, block_table=block_table, blk=blk)
+    NK = _key_blocks(Sk, blk)
     if start is not None and out is None:
         raise ValueError("out: required when start is given (an update writes into the cache it is given)")
     if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, Hkv, NK, D)
@@ -542,12 +562,8 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
                          f"{tuple(getattr(out, 'shape', ()))}")
     lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
     starts = _check_limit("start", start, B, Sk, 0)
-    if k.stride(-1) != 1 or any(st % 8 for st in k.stride()[:-1]) or any(st < 0 for st in k.stride()):
-        raise ValueError(f"k: a contiguous head dim and strides that are multiples of 8 elements (a cache is not copied), "
-                         f"got strides {tuple(k.stride())}")
+    _check_cache(k)
     _core._require_device(k)
-    if k.data_ptr() % 16:
-        raise ValueError("k: 16-byte aligned (a cache is not copied)")
     dev = k.device
     if out is None:
         out = torch.empty((B, Hkv, NK, D), dtype=torch.float32, device=dev)
@@ -555,10 +571,7 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
         _core._require_device(out)
     if out.data_ptr() % 16:
         raise ValueError("out: 16-byte aligned")
-    table = None
-    if paged:
-        _core._require_device(block_table)
-        table = block_table if block_table.stride(1) == 1 else block_table.contiguous()
+    table, _held = _table_args(block_table, k)
     kv_dev, kv_valid, lens = _device_limit(lens, B, Sk, dev)
     st_dev, st_host, starts = _device_limit(starts, B, Sk, dev)
     if workgroups_per_head is not None:
@@ -568,12 +581,9 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
     else:
         wph = NK if start is None else 2
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rsa_pool_keys(B, Hkv, Sk, D, _core.dtype_code(k.dtype), blk, NK, _core._t4(k),
-                                            table.data_ptr() if table is not None else None,
-                                            table.stride(0) if table is not None else 0, k.shape[0] if paged else 0,
-                                            kv_dev.data_ptr() if kv_dev is not None else None, kv_valid,
-                                            st_dev.data_ptr() if st_dev is not None else None, st_host, wph, out.data_ptr(),
-                                            _core._stream()), "rsa_pool_keys")
+        _lib.check(_lib.lib().rsa_pool_keys(B, Hkv, Sk, D, _core.dtype_code(k.dtype), blk, NK, _core._t4(k), *table,
+                                            _ptr(kv_dev), kv_valid, _ptr(st_dev), st_host, wph, out.data_ptr(), _core._stream()),
+                   "rsa_pool_keys")
     return out
 
 
@@ -591,63 +601,8 @@ def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *,
     score_splits: workgroups per list row that compute the row's scores before the select workgroup ranks them (few list rows,
     many key blocks: a decode step); 1 = inside the select workgroup; None = the library's choice, a function of the shapes alone
     (measured: DESIGN.md 5.13).  Every value gives the same bytes.  Asynchronous on the current stream, capturable."""
-    if block_size not in _lib.BLOCKS:
-        raise NotImplementedError(f"select_blocks_pooled on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
-    blk = int(block_size)
-    if mask_heads not in ("kv", "q"):
-        raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
-    for name, val in (("top_k", top_k), ("keep_first", keep_first), ("keep_local", keep_local)):
-        if not isinstance(val, int) or isinstance(val, bool) or val < 0:
-            raise ValueError(f"{name}: an int >= 0, got {val!r}")
-    if score_splits is not None and (not isinstance(score_splits, int) or isinstance(score_splits, bool)
-                                     or not 1 <= score_splits <= MAX_SCORE_SPLITS):
-        raise ValueError(f"score_splits: None or an int in 1..{MAX_SCORE_SPLITS}, got {score_splits!r}")
-    if not isinstance(q, torch.Tensor) or not isinstance(pooled_k, torch.Tensor) or q.dim() != 4 or pooled_k.dim() != 4:
-        raise ValueError("q: a [B, H, Sq, D] tensor, pooled_k: a [B, Hkv, NK, D] tensor")
-    B, H, Sq, D = q.shape
-    Hkv, NK = pooled_k.shape[1], pooled_k.shape[2]
-    if Hkv <= 0 or H % Hkv:
-        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h belongs to K/V head h // (H // Hkv))")
-    if pooled_k.shape[0] != B or pooled_k.shape[3] != D:
-        raise ValueError(f"pooled_k {tuple(pooled_k.shape)} does not match q {tuple(q.shape)}")
-    if q.dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError(f"q: bfloat16 or float16, got dtype {q.dtype}")
-    if pooled_k.dtype != torch.float32 or not pooled_k.is_contiguous():
-        raise ValueError(f"pooled_k: a contiguous float32 tensor (pool_keys' result), got dtype {pooled_k.dtype}, "
-                         f"strides {tuple(pooled_k.stride())}")
-    if D not in (16, 32, 64, 128):
-        raise ValueError(f"head dim {D}: 16, 32, 64 or 128")
-    if Sq <= 0 or NK <= 0:
-        raise ValueError(f"empty operands (Sq = {Sq}, NK = {NK})")
-    if NK > MAX_KEY_BLOCKS:
-        raise ValueError(f"pooled_k holds {NK} key blocks: at most {MAX_KEY_BLOCKS}")
-    NQ, Sk = -(-Sq // blk), NK * blk
-    Hl = Hkv if mask_heads == "kv" else H
-    lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
-    _core._require_device(q, pooled_k)
-    dev = q.device
-    if pooled_k.data_ptr() % 16:
-        raise ValueError("pooled_k: 16-byte aligned")
-    kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
-    L = _lib.lib()
-    q = _core._as_bhsd(q)
-    need = ctypes.c_size_t(0)
-    _lib.check(L.rsa_block_select_pooled_bytes(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), "rsa_block_select_pooled_bytes")
-    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
-    out = dict(bitmask=torch.empty((B * Hl, NQ, (NK + 31) // 32), dtype=torch.int32, device=dev),
-               cols=torch.empty((B * Hl, NQ, NK), dtype=torch.int32, device=dev),
-               counts=torch.empty((B * Hl, NQ), dtype=torch.int32, device=dev))
-    scores = torch.empty((B, Hl, NQ, NK), dtype=torch.float32, device=dev) if return_scores else None
-    with torch.cuda.device(dev):
-        _lib.check(L.rsa_block_select_pooled(B, H, Hkv, Hl, Sq, D, _core.dtype_code(q.dtype), blk, NQ, NK, _core._t4(q),
-                                             pooled_k.data_ptr(), kv_dev.data_ptr() if kv_dev is not None else None, kv_valid,
-                                             int(bool(causal)), min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1),
-                                             0 if score_splits is None else int(score_splits), ws.data_ptr(), need.value,
-                                             out["bitmask"].data_ptr(), out["cols"].data_ptr(), out["counts"].data_ptr(),
-                                             scores.data_ptr() if scores is not None else None, _core._stream()),
-                   "rsa_block_select_pooled")
-    sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
-    return (sel, scores) if return_scores else sel
+    return _select("select_blocks_pooled", q, pooled_k, True, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
+                   return_scores, as_lists, score_splits)
 
 
 DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_decode.hip)
@@ -678,42 +633,9 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     blocks_per_split: kept-list entries per workgroup; None = the library's choice, min(8, NK) (measured: DESIGN.md 5.12).  The result may
     depend on it through the summation order of the merge; for one value two calls give the same bytes.  Asynchronous on the
     current stream, no host synchronisation, capturable in a HIP graph (the workspace comes from torch inside the capture)."""
-    if block_size not in _lib.BLOCKS:
-        raise NotImplementedError(f"block-sparse decode on the HIP path: block_size in {_lib.BLOCKS}, got {block_size}")
-    blk = int(block_size)
-    if blocks_per_split is not None and (not isinstance(blocks_per_split, int) or isinstance(blocks_per_split, bool)
-                                         or blocks_per_split < 1):
-        raise ValueError(f"blocks_per_split: None or an int >= 1, got {blocks_per_split!r}")
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError("q, k, v: [B, H, S, D] tensors")
-    B, H, Sq, D = q.shape
-    Hkv = k.shape[1]
-    if v.shape[1] != Hkv:
-        raise ValueError(f"k has Hkv = {Hkv} heads, v {v.shape[1]}: k and v must hold the same K/V heads")
-    if Hkv <= 0 or H % Hkv:
-        raise ValueError(f"Hkv = {Hkv} K/V heads do not divide the {H} query heads (query head h reads K/V head h // (H // Hkv))")
-    paged = block_table is not None
-    if paged:
-        if (not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2
-                or block_table.shape[0] != B or block_table.shape[1] < 1):
-            raise ValueError(f"block_table: an int32 tensor [{B}, NKt], got {getattr(block_table, 'dtype', type(block_table))} "
-                             f"{tuple(getattr(block_table, 'shape', ()))}")
-        if k.shape != v.shape or k.shape[2] != blk or k.shape[3] != D:
-            raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}: with a block_table they are "
-                             f"page pools [P, Hkv, {blk}, {D}]")
-        Sk = block_table.shape[1] * blk
-    else:
-        if k.shape != v.shape or k.shape[0] != B or k.shape[3] != D:
-            raise ValueError(f"k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
-        Sk = k.shape[2]
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise ValueError(f"q, k, v: one dtype, bfloat16 or float16 (got {q.dtype}, {k.dtype}, {v.dtype})")
-    if D in (16, 32):
-        raise NotImplementedError(f"head dim {D}: block_sparse_decode serves 64 and 128 (padding a cache would copy it)")
-    if D not in (64, 128):
-        raise ValueError(f"head dim {D}: 64 or 128")
-    if Sq <= 0 or Sk <= 0:
-        raise ValueError(f"empty operands (Sq = {Sq}, Sk = {Sk})")
+    blk = _check_block("block-sparse decode", block_size)
+    _check_count("blocks_per_split", blocks_per_split, 1, optional=True)
+    B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v, dims=(64, 128), block_table=block_table, blk=blk)
     if Sq > blk:
         raise ValueError(f"Sq = {Sq}: block_sparse_decode serves one query block, Sq <= block_size = {blk}")
     NKmax = min(-(-Sk // blk), MAX_KEY_BLOCKS)
@@ -742,37 +664,18 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     if rows > DECODE_MAX_ROWS:
         raise NotImplementedError(f"Sq * H // max(Hl, Hkv) = {rows} rows share a K/V head and a list row: block_sparse_decode "
                                   f"serves at most {DECODE_MAX_ROWS}; use block_sparse_attention")
-    on_device = isinstance(kv_len, torch.Tensor) and kv_len.is_cuda      # (then it is read on the device only)
-    if on_device:
-        if kv_len.numel() not in (1, B) or kv_len.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f"kv_len: an int32 / int64 tensor of 1 or {B} values, got {kv_len.dtype} {tuple(kv_len.shape)}")
-        lens = None
-    else:
-        lens = _kv_lens(kv_len, B, Sk)
-    for name, t in (("k", k), ("v", v)):
-        if t.stride(-1) != 1 or any(st % 8 for st in t.stride()[:-1]) or any(st < 0 for st in t.stride()):
-            raise ValueError(f"{name}: a contiguous head dim and strides that are multiples of 8 elements (a cache is not copied), "
-                             f"got strides {tuple(t.stride())}")
+    lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
+    _check_cache(k, v)
     _core._require_device(q, k, v)
-    if k.data_ptr() % 16 or v.data_ptr() % 16:
-        raise ValueError("k, v: 16-byte aligned (a cache is not copied)")
     dev = q.device
-    if on_device:
-        kv_dev, kv_valid = kv_len.to(dev).reshape(-1).clamp(0, Sk).to(torch.int32).expand(B).contiguous(), Sk
-    elif len(set(lens)) == 1:
-        kv_dev, kv_valid = None, lens[0]
-    else:
-        kv_dev, kv_valid = torch.tensor(lens, dtype=torch.int32, device=dev), Sk
+    kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
     scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
     if mask is not None:
         lists = block_mask_to_lists(mask.to(dev) if mask.device != dev else mask, B, Hl)
         cols, counts = lists["cols"], lists["counts"]
     else:
         _core._require_device(cols, counts)
-    table = None
-    if paged:
-        _core._require_device(block_table)
-        table = block_table if block_table.stride(1) == 1 else block_table.contiguous()
+    table, _held = _table_args(block_table, k)
     L = _lib.lib()
     q = _core._as_bhsd(q)
     bps = 0 if blocks_per_split is None else int(blocks_per_split)
@@ -782,15 +685,10 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
     with torch.cuda.device(dev):
-        _lib.check(L.rsa_block_sparse_decode(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK,
-                                             kv_dev.data_ptr() if kv_dev is not None else None, kv_valid, int(bool(causal)), scale,
-                                             _core._t4(q), _core._t4(k), _core._t4(v),
-                                             table.data_ptr() if table is not None else None,
-                                             table.stride(0) if table is not None else 0, k.shape[0] if paged else 0,
-                                             cols.data_ptr(), counts.data_ptr(), bps, ws.data_ptr(), need.value,
-                                             RsaOut4(out.data_ptr(), out.stride(0), out.stride(1), out.stride(2)),
-                                             lse.data_ptr() if lse is not None else None, _core._stream()),
-                   "rsa_block_sparse_decode")
+        _lib.check(L.rsa_block_sparse_decode(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
+                                             int(bool(causal)), scale, _core._t4(q), _core._t4(k), _core._t4(v), *table,
+                                             cols.data_ptr(), counts.data_ptr(), bps, ws.data_ptr(), need.value, _out4(out),
+                                             _ptr(lse), _core._stream()), "rsa_block_sparse_decode")
     return (out, lse) if return_lse else out
 
 

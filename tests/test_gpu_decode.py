@@ -186,6 +186,39 @@ def test_strided_views_and_a_batch_broadcast_mask_give_the_same_bytes():
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
 
 
+@pytest.mark.parametrize("dtype,n", [(torch.int32, 2), (torch.int64, 2), (torch.int64, 1)])
+def test_device_kv_len_gives_the_ints_result_and_is_not_read_on_the_host(monkeypatch, dtype, n):
+    from rectified_spaattn_amd import block_sparse_decode as dec
+    B, H, Hkv, Sq, D, Sk = 2, 4, 2, 2, 64, 389
+    g = torch.Generator().manual_seed(17)
+    q = torch.randn(B, H, Sq, D, generator=g).to(DEV, torch.bfloat16)
+    k, v = (torch.randn(B, Hkv, Sk, D, generator=g).to(DEV, torch.bfloat16) for _ in range(2))
+    mask = torch.ones(1, 1, 1, 4, dtype=torch.bool, device=DEV)
+    lens = [389, 130] if n == 2 else [130]
+    kw = dict(block_size=128, causal=True, return_lse=True)
+    on_host = dec(q, k, v, mask, kv_len=lens if n == 2 else lens[0], **kw)
+    kv = torch.tensor(lens, dtype=dtype, device=DEV)
+    torch.cuda.synchronize()
+
+    def refuse(*a, **kws):
+        raise AssertionError("kv_len was read on the host")
+    for name in ("item", "tolist", "cpu"):
+        monkeypatch.setattr(torch.Tensor, name, refuse)
+    before = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        on_device = dec(q, k, v, mask, kv_len=kv, **kw)
+    finally:
+        torch.cuda.set_sync_debug_mode(before)
+        monkeypatch.undo()
+    for a, b in zip(on_device, on_host):
+        assert a.dtype == b.dtype and a.shape == b.shape
+        assert torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16 else a.view(torch.int32),
+                           b.view(torch.int16) if b.dtype == torch.bfloat16 else b.view(torch.int32))
+    out = on_host[0]
+    assert bool(out.any()) and not torch.equal(out[0], out[1])
+
+
 def test_graph_replay_on_changed_contents():
     """One call captured on a side stream with a device kv_len, a mask tensor and a table; then one more key is written into the
     cache in place, kv_len is bumped, mask bits flip and a page moves; the replay equals the eager call on the new contents."""
