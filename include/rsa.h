@@ -386,6 +386,50 @@ int rsa_block_select_pooled(int B, int H, int Hkv, int Hl, int Sq, int D, int dt
                             int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
                             int32_t* counts, float* scores, void* stream);
 
+/* ---- the decode step over an e4m3 K/V cache with one static fp32 scale per K/V head (found by symbol: the header version stays
+ * 6.1).  The cache holds OCP e4m3fn codes, one byte per element: [B, Hkv, Sk, D], or with a block_table
+ * page pools [num_pages, Hkv, block, D]; its strides count bytes.  The value of a code is float(code) * scale[hk]; k_scale and
+ * v_scale are DEVICE fp32 arrays of Hkv values, positive and finite.  They are not checked and no address depends on them: a
+ * zero, negative, infinite or NaN scale garbles the rows of its head and nothing else.  Head dims 64 and 128 only.
+ *
+ * rsa_kv8_append writes new rows.  k_new / v_new: [B, Hkv, T, D] of `dtype` through any strides rsa_block_sparse_decode accepts
+ * for k / v (never copied).  Token t < n_b of batch item b goes to position start_b + t; start_b = start_dev[b] clamped into
+ * [0, Sk] (DEVICE int32, B values, never read on the host) or, with start_dev NULL, start in [0, Sk]; n_b likewise from n_new_dev
+ * (clamped into [0, T]) or n_new.  Sk is the capacity: the caches' rows, or with a table NKt * block for a table [B, >= NKt] with
+ * row stride table_stride_b.  The grid is sized from T alone.  Per element: y = x / scale[hk] as one IEEE fp32 division, clamped to
+ * [-448, 448] (+-Inf saturate; a NaN becomes the NaN code with the sign bit of its input), converted round-to-nearest-even with
+ * subnormals kept.  The call writes the D
+ * bytes of every placed row and no other byte; a position at or beyond Sk, or one whose table entry lies outside [0, num_pages),
+ * is dropped and no address is formed from it.  Two batch items that map to one page race: the caller's business.  Caches: pointer
+ * and strides multiples of 8 bytes (8-byte stores).  One launch, prefill is the call with start = 0.
+ *
+ * rsa_block_sparse_decode_kv8 is rsa_block_sparse_decode over such a cache: its argument list with k_scale and v_scale in front of
+ * the stream; dtype names q's (and out's) type; the workspace is rsa_block_sparse_decode_bytes'.  The codes become q's type in
+ * registers (exact: every finite e4m3 value is a bf16 and an fp16), the MFMAs, the softmax, the splits and the merge are those of
+ * the 2-byte call.  The K scale multiplies each fp32 score once behind the dot product, before masking and the maximum; the V
+ * scale multiplies the merged row once, out = round((O / l) * v_scale[hk]); l and the log-sum-exp do not see v_scale.  With
+ * power-of-two scales (and nothing under- or overflowing) the bytes are those of rsa_block_sparse_decode on the cache
+ * code * scale.  Every rule of that call holds word for word (visible set, device kv_len, bytes beyond len_b never multiplied,
+ * unvisited blocks and out-of-range entries not read).  k: pointer and strides multiples of 8 bytes; v: of 16 bytes; other views are
+ * RSA_ERR_BAD_ARG, as is a NULL or misaligned scale pointer.
+ *
+ * rsa_pool_keys_kv8 is rsa_pool_keys from an e4m3 k (no dtype argument; pointer and strides multiples of 8 bytes): out[b, hk, j, :] =
+ * (the fp32 sum of float(code) over the block's keys below len_b, in rsa_pool_keys' order, divided once by their count) multiplied
+ * once by k_scale[hk].  Every other clause of rsa_pool_keys holds.  rsa_block_select_pooled reads the fp32 cache as before.
+ * Refusals as the 2-byte entries'; D outside {64, 128}: RSA_ERR_UNSUPPORTED.  Every check runs before the first HIP call. */
+int rsa_kv8_append(int B, int Hkv, int T, int Sk, int D, int dtype, int block, rsa_tensor4 k_new, rsa_tensor4 v_new,
+                   rsa_out4 k_cache, rsa_out4 v_cache, const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                   const int32_t* start_dev, int start, const int32_t* n_new_dev, int n_new, const float* k_scale,
+                   const float* v_scale, void* stream);
+int rsa_block_sparse_decode_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
+                                rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                                const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes,
+                                rsa_out4 out, float* lse, const float* k_scale, const float* v_scale, void* stream);
+int rsa_pool_keys_kv8(int B, int Hkv, int Sk, int D, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                      int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid, const int32_t* start_dev,
+                      int start, int workgroups_per_head, float* out, const float* k_scale, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

@@ -10,7 +10,7 @@ Module names mirror the reference package `rectified_spaattn`:
     rectified_cogvideo_attn   rectified_block_sparse_attention, RectifiedCogVideoXVideoSpaAttnProcessor2_0
     attn_processor            get_attn_processors, set_attn_processor
     block_sparse              block_sparse_attention over a caller's block mask, block_sparse_decode (its decode half: few query rows over a
-                              (paged) K/V cache, with log-sum-exp) and select_blocks, the top-k block selection
+                              (paged) K/V cache, with log-sum-exp; 2-byte or e4m3 with append_kv_e4m3 as its writer) and select_blocks, the top-k block selection
                               per K/V head that makes one (both also exported here), the mask <-> list conversions; the four rectified_*_attn modules above also carry the reference's
                               _build_block_index_with_importance_optimized and _triton_block_sparse_attention_onehot
     teacache                  TeaCache step-skipping controller (scripts' teacache_forward bookkeeping), rel_l1_distance
@@ -64,23 +64,33 @@ def select_blocks(q, k, top_k, *, block_size=128, kv_len=None, causal=False, kee
 
 
 def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
-                        return_lse=False, blocks_per_split=None):
+                        return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None):
     """Block-sparse decode attention: q [B,H,Sq,D] with Sq <= block over a K/V cache [B,Hkv,Sk,D], or over page pools
     [P,Hkv,block,D] behind block_table int32 [B,NKt]; block_mask bool / uint8 [B|1, Hl, 1, NK] or select_blocks' lists;
-    return_lse=True adds the fp32 log-sum-exp [B,H,Sq].  See rectified_spaattn_amd.block_sparse.block_sparse_decode."""
+    return_lse=True adds the fp32 log-sum-exp [B,H,Sq].  k / v float8_e4m3fn with k_scale / v_scale (one fp32 scale per K/V
+    head): the one-byte cache append_kv_e4m3 writes.  See rectified_spaattn_amd.block_sparse.block_sparse_decode."""
     from . import block_sparse
     return block_sparse.block_sparse_decode(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                             causal=causal, block_table=block_table, return_lse=return_lse,
-                                            blocks_per_split=blocks_per_split)
+                                            blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale)
 
 
-def pool_keys(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None):
+def pool_keys(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None, k_scale=None):
     """The cache of pooled keys for select_blocks_pooled: k [B,Hkv,Sk,D] (or a page pool behind block_table) -> fp32
-    [B, Hkv, ceil(Sk/block), D]; with start= and out= only the blocks from start // block up to kv_len are written again.
-    See rectified_spaattn_amd.block_sparse.pool_keys."""
+    [B, Hkv, ceil(Sk/block), D]; with start= and out= only the blocks from start // block up to kv_len are written again; k
+    float8_e4m3fn with k_scale: from the one-byte cache.  See rectified_spaattn_amd.block_sparse.pool_keys."""
     from . import block_sparse
     return block_sparse.pool_keys(k, block_size=block_size, kv_len=kv_len, block_table=block_table, out=out, start=start,
-                                  workgroups_per_head=workgroups_per_head)
+                                  workgroups_per_head=workgroups_per_head, k_scale=k_scale)
+
+
+def append_kv_e4m3(k_new, v_new, k_cache, v_cache, *, start, k_scale, v_scale, n_new=None, block_size=128, block_table=None):
+    """The writer of the one-byte K/V cache: k_new / v_new [B,Hkv,T,D] (bf16 / fp16) become float8_e4m3fn codes under one static
+    fp32 scale per K/V head, at positions start[b] + t of k_cache / v_cache [B,Hkv,Sk,D] or of page pools behind block_table.
+    See rectified_spaattn_amd.block_sparse.append_kv_e4m3."""
+    from . import block_sparse
+    return block_sparse.append_kv_e4m3(k_new, v_new, k_cache, v_cache, start=start, k_scale=k_scale, v_scale=v_scale,
+                                       n_new=n_new, block_size=block_size, block_table=block_table)
 
 
 def select_blocks_pooled(q, pooled_k, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0,

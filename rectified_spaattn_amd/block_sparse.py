@@ -17,10 +17,13 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              grows, directly or through a block table (rsa_pool_keys)
     select_blocks_pooled     select_blocks from that cache instead of K: the same bytes without a pass over K
                              (rsa_block_select_pooled)
+    append_kv_e4m3           the writer of a one-byte K/V cache: new rows become e4m3 codes under one static fp32 scale per K/V
+                             head (rsa_kv8_append); block_sparse_decode and pool_keys read such a cache in place
+                             (k_scale= / v_scale=: rsa_block_sparse_decode_kv8, rsa_pool_keys_kv8)
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
-The five calls above build_block_index share one argument layer, below _mask_u8: _check_operands (ranks, head counts, shapes, the
+The calls above build_block_index share one argument layer, below _mask_u8: _check_operands (ranks, head counts, shapes, the
 one 2-byte dtype, the head dims a call serves), _check_limit / _device_limit (kv_len and start: host ints, or a device tensor that
 is never read on the host), _check_block_table / _table_args, _check_cache (a cache is not copied: the negation of what
 _core._as_bhsd copies), _empty_lists and _out4.  Every check runs on CPU tensors, before _core._require_device.  select_blocks and
@@ -104,11 +107,16 @@ def _table_args(block_table, pool):
     return (table.data_ptr(), table.stride(0), pool.shape[0]), table
 
 
-def _check_operands(q, k, v=None, *, dims=HEAD_DIMS, block_table=None, blk: int = 0, pooled: bool = False):
+E4M3 = torch.float8_e4m3fn
+KV8_HEAD_DIMS = (64, 128)
+
+
+def _check_operands(q, k, v=None, *, dims=HEAD_DIMS, block_table=None, blk: int = 0, pooled: bool = False, kv8_ok: bool = False):
     """The tensor operands a call takes -> (B, H, Hkv, Sq, Sk, D).  q [B,H,Sq,D] or None (pool_keys: B from k, H = Hkv, Sq = 1);
     k [B,Hkv,Sk,D], or with a block_table [B, NKt] a page pool [P,Hkv,blk,D] of capacity Sk = NKt * blk, or with pooled the
-    fp32 cache [B,Hkv,NK,D] of pool_keys (Sk is then NK); v like k, or None.  One 2-byte dtype; D among dims, the head dims the
-    call serves (another of HEAD_DIMS is NotImplementedError); nothing empty."""
+    fp32 cache [B,Hkv,NK,D] of pool_keys (Sk is then NK); v like k, or None.  One 2-byte dtype -- or, where the call serves it
+    (kv8_ok), k and v both float8_e4m3fn beside a 2-byte q; D among dims, the head dims the call serves (another of HEAD_DIMS is
+    NotImplementedError); nothing empty."""
     kname = "pooled_k" if pooled else "k"
     for t in (q, k, v):
         if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 4):
@@ -131,7 +139,15 @@ def _check_operands(q, k, v=None, *, dims=HEAD_DIMS, block_table=None, blk: int 
                          f"{'' if q is None else f' q {tuple(q.shape)}'}"
                          + (f": with a block_table k / v are page pools [P, Hkv, {blk}, {D}]" if block_table is not None else ""))
     dt = k.dtype if q is None else q.dtype
-    if dt not in (torch.bfloat16, torch.float16) or (not pooled and k.dtype != dt) or (v is not None and v.dtype != dt):
+    if kv8_ok and not pooled and E4M3 in (k.dtype, getattr(v, "dtype", None)):
+        if k.dtype != E4M3 or (v is not None and v.dtype != E4M3) or (q is not None and dt not in (torch.bfloat16, torch.float16)):
+            raise ValueError(f"{_names(q, kname, v)}: an e4m3 cache is k and v both float8_e4m3fn beside a bfloat16 / float16 q, got "
+                             f"{', '.join(str(t.dtype) for t in (q, k, v) if t is not None)}")
+        if D not in KV8_HEAD_DIMS:
+            if D in HEAD_DIMS:
+                raise NotImplementedError(f"head dim {D}: an e4m3 cache serves {KV8_HEAD_DIMS}")
+            raise ValueError(f"head dim {D}: one of {KV8_HEAD_DIMS}")
+    elif dt not in (torch.bfloat16, torch.float16) or (not pooled and k.dtype != dt) or (v is not None and v.dtype != dt):
         raise ValueError(f"{_names(q, kname, v)}: one dtype, bfloat16 or float16 (pooled_k apart), got "
                          f"{', '.join(str(t.dtype) for t in (q, k, v) if t is not None)}")
     if pooled and (k.dtype != torch.float32 or not k.is_contiguous()):
@@ -151,7 +167,17 @@ def _names(q, kname: str, v) -> str:
 
 
 def _check_cache(k, v=None):
-    """A K/V cache is read where it lies: what _core._as_bhsd would copy is refused."""
+    """A K/V cache is read where it lies: what _core._as_bhsd would copy is refused.  An e4m3 cache: K is loaded 8 bytes a lane,
+    V 16 -- pointer and strides are multiples of that."""
+    for name, t, align in (("k", k, 8), ("v", v, 16)):
+        if t is not None and t.dtype == E4M3:
+            *outer, inner = t.stride()
+            if inner != 1 or any(st % align for st in outer) or t.data_ptr() % align:
+                raise ValueError(f"{name}: a contiguous head dim, strides that are multiples of {align} bytes and a {align}-byte "
+                                 f"aligned pointer (a cache is not copied), got strides {tuple(t.stride())}, pointer % {align} = "
+                                 f"{t.data_ptr() % align}")
+    if k.dtype == E4M3:
+        return
     for name, t in (("k", k), ("v", v)):
         if t is not None and not _core._read_in_place(t):
             raise ValueError(f"{name}: a contiguous head dim, strides that are multiples of 8 elements and a 16-byte aligned "
@@ -190,6 +216,33 @@ def _device_limit(val, B: int, Sk: int, dev):
     if len(set(val)) == 1:
         return None, val[0], val
     return torch.tensor(val, dtype=torch.int32, device=dev), Sk, val
+
+
+def _check_scales(k, Hkv: int, **scales):
+    """k_scale= / v_scale= of a call over the cache k: required with an e4m3 cache, refused with a 2-byte one.  A scale is a
+    positive finite Python float or a float32 tensor of 1 or Hkv values on the cache's device (its values are not read)."""
+    if k.dtype != E4M3:
+        given = [n for n, s in scales.items() if s is not None]
+        if given:
+            raise ValueError(f"{', '.join(given)}: scales belong to a float8_e4m3fn cache, k is {k.dtype}")
+        return
+    for name, sc in scales.items():
+        if sc is None:
+            raise ValueError(f"{name}: required with a float8_e4m3fn cache (one fp32 scale per K/V head, or one for all)")
+        if isinstance(sc, torch.Tensor):
+            if sc.dtype != torch.float32 or sc.numel() not in (1, Hkv):
+                raise ValueError(f"{name}: a float32 tensor of 1 or {Hkv} values, got {sc.dtype} {tuple(sc.shape)}")
+            if sc.device != k.device:
+                raise ValueError(f"{name} is on {sc.device}, the cache on {k.device}")
+        elif isinstance(sc, bool) or not isinstance(sc, (int, float)) or not 0.0 < float(sc) < float("inf"):
+            raise ValueError(f"{name}: a positive finite float or a float32 tensor of 1 or {Hkv} values, got {sc!r}")
+
+
+def _scale_arg(sc, Hkv: int, dev) -> torch.Tensor:
+    """What _check_scales passed, as the C entries' DEVICE fp32 [Hkv]: a Python float is filled in by torch (capturable)."""
+    if isinstance(sc, torch.Tensor):
+        return sc.reshape(-1).expand(Hkv).contiguous()
+    return torch.full((Hkv,), float(sc), dtype=torch.float32, device=dev)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -531,7 +584,7 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
 
 
 def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_table=None, out: Optional[torch.Tensor] = None,
-              start=None, workgroups_per_head: Optional[int] = None) -> torch.Tensor:
+              start=None, workgroups_per_head: Optional[int] = None, k_scale=None) -> torch.Tensor:
     """The cache of pooled keys select_blocks_pooled reads: per key block the kbar of select_blocks, the
     fp32 sum of the block's keys below kv_len[b] divided once by their count, in select_blocks' summation order.
     k [B,Hkv,Sk,D], any strides block_sparse_decode accepts (a cache is never copied), or with block_table int32 [B, NKt] a page
@@ -549,10 +602,15 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
     for blocks the call writes; an entry outside [0, P) gives a block of zeros.
     workgroups_per_head: workgroups per (b, K/V head) that stride over the block range -- a performance hint, any count >= 1
     gives the same bytes.  None: the exact count when both limits are host values, NKt with start=None, else 2 (an append of
-    at most block tokens touches at most two blocks).  Asynchronous on the current stream, no host synchronisation, capturable."""
+    at most block tokens touches at most two blocks).  Asynchronous on the current stream, no host synchronisation, capturable.
+    An e4m3 cache: k float8_e4m3fn, contiguous or paged, head dim 64 / 128, strides multiples of 8 bytes,
+    with k_scale a positive float or a float32 device tensor of 1 or Hkv values (required then, refused otherwise).  The value of
+    a block is the fp32 sum of float(code) over its keys below kv_len[b], in the same order, divided once by their count and
+    multiplied once by k_scale[hkv]; every other clause above holds.  select_blocks_pooled reads the result as before."""
     blk = _check_block("pool_keys", block_size)
     _check_count("workgroups_per_head", workgroups_per_head, 1, optional=True)
-    B, _, Hkv, _, Sk, D = _check_operands(None, k, block_table=block_table, blk=blk)
+    B, _, Hkv, _, Sk, D = _check_operands(None, k, block_table=block_table, blk=blk, kv8_ok=True)
+    _check_scales(k, Hkv, k_scale=k_scale)
     NK = _key_blocks(Sk, blk)
     if start is not None and out is None:
         raise ValueError("out: required when start is given (an update writes into the cache it is given)")
@@ -581,10 +639,68 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
     else:
         wph = NK if start is None else 2
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().rsa_pool_keys(B, Hkv, Sk, D, _core.dtype_code(k.dtype), blk, NK, _core._t4(k), *table,
-                                            _ptr(kv_dev), kv_valid, _ptr(st_dev), st_host, wph, out.data_ptr(), _core._stream()),
-                   "rsa_pool_keys")
+        if k.dtype == E4M3:
+            ks = _scale_arg(k_scale, Hkv, dev)
+            _lib.check(_lib.lib().rsa_pool_keys_kv8(B, Hkv, Sk, D, blk, NK, _core._t4(k), *table, _ptr(kv_dev), kv_valid,
+                                                    _ptr(st_dev), st_host, wph, out.data_ptr(), ks.data_ptr(), _core._stream()),
+                       "rsa_pool_keys_kv8")
+        else:
+            _lib.check(_lib.lib().rsa_pool_keys(B, Hkv, Sk, D, _core.dtype_code(k.dtype), blk, NK, _core._t4(k), *table,
+                                                _ptr(kv_dev), kv_valid, _ptr(st_dev), st_host, wph, out.data_ptr(),
+                                                _core._stream()), "rsa_pool_keys")
     return out
+
+
+def append_kv_e4m3(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, start, k_scale,
+                   v_scale, n_new=None, block_size: int = 128, block_table=None) -> None:
+    """The writer of an e4m3 K/V cache: new K / V rows become one-byte codes under one static fp32 scale
+    per K/V head and land where block_sparse_decode and pool_keys read them.
+    k_new / v_new [B,Hkv,T,D], bf16 / fp16, through any strides block_sparse_decode accepts for k / v (head-strided views of a
+    fused projection included; the inputs are never copied).  k_cache / v_cache float8_e4m3fn: [B,Hkv,Sk,D], or with block_table
+    int32 [B, NKt] page pools [P,Hkv,block_size,D] of capacity Sk = NKt * block_size (one page = one key block); strides and
+    pointers multiples of 8 bytes (block_sparse_decode asks 16 of V).  Head dim 64 or 128.
+    Token t < n_new[b] (default T) of batch item b goes to position start[b] + t.  start, n_new: an int, one value per batch item,
+    or an int32 / int64 device tensor of 1 or B values, which is clamped on the device (into [0, Sk] / [0, T]) and never read on
+    the host; the grid is sized from T alone.  Prefill is the call with start=0.
+    k_scale / v_scale: a positive finite float, or a float32 device tensor of 1 or Hkv values.  Per element
+        code = (x.float() / scale[hkv]).clamp(-448, 448).to(torch.float8_e4m3fn)
+    bit for bit: one IEEE fp32 division, round to nearest even, subnormals kept, +-Inf saturates, a NaN stays a NaN code (0x7F or
+    0xFF by the sign bit of the input).  The
+    values of a scale tensor are not checked and no address depends on them: a zero, negative or non-finite scale garbles that
+    head's rows only.
+    The call writes exactly the D bytes of every placed row and no other byte.  A position at or beyond the capacity is dropped,
+    and so is one whose table entry lies outside [0, P).  Two batch items whose table entries name the same page race: keeping
+    pages apart is the caller's business.  Static scales mean an append never re-quantises what the page already holds.
+    Asynchronous on the current stream, no host synchronisation, capturable."""
+    blk = _check_block("append_kv_e4m3", block_size)
+    B, _, Hkv, T, _, D = _check_operands(k_new, k_new, v_new, dims=KV8_HEAD_DIMS)
+    _, _, _, _, Sk, _ = _check_operands(None, k_cache, v_cache, dims=KV8_HEAD_DIMS, block_table=block_table, blk=blk, kv8_ok=True)
+    if k_cache.dtype != E4M3:
+        raise ValueError(f"k_cache, v_cache: float8_e4m3fn, got {k_cache.dtype}")
+    if (k_cache.shape[1], k_cache.shape[3]) != (Hkv, D) or (block_table is None and k_cache.shape[0] != B):
+        raise ValueError(f"k_cache {tuple(k_cache.shape)} does not match k_new {tuple(k_new.shape)}")
+    if block_table is not None:
+        _check_block_table(block_table, B)
+    _check_scales(k_cache, Hkv, k_scale=k_scale, v_scale=v_scale)
+    starts = _check_limit("start", start, B, Sk, 0)
+    counts = _check_limit("n_new", n_new, B, T, T)
+    _check_cache(k_new, v_new)
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        *outer, inner = t.stride()
+        if inner != 1 or any(st % 8 for st in outer) or t.data_ptr() % 8:
+            raise ValueError(f"{name}: a contiguous head dim, strides that are multiples of 8 bytes and an 8-byte aligned pointer, "
+                             f"got strides {tuple(t.stride())}, pointer % 8 = {t.data_ptr() % 8}")
+    _core._require_device(k_new, v_new, k_cache, v_cache)
+    dev = k_cache.device
+    table, _held = _table_args(block_table, k_cache)
+    st_dev, st_host, _ = _device_limit(starts, B, Sk, dev)
+    n_dev, n_host, _ = _device_limit(counts, B, T, dev)
+    ks, vs = _scale_arg(k_scale, Hkv, dev), _scale_arg(v_scale, Hkv, dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rsa_kv8_append(B, Hkv, T, Sk, D, _core.dtype_code(k_new.dtype), blk, _core._t4(k_new),
+                                             _core._t4(v_new), _out4(k_cache), _out4(v_cache), *table, _ptr(st_dev), st_host,
+                                             _ptr(n_dev), n_host, ks.data_ptr(), vs.data_ptr(), _core._stream()),
+                   "rsa_kv8_append")
 
 
 def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None,
@@ -610,7 +726,7 @@ DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_dec
 
 def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask, *, kv_len=None,
                         sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, block_table=None,
-                        return_lse: bool = False, blocks_per_split: Optional[int] = None):
+                        return_lse: bool = False, blocks_per_split: Optional[int] = None, k_scale=None, v_scale=None):
     """Block-sparse attention of a few query rows (decode: one token, or a handful of speculative ones) over a long K/V cache:
     block_sparse_attention's result at one query block, from kernels built for it.
     q [B,H,Sq,D] with Sq <= block_size; k / v [B,Hkv,Sk,D], H % Hkv == 0, query head h reads K/V head h // (H // Hkv); any strides
@@ -632,10 +748,19 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     return_lse=True: (out, lse), lse fp32 [B,H,Sq] = ln sum over the visible keys of exp(sm_scale q . k).
     blocks_per_split: kept-list entries per workgroup; None = the library's choice, min(8, NK) (measured: DESIGN.md 5.12).  The result may
     depend on it through the summation order of the merge; for one value two calls give the same bytes.  Asynchronous on the
-    current stream, no host synchronisation, capturable in a HIP graph (the workspace comes from torch inside the capture)."""
+    current stream, no host synchronisation, capturable in a HIP graph (the workspace comes from torch inside the capture).
+    An e4m3 cache: k and v float8_e4m3fn (append_kv_e4m3 writes them), contiguous or paged, with k_scale
+    and v_scale each a positive float or a float32 device tensor of 1 or Hkv values -- both required then, and refused with a
+    2-byte cache; q and the output stay bf16 / fp16.  The value of a code is float(code) * scale[hkv].  The codes become q's type in
+    registers (exact), the K scale multiplies each fp32 score once, the V scale the merged row once; the log-sum-exp carries the K
+    scale through the scores and does not see v_scale.  With power-of-two scales the bytes are those of this call on the
+    dequantised 2-byte cache.  Every rule above holds unchanged; K views need strides and a pointer that are multiples of 8 bytes, V
+    views of 16 (others are refused, never copied).  The scales' values are not checked: a zero, negative or non-finite one garbles
+    its head's rows only."""
     blk = _check_block("block-sparse decode", block_size)
     _check_count("blocks_per_split", blocks_per_split, 1, optional=True)
-    B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v, dims=(64, 128), block_table=block_table, blk=blk)
+    B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v, dims=(64, 128), block_table=block_table, blk=blk, kv8_ok=True)
+    _check_scales(k, Hkv, k_scale=k_scale, v_scale=v_scale)
     if Sq > blk:
         raise ValueError(f"Sq = {Sq}: block_sparse_decode serves one query block, Sq <= block_size = {blk}")
     NKmax = min(-(-Sk // blk), MAX_KEY_BLOCKS)
@@ -684,11 +809,14 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
     out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+    kv8 = k.dtype == E4M3
+    entry = "rsa_block_sparse_decode_kv8" if kv8 else "rsa_block_sparse_decode"
+    held = [_scale_arg(sc, Hkv, dev) for sc in (k_scale, v_scale)] if kv8 else []
     with torch.cuda.device(dev):
-        _lib.check(L.rsa_block_sparse_decode(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
-                                             int(bool(causal)), scale, _core._t4(q), _core._t4(k), _core._t4(v), *table,
-                                             cols.data_ptr(), counts.data_ptr(), bps, ws.data_ptr(), need.value, _out4(out),
-                                             _ptr(lse), _core._stream()), "rsa_block_sparse_decode")
+        _lib.check(getattr(L, entry)(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
+                                     int(bool(causal)), scale, _core._t4(q), _core._t4(k), _core._t4(v), *table,
+                                     cols.data_ptr(), counts.data_ptr(), bps, ws.data_ptr(), need.value, _out4(out), _ptr(lse),
+                                     *[t.data_ptr() for t in held], _core._stream()), entry)
     return (out, lse) if return_lse else out
 
 

@@ -23,14 +23,31 @@
 
 #include <math.h>
 
+#include <type_traits>
+
 #define SEL_NT 256
 #define SEL_MAX_NK 8192
 #define SEL_MAX_STEPS (SEL_MAX_NK / 64)
 #define SEL_MAX_SPLITS 256      // score workgroups per list row of the pooled selection, at most
 
 // ---- pooling ---------------------------------------------------------------------------------------------------------------------
+// The element loaders: what a lane reads for its 8 channels of a row, and how it adds them.  bf16 / fp16: 16 bytes.  e4m3_tag (the
+// one-byte K cache of DESIGN.md section 5.14, rsa_pool_keys_kv8): 8 bytes of codes, added as float(code); the head's scale
+// multiplies the finished mean once.  Everything below the loaders exists once.
+struct e4m3_tag {};
 template <typename Tag>
-__device__ __forceinline__ void sel_add8(float (&a)[8], const uint4 v) {
+struct SelElem {
+    using type = unsigned short;
+    using vec = uint4;
+};
+template <>
+struct SelElem<e4m3_tag> {
+    using type = unsigned char;
+    using vec = uint2;
+};
+
+template <typename Tag>
+__device__ __forceinline__ void sel_add8(float (&a)[8], const typename SelElem<Tag>::vec v) {
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -38,27 +55,41 @@ __device__ __forceinline__ void sel_add8(float (&a)[8], const uint4 v) {
         a[2 * i + 1] += rsa_to_f32<Tag>((unsigned short)(w[i] >> 16));
     }
 }
+template <>
+__device__ __forceinline__ void sel_add8<e4m3_tag>(float (&a)[8], const uint2 v) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const unsigned w[2] = {v.x, v.y};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        a[4 * i] += lo[0];
+        a[4 * i + 1] += lo[1];
+        a[4 * i + 2] += hi[0];
+        a[4 * i + 3] += hi[1];
+    }
+}
 
 // Sum over `rows` rows (>= 1, uniform over the workgroup) of D channels: thread t < D returns channel t's sum.  Thread t reads the
 // 16-byte chunk t % (D / 8) of rows t / (D / 8), + 2048 / D, ...; the partials meet over xor strides D / 8 .. 32 inside the wave
 // and as (w0 + w1) + (w2 + w3) through LDS.
 template <typename Tag>
-__device__ __forceinline__ float sel_pool_block(const unsigned short* __restrict__ base, long stride_s, int rows, int D,
-                                                float (*red)[128]) {
+__device__ __forceinline__ float sel_pool_block(const typename SelElem<Tag>::type* __restrict__ base, long stride_s, int rows,
+                                                int D, float (*red)[128]) {
+    using vec = typename SelElem<Tag>::vec;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = D >> 3, RP = SEL_NT / C;
     const int c = tid % C;
-    const unsigned short* p = base + c * 8;
+    const typename SelElem<Tag>::type* p = base + c * 8;
     float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int r = tid / C;
     for (; r + 3 * RP < rows; r += 4 * RP) {
-        uint4 v[4];
+        vec v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const uint4*>(p + (long)(r + u * RP) * stride_s);
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const vec*>(p + (long)(r + u * RP) * stride_s);
 #pragma unroll
         for (int u = 0; u < 4; ++u) sel_add8<Tag>(a, v[u]);
     }
-    for (; r < rows; r += RP) sel_add8<Tag>(a, *reinterpret_cast<const uint4*>(p + (long)r * stride_s));
+    for (; r < rows; r += RP) sel_add8<Tag>(a, *reinterpret_cast<const vec*>(p + (long)r * stride_s));
     for (int m = C; m < 64; m <<= 1) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] += __shfl_xor(a[e], m, 64);
@@ -74,8 +105,8 @@ __device__ __forceinline__ float sel_pool_block(const unsigned short* __restrict
 
 // The value of a key block in the selection: the fp32 sum of its `rows` (>= 1) keys below the limit, divided once by their count.
 template <typename Tag>
-__device__ __forceinline__ float sel_pool_mean(const unsigned short* __restrict__ base, long stride_s, int rows, int D,
-                                               float (*red)[128]) {
+__device__ __forceinline__ float sel_pool_mean(const typename SelElem<Tag>::type* __restrict__ base, long stride_s, int rows,
+                                               int D, float (*red)[128]) {
     return sel_pool_block<Tag>(base, stride_s, rows, D, red) / (float)rows;
 }
 
@@ -127,13 +158,16 @@ __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q
 // The pooled-key cache: workgroup w of the W of (b, K/V head) writes the blocks start / blk + w, + W, ... below ceil(len / blk) and
 // nothing else.  Both limits are uniform over the workgroup, so every barrier of sel_pool_block is met by all of it.  With a table
 // the page of a block is read for written blocks only, and an entry outside [0, num_pages) gives zeros: no address is formed
-// from it.
+// from it.  Tag = e4m3_tag: k holds codes (strides in bytes) and the mean of the codes is multiplied once by k_scale[hk]; the
+// 2-byte forms never read k_scale.
 template <typename Tag>
 __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hkv, int Sk, int D, int blk, int NK, int W,
                                                            const int32_t* __restrict__ kv_len, int kv_valid,
                                                            const int32_t* __restrict__ start_dev, int start_host,
                                                            const int32_t* __restrict__ table, long table_stride_b,
-                                                           int num_pages, float* __restrict__ out) {
+                                                           int num_pages, float* __restrict__ out,
+                                                           const float* __restrict__ k_scale) {
+    using KT = typename SelElem<Tag>::type;
     __shared__ float red[4][128];
     const int tid = threadIdx.x;
     const int w = (int)(blockIdx.x % (unsigned)W);
@@ -146,16 +180,17 @@ __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hk
     const int j_hi = min(NK, (len + blk - 1) / blk);
     for (int j = st / blk + w; j < j_hi; j += W) {
         const int rows = min(blk, len - j * blk);       // >= 1 below j_hi
-        const unsigned short* base;
+        const KT* base;
         bool have = true;
         if (table) {
             const int page = table[b * table_stride_b + j];
             have = page >= 0 && page < num_pages;
-            base = static_cast<const unsigned short*>(k.ptr) + (long)(have ? page : 0) * k.stride_b + (long)hk * k.stride_h;
+            base = static_cast<const KT*>(k.ptr) + (long)(have ? page : 0) * k.stride_b + (long)hk * k.stride_h;
         } else {
-            base = static_cast<const unsigned short*>(k.ptr) + b * k.stride_b + (long)hk * k.stride_h + (long)j * blk * k.stride_s;
+            base = static_cast<const KT*>(k.ptr) + b * k.stride_b + (long)hk * k.stride_h + (long)j * blk * k.stride_s;
         }
-        const float mean = have ? sel_pool_mean<Tag>(base, k.stride_s, rows, D, red) : 0.f;
+        float mean = have ? sel_pool_mean<Tag>(base, k.stride_s, rows, D, red) : 0.f;
+        if constexpr (std::is_same<Tag, e4m3_tag>::value) mean *= k_scale[hk];
         if (tid < D) out[(bh * NK + j) * D + tid] = mean;
     }
 }
@@ -449,19 +484,27 @@ extern "C" int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, i
 }
 
 // ---- the pooled-key cache ----------------------------------------------------------------------------------
-extern "C" int rsa_pool_keys(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
-                             int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
-                             const int32_t* start_dev, int start, int workgroups_per_head, float* out, void* stream) {
+// Both entries: kv8 = k holds e4m3 codes (no dtype; head dims 64 / 128; 8-byte loads) and k_scale is there.
+static int sel_pool_keys_run(bool kv8, int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k,
+                             const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev,
+                             int kv_valid, const int32_t* start_dev, int start, int workgroups_per_head, float* out,
+                             const float* k_scale, void* stream) {
     if (B <= 0 || Hkv <= 0 || Sk <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
-    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
-    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (!kv8 && dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (kv8 ? (D != 64 && D != 128) : (D != 16 && D != 32 && D != 64 && D != 128)) return RSA_ERR_UNSUPPORTED;
     if (NK != (int)(((long)Sk + block - 1) / block)) return RSA_ERR_BAD_ARG;
     if (NK > SEL_MAX_NK) return RSA_ERR_UNSUPPORTED;
     if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
     if (!start_dev && (start < 0 || start > Sk)) return RSA_ERR_BAD_ARG;
     if (workgroups_per_head < 0) return RSA_ERR_BAD_ARG;
-    if (!out || rsa_check_tensor(k) != RSA_OK) return RSA_ERR_BAD_ARG;
+    if (!out || !k.ptr) return RSA_ERR_BAD_ARG;
+    if (kv8) {      // (strides in bytes: 8 of them per lane and load)
+        if (!k_scale || (reinterpret_cast<uintptr_t>(k_scale) & 3)) return RSA_ERR_BAD_ARG;
+        if ((reinterpret_cast<uintptr_t>(k.ptr) & 7) || (k.stride_b % 8) || (k.stride_h % 8) || (k.stride_s % 8)) return RSA_ERR_BAD_ARG;
+    } else if (rsa_check_tensor(k) != RSA_OK) {
+        return RSA_ERR_BAD_ARG;
+    }
     if (k.stride_b < 0 || k.stride_h < 0 || k.stride_s < 0) return RSA_ERR_BAD_ARG;
     if (block_table && (num_pages <= 0 || table_stride_b < 0)) return RSA_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_len_dev) | reinterpret_cast<uintptr_t>(start_dev)) & 3)
@@ -477,13 +520,33 @@ extern "C" int rsa_pool_keys(int B, int Hkv, int Sk, int D, int dtype, int block
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((size_t)B * Hkv * W));
-    if (dtype == RSA_BF16)
+    if (kv8)
+        pool_keys_kernel<e4m3_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start,
+                                                           block_table, (long)table_stride_b, num_pages, out, k_scale);
+    else if (dtype == RSA_BF16)
         pool_keys_kernel<bf16_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start,
-                                                           block_table, (long)table_stride_b, num_pages, out);
+                                                           block_table, (long)table_stride_b, num_pages, out, nullptr);
     else
         pool_keys_kernel<fp16_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start,
-                                                           block_table, (long)table_stride_b, num_pages, out);
+                                                           block_table, (long)table_stride_b, num_pages, out, nullptr);
     return rsa_launch_status();
+}
+
+extern "C" int rsa_pool_keys(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                             int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
+                             const int32_t* start_dev, int start, int workgroups_per_head, float* out, void* stream) {
+    return sel_pool_keys_run(false, B, Hkv, Sk, D, dtype, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
+                             start_dev, start, workgroups_per_head, out, nullptr, stream);
+}
+
+// The cache from an e4m3 K: per block the fp32 sum of float(code) in sel_pool_block's order, divided once
+// by the count, multiplied once by k_scale[hk] (DEVICE fp32 [Hkv]).
+extern "C" int rsa_pool_keys_kv8(int B, int Hkv, int Sk, int D, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                                 int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
+                                 const int32_t* start_dev, int start, int workgroups_per_head, float* out, const float* k_scale,
+                                 void* stream) {
+    return sel_pool_keys_run(true, B, Hkv, Sk, D, 0, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
+                             start_dev, start, workgroups_per_head, out, k_scale, stream);
 }
 
 static int sel_pooled_check_sizes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {

@@ -21,6 +21,12 @@
 // in the log2 domain, P rounded to the input type for P.V, fp32 accumulation.  Keys at or beyond the limit are never multiplied:
 // their scores are replaced by selection, their V rows are zeroed on the way into LDS, and blocks without a key below the limit
 // (or with a list / table entry out of range) are not read at all.  No atomics: the same inputs give the same bytes.
+//
+// The e4m3 cache (rsa_block_sparse_decode_kv8) is the same two kernels instantiated over the cache's
+// element: Tag = kv8_tag<query type>.  K and V are then one-byte codes with one fp32 scale per K/V head: a lane loads 8 bytes of K
+// where it loads 16 (same keys, same d range) and half as many 16-byte pieces of V, and the codes become the query's 2-byte type in
+// registers (the packed scaled conversions with a unit scale: exact, every finite e4m3 value is a bf16 and an fp16).  The K scale multiplies the fp32
+// score behind the MFMA chain, the V scale the merged row once; the V image, the MFMAs, the softmax and the meet are the code below.
 #include "rsa_attn.h"
 
 #include <math.h>
@@ -48,6 +54,51 @@ struct DecArgs {
     float2* ws_ml;              // [B * U * nsplit, R16] (m in the log2 domain, l)
 };
 
+struct DecArgs8 : DecArgs {
+    const float *k_scale, *v_scale;     // [Hkv]: the value of a code is float(code) * scale[hk]
+};
+
+// The cache's element: the query's own 2-byte type (Tag = bf16_tag / fp16_tag), or e4m3 codes (kv8_tag<query type>).
+template <typename QTag>
+struct kv8_tag {};
+template <typename Tag>
+struct DecCache {
+    using Q = Tag;
+    using elem = unsigned short;
+    using Args = DecArgs;
+    using kfrag = uint4;                // 8 elements of a key: one A fragment
+    static constexpr bool kv8 = false;
+    static constexpr int VPIECE = 8;    // elements of a 16-byte piece of V
+};
+template <typename QTag>
+struct DecCache<kv8_tag<QTag>> {
+    using Q = QTag;
+    using elem = unsigned char;
+    using Args = DecArgs8;
+    using kfrag = uint2;
+    static constexpr bool kv8 = true;
+    static constexpr int VPIECE = 16;
+};
+
+// Four e4m3 codes -> four elements of the query's type (element i from byte i): gfx950's packed scaled conversions with a unit
+// scale, v_cvt_scalef32_pk_bf16_fp8 / v_cvt_scalef32_pk_f16_fp8, one per half of the dword: two instructions per dword.  Exact
+// (every finite code is a bf16 and an fp16: nothing is rounded).
+template <typename QTag>
+__device__ __forceinline__ uint2 dec_cvt4(unsigned w) {
+    if constexpr (std::is_same<QTag, bf16_tag>::value) {
+        return make_uint2(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false)),
+                          __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true)));
+    } else {
+        return make_uint2(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false)),
+                          __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true)));
+    }
+}
+template <typename QTag>
+__device__ __forceinline__ uint4 dec_cvt8(uint2 w) {
+    const uint2 a = dec_cvt4<QTag>(w.x), b = dec_cvt4<QTag>(w.y);
+    return make_uint4(a.x, a.y, b.x, b.y);
+}
+
 template <typename Tag>
 struct Mfma16;
 template <>
@@ -65,11 +116,11 @@ struct Mfma16<fp16_tag> {
 
 // A chunk's operands as they come from global memory: K as the A fragments of S^T (key = 16 t + (lane & 15), d = 32 ks +
 // 8 (lane >> 4) ..), V as 16-byte pieces of its [32][D] row image.  key0 < 0: nothing to do (the block is not visited).
-template <int D>
+template <int D, typename Cache>
 struct DecRaw {
-    uint4 kf[2][D / 32];
-    uint4 vf[D / 16];
-    const unsigned short* vb;   // the V rows of the chunk's batch item or page, and the offset of its row numbers
+    typename Cache::kfrag kf[2][D / 32];
+    uint4 vf[32 * D / Cache::VPIECE / 64];
+    const typename Cache::elem* vb;     // the V rows of the chunk's batch item or page, and the offset of its row numbers
     long roff;
     int key0;
 };
@@ -78,9 +129,15 @@ __device__ __forceinline__ s16x4 dec_tr_read(const unsigned char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
-template <typename Tag, int D, int MT>
-__global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(DecArgs a) {
-    constexpr int KS = D / 32, DT = D / 16, CH = D / 8, VL = D / 16;
+template <typename CTag, int D, int MT>
+__global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(typename DecCache<CTag>::Args a) {
+    using Cache = DecCache<CTag>;
+    using Tag = typename Cache::Q;      // the type of q, of the MFMA operands and of the output
+    using KT = typename Cache::elem;
+    using Raw = DecRaw<D, Cache>;
+    constexpr bool KV8 = Cache::kv8;
+    constexpr int VP = Cache::VPIECE;   // elements of a 16-byte piece of V
+    constexpr int KS = D / 32, DT = D / 16, CH = D / VP, VL = 32 * CH / 64;
     // At head dim 128 with four row tiles Q (64 registers) and O^T (128) do not fit beside two sets of K and V: the scaled Q
     // fragments then live in LDS (one image for the four waves) and are read again in every chunk.
     constexpr bool QLDS = D == 128 && MT == 4;
@@ -145,8 +202,10 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(D
     }
     unsigned char* vst = vimg + wave * (DEC_CHUNK * VROW);
     if constexpr (QLDS) __syncthreads();
-    const unsigned short* kbase = a.k + (long)hk * a.ksh;
-    const unsigned short* vbase = a.v + (long)hk * a.vsh;
+    const KT* kbase = reinterpret_cast<const KT*>(a.k) + (long)hk * a.ksh;
+    const KT* vbase = reinterpret_cast<const KT*>(a.v) + (long)hk * a.vsh;
+    float kscale = 1.f;
+    if constexpr (KV8) kscale = a.k_scale[hk];
 
     for (int e0 = 0; e0 < n_items; e0 += 64) {
         // this lane's list entry: the key block and where it lives, or -1 (out of range, no key below the limit, no page).  No
@@ -165,15 +224,15 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(D
         }
         const int nch = min(64, n_items - e0) << cshift;
 
-        auto load_v = [&](uint4 (&vf)[VL], const DecRaw<D>& r) {
+        auto load_v = [&](uint4 (&vf)[VL], const Raw& r) {
 #pragma unroll
             for (int i = 0; i < VL; ++i) {
                 const int idx = i * 64 + lane, vr = idx / CH, ch = idx % CH;
                 const long row = min(r.key0 + vr, kvlen - 1) + r.roff;
-                vf[i] = *reinterpret_cast<const uint4*>(r.vb + row * a.vss + 8 * ch);
+                vf[i] = *reinterpret_cast<const uint4*>(r.vb + row * a.vss + VP * ch);
             }
         };
-        auto load = [&](DecRaw<D>& r, int c) {
+        auto load = [&](Raw& r, int c) {
             const int entry = c >> cshift, sub = c & ((1 << cshift) - 1);
             const int j = __shfl(jv, entry, 64), pg = __shfl(pv, entry, 64);
             const int key0 = j * a.blk + sub * DEC_CHUNK;
@@ -182,7 +241,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(D
             r.key0 = key0;
             // rows at or beyond the limit are read as the last row below it: in bounds, masked (K) or zeroed (V) later
             const long roff = a.table ? -(long)j * a.blk : 0;     // paged: rows count from the page's first
-            const unsigned short* kb = kbase + (a.table ? (long)pg * a.ksb : (long)b * a.ksb);
+            const KT* kb = kbase + (a.table ? (long)pg * a.ksb : (long)b * a.ksb);
             r.vb = vbase + (a.table ? (long)pg * a.vsb : (long)b * a.vsb);
             r.roff = roff;
 #pragma unroll
@@ -190,7 +249,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(D
                 const long row = min(key0 + 16 * t + lr, kvlen - 1) + roff;
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)
-                    r.kf[t][ks] = *reinterpret_cast<const uint4*>(kb + row * a.kss + 32 * ks + 8 * lh);
+                    r.kf[t][ks] = *reinterpret_cast<const typename Cache::kfrag*>(kb + row * a.kss + 32 * ks + 8 * lh);
             }
             load_v(r.vf, r);
         };
@@ -199,7 +258,11 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(D
             if constexpr (QLDS) return *reinterpret_cast<const s16x8*>(qimg + qoff + 16 * mt * QROW + 64 * ks);
             else return qf[mt][ks];
         };
-        auto compute = [&](const DecRaw<D>& r) {
+        auto kfrag = [&](const Raw& r, int t, int ks) {
+            if constexpr (KV8) return __builtin_bit_cast(s16x8, dec_cvt8<Tag>(r.kf[t][ks]));
+            else return __builtin_bit_cast(s16x8, r.kf[t][ks]);
+        };
+        auto compute = [&](const Raw& r) {
             if (r.key0 < 0) return;                     // (uniform: the transposed reads below need every lane)
             const int key0 = r.key0;
             int qoff = lr * QROW + 16 * lh;
@@ -214,7 +277,8 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(D
                     f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks)
-                        s = Mfma16<Tag>::mfma(__builtin_bit_cast(s16x8, r.kf[t][ks]), qfrag(mt, ks, qoff), s);
+                        s = Mfma16<Tag>::mfma(kfrag(r, t, ks), qfrag(mt, ks, qoff), s);
+                    if constexpr (KV8) s *= kscale;         // the K scale: one fp32 multiply of the finished score
 #pragma unroll
                     for (int i = 0; i < 4; ++i) x[4 * t + i] = key0 + 16 * t + 4 * lh + i < lim[mt] ? s[i] : -INFINITY;
                 }
@@ -244,7 +308,12 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(D
             for (int i = 0; i < VL; ++i) {
                 const int idx = i * 64 + lane, vr = idx / CH, ch = idx % CH;
                 const uint4 x = key0 + vr < kvlen ? r.vf[i] : make_uint4(0, 0, 0, 0);
-                *reinterpret_cast<uint4*>(vst + vr * VROW + 16 * ch) = x;
+                if constexpr (KV8) {        // (the zero code is the zero element)
+                    *reinterpret_cast<uint4*>(vst + vr * VROW + 32 * ch) = dec_cvt8<Tag>(make_uint2(x.x, x.y));
+                    *reinterpret_cast<uint4*>(vst + vr * VROW + 32 * ch + 16) = dec_cvt8<Tag>(make_uint2(x.z, x.w));
+                } else {
+                    *reinterpret_cast<uint4*>(vst + vr * VROW + 16 * ch) = x;
+                }
             }
             // O^T += V^T . P^T: lane 4 q + p of a 16-lane group addresses key row (4 lh + q), d = 16 dt + 4 p .. + 3, and receives
             // d = 16 dt + lr of the rows' four keys
@@ -258,7 +327,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(D
             }
         };
 
-        DecRaw<D> ra, rb;
+        Raw ra, rb;
         int c = wave;
         if (c < nch) load(ra, c);
         while (c < nch) {
@@ -328,9 +397,16 @@ struct DecMergeArgs {
     long rows;                  // B * H * Sq
 };
 
+struct DecMergeArgs8 : DecMergeArgs {
+    const float* v_scale;       // [Hkv]: multiplies the merged row once
+    int Hkv;
+};
+
 // D / 4 threads per output row, four channels each; the splits in ascending order.
-template <typename Tag, int D>
-__global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(DecMergeArgs a) {
+template <typename CTag, int D>
+__global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
+    typename std::conditional<DecCache<CTag>::kv8, DecMergeArgs8, DecMergeArgs>::type a) {
+    using Tag = typename DecCache<CTag>::Q;
     constexpr int TPR = D / 4;
     const long g = (long)blockIdx.x * DEC_NT + threadIdx.x;
     const long row = g / TPR;
@@ -342,6 +418,8 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(DecMergeArgs a) {
     const long p0 = ((b * a.U + unit) * a.nsplit) * a.R16 + rr;
     const int count = min(max(a.counts[b * a.Hl + unit / (a.U / a.Hl)], 0), a.NK);
     const int nlive = min(a.nsplit, (count + a.C - 1) / a.C);
+    float vs = 1.f;
+    if constexpr (DecCache<CTag>::kv8) vs = a.v_scale[h / (a.H / a.Hkv)];      // (asked for before the partials: not behind them)
     float ms = -INFINITY;
     for (int s = 0; s < nlive; ++s) {
         const float2 v = a.ws_ml[p0 + (long)s * a.R16];
@@ -361,7 +439,11 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(DecMergeArgs a) {
         lt += f * v.y;
     }
     const bool any = lt > 0.f;
-    const float r[4] = {any ? acc.x / lt : 0.f, any ? acc.y / lt : 0.f, any ? acc.z / lt : 0.f, any ? acc.w / lt : 0.f};
+    float r[4] = {any ? acc.x / lt : 0.f, any ? acc.y / lt : 0.f, any ? acc.z / lt : 0.f, any ? acc.w / lt : 0.f};
+    if constexpr (DecCache<CTag>::kv8) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] *= vs;
+    }
     uint2 pk;
     pk.x = (unsigned)Elem<Tag>::from_f32(r[0]) | ((unsigned)Elem<Tag>::from_f32(r[1]) << 16);
     pk.y = (unsigned)Elem<Tag>::from_f32(r[2]) | ((unsigned)Elem<Tag>::from_f32(r[3]) << 16);
@@ -406,8 +488,8 @@ extern "C" int rsa_block_sparse_decode_bytes(int B, int H, int Hkv, int Hl, int 
     return st;
 }
 
-template <typename Tag, int D>
-static void dec_launch(const DecArgs& a, const DecMergeArgs& g, int MT, dim3 grid, hipStream_t s) {
+template <typename Tag, int D, typename A, typename G>
+static void dec_launch(const A& a, const G& g, int MT, dim3 grid, hipStream_t s) {
     if (MT == 1) decode_split_kernel<Tag, D, 1><<<grid, DEC_NT, 0, s>>>(a);
     else if (MT == 2) decode_split_kernel<Tag, D, 2><<<grid, DEC_NT, 0, s>>>(a);
     else decode_split_kernel<Tag, D, 4><<<grid, DEC_NT, 0, s>>>(a);
@@ -415,11 +497,19 @@ static void dec_launch(const DecArgs& a, const DecMergeArgs& g, int MT, dim3 gri
     decode_merge_kernel<Tag, D><<<dim3((unsigned)((threads + DEC_NT - 1) / DEC_NT)), DEC_NT, 0, s>>>(g);
 }
 
-extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
-                                       const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
-                                       rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
-                                       int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
-                                       size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
+// An e4m3 cache view as the loads need it: K is read 8 bytes a lane, V 16 (strides in elements = bytes).
+static int dec_check_cache8(const rsa_tensor4& t, int align) {
+    if (!t.ptr || (reinterpret_cast<uintptr_t>(t.ptr) & (align - 1))) return RSA_ERR_BAD_ARG;
+    if ((t.stride_b % align) || (t.stride_h % align) || (t.stride_s % align)) return RSA_ERR_BAD_ARG;
+    return RSA_OK;
+}
+
+// Both entries: kv8 = the cache holds e4m3 codes and the two scale arrays are there.
+static int dec_run(bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                   const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
+                   rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* cols,
+                   const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
+                   const float* k_scale, const float* v_scale, void* stream) {
     if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || Sk <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
     if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
@@ -433,7 +523,14 @@ extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, in
     const int st = dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
     if (st != RSA_OK) return st;
     if (!cols || !counts || !ws || !out.ptr) return RSA_ERR_BAD_ARG;
-    if (rsa_check_tensor(q) != RSA_OK || rsa_check_tensor(k) != RSA_OK || rsa_check_tensor(v) != RSA_OK) return RSA_ERR_BAD_ARG;
+    if (rsa_check_tensor(q) != RSA_OK) return RSA_ERR_BAD_ARG;
+    if (kv8) {
+        if (!k_scale || !v_scale || ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3))
+            return RSA_ERR_BAD_ARG;
+        if (dec_check_cache8(k, 8) != RSA_OK || dec_check_cache8(v, 16) != RSA_OK) return RSA_ERR_BAD_ARG;
+    } else if (rsa_check_tensor(k) != RSA_OK || rsa_check_tensor(v) != RSA_OK) {
+        return RSA_ERR_BAD_ARG;
+    }
     if (q.stride_b < 0 || q.stride_h < 0 || q.stride_s < 0 || k.stride_b < 0 || k.stride_h < 0 || k.stride_s < 0 ||
         v.stride_b < 0 || v.stride_h < 0 || v.stride_s < 0 || out.stride_b < 0 || out.stride_h < 0 || out.stride_s < 0)
         return RSA_ERR_BAD_ARG;
@@ -448,7 +545,7 @@ extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, in
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long parts = (long)B * p.U * p.nsplit;
-    DecArgs a;
+    DecArgs8 a;
     a.q = static_cast<const unsigned short*>(q.ptr);
     a.k = static_cast<const unsigned short*>(k.ptr);
     a.v = static_cast<const unsigned short*>(v.ptr);
@@ -467,7 +564,11 @@ extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, in
     a.qk_scale = (float)(sm_scale * 1.44269504);    // (as rsa_block_sparse_plain_fwd)
     a.ws_o = static_cast<float*>(ws);
     a.ws_ml = reinterpret_cast<float2*>(a.ws_o + parts * a.R16 * D);
-    DecMergeArgs g;
+    a.k_scale = k_scale;
+    a.v_scale = v_scale;
+    DecMergeArgs8 g;
+    g.v_scale = v_scale;
+    g.Hkv = Hkv;
     g.ws_o = a.ws_o;
     g.ws_ml = a.ws_ml;
     g.out = static_cast<unsigned short*>(out.ptr);
@@ -478,12 +579,42 @@ extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, in
     g.H = H; g.U = p.U; g.Sq = Sq; g.nsplit = p.nsplit; g.R16 = a.R16;
     g.rows = (long)B * H * Sq;
     const dim3 grid((unsigned)((long)B * p.U), (unsigned)p.nsplit);
-    if (dtype == RSA_BF16) {
-        if (D == 128) dec_launch<bf16_tag, 128>(a, g, p.MT, grid, s);
-        else dec_launch<bf16_tag, 64>(a, g, p.MT, grid, s);
+    const DecArgs& a2 = a;              // the 2-byte kernels take the base structs
+    const DecMergeArgs& g2 = g;
+    if (kv8) {
+        if (dtype == RSA_BF16) {
+            if (D == 128) dec_launch<kv8_tag<bf16_tag>, 128>(a, g, p.MT, grid, s);
+            else dec_launch<kv8_tag<bf16_tag>, 64>(a, g, p.MT, grid, s);
+        } else {
+            if (D == 128) dec_launch<kv8_tag<fp16_tag>, 128>(a, g, p.MT, grid, s);
+            else dec_launch<kv8_tag<fp16_tag>, 64>(a, g, p.MT, grid, s);
+        }
+    } else if (dtype == RSA_BF16) {
+        if (D == 128) dec_launch<bf16_tag, 128>(a2, g2, p.MT, grid, s);
+        else dec_launch<bf16_tag, 64>(a2, g2, p.MT, grid, s);
     } else {
-        if (D == 128) dec_launch<fp16_tag, 128>(a, g, p.MT, grid, s);
-        else dec_launch<fp16_tag, 64>(a, g, p.MT, grid, s);
+        if (D == 128) dec_launch<fp16_tag, 128>(a2, g2, p.MT, grid, s);
+        else dec_launch<fp16_tag, 64>(a2, g2, p.MT, grid, s);
     }
     return rsa_launch_status();
+}
+
+extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                       const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                       rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                       int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
+                                       size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
+    return dec_run(false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
+                   table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr, stream);
+}
+
+// The e4m3 cache: dtype names q's type; k / v hold one-byte codes (strides in bytes) and the scales are DEVICE fp32 [Hkv].
+extern "C" int rsa_block_sparse_decode_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                           const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                           rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                           int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split,
+                                           void* ws, size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale,
+                                           const float* v_scale, void* stream) {
+    return dec_run(true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
+                   table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale, stream);
 }
