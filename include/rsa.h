@@ -430,6 +430,34 @@ int rsa_pool_keys_kv8(int B, int Hkv, int Sk, int D, int block, int NK, rsa_tens
                       int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid, const int32_t* start_dev,
                       int start, int workgroups_per_head, float* out, const float* k_scale, void* stream);
 
+/* ---- top-p block selection: a budget per list row (found by symbol: the header version stays 6.1).
+ * rsa_block_select_p and rsa_block_select_pooled_p are rsa_block_select and rsa_block_select_pooled -- their argument lists,
+ * pooling, scores, visible and forced sets, outputs, workspaces (the _bytes entries return their counterparts' sizes) and refusals
+ * -- with p16, c and mass in front of the stream, and top_k as the cap on the kept count.  All weights are integers:
+ *   weight    t_max = the maximum of t over the row's visible blocks (forced ones included, -0 as +0); a_j = (t_j - t_max) * c, one
+ *             fp32 subtraction and one fp32 multiplication; u_j = (uint32) floor(exp2(a_j) * 2^18 + 0.5) <= 2^18, the product
+ *             and the sum in fp32.  c = (float)(score_scale * log2(e)) is formed by the caller; exp2 is exact at integers.
+ *   target    total = sum of u_j over the visible blocks; target = (total * p16 + 65535) >> 16 in 64 bits, p16 = round(top_p * 65536)
+ *   kept      the forced blocks and the first min(n_p, n_k, |unforced|) visible unforced blocks by t descending, the lower j first
+ *             among equals: n_p = the length of the shortest such prefix with sum(forced u) + sum(prefix u) >= target (0 when the
+ *             forced blocks alone reach it), n_k = max(top_k - |forced|, 0).  p16 = 0 keeps the forced blocks alone; p16 = 65536
+ *             every block of non-zero weight, up to the cap.
+ *   mass      NULL, or DEVICE fp32 [B * Hl * NQ]: (float)(sum of u_j over the kept blocks) / (float)total, 0 for a row that sees
+ *             nothing.
+ * The same inputs give the same bytes (integer sums).  With non-finite scores which blocks win is unspecified; the lists stay well
+ * formed.  p16 outside [0, 65536], a c that is not finite or not > 0, a misaligned mass: RSA_ERR_BAD_ARG.  Every check runs before
+ * the first HIP call.  The select workgroup runs in place of the top-k one: the same number of launches. */
+int rsa_block_select_p_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes);
+int rsa_block_select_p(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q,
+                       rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k, int keep_first,
+                       int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores,
+                       int p16, float c, float* mass, void* stream);
+int rsa_block_select_pooled_p_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes);
+int rsa_block_select_pooled_p(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q,
+                              const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k,
+                              int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask,
+                              int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

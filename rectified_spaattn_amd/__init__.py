@@ -52,15 +52,17 @@ def block_sparse_attention(q, k, v, block_mask, *, kv_len=None, sm_scale=None, b
 
 
 def select_blocks(q, k, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0, mask_heads="kv",
-                  return_scores=False, as_lists=False):
+                  return_scores=False, as_lists=False, top_p=None, score_scale=None, return_mass=False):
     """Top-k key blocks per query block by pooled scores, per K/V head (mask_heads="q": per query head), on the device: q
     [B,H,Sq,D], k [B,Hkv,Sk,D] -> bool block mask [B, Hkv|H, ceil(Sq/block), ceil(Sk/block)] for block_sparse_attention with
-    the same kv_len / causal / block_size; keep_first / keep_local force the first blocks and the diagonal band.
+    the same kv_len / causal / block_size; keep_first / keep_local force the first blocks and the diagonal band.  top_p in
+    [0, 1]: a budget per row, the shortest prefix of the ranking whose softmax mass (at score_scale) reaches top_p, capped at
+    top_k; return_mass=True adds the kept mass, fp32 [B, Hkv|H, NQ].
     See rectified_spaattn_amd.block_sparse.select_blocks."""
     from . import block_sparse
     return block_sparse.select_blocks(q, k, top_k, block_size=block_size, kv_len=kv_len, causal=causal, keep_first=keep_first,
                                       keep_local=keep_local, mask_heads=mask_heads, return_scores=return_scores,
-                                      as_lists=as_lists)
+                                      as_lists=as_lists, top_p=top_p, score_scale=score_scale, return_mass=return_mass)
 
 
 def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
@@ -94,13 +96,15 @@ def append_kv_e4m3(k_new, v_new, k_cache, v_cache, *, start, k_scale, v_scale, n
 
 
 def select_blocks_pooled(q, pooled_k, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0,
-                         mask_heads="kv", return_scores=False, as_lists=False, score_splits=None):
-    """select_blocks from a cache of pooled keys (pool_keys) in place of k: the same bytes without a pass over K.
+                         mask_heads="kv", return_scores=False, as_lists=False, score_splits=None, top_p=None, score_scale=None,
+                         return_mass=False):
+    """select_blocks from a cache of pooled keys (pool_keys) in place of k: the same bytes without a pass over K, with top_p too.
     See rectified_spaattn_amd.block_sparse.select_blocks_pooled."""
     from . import block_sparse
     return block_sparse.select_blocks_pooled(q, pooled_k, top_k, block_size=block_size, kv_len=kv_len, causal=causal,
                                              keep_first=keep_first, keep_local=keep_local, mask_heads=mask_heads,
-                                             return_scores=return_scores, as_lists=as_lists, score_splits=score_splits)
+                                             return_scores=return_scores, as_lists=as_lists, score_splits=score_splits,
+                                             top_p=top_p, score_scale=score_scale, return_mass=return_mass)
 
 
 def clear_buffer_cache() -> None:

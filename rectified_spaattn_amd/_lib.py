@@ -118,6 +118,12 @@ PROTOTYPES = {
     "rsa_block_sparse_decode_kv8": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp,
                                           i64, i32, vp, vp, i32, vp, sz, O4, vp, vp, vp, vp]),
     "rsa_pool_keys_kv8": (i32, [i32, i32, i32, i32, i32, i32, T4, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp, vp]),
+    "rsa_block_select_p_bytes": (i32, [i32, i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_block_select_p": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, T4, vp, i32, i32, i32, i32, i32, vp,
+                                 sz, vp, vp, vp, vp, i32, f32, vp, vp]),
+    "rsa_block_select_pooled_p_bytes": (i32, [i32, i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_block_select_pooled_p": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, vp, vp, i32, i32, i32, i32, i32, i32,
+                                        vp, sz, vp, vp, vp, vp, i32, f32, vp, vp]),
     "rsa_select_from_mask": (i32, [P(RsaLayout), vp, i64, i64, i64, P(RsaBuffers), vp]),
     "rsa_select_from_mask_ex": (i32, [P(RsaLayoutEx), vp, i64, i64, i64, P(RsaBuffers), vp]),
     "rsa_rectified_attention_masked": (i32, [P(RsaLayout), T4, T4, T4, vp, i64, i64, i64, vp, sz, O4, vp]),

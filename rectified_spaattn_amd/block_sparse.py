@@ -36,6 +36,7 @@ kv_len) is 0 here; the reference's Triton kernel divides 0 by 0 there and return
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Dict, Optional
 
 import torch
@@ -512,7 +513,8 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
 
 def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None, causal: bool = False,
                   keep_first: int = 0, keep_local: int = 0, mask_heads: str = "kv", return_scores: bool = False,
-                  as_lists: bool = False):
+                  as_lists: bool = False, top_p: Optional[float] = None, score_scale: Optional[float] = None,
+                  return_mass: bool = False):
     """Top-k key blocks per query block by pooled scores, per K/V head, on the device (MoBA-style): the
     block_mask of a following block_sparse_attention(q, k, v, mask, kv_len=..., causal=..., block_size=...).
     q [B,H,Sq,D], k [B,Hkv,Sk,D] with H % Hkv == 0 (query head h belongs to K/V head h // (H // Hkv)), bf16 or fp16, head dim 16,
@@ -532,24 +534,60 @@ def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: i
     Returns the bool mask [B, Hl, NQ, NK] (Hl = Hkv or H), or with as_lists=True the dict block_mask_to_lists returns for it
     (bitmask, cols, counts; row (b * Hl + hl) * NQ + i); with return_scores=True a pair, the second the fp32 scores
     [B, Hl, NQ, NK] with -inf at invisible blocks.  Two calls on the same inputs give the same bytes.  With non-finite scores
-    which blocks win is unspecified; the rows stay well formed.  Asynchronous on the current stream."""
+    which blocks win is unspecified; the rows stay well formed.  Asynchronous on the current stream.
+
+    top_p in [0, 1] (rsa_block_select_p): a budget per row.  Everything above stands, except that top_k
+    becomes the cap on |kept| and the row keeps the forced blocks and the shortest prefix of the ranking above (t descending, the
+    lower j on equal t) whose softmax mass reaches top_p:
+      weight    u_j = floor(exp2((t_j - t_max) * c) * 2^18 + 0.5), an integer, t_max over the row's visible blocks, c =
+                float32(score_scale * log2(e)); score_scale defaults to 1 / ((H // Hl) * sqrt(D)) -- the logit is then the mean
+                pooled logit of the list head's query heads at block_sparse_attention's default sm_scale -- and must be finite, > 0
+      target    (total * round(top_p * 65536) + 65535) >> 16, total = the sum of u_j over the visible blocks
+      kept      forced and the first min(n_p, max(top_k - |forced|, 0)) visible unforced blocks, n_p = the length of the shortest
+                prefix with sum(forced u) + sum(prefix u) >= target.  top_p = 0 keeps the forced blocks alone, top_p = 1 every
+                block of non-zero weight, up to the cap
+    return_mass=True appends the fp32 tensor [B, Hl, NQ] of float(sum of kept u) / float(total) (0 for a row that sees nothing)
+    to the return value.  Integer sums: two calls give the same bytes.  score_scale and return_mass are refused without top_p."""
     return _select("select_blocks", q, k, False, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
-                   return_scores, as_lists)
+                   return_scores, as_lists, None, top_p, score_scale, return_mass)
 
 
 MAX_SCORE_SPLITS = 256  # score workgroups per list row of select_blocks_pooled, at most (rsa_block_select.hip)
+LOG2_E = 1.4426950408889634     # c = float32(score_scale * LOG2_E), the product formed in double (ctypes rounds it once)
+
+
+def _check_top_p(top_p, score_scale, return_mass):
+    """The budget options of the two selections: top_p None or a real in [0, 1]; score_scale None or a finite real > 0 whose c
+    is still a finite float32 > 0; score_scale and return_mass belong to top_p."""
+    def real(x):
+        return isinstance(x, (int, float)) and not isinstance(x, bool)
+    if top_p is None:
+        if score_scale is not None:
+            raise ValueError(f"score_scale: belongs to top_p (top_p is None), got {score_scale!r}")
+        if return_mass:
+            raise ValueError("return_mass: belongs to top_p (top_p is None)")
+        return
+    if not real(top_p) or not 0.0 <= float(top_p) <= 1.0:
+        raise ValueError(f"top_p: None or a number in [0, 1], got {top_p!r}")
+    if score_scale is not None:
+        c = ctypes.c_float(float(score_scale) * LOG2_E).value if real(score_scale) else float("nan")
+        if not 0.0 < c < float("inf"):
+            raise ValueError(f"score_scale: None or a finite number > 0 (and score_scale * log2(e) a finite float32 > 0), "
+                             f"got {score_scale!r}")
 
 
 def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
-            return_scores, as_lists, score_splits=None):
+            return_scores, as_lists, score_splits=None, top_p=None, score_scale=None, return_mass=False):
     """select_blocks (keys = k, rsa_block_select) and select_blocks_pooled (keys = pool_keys' cache, rsa_block_select_pooled,
-    with its score_splits): the two differ in where kbar comes from and in nothing else."""
+    with its score_splits): the two differ in where kbar comes from and in nothing else.  With top_p the entries are their _p
+    forms, which take (p16, c, mass) in front of the stream."""
     blk = _check_block(what, block_size)
     if mask_heads not in ("kv", "q"):
         raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
     for name, val in (("top_k", top_k), ("keep_first", keep_first), ("keep_local", keep_local)):
         _check_count(name, val, 0)
     _check_count("score_splits", score_splits, 1, MAX_SCORE_SPLITS, optional=True)
+    _check_top_p(top_p, score_scale, return_mass)
     B, H, Hkv, Sq, Sk, D = _check_operands(q, keys, pooled=pooled)
     if pooled:      # the cache holds NK blocks: the capacity is taken as NK * block
         Sk *= blk
@@ -563,7 +601,7 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
     kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
     L = _lib.lib()
     q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
-    entry = "rsa_block_select_pooled" if pooled else "rsa_block_select"
+    entry = ("rsa_block_select_pooled" if pooled else "rsa_block_select") + ("" if top_p is None else "_p")
     need = ctypes.c_size_t(0)
     _lib.check(getattr(L, entry + "_bytes")(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), entry + "_bytes")
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
@@ -574,13 +612,19 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         splits = (0 if score_splits is None else int(score_splits),)
     else:
         shape, source, splits = (B, H, Hkv, Hl, Sq, Sk, D), _core._t4(keys), ()
+    mass, budget = None, ()
+    if top_p is not None:
+        mass = torch.empty((B, Hl, NQ), dtype=torch.float32, device=dev) if return_mass else None
+        scale = 1.0 / ((H // Hl) * math.sqrt(D)) if score_scale is None else float(score_scale)
+        budget = (int(round(float(top_p) * 65536.0)), scale * LOG2_E, _ptr(mass))
     with torch.cuda.device(dev):
         _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, NQ, NK, _core._t4(q), source, _ptr(kv_dev), kv_valid,
                                      int(bool(causal)), min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), *splits,
                                      ws.data_ptr(), need.value, out["bitmask"].data_ptr(), out["cols"].data_ptr(),
-                                     out["counts"].data_ptr(), _ptr(scores), _core._stream()), entry)
+                                     out["counts"].data_ptr(), _ptr(scores), *budget, _core._stream()), entry)
     sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
-    return (sel, scores) if return_scores else sel
+    extra = tuple(t for t in (scores, mass) if t is not None)
+    return (sel,) + extra if extra else sel
 
 
 def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_table=None, out: Optional[torch.Tensor] = None,
@@ -705,7 +749,8 @@ def append_kv_e4m3(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tens
 
 def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None,
                          causal: bool = False, keep_first: int = 0, keep_local: int = 0, mask_heads: str = "kv",
-                         return_scores: bool = False, as_lists: bool = False, score_splits: Optional[int] = None):
+                         return_scores: bool = False, as_lists: bool = False, score_splits: Optional[int] = None,
+                         top_p: Optional[float] = None, score_scale: Optional[float] = None, return_mass: bool = False):
     """select_blocks from a cache of pooled keys: q [B,H,Sq,D] (any Sq), pooled_k fp32 [B, Hkv, NK, D]
     contiguous as pool_keys returns it, Sk taken as NK * block_size.  Visible set, forced blocks, top-k, ties and the returned
     mask / lists / scores are select_blocks' contract word for word, and on inputs both calls accept
@@ -716,9 +761,10 @@ def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *,
     device only).
     score_splits: workgroups per list row that compute the row's scores before the select workgroup ranks them (few list rows,
     many key blocks: a decode step); 1 = inside the select workgroup; None = the library's choice, a function of the shapes alone
-    (measured: DESIGN.md 5.13).  Every value gives the same bytes.  Asynchronous on the current stream, capturable."""
+    (measured: DESIGN.md 5.13).  Every value gives the same bytes.  Asynchronous on the current stream, capturable.
+    top_p, score_scale, return_mass: select_blocks' (rsa_block_select_pooled_p), with the same bytes."""
     return _select("select_blocks_pooled", q, pooled_k, True, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
-                   return_scores, as_lists, score_splits)
+                   return_scores, as_lists, score_splits, top_p, score_scale, return_mass)
 
 
 DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_decode.hip)

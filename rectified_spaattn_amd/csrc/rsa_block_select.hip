@@ -19,16 +19,12 @@
 //   block_select_kernel<L, 1>  the select body over keys loaded from that workspace instead of computed
 //
 // Every sum has a fixed order (no floating-point atomics; the histograms count integers): two calls give the same bytes.
-#include "rsa_common.h"
-
-#include <math.h>
+//
+// The score-and-select device functions live in rsa_block_select.h, which the top-p selection (rsa_block_select_p.hip, DESIGN.md
+// section 5.15) includes too; the host bodies sel_run / sel_pooled_run serve both and hand the select launch to it with a budget.
+#include "rsa_block_select.h"
 
 #include <type_traits>
-
-#define SEL_NT 256
-#define SEL_MAX_NK 8192
-#define SEL_MAX_STEPS (SEL_MAX_NK / 64)
-#define SEL_MAX_SPLITS 256      // score workgroups per list row of the pooled selection, at most
 
 // ---- pooling ---------------------------------------------------------------------------------------------------------------------
 // The element loaders: what a lane reads for its 8 channels of a row, and how it adds them.  bf16 / fp16: 16 bytes.  e4m3_tag (the
@@ -108,10 +104,6 @@ template <typename Tag>
 __device__ __forceinline__ float sel_pool_mean(const typename SelElem<Tag>::type* __restrict__ base, long stride_s, int rows,
                                                int D, float (*red)[128]) {
     return sel_pool_block<Tag>(base, stride_s, rows, D, red) / (float)rows;
-}
-
-__device__ __forceinline__ int sel_key_limit(const int32_t* __restrict__ kv_len, int b, int kv_valid, int Sk) {
-    return kv_len ? min(max(kv_len[b], 0), Sk) : kv_valid;
 }
 
 template <typename Tag>
@@ -196,70 +188,6 @@ __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hk
 }
 
 // ---- score and select ------------------------------------------------------------------------------------------------------------
-// fp32 -> u32 with the order of the floats (-0 counts as +0); and back.
-__device__ __forceinline__ unsigned sel_key(float x) {
-    unsigned u = __float_as_uint(x);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sel_unkey(unsigned key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
-// Exclusive prefix sums of cnt[0 .. n) in place (n <= SEL_MAX_STEPS) by one wave; returns the total (in every lane).
-__device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
-    int run = 0;
-    for (int s0 = 0; s0 < n; s0 += 64) {
-        const int s = s0 + lane;
-        const int c = s < n ? cnt[s] : 0;
-        int inc = c;
-        for (int m = 1; m < 64; m <<= 1) {
-            const int o = __shfl_up(inc, m, 64);
-            if (lane >= m) inc += o;
-        }
-        if (s < n) cnt[s] = run + inc - c;
-        run += __shfl(inc, 63, 64);
-    }
-    return run;
-}
-
-// Visible blocks of list row (b, i): a prefix [0, nvis) of the row.
-__device__ __forceinline__ int sel_visible(int len, int Sq, int blk, int NK, int i, int causal) {
-    const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
-    int nvis = min(NK, (len + blk - 1) / blk);
-    if (causal) nvis = r1 + off < 0 ? 0 : (int)min((long)nvis, (r1 + off) / blk + 1);
-    return nvis;
-}
-
-// Scores of the key blocks [lo, hi) of one list row as ordered keys into dst[j], by one workgroup.  L = D / 4 lanes share one
-// pooled key row (a float4 each); a wave scores 64 / L key blocks per step.  kb: the pooled rows of (b, K/V head); qrow: the row's
-// pooled query.
-template <int L>
-__device__ __forceinline__ void sel_score_blocks(const float* __restrict__ kb, const float* __restrict__ qrow, int lo, int hi,
-                                                 unsigned* dst) {
-    constexpr int D = 4 * L, RW = 64 / L, U = 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int cl = lane % L, sub = lane / L;
-    const float4 qv = *reinterpret_cast<const float4*>(qrow + cl * 4);
-    kb += cl * 4;
-    for (int j0 = lo + wave * RW; j0 < hi; j0 += 4 * RW * U) {
-        float4 kv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * 4 * RW + sub;
-            kv[u] = j < hi ? *reinterpret_cast<const float4*>(kb + (long)j * D) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * 4 * RW + sub;
-            float p = fmaf(qv.w, kv[u].w, fmaf(qv.z, kv[u].z, fmaf(qv.y, kv[u].y, qv.x * kv[u].x)));
-#pragma unroll
-            for (int m = 1; m < L; m <<= 1) p += __shfl_xor(p, m, 64);
-            if (cl == 0 && j < hi) dst[j] = sel_key(p);
-        }
-    }
-}
-
 // The score pass of the pooled selection spread over `splits` workgroups per list row: workgroup (row, part) writes the keys of
 // its slice of the visible blocks to wkeys[row, :].
 template <int L>
@@ -433,6 +361,14 @@ extern "C" int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, i
                                 rsa_tensor4 q, rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k,
                                 int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
                                 int32_t* counts, float* scores, void* stream) {
+    return sel_run(B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NQ, NK, q, k, kv_len_dev, kv_valid, causal, top_k, keep_first, keep_local,
+                   ws, ws_bytes, bitmask, cols, counts, scores, nullptr, stream);
+}
+
+int sel_run(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q, rsa_tensor4 k,
+            const int32_t* kv_len_dev, int kv_valid, int causal, int top_k, int keep_first, int keep_local, void* ws,
+            size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, const sel_top_p* top_p,
+            void* stream) {
     if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || Sk <= 0) return RSA_ERR_BAD_ARG;
     if (H % Hkv || (Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
     if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
@@ -467,6 +403,9 @@ extern "C" int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, i
                                                                         kv_len_dev, kv_valid, kbar, qsum);
     int rc = rsa_launch_status();
     if (rc != RSA_OK) return rc;
+    if (top_p)
+        return sel_launch_top_p(D, q_jobs, {kbar, qsum, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid, causal != 0,
+                                            top_k, keep_first, keep_local, bitmask, cols, counts, scores}, *top_p, s);
     const dim3 grid((unsigned)q_jobs);
     const size_t lds = (size_t)NK * sizeof(unsigned);
 #define SEL_LAUNCH(LANES)                                                                                                       \
@@ -579,6 +518,14 @@ extern "C" int rsa_block_select_pooled(int B, int H, int Hkv, int Hl, int Sq, in
                                        rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal,
                                        int top_k, int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes,
                                        uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, void* stream) {
+    return sel_pooled_run(B, H, Hkv, Hl, Sq, D, dtype, block, NQ, NK, q, pooled_k, kv_len_dev, kv_valid, causal, top_k, keep_first,
+                          keep_local, score_splits, ws, ws_bytes, bitmask, cols, counts, scores, nullptr, stream);
+}
+
+int sel_pooled_run(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q,
+                   const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k, int keep_first,
+                   int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                   int32_t* counts, float* scores, const sel_top_p* top_p, void* stream) {
     if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (H % Hkv || (Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
     if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
@@ -623,6 +570,12 @@ extern "C" int rsa_block_select_pooled(int B, int H, int Hkv, int Hl, int Sq, in
                                                            kv_valid, causal != 0, wkeys);                                       \
         rc = rsa_launch_status();                                                                                               \
         if (rc != RSA_OK) return rc;                                                                                            \
+    }                                                                                                                           \
+    if (top_p)                                                                                                                  \
+        return sel_launch_top_p(D, q_jobs, {pooled_k, qsum, splits > 1 ? wkeys : nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK,       \
+                                            kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols,    \
+                                            counts, scores}, *top_p, s);                                                        \
+    if (splits > 1) {                                                                                                           \
         block_select_kernel<LANES, 1><<<grid, SEL_NT, lds, s>>>(pooled_k, qsum, wkeys, Hkv, Hl, Sq, Sk, block, NQ, NK,          \
                                                                 kv_len_dev, kv_valid, causal != 0, top_k, keep_first,           \
                                                                 keep_local, bitmask, cols, counts, scores);                     \
