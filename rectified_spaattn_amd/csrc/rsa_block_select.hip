@@ -1,30 +1,76 @@
-// Top-k block selection per list head on the device (include/rsa.h: rsa_block_select_bytes, rsa_block_select; DESIGN.md
-// section 5.11).  Two kernels, both plain HIP C++ for wave64:
+// Block selection per list head on the device: the top-k budget (include/rsa.h: rsa_block_select), the
+// pooled-key cache (rsa_pool_keys, rsa_block_select_pooled; section 5.13) and the top-p budget (rsa_block_select_p,
+// rsa_block_select_pooled_p; section 5.15).  The only selection source.  All kernels are plain HIP C++ for wave64:
 //
 //   block_select_pool_kernel   one workgroup per (b, list head, query block) and per (b, K/V head, key block): the fp32 mean of
 //                              the block's rows per channel.  q and k are read exactly once, 16 bytes per lane and load.  The
 //                              query side adds the means of the list head's query heads in ascending order (H / Hl of them).
-//   block_select_kernel        one 256-thread workgroup per list row (b, list head, query block): the pooled scores of the
-//                              visible key blocks into LDS as order-preserving 32-bit keys, the k-th best by a radix select over
-//                              LDS histograms (8 bits a pass), ties to the lower block index by ballot / prefix popcount, and the
-//                              list contract of rsa_block_mask.hip (bitmask, ascending cols, counts) in 64-block ballot steps.
-//
-// The pooled-key cache (rsa_pool_keys, rsa_block_select_pooled_bytes, rsa_block_select_pooled) runs the
-// same device code: sel_pool_mean, sel_score_blocks and the select body below exist once.
-//
 //   pool_keys_kernel           W workgroups per (b, K/V head) stride over the key blocks [start / block, ceil(len / block)) and
 //                              write sel_pool_mean of each, read directly or through a block table, into the fp32 cache
 //   block_score_kernel         `splits` workgroups per list row: each writes its slice of the row's ordered keys to the workspace
 //                              (a lane group computes a whole score: nothing is summed across workgroups)
-//   block_select_kernel<L, 1>  the select body over keys loaded from that workspace instead of computed
+//   block_select[_p]_kernel    one 256-thread workgroup per list row (b, list head, query block): top-k; top-p capped at top_k
 //
-// Every sum has a fixed order (no floating-point atomics; the histograms count integers): two calls give the same bytes.
+// The two select kernels are sel_row_body<L, LOADED, BUDGET>: the pooled scores of the visible key blocks into LDS as
+// order-preserving 32-bit keys (computed, or LOADED from block_score_kernel's workspace), one decision (take_all, cut, T, need_eq),
+// and the list contract of rsa_block_mask.hip (bitmask, ascending cols, counts) in 64-block ballot steps, ties to the lower block
+// index by ballot / prefix popcount.  The decision is the one place where the budgets differ.  Top-k: the key T of the n_k-th best
+// unforced block by a radix select over LDS histograms (8 bits a pass, sel_radix<false>).  Top-p: a block weighs
+// u = floor(exp2((t - t_max) c) 2^18 + 0.5), an integer, recomputed from its key wherever it is needed: t_max by an integer maximum
+// over the keys, the row's total and its forced mass by integer sums, the cut by the same radix with hist[digit] += u
+// (sel_radix<true>), need_eq = ceil(rest / u_T); where the cap top_k binds, (T, need_eq) come from the counting radix instead.
 //
-// The score-and-select device functions live in rsa_block_select.h, which the top-p selection (rsa_block_select_p.hip, DESIGN.md
-// section 5.15) includes too; the host bodies sel_run / sel_pooled_run serve both and hand the select launch to it with a budget.
-#include "rsa_block_select.h"
+// exp2 is __builtin_amdgcn_exp2f (v_exp_f32), the function of the attention kernels: exact at integer arguments.  Every fp32 sum has
+// a fixed order; histograms and weights are unsigned integer sums (at most 8192 weights of at most 2^18): two calls, the same bytes.
+#include "rsa_common.h"
 
+#include <math.h>
 #include <type_traits>
+
+#define SEL_NT 256
+#define SEL_MAX_NK 8192
+#define SEL_MAX_STEPS (SEL_MAX_NK / 64)
+#define SEL_MAX_SPLITS 256      // score workgroups per list row of the pooled selection, at most
+#define SELP_ONE 262144u        // 2^18: the weight of the row's best block
+
+__device__ __forceinline__ int sel_key_limit(const int32_t* __restrict__ kv_len, int b, int kv_valid, int Sk) {
+    return kv_len ? min(max(kv_len[b], 0), Sk) : kv_valid;
+}
+
+// fp32 -> u32 with the order of the floats (-0 counts as +0); and back.
+__device__ __forceinline__ unsigned sel_key(float x) {
+    unsigned u = __float_as_uint(x);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sel_unkey(unsigned key) {
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+// Exclusive prefix sums of cnt[0 .. n) in place (n <= SEL_MAX_STEPS) by one wave; returns the total (in every lane).
+__device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
+    int run = 0;
+    for (int s0 = 0; s0 < n; s0 += 64) {
+        const int s = s0 + lane;
+        const int c = s < n ? cnt[s] : 0;
+        int inc = c;
+        for (int m = 1; m < 64; m <<= 1) {
+            const int o = __shfl_up(inc, m, 64);
+            if (lane >= m) inc += o;
+        }
+        if (s < n) cnt[s] = run + inc - c;
+        run += __shfl(inc, 63, 64);
+    }
+    return run;
+}
+
+// Visible blocks of list row (b, i): a prefix [0, nvis) of the row.
+__device__ __forceinline__ int sel_visible(int len, int Sq, int blk, int NK, int i, int causal) {
+    const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
+    int nvis = min(NK, (len + blk - 1) / blk);
+    if (causal) nvis = r1 + off < 0 ? 0 : (int)min((long)nvis, (r1 + off) / blk + 1);
+    return nvis;
+}
 
 // ---- pooling ---------------------------------------------------------------------------------------------------------------------
 // The element loaders: what a lane reads for its 8 channels of a row, and how it adds them.  bf16 / fp16: 16 bytes.  e4m3_tag (the
@@ -187,7 +233,36 @@ __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hk
     }
 }
 
-// ---- score and select ------------------------------------------------------------------------------------------------------------
+// ---- scores ----------------------------------------------------------------------------------------------------------------------
+// Scores of the key blocks [lo, hi) of one list row as ordered keys into dst[j], by one workgroup.  L = D / 4 lanes share one
+// pooled key row (a float4 each); a wave scores 64 / L key blocks per step.  kb: the pooled rows of (b, K/V head); qrow: the row's
+// pooled query.
+template <int L>
+__device__ __forceinline__ void sel_score_blocks(const float* __restrict__ kb, const float* __restrict__ qrow, int lo, int hi,
+                                                 unsigned* dst) {
+    constexpr int D = 4 * L, RW = 64 / L, U = 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cl = lane % L, sub = lane / L;
+    const float4 qv = *reinterpret_cast<const float4*>(qrow + cl * 4);
+    kb += cl * 4;
+    for (int j0 = lo + wave * RW; j0 < hi; j0 += 4 * RW * U) {
+        float4 kv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * 4 * RW + sub;
+            kv[u] = j < hi ? *reinterpret_cast<const float4*>(kb + (long)j * D) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * 4 * RW + sub;
+            float p = fmaf(qv.w, kv[u].w, fmaf(qv.z, kv[u].z, fmaf(qv.y, kv[u].y, qv.x * kv[u].x)));
+#pragma unroll
+            for (int m = 1; m < L; m <<= 1) p += __shfl_xor(p, m, 64);
+            if (cl == 0 && j < hi) dst[j] = sel_key(p);
+        }
+    }
+}
+
 // The score pass of the pooled selection spread over `splits` workgroups per list row: workgroup (row, part) writes the keys of
 // its slice of the visible blocks to wkeys[row, :].
 template <int L>
@@ -209,118 +284,212 @@ __global__ __launch_bounds__(SEL_NT) void block_score_kernel(const float* __rest
     sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, lo, hi, wkeys + row * NK);
 }
 
-// LOADED = 0: the scores are computed here (kbar, qsum); LOADED = 1: their keys are loaded from wkeys [rows, NK] (block_score_kernel).
-template <int L, int LOADED>
-__global__ __launch_bounds__(SEL_NT) void block_select_kernel(const float* __restrict__ kbar, const float* __restrict__ qsum,
-                                                              const unsigned* __restrict__ wkeys,
-                                                              int Hkv, int Hl, int Sq, int Sk, int blk, int NQ, int NK,
-                                                              const int32_t* __restrict__ kv_len, int kv_valid, int causal,
-                                                              int top_k, int keep_first, int keep_local,
-                                                              uint32_t* __restrict__ bitmask, int32_t* __restrict__ cols,
-                                                              int32_t* __restrict__ counts, float* __restrict__ scores) {
+// ---- select ----------------------------------------------------------------------------------------------------------------------
+// The rows the select kernels are launched over.
+struct sel_rows {
+    const float* kbar;
+    const float* qsum;
+    const unsigned* wkeys;      // NULL: the select workgroup computes its scores
+    int Hkv, Hl, Sq, Sk, blk, NQ, NK;
+    const int32_t* kv_len;
+    int kv_valid, causal, top_k, keep_first, keep_local;
+    uint32_t* bitmask;
+    int32_t* cols;
+    int32_t* counts;
+    float* scores;
+};
+
+struct SelForced {      // the forced blocks of a row: [0, kf) and [flo, fhi]
+    int kf, flo, fhi;
+    __device__ __forceinline__ bool operator()(int j) const { return j < kf || (j >= flo && j <= fhi); }
+};
+
+// The weight of the block with ordered key `key` in a row whose best visible score is tmax.  A NaN (non-finite scores) weighs 0.
+__device__ __forceinline__ unsigned selp_weight(unsigned key, float tmax, float c) {
+    const float a = (sel_unkey(key) - tmax) * c;
+    const float x = __builtin_amdgcn_exp2f(a) * (float)SELP_ONE + 0.5f;
+    return x >= 1.f ? (unsigned)fminf(x, (float)SELP_ONE) : 0u;
+}
+
+// Sums of a and of b over the workgroup, in every thread (red: 8 words).
+__device__ __forceinline__ uint2 selp_sum2(unsigned a, unsigned b, unsigned* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int m = 32; m >= 1; m >>= 1) {
+        a += __shfl_xor(a, m, 64);
+        b += __shfl_xor(b, m, 64);
+    }
+    __syncthreads();    // (red may still be read from the previous sum)
+    if (lane == 0) {
+        red[2 * wave] = a;
+        red[2 * wave + 1] = b;
+    }
+    __syncthreads();
+    return make_uint2(red[0] + red[2] + red[4] + red[6], red[1] + red[3] + red[5] + red[7]);
+}
+
+// The radix select over the unforced visible keys, 8 bits a pass, on weights (MASS) or on counts (every block weighs 1): the key T
+// at which the running sum over the ranking first reaches rem (0 < rem <= the sum over all of them), and what of rem is left for
+// the blocks that tie at T.
+template <bool MASS>
+__device__ __forceinline__ void sel_radix(const unsigned* keys, int nvis, SelForced forced, float tmax, float c, unsigned rem,
+                                          unsigned* hist, unsigned* wsum, unsigned* pick, unsigned& T, unsigned& left) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned prefix = 0u;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hist[tid] = 0u;
+        __syncthreads();
+        const unsigned himask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+        for (int j = tid; j < nvis; j += SEL_NT) {
+            const unsigned key = keys[j];
+            if (!forced(j) && (key & himask) == prefix) {
+                const unsigned u = MASS ? selp_weight(key, tmax, c) : 1u;
+                if (u) atomicAdd(&hist[(key >> shift) & 255u], u);
+            }
+        }
+        __syncthreads();
+        // thread t owns digit 255 - t: its inclusive prefix over t sums the keys with that digit or a higher one
+        const unsigned h = hist[255 - tid];
+        unsigned inc = h;
+        for (int m = 1; m < 64; m <<= 1) {
+            const unsigned o = __shfl_up(inc, m, 64);
+            if (lane >= m) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        for (int w = 0; w < wave; ++w) inc += wsum[w];
+        if (inc - h < rem && rem <= inc) {      // exactly one thread: the digit in which the sum reaches rem
+            pick[0] = prefix | ((unsigned)(255 - tid) << shift);
+            pick[1] = rem - (inc - h);
+        }
+        __syncthreads();
+        prefix = pick[0];
+        rem = pick[1];
+    }
+    T = prefix;
+    left = rem;
+}
+
+// One list row by one workgroup.  LOADED = 0: the scores are computed here (r.kbar, r.qsum); LOADED = 1: their keys are loaded from
+// r.wkeys (block_score_kernel).  BUDGET = false: top-k (p16, c and mass are not read); true: top-p capped at top_k.
+template <int L, int LOADED, bool BUDGET>
+__device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c, float* __restrict__ mass) {
     extern __shared__ unsigned keys[];              // [NK]: the scores of the visible blocks as ordered keys
-    __shared__ int hist[256];
-    __shared__ int wsum[4];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned wsum[4];
     __shared__ unsigned pick[2];
     __shared__ int step_eq[SEL_MAX_STEPS], step_kept[SEL_MAX_STEPS];
     __shared__ unsigned long long step_mask[SEL_MAX_STEPS];
     constexpr int D = 4 * L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int blk = r.blk, NK = r.NK, Sq = r.Sq;
     const long row = blockIdx.x;
-    const int i = (int)(row % NQ);
-    const long bh = row / NQ;
-    const int hl = (int)(bh % Hl);
-    const long b = bh / Hl;
-    const int hk = hl / (Hl / Hkv);
-    const int len = sel_key_limit(kv_len, (int)b, kv_valid, Sk);
+    const int i = (int)(row % r.NQ);
+    const long bh = row / r.NQ;
+    const int hl = (int)(bh % r.Hl);
+    const long b = bh / r.Hl;
+    const int hk = hl / (r.Hl / r.Hkv);
+    const int len = sel_key_limit(r.kv_len, (int)b, r.kv_valid, r.Sk);
 
-    // visible blocks: a prefix [0, nvis) of the row; forced blocks: [0, kf) and [flo, fhi] within it
+    // 1. visible blocks: a prefix [0, nvis) of the row; forced blocks: [0, kf) and [flo, fhi] within it
     const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
-    const int nvis = sel_visible(len, Sq, blk, NK, i, causal);
-    const int kf = min(keep_first, nvis);
-    int flo = 1, fhi = 0;
-    if (keep_local >= 1 && nvis > 0) {
+    const int nvis = sel_visible(len, Sq, blk, NK, i, r.causal);
+    SelForced forced = {min(r.keep_first, nvis), 1, 0};
+    if (r.keep_local >= 1 && nvis > 0) {
         const long jd_lo = max(r0 + off, 0L) / blk, jd_hi = min(max(r1 + off, 0L), (long)len - 1) / blk;
-        const long ext = min(keep_local - 1, SEL_MAX_NK);
-        flo = (int)max(jd_lo - ext, 0L);
-        fhi = (int)min(causal ? jd_hi : jd_hi + ext, (long)nvis - 1);
+        const long ext = min(r.keep_local - 1, SEL_MAX_NK);
+        forced.flo = (int)max(jd_lo - ext, 0L);
+        forced.fhi = (int)min(r.causal ? jd_hi : jd_hi + ext, (long)nvis - 1);
     }
-    const int nf = kf + max(0, fhi - max(flo, kf) + 1);
-    auto forced = [&](int j) { return j < kf || (j >= flo && j <= fhi); };
+    const int nf = forced.kf + max(0, forced.fhi - max(forced.flo, forced.kf) + 1);
 
-    // scores of the visible blocks
+    // 2. scores of the visible blocks
     if (LOADED) {
-        const unsigned* wr = wkeys + row * NK;
+        const unsigned* wr = r.wkeys + row * NK;
         for (int j = tid; j < nvis; j += SEL_NT) keys[j] = wr[j];
     } else {
-        sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, 0, nvis, keys);
+        sel_score_blocks<L>(r.kbar + ((b * r.Hkv + hk) * NK) * D, r.qsum + row * D, 0, nvis, keys);
     }
     __syncthreads();
-    if (scores) {
-        float* sr = scores + row * NK;
+    if (r.scores) {
+        float* sr = r.scores + row * NK;
         for (int j = tid; j < NK; j += SEL_NT) sr[j] = j < nvis ? sel_unkey(keys[j]) : -INFINITY;
     }
 
-    // the key of the need-th best unforced visible block
-    const int nunf = nvis - nf, need = max(top_k - nf, 0);
-    const bool take_all = need >= nunf;
-    const bool radix = !take_all && need > 0;
-    unsigned T = 0u;
+    // 3. the decision (uniform over the workgroup): every unforced visible block (take_all), or with `cut` those above key T and,
+    // of those that tie at T, the need_eq lowest; neither: the forced blocks alone.  n_k: what top_k leaves for unforced blocks.
+    const int nunf = nvis - nf, n_k = max(r.top_k - nf, 0);
+    bool take_all = false, cut;
+    unsigned T = 0u, left;
     int need_eq = 0;
-    if (radix) {    // (uniform over the workgroup)
-        unsigned prefix = 0u;
-        int rem = need;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            hist[tid] = 0;
-            __syncthreads();
-            const unsigned himask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
-            for (int j = tid; j < nvis; j += SEL_NT) {
-                const unsigned key = keys[j];
-                if (!forced(j) && (key & himask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            // thread t owns digit 255 - t: its inclusive prefix over t counts the keys with that digit or a higher one
-            const int h = hist[255 - tid];
-            int inc = h;
-            for (int m = 1; m < 64; m <<= 1) {
-                const int o = __shfl_up(inc, m, 64);
-                if (lane >= m) inc += o;
-            }
-            if (lane == 63) wsum[wave] = inc;
-            __syncthreads();
-            for (int w = 0; w < wave; ++w) inc += wsum[w];
-            if (inc - h < rem && rem <= inc) {      // exactly one thread: the digit that holds the rem-th best
-                pick[0] = prefix | ((unsigned)(255 - tid) << shift);
-                pick[1] = (unsigned)(rem - (inc - h));
-            }
-            __syncthreads();
-            prefix = pick[0];
-            rem = (int)pick[1];
+    if constexpr (!BUDGET) {
+        take_all = n_k >= nunf;
+        cut = !take_all && n_k > 0;
+        if (cut) {      // the key of the n_k-th best unforced visible block
+            sel_radix<false>(keys, nvis, forced, 0.f, 0.f, (unsigned)n_k, hist, wsum, pick, T, left);
+            need_eq = (int)left;
         }
-        T = prefix;
-        need_eq = rem;      // of the blocks that tie at T, the need_eq lowest are kept
+    } else {
+        // t_max over the visible blocks, on the keys; then the row's total weight and the weight of its forced blocks
+        __shared__ unsigned red[8];
+        unsigned kmax = 0u;
+        for (int j = tid; j < nvis; j += SEL_NT) kmax = max(kmax, keys[j]);
+        for (int m = 32; m >= 1; m >>= 1) kmax = max(kmax, __shfl_xor(kmax, m, 64));
+        if (lane == 0) red[wave] = kmax;
+        __syncthreads();
+        const float tmax = sel_unkey(max(max(red[0], red[1]), max(red[2], red[3])));
+        unsigned part = 0u, fpart = 0u;
+        for (int j = tid; j < nvis; j += SEL_NT) {
+            const unsigned u = selp_weight(keys[j], tmax, c);
+            part += u;
+            if (forced(j)) fpart += u;
+        }
+        const uint2 sums = selp_sum2(part, fpart, red);
+        const unsigned total = sums.x, fmass = sums.y;
+        const unsigned target = (unsigned)(((unsigned long long)total * (unsigned)p16 + 65535ull) >> 16);      // <= total
+        cut = fmass < target && n_k > 0;
+        if (cut) {      // (target <= total: the unforced blocks hold target - fmass, so the sum reaches it)
+            sel_radix<true>(keys, nvis, forced, tmax, c, target - fmass, hist, wsum, pick, T, left);
+            const unsigned uT = selp_weight(T, tmax, c);        // > 0: its digit held weight in every pass
+            need_eq = (int)((left + uT - 1u) / uT);
+            if (n_k < nunf) {       // the cap may bind: n_p = #{key > T} + need_eq against n_k
+                unsigned above = 0u;
+                for (int j = tid; j < nvis; j += SEL_NT) above += (!forced(j) && keys[j] > T) ? 1u : 0u;
+                const unsigned n_p = selp_sum2(above, 0u, red).x + (unsigned)need_eq;
+                if (n_p > (unsigned)n_k) {
+                    sel_radix<false>(keys, nvis, forced, tmax, c, (unsigned)n_k, hist, wsum, pick, T, left);
+                    need_eq = (int)left;
+                }
+            }
+        }
+        if (mass) {     // float(sum of the kept weights) / float(total); a row that sees nothing: 0
+            unsigned kpart = 0u;
+            if (cut)
+                for (int j = tid; j < nvis; j += SEL_NT) kpart += (!forced(j) && keys[j] > T) ? selp_weight(keys[j], tmax, c) : 0u;
+            const unsigned kmass = fmass + selp_sum2(kpart, 0u, red).x + (cut ? (unsigned)need_eq * selp_weight(T, tmax, c) : 0u);
+            if (tid == 0) mass[row] = total ? (float)kmass / (float)total : 0.f;
+        }
     }
 
-    // the lists, in 64-block ballot steps: wave w takes steps w, w + 4, ...
+    // 4. the lists, in 64-block ballot steps: wave w takes steps w, w + 4, ...
     const int nsteps = (NK + 63) >> 6, NW = (NK + 31) >> 5;
     const unsigned long long below = (1ull << lane) - 1ull;
     for (int s = wave; s < nsteps; s += 4) {
         const int j = s * 64 + lane;
-        const bool eq = radix && j < nvis && !forced(j) && keys[j] == T;
+        const bool eq = cut && j < nvis && !forced(j) && keys[j] == T;
         const unsigned long long m = __ballot(eq);
         if (lane == 0) step_eq[s] = __popcll(m);
     }
     __syncthreads();
     if (wave == 0) sel_wave_scan(step_eq, nsteps, lane);
     __syncthreads();
-    uint32_t* wr = bitmask + row * NW;
+    uint32_t* wr = r.bitmask + row * NW;
     for (int s = wave; s < nsteps; s += 4) {
         const int j = s * 64 + lane;
         const bool vis = j < nvis, f = vis && forced(j);
         const unsigned key = vis ? keys[j] : 0u;
-        const bool eq = radix && vis && !f && key == T;
+        const bool eq = cut && vis && !f && key == T;
         const unsigned long long me = __ballot(eq);
-        const bool kept = f || (vis && (take_all || (radix && key > T))) || (eq && step_eq[s] + __popcll(me & below) < need_eq);
+        const bool kept = f || (vis && (take_all || (cut && key > T))) || (eq && step_eq[s] + __popcll(me & below) < need_eq);
         const unsigned long long m = __ballot(kept);
         if (lane < 2 && 2 * s + lane < NW) wr[2 * s + lane] = lane ? (unsigned)(m >> 32) : (unsigned)m;
         if (lane == 0) {
@@ -331,95 +500,149 @@ __global__ __launch_bounds__(SEL_NT) void block_select_kernel(const float* __res
     __syncthreads();
     if (wave == 0) {
         const int total = sel_wave_scan(step_kept, nsteps, lane);
-        if (lane == 0) counts[row] = total;
+        if (lane == 0) r.counts[row] = total;
     }
     __syncthreads();
-    int32_t* cr = cols + row * NK;
+    int32_t* cr = r.cols + row * NK;
     for (int s = wave; s < nsteps; s += 4) {
         const unsigned long long m = step_mask[s];
         if ((m >> lane) & 1ull) cr[step_kept[s] + __popcll(m & below)] = s * 64 + lane;
     }
 }
 
+template <int L, int LOADED>
+__global__ __launch_bounds__(SEL_NT) void block_select_kernel(const sel_rows r) {
+    sel_row_body<L, LOADED, false>(r, 0, 0.f, nullptr);
+}
+
+template <int L, int LOADED>
+__global__ __launch_bounds__(SEL_NT) void block_select_p_kernel(const sel_rows r, int p16, float c, float* __restrict__ mass) {
+    sel_row_body<L, LOADED, true>(r, p16, c, mass);
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-static int sel_check_sizes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
-    if (B <= 0 || Hkv <= 0 || Hl <= 0 || NQ <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+// The budget of the top-p selection: p16 = round(top_p * 65536) in [0, 65536], c = float(score_scale * log2(e)) finite and > 0,
+// mass NULL or fp32 [B * Hl * NQ].
+struct sel_top_p {
+    int p16;
+    float c;
+    float* mass;
+};
+
+// The one place that maps the head dimension to L = D / 4 lanes per pooled row: f(std::integral_constant<int, L>).
+template <typename F>
+static void sel_with_lanes(int D, F f) {
+    switch (D) {
+        case 16: f(std::integral_constant<int, 4>()); break;
+        case 32: f(std::integral_constant<int, 8>()); break;
+        case 64: f(std::integral_constant<int, 16>()); break;
+        default: f(std::integral_constant<int, 32>()); break;
+    }
+}
+
+// The select kernel over `rows` list rows: LOADED from r.wkeys, the top-p kernel with a budget.
+static int sel_launch_select(int D, long rows, const sel_rows& r, const sel_top_p* p, hipStream_t s) {
+    const dim3 grid((unsigned)rows);
+    const size_t lds = (size_t)r.NK * sizeof(unsigned);
+    sel_with_lanes(D, [&](auto lanes) {
+        constexpr int L = decltype(lanes)::value;
+        if (p && r.wkeys) block_select_p_kernel<L, 1><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass);
+        else if (p) block_select_p_kernel<L, 0><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass);
+        else if (r.wkeys) block_select_kernel<L, 1><<<grid, SEL_NT, lds, s>>>(r);
+        else block_select_kernel<L, 0><<<grid, SEL_NT, lds, s>>>(r);
+    });
+    return rsa_launch_status();
+}
+
+// The pool kernel over the query jobs of r's rows and k_jobs key jobs behind them (none: k and kbar are not touched).
+static int sel_launch_pool(int dtype, int H, int D, rsa_tensor4 q, rsa_tensor4 k, long q_jobs, long k_jobs, const sel_rows& r,
+                           float* kbar, float* qsum, hipStream_t s) {
+    auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag> : block_select_pool_kernel<fp16_tag>;
+    kernel<<<dim3((unsigned)(q_jobs + k_jobs)), SEL_NT, 0, s>>>(q, k, H, r.Hkv, r.Hl, r.Sq, r.Sk, D, r.blk, r.NQ, r.NK, q_jobs, r.kv_len,
+                                                                r.kv_valid, kbar, qsum);
+    return rsa_launch_status();
+}
+
+// The workspace of the plain selection (the pooled queries and keys) or of the pooled one (the pooled queries, the ordered keys).
+static int sel_sizes(bool pooled, int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
+    if (!bytes || B <= 0 || Hkv <= 0 || Hl <= 0 || NQ <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
     if (NK > SEL_MAX_NK) return RSA_ERR_UNSUPPORTED;     // K5's key-block limit
-    const size_t q_jobs = (size_t)B * Hl * NQ, k_jobs = (size_t)B * Hkv * NK;
-    if (q_jobs + k_jobs > 0x7FFFFFFFull) return RSA_ERR_UNSUPPORTED;     // one workgroup each
-    if (bytes) *bytes = (q_jobs + k_jobs) * (size_t)D * sizeof(float);
+    const size_t q_jobs = (size_t)B * Hl * NQ, k_jobs = (size_t)B * Hkv * NK;     // one workgroup per job; pooled: per row and split
+    if ((pooled ? q_jobs * SEL_MAX_SPLITS : q_jobs + k_jobs) > 0x7FFFFFFFull) return RSA_ERR_UNSUPPORTED;
+    *bytes = pooled ? q_jobs * ((size_t)D * sizeof(float) + (size_t)NK * sizeof(unsigned)) : (q_jobs + k_jobs) * (size_t)D * sizeof(float);
     return RSA_OK;
 }
 
+// What rsa_block_select[_p] and rsa_block_select_pooled[_p] check alike, in the order that decides the status of a call that is
+// wrong in two ways (the caller's own checks before it and behind it all return RSA_ERR_BAD_ARG).  cap: the keys the K side can
+// hold, Sk or NK * block.
+static int sel_check(bool pooled, int B, int H, int D, int dtype, rsa_tensor4 q, const sel_rows& r, long cap, size_t* need) {
+    if (B <= 0 || H <= 0 || r.Hkv <= 0 || r.Hl <= 0 || r.Sq <= 0) return RSA_ERR_BAD_ARG;
+    if (H % r.Hkv || (r.Hl != r.Hkv && r.Hl != H)) return RSA_ERR_BAD_ARG;
+    if (r.blk != 64 && r.blk != 128) return RSA_ERR_UNSUPPORTED;
+    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (r.NQ != (int)(((long)r.Sq + r.blk - 1) / r.blk) || r.NK != (int)((cap + r.blk - 1) / r.blk)) return RSA_ERR_BAD_ARG;
+    const int st = sel_sizes(pooled, B, r.Hkv, r.Hl, D, r.NQ, r.NK, need);
+    if (st != RSA_OK) return st;
+    if (r.top_k < 0 || r.keep_first < 0 || r.keep_local < 0) return RSA_ERR_BAD_ARG;
+    if (!r.kv_len && (r.kv_valid < 0 || r.kv_valid > cap)) return RSA_ERR_BAD_ARG;
+    if (!r.bitmask || !r.cols || !r.counts) return RSA_ERR_BAD_ARG;
+    if (rsa_check_tensor(q) != RSA_OK || q.stride_b < 0 || q.stride_h < 0 || q.stride_s < 0) return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(r.bitmask) | reinterpret_cast<uintptr_t>(r.cols) | reinterpret_cast<uintptr_t>(r.counts) |
+         reinterpret_cast<uintptr_t>(r.scores) | reinterpret_cast<uintptr_t>(r.kv_len)) & 3)
+        return RSA_ERR_BAD_ARG;
+    return RSA_OK;
+}
+
+static bool selp_budget_ok(const sel_top_p& p) {
+    return p.p16 >= 0 && p.p16 <= 65536 && isfinite(p.c) && p.c > 0.f && !(reinterpret_cast<uintptr_t>(p.mass) & 3);
+}
+
+// The body of rsa_block_select and rsa_block_select_p (top_p NULL: top-k).  r: the call's arguments; kbar, qsum are set here.
+static int sel_run(int B, int H, int D, int dtype, rsa_tensor4 q, rsa_tensor4 k, void* ws, size_t ws_bytes, sel_rows r,
+                   const sel_top_p* top_p, void* stream) {
+    if ((top_p && !selp_budget_ok(*top_p)) || r.Sk <= 0) return RSA_ERR_BAD_ARG;
+    size_t need = 0;
+    const int st = sel_check(false, B, H, D, dtype, q, r, r.Sk, &need);
+    if (st != RSA_OK) return st;
+    if (!ws || rsa_check_tensor(k) != RSA_OK || k.stride_b < 0 || k.stride_h < 0 || k.stride_s < 0) return RSA_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return RSA_ERR_BAD_ARG;
+    if (ws_bytes < need) return RSA_ERR_WORKSPACE;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long q_jobs = (long)B * r.Hl * r.NQ, k_jobs = (long)B * r.Hkv * r.NK;
+    float* qsum = static_cast<float*>(ws);              // [B, Hl, NQ, D]
+    float* kbar = qsum + q_jobs * D;                    // [B, Hkv, NK, D]
+    r.kbar = kbar, r.qsum = qsum;
+    const int rc = sel_launch_pool(dtype, H, D, q, k, q_jobs, k_jobs, r, kbar, qsum, s);
+    return rc != RSA_OK ? rc : sel_launch_select(D, q_jobs, r, top_p, s);
+}
+
 extern "C" int rsa_block_select_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
-    if (!bytes) return RSA_ERR_BAD_ARG;
-    return sel_check_sizes(B, Hkv, Hl, D, NQ, NK, bytes);
+    return sel_sizes(false, B, Hkv, Hl, D, NQ, NK, bytes);
+}
+
+extern "C" int rsa_block_select_p_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
+    return sel_sizes(false, B, Hkv, Hl, D, NQ, NK, bytes);
 }
 
 extern "C" int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK,
                                 rsa_tensor4 q, rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k,
                                 int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
                                 int32_t* counts, float* scores, void* stream) {
-    return sel_run(B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NQ, NK, q, k, kv_len_dev, kv_valid, causal, top_k, keep_first, keep_local,
-                   ws, ws_bytes, bitmask, cols, counts, scores, nullptr, stream);
+    return sel_run(B, H, D, dtype, q, k, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid,
+                   causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, nullptr, stream);
 }
 
-int sel_run(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q, rsa_tensor4 k,
-            const int32_t* kv_len_dev, int kv_valid, int causal, int top_k, int keep_first, int keep_local, void* ws,
-            size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, const sel_top_p* top_p,
-            void* stream) {
-    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || Sk <= 0) return RSA_ERR_BAD_ARG;
-    if (H % Hkv || (Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
-    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
-    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
-    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
-    if (NQ != (int)(((long)Sq + block - 1) / block) || NK != (int)(((long)Sk + block - 1) / block)) return RSA_ERR_BAD_ARG;
-    size_t need = 0;
-    const int st = sel_check_sizes(B, Hkv, Hl, D, NQ, NK, &need);
-    if (st != RSA_OK) return st;
-    if (top_k < 0 || keep_first < 0 || keep_local < 0) return RSA_ERR_BAD_ARG;
-    if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
-    if (!ws || !bitmask || !cols || !counts) return RSA_ERR_BAD_ARG;
-    if (rsa_check_tensor(q) != RSA_OK || rsa_check_tensor(k) != RSA_OK) return RSA_ERR_BAD_ARG;
-    if (q.stride_b < 0 || q.stride_h < 0 || q.stride_s < 0 || k.stride_b < 0 || k.stride_h < 0 || k.stride_s < 0)
-        return RSA_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(bitmask) | reinterpret_cast<uintptr_t>(cols) | reinterpret_cast<uintptr_t>(counts) |
-         reinterpret_cast<uintptr_t>(scores) | reinterpret_cast<uintptr_t>(kv_len_dev)) & 3)
-        return RSA_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(ws) & 15) return RSA_ERR_BAD_ARG;
-    if (ws_bytes < need) return RSA_ERR_WORKSPACE;
-
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long q_jobs = (long)B * Hl * NQ, k_jobs = (long)B * Hkv * NK;
-    float* qsum = static_cast<float*>(ws);              // [B, Hl, NQ, D]
-    float* kbar = qsum + q_jobs * D;                    // [B, Hkv, NK, D]
-    const dim3 pool_grid((unsigned)(q_jobs + k_jobs));
-    if (dtype == RSA_BF16)
-        block_select_pool_kernel<bf16_tag><<<pool_grid, SEL_NT, 0, s>>>(q, k, H, Hkv, Hl, Sq, Sk, D, block, NQ, NK, q_jobs,
-                                                                        kv_len_dev, kv_valid, kbar, qsum);
-    else
-        block_select_pool_kernel<fp16_tag><<<pool_grid, SEL_NT, 0, s>>>(q, k, H, Hkv, Hl, Sq, Sk, D, block, NQ, NK, q_jobs,
-                                                                        kv_len_dev, kv_valid, kbar, qsum);
-    int rc = rsa_launch_status();
-    if (rc != RSA_OK) return rc;
-    if (top_p)
-        return sel_launch_top_p(D, q_jobs, {kbar, qsum, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid, causal != 0,
-                                            top_k, keep_first, keep_local, bitmask, cols, counts, scores}, *top_p, s);
-    const dim3 grid((unsigned)q_jobs);
-    const size_t lds = (size_t)NK * sizeof(unsigned);
-#define SEL_LAUNCH(LANES)                                                                                                       \
-    block_select_kernel<LANES, 0><<<grid, SEL_NT, lds, s>>>(kbar, qsum, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev,    \
-                                                            kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask,     \
-                                                            cols, counts, scores)
-    switch (D) {
-        case 16: SEL_LAUNCH(4); break;
-        case 32: SEL_LAUNCH(8); break;
-        case 64: SEL_LAUNCH(16); break;
-        default: SEL_LAUNCH(32); break;
-    }
-#undef SEL_LAUNCH
-    return rsa_launch_status();
+extern "C" int rsa_block_select_p(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK,
+                                  rsa_tensor4 q, rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k,
+                                  int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                                  int32_t* counts, float* scores, int p16, float c, float* mass, void* stream) {
+    const sel_top_p p = {p16, c, mass};
+    return sel_run(B, H, D, dtype, q, k, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid,
+                   causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, &p, stream);
 }
 
 // ---- the pooled-key cache ----------------------------------------------------------------------------------
@@ -459,15 +682,9 @@ static int sel_pool_keys_run(bool kv8, int B, int Hkv, int Sk, int D, int dtype,
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((size_t)B * Hkv * W));
-    if (kv8)
-        pool_keys_kernel<e4m3_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start,
-                                                           block_table, (long)table_stride_b, num_pages, out, k_scale);
-    else if (dtype == RSA_BF16)
-        pool_keys_kernel<bf16_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start,
-                                                           block_table, (long)table_stride_b, num_pages, out, nullptr);
-    else
-        pool_keys_kernel<fp16_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start,
-                                                           block_table, (long)table_stride_b, num_pages, out, nullptr);
+    auto* kernel = kv8 ? pool_keys_kernel<e4m3_tag> : dtype == RSA_BF16 ? pool_keys_kernel<bf16_tag> : pool_keys_kernel<fp16_tag>;
+    kernel<<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start, block_table,
+                                   (long)table_stride_b, num_pages, out, k_scale);     // (k_scale: NULL unless kv8)
     return rsa_launch_status();
 }
 
@@ -488,16 +705,6 @@ extern "C" int rsa_pool_keys_kv8(int B, int Hkv, int Sk, int D, int block, int N
                              start_dev, start, workgroups_per_head, out, k_scale, stream);
 }
 
-static int sel_pooled_check_sizes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
-    if (B <= 0 || Hkv <= 0 || Hl <= 0 || NQ <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
-    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
-    if (NK > SEL_MAX_NK) return RSA_ERR_UNSUPPORTED;
-    const size_t q_jobs = (size_t)B * Hl * NQ;
-    if (q_jobs * SEL_MAX_SPLITS > 0x7FFFFFFFull) return RSA_ERR_UNSUPPORTED;    // one workgroup per row and split
-    if (bytes) *bytes = q_jobs * ((size_t)D * sizeof(float) + (size_t)NK * sizeof(unsigned));   // the pooled queries, the keys
-    return RSA_OK;
-}
-
 // The library's choice of score_splits, a function of the shapes alone (measured: profiles/pooled_select_perf.txt).
 // One pass of sel_score_blocks' loop per score workgroup (4096 / D key blocks: 32 at D = 128), which is the best or within the
 // baseline's spread of the best at both measured row counts (8 rows x 1024 blocks: 32 splits; 64 rows x 256 blocks: 8); at most 64
@@ -509,87 +716,62 @@ static int sel_default_splits(size_t rows, int NK, int D) {
     return max(1, min(min(by_blocks, by_rows), 64));
 }
 
+// The body of rsa_block_select_pooled and rsa_block_select_pooled_p (top_p NULL: top-k).  r: the call's arguments; Sk, kbar, qsum
+// and wkeys are set here.
+static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const float* pooled_k, int score_splits, void* ws,
+                          size_t ws_bytes, sel_rows r, const sel_top_p* top_p, void* stream) {
+    if ((top_p && !selp_budget_ok(*top_p)) || r.NK <= 0) return RSA_ERR_BAD_ARG;
+    size_t need = 0;
+    const int st = sel_check(true, B, H, D, dtype, q, r, (long)r.NK * r.blk, &need);
+    if (st != RSA_OK) return st;
+    if (score_splits < 0 || score_splits > SEL_MAX_SPLITS || !ws || !pooled_k) return RSA_ERR_BAD_ARG;
+    if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(pooled_k)) & 15) return RSA_ERR_BAD_ARG;
+    if (ws_bytes < need) return RSA_ERR_WORKSPACE;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long q_jobs = (long)B * r.Hl * r.NQ;
+    const int splits = min(score_splits ? score_splits : sel_default_splits((size_t)q_jobs, r.NK, D), r.NK);
+    float* qsum = static_cast<float*>(ws);                              // [B, Hl, NQ, D]
+    unsigned* wkeys = reinterpret_cast<unsigned*>(qsum + q_jobs * D);   // [B, Hl, NQ, NK]
+    r.Sk = r.NK * r.blk;        // the capacity of the cache
+    r.kbar = pooled_k, r.qsum = qsum, r.wkeys = splits > 1 ? wkeys : nullptr;
+    int rc = sel_launch_pool(dtype, H, D, q, q, q_jobs, 0, r, nullptr, qsum, s);    // the pooled queries
+    if (rc != RSA_OK) return rc;
+    if (splits > 1) {
+        sel_with_lanes(D, [&](auto lanes) {
+            block_score_kernel<decltype(lanes)::value><<<dim3((unsigned)(q_jobs * splits)), SEL_NT, 0, s>>>(
+                pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits, r.kv_len, r.kv_valid, r.causal, wkeys);
+        });
+        rc = rsa_launch_status();
+        if (rc != RSA_OK) return rc;
+    }
+    return sel_launch_select(D, q_jobs, r, top_p, s);
+}
+
 extern "C" int rsa_block_select_pooled_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
-    if (!bytes) return RSA_ERR_BAD_ARG;
-    return sel_pooled_check_sizes(B, Hkv, Hl, D, NQ, NK, bytes);
+    return sel_sizes(true, B, Hkv, Hl, D, NQ, NK, bytes);
+}
+
+extern "C" int rsa_block_select_pooled_p_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
+    return sel_sizes(true, B, Hkv, Hl, D, NQ, NK, bytes);
 }
 
 extern "C" int rsa_block_select_pooled(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK,
                                        rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal,
                                        int top_k, int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes,
                                        uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, void* stream) {
-    return sel_pooled_run(B, H, Hkv, Hl, Sq, D, dtype, block, NQ, NK, q, pooled_k, kv_len_dev, kv_valid, causal, top_k, keep_first,
-                          keep_local, score_splits, ws, ws_bytes, bitmask, cols, counts, scores, nullptr, stream);
+    return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, 0, block, NQ,
+                          NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, nullptr,
+                          stream);
 }
 
-int sel_pooled_run(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q,
-                   const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k, int keep_first,
-                   int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
-                   int32_t* counts, float* scores, const sel_top_p* top_p, void* stream) {
-    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
-    if (H % Hkv || (Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
-    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
-    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
-    if (D != 16 && D != 32 && D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
-    if (NQ != (int)(((long)Sq + block - 1) / block)) return RSA_ERR_BAD_ARG;
-    size_t need = 0;
-    const int st = sel_pooled_check_sizes(B, Hkv, Hl, D, NQ, NK, &need);
-    if (st != RSA_OK) return st;
-    const int Sk = NK * block;      // the capacity of the cache
-    if (top_k < 0 || keep_first < 0 || keep_local < 0) return RSA_ERR_BAD_ARG;
-    if (score_splits < 0 || score_splits > SEL_MAX_SPLITS) return RSA_ERR_BAD_ARG;
-    if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
-    if (!ws || !pooled_k || !bitmask || !cols || !counts) return RSA_ERR_BAD_ARG;
-    if (rsa_check_tensor(q) != RSA_OK) return RSA_ERR_BAD_ARG;
-    if (q.stride_b < 0 || q.stride_h < 0 || q.stride_s < 0) return RSA_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(bitmask) | reinterpret_cast<uintptr_t>(cols) | reinterpret_cast<uintptr_t>(counts) |
-         reinterpret_cast<uintptr_t>(scores) | reinterpret_cast<uintptr_t>(kv_len_dev)) & 3)
-        return RSA_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(pooled_k)) & 15) return RSA_ERR_BAD_ARG;
-    if (ws_bytes < need) return RSA_ERR_WORKSPACE;
-
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long q_jobs = (long)B * Hl * NQ;
-    const int splits = min(score_splits ? score_splits : sel_default_splits((size_t)q_jobs, NK, D), NK);
-    float* qsum = static_cast<float*>(ws);                              // [B, Hl, NQ, D]
-    unsigned* wkeys = reinterpret_cast<unsigned*>(qsum + q_jobs * D);   // [B, Hl, NQ, NK]
-    // the pooled queries: the query jobs of the pool kernel alone (no key job in the grid: k and kbar are not touched)
-    if (dtype == RSA_BF16)
-        block_select_pool_kernel<bf16_tag><<<dim3((unsigned)q_jobs), SEL_NT, 0, s>>>(q, q, H, Hkv, Hl, Sq, Sk, D, block, NQ, NK, q_jobs,
-                                                                                     kv_len_dev, kv_valid, nullptr, qsum);
-    else
-        block_select_pool_kernel<fp16_tag><<<dim3((unsigned)q_jobs), SEL_NT, 0, s>>>(q, q, H, Hkv, Hl, Sq, Sk, D, block, NQ, NK, q_jobs,
-                                                                                     kv_len_dev, kv_valid, nullptr, qsum);
-    int rc = rsa_launch_status();
-    if (rc != RSA_OK) return rc;
-    const dim3 grid((unsigned)q_jobs), sgrid((unsigned)(q_jobs * splits));
-    const size_t lds = (size_t)NK * sizeof(unsigned);
-#define SEL_LAUNCH(LANES)                                                                                                       \
-    if (splits > 1) {                                                                                                           \
-        block_score_kernel<LANES><<<sgrid, SEL_NT, 0, s>>>(pooled_k, qsum, Hkv, Hl, Sq, Sk, block, NQ, NK, splits, kv_len_dev,  \
-                                                           kv_valid, causal != 0, wkeys);                                       \
-        rc = rsa_launch_status();                                                                                               \
-        if (rc != RSA_OK) return rc;                                                                                            \
-    }                                                                                                                           \
-    if (top_p)                                                                                                                  \
-        return sel_launch_top_p(D, q_jobs, {pooled_k, qsum, splits > 1 ? wkeys : nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK,       \
-                                            kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols,    \
-                                            counts, scores}, *top_p, s);                                                        \
-    if (splits > 1) {                                                                                                           \
-        block_select_kernel<LANES, 1><<<grid, SEL_NT, lds, s>>>(pooled_k, qsum, wkeys, Hkv, Hl, Sq, Sk, block, NQ, NK,          \
-                                                                kv_len_dev, kv_valid, causal != 0, top_k, keep_first,           \
-                                                                keep_local, bitmask, cols, counts, scores);                     \
-    } else {                                                                                                                    \
-        block_select_kernel<LANES, 0><<<grid, SEL_NT, lds, s>>>(pooled_k, qsum, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK,        \
-                                                                kv_len_dev, kv_valid, causal != 0, top_k, keep_first,           \
-                                                                keep_local, bitmask, cols, counts, scores);                     \
-    }
-    switch (D) {
-        case 16: SEL_LAUNCH(4); break;
-        case 32: SEL_LAUNCH(8); break;
-        case 64: SEL_LAUNCH(16); break;
-        default: SEL_LAUNCH(32); break;
-    }
-#undef SEL_LAUNCH
-    return rsa_launch_status();
+extern "C" int rsa_block_select_pooled_p(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK,
+                                         rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid,
+                                         int causal, int top_k, int keep_first, int keep_local, int score_splits, void* ws,
+                                         size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores,
+                                         int p16, float c, float* mass, void* stream) {
+    const sel_top_p p = {p16, c, mass};
+    return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, 0, block, NQ,
+                          NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, &p,
+                          stream);
 }

@@ -197,3 +197,35 @@ def exact_cases():
 
 def exact_top_k(tk, NK):
     return {"NK": NK, "NK+5": NK + 5}.get(tk, tk)
+
+
+# ---- where the two budgets coincide: top_p = 1 over rows without a zero weight ---------------------------------------------------------
+def plateau_inputs(B, H, Hkv, Sq, Sk, D, blk, mask_heads, seed):
+    """exact_inputs with the plateau profile for every (b, hk) and without the doubled odd query blocks: t[b, hl, i, j] =
+    level[b, hk, j] in [-12, 0], so at c == 1 every visible block weighs at least 2^6 and top_p = 1 keeps what top-k keeps."""
+    NK = -(-Sk // blk)
+    Hl = Hkv if mask_heads == "kv" else H
+    q = np.zeros((B, H, Sq, D))
+    q[..., 0] = 1.0 / (H // Hl)
+    k = np.zeros((B, Hkv, Sk, D))
+    for b in range(B):
+        for hk in range(Hkv):
+            k[b, hk, :, 0] = np.repeat(levels("plateau", NK, seed + 7 * (b * Hkv + hk)), blk)[:Sk]
+    return q, k
+
+
+PLATEAU_BUDGETS = [(1, 0, 0), (5, 0, 0), (8, 1, 1), (12, 2, 2), ("NK+5", 0, 1), (0, 1, 0)]      # (top_k, keep_first, keep_local)
+
+
+def plateau_cases():
+    """The grid of 72 shapes (B = 2, H = 4, D = 16), each for the six PLATEAU_BUDGETS."""
+    out = []
+    for blk in (64, 128):
+        for NK in (3, 70, 300):
+            Sk = (NK - 1) * blk + blk // 2 + 3
+            for Hkv, heads in ((4, "kv"), (2, "q"), (1, "kv")):
+                for causal in (False, True):
+                    for Sq in (1, blk):
+                        out.append(dict(B=2, H=4, D=16, blk=blk, NK=NK, Sk=Sk, lens=[Sk, max(Sk - 2 * blk - 17, 5)], Hkv=Hkv,
+                                        heads=heads, causal=causal, Sq=Sq, seed=300 + NK))
+    return out

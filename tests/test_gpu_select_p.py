@@ -9,7 +9,8 @@ tests/select_p_ref.py.
     rounding class   random normal inputs over ragged counts: set relations exactly, the ranking within section 5.11's score
                      tolerance, the kept fraction within an epsilon derived below (_epsilon) from the fixed point and that
                      tolerance.
-    byte for byte    the pooled call against the plain one, lists against mask, call against call, a device kv_len, one graph.
+    byte for byte    the pooled call against the plain one, lists against mask, call against call, a device kv_len, one graph;
+                     top_p = 1 over rows without a zero weight against top-k, whose contract it then is.
     end to end       the top-p lists drive block_sparse_decode (paged, log-sum-exp), the mask block_sparse_attention(causal).
 """
 import numpy as np
@@ -220,6 +221,45 @@ def test_selection_from_the_cache_equals_select_blocks(dt, D, blk, NK, Sq, Hkv, 
         assert m1.dtype == torch.bool and torch.equal(m1, m2)
         kept += int(want[0]["counts"].sum())
     assert kept > 0
+
+
+# (blk, NK, (Hkv, mask_heads), causal, Sq in blocks, dtype) out of select_p_ref.plateau_cases: every value of every axis
+COINCIDE = [(64, 3, (4, "kv"), False, 0, "bf16"), (128, 70, (2, "q"), True, 1, "fp16"), (64, 300, (1, "kv"), True, 0, "fp16"),
+            (128, 3, (2, "q"), False, 1, "bf16"), (64, 70, (1, "kv"), False, 1, "bf16"), (128, 300, (4, "kv"), True, 0, "fp16")]
+
+
+@pytest.mark.parametrize("blk,NK,form,causal,sq_blocks,dt", COINCIDE,
+                         ids=[f"b{a}-NK{b}-kv{c[0]}-{c[1]}-{'causal' if d else 'full'}-Sq{e}-{f}" for a, b, c, d, e, f in COINCIDE])
+def test_top_p_one_over_nonzero_weights_equals_top_k_byte_for_byte(blk, NK, form, causal, sq_blocks, dt):
+    """Both select kernels on inputs where their contracts coincide (tests/test_select_p_cpu.py: top_p = 1, every visible weight
+    >= 1): mask, bitmask, counts, live cols and scores are the same bytes, from q and k and from the cache, scored in the select
+    workgroup (score_splits = 1) and loaded from the score pass (4)."""
+    from rectified_spaattn_amd import pool_keys, select_blocks, select_blocks_pooled
+    (Hkv, heads), Sq = form, sq_blocks * blk or 1
+    c = next(c for c in pref.plateau_cases() if (c["blk"], c["NK"], c["Hkv"], c["heads"], c["causal"], c["Sq"]) ==
+             (blk, NK, Hkv, heads, causal, Sq))
+    q64, k64 = pref.plateau_inputs(c["B"], c["H"], Hkv, Sq, c["Sk"], c["D"], blk, heads, c["seed"])
+    q, k = (torch.from_numpy(a).to(DEV, DT[dt]) for a in (q64, k64))
+    assert np.array_equal(q.double().cpu().numpy(), q64) and np.array_equal(k.double().cpu().numpy(), k64)
+    cache = pool_keys(k, block_size=blk, kv_len=c["lens"])
+    calls = [lambda *a, **kw: select_blocks(q, k, *a, **kw)] + [
+        lambda *a, s=s, **kw: select_blocks_pooled(q, cache, *a, score_splits=s, **kw) for s in (1, 4)]
+    kept = dropped = 0
+    for tk, kf, kl in pref.PLATEAU_BUDGETS:
+        top_k = pref.exact_top_k(tk, NK)
+        kw = dict(block_size=blk, kv_len=c["lens"], causal=causal, keep_first=kf, keep_local=kl, mask_heads=heads, return_scores=True)
+        for n, call in enumerate(calls):
+            what = (tk, kf, kl, n)
+            by_k, by_p = call(top_k, as_lists=True, **kw), call(top_k, as_lists=True, top_p=1.0, score_scale=pref.SCALE_EXACT, **kw)
+            _same_lists(by_p[0], by_k[0], what)
+            _same_scores(by_p[1], by_k[1], what)
+            m_k, m_p = call(top_k, **kw), call(top_k, top_p=1.0, score_scale=pref.SCALE_EXACT, **kw)
+            assert m_k[0].dtype == torch.bool and torch.equal(_bits(m_p[0]), _bits(m_k[0])), what
+            _same_scores(m_p[1], m_k[1], what)
+            assert int(m_k[0].sum()) == int(by_k[0]["counts"].sum()), what
+            kept += int(m_k[0].sum())
+            dropped += int((~m_k[0] & torch.isfinite(m_k[1])).sum())
+    assert kept > 0 and dropped > 0
 
 
 def test_selection_from_the_cache_at_the_key_block_limit():

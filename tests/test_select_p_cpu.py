@@ -107,6 +107,34 @@ def test_the_exact_class_holds_every_case_the_contract_names():
     assert all(n > 0 for n in seen.values()), seen
 
 
+def test_top_p_one_over_nonzero_weights_is_top_k():
+    """Where every visible block has weight >= 1, top_p = 1 keeps the forced blocks and the best min(n_k, nunf) unforced ones, ties
+    to the lower index: select_ref's mask.  On the reference alone; tests/test_gpu_select_p.py holds the kernels to it."""
+    inputs = {}
+    cases = ties = everything = 0
+    for c in pref.plateau_cases():
+        key = (c["blk"], c["NK"], c["Hkv"], c["heads"], c["Sq"])
+        if key not in inputs:
+            q, k = pref.plateau_inputs(c["B"], c["H"], c["Hkv"], c["Sq"], c["Sk"], c["D"], c["blk"], c["heads"], c["seed"])
+            inputs[key] = (q, k, ref.scores(q, k, c["lens"], c["blk"], c["heads"]))
+        q, k, t = inputs[key]
+        for tk, kf, kl in pref.PLATEAU_BUDGETS:
+            top_k = pref.exact_top_k(tk, c["NK"])
+            kw = dict(blk=c["blk"], lens=c["lens"], causal=c["causal"], keep_first=kf, keep_local=kl, mask_heads=c["heads"])
+            by_k = ref.select(q, k, top_k, **kw)
+            by_p = pref.select(q, k, top_k, 1.0, score_scale=pref.SCALE_EXACT, t=t, **kw)
+            what = (c, tk, kf, kl)
+            assert np.array_equal(by_k["mask"], by_p["mask"]), what
+            vis, frc = (np.broadcast_to(a[:, None], by_p["mask"].shape) for a in (by_p["vis"], by_p["frc"]))
+            assert (by_p["u"][vis] >= 1).all(), what
+            kept, cand = by_k["mask"], vis & ~frc
+            low = np.where(kept & cand, by_k["t"], np.inf).min(-1, keepdims=True)    # the lowest kept unforced score of a row
+            ties += int((cand & ~kept & (by_k["t"] == low)).any())
+            everything += int(vis.any() and np.array_equal(kept, vis))
+            cases += 1
+    assert cases == 432 and ties > 0 and everything > 0, (cases, ties, everything)
+
+
 # ---- 2. the Python refusals --------------------------------------------------------------------------------------------------------
 def _q(Sq=3):
     return torch.zeros(2, 8, Sq, 64, dtype=torch.bfloat16)
