@@ -458,6 +458,43 @@ int rsa_block_select_pooled_p(int B, int H, int Hkv, int Hl, int Sq, int D, int 
                               int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask,
                               int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass, void* stream);
 
+/* ---- block-sparse EXTEND attention: a chunk of any number of query rows over a (paged, e4m3) K/V cache that already holds a
+ * prefix (found by symbol: the header version stays 6.1).  rsa_block_sparse_extend and
+ * rsa_block_sparse_extend_kv8 are rsa_block_sparse_decode and rsa_block_sparse_decode_kv8 -- their argument lists, operand
+ * strides and alignment, len_b, the cache and table rules, the numerics, the outputs and the refusals -- with the one-query-block
+ * limit and the 64-row limit lifted:
+ *   shape     q [B, H, Sq, D] with any Sq >= 1; NQ = ceil(Sq / block) is derived, not passed.  Query block i is rows
+ *             [i block, min((i + 1) block, Sq)) of q.  cols [B * Hl, NQ, NK] / counts [B * Hl, NQ] as rsa_block_mask_to_lists,
+ *             rsa_block_select and rsa_block_select_pooled write them: the list row of (b, list head hl, query block i) is
+ *             (b * Hl + hl) * NQ + i.  lse NULL or fp32 [B, H, Sq].
+ *   visible   row r of (b, h) sees key j iff block j / block is in list row (b, list head of h, r / block), j < len_b,
+ *             j < NK * block, and with causal j <= r + len_b - Sq (bottom-right aligned, r counted in the whole call).  A row
+ *             without a visible key -- every row with r + len_b - Sq < 0 among them -- is 0 and its log-sum-exp -inf.
+ *   groups    the H / max(Hl, Hkv) heads x rows-of-block-i rectangle of a unit's query block is cut into row groups of gh heads x
+ *             qg query rows: gh = ceil(gu / ceil(gu / 64)), qg = min(64 / gh, Sq, block) (gu = H / max(Hl, Hkv): any gu is served).
+ *             One workgroup per (row group, split); a chunk of 32 keys that starts at or beyond the causal limit of the group's
+ *             last row is skipped before its loads.  On shapes rsa_block_sparse_decode serves, at an equal explicit
+ *             blocks_per_split, the bytes are that call's.
+ *   splits    C = blocks_per_split; 0 = the library's choice, a function of the shapes alone: min(8, NK) while the launch has
+ *             fewer than 256 row groups, NK (one split) from there on.  ws: rsa_block_sparse_extend_bytes(...) bytes, 16-byte
+ *             aligned = groups * ceil(NK / C) * rows16 * (D + 2) * 4, groups = B * max(Hl, Hkv) * ceil(gu / gh) * (the number of
+ *             qg-row pieces of the NQ query blocks), rows16 = gh * qg rounded up to 16, 32 or 64.
+ * RSA_ERR_UNSUPPORTED beyond the grid: more than 2^31 - 1 row groups, or B * H * Sq * D / 1024 > 2^31 - 1 (the merge's grid);
+ * block outside {64, 128} and D outside {64, 128} likewise.  Every other refusal is the decode entries', Sq > block and the row
+ * limit apart.  Every check runs before the first HIP call.  Two launches. */
+int rsa_block_sparse_extend_bytes(int B, int H, int Hkv, int Hl, int Sq, int D, int block, int NK, int blocks_per_split,
+                                  size_t* bytes);
+int rsa_block_sparse_extend(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                            const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
+                            rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* cols,
+                            const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
+                            void* stream);
+int rsa_block_sparse_extend_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
+                                rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                                const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes,
+                                rsa_out4 out, float* lse, const float* k_scale, const float* v_scale, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

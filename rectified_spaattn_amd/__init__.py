@@ -10,7 +10,8 @@ Module names mirror the reference package `rectified_spaattn`:
     rectified_cogvideo_attn   rectified_block_sparse_attention, RectifiedCogVideoXVideoSpaAttnProcessor2_0
     attn_processor            get_attn_processors, set_attn_processor
     block_sparse              block_sparse_attention over a caller's block mask, block_sparse_decode (its decode half: few query rows over a
-                              (paged) K/V cache, with log-sum-exp; 2-byte or e4m3 with append_kv_e4m3 as its writer) and select_blocks, the top-k block selection
+                              (paged) K/V cache, with log-sum-exp; 2-byte or e4m3 with append_kv_e4m3 as its writer), block_sparse_extend (the same
+                              over a chunk of any number of query rows: chunked prefill, a second turn, a draft's verification) and select_blocks, the top-k block selection
                               per K/V head that makes one (both also exported here), the mask <-> list conversions; the four rectified_*_attn modules above also carry the reference's
                               _build_block_index_with_importance_optimized and _triton_block_sparse_attention_onehot
     teacache                  TeaCache step-skipping controller (scripts' teacache_forward bookkeeping), rel_l1_distance
@@ -73,6 +74,18 @@ def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, bloc
     head): the one-byte cache append_kv_e4m3 writes.  See rectified_spaattn_amd.block_sparse.block_sparse_decode."""
     from . import block_sparse
     return block_sparse.block_sparse_decode(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
+                                            causal=causal, block_table=block_table, return_lse=return_lse,
+                                            blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale)
+
+
+def block_sparse_extend(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
+                        return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None):
+    """Block-sparse extend attention: a chunk q [B,H,Sq,D] of any length over a K/V cache that already holds a prefix --
+    block_sparse_decode without the one-query-block and 64-row limits; block_mask bool / uint8 [B|1, Hl, ceil(Sq/block), NK] or
+    select_blocks' lists for that many query blocks; causal is bottom-right aligned; return_lse=True adds the fp32 log-sum-exp
+    [B,H,Sq].  See rectified_spaattn_amd.block_sparse.block_sparse_extend."""
+    from . import block_sparse
+    return block_sparse.block_sparse_extend(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                             causal=causal, block_table=block_table, return_lse=return_lse,
                                             blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale)
 

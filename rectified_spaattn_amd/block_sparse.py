@@ -803,18 +803,92 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     dequantised 2-byte cache.  Every rule above holds unchanged; K views need strides and a pointer that are multiples of 8 bytes, V
     views of 16 (others are refused, never copied).  The scales' values are not checked: a zero, negative or non-finite one garbles
     its head's rows only."""
-    blk = _check_block("block-sparse decode", block_size)
+    return _sparse_rows(False, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
+                        k_scale, v_scale)
+
+
+EXTEND_FILL_GROUPS = 256    # row groups from which block_sparse_extend's default is one split (rsa_decode.hip: EXT_FILL_GROUPS)
+
+
+def extend_row_groups(B: int, H: int, Hkv: int, Hl: int, Sq: int, block_size: int) -> Dict[str, int]:
+    """How block_sparse_extend cuts a call into row groups (DESIGN.md section 5.16), from the shapes alone: gu = H // max(Hl, Hkv)
+    heads share a K/V head and a list row; a group is gh = ceil(gu / ceil(gu / 64)) of them x qg = min(64 // gh, Sq, block_size)
+    consecutive query rows of one query block.  -> dict(gh, qg, head_chunks, query_chunks, groups, rows16): groups = B *
+    max(Hl, Hkv) * head_chunks * query_chunks workgroups per split, rows16 = gh * qg rounded up to 16, 32 or 64."""
+    U = max(Hl, Hkv)
+    gu = H // U
+    HC = -(-gu // DECODE_MAX_ROWS)
+    gh = -(-gu // HC)
+    qmax = min(Sq, block_size)
+    qg = min(DECODE_MAX_ROWS // gh, qmax)
+    NQ = -(-Sq // block_size)
+    QC = (NQ - 1) * (-(-qmax // qg)) + -(-(Sq - (NQ - 1) * block_size) // qg)
+    rows = gh * qg
+    return dict(gh=gh, qg=qg, head_chunks=HC, query_chunks=QC, groups=B * U * HC * QC,
+                rows16=16 if rows <= 16 else (32 if rows <= 32 else 64))
+
+
+def extend_default_split(groups: int, NK: int) -> int:
+    """block_sparse_extend's blocks_per_split=None: min(8, NK) while the launch has fewer than 256 row groups (one per CU), NK --
+    one split -- from there on."""
+    return min(8, NK) if groups < EXTEND_FILL_GROUPS else NK
+
+
+def block_sparse_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask, *, kv_len=None,
+                        sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, block_table=None,
+                        return_lse: bool = False, blocks_per_split: Optional[int] = None, k_scale=None, v_scale=None):
+    """Block-sparse attention of a chunk of new tokens over a K/V cache that already holds a prefix ("extend": chunked prefill, a
+    second turn on a cached conversation, a prefix-cache hit, verification of a speculative draft): block_sparse_decode with the
+    one-query-block limit and the 64-row limit lifted.  Everything not said here is block_sparse_decode's
+    as documented: operand strides and alignment, every kv_len form (a device kv_len is clamped on the device and never read on
+    the host), NaN beyond kv_len, out-of-range table or list entries as cleared bits, the paged pools, the e4m3 cache with k_scale /
+    v_scale, bf16 / fp16, head dim 64 / 128, block_size 64 / 128, the same bytes from two calls, asynchronous on the current
+    stream and capturable in a HIP graph.
+    q [B,H,Sq,D] with any Sq >= 1; NQ = ceil(Sq / block_size); query block i is rows [i * block, min((i + 1) * block, Sq)) of q,
+    counted from q's row 0 (as block_sparse_attention and select_blocks count them).
+    block_mask: bool / uint8 [B|1, Hl, NQ, NK], Hl in {1, Hkv, H}, or the dict select_blocks(_pooled)(..., as_lists=True) returns
+    for NQ query blocks: cols int32 [B * Hl, NQ, NK] and counts int32 [B * Hl, NQ], contiguous, used as they are (no conversion
+    launch).
+    Row r of (b, h) sees key j iff mask[b, hl(h), r // block, j // block] and j < kv_len[b] and j < NK * block and, with
+    causal=True, j <= r + kv_len[b] - Sq: block_sparse_attention(causal=True)'s rule, bottom-right aligned, at both block sizes.  A
+    row without a visible key -- every row with r + kv_len[b] - Sq < 0 among them -- is 0 and its log-sum-exp -inf.
+    Any H // max(Hl, Hkv) is served, more than 64 query heads in a unit included.  The kernels are the decode kernels' body: a
+    unit's query block is cut into row groups of at most 64 rows (extend_row_groups), one workgroup per (row group, split); on
+    shapes block_sparse_decode serves, at an equal explicit blocks_per_split, the bytes are that call's.
+    return_lse=True: (out, lse), lse fp32 [B,H,Sq].
+    blocks_per_split: None = min(8, NK) while the launch has fewer than 256 row groups, NK (one split) from there on: a function of
+    the shapes alone (extend_default_split).  The workspace, taken from torch, is groups * ceil(NK / blocks_per_split) * rows16 *
+    (D + 2) * 4 bytes.
+    Grid limits, refused before the first HIP call: at most 2^31 - 1 row groups, and B * H * Sq * D / 1024 <= 2^31 - 1.
+    When to use it (measured, profiles/extend_perf.txt; H = 32 over 8 K/V heads, D = 128, paged bf16 / e4m3 caches): against
+    gathering the cache through the table (and dequantising it) for block_sparse_attention, this call is faster at every measured
+    shape up to Sq = 512 and at Sq = 2048 over a 131 072-key cache; over 8 x 32 768 keys the crossover lies near Sq = 512 at top_k
+    64 and near 1 300 at top_k 16 -- beyond it gather once and call block_sparse_attention.  Against block_sparse_attention on a
+    cache that is already contiguous and 2-byte it is faster up to Sq = 128 and slower from 512 rows on (every 64-row group
+    re-reads its kept blocks)."""
+    return _sparse_rows(True, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
+                        k_scale, v_scale)
+
+
+def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
+                 k_scale, v_scale):
+    """block_sparse_decode (ext False) and block_sparse_extend: one argument layer, the C entries of either."""
+    blk = _check_block("block-sparse extend" if ext else "block-sparse decode", block_size)
     _check_count("blocks_per_split", blocks_per_split, 1, optional=True)
     B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v, dims=(64, 128), block_table=block_table, blk=blk, kv8_ok=True)
     _check_scales(k, Hkv, k_scale=k_scale, v_scale=v_scale)
-    if Sq > blk:
+    NQ = -(-Sq // blk) if ext else 1
+    if Sq > blk and not ext:
         raise ValueError(f"Sq = {Sq}: block_sparse_decode serves one query block, Sq <= block_size = {blk}")
     NKmax = min(-(-Sk // blk), MAX_KEY_BLOCKS)
     if isinstance(block_mask, dict):
         cols, counts = block_mask.get("cols"), block_mask.get("counts")
         if (not isinstance(cols, torch.Tensor) or not isinstance(counts, torch.Tensor) or cols.dtype != torch.int32
-                or counts.dtype != torch.int32 or cols.dim() != 3 or cols.shape[1] != 1 or cols.shape[0] % B
-                or counts.numel() != cols.shape[0] or not cols.is_contiguous() or not counts.is_contiguous()):
+                or counts.dtype != torch.int32 or cols.dim() != 3 or cols.shape[1] != NQ or cols.shape[0] % B
+                or counts.numel() != cols.shape[0] * NQ or not cols.is_contiguous() or not counts.is_contiguous()):
+            if ext:
+                raise ValueError(f"block_mask: a bool / uint8 tensor, or the lists of {NQ} query block(s) of {blk}: cols int32 "
+                                 f"[B * Hl, {NQ}, NK] and counts int32 [B * Hl, {NQ}], contiguous (select_blocks(..., as_lists=True))")
             raise ValueError("block_mask: a bool / uint8 tensor, or the lists of one query block: cols int32 [B * Hl, 1, NK] and "
                              "counts int32 [B * Hl, 1], contiguous (select_blocks(..., as_lists=True))")
         Hl, NK = cols.shape[0] // B, cols.shape[2]
@@ -825,14 +899,15 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
             raise ValueError(f"block_mask: a 4-d bool or uint8 tensor, got {getattr(mask, 'dtype', type(mask))} "
                              f"{tuple(getattr(mask, 'shape', ()))}")
         Hl, NK = mask.shape[1], mask.shape[3]
-        if mask.shape[0] not in (1, B) or mask.shape[2] != 1:
-            raise ValueError(f"block_mask {tuple(mask.shape)}: expected [{B}|1, Hl, 1, 1..{NKmax}] for block {blk} (one query block)")
+        if mask.shape[0] not in (1, B) or mask.shape[2] != NQ:
+            raise ValueError(f"block_mask {tuple(mask.shape)}: expected [{B}|1, Hl, {NQ}, 1..{NKmax}] for block {blk} "
+                             + (f"(Sq = {Sq}: {NQ} query block(s))" if ext else "(one query block)"))
     if Hl not in (1, Hkv, H):
         raise ValueError(f"block_mask: a head axis of {H} (per query head), Hkv = {Hkv} (per K/V head) or 1, got {Hl}")
     if not 1 <= NK <= NKmax:
         raise ValueError(f"block_mask: {NK} key blocks, expected 1..{NKmax} for block {blk} (at most {MAX_KEY_BLOCKS} key blocks)")
     rows = Sq * (H // max(Hl, Hkv))
-    if rows > DECODE_MAX_ROWS:
+    if rows > DECODE_MAX_ROWS and not ext:
         raise NotImplementedError(f"Sq * H // max(Hl, Hkv) = {rows} rows share a K/V head and a list row: block_sparse_decode "
                                   f"serves at most {DECODE_MAX_ROWS}; use block_sparse_attention")
     lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
@@ -851,12 +926,17 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     q = _core._as_bhsd(q)
     bps = 0 if blocks_per_split is None else int(blocks_per_split)
     need = ctypes.c_size_t(0)
-    _lib.check(L.rsa_block_sparse_decode_bytes(B, H, Hkv, Hl, Sq, D, NK, bps, ctypes.byref(need)), "rsa_block_sparse_decode_bytes")
+    if ext:
+        _lib.check(L.rsa_block_sparse_extend_bytes(B, H, Hkv, Hl, Sq, D, blk, NK, bps, ctypes.byref(need)),
+                   "rsa_block_sparse_extend_bytes")
+    else:
+        _lib.check(L.rsa_block_sparse_decode_bytes(B, H, Hkv, Hl, Sq, D, NK, bps, ctypes.byref(need)),
+                   "rsa_block_sparse_decode_bytes")
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
     out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
     kv8 = k.dtype == E4M3
-    entry = "rsa_block_sparse_decode_kv8" if kv8 else "rsa_block_sparse_decode"
+    entry = ("rsa_block_sparse_extend" if ext else "rsa_block_sparse_decode") + ("_kv8" if kv8 else "")
     held = [_scale_arg(sc, Hkv, dev) for sc in (k_scale, v_scale)] if kv8 else []
     with torch.cuda.device(dev):
         _lib.check(getattr(L, entry)(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,

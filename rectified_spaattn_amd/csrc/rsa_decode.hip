@@ -27,6 +27,13 @@
 // where it loads 16 (same keys, same d range) and half as many 16-byte pieces of V, and the codes become the query's 2-byte type in
 // registers (the packed scaled conversions with a unit scale: exact, every finite e4m3 value is a bf16 and an fp16).  The K scale multiplies the fp32
 // score behind the MFMA chain, the V scale the merged row once; the V image, the MFMAs, the softmax and the meet are the code below.
+//
+// Extend (rsa_block_sparse_extend, rsa_block_sparse_extend_kv8) is the same two kernels instantiated with
+// EXT: any number of query rows and query blocks, any number of heads in a unit.  A workgroup then serves a ROW GROUP (DecGroups: at
+// most 64 rows of one batch item, unit and query block) where the decode kernel serves a whole unit: the list row is the query
+// block's, a row's causal limit comes from its index in the whole call, a chunk that starts at or beyond the limit of the group's
+// last row is skipped before its loads (byte-neutral), and partials and the merge are indexed by (row group, split).  The decode
+// instantiations keep their arguments' layout and their code: the group arithmetic lives behind `if constexpr (EXT)`.
 #include "rsa_attn.h"
 
 #include <math.h>
@@ -37,6 +44,14 @@
 #define DEC_CHUNK 32            // keys per wave step
 #define DEC_SPLIT 8             // default list entries per split: within a fifth of the best split size at every measured shape
                                 // (profiles/decode_perf.txt), and the partials it costs stay below a tenth of the K/V it reads
+
+// The extend kernels' row groups.  The gu x rows_i rectangle of (unit, query block i) is cut into groups of
+// gh heads x qg query rows (gh * qg <= 64; row = head_in_group * qg + query row in group): HC head chunks, cpb query chunks per
+// full query block, QC query chunks per unit over all NQ query blocks (only the last block is ragged, so chunk qc belongs to
+// block qc / cpb).  Group index = ((b * U + unit) * QC + qc) * HC + hc.  Decode is the case NQ = QC = HC = 1, gh = gu, qg = Sq.
+struct DecGroups {
+    int NQ, QC, cpb, HC, gh, qg;
+};
 
 struct DecArgs {
     const unsigned short *q, *k, *v;
@@ -57,6 +72,15 @@ struct DecArgs {
 struct DecArgs8 : DecArgs {
     const float *k_scale, *v_scale;     // [Hkv]: the value of a code is float(code) * scale[hk]
 };
+
+// The extend kernels' arguments: the decode kernels' (whose layout stays as it is) and the row groups behind them.
+template <typename A>
+struct DecExt : A {
+    DecGroups g;
+    int qblk;                   // rows of a query block (the merge's base struct holds no block size)
+};
+template <typename A, bool EXT>
+using DecArgsFor = typename std::conditional<EXT, DecExt<A>, A>::type;
 
 // The cache's element: the query's own 2-byte type (Tag = bf16_tag / fp16_tag), or e4m3 codes (kv8_tag<query type>).
 template <typename QTag>
@@ -129,8 +153,9 @@ __device__ __forceinline__ s16x4 dec_tr_read(const unsigned char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
-template <typename CTag, int D, int MT>
-__global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(typename DecCache<CTag>::Args a) {
+template <typename CTag, int D, int MT, bool EXT>
+__global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
+    DecArgsFor<typename DecCache<CTag>::Args, EXT> a) {
     using Cache = DecCache<CTag>;
     using Tag = typename Cache::Q;      // the type of q, of the MFMA operands and of the output
     using KT = typename Cache::elem;
@@ -153,17 +178,39 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(t
     float (*const red)[16 * D] = reinterpret_cast<float (*)[16 * D]>(lds);
     float2 (*const ml)[16 * MT] = reinterpret_cast<float2 (*)[16 * MT]>(lds + VIMG + QIMG);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lh = lane >> 4;
-    const int unit = blockIdx.x % a.U, b = blockIdx.x / a.U, split = blockIdx.y;
+    // the workgroup's rows: heads [h0, h0 + hn) of the unit x query rows [q0, q0 + qn) of the call, row = head * qw + query row
+    // in the group; list row (b * Hl + hl) * NQ + qb.  Decode: the whole unit (the arithmetic below, spelled as it always was).
+    int ext_unit = 0, ext_b = 0, qb = 0, h0 = 0, hn = 0, q0 = 0, qn = 0, qw = 1, nq = 1;
+    if constexpr (EXT) {
+        int g = blockIdx.x;
+        const int hc = g % a.g.HC;
+        g /= a.g.HC;
+        const int qc = g % a.g.QC;
+        g /= a.g.QC;
+        ext_unit = g % a.U;
+        ext_b = g / a.U;
+        qb = qc / a.g.cpb;
+        qw = a.g.qg;
+        nq = a.g.NQ;
+        q0 = qb * a.blk + (qc - qb * a.g.cpb) * qw;
+        qn = min(qw, min((qb + 1) * a.blk, a.Sq) - q0);
+        h0 = hc * a.g.gh;
+        hn = min(a.g.gh, a.H / a.U - h0);
+    }
+    const int unit = EXT ? ext_unit : blockIdx.x % a.U, b = EXT ? ext_b : blockIdx.x / a.U, split = blockIdx.y;
     const int gu = a.H / a.U, R = a.Sq * gu;
     const int hk = unit / (a.U / a.Hkv), hl = unit / (a.U / a.Hl);
     const int kvlen = a.kv_len ? min(max(a.kv_len[b], 0), a.Sk) : a.kv_valid;
-    const long lrow = (long)b * a.Hl + hl;
+    // no row of the group sees a key at or beyond glim (causal: the limit of the group's last query row): chunks from there on
+    // are skipped before their loads.  Decode's last row is the call's last: its glim is kvlen.
+    const int glim = EXT && a.causal ? min(kvlen, max(0, q0 + qn + kvlen - a.Sq)) : kvlen;
+    const long lrow = EXT ? ((long)b * a.Hl + hl) * nq + qb : (long)b * a.Hl + hl;
     const long part = ((long)blockIdx.x * a.nsplit + split) * a.R16;
     const int count = min(max(a.counts[lrow], 0), a.NK);
     const int first = split * a.C;
     const int n_items = max(0, min(a.C, count - first));
     if (n_items == 0) return;               // (uniform) past the list's end: the merge stops at the list's count
-    if (kvlen == 0) {                       // (uniform) no key at all: m = -inf, l = 0; the merge never reads its O
+    if (glim == 0) {                        // (uniform) no key at all: m = -inf, l = 0; the merge never reads its O
         if (tid < 16 * MT) a.ws_ml[part + tid] = make_float2(-INFINITY, 0.f);
         return;
     }
@@ -176,8 +223,14 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(t
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int rr = 16 * mt + lr;
-        const bool ok = rr < R;
-        const int hu = ok ? rr / a.Sq : 0, qrow = ok ? rr - hu * a.Sq : 0;
+        bool ok = rr < R;
+        int hu = ok ? rr / a.Sq : 0, qrow = ok ? rr - hu * a.Sq : 0;      // (qrow: the row's index in the whole call)
+        if constexpr (EXT) {
+            const int hr = rr / qw, qr = rr - hr * qw;
+            ok = hr < hn && qr < qn;
+            hu = ok ? h0 + hr : 0;
+            qrow = ok ? q0 + qr : 0;
+        }
         const unsigned short* qp = a.q + (long)b * a.qsb + (long)(unit * gu + hu) * a.qsh + (long)qrow * a.qss + 8 * lh;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -213,7 +266,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(t
         int jv = -1, pv = -1;
         if (e0 + lane < n_items) {
             const int j = list[e0 + lane];
-            if (j >= 0 && j < a.NK && (long)j * a.blk < kvlen) {
+            if (j >= 0 && j < a.NK && (long)j * a.blk < glim) {
                 jv = j;
                 pv = j;
                 if (a.table) {
@@ -237,7 +290,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(t
             const int j = __shfl(jv, entry, 64), pg = __shfl(pv, entry, 64);
             const int key0 = j * a.blk + sub * DEC_CHUNK;
             r.key0 = -1;
-            if (j < 0 || key0 >= kvlen) return;         // (uniform)
+            if (j < 0 || key0 >= glim) return;          // (uniform)
             r.key0 = key0;
             // rows at or beyond the limit are read as the last row below it: in bounds, masked (K) or zeroed (V) later
             const long roff = a.table ? -(long)j * a.blk : 0;     // paged: rows count from the page's first
@@ -403,9 +456,9 @@ struct DecMergeArgs8 : DecMergeArgs {
 };
 
 // D / 4 threads per output row, four channels each; the splits in ascending order.
-template <typename CTag, int D>
+template <typename CTag, int D, bool EXT>
 __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
-    typename std::conditional<DecCache<CTag>::kv8, DecMergeArgs8, DecMergeArgs>::type a) {
+    DecArgsFor<typename std::conditional<DecCache<CTag>::kv8, DecMergeArgs8, DecMergeArgs>::type, EXT> a) {
     using Tag = typename DecCache<CTag>::Q;
     constexpr int TPR = D / 4;
     const long g = (long)blockIdx.x * DEC_NT + threadIdx.x;
@@ -415,8 +468,15 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
     const int qrow = (int)(row % a.Sq), h = (int)((row / a.Sq) % a.H);
     const long b = row / ((long)a.Sq * a.H);
     const int gu = a.H / a.U, unit = h / gu, rr = (h % gu) * a.Sq + qrow;
-    const long p0 = ((b * a.U + unit) * a.nsplit) * a.R16 + rr;
-    const int count = min(max(a.counts[b * a.Hl + unit / (a.U / a.Hl)], 0), a.NK);
+    long p0 = ((b * a.U + unit) * a.nsplit) * a.R16 + rr;       // decode: the unit's partials, head-major rows
+    long lrow = b * a.Hl + unit / (a.U / a.Hl);
+    if constexpr (EXT) {        // the row's group and its place in it (DecGroups)
+        const int hu = h % gu, hc = hu / a.g.gh, qb = qrow / a.qblk, qi = qrow - qb * a.qblk, qcl = qi / a.g.qg;
+        const long grp = ((b * a.U + unit) * a.g.QC + qb * a.g.cpb + qcl) * a.g.HC + hc;
+        p0 = (grp * a.nsplit) * a.R16 + (hu - hc * a.g.gh) * a.g.qg + (qi - qcl * a.g.qg);
+        lrow = lrow * a.g.NQ + qb;
+    }
+    const int count = min(max(a.counts[lrow], 0), a.NK);
     const int nlive = min(a.nsplit, (count + a.C - 1) / a.C);
     float vs = 1.f;
     if constexpr (DecCache<CTag>::kv8) vs = a.v_scale[h / (a.H / a.Hkv)];      // (asked for before the partials: not behind them)
@@ -455,7 +515,11 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
 struct DecPlan {
     int U, MT, C, nsplit;
     size_t bytes;
+    long groups;                // workgroups per split: units (decode) or row groups (extend)
+    DecGroups g;
 };
+
+#define EXT_FILL_GROUPS 256     // row groups from which a launch fills the chip (256 CUs) without splitting its lists
 
 // Shapes only: units, rows per unit, split size (0 = the library's choice) and the workspace.
 static int dec_plan(int B, int H, int Hkv, int Hl, int Sq, int D, int NK, int blocks_per_split, DecPlan* p) {
@@ -476,6 +540,42 @@ static int dec_plan(int B, int H, int Hkv, int Hl, int Sq, int D, int NK, int bl
     }
     p->nsplit = (NK + p->C - 1) / p->C;
     p->bytes = (size_t)units * p->nsplit * (16 * p->MT) * ((size_t)D + 2) * sizeof(float);
+    p->groups = units;
+    p->g = DecGroups{1, 1, 1, 1, H / p->U, Sq};
+    return RSA_OK;
+}
+
+// The extend call's plan, from the shapes alone: the row groups (DecGroups), the rows of a group, the split size and the workspace.
+static int ext_plan(int B, int H, int Hkv, int Hl, int Sq, int D, int block, int NK, int blocks_per_split, DecPlan* p) {
+    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+    if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
+    if (NK > DEC_MAX_NK || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
+    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
+    p->U = Hl > Hkv ? Hl : Hkv;
+    const int gu = H / p->U;
+    DecGroups& g = p->g;
+    g.HC = (gu + DEC_MAX_ROWS - 1) / DEC_MAX_ROWS;
+    g.gh = (gu + g.HC - 1) / g.HC;                  // the unit's heads in HC even chunks of at most 64
+    const int qmax = Sq < block ? Sq : block;       // query rows of a full query block
+    g.qg = DEC_MAX_ROWS / g.gh < qmax ? DEC_MAX_ROWS / g.gh : qmax;
+    g.NQ = (int)(((long)Sq + block - 1) / block);
+    g.cpb = (qmax + g.qg - 1) / g.qg;
+    const long qc = (long)(g.NQ - 1) * g.cpb + (Sq - (g.NQ - 1) * block + g.qg - 1) / g.qg;
+    const int rows = g.gh * g.qg;
+    p->MT = rows <= 16 ? 1 : (rows <= 32 ? 2 : 4);
+    // grid limits: the row groups are the grid's x extent, the merge runs one thread per four output channels
+    if (qc > 0x7FFFFFFFl / g.HC || (long)B * p->U > 0x7FFFFFFFl / (qc * g.HC)) return RSA_ERR_UNSUPPORTED;
+    if ((long)B * H > (0x7FFFFFFFl * (long)DEC_NT) / ((long)Sq * (D / 4))) return RSA_ERR_UNSUPPORTED;
+    g.QC = (int)qc;
+    p->groups = (long)B * p->U * qc * g.HC;
+    if (blocks_per_split > 0) {
+        p->C = blocks_per_split < NK ? blocks_per_split : NK;
+    } else {
+        p->C = p->groups < EXT_FILL_GROUPS ? (DEC_SPLIT < NK ? DEC_SPLIT : NK) : NK;
+    }
+    p->nsplit = (NK + p->C - 1) / p->C;
+    p->bytes = (size_t)p->groups * p->nsplit * (16 * p->MT) * ((size_t)D + 2) * sizeof(float);
     return RSA_OK;
 }
 
@@ -488,13 +588,36 @@ extern "C" int rsa_block_sparse_decode_bytes(int B, int H, int Hkv, int Hl, int 
     return st;
 }
 
-template <typename Tag, int D, typename A, typename G>
-static void dec_launch(const A& a, const G& g, int MT, dim3 grid, hipStream_t s) {
-    if (MT == 1) decode_split_kernel<Tag, D, 1><<<grid, DEC_NT, 0, s>>>(a);
-    else if (MT == 2) decode_split_kernel<Tag, D, 2><<<grid, DEC_NT, 0, s>>>(a);
-    else decode_split_kernel<Tag, D, 4><<<grid, DEC_NT, 0, s>>>(a);
+extern "C" int rsa_block_sparse_extend_bytes(int B, int H, int Hkv, int Hl, int Sq, int D, int block, int NK,
+                                             int blocks_per_split, size_t* bytes) {
+    if (!bytes) return RSA_ERR_BAD_ARG;
+    DecPlan p;
+    const int st = ext_plan(B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p);
+    if (st == RSA_OK) *bytes = p.bytes;
+    return st;
+}
+
+template <typename Tag, int D, bool EXT, typename A0, typename G0>
+static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, int MT, dim3 grid, hipStream_t s) {
+    DecArgsFor<A0, EXT> a;
+    DecArgsFor<G0, EXT> g;
+    static_cast<A0&>(a) = a0;
+    static_cast<G0&>(g) = g0;
+    if constexpr (EXT) {
+        a.g = g.g = gr;
+        a.qblk = g.qblk = a0.blk;
+    }
+    if (MT == 1) decode_split_kernel<Tag, D, 1, EXT><<<grid, DEC_NT, 0, s>>>(a);
+    else if (MT == 2) decode_split_kernel<Tag, D, 2, EXT><<<grid, DEC_NT, 0, s>>>(a);
+    else decode_split_kernel<Tag, D, 4, EXT><<<grid, DEC_NT, 0, s>>>(a);
     const long threads = g.rows * (D / 4);
-    decode_merge_kernel<Tag, D><<<dim3((unsigned)((threads + DEC_NT - 1) / DEC_NT)), DEC_NT, 0, s>>>(g);
+    decode_merge_kernel<Tag, D, EXT><<<dim3((unsigned)((threads + DEC_NT - 1) / DEC_NT)), DEC_NT, 0, s>>>(g);
+}
+
+template <typename Tag, int D, typename A, typename G>
+static void dec_launch(bool ext, const A& a, const G& g, const DecGroups& gr, int MT, dim3 grid, hipStream_t s) {
+    if (ext) dec_launch2<Tag, D, true>(a, g, gr, MT, grid, s);
+    else dec_launch2<Tag, D, false>(a, g, gr, MT, grid, s);
 }
 
 // An e4m3 cache view as the loads need it: K is read 8 bytes a lane, V 16 (strides in elements = bytes).
@@ -504,8 +627,8 @@ static int dec_check_cache8(const rsa_tensor4& t, int align) {
     return RSA_OK;
 }
 
-// Both entries: kv8 = the cache holds e4m3 codes and the two scale arrays are there.
-static int dec_run(bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+// All four entries: kv8 = the cache holds e4m3 codes and the two scale arrays are there; ext = the extend call (any Sq, row groups).
+static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
                    const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
                    rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* cols,
                    const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
@@ -517,10 +640,11 @@ static int dec_run(bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int 
     if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
     const long nkmax = ((long)Sk + block - 1) / block;
     if (NK > (nkmax < DEC_MAX_NK ? nkmax : DEC_MAX_NK)) return RSA_ERR_BAD_ARG;
-    if (Sq > block || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
+    if ((!ext && Sq > block) || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
     if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
     DecPlan p;
-    const int st = dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
+    const int st = ext ? ext_plan(B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p)
+                       : dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
     if (st != RSA_OK) return st;
     if (!cols || !counts || !ws || !out.ptr) return RSA_ERR_BAD_ARG;
     if (rsa_check_tensor(q) != RSA_OK) return RSA_ERR_BAD_ARG;
@@ -544,7 +668,7 @@ static int dec_run(bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int 
     if (ws_bytes < p.bytes) return RSA_ERR_WORKSPACE;
 
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long parts = (long)B * p.U * p.nsplit;
+    const long parts = p.groups * p.nsplit;
     DecArgs8 a;
     a.q = static_cast<const unsigned short*>(q.ptr);
     a.k = static_cast<const unsigned short*>(k.ptr);
@@ -578,23 +702,23 @@ static int dec_run(bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int 
     g.Hl = Hl; g.NK = NK; g.C = p.C;
     g.H = H; g.U = p.U; g.Sq = Sq; g.nsplit = p.nsplit; g.R16 = a.R16;
     g.rows = (long)B * H * Sq;
-    const dim3 grid((unsigned)((long)B * p.U), (unsigned)p.nsplit);
+    const dim3 grid((unsigned)p.groups, (unsigned)p.nsplit);
     const DecArgs& a2 = a;              // the 2-byte kernels take the base structs
     const DecMergeArgs& g2 = g;
     if (kv8) {
         if (dtype == RSA_BF16) {
-            if (D == 128) dec_launch<kv8_tag<bf16_tag>, 128>(a, g, p.MT, grid, s);
-            else dec_launch<kv8_tag<bf16_tag>, 64>(a, g, p.MT, grid, s);
+            if (D == 128) dec_launch<kv8_tag<bf16_tag>, 128>(ext, a, g, p.g, p.MT, grid, s);
+            else dec_launch<kv8_tag<bf16_tag>, 64>(ext, a, g, p.g, p.MT, grid, s);
         } else {
-            if (D == 128) dec_launch<kv8_tag<fp16_tag>, 128>(a, g, p.MT, grid, s);
-            else dec_launch<kv8_tag<fp16_tag>, 64>(a, g, p.MT, grid, s);
+            if (D == 128) dec_launch<kv8_tag<fp16_tag>, 128>(ext, a, g, p.g, p.MT, grid, s);
+            else dec_launch<kv8_tag<fp16_tag>, 64>(ext, a, g, p.g, p.MT, grid, s);
         }
     } else if (dtype == RSA_BF16) {
-        if (D == 128) dec_launch<bf16_tag, 128>(a2, g2, p.MT, grid, s);
-        else dec_launch<bf16_tag, 64>(a2, g2, p.MT, grid, s);
+        if (D == 128) dec_launch<bf16_tag, 128>(ext, a2, g2, p.g, p.MT, grid, s);
+        else dec_launch<bf16_tag, 64>(ext, a2, g2, p.g, p.MT, grid, s);
     } else {
-        if (D == 128) dec_launch<fp16_tag, 128>(a2, g2, p.MT, grid, s);
-        else dec_launch<fp16_tag, 64>(a2, g2, p.MT, grid, s);
+        if (D == 128) dec_launch<fp16_tag, 128>(ext, a2, g2, p.g, p.MT, grid, s);
+        else dec_launch<fp16_tag, 64>(ext, a2, g2, p.g, p.MT, grid, s);
     }
     return rsa_launch_status();
 }
@@ -604,7 +728,7 @@ extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, in
                                        rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
                                        int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
                                        size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
-    return dec_run(false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
+    return dec_run(false, false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
                    table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr, stream);
 }
 
@@ -615,6 +739,29 @@ extern "C" int rsa_block_sparse_decode_kv8(int B, int H, int Hkv, int Hl, int Sq
                                            int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split,
                                            void* ws, size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale,
                                            const float* v_scale, void* stream) {
-    return dec_run(true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
+    return dec_run(false, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
                    table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale, stream);
+}
+
+// ---- extend: any number of query rows.  The decode entries' argument lists; NQ = ceil(Sq / block) and cols /
+// counts hold NQ list rows per (b, list head).
+extern "C" int rsa_block_sparse_extend(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                       const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                       rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                       int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
+                                       size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
+    return dec_run(true, false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
+                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr,
+                   stream);
+}
+
+extern "C" int rsa_block_sparse_extend_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                           const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                           rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                           int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split,
+                                           void* ws, size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale,
+                                           const float* v_scale, void* stream) {
+    return dec_run(true, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
+                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale,
+                   stream);
 }

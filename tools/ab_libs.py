@@ -9,6 +9,11 @@ Each library gets the same q, k, v and the same statistics / kept lists (compute
 members never moved, the split-KV partial buffer `tpart` is the last member of the later ones.  Prints every round's time
 per library, medians, minima and the max |difference| of the outputs against the first library.  --pmc: two launches per
 library and nothing else (for rocprofv3 --pmc passes; kernels of different builds differ by template arguments).
+
+    python tools/ab_libs.py --decode name=path [--rounds 5] [--reps 8] [--out FILE]
+
+times rsa_block_sparse_decode of the in-tree library against the build at path instead: the six shapes of tools/perf_decode.py at
+the default split, interleaved (tools/perf_extend.py --ab-decode).
 """
 import ctypes
 import os
@@ -41,6 +46,11 @@ def load(path, nbuf):
 
 
 def main():
+    if "--decode" in sys.argv:      # rsa_block_sparse_decode of this tree against ONE other build: tools/perf_extend.py has the rows
+        import perf_extend
+        rest = [a for a in sys.argv[1:] if a != "--decode"]
+        other = next(a for a in rest if "=" in a and not a.startswith("--"))
+        return perf_extend.main(["--ab-decode", other] + [a for a in rest if a != other])
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     rounds = 12
     if "--rounds" in sys.argv:
