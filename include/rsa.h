@@ -495,6 +495,48 @@ int rsa_block_sparse_extend_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, i
                                 const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes,
                                 rsa_out4 out, float* lse, const float* k_scale, const float* v_scale, void* stream);
 
+/* ---- RAGGED chunks: a row count per batch item for the extend call and for the selection (found by symbol: the header version
+ * stays 6.1).  q [B, H, Sq, D] holds a padded batch -- prefill chunks, second turns, decode items and draft
+ * verifications side by side -- and q_len_dev, DEVICE int32 [B], in front of the stream, the rows of each item: n_b = q_len_dev[b]
+ * clamped into [0, Sq] on the device, never read on the host.  q_len_dev NULL: n_b = Sq, the call and the bytes of the entry
+ * without it.  len_b (kv_len_dev / kv_valid) is the length AFTER the append: it includes item b's n_b new tokens.
+ *   extend    rsa_block_sparse_extend_ragged[_kv8] are rsa_block_sparse_extend[_kv8] -- argument lists, lists, workspace
+ *             (rsa_block_sparse_extend_bytes, a function of the padded shapes alone), grid, row groups, splits and refusals --
+ *             with n_b where Sq counts rows.  Row r < n_b of (b, h) sees key j iff block j / block is in list row (b, list head of
+ *             h, r / block), j < len_b, j < NK * block, and with causal j <= r + len_b - n_b: the extend call on rows [0, n_b) of
+ *             item b with len_b, and at an equal explicit blocks_per_split its bytes.  Rows r >= n_b are written: 0, log-sum-exp
+ *             -inf.  q's rows at or beyond n_b are never loaded and may hold anything, NaN included.  A row group whose first row
+ *             is at or beyond n_b leaves before it reads a list entry, a table entry or a K/V byte, and the merge writes its rows
+ *             without reading a partial; list rows of query blocks i >= ceil(n_b / block) are never read.
+ *   select    rsa_block_select_ragged and rsa_block_select_pooled_ragged are rsa_block_select_p and rsa_block_select_pooled_p
+ *             (workspaces: their _bytes entries) with q_len_dev in front of the stream; p16 = -1 is the plain top-k of
+ *             rsa_block_select / rsa_block_select_pooled (c and mass are then not read).  The selection contract with n_b for
+ *             Sq: qbar[b, h, i] is the mean over the rows < n_b of block i, off_b = len_b - n_b, r1 = min((i + 1) block, n_b) - 1.
+ *             A query block i >= ceil(n_b / block) has no row: counts 0, bitmask words 0, scores -inf, mass 0, cols unspecified
+ *             (as beyond counts).  Both entries give the same bytes on shared inputs.
+ * A q_len_dev that is not 4-byte aligned: RSA_ERR_BAD_ARG; every other refusal is the counterpart's.  Every check runs before the
+ * first HIP call.  The same number of launches as the counterparts; capturable, and a replay follows q_len_dev's values. */
+int rsa_block_sparse_extend_ragged(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                   const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                   rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                                   const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes,
+                                   rsa_out4 out, float* lse, const int32_t* q_len_dev, void* stream);
+int rsa_block_sparse_extend_ragged_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                       const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                       rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                       int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
+                                       size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale, const float* v_scale,
+                                       const int32_t* q_len_dev, void* stream);
+int rsa_block_select_ragged(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK,
+                            rsa_tensor4 q, rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k,
+                            int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                            int32_t* counts, float* scores, int p16, float c, float* mass, const int32_t* q_len_dev, void* stream);
+int rsa_block_select_pooled_ragged(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK,
+                                   rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal,
+                                   int top_k, int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes,
+                                   uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass,
+                                   const int32_t* q_len_dev, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

@@ -53,17 +53,19 @@ def block_sparse_attention(q, k, v, block_mask, *, kv_len=None, sm_scale=None, b
 
 
 def select_blocks(q, k, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0, mask_heads="kv",
-                  return_scores=False, as_lists=False, top_p=None, score_scale=None, return_mass=False):
+                  return_scores=False, as_lists=False, top_p=None, score_scale=None, return_mass=False, q_len=None):
     """Top-k key blocks per query block by pooled scores, per K/V head (mask_heads="q": per query head), on the device: q
     [B,H,Sq,D], k [B,Hkv,Sk,D] -> bool block mask [B, Hkv|H, ceil(Sq/block), ceil(Sk/block)] for block_sparse_attention with
     the same kv_len / causal / block_size; keep_first / keep_local force the first blocks and the diagonal band.  top_p in
     [0, 1]: a budget per row, the shortest prefix of the ranking whose softmax mass (at score_scale) reaches top_p, capped at
-    top_k; return_mass=True adds the kept mass, fp32 [B, Hkv|H, NQ].
+    top_k; return_mass=True adds the kept mass, fp32 [B, Hkv|H, NQ].  q_len (kv_len's forms): the rows of each item of a ragged
+    batch padded to Sq -- item b is selected as q[b, :, :q_len[b]] would be, its query blocks without a row keep nothing.
     See rectified_spaattn_amd.block_sparse.select_blocks."""
     from . import block_sparse
     return block_sparse.select_blocks(q, k, top_k, block_size=block_size, kv_len=kv_len, causal=causal, keep_first=keep_first,
                                       keep_local=keep_local, mask_heads=mask_heads, return_scores=return_scores,
-                                      as_lists=as_lists, top_p=top_p, score_scale=score_scale, return_mass=return_mass)
+                                      as_lists=as_lists, top_p=top_p, score_scale=score_scale, return_mass=return_mass,
+                                      q_len=q_len)
 
 
 def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
@@ -71,7 +73,8 @@ def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, bloc
     """Block-sparse decode attention: q [B,H,Sq,D] with Sq <= block over a K/V cache [B,Hkv,Sk,D], or over page pools
     [P,Hkv,block,D] behind block_table int32 [B,NKt]; block_mask bool / uint8 [B|1, Hl, 1, NK] or select_blocks' lists;
     return_lse=True adds the fp32 log-sum-exp [B,H,Sq].  k / v float8_e4m3fn with k_scale / v_scale (one fp32 scale per K/V
-    head): the one-byte cache append_kv_e4m3 writes.  See rectified_spaattn_amd.block_sparse.block_sparse_decode."""
+    head): the one-byte cache append_kv_e4m3 writes.  No q_len: a ragged decode batch is block_sparse_extend(q_len=), with this
+    call's bytes.  See rectified_spaattn_amd.block_sparse.block_sparse_decode."""
     from . import block_sparse
     return block_sparse.block_sparse_decode(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                             causal=causal, block_table=block_table, return_lse=return_lse,
@@ -79,15 +82,17 @@ def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, bloc
 
 
 def block_sparse_extend(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
-                        return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None):
+                        return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None, q_len=None):
     """Block-sparse extend attention: a chunk q [B,H,Sq,D] of any length over a K/V cache that already holds a prefix --
     block_sparse_decode without the one-query-block and 64-row limits; block_mask bool / uint8 [B|1, Hl, ceil(Sq/block), NK] or
     select_blocks' lists for that many query blocks; causal is bottom-right aligned; return_lse=True adds the fp32 log-sum-exp
-    [B,H,Sq].  See rectified_spaattn_amd.block_sparse.block_sparse_extend."""
+    [B,H,Sq].  q_len (kv_len's forms; a device tensor is never read on the host): the rows of each item of a ragged batch padded
+    to Sq -- prefill chunks, decode items and draft verifications in one call of fixed shape; item b's rows < q_len[b] are this
+    call on q[b, :, :q_len[b]], the rows beyond are 0 / -inf.  See rectified_spaattn_amd.block_sparse.block_sparse_extend."""
     from . import block_sparse
     return block_sparse.block_sparse_extend(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                             causal=causal, block_table=block_table, return_lse=return_lse,
-                                            blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale)
+                                            blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale, q_len=q_len)
 
 
 def pool_keys(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None, k_scale=None):
@@ -110,14 +115,15 @@ def append_kv_e4m3(k_new, v_new, k_cache, v_cache, *, start, k_scale, v_scale, n
 
 def select_blocks_pooled(q, pooled_k, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0,
                          mask_heads="kv", return_scores=False, as_lists=False, score_splits=None, top_p=None, score_scale=None,
-                         return_mass=False):
-    """select_blocks from a cache of pooled keys (pool_keys) in place of k: the same bytes without a pass over K, with top_p too.
+                         return_mass=False, q_len=None):
+    """select_blocks from a cache of pooled keys (pool_keys) in place of k: the same bytes without a pass over K, with top_p and
+    q_len too.
     See rectified_spaattn_amd.block_sparse.select_blocks_pooled."""
     from . import block_sparse
     return block_sparse.select_blocks_pooled(q, pooled_k, top_k, block_size=block_size, kv_len=kv_len, causal=causal,
                                              keep_first=keep_first, keep_local=keep_local, mask_heads=mask_heads,
                                              return_scores=return_scores, as_lists=as_lists, score_splits=score_splits,
-                                             top_p=top_p, score_scale=score_scale, return_mass=return_mass)
+                                             top_p=top_p, score_scale=score_scale, return_mass=return_mass, q_len=q_len)
 
 
 def clear_buffer_cache() -> None:

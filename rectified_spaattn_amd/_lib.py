@@ -166,6 +166,15 @@ PROTOTYPES = {
     "rsa_set_tuning": (i32, [cstr, i32]),
     "rsa_status_string": (cstr, [i32]),
     "rsa_last_hip_error": (cstr, []),
+    # the ragged entries: additive and found by symbol like the extend entries, which stay the table's last three
+    "rsa_block_sparse_extend_ragged": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp,
+                                             i64, i32, vp, vp, i32, vp, sz, O4, vp, vp, vp]),
+    "rsa_block_sparse_extend_ragged_kv8": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4,
+                                                 vp, i64, i32, vp, vp, i32, vp, sz, O4, vp, vp, vp, vp, vp]),
+    "rsa_block_select_ragged": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, T4, vp, i32, i32, i32, i32, i32,
+                                      vp, sz, vp, vp, vp, vp, i32, f32, vp, vp, vp]),
+    "rsa_block_select_pooled_ragged": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, vp, vp, i32, i32, i32, i32, i32,
+                                             i32, vp, sz, vp, vp, vp, vp, i32, f32, vp, vp, vp]),
     "rsa_block_sparse_extend_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz)]),
     "rsa_block_sparse_extend": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp, i64,
                                       i32, vp, vp, i32, vp, sz, O4, vp, vp]),

@@ -219,6 +219,15 @@ def _device_limit(val, B: int, Sk: int, dev):
     return torch.tensor(val, dtype=torch.int32, device=dev), Sk, val
 
 
+def _row_limit(val, B: int, Sq: int, dev):
+    """q_len as _check_limit("q_len", ...) returned it, for the ragged C entries: DEVICE int32 [B], or None where every item has
+    Sq rows (None, or host values that all equal Sq: the existing entries).  A device tensor is never read on the host."""
+    if isinstance(val, list) and all(n == Sq for n in val):
+        return None
+    q_dev, q_host, _ = _device_limit(val, B, Sq, dev)
+    return torch.full((B,), q_host, dtype=torch.int32, device=dev) if q_dev is None else q_dev
+
+
 def _check_scales(k, Hkv: int, **scales):
     """k_scale= / v_scale= of a call over the cache k: required with an e4m3 cache, refused with a 2-byte one.  A scale is a
     positive finite Python float or a float32 tensor of 1 or Hkv values on the cache's device (its values are not read)."""
@@ -514,7 +523,7 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
 def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None, causal: bool = False,
                   keep_first: int = 0, keep_local: int = 0, mask_heads: str = "kv", return_scores: bool = False,
                   as_lists: bool = False, top_p: Optional[float] = None, score_scale: Optional[float] = None,
-                  return_mass: bool = False):
+                  return_mass: bool = False, q_len=None):
     """Top-k key blocks per query block by pooled scores, per K/V head, on the device (MoBA-style): the
     block_mask of a following block_sparse_attention(q, k, v, mask, kv_len=..., causal=..., block_size=...).
     q [B,H,Sq,D], k [B,Hkv,Sk,D] with H % Hkv == 0 (query head h belongs to K/V head h // (H // Hkv)), bf16 or fp16, head dim 16,
@@ -547,9 +556,17 @@ def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: i
                 prefix with sum(forced u) + sum(prefix u) >= target.  top_p = 0 keeps the forced blocks alone, top_p = 1 every
                 block of non-zero weight, up to the cap
     return_mass=True appends the fp32 tensor [B, Hl, NQ] of float(sum of kept u) / float(total) (0 for a row that sees nothing)
-    to the return value.  Integer sums: two calls give the same bytes.  score_scale and return_mass are refused without top_p."""
+    to the return value.  Integer sums: two calls give the same bytes.  score_scale and return_mass are refused without top_p.
+
+    q_len (rsa_block_select_ragged): the query rows of each batch item in a ragged batch padded to Sq rows
+    -- None (= Sq), an int, one value per batch item, or an int32 / int64 device tensor of 1 or B values, which is clamped into
+    [0, Sq] on the device and never read on the host (kv_len's forms).  With n_b = q_len[b] everything above stands with n_b in
+    place of Sq wherever Sq counts rows: qbar is the mean over the rows < n_b of the block, off_b = kv_len[b] - n_b (kv_len[b]
+    includes the item's n_b new tokens) and r1 = min((i + 1) * block, n_b) - 1, so item b's query blocks i < ceil(n_b / block)
+    carry the bytes of the call on q[b:b+1, :, :n_b].  A query block i >= ceil(n_b / block) has no row: counts 0, mask row clear,
+    scores -inf, mass 0, its cols unspecified.  q's rows at or beyond n_b are never read and may hold NaN."""
     return _select("select_blocks", q, k, False, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
-                   return_scores, as_lists, None, top_p, score_scale, return_mass)
+                   return_scores, as_lists, None, top_p, score_scale, return_mass, q_len)
 
 
 MAX_SCORE_SPLITS = 256  # score workgroups per list row of select_blocks_pooled, at most (rsa_block_select.hip)
@@ -577,10 +594,11 @@ def _check_top_p(top_p, score_scale, return_mass):
 
 
 def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
-            return_scores, as_lists, score_splits=None, top_p=None, score_scale=None, return_mass=False):
+            return_scores, as_lists, score_splits=None, top_p=None, score_scale=None, return_mass=False, q_len=None):
     """select_blocks (keys = k, rsa_block_select) and select_blocks_pooled (keys = pool_keys' cache, rsa_block_select_pooled,
     with its score_splits): the two differ in where kbar comes from and in nothing else.  With top_p the entries are their _p
-    forms, which take (p16, c, mass) in front of the stream."""
+    forms, which take (p16, c, mass) in front of the stream.  With q_len the entries are their _ragged forms: the _p argument
+    lists (p16 = -1: top-k) and the device row counts in front of the stream."""
     blk = _check_block(what, block_size)
     if mask_heads not in ("kv", "q"):
         raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
@@ -594,16 +612,20 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
     NQ, NK = -(-Sq // blk), _key_blocks(Sk, blk)
     Hl = Hkv if mask_heads == "kv" else H
     lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
+    rows = _check_limit("q_len", q_len, B, Sq, Sq)
     _core._require_device(q, keys)
     dev = q.device
     if pooled and keys.data_ptr() % 16:
         raise ValueError("pooled_k: 16-byte aligned")
     kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
+    q_dev = _row_limit(rows, B, Sq, dev)
     L = _lib.lib()
     q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
     entry = ("rsa_block_select_pooled" if pooled else "rsa_block_select") + ("" if top_p is None else "_p")
     need = ctypes.c_size_t(0)
     _lib.check(getattr(L, entry + "_bytes")(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), entry + "_bytes")
+    if q_dev is not None:
+        entry = "rsa_block_select_pooled_ragged" if pooled else "rsa_block_select_ragged"
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
     out = _empty_lists(B * Hl, NQ, NK, dev)
     scores = torch.empty((B, Hl, NQ, NK), dtype=torch.float32, device=dev) if return_scores else None
@@ -617,6 +639,8 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         mass = torch.empty((B, Hl, NQ), dtype=torch.float32, device=dev) if return_mass else None
         scale = 1.0 / ((H // Hl) * math.sqrt(D)) if score_scale is None else float(score_scale)
         budget = (int(round(float(top_p) * 65536.0)), scale * LOG2_E, _ptr(mass))
+    if q_dev is not None:
+        budget = (budget or (-1, 0.0, None)) + (q_dev.data_ptr(),)
     with torch.cuda.device(dev):
         _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, NQ, NK, _core._t4(q), source, _ptr(kv_dev), kv_valid,
                                      int(bool(causal)), min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), *splits,
@@ -750,7 +774,8 @@ def append_kv_e4m3(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tens
 def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None,
                          causal: bool = False, keep_first: int = 0, keep_local: int = 0, mask_heads: str = "kv",
                          return_scores: bool = False, as_lists: bool = False, score_splits: Optional[int] = None,
-                         top_p: Optional[float] = None, score_scale: Optional[float] = None, return_mass: bool = False):
+                         top_p: Optional[float] = None, score_scale: Optional[float] = None, return_mass: bool = False,
+                         q_len=None):
     """select_blocks from a cache of pooled keys: q [B,H,Sq,D] (any Sq), pooled_k fp32 [B, Hkv, NK, D]
     contiguous as pool_keys returns it, Sk taken as NK * block_size.  Visible set, forced blocks, top-k, ties and the returned
     mask / lists / scores are select_blocks' contract word for word, and on inputs both calls accept
@@ -762,9 +787,11 @@ def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *,
     score_splits: workgroups per list row that compute the row's scores before the select workgroup ranks them (few list rows,
     many key blocks: a decode step); 1 = inside the select workgroup; None = the library's choice, a function of the shapes alone
     (measured: DESIGN.md 5.13).  Every value gives the same bytes.  Asynchronous on the current stream, capturable.
-    top_p, score_scale, return_mass: select_blocks' (rsa_block_select_pooled_p), with the same bytes."""
+    top_p, score_scale, return_mass: select_blocks' (rsa_block_select_pooled_p), with the same bytes.
+    q_len: select_blocks' (rsa_block_select_pooled_ragged), with the same bytes: the rows of each batch item
+    of a ragged batch, the selection half of the continuous-batching step block_sparse_extend(q_len=) describes."""
     return _select("select_blocks_pooled", q, pooled_k, True, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
-                   return_scores, as_lists, score_splits, top_p, score_scale, return_mass)
+                   return_scores, as_lists, score_splits, top_p, score_scale, return_mass, q_len)
 
 
 DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_decode.hip)
@@ -802,7 +829,9 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     scale through the scores and does not see v_scale.  With power-of-two scales the bytes are those of this call on the
     dequantised 2-byte cache.  Every rule above holds unchanged; K views need strides and a pointer that are multiples of 8 bytes, V
     views of 16 (others are refused, never copied).  The scales' values are not checked: a zero, negative or non-finite one garbles
-    its head's rows only."""
+    its head's rows only.
+    There is no q_len here: a ragged decode or draft-verification batch (items of different row counts in one padded q) is
+    block_sparse_extend(..., q_len=), which gives this call's bytes on every shape this call serves."""
     return _sparse_rows(False, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
                         k_scale, v_scale)
 
@@ -836,7 +865,8 @@ def extend_default_split(groups: int, NK: int) -> int:
 
 def block_sparse_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask, *, kv_len=None,
                         sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, block_table=None,
-                        return_lse: bool = False, blocks_per_split: Optional[int] = None, k_scale=None, v_scale=None):
+                        return_lse: bool = False, blocks_per_split: Optional[int] = None, k_scale=None, v_scale=None,
+                        q_len=None):
     """Block-sparse attention of a chunk of new tokens over a K/V cache that already holds a prefix ("extend": chunked prefill, a
     second turn on a cached conversation, a prefix-cache hit, verification of a speculative draft): block_sparse_decode with the
     one-query-block limit and the 64-row limit lifted.  Everything not said here is block_sparse_decode's
@@ -865,14 +895,35 @@ def block_sparse_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     shape up to Sq = 512 and at Sq = 2048 over a 131 072-key cache; over 8 x 32 768 keys the crossover lies near Sq = 512 at top_k
     64 and near 1 300 at top_k 16 -- beyond it gather once and call block_sparse_attention.  Against block_sparse_attention on a
     cache that is already contiguous and 2-byte it is faster up to Sq = 128 and slower from 512 rows on (every 64-row group
-    re-reads its kept blocks)."""
+    re-reads its kept blocks).
+
+    q_len (rsa_block_sparse_extend_ragged[_kv8]): a ragged batch -- prefill chunks, second turns, decode
+    items and draft verifications in one q padded to Sq rows.  None (= Sq), an int, one value per batch item, or an int32 / int64
+    device tensor of 1 or B values, which is clamped into [0, Sq] on the device and never read on the host (kv_len's forms).  With
+    n_b = q_len[b], and kv_len[b] the length AFTER the append (it includes the n_b new tokens): row r < n_b of (b, h) sees key j
+    iff mask[b, hl(h), r // block, j // block] and j < kv_len[b] and j < NK * block and, with causal=True,
+    j <= r + kv_len[b] - n_b -- what this call computes on q[b:b+1, :, :n_b] with mask[b:b+1, :, :ceil(n_b / block)], and at an
+    explicit blocks_per_split with the same bytes.  Rows r >= n_b come out 0 with log-sum-exp -inf (written, not left
+    unwritten); q's rows there are never loaded and may hold NaN; mask / list rows of query blocks i >= ceil(n_b / block) are
+    never read.  A row group of padding rows leaves before it reads a list entry, a table entry or a K/V byte.  The grid, the row
+    groups, the default split and the workspace are those of the padded shapes (extend_row_groups, extend_default_split): the call
+    is capturable and a replay follows q_len, kv_len, the cache and the table as they change in place.  The ragged step on a paged
+    e4m3 cache, every length on the device:
+        append_kv_e4m3(k_new, v_new, kc, vc, start=prev, n_new=q_len, ...); pool_keys(kc, out=pooled, start=prev, kv_len=prev + q_len, ...)
+        lists = select_blocks_pooled(q, pooled, top_k, kv_len=prev + q_len, q_len=q_len, causal=True, as_lists=True)
+        out = block_sparse_extend(q, kc, vc, lists, kv_len=prev + q_len, q_len=q_len, causal=True, block_table=..., ...)
+    What the padding costs (measured, profiles/extend_ragged_perf.txt; 8 x 32 768 keys, padded Sq = 512, top_k 16 / 64): eight
+    one-token items take 3.1x to 5.3x block_sparse_decode's time, a 512-row chunk beside seven one-token items 3.1x to 3.7x the
+    two separate calls.  The call buys one graph of fixed shape, not speed: pad to the longest chunk a step really holds and keep
+    decode-only steps on block_sparse_decode."""
     return _sparse_rows(True, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
-                        k_scale, v_scale)
+                        k_scale, v_scale, q_len)
 
 
 def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
-                 k_scale, v_scale):
-    """block_sparse_decode (ext False) and block_sparse_extend: one argument layer, the C entries of either."""
+                 k_scale, v_scale, q_len=None):
+    """block_sparse_decode (ext False) and block_sparse_extend: one argument layer, the C entries of either; with row counts
+    (q_len, extend only) the _ragged entries, which take them in front of the stream."""
     blk = _check_block("block-sparse extend" if ext else "block-sparse decode", block_size)
     _check_count("blocks_per_split", blocks_per_split, 1, optional=True)
     B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v, dims=(64, 128), block_table=block_table, blk=blk, kv8_ok=True)
@@ -911,10 +962,12 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
         raise NotImplementedError(f"Sq * H // max(Hl, Hkv) = {rows} rows share a K/V head and a list row: block_sparse_decode "
                                   f"serves at most {DECODE_MAX_ROWS}; use block_sparse_attention")
     lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
+    nrows = _check_limit("q_len", q_len, B, Sq, Sq)
     _check_cache(k, v)
     _core._require_device(q, k, v)
     dev = q.device
     kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
+    q_dev = _row_limit(nrows, B, Sq, dev) if ext else None
     scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
     if mask is not None:
         lists = block_mask_to_lists(mask.to(dev) if mask.device != dev else mask, B, Hl)
@@ -936,8 +989,11 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
     out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
     kv8 = k.dtype == E4M3
-    entry = ("rsa_block_sparse_extend" if ext else "rsa_block_sparse_decode") + ("_kv8" if kv8 else "")
+    entry = ("rsa_block_sparse_extend" if ext else "rsa_block_sparse_decode") + ("_ragged" if q_dev is not None else "") \
+        + ("_kv8" if kv8 else "")
     held = [_scale_arg(sc, Hkv, dev) for sc in (k_scale, v_scale)] if kv8 else []
+    if q_dev is not None:
+        held.append(q_dev)
     with torch.cuda.device(dev):
         _lib.check(getattr(L, entry)(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
                                      int(bool(causal)), scale, _core._t4(q), _core._t4(k), _core._t4(v), *table,

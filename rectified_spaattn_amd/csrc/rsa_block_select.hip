@@ -64,9 +64,23 @@ __device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
     return run;
 }
 
-// Visible blocks of list row (b, i): a prefix [0, nvis) of the row.
+// The ragged entries run instantiations of their own, RAG, which take the rows of each batch item, DEVICE
+// int32 q_len [B], as one more kernel argument behind the others (the pack Q: empty without RAG, so those kernels keep their
+// arguments and their code).  sel_row_count: q_len[b] clamped into [0, Sq]; Sq without RAG.
+__device__ __forceinline__ const int32_t* sel_q_len() { return nullptr; }
+__device__ __forceinline__ const int32_t* sel_q_len(const int32_t* q_len) { return q_len; }
+template <bool RAG>
+__device__ __forceinline__ int sel_row_count(const int32_t* __restrict__ q_len, int b, int Sq) {
+    if constexpr (RAG) return min(max(q_len[b], 0), Sq);
+    else return Sq;
+}
+
+// Visible blocks of list row (b, i): a prefix [0, nvis) of the row.  Sq: the batch item's row count (sel_row_count); RAG: a query
+// block without a row sees nothing.
+template <bool RAG = false>
 __device__ __forceinline__ int sel_visible(int len, int Sq, int blk, int NK, int i, int causal) {
     const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
+    if (RAG && r0 >= Sq) return 0;
     int nvis = min(NK, (len + blk - 1) / blk);
     if (causal) nvis = r1 + off < 0 ? 0 : (int)min((long)nvis, (r1 + off) / blk + 1);
     return nvis;
@@ -152,11 +166,11 @@ __device__ __forceinline__ float sel_pool_mean(const typename SelElem<Tag>::type
     return sel_pool_block<Tag>(base, stride_s, rows, D, red) / (float)rows;
 }
 
-template <typename Tag>
+template <typename Tag, bool RAG = false, typename... Q>
 __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q, rsa_tensor4 k, int H, int Hkv, int Hl, int Sq,
                                                                    int Sk, int D, int blk, int NQ, int NK, long q_jobs,
                                                                    const int32_t* __restrict__ kv_len, int kv_valid,
-                                                                   float* __restrict__ kbar, float* __restrict__ qsum) {
+                                                                   float* __restrict__ kbar, float* __restrict__ qsum, Q... q_len) {
     __shared__ float red[4][128];
     const int tid = threadIdx.x;
     long job = blockIdx.x;
@@ -166,10 +180,13 @@ __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q
         const int hl = (int)(bh % Hl), gl = H / Hl;
         const long b = bh / Hl;
         const long r0 = (long)i * blk;
-        const int rows = (int)min((long)blk, (long)Sq - r0);
+        // the block's rows below the batch item's count (uniform over the workgroup); RAG: none, in a block of padding -- the block's
+        // value is then 0, q is not read and cnt is not used
+        const int rows = (int)min((long)blk, (long)sel_row_count<RAG>(sel_q_len(q_len...), (int)b, Sq) - r0);
         const float cnt = (float)rows;
         float tot = 0.f;
-        for (int u = 0; u < gl; ++u) {      // the list head's query heads, ascending: each head's own mean, then the sum
+        // the list head's query heads, ascending: each head's own mean, then the sum
+        for (int u = 0; (!RAG || rows > 0) && u < gl; ++u) {
             const unsigned short* base = static_cast<const unsigned short*>(q.ptr) + b * q.stride_b +
                                          (long)(hl * gl + u) * q.stride_h + r0 * q.stride_s;
             tot += sel_pool_block<Tag>(base, q.stride_s, rows, D, red) / cnt;
@@ -265,11 +282,11 @@ __device__ __forceinline__ void sel_score_blocks(const float* __restrict__ kb, c
 
 // The score pass of the pooled selection spread over `splits` workgroups per list row: workgroup (row, part) writes the keys of
 // its slice of the visible blocks to wkeys[row, :].
-template <int L>
+template <int L, bool RAG = false, typename... Q>
 __global__ __launch_bounds__(SEL_NT) void block_score_kernel(const float* __restrict__ kbar, const float* __restrict__ qsum, int Hkv,
                                                              int Hl, int Sq, int Sk, int blk, int NQ, int NK, int splits,
                                                              const int32_t* __restrict__ kv_len, int kv_valid, int causal,
-                                                             unsigned* __restrict__ wkeys) {
+                                                             unsigned* __restrict__ wkeys, Q... q_len) {
     constexpr int D = 4 * L;
     const int part = (int)(blockIdx.x % (unsigned)splits);
     const long row = blockIdx.x / (unsigned)splits;
@@ -278,7 +295,8 @@ __global__ __launch_bounds__(SEL_NT) void block_score_kernel(const float* __rest
     const int hl = (int)(bh % Hl);
     const long b = bh / Hl;
     const int hk = hl / (Hl / Hkv);
-    const int nvis = sel_visible(sel_key_limit(kv_len, (int)b, kv_valid, Sk), Sq, blk, NK, i, causal);
+    const int nvis = sel_visible<RAG>(sel_key_limit(kv_len, (int)b, kv_valid, Sk), sel_row_count<RAG>(sel_q_len(q_len...), (int)b, Sq),
+                                      blk, NK, i, causal);
     const int chunk = (NK + splits - 1) / splits;
     const int lo = part * chunk, hi = min(lo + chunk, nvis);
     sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, lo, hi, wkeys + row * NK);
@@ -371,8 +389,9 @@ __device__ __forceinline__ void sel_radix(const unsigned* keys, int nvis, SelFor
 
 // One list row by one workgroup.  LOADED = 0: the scores are computed here (r.kbar, r.qsum); LOADED = 1: their keys are loaded from
 // r.wkeys (block_score_kernel).  BUDGET = false: top-k (p16, c and mass are not read); true: top-p capped at top_k.
-template <int L, int LOADED, bool BUDGET>
-__device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c, float* __restrict__ mass) {
+template <int L, int LOADED, bool BUDGET, bool RAG>
+__device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c, float* __restrict__ mass,
+                                             const int32_t* __restrict__ q_len) {
     extern __shared__ unsigned keys[];              // [NK]: the scores of the visible blocks as ordered keys
     __shared__ unsigned hist[256];
     __shared__ unsigned wsum[4];
@@ -381,7 +400,7 @@ __device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c
     __shared__ unsigned long long step_mask[SEL_MAX_STEPS];
     constexpr int D = 4 * L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int blk = r.blk, NK = r.NK, Sq = r.Sq;
+    const int blk = r.blk, NK = r.NK;
     const long row = blockIdx.x;
     const int i = (int)(row % r.NQ);
     const long bh = row / r.NQ;
@@ -389,10 +408,11 @@ __device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c
     const long b = bh / r.Hl;
     const int hk = hl / (r.Hl / r.Hkv);
     const int len = sel_key_limit(r.kv_len, (int)b, r.kv_valid, r.Sk);
+    const int Sq = sel_row_count<RAG>(q_len, (int)b, r.Sq);    // the batch item's rows: r1 and off count from them
 
     // 1. visible blocks: a prefix [0, nvis) of the row; forced blocks: [0, kf) and [flo, fhi] within it
     const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
-    const int nvis = sel_visible(len, Sq, blk, NK, i, r.causal);
+    const int nvis = sel_visible<RAG>(len, Sq, blk, NK, i, r.causal);
     SelForced forced = {min(r.keep_first, nvis), 1, 0};
     if (r.keep_local >= 1 && nvis > 0) {
         const long jd_lo = max(r0 + off, 0L) / blk, jd_hi = min(max(r1 + off, 0L), (long)len - 1) / blk;
@@ -510,14 +530,15 @@ __device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c
     }
 }
 
-template <int L, int LOADED>
-__global__ __launch_bounds__(SEL_NT) void block_select_kernel(const sel_rows r) {
-    sel_row_body<L, LOADED, false>(r, 0, 0.f, nullptr);
+template <int L, int LOADED, bool RAG = false, typename... Q>
+__global__ __launch_bounds__(SEL_NT) void block_select_kernel(const sel_rows r, Q... q_len) {
+    sel_row_body<L, LOADED, false, RAG>(r, 0, 0.f, nullptr, sel_q_len(q_len...));
 }
 
-template <int L, int LOADED>
-__global__ __launch_bounds__(SEL_NT) void block_select_p_kernel(const sel_rows r, int p16, float c, float* __restrict__ mass) {
-    sel_row_body<L, LOADED, true>(r, p16, c, mass);
+template <int L, int LOADED, bool RAG = false, typename... Q>
+__global__ __launch_bounds__(SEL_NT) void block_select_p_kernel(const sel_rows r, int p16, float c, float* __restrict__ mass,
+                                                                Q... q_len) {
+    sel_row_body<L, LOADED, true, RAG>(r, p16, c, mass, sel_q_len(q_len...));
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -540,13 +561,19 @@ static void sel_with_lanes(int D, F f) {
     }
 }
 
-// The select kernel over `rows` list rows: LOADED from r.wkeys, the top-p kernel with a budget.
-static int sel_launch_select(int D, long rows, const sel_rows& r, const sel_top_p* p, hipStream_t s) {
+// The select kernel over `rows` list rows: LOADED from r.wkeys, the top-p kernel with a budget; with q_len (the ragged entries:
+// the rows of each batch item) their RAG instantiations.
+static int sel_launch_select(int D, long rows, const sel_rows& r, const sel_top_p* p, const int32_t* q_len, hipStream_t s) {
     const dim3 grid((unsigned)rows);
     const size_t lds = (size_t)r.NK * sizeof(unsigned);
     sel_with_lanes(D, [&](auto lanes) {
         constexpr int L = decltype(lanes)::value;
-        if (p && r.wkeys) block_select_p_kernel<L, 1><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass);
+        if (q_len) {
+            if (p && r.wkeys) block_select_p_kernel<L, 1, true><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass, q_len);
+            else if (p) block_select_p_kernel<L, 0, true><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass, q_len);
+            else if (r.wkeys) block_select_kernel<L, 1, true><<<grid, SEL_NT, lds, s>>>(r, q_len);
+            else block_select_kernel<L, 0, true><<<grid, SEL_NT, lds, s>>>(r, q_len);
+        } else if (p && r.wkeys) block_select_p_kernel<L, 1><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass);
         else if (p) block_select_p_kernel<L, 0><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass);
         else if (r.wkeys) block_select_kernel<L, 1><<<grid, SEL_NT, lds, s>>>(r);
         else block_select_kernel<L, 0><<<grid, SEL_NT, lds, s>>>(r);
@@ -556,10 +583,17 @@ static int sel_launch_select(int D, long rows, const sel_rows& r, const sel_top_
 
 // The pool kernel over the query jobs of r's rows and k_jobs key jobs behind them (none: k and kbar are not touched).
 static int sel_launch_pool(int dtype, int H, int D, rsa_tensor4 q, rsa_tensor4 k, long q_jobs, long k_jobs, const sel_rows& r,
-                           float* kbar, float* qsum, hipStream_t s) {
+                           float* kbar, float* qsum, const int32_t* q_len, hipStream_t s) {
+    const dim3 grid((unsigned)(q_jobs + k_jobs));
+    if (q_len) {
+        auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag, true, const int32_t*>
+                                         : block_select_pool_kernel<fp16_tag, true, const int32_t*>;
+        kernel<<<grid, SEL_NT, 0, s>>>(q, k, H, r.Hkv, r.Hl, r.Sq, r.Sk, D, r.blk, r.NQ, r.NK, q_jobs, r.kv_len, r.kv_valid, kbar, qsum,
+                                       q_len);
+        return rsa_launch_status();
+    }
     auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag> : block_select_pool_kernel<fp16_tag>;
-    kernel<<<dim3((unsigned)(q_jobs + k_jobs)), SEL_NT, 0, s>>>(q, k, H, r.Hkv, r.Hl, r.Sq, r.Sk, D, r.blk, r.NQ, r.NK, q_jobs, r.kv_len,
-                                                                r.kv_valid, kbar, qsum);
+    kernel<<<grid, SEL_NT, 0, s>>>(q, k, H, r.Hkv, r.Hl, r.Sq, r.Sk, D, r.blk, r.NQ, r.NK, q_jobs, r.kv_len, r.kv_valid, kbar, qsum);
     return rsa_launch_status();
 }
 
@@ -577,7 +611,8 @@ static int sel_sizes(bool pooled, int B, int Hkv, int Hl, int D, int NQ, int NK,
 // What rsa_block_select[_p] and rsa_block_select_pooled[_p] check alike, in the order that decides the status of a call that is
 // wrong in two ways (the caller's own checks before it and behind it all return RSA_ERR_BAD_ARG).  cap: the keys the K side can
 // hold, Sk or NK * block.
-static int sel_check(bool pooled, int B, int H, int D, int dtype, rsa_tensor4 q, const sel_rows& r, long cap, size_t* need) {
+static int sel_check(bool pooled, int B, int H, int D, int dtype, rsa_tensor4 q, const sel_rows& r, const int32_t* q_len, long cap,
+                     size_t* need) {
     if (B <= 0 || H <= 0 || r.Hkv <= 0 || r.Hl <= 0 || r.Sq <= 0) return RSA_ERR_BAD_ARG;
     if (H % r.Hkv || (r.Hl != r.Hkv && r.Hl != H)) return RSA_ERR_BAD_ARG;
     if (r.blk != 64 && r.blk != 128) return RSA_ERR_UNSUPPORTED;
@@ -591,7 +626,7 @@ static int sel_check(bool pooled, int B, int H, int D, int dtype, rsa_tensor4 q,
     if (!r.bitmask || !r.cols || !r.counts) return RSA_ERR_BAD_ARG;
     if (rsa_check_tensor(q) != RSA_OK || q.stride_b < 0 || q.stride_h < 0 || q.stride_s < 0) return RSA_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(r.bitmask) | reinterpret_cast<uintptr_t>(r.cols) | reinterpret_cast<uintptr_t>(r.counts) |
-         reinterpret_cast<uintptr_t>(r.scores) | reinterpret_cast<uintptr_t>(r.kv_len)) & 3)
+         reinterpret_cast<uintptr_t>(r.scores) | reinterpret_cast<uintptr_t>(r.kv_len) | reinterpret_cast<uintptr_t>(q_len)) & 3)
         return RSA_ERR_BAD_ARG;
     return RSA_OK;
 }
@@ -602,10 +637,10 @@ static bool selp_budget_ok(const sel_top_p& p) {
 
 // The body of rsa_block_select and rsa_block_select_p (top_p NULL: top-k).  r: the call's arguments; kbar, qsum are set here.
 static int sel_run(int B, int H, int D, int dtype, rsa_tensor4 q, rsa_tensor4 k, void* ws, size_t ws_bytes, sel_rows r,
-                   const sel_top_p* top_p, void* stream) {
+                   const sel_top_p* top_p, const int32_t* q_len, void* stream) {
     if ((top_p && !selp_budget_ok(*top_p)) || r.Sk <= 0) return RSA_ERR_BAD_ARG;
     size_t need = 0;
-    const int st = sel_check(false, B, H, D, dtype, q, r, r.Sk, &need);
+    const int st = sel_check(false, B, H, D, dtype, q, r, q_len, r.Sk, &need);
     if (st != RSA_OK) return st;
     if (!ws || rsa_check_tensor(k) != RSA_OK || k.stride_b < 0 || k.stride_h < 0 || k.stride_s < 0) return RSA_ERR_BAD_ARG;
     if (reinterpret_cast<uintptr_t>(ws) & 15) return RSA_ERR_BAD_ARG;
@@ -616,8 +651,8 @@ static int sel_run(int B, int H, int D, int dtype, rsa_tensor4 q, rsa_tensor4 k,
     float* qsum = static_cast<float*>(ws);              // [B, Hl, NQ, D]
     float* kbar = qsum + q_jobs * D;                    // [B, Hkv, NK, D]
     r.kbar = kbar, r.qsum = qsum;
-    const int rc = sel_launch_pool(dtype, H, D, q, k, q_jobs, k_jobs, r, kbar, qsum, s);
-    return rc != RSA_OK ? rc : sel_launch_select(D, q_jobs, r, top_p, s);
+    const int rc = sel_launch_pool(dtype, H, D, q, k, q_jobs, k_jobs, r, kbar, qsum, q_len, s);
+    return rc != RSA_OK ? rc : sel_launch_select(D, q_jobs, r, top_p, q_len, s);
 }
 
 extern "C" int rsa_block_select_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
@@ -633,7 +668,7 @@ extern "C" int rsa_block_select(int B, int H, int Hkv, int Hl, int Sq, int Sk, i
                                 int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
                                 int32_t* counts, float* scores, void* stream) {
     return sel_run(B, H, D, dtype, q, k, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid,
-                   causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, nullptr, stream);
+                   causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, nullptr, nullptr, stream);
 }
 
 extern "C" int rsa_block_select_p(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK,
@@ -642,7 +677,7 @@ extern "C" int rsa_block_select_p(int B, int H, int Hkv, int Hl, int Sq, int Sk,
                                   int32_t* counts, float* scores, int p16, float c, float* mass, void* stream) {
     const sel_top_p p = {p16, c, mass};
     return sel_run(B, H, D, dtype, q, k, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid,
-                   causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, &p, stream);
+                   causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, &p, nullptr, stream);
 }
 
 // ---- the pooled-key cache ----------------------------------------------------------------------------------
@@ -719,10 +754,10 @@ static int sel_default_splits(size_t rows, int NK, int D) {
 // The body of rsa_block_select_pooled and rsa_block_select_pooled_p (top_p NULL: top-k).  r: the call's arguments; Sk, kbar, qsum
 // and wkeys are set here.
 static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const float* pooled_k, int score_splits, void* ws,
-                          size_t ws_bytes, sel_rows r, const sel_top_p* top_p, void* stream) {
+                          size_t ws_bytes, sel_rows r, const sel_top_p* top_p, const int32_t* q_len, void* stream) {
     if ((top_p && !selp_budget_ok(*top_p)) || r.NK <= 0) return RSA_ERR_BAD_ARG;
     size_t need = 0;
-    const int st = sel_check(true, B, H, D, dtype, q, r, (long)r.NK * r.blk, &need);
+    const int st = sel_check(true, B, H, D, dtype, q, r, q_len, (long)r.NK * r.blk, &need);
     if (st != RSA_OK) return st;
     if (score_splits < 0 || score_splits > SEL_MAX_SPLITS || !ws || !pooled_k) return RSA_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(pooled_k)) & 15) return RSA_ERR_BAD_ARG;
@@ -735,17 +770,23 @@ static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const f
     unsigned* wkeys = reinterpret_cast<unsigned*>(qsum + q_jobs * D);   // [B, Hl, NQ, NK]
     r.Sk = r.NK * r.blk;        // the capacity of the cache
     r.kbar = pooled_k, r.qsum = qsum, r.wkeys = splits > 1 ? wkeys : nullptr;
-    int rc = sel_launch_pool(dtype, H, D, q, q, q_jobs, 0, r, nullptr, qsum, s);    // the pooled queries
+    int rc = sel_launch_pool(dtype, H, D, q, q, q_jobs, 0, r, nullptr, qsum, q_len, s);    // the pooled queries
     if (rc != RSA_OK) return rc;
     if (splits > 1) {
         sel_with_lanes(D, [&](auto lanes) {
-            block_score_kernel<decltype(lanes)::value><<<dim3((unsigned)(q_jobs * splits)), SEL_NT, 0, s>>>(
-                pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits, r.kv_len, r.kv_valid, r.causal, wkeys);
+            constexpr int L = decltype(lanes)::value;
+            const dim3 grid((unsigned)(q_jobs * splits));
+            if (q_len)
+                block_score_kernel<L, true><<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits,
+                                                                    r.kv_len, r.kv_valid, r.causal, wkeys, q_len);
+            else
+                block_score_kernel<L><<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits, r.kv_len,
+                                                              r.kv_valid, r.causal, wkeys);
         });
         rc = rsa_launch_status();
         if (rc != RSA_OK) return rc;
     }
-    return sel_launch_select(D, q_jobs, r, top_p, s);
+    return sel_launch_select(D, q_jobs, r, top_p, q_len, s);
 }
 
 extern "C" int rsa_block_select_pooled_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
@@ -762,7 +803,7 @@ extern "C" int rsa_block_select_pooled(int B, int H, int Hkv, int Hl, int Sq, in
                                        uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, void* stream) {
     return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, 0, block, NQ,
                           NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, nullptr,
-                          stream);
+                          nullptr, stream);
 }
 
 extern "C" int rsa_block_select_pooled_p(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK,
@@ -773,5 +814,30 @@ extern "C" int rsa_block_select_pooled_p(int B, int H, int Hkv, int Hl, int Sq, 
     const sel_top_p p = {p16, c, mass};
     return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, 0, block, NQ,
                           NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, &p,
-                          stream);
+                          nullptr, stream);
+}
+
+// ---- ragged selection: a row count per batch item.  The _p entries' argument lists with q_len_dev, DEVICE
+// int32 [B] (clamped into [0, Sq] on the device; NULL: the existing entry's call), in front of the stream; p16 = -1: plain top-k
+// (c and mass are then not read).
+extern "C" int rsa_block_select_ragged(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK,
+                                       rsa_tensor4 q, rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k,
+                                       int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                                       int32_t* counts, float* scores, int p16, float c, float* mass, const int32_t* q_len_dev,
+                                       void* stream) {
+    const sel_top_p p = {p16, c, mass};
+    return sel_run(B, H, D, dtype, q, k, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, Sk, block, NQ, NK, kv_len_dev, kv_valid,
+                   causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, p16 == -1 ? nullptr : &p, q_len_dev,
+                   stream);
+}
+
+extern "C" int rsa_block_select_pooled_ragged(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK,
+                                              rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid,
+                                              int causal, int top_k, int keep_first, int keep_local, int score_splits, void* ws,
+                                              size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores,
+                                              int p16, float c, float* mass, const int32_t* q_len_dev, void* stream) {
+    const sel_top_p p = {p16, c, mass};
+    return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, 0, block, NQ,
+                          NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores},
+                          p16 == -1 ? nullptr : &p, q_len_dev, stream);
 }

@@ -34,6 +34,13 @@
 // block's, a row's causal limit comes from its index in the whole call, a chunk that starts at or beyond the limit of the group's
 // last row is skipped before its loads (byte-neutral), and partials and the merge are indexed by (row group, split).  The decode
 // instantiations keep their arguments' layout and their code: the group arithmetic lives behind `if constexpr (EXT)`.
+//
+// Ragged (rsa_block_sparse_extend_ragged, rsa_block_sparse_extend_ragged_kv8) is the extend kernels with a
+// row count per batch item, n_b = q_len[b] clamped into [0, Sq]: instantiations of their own (RAG, whose arguments are DecRag: the
+// extend kernels' and q_len behind them), so the decode and the extend instantiations keep their code.  n_b stands where Sq is a
+// row count -- the rows of the group (qn), the group's and each row's causal limit, the merge's row test -- and nowhere else: the
+// grid, the groups and the partials are the padded call's.  A group whose first row is at or beyond n_b leaves before it reads a
+// list entry, a table entry or a K/V byte; the merge writes its rows (0, -inf) unread.
 #include "rsa_attn.h"
 
 #include <math.h>
@@ -79,8 +86,13 @@ struct DecExt : A {
     DecGroups g;
     int qblk;                   // rows of a query block (the merge's base struct holds no block size)
 };
-template <typename A, bool EXT>
-using DecArgsFor = typename std::conditional<EXT, DecExt<A>, A>::type;
+// The ragged kernels' arguments: the extend kernels' and the rows of each batch item behind them.
+template <typename A>
+struct DecRag : DecExt<A> {
+    const int32_t* q_len;       // DEVICE [B], clamped into [0, Sq] in the kernel
+};
+template <typename A, bool EXT, bool RAG = false>
+using DecArgsFor = typename std::conditional<RAG, DecRag<A>, typename std::conditional<EXT, DecExt<A>, A>::type>::type;
 
 // The cache's element: the query's own 2-byte type (Tag = bf16_tag / fp16_tag), or e4m3 codes (kv8_tag<query type>).
 template <typename QTag>
@@ -153,9 +165,10 @@ __device__ __forceinline__ s16x4 dec_tr_read(const unsigned char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
-template <typename CTag, int D, int MT, bool EXT>
+template <typename CTag, int D, int MT, bool EXT, bool RAG = false>
 __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
-    DecArgsFor<typename DecCache<CTag>::Args, EXT> a) {
+    DecArgsFor<typename DecCache<CTag>::Args, EXT, RAG> a) {
+    static_assert(EXT || !RAG, "row counts belong to the extend kernels");
     using Cache = DecCache<CTag>;
     using Tag = typename Cache::Q;      // the type of q, of the MFMA operands and of the output
     using KT = typename Cache::elem;
@@ -180,20 +193,36 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 15, lh = lane >> 4;
     // the workgroup's rows: heads [h0, h0 + hn) of the unit x query rows [q0, q0 + qn) of the call, row = head * qw + query row
     // in the group; list row (b * Hl + hl) * NQ + qb.  Decode: the whole unit (the arithmetic below, spelled as it always was).
-    int ext_unit = 0, ext_b = 0, qb = 0, h0 = 0, hn = 0, q0 = 0, qn = 0, qw = 1, nq = 1;
+    int ext_unit = 0, ext_b = 0, qb = 0, h0 = 0, hn = 0, q0 = 0, qn = 0, qw = 1, nq = 1, nrow = a.Sq;
+    long gid = blockIdx.x;                  // the row group: what the partials and the merge are indexed by
     if constexpr (EXT) {
         int g = blockIdx.x;
         const int hc = g % a.g.HC;
         g /= a.g.HC;
-        const int qc = g % a.g.QC;
-        g /= a.g.QC;
-        ext_unit = g % a.U;
-        ext_b = g / a.U;
+        int qc;
+        if constexpr (RAG) {
+            // ragged: the workgroups are dealt query chunk by query chunk, (qc, b, unit, hc).  An item's live groups are its first
+            // chunks, so the live groups of a batch of short items are the launch's first workgroups, side by side on the chip; in
+            // the groups' own order they sit QC * HC apart and pile up on the few compute units that stride reaches.
+            ext_unit = g % a.U;
+            g /= a.U;
+            const int nb = gridDim.x / (a.U * a.g.QC * a.g.HC);
+            ext_b = g % nb;
+            qc = g / nb;
+            gid = (((long)ext_b * a.U + ext_unit) * a.g.QC + qc) * a.g.HC + hc;
+        } else {
+            qc = g % a.g.QC;
+            g /= a.g.QC;
+            ext_unit = g % a.U;
+            ext_b = g / a.U;
+        }
         qb = qc / a.g.cpb;
         qw = a.g.qg;
         nq = a.g.NQ;
         q0 = qb * a.blk + (qc - qb * a.g.cpb) * qw;
-        qn = min(qw, min((qb + 1) * a.blk, a.Sq) - q0);
+        if constexpr (RAG) nrow = min(max(a.q_len[ext_b], 0), a.Sq);     // the batch item's rows: the causal offset counts from them
+        qn = min(qw, min((qb + 1) * a.blk, nrow) - q0);
+        if (RAG && qn <= 0) return;         // (uniform) a group of padding rows: the merge writes them without a partial
         h0 = hc * a.g.gh;
         hn = min(a.g.gh, a.H / a.U - h0);
     }
@@ -203,9 +232,9 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
     const int kvlen = a.kv_len ? min(max(a.kv_len[b], 0), a.Sk) : a.kv_valid;
     // no row of the group sees a key at or beyond glim (causal: the limit of the group's last query row): chunks from there on
     // are skipped before their loads.  Decode's last row is the call's last: its glim is kvlen.
-    const int glim = EXT && a.causal ? min(kvlen, max(0, q0 + qn + kvlen - a.Sq)) : kvlen;
+    const int glim = EXT && a.causal ? min(kvlen, max(0, q0 + qn + kvlen - nrow)) : kvlen;
     const long lrow = EXT ? ((long)b * a.Hl + hl) * nq + qb : (long)b * a.Hl + hl;
-    const long part = ((long)blockIdx.x * a.nsplit + split) * a.R16;
+    const long part = ((EXT ? gid : (long)blockIdx.x) * a.nsplit + split) * a.R16;
     const int count = min(max(a.counts[lrow], 0), a.NK);
     const int first = split * a.C;
     const int n_items = max(0, min(a.C, count - first));
@@ -241,7 +270,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
                 qf[mt][ks] = f;
             }
         }
-        lim[mt] = !ok ? 0 : (a.causal ? min(kvlen, max(0, qrow + kvlen - a.Sq + 1)) : kvlen);
+        lim[mt] = !ok ? 0 : (a.causal ? min(kvlen, max(0, qrow + kvlen - nrow + 1)) : kvlen);
     }
 
     f32x4 o[DT][MT];
@@ -456,9 +485,9 @@ struct DecMergeArgs8 : DecMergeArgs {
 };
 
 // D / 4 threads per output row, four channels each; the splits in ascending order.
-template <typename CTag, int D, bool EXT>
+template <typename CTag, int D, bool EXT, bool RAG = false>
 __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
-    DecArgsFor<typename std::conditional<DecCache<CTag>::kv8, DecMergeArgs8, DecMergeArgs>::type, EXT> a) {
+    DecArgsFor<typename std::conditional<DecCache<CTag>::kv8, DecMergeArgs8, DecMergeArgs>::type, EXT, RAG> a) {
     using Tag = typename DecCache<CTag>::Q;
     constexpr int TPR = D / 4;
     const long g = (long)blockIdx.x * DEC_NT + threadIdx.x;
@@ -471,6 +500,13 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
     long p0 = ((b * a.U + unit) * a.nsplit) * a.R16 + rr;       // decode: the unit's partials, head-major rows
     long lrow = b * a.Hl + unit / (a.U / a.Hl);
     if constexpr (EXT) {        // the row's group and its place in it (DecGroups)
+        if constexpr (RAG) {
+            if (qrow >= min(max(a.q_len[b], 0), a.Sq)) {    // a padding row: 0 / -inf, no list row and no partial read
+                *reinterpret_cast<uint2*>(a.out + b * a.osb + (long)h * a.osh + (long)qrow * a.oss + 4 * c) = make_uint2(0u, 0u);
+                if (a.lse && c == 0) a.lse[row] = -INFINITY;
+                return;
+            }
+        }
         const int hu = h % gu, hc = hu / a.g.gh, qb = qrow / a.qblk, qi = qrow - qb * a.qblk, qcl = qi / a.g.qg;
         const long grp = ((b * a.U + unit) * a.g.QC + qb * a.g.cpb + qcl) * a.g.HC + hc;
         p0 = (grp * a.nsplit) * a.R16 + (hu - hc * a.g.gh) * a.g.qg + (qi - qcl * a.g.qg);
@@ -598,7 +634,7 @@ extern "C" int rsa_block_sparse_extend_bytes(int B, int H, int Hkv, int Hl, int 
 }
 
 template <typename Tag, int D, bool EXT, typename A0, typename G0>
-static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, int MT, dim3 grid, hipStream_t s) {
+static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, const int32_t* q_len, int MT, dim3 grid, hipStream_t s) {
     DecArgsFor<A0, EXT> a;
     DecArgsFor<G0, EXT> g;
     static_cast<A0&>(a) = a0;
@@ -607,17 +643,33 @@ static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, int MT,
         a.g = g.g = gr;
         a.qblk = g.qblk = a0.blk;
     }
+    const long threads = g.rows * (D / 4);
+    const dim3 mgrid((unsigned)((threads + DEC_NT - 1) / DEC_NT));
+    if constexpr (EXT) {
+        if (q_len) {        // the ragged instantiations
+            DecRag<A0> ar;
+            DecRag<G0> gr2;
+            static_cast<DecExt<A0>&>(ar) = a;
+            static_cast<DecExt<G0>&>(gr2) = g;
+            ar.q_len = gr2.q_len = q_len;
+            if (MT == 1) decode_split_kernel<Tag, D, 1, true, true><<<grid, DEC_NT, 0, s>>>(ar);
+            else if (MT == 2) decode_split_kernel<Tag, D, 2, true, true><<<grid, DEC_NT, 0, s>>>(ar);
+            else decode_split_kernel<Tag, D, 4, true, true><<<grid, DEC_NT, 0, s>>>(ar);
+            decode_merge_kernel<Tag, D, true, true><<<mgrid, DEC_NT, 0, s>>>(gr2);
+            return;
+        }
+    }
     if (MT == 1) decode_split_kernel<Tag, D, 1, EXT><<<grid, DEC_NT, 0, s>>>(a);
     else if (MT == 2) decode_split_kernel<Tag, D, 2, EXT><<<grid, DEC_NT, 0, s>>>(a);
     else decode_split_kernel<Tag, D, 4, EXT><<<grid, DEC_NT, 0, s>>>(a);
-    const long threads = g.rows * (D / 4);
-    decode_merge_kernel<Tag, D, EXT><<<dim3((unsigned)((threads + DEC_NT - 1) / DEC_NT)), DEC_NT, 0, s>>>(g);
+    decode_merge_kernel<Tag, D, EXT><<<mgrid, DEC_NT, 0, s>>>(g);
 }
 
 template <typename Tag, int D, typename A, typename G>
-static void dec_launch(bool ext, const A& a, const G& g, const DecGroups& gr, int MT, dim3 grid, hipStream_t s) {
-    if (ext) dec_launch2<Tag, D, true>(a, g, gr, MT, grid, s);
-    else dec_launch2<Tag, D, false>(a, g, gr, MT, grid, s);
+static void dec_launch(bool ext, const A& a, const G& g, const DecGroups& gr, const int32_t* q_len, int MT, dim3 grid,
+                       hipStream_t s) {
+    if (ext) dec_launch2<Tag, D, true>(a, g, gr, q_len, MT, grid, s);
+    else dec_launch2<Tag, D, false>(a, g, gr, nullptr, MT, grid, s);
 }
 
 // An e4m3 cache view as the loads need it: K is read 8 bytes a lane, V 16 (strides in elements = bytes).
@@ -627,12 +679,13 @@ static int dec_check_cache8(const rsa_tensor4& t, int align) {
     return RSA_OK;
 }
 
-// All four entries: kv8 = the cache holds e4m3 codes and the two scale arrays are there; ext = the extend call (any Sq, row groups).
+// All six entries: kv8 = the cache holds e4m3 codes and the two scale arrays are there; ext = the extend call (any Sq, row groups);
+// q_len_dev = the ragged extend call's rows per batch item (null: Sq; never given without ext).
 static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
                    const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
                    rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* cols,
                    const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
-                   const float* k_scale, const float* v_scale, void* stream) {
+                   const float* k_scale, const float* v_scale, const int32_t* q_len_dev, void* stream) {
     if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || Sk <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
     if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
@@ -661,7 +714,7 @@ static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, in
     if ((reinterpret_cast<uintptr_t>(out.ptr) & 7) || (out.stride_b % 4) || (out.stride_h % 4) || (out.stride_s % 4))
         return RSA_ERR_BAD_ARG;         // 8-byte stores of four channels
     if ((reinterpret_cast<uintptr_t>(cols) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(kv_len_dev) |
-         reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(lse)) & 3)
+         reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(q_len_dev)) & 3)
         return RSA_ERR_BAD_ARG;
     if (block_table && (num_pages <= 0 || table_stride_b < 0)) return RSA_ERR_BAD_ARG;
     if (reinterpret_cast<uintptr_t>(ws) & 15) return RSA_ERR_BAD_ARG;
@@ -707,18 +760,18 @@ static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, in
     const DecMergeArgs& g2 = g;
     if (kv8) {
         if (dtype == RSA_BF16) {
-            if (D == 128) dec_launch<kv8_tag<bf16_tag>, 128>(ext, a, g, p.g, p.MT, grid, s);
-            else dec_launch<kv8_tag<bf16_tag>, 64>(ext, a, g, p.g, p.MT, grid, s);
+            if (D == 128) dec_launch<kv8_tag<bf16_tag>, 128>(ext, a, g, p.g, q_len_dev, p.MT, grid, s);
+            else dec_launch<kv8_tag<bf16_tag>, 64>(ext, a, g, p.g, q_len_dev, p.MT, grid, s);
         } else {
-            if (D == 128) dec_launch<kv8_tag<fp16_tag>, 128>(ext, a, g, p.g, p.MT, grid, s);
-            else dec_launch<kv8_tag<fp16_tag>, 64>(ext, a, g, p.g, p.MT, grid, s);
+            if (D == 128) dec_launch<kv8_tag<fp16_tag>, 128>(ext, a, g, p.g, q_len_dev, p.MT, grid, s);
+            else dec_launch<kv8_tag<fp16_tag>, 64>(ext, a, g, p.g, q_len_dev, p.MT, grid, s);
         }
     } else if (dtype == RSA_BF16) {
-        if (D == 128) dec_launch<bf16_tag, 128>(ext, a2, g2, p.g, p.MT, grid, s);
-        else dec_launch<bf16_tag, 64>(ext, a2, g2, p.g, p.MT, grid, s);
+        if (D == 128) dec_launch<bf16_tag, 128>(ext, a2, g2, p.g, q_len_dev, p.MT, grid, s);
+        else dec_launch<bf16_tag, 64>(ext, a2, g2, p.g, q_len_dev, p.MT, grid, s);
     } else {
-        if (D == 128) dec_launch<fp16_tag, 128>(ext, a2, g2, p.g, p.MT, grid, s);
-        else dec_launch<fp16_tag, 64>(ext, a2, g2, p.g, p.MT, grid, s);
+        if (D == 128) dec_launch<fp16_tag, 128>(ext, a2, g2, p.g, q_len_dev, p.MT, grid, s);
+        else dec_launch<fp16_tag, 64>(ext, a2, g2, p.g, q_len_dev, p.MT, grid, s);
     }
     return rsa_launch_status();
 }
@@ -729,7 +782,7 @@ extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, in
                                        int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
                                        size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
     return dec_run(false, false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
-                   table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr, stream);
+                   table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr, nullptr, stream);
 }
 
 // The e4m3 cache: dtype names q's type; k / v hold one-byte codes (strides in bytes) and the scales are DEVICE fp32 [Hkv].
@@ -740,7 +793,7 @@ extern "C" int rsa_block_sparse_decode_kv8(int B, int H, int Hkv, int Hl, int Sq
                                            void* ws, size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale,
                                            const float* v_scale, void* stream) {
     return dec_run(false, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
-                   table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale, stream);
+                   table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale, nullptr, stream);
 }
 
 // ---- extend: any number of query rows.  The decode entries' argument lists; NQ = ceil(Sq / block) and cols /
@@ -752,7 +805,7 @@ extern "C" int rsa_block_sparse_extend(int B, int H, int Hkv, int Hl, int Sq, in
                                        size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
     return dec_run(true, false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
                    block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr,
-                   stream);
+                   nullptr, stream);
 }
 
 extern "C" int rsa_block_sparse_extend_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
@@ -763,5 +816,30 @@ extern "C" int rsa_block_sparse_extend_kv8(int B, int H, int Hkv, int Hl, int Sq
                                            const float* v_scale, void* stream) {
     return dec_run(true, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
                    block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale,
-                   stream);
+                   nullptr, stream);
+}
+
+// ---- ragged extend: a row count per batch item.  The extend entries' argument lists with q_len_dev, DEVICE
+// int32 [B] (clamped into [0, Sq] on the device; NULL: the extend entry's call), in front of the stream.
+extern "C" int rsa_block_sparse_extend_ragged(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                              const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                              rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                              int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split,
+                                              void* ws, size_t ws_bytes, rsa_out4 out, float* lse, const int32_t* q_len_dev,
+                                              void* stream) {
+    return dec_run(true, false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
+                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr,
+                   q_len_dev, stream);
+}
+
+extern "C" int rsa_block_sparse_extend_ragged_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                                  const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale,
+                                                  rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table,
+                                                  int64_t table_stride_b, int num_pages, const int32_t* cols, const int32_t* counts,
+                                                  int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
+                                                  const float* k_scale, const float* v_scale, const int32_t* q_len_dev,
+                                                  void* stream) {
+    return dec_run(true, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
+                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale,
+                   q_len_dev, stream);
 }
