@@ -537,6 +537,62 @@ int rsa_block_select_pooled_ragged(int B, int H, int Hkv, int Hl, int Sq, int D,
                                    uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass,
                                    const int32_t* q_len_dev, void* stream);
 
+/* ---- PACKED batches: q [T, H, D] with cu_seqlens_q for the extend call, the pooled selection and the e4m3 append (found by
+ * symbol: the header version stays 6.1).  A continuous-batching step holds its tokens back to back: q is
+ * [T, H, D] (T, the token budget, a host value that fixes grid and workspace), cu_seqlens_q_dev DEVICE int32 [B + 1] says where
+ * each item starts, and max_q_len (M, a host int, 1 <= M <= T: flash-attn's max_seqlen_q) bounds an item's rows.  The device
+ * sanitises cu_seqlens_q once per call and never forms an address from a value of it; the host never reads it:
+ *     s_b = the running maximum of clamp(cu[b], 0, T),  n_b = min(s_{b+1} - s_b, M),  item b = rows [s_b, s_b + n_b).
+ * Rows t < T of no item -- behind s_B, in front of s_0, an item's rows beyond M -- are never loaded (q may hold NaN there).
+ * q, out (and k_new / v_new of the append) are passed as rsa_tensor4 / rsa_out4 whose stride_s is the stride of a row (a token) and
+ * stride_h that of a head; stride_b is not read.  Strides as the padded entries ask (multiples of 8 elements for q, 4 for out): a
+ * view of a fused projection [T, (H + 2 Hkv) D] runs without a copy.  len_b (kv_len_dev / kv_valid) is the length AFTER the append.
+ *   extend    rsa_block_sparse_extend_packed[_kv8] are rsa_block_sparse_extend_ragged[_kv8] with T in front, M where Sq stood and
+ *             cu_seqlens_q_dev where q_len_dev stood.  cols / counts keep the padded layout [B * Hl, NQ, NK] / [B * Hl, NQ] with
+ *             NQ = ceil(M / block); list rows of query blocks i >= ceil(n_b / block) are never read.  Item b is
+ *             rsa_block_sparse_extend on q[s_b : s_b + n_b] seen as [1, H, n_b, D] with its list rows and len_b (causal: j <= r +
+ *             len_b - n_b), at an equal explicit blocks_per_split its bytes, and the bytes of the ragged entry on the padded
+ *             copy.  out [T, H, D] and lse fp32 [T, H]: every row is written exactly once, rows of no item as 0 / -inf before a
+ *             list row or a partial is looked at.  Row groups: gh as in extend, qg = min(64 / gh, block, M) -- M = 1 runs the
+ *             one-row-tile kernels decode runs.  A scan launch writes the sanitised starts and the prefix sums of the items' row
+ *             groups to the head of the workspace; the split kernel's grid holds QP * U * HC workgroups, QP a host bound on the
+ *             row groups any sanitised cu_seqlens_q can ask for (rsa_block_sparse_extend_packed_bytes reports it in *pieces,
+ *             which may be NULL): the live ones are the first, the rest leave before they read a list entry, a table entry or a
+ *             K/V byte.  blocks_per_split 0: min(8, NK) while QP * U * HC < 256, else NK.  Three launches.
+ *             rsa_block_sparse_extend_packed_bytes: the workspace, a function of its host arguments alone.
+ *   select    rsa_block_select_pooled_packed is rsa_block_select_pooled_ragged with T in front, M where Sq stood (NQ =
+ *             ceil(M / block)) and cu_seqlens_q_dev, item_ws where q_len_dev stood; item_ws: DEVICE int32 [2 (B + 1)] scratch of
+ *             the call.  Workspace: rsa_block_select_pooled_p_bytes(B, ..., NQ, NK).  Results [B * Hl, NQ, ..] with the bytes of
+ *             the ragged entry on the padded copy of q with q_len = n_b.  One launch more than that entry (the scan).
+ *   append    rsa_kv8_append_packed is rsa_kv8_append with k_new / v_new [T, Hkv, D] and cu_seqlens_dev, item_ws where n_new_dev,
+ *             n_new stood; item_ws: DEVICE int32 [B + 1] scratch.  Token t < n_b of item b is row s_b + t and goes to position
+ *             start[b] + t, with n_b = s_{b+1} - s_b (M = T).  The grid is sized from T.  Placed and untouched bytes are those of
+ *             the padded entry.  Two launches.
+ * Refusals (RSA_ERR_BAD_ARG), all before the first HIP call: T < 1, M outside [1, T], cu_seqlens_q_dev / item_ws NULL or not
+ * 4-byte aligned, and whatever the counterpart refuses.  Capturable; a replay follows cu_seqlens_q's values. */
+int rsa_block_sparse_extend_packed_bytes(int T, int B, int H, int Hkv, int Hl, int max_q_len, int D, int block, int NK,
+                                         int blocks_per_split, size_t* bytes, int64_t* pieces);
+int rsa_block_sparse_extend_packed(int T, int B, int H, int Hkv, int Hl, int max_q_len, int Sk, int D, int dtype, int block, int NK,
+                                   const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                   rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                                   const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes,
+                                   rsa_out4 out, float* lse, const int32_t* cu_seqlens_q_dev, void* stream);
+int rsa_block_sparse_extend_packed_kv8(int T, int B, int H, int Hkv, int Hl, int max_q_len, int Sk, int D, int dtype, int block,
+                                       int NK, const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                       rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                       int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
+                                       size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale, const float* v_scale,
+                                       const int32_t* cu_seqlens_q_dev, void* stream);
+int rsa_block_select_pooled_packed(int T, int B, int H, int Hkv, int Hl, int max_q_len, int D, int dtype, int block, int NQ, int NK,
+                                   rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal,
+                                   int top_k, int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes,
+                                   uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass,
+                                   const int32_t* cu_seqlens_q_dev, int32_t* item_ws, void* stream);
+int rsa_kv8_append_packed(int B, int Hkv, int T, int Sk, int D, int dtype, int block, rsa_tensor4 k_new, rsa_tensor4 v_new,
+                          rsa_out4 k_cache, rsa_out4 v_cache, const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                          const int32_t* start_dev, int start, const int32_t* cu_seqlens_dev, int32_t* item_ws,
+                          const float* k_scale, const float* v_scale, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

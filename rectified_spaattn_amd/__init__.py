@@ -82,17 +82,21 @@ def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, bloc
 
 
 def block_sparse_extend(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
-                        return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None, q_len=None):
+                        return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None, q_len=None,
+                        cu_seqlens_q=None, max_q_len=None):
     """Block-sparse extend attention: a chunk q [B,H,Sq,D] of any length over a K/V cache that already holds a prefix --
     block_sparse_decode without the one-query-block and 64-row limits; block_mask bool / uint8 [B|1, Hl, ceil(Sq/block), NK] or
     select_blocks' lists for that many query blocks; causal is bottom-right aligned; return_lse=True adds the fp32 log-sum-exp
     [B,H,Sq].  q_len (kv_len's forms; a device tensor is never read on the host): the rows of each item of a ragged batch padded
     to Sq -- prefill chunks, decode items and draft verifications in one call of fixed shape; item b's rows < q_len[b] are this
-    call on q[b, :, :q_len[b]], the rows beyond are 0 / -inf.  See rectified_spaattn_amd.block_sparse.block_sparse_extend."""
+    call on q[b, :, :q_len[b]], the rows beyond are 0 / -inf.  cu_seqlens_q (device int32 [B + 1], sanitised on the device, never
+    read on the host) with max_q_len: the packed batch -- q [T, H, D], out [T, H, D], lse [T, H], item b = rows cu[b] .. cu[b + 1]
+    with this call's bytes, the grid sized from T.  See rectified_spaattn_amd.block_sparse.block_sparse_extend."""
     from . import block_sparse
     return block_sparse.block_sparse_extend(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                             causal=causal, block_table=block_table, return_lse=return_lse,
-                                            blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale, q_len=q_len)
+                                            blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale, q_len=q_len,
+                                            cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len)
 
 
 def pool_keys(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None, k_scale=None):
@@ -104,26 +108,29 @@ def pool_keys(k, *, block_size=128, kv_len=None, block_table=None, out=None, sta
                                   workgroups_per_head=workgroups_per_head, k_scale=k_scale)
 
 
-def append_kv_e4m3(k_new, v_new, k_cache, v_cache, *, start, k_scale, v_scale, n_new=None, block_size=128, block_table=None):
+def append_kv_e4m3(k_new, v_new, k_cache, v_cache, *, start, k_scale, v_scale, n_new=None, block_size=128, block_table=None,
+                   cu_seqlens=None):
     """The writer of the one-byte K/V cache: k_new / v_new [B,Hkv,T,D] (bf16 / fp16) become float8_e4m3fn codes under one static
     fp32 scale per K/V head, at positions start[b] + t of k_cache / v_cache [B,Hkv,Sk,D] or of page pools behind block_table.
+    cu_seqlens (device int32 [B + 1]): the packed form, k_new / v_new [T,Hkv,D].
     See rectified_spaattn_amd.block_sparse.append_kv_e4m3."""
     from . import block_sparse
     return block_sparse.append_kv_e4m3(k_new, v_new, k_cache, v_cache, start=start, k_scale=k_scale, v_scale=v_scale,
-                                       n_new=n_new, block_size=block_size, block_table=block_table)
+                                       n_new=n_new, block_size=block_size, block_table=block_table, cu_seqlens=cu_seqlens)
 
 
 def select_blocks_pooled(q, pooled_k, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0,
                          mask_heads="kv", return_scores=False, as_lists=False, score_splits=None, top_p=None, score_scale=None,
-                         return_mass=False, q_len=None):
+                         return_mass=False, q_len=None, cu_seqlens_q=None, max_q_len=None):
     """select_blocks from a cache of pooled keys (pool_keys) in place of k: the same bytes without a pass over K, with top_p and
-    q_len too.
+    q_len too; with cu_seqlens_q / max_q_len for a packed q [T, H, D] (block_sparse_extend's packed batch).
     See rectified_spaattn_amd.block_sparse.select_blocks_pooled."""
     from . import block_sparse
     return block_sparse.select_blocks_pooled(q, pooled_k, top_k, block_size=block_size, kv_len=kv_len, causal=causal,
                                              keep_first=keep_first, keep_local=keep_local, mask_heads=mask_heads,
                                              return_scores=return_scores, as_lists=as_lists, score_splits=score_splits,
-                                             top_p=top_p, score_scale=score_scale, return_mass=return_mass, q_len=q_len)
+                                             top_p=top_p, score_scale=score_scale, return_mass=return_mass, q_len=q_len,
+                                             cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len)
 
 
 def clear_buffer_cache() -> None:

@@ -166,6 +166,15 @@ PROTOTYPES = {
     "rsa_set_tuning": (i32, [cstr, i32]),
     "rsa_status_string": (cstr, [i32]),
     "rsa_last_hip_error": (cstr, []),
+    # the packed entries: additive and found by symbol, in front of the ragged ones for the same reason
+    "rsa_block_sparse_extend_packed_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz), P(i64)]),
+    "rsa_block_sparse_extend_packed": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp,
+                                             i64, i32, vp, vp, i32, vp, sz, O4, vp, vp, vp]),
+    "rsa_block_sparse_extend_packed_kv8": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4,
+                                                 vp, i64, i32, vp, vp, i32, vp, sz, O4, vp, vp, vp, vp, vp]),
+    "rsa_block_select_pooled_packed": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, vp, vp, i32, i32, i32, i32,
+                                             i32, i32, vp, sz, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp]),
+    "rsa_kv8_append_packed": (i32, [i32, i32, i32, i32, i32, i32, i32, T4, T4, O4, O4, vp, i64, i32, vp, i32, vp, vp, vp, vp, vp]),
     # the ragged entries: additive and found by symbol like the extend entries, which stay the table's last three
     "rsa_block_sparse_extend_ragged": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp,
                                              i64, i32, vp, vp, i32, vp, sz, O4, vp, vp, vp]),

@@ -42,7 +42,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _core, _lib
-from ._lib import RsaOut4
+from ._lib import RsaOut4, RsaTensor4
 
 
 def _check_block_pair(block_size_M: int, block_size_N: int) -> int:
@@ -226,6 +226,45 @@ def _row_limit(val, B: int, Sq: int, dev):
         return None
     q_dev, q_host, _ = _device_limit(val, B, Sq, dev)
     return torch.full((B,), q_host, dtype=torch.int32, device=dev) if q_dev is None else q_dev
+
+
+def _packed_view(name: str, x, cu, keys, block_table):
+    """The packed form of a call: x [T, H, D] beside cu (cu_seqlens_q / cu_seqlens) -> (the [B, H, T, D]
+    view of x with batch stride 0 that _check_operands reads, B).  x is 3-d if and only if cu is given; B, the number of items,
+    comes from the block table, else from the cache (k, the pooled keys) -- the lists and kv_len are then held to it."""
+    if cu is None:          # (a 3-d tensor without cu_seqlens is refused by _check_operands, in its own words)
+        return x, None
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError(f"{name}: a packed [T, H, D] tensor if and only if its cu_seqlens is given (a padded [B, H, S, D] one "
+                         f"otherwise), got {tuple(getattr(x, 'shape', ()))} with cu_seqlens")
+    if isinstance(block_table, torch.Tensor) and block_table.dim() == 2:
+        B = block_table.shape[0]
+    elif isinstance(keys, torch.Tensor) and keys.dim() == 4:
+        B = keys.shape[0]
+    else:
+        raise ValueError("packed call: the number of items comes from block_table [B, NKt] or from the cache [B, Hkv, Sk, D]")
+    if B < 1 or x.shape[0] < 1:
+        raise ValueError(f"empty operands (B = {B}, T = {x.shape[0]})")
+    return x.permute(1, 0, 2).unsqueeze(0).expand(B, -1, -1, -1), B
+
+
+def _check_packed(name: str, cu, max_len, B: int, T: int, need_max: bool = True):
+    """cu_seqlens_q (or the append's cu_seqlens) and max_q_len of a packed call -> (the int32 [B + 1] tensor, M).  The values of cu
+    are never read on the host: the device sanitises them.  M: a host int in [1, T] (flash-attn's max_seqlen_q)."""
+    if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32 or cu.numel() != B + 1:
+        raise ValueError(f"{name}: a device int32 tensor of B + 1 = {B + 1} values, got {getattr(cu, 'dtype', type(cu))} "
+                         f"{tuple(getattr(cu, 'shape', ()))}")
+    if need_max:
+        if not isinstance(max_len, int) or isinstance(max_len, bool) or not 1 <= max_len <= T:
+            raise ValueError(f"max_q_len: an int in 1..T = {T} (the rows of the longest item; required with {name}), got {max_len!r}")
+    elif max_len is not None:
+        raise ValueError(f"max_q_len belongs to {name}")
+    return cu.reshape(-1), (int(max_len) if need_max else T)
+
+
+def _t3(t: torch.Tensor) -> RsaTensor4:
+    """A packed [T, H, D] tensor as the packed C entries read it: stride_s the row's, stride_h the head's, stride_b unread."""
+    return RsaTensor4(t.data_ptr(), 0, t.stride(1), t.stride(0))
 
 
 def _check_scales(k, Hkv: int, **scales):
@@ -594,11 +633,13 @@ def _check_top_p(top_p, score_scale, return_mass):
 
 
 def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
-            return_scores, as_lists, score_splits=None, top_p=None, score_scale=None, return_mass=False, q_len=None):
+            return_scores, as_lists, score_splits=None, top_p=None, score_scale=None, return_mass=False, q_len=None,
+            cu_seqlens_q=None, max_q_len=None):
     """select_blocks (keys = k, rsa_block_select) and select_blocks_pooled (keys = pool_keys' cache, rsa_block_select_pooled,
     with its score_splits): the two differ in where kbar comes from and in nothing else.  With top_p the entries are their _p
     forms, which take (p16, c, mass) in front of the stream.  With q_len the entries are their _ragged forms: the _p argument
-    lists (p16 = -1: top-k) and the device row counts in front of the stream."""
+    lists (p16 = -1: top-k) and the device row counts in front of the stream.  With cu_seqlens_q (pooled only) the entry is
+    rsa_block_select_pooled_packed: q [T, H, D], the ragged argument list with T in front and M for Sq."""
     blk = _check_block(what, block_size)
     if mask_heads not in ("kv", "q"):
         raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
@@ -606,7 +647,16 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         _check_count(name, val, 0)
     _check_count("score_splits", score_splits, 1, MAX_SCORE_SPLITS, optional=True)
     _check_top_p(top_p, score_scale, return_mass)
+    q3 = q
+    q, Bp = _packed_view("q", q, cu_seqlens_q, keys, None)
+    if Bp is not None and q_len is not None:
+        raise ValueError("q_len belongs to a padded q: with cu_seqlens_q the rows of an item are cu_seqlens_q[b + 1] - cu_seqlens_q[b]")
+    if Bp is None and max_q_len is not None:
+        raise ValueError("max_q_len belongs to cu_seqlens_q")
     B, H, Hkv, Sq, Sk, D = _check_operands(q, keys, pooled=pooled)
+    if Bp is not None:
+        T = Sq
+        cu, Sq = _check_packed("cu_seqlens_q", cu_seqlens_q, max_q_len, B, T)
     if pooled:      # the cache holds NK blocks: the capacity is taken as NK * block
         Sk *= blk
     NQ, NK = -(-Sq // blk), _key_blocks(Sk, blk)
@@ -620,7 +670,11 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
     kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
     q_dev = _row_limit(rows, B, Sq, dev)
     L = _lib.lib()
-    q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
+    if Bp is not None:
+        _core._require_device(cu)
+        q = q3 if _core._read_in_place(q3) else q3.contiguous()
+    else:
+        q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
     entry = ("rsa_block_select_pooled" if pooled else "rsa_block_select") + ("" if top_p is None else "_p")
     need = ctypes.c_size_t(0)
     _lib.check(getattr(L, entry + "_bytes")(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), entry + "_bytes")
@@ -641,8 +695,13 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         budget = (int(round(float(top_p) * 65536.0)), scale * LOG2_E, _ptr(mass))
     if q_dev is not None:
         budget = (budget or (-1, 0.0, None)) + (q_dev.data_ptr(),)
+    tq = _core._t4(q) if Bp is None else _t3(q)
+    if Bp is not None:      # T in front, M where Sq stood, cu_seqlens_q and the scan's scratch where q_len stood
+        entry, shape = "rsa_block_select_pooled_packed", (T,) + shape
+        cu, items = cu.contiguous(), torch.empty((2 * (B + 1),), dtype=torch.int32, device=dev)
+        budget = (budget or (-1, 0.0, None)) + (cu.data_ptr(), items.data_ptr())
     with torch.cuda.device(dev):
-        _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, NQ, NK, _core._t4(q), source, _ptr(kv_dev), kv_valid,
+        _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, NQ, NK, tq, source, _ptr(kv_dev), kv_valid,
                                      int(bool(causal)), min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), *splits,
                                      ws.data_ptr(), need.value, out["bitmask"].data_ptr(), out["cols"].data_ptr(),
                                      out["counts"].data_ptr(), _ptr(scores), *budget, _core._stream()), entry)
@@ -720,7 +779,7 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
 
 
 def append_kv_e4m3(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, start, k_scale,
-                   v_scale, n_new=None, block_size: int = 128, block_table=None) -> None:
+                   v_scale, n_new=None, block_size: int = 128, block_table=None, cu_seqlens=None) -> None:
     """The writer of an e4m3 K/V cache: new K / V rows become one-byte codes under one static fp32 scale
     per K/V head and land where block_sparse_decode and pool_keys read them.
     k_new / v_new [B,Hkv,T,D], bf16 / fp16, through any strides block_sparse_decode accepts for k / v (head-strided views of a
@@ -739,9 +798,22 @@ def append_kv_e4m3(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tens
     The call writes exactly the D bytes of every placed row and no other byte.  A position at or beyond the capacity is dropped,
     and so is one whose table entry lies outside [0, P).  Two batch items whose table entries name the same page race: keeping
     pages apart is the caller's business.  Static scales mean an append never re-quantises what the page already holds.
-    Asynchronous on the current stream, no host synchronisation, capturable."""
+    Asynchronous on the current stream, no host synchronisation, capturable.
+    cu_seqlens (rsa_kv8_append_packed): the packed batch -- k_new / v_new [T, Hkv, D] (row and head strides
+    multiples of 8 elements), cu_seqlens a device int32 tensor of B + 1 values (B from block_table, else from k_cache), sanitised on
+    the device as block_sparse_extend(cu_seqlens_q=) describes, with M = T: token t < n_b = s_{b+1} - s_b of item b is row s_b + t
+    and goes to position start[b] + t.  Placed and untouched bytes are those of the padded call.  k_new is 3-d if and only if
+    cu_seqlens is given; n_new= beside it is refused.  Two launches; the grid is sized from T."""
     blk = _check_block("append_kv_e4m3", block_size)
+    packed = cu_seqlens is not None
+    if packed and n_new is not None:
+        raise ValueError("n_new belongs to a padded k_new: with cu_seqlens the tokens of an item are cu_seqlens[b + 1] - cu_seqlens[b]")
+    k3, v3 = k_new, v_new
+    k_new, Bp = _packed_view("k_new", k_new, cu_seqlens, k_cache, block_table)
+    v_new, _ = _packed_view("v_new", v_new, cu_seqlens, k_cache, block_table)
     B, _, Hkv, T, _, D = _check_operands(k_new, k_new, v_new, dims=KV8_HEAD_DIMS)
+    if packed:
+        cu, _ = _check_packed("cu_seqlens", cu_seqlens, None, B, T, need_max=False)
     _, _, _, _, Sk, _ = _check_operands(None, k_cache, v_cache, dims=KV8_HEAD_DIMS, block_table=block_table, blk=blk, kv8_ok=True)
     if k_cache.dtype != E4M3:
         raise ValueError(f"k_cache, v_cache: float8_e4m3fn, got {k_cache.dtype}")
@@ -764,6 +836,15 @@ def append_kv_e4m3(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tens
     st_dev, st_host, _ = _device_limit(starts, B, Sk, dev)
     n_dev, n_host, _ = _device_limit(counts, B, T, dev)
     ks, vs = _scale_arg(k_scale, Hkv, dev), _scale_arg(v_scale, Hkv, dev)
+    if packed:
+        _core._require_device(cu)
+        cu, items = cu.contiguous(), torch.empty((B + 1,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rsa_kv8_append_packed(B, Hkv, T, Sk, D, _core.dtype_code(k3.dtype), blk, _t3(k3), _t3(v3),
+                                                        _out4(k_cache), _out4(v_cache), *table, _ptr(st_dev), st_host,
+                                                        cu.data_ptr(), items.data_ptr(), ks.data_ptr(), vs.data_ptr(),
+                                                        _core._stream()), "rsa_kv8_append_packed")
+        return
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().rsa_kv8_append(B, Hkv, T, Sk, D, _core.dtype_code(k_new.dtype), blk, _core._t4(k_new),
                                              _core._t4(v_new), _out4(k_cache), _out4(v_cache), *table, _ptr(st_dev), st_host,
@@ -775,7 +856,7 @@ def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *,
                          causal: bool = False, keep_first: int = 0, keep_local: int = 0, mask_heads: str = "kv",
                          return_scores: bool = False, as_lists: bool = False, score_splits: Optional[int] = None,
                          top_p: Optional[float] = None, score_scale: Optional[float] = None, return_mass: bool = False,
-                         q_len=None):
+                         q_len=None, cu_seqlens_q=None, max_q_len: Optional[int] = None):
     """select_blocks from a cache of pooled keys: q [B,H,Sq,D] (any Sq), pooled_k fp32 [B, Hkv, NK, D]
     contiguous as pool_keys returns it, Sk taken as NK * block_size.  Visible set, forced blocks, top-k, ties and the returned
     mask / lists / scores are select_blocks' contract word for word, and on inputs both calls accept
@@ -789,9 +870,14 @@ def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *,
     (measured: DESIGN.md 5.13).  Every value gives the same bytes.  Asynchronous on the current stream, capturable.
     top_p, score_scale, return_mass: select_blocks' (rsa_block_select_pooled_p), with the same bytes.
     q_len: select_blocks' (rsa_block_select_pooled_ragged), with the same bytes: the rows of each batch item
-    of a ragged batch, the selection half of the continuous-batching step block_sparse_extend(q_len=) describes."""
+    of a ragged batch, the selection half of the continuous-batching step block_sparse_extend(q_len=) describes.
+    cu_seqlens_q, max_q_len (rsa_block_select_pooled_packed): the packed batch block_sparse_extend describes --
+    q [T, H, D], cu_seqlens_q a device int32 tensor of B + 1 values (B = pooled_k.shape[0]) that is sanitised on the device and never
+    read on the host, max_q_len = M a host int in [1, T].  The result keeps the padded layout [B, Hl, NQ, NK] with
+    NQ = ceil(M / block) and holds the bytes of the q_len= call on the padded copy of q with q_len[b] = n_b.  q is 3-d if and only
+    if cu_seqlens_q is given; q_len= beside it is refused.  One launch more than the q_len= call (the scan of cu_seqlens_q)."""
     return _select("select_blocks_pooled", q, pooled_k, True, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
-                   return_scores, as_lists, score_splits, top_p, score_scale, return_mass, q_len)
+                   return_scores, as_lists, score_splits, top_p, score_scale, return_mass, q_len, cu_seqlens_q, max_q_len)
 
 
 DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_decode.hip)
@@ -866,7 +952,7 @@ def extend_default_split(groups: int, NK: int) -> int:
 def block_sparse_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask, *, kv_len=None,
                         sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, block_table=None,
                         return_lse: bool = False, blocks_per_split: Optional[int] = None, k_scale=None, v_scale=None,
-                        q_len=None):
+                        q_len=None, cu_seqlens_q=None, max_q_len: Optional[int] = None):
     """Block-sparse attention of a chunk of new tokens over a K/V cache that already holds a prefix ("extend": chunked prefill, a
     second turn on a cached conversation, a prefix-cache hit, verification of a speculative draft): block_sparse_decode with the
     one-query-block limit and the 64-row limit lifted.  Everything not said here is block_sparse_decode's
@@ -914,19 +1000,73 @@ def block_sparse_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
         out = block_sparse_extend(q, kc, vc, lists, kv_len=prev + q_len, q_len=q_len, causal=True, block_table=..., ...)
     What the padding costs (measured, profiles/extend_ragged_perf.txt; 8 x 32 768 keys, padded Sq = 512, top_k 16 / 64): eight
     one-token items take 3.1x to 5.3x block_sparse_decode's time, a 512-row chunk beside seven one-token items 3.1x to 3.7x the
-    two separate calls.  The call buys one graph of fixed shape, not speed: pad to the longest chunk a step really holds and keep
-    decode-only steps on block_sparse_decode."""
+    two separate calls.  The call buys one graph of fixed shape, not speed: pad to the longest chunk a step really holds
+     -- or pack the batch, below.
+
+    cu_seqlens_q, max_q_len (rsa_block_sparse_extend_packed[_kv8]): the packed batch of a continuous-batching
+    step, flash-attn's varlen layout.  q is [T, H, D] -- T the token budget, any row and head strides that are multiples of 8
+    elements, so a view of a fused projection [T, (H + 2 Hkv) D] runs without a copy --, cu_seqlens_q a device int32 tensor of B + 1
+    values (B from block_table, else from k), max_q_len = M a host int in [1, T].  The device sanitises cu_seqlens_q once and the
+    host never reads it: s_b = the running maximum of clamp(cu[b], 0, T), n_b = min(s_{b+1} - s_b, M), item b = rows
+    [s_b, s_b + n_b).  Returns out [T, H, D] (and lse fp32 [T, H]); every row is written exactly once whatever cu_seqlens_q
+    holds, rows of no item -- behind s_B, in front of s_0, an item's rows beyond M -- as 0 / -inf, and q is never loaded there
+    (NaN allowed).  block_mask / lists keep the padded layout [B|1, Hl, NQ, NK] with NQ = ceil(M / block); rows of query blocks
+    i >= ceil(n_b / block) are never read.  Item b is this call on q[s_b : s_b + n_b] seen as [1, H, n_b, D] with its list rows
+    and kv_len[b] (the length after the append; causal: j <= r + kv_len[b] - n_b): at an equal explicit blocks_per_split its
+    bytes, and the bytes of the q_len= call on the padded copy.  q is 3-d if and only if cu_seqlens_q is given; q_len= beside it is
+    refused.  Grid and workspace depend on (T, B, M) and the head counts alone (packed_row_groups): row groups are gh heads x
+    qg = min(64 // gh, block, M) rows, so M = 1 runs the kernels block_sparse_decode runs; the launch holds one workgroup per
+    (row group the bound QP allows, unit, head chunk, split), the live ones first, and blocks_per_split=None is
+    extend_default_split(QP * units * head chunks, NK).  Three launches, capturable, a replay follows cu_seqlens_q.  The step:
+        append_kv_e4m3(k_new, v_new, kc, vc, start=prev, cu_seqlens=cu, block_table=table, ...)       # k_new [T, Hkv, D]
+        pool_keys(kc, kv_len=kv_len, start=prev, block_table=table, out=pooled, ...)
+        lists = select_blocks_pooled(q, pooled, 16, kv_len=kv_len, cu_seqlens_q=cu, max_q_len=M, causal=True, as_lists=True)
+        out, lse = block_sparse_extend(q, kc, vc, lists, kv_len=kv_len, cu_seqlens_q=cu, max_q_len=M, causal=True, ...)"""
     return _sparse_rows(True, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
-                        k_scale, v_scale, q_len)
+                        k_scale, v_scale, q_len, cu_seqlens_q, max_q_len)
+
+
+def packed_row_groups(T: int, B: int, H: int, Hkv: int, Hl: int, max_q_len: int, block_size: int) -> Dict[str, int]:
+    """How the packed block_sparse_extend sizes its launch, from host values alone: extend_row_groups'
+    gh, and qg = min(64 // gh, block, M) rows per group.  An item of n rows holds pieces(n) = (n // block) * cpb +
+    ceil(n % block / qg) row groups per (unit, head chunk), cpb = ceil(min(M, block) / qg).  QP bounds their sum over every
+    cu_seqlens_q the device can sanitise (sum n_b <= T, n_b <= M): piece j of an item starts at row >= j * min(M, block) / cpb,
+    so k non-empty items holding J pieces own at least k + (J - k) * min(M, block) / cpb rows, whence
+        QP = min(B * pieces(M), k + (T - k) * cpb // min(M, block)),  k = min(B, T).
+    -> dict(gh, qg, head_chunks, pieces_per_block, pieces (QP), groups (QP * max(Hl, Hkv) * head_chunks workgroups per split),
+    rows16)."""
+    U = max(Hl, Hkv)
+    gu = H // U
+    HC = -(-gu // DECODE_MAX_ROWS)
+    gh = -(-gu // HC)
+    qmax = min(max_q_len, block_size)
+    qg = min(DECODE_MAX_ROWS // gh, qmax)
+    cpb = -(-qmax // qg)
+    per_item = (max_q_len // block_size) * cpb + -(-(max_q_len % block_size) // qg)
+    k = min(B, T)
+    QP = min(B * per_item, k + (T - k) * cpb // qmax)
+    rows = gh * qg
+    return dict(gh=gh, qg=qg, head_chunks=HC, pieces_per_block=cpb, pieces=QP, groups=QP * U * HC,
+                rows16=16 if rows <= 16 else (32 if rows <= 32 else 64))
 
 
 def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
-                 k_scale, v_scale, q_len=None):
+                 k_scale, v_scale, q_len=None, cu_seqlens_q=None, max_q_len=None):
     """block_sparse_decode (ext False) and block_sparse_extend: one argument layer, the C entries of either; with row counts
-    (q_len, extend only) the _ragged entries, which take them in front of the stream."""
+    (q_len, extend only) the _ragged entries, which take them in front of the stream; with cu_seqlens_q (extend only) the _packed
+    entries: q [T, H, D], T in front, M = max_q_len where Sq stood, cu_seqlens_q where q_len stood."""
     blk = _check_block("block-sparse extend" if ext else "block-sparse decode", block_size)
     _check_count("blocks_per_split", blocks_per_split, 1, optional=True)
+    q3 = q
+    q, Bp = _packed_view("q", q, cu_seqlens_q if ext else None, k, block_table)
+    if Bp is not None and q_len is not None:
+        raise ValueError("q_len belongs to a padded q: with cu_seqlens_q the rows of an item are cu_seqlens_q[b + 1] - cu_seqlens_q[b]")
+    if Bp is None and max_q_len is not None:
+        raise ValueError("max_q_len belongs to cu_seqlens_q")
     B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v, dims=(64, 128), block_table=block_table, blk=blk, kv8_ok=True)
+    if Bp is not None:      # Sq is M from here on: the rows of an item at most
+        T = Sq
+        cu, Sq = _check_packed("cu_seqlens_q", cu_seqlens_q, max_q_len, B, T)
     _check_scales(k, Hkv, k_scale=k_scale, v_scale=v_scale)
     NQ = -(-Sq // blk) if ext else 1
     if Sq > blk and not ext:
@@ -976,9 +1116,27 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
         _core._require_device(cols, counts)
     table, _held = _table_args(block_table, k)
     L = _lib.lib()
-    q = _core._as_bhsd(q)
     bps = 0 if blocks_per_split is None else int(blocks_per_split)
     need = ctypes.c_size_t(0)
+    kv8 = k.dtype == E4M3
+    if Bp is not None:
+        _core._require_device(cu)
+        q, cu = (q3 if _core._read_in_place(q3) else q3.contiguous()), cu.contiguous()
+        _lib.check(L.rsa_block_sparse_extend_packed_bytes(T, B, H, Hkv, Hl, Sq, D, blk, NK, bps, ctypes.byref(need), None),
+                   "rsa_block_sparse_extend_packed_bytes")
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+        out = torch.empty((T, H, D), dtype=q.dtype, device=dev)
+        lse = torch.empty((T, H), dtype=torch.float32, device=dev) if return_lse else None
+        entry = "rsa_block_sparse_extend_packed" + ("_kv8" if kv8 else "")
+        held = [_scale_arg(sc, Hkv, dev) for sc in (k_scale, v_scale)] if kv8 else []
+        with torch.cuda.device(dev):
+            _lib.check(getattr(L, entry)(T, B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
+                                         int(bool(causal)), scale, _t3(q), _core._t4(k), _core._t4(v), *table, cols.data_ptr(),
+                                         counts.data_ptr(), bps, ws.data_ptr(), need.value,
+                                         RsaOut4(out.data_ptr(), 0, out.stride(1), out.stride(0)), _ptr(lse),
+                                         *[t.data_ptr() for t in held], cu.data_ptr(), _core._stream()), entry)
+        return (out, lse) if return_lse else out
+    q = _core._as_bhsd(q)
     if ext:
         _lib.check(L.rsa_block_sparse_extend_bytes(B, H, Hkv, Hl, Sq, D, blk, NK, bps, ctypes.byref(need)),
                    "rsa_block_sparse_extend_bytes")
@@ -988,7 +1146,6 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
     out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
-    kv8 = k.dtype == E4M3
     entry = ("rsa_block_sparse_extend" if ext else "rsa_block_sparse_decode") + ("_ragged" if q_dev is not None else "") \
         + ("_kv8" if kv8 else "")
     held = [_scale_arg(sc, Hkv, dev) for sc in (k_scale, v_scale)] if kv8 else []

@@ -23,6 +23,7 @@
 // exp2 is __builtin_amdgcn_exp2f (v_exp_f32), the function of the attention kernels: exact at integer arguments.  Every fp32 sum has
 // a fixed order; histograms and weights are unsigned integer sums (at most 8192 weights of at most 2^18): two calls, the same bytes.
 #include "rsa_common.h"
+#include "rsa_packed.h"
 
 #include <math.h>
 #include <type_traits>
@@ -69,6 +70,13 @@ __device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
 // arguments and their code).  sel_row_count: q_len[b] clamped into [0, Sq]; Sq without RAG.
 __device__ __forceinline__ const int32_t* sel_q_len() { return nullptr; }
 __device__ __forceinline__ const int32_t* sel_q_len(const int32_t* q_len) { return q_len; }
+// The packed entry hands the pool kernel a second pointer behind the row counts: row_start, DEVICE int32
+// [B + 1], the first row of each item in q [T, H, D] (both written by pk_scan_kernel: sanitised).  Its other kernels are the ragged
+// instantiations over the sanitised row counts.
+__device__ __forceinline__ const int32_t* sel_q_len(const int32_t* q_len, const int32_t*) { return q_len; }
+__device__ __forceinline__ long sel_row_base(long) { return 0; }
+__device__ __forceinline__ long sel_row_base(long, const int32_t*) { return 0; }
+__device__ __forceinline__ long sel_row_base(long b, const int32_t*, const int32_t* row_start) { return row_start[b]; }
 template <bool RAG>
 __device__ __forceinline__ int sel_row_count(const int32_t* __restrict__ q_len, int b, int Sq) {
     if constexpr (RAG) return min(max(q_len[b], 0), Sq);
@@ -189,6 +197,7 @@ __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q
         for (int u = 0; (!RAG || rows > 0) && u < gl; ++u) {
             const unsigned short* base = static_cast<const unsigned short*>(q.ptr) + b * q.stride_b +
                                          (long)(hl * gl + u) * q.stride_h + r0 * q.stride_s;
+            if constexpr (sizeof...(Q) == 2) base += sel_row_base(b, q_len...) * q.stride_s;    // packed: the item's first row
             tot += sel_pool_block<Tag>(base, q.stride_s, rows, D, red) / cnt;
         }
         if (tid < D) qsum[job * D + tid] = tot;
@@ -583,8 +592,15 @@ static int sel_launch_select(int D, long rows, const sel_rows& r, const sel_top_
 
 // The pool kernel over the query jobs of r's rows and k_jobs key jobs behind them (none: k and kbar are not touched).
 static int sel_launch_pool(int dtype, int H, int D, rsa_tensor4 q, rsa_tensor4 k, long q_jobs, long k_jobs, const sel_rows& r,
-                           float* kbar, float* qsum, const int32_t* q_len, hipStream_t s) {
+                           float* kbar, float* qsum, const int32_t* q_len, hipStream_t s, const int32_t* row_start = nullptr) {
     const dim3 grid((unsigned)(q_jobs + k_jobs));
+    if (row_start) {        // the packed entry: q [T, H, D] behind stride_h and stride_s, item b from row row_start[b]
+        auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag, true, const int32_t*, const int32_t*>
+                                         : block_select_pool_kernel<fp16_tag, true, const int32_t*, const int32_t*>;
+        kernel<<<grid, SEL_NT, 0, s>>>(q, k, H, r.Hkv, r.Hl, r.Sq, r.Sk, D, r.blk, r.NQ, r.NK, q_jobs, r.kv_len, r.kv_valid, kbar, qsum,
+                                       q_len, row_start);
+        return rsa_launch_status();
+    }
     if (q_len) {
         auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag, true, const int32_t*>
                                          : block_select_pool_kernel<fp16_tag, true, const int32_t*>;
@@ -751,11 +767,25 @@ static int sel_default_splits(size_t rows, int NK, int D) {
     return max(1, min(min(by_blocks, by_rows), 64));
 }
 
+// The packed entry's batch: T rows of q, cu_seqlens_q and the scratch of 2 (B + 1) int32 the scan writes.
+struct SelPacked {
+    int T;
+    const int32_t* cu;
+    int32_t* items;
+};
+
 // The body of rsa_block_select_pooled and rsa_block_select_pooled_p (top_p NULL: top-k).  r: the call's arguments; Sk, kbar, qsum
-// and wkeys are set here.
+// and wkeys are set here.  pk: the packed entry (r.Sq = M; q_len is then set here, to the scan's row counts).
 static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const float* pooled_k, int score_splits, void* ws,
-                          size_t ws_bytes, sel_rows r, const sel_top_p* top_p, const int32_t* q_len, void* stream) {
+                          size_t ws_bytes, sel_rows r, const sel_top_p* top_p, const int32_t* q_len, void* stream,
+                          const SelPacked* pk = nullptr) {
     if ((top_p && !selp_budget_ok(*top_p)) || r.NK <= 0) return RSA_ERR_BAD_ARG;
+    if (pk) {
+        if (pk->T <= 0 || r.Sq <= 0 || r.Sq > pk->T || !pk->cu || !pk->items || B >= 0x7FFFFFFF) return RSA_ERR_BAD_ARG;
+        if ((reinterpret_cast<uintptr_t>(pk->cu) | reinterpret_cast<uintptr_t>(pk->items)) & 3) return RSA_ERR_BAD_ARG;
+        q.stride_b = 0;
+        q_len = pk->items + B + 1;
+    }
     size_t need = 0;
     const int st = sel_check(true, B, H, D, dtype, q, r, q_len, (long)r.NK * r.blk, &need);
     if (st != RSA_OK) return st;
@@ -770,7 +800,8 @@ static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const f
     unsigned* wkeys = reinterpret_cast<unsigned*>(qsum + q_jobs * D);   // [B, Hl, NQ, NK]
     r.Sk = r.NK * r.blk;        // the capacity of the cache
     r.kbar = pooled_k, r.qsum = qsum, r.wkeys = splits > 1 ? wkeys : nullptr;
-    int rc = sel_launch_pool(dtype, H, D, q, q, q_jobs, 0, r, nullptr, qsum, q_len, s);    // the pooled queries
+    if (pk) pk_scan_launch(pk->cu, B, pk->T, r.Sq, r.blk, 0, 0, pk->items, pk->items + B + 1, nullptr, s);
+    int rc = sel_launch_pool(dtype, H, D, q, q, q_jobs, 0, r, nullptr, qsum, q_len, s, pk ? pk->items : nullptr);    // the pooled queries
     if (rc != RSA_OK) return rc;
     if (splits > 1) {
         sel_with_lanes(D, [&](auto lanes) {
@@ -840,4 +871,20 @@ extern "C" int rsa_block_select_pooled_ragged(int B, int H, int Hkv, int Hl, int
     return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, 0, block, NQ,
                           NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores},
                           p16 == -1 ? nullptr : &p, q_len_dev, stream);
+}
+
+// ---- packed selection: q [T, H, D] with cu_seqlens_q.  rsa_block_select_pooled_ragged's argument list with
+// T in front, M = max_q_len where Sq stood (NQ = ceil(M / block)), and cu_seqlens_q_dev, DEVICE int32 [B + 1], with item_ws, DEVICE
+// int32 [2 (B + 1)] scratch, where q_len_dev stood.  One launch more than the ragged entry: the scan.
+extern "C" int rsa_block_select_pooled_packed(int T, int B, int H, int Hkv, int Hl, int max_q_len, int D, int dtype, int block, int NQ,
+                                              int NK, rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid,
+                                              int causal, int top_k, int keep_first, int keep_local, int score_splits, void* ws,
+                                              size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores,
+                                              int p16, float c, float* mass, const int32_t* cu_seqlens_q_dev, int32_t* item_ws,
+                                              void* stream) {
+    const sel_top_p p = {p16, c, mass};
+    const SelPacked pk = {T, cu_seqlens_q_dev, item_ws};
+    return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, max_q_len, 0,
+                          block, NQ, NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores},
+                          p16 == -1 ? nullptr : &p, nullptr, stream, &pk);
 }

@@ -41,7 +41,17 @@
 // row count -- the rows of the group (qn), the group's and each row's causal limit, the merge's row test -- and nowhere else: the
 // grid, the groups and the partials are the padded call's.  A group whose first row is at or beyond n_b leaves before it reads a
 // list entry, a table entry or a K/V byte; the merge writes its rows (0, -inf) unread.
+//
+// Packed (rsa_block_sparse_extend_packed, rsa_block_sparse_extend_packed_kv8) is a third family, PK (arguments:
+// DecPk, the extend kernels' and the packed batch behind them): q, out are [T, H, D] and item b is rows [s_b, s_b + n_b) of them.  A
+// one-workgroup scan (rsa_packed.h) sanitises cu_seqlens_q into row_start and piece_start, the exclusive prefix sums of the items'
+// row groups, at the head of the workspace.  Split workgroup (piece p, unit, hc) finds its item by a bounded binary search over
+// piece_start -- the live groups are the launch's first workgroups by construction, and p >= piece_start[B] leaves before it reads
+// a list entry, a table entry or a K/V byte -- and stands where the ragged group stands from there on: n_b for the row count, s_b
+// added to the row of q.  Partials are indexed by (compact group, split); the merge runs one thread group per row t of [0, T),
+// finds the item over row_start and writes rows outside every item (0, -inf) before it looks at a list row or a partial.
 #include "rsa_attn.h"
+#include "rsa_packed.h"
 
 #include <math.h>
 
@@ -91,8 +101,15 @@ template <typename A>
 struct DecRag : DecExt<A> {
     const int32_t* q_len;       // DEVICE [B], clamped into [0, Sq] in the kernel
 };
-template <typename A, bool EXT, bool RAG = false>
-using DecArgsFor = typename std::conditional<RAG, DecRag<A>, typename std::conditional<EXT, DecExt<A>, A>::type>::type;
+// The packed kernels' arguments: the extend kernels' and the packed batch behind them (Sq holds M, the rows of an item at most).
+template <typename A>
+struct DecPk : DecExt<A> {
+    const int32_t *row_start, *piece_start;     // DEVICE [B + 1] each, written by pk_scan_kernel: sanitised, ascending
+    int pk_B, pk_steps;                         // items; halvings of the search (ceil(log2 B))
+};
+template <typename A, bool EXT, bool RAG = false, bool PK = false>
+using DecArgsFor = typename std::conditional<
+    PK, DecPk<A>, typename std::conditional<RAG, DecRag<A>, typename std::conditional<EXT, DecExt<A>, A>::type>::type>::type;
 
 // The cache's element: the query's own 2-byte type (Tag = bf16_tag / fp16_tag), or e4m3 codes (kv8_tag<query type>).
 template <typename QTag>
@@ -165,10 +182,10 @@ __device__ __forceinline__ s16x4 dec_tr_read(const unsigned char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
-template <typename CTag, int D, int MT, bool EXT, bool RAG = false>
+template <typename CTag, int D, int MT, bool EXT, bool RAG = false, bool PK = false>
 __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
-    DecArgsFor<typename DecCache<CTag>::Args, EXT, RAG> a) {
-    static_assert(EXT || !RAG, "row counts belong to the extend kernels");
+    DecArgsFor<typename DecCache<CTag>::Args, EXT, RAG, PK> a) {
+    static_assert((EXT || !(RAG || PK)) && !(RAG && PK), "row counts belong to the extend kernels, from q_len or from cu_seqlens_q");
     using Cache = DecCache<CTag>;
     using Tag = typename Cache::Q;      // the type of q, of the MFMA operands and of the output
     using KT = typename Cache::elem;
@@ -194,13 +211,24 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
     // the workgroup's rows: heads [h0, h0 + hn) of the unit x query rows [q0, q0 + qn) of the call, row = head * qw + query row
     // in the group; list row (b * Hl + hl) * NQ + qb.  Decode: the whole unit (the arithmetic below, spelled as it always was).
     int ext_unit = 0, ext_b = 0, qb = 0, h0 = 0, hn = 0, q0 = 0, qn = 0, qw = 1, nq = 1, nrow = a.Sq;
+    int pk_row0 = 0;                        // packed: the item's first row of q
     long gid = blockIdx.x;                  // the row group: what the partials and the merge are indexed by
     if constexpr (EXT) {
         int g = blockIdx.x;
         const int hc = g % a.g.HC;
         g /= a.g.HC;
         int qc;
-        if constexpr (RAG) {
+        if constexpr (PK) {
+            // packed: blockIdx.x = (piece * U + unit) * HC + hc over the QP pieces the host's bound allows.  The live pieces are
+            // [0, piece_start[B]): the rest leave here.  Everything below is uniform: scalar loads, scalar registers.
+            ext_unit = g % a.U;
+            const int piece = g / a.U;
+            if (piece >= a.piece_start[a.pk_B]) return;
+            ext_b = pk_find(a.piece_start, a.pk_B, a.pk_steps, piece);
+            qc = piece - a.piece_start[ext_b];
+            pk_row0 = a.row_start[ext_b];
+            nrow = min(a.row_start[ext_b + 1] - pk_row0, a.Sq);
+        } else if constexpr (RAG) {
             // ragged: the workgroups are dealt query chunk by query chunk, (qc, b, unit, hc).  An item's live groups are its first
             // chunks, so the live groups of a batch of short items are the launch's first workgroups, side by side on the chip; in
             // the groups' own order they sit QC * HC apart and pile up on the few compute units that stride reaches.
@@ -222,7 +250,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
         q0 = qb * a.blk + (qc - qb * a.g.cpb) * qw;
         if constexpr (RAG) nrow = min(max(a.q_len[ext_b], 0), a.Sq);     // the batch item's rows: the causal offset counts from them
         qn = min(qw, min((qb + 1) * a.blk, nrow) - q0);
-        if (RAG && qn <= 0) return;         // (uniform) a group of padding rows: the merge writes them without a partial
+        if ((RAG || PK) && qn <= 0) return;     // (uniform) a group of padding rows: the merge writes them without a partial
         h0 = hc * a.g.gh;
         hn = min(a.g.gh, a.H / a.U - h0);
     }
@@ -261,6 +289,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
             qrow = ok ? q0 + qr : 0;
         }
         const unsigned short* qp = a.q + (long)b * a.qsb + (long)(unit * gu + hu) * a.qsh + (long)qrow * a.qss + 8 * lh;
+        if constexpr (PK) qp = a.q + (long)(unit * gu + hu) * a.qsh + (long)(pk_row0 + qrow) * a.qss + 8 * lh;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const s16x8 f = rsa_q_frag<Tag>(qp + 32 * ks, ok, a.qk_scale);
@@ -485,17 +514,32 @@ struct DecMergeArgs8 : DecMergeArgs {
 };
 
 // D / 4 threads per output row, four channels each; the splits in ascending order.
-template <typename CTag, int D, bool EXT, bool RAG = false>
+template <typename CTag, int D, bool EXT, bool RAG = false, bool PK = false>
 __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
-    DecArgsFor<typename std::conditional<DecCache<CTag>::kv8, DecMergeArgs8, DecMergeArgs>::type, EXT, RAG> a) {
+    DecArgsFor<typename std::conditional<DecCache<CTag>::kv8, DecMergeArgs8, DecMergeArgs>::type, EXT, RAG, PK> a) {
     using Tag = typename DecCache<CTag>::Q;
     constexpr int TPR = D / 4;
     const long g = (long)blockIdx.x * DEC_NT + threadIdx.x;
     const long row = g / TPR;
     const int c = (int)(g % TPR);
     if (row >= a.rows) return;
-    const int qrow = (int)(row % a.Sq), h = (int)((row / a.Sq) % a.H);
-    const long b = row / ((long)a.Sq * a.H);
+    int qrow = (int)(row % a.Sq), h = (int)((row / a.Sq) % a.H);
+    long b = row / ((long)a.Sq * a.H);
+    long orow = qrow;           // the row's place in out (behind b * osb: 0 in the packed call)
+    int pk_piece0 = 0;
+    if constexpr (PK) {         // row = t * H + h over q's T rows: the item by search, the row's index in it, or no item at all
+        h = (int)(row % a.H);
+        orow = row / a.H;
+        b = pk_find(a.row_start, a.pk_B, a.pk_steps, (int)orow);
+        const int s0 = a.row_start[b];
+        qrow = (int)orow - s0;
+        if (qrow < 0 || qrow >= min(a.row_start[b + 1] - s0, a.Sq)) {      // 0 / -inf, no list row and no partial read
+            *reinterpret_cast<uint2*>(a.out + (long)h * a.osh + orow * a.oss + 4 * c) = make_uint2(0u, 0u);
+            if (a.lse && c == 0) a.lse[row] = -INFINITY;
+            return;
+        }
+        pk_piece0 = a.piece_start[b];
+    }
     const int gu = a.H / a.U, unit = h / gu, rr = (h % gu) * a.Sq + qrow;
     long p0 = ((b * a.U + unit) * a.nsplit) * a.R16 + rr;       // decode: the unit's partials, head-major rows
     long lrow = b * a.Hl + unit / (a.U / a.Hl);
@@ -508,7 +552,8 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
             }
         }
         const int hu = h % gu, hc = hu / a.g.gh, qb = qrow / a.qblk, qi = qrow - qb * a.qblk, qcl = qi / a.g.qg;
-        const long grp = ((b * a.U + unit) * a.g.QC + qb * a.g.cpb + qcl) * a.g.HC + hc;
+        long grp = ((b * a.U + unit) * a.g.QC + qb * a.g.cpb + qcl) * a.g.HC + hc;
+        if constexpr (PK) grp = ((long)(pk_piece0 + qb * a.g.cpb + qcl) * a.U + unit) * a.g.HC + hc;    // the compact group
         p0 = (grp * a.nsplit) * a.R16 + (hu - hc * a.g.gh) * a.g.qg + (qi - qcl * a.g.qg);
         lrow = lrow * a.g.NQ + qb;
     }
@@ -543,7 +588,7 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
     uint2 pk;
     pk.x = (unsigned)Elem<Tag>::from_f32(r[0]) | ((unsigned)Elem<Tag>::from_f32(r[1]) << 16);
     pk.y = (unsigned)Elem<Tag>::from_f32(r[2]) | ((unsigned)Elem<Tag>::from_f32(r[3]) << 16);
-    *reinterpret_cast<uint2*>(a.out + b * a.osb + (long)h * a.osh + (long)qrow * a.oss + 4 * c) = pk;
+    *reinterpret_cast<uint2*>(a.out + (PK ? 0 : b * a.osb) + (long)h * a.osh + orow * a.oss + 4 * c) = pk;
     if (a.lse && c == 0) a.lse[row] = any ? (ms + __builtin_amdgcn_logf(lt)) * 0.69314718055994530942f : -INFINITY;
 }
 
@@ -615,6 +660,69 @@ static int ext_plan(int B, int H, int Hkv, int Hl, int Sq, int D, int block, int
     return RSA_OK;
 }
 
+// The packed call: T rows of q hold B items of at most M rows each.
+struct DecPacked {
+    int T, B;
+    const int32_t* cu;          // DEVICE [B + 1]
+};
+
+// The packed call's plan, from host values alone: the extend call's row groups with M for Sq (qg = min(64 / gh, block, M)), and
+// QP, the pieces (row groups per (unit, head chunk)) the grid holds.  An item of n rows has pk_pieces(n) of them; piece j of an
+// item starts at row (j / cpb) * block + (j % cpb) * qg >= j * qmax / cpb (qmax = min(M, block); cpb * qg >= qmax), so k non-empty
+// items that hold J pieces in all own at least k + (J - k) * qmax / cpb <= T rows: J <= k + (T - k) * cpb / qmax, which grows with
+// k <= min(B, T).  QP is that bound, capped by B * pk_pieces(M).  p->groups = QP * U * HC; p->bytes includes the head of the
+// workspace, row_start and piece_start.
+static int pk_plan(int T, int B, int H, int Hkv, int Hl, int M, int D, int block, int NK, int blocks_per_split, DecPlan* p,
+                   long* qp_out = nullptr) {
+    if (T <= 0 || M <= 0 || M > T) return RSA_ERR_BAD_ARG;
+    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
+    if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
+    if (NK > DEC_MAX_NK || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
+    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
+    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
+    if (B >= 0x7FFFFFFF) return RSA_ERR_UNSUPPORTED;
+    p->U = Hl > Hkv ? Hl : Hkv;
+    const int gu = H / p->U;
+    DecGroups& g = p->g;
+    g.HC = (gu + DEC_MAX_ROWS - 1) / DEC_MAX_ROWS;
+    g.gh = (gu + g.HC - 1) / g.HC;
+    const int qmax = M < block ? M : block;
+    g.qg = DEC_MAX_ROWS / g.gh < qmax ? DEC_MAX_ROWS / g.gh : qmax;
+    g.NQ = (int)(((long)M + block - 1) / block);
+    g.cpb = (qmax + g.qg - 1) / g.qg;
+    g.QC = pk_pieces(M, block, g.qg, g.cpb);        // (of an item of M rows: the kernels do not read it)
+    const long k = B < T ? B : T;
+    long qp = k + ((long)T - k) * g.cpb / qmax;
+    if (qp > (long)B * g.QC) qp = (long)B * g.QC;
+    const int rows = g.gh * g.qg;
+    p->MT = rows <= 16 ? 1 : (rows <= 32 ? 2 : 4);
+    if (qp > 0x7FFFFFFFl / ((long)p->U * g.HC)) return RSA_ERR_UNSUPPORTED;
+    if ((long)H > (0x7FFFFFFFl * (long)DEC_NT) / ((long)T * (D / 4))) return RSA_ERR_UNSUPPORTED;
+    p->groups = qp * p->U * g.HC;
+    if (blocks_per_split > 0) {
+        p->C = blocks_per_split < NK ? blocks_per_split : NK;
+    } else {
+        p->C = p->groups < EXT_FILL_GROUPS ? (DEC_SPLIT < NK ? DEC_SPLIT : NK) : NK;
+    }
+    p->nsplit = (NK + p->C - 1) / p->C;
+    p->bytes = pk_head_bytes(2 * ((long)B + 1)) + (size_t)p->groups * p->nsplit * (16 * p->MT) * ((size_t)D + 2) * sizeof(float);
+    if (qp_out) *qp_out = qp;
+    return RSA_OK;
+}
+
+extern "C" int rsa_block_sparse_extend_packed_bytes(int T, int B, int H, int Hkv, int Hl, int max_q_len, int D, int block, int NK,
+                                                    int blocks_per_split, size_t* bytes, int64_t* pieces) {
+    if (!bytes) return RSA_ERR_BAD_ARG;
+    DecPlan p;
+    long qp = 0;
+    const int st = pk_plan(T, B, H, Hkv, Hl, max_q_len, D, block, NK, blocks_per_split, &p, &qp);
+    if (st == RSA_OK) {
+        *bytes = p.bytes;
+        if (pieces) *pieces = qp;
+    }
+    return st;
+}
+
 extern "C" int rsa_block_sparse_decode_bytes(int B, int H, int Hkv, int Hl, int Sq, int D, int NK, int blocks_per_split,
                                              size_t* bytes) {
     if (!bytes) return RSA_ERR_BAD_ARG;
@@ -634,7 +742,8 @@ extern "C" int rsa_block_sparse_extend_bytes(int B, int H, int Hkv, int Hl, int 
 }
 
 template <typename Tag, int D, bool EXT, typename A0, typename G0>
-static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, const int32_t* q_len, int MT, dim3 grid, hipStream_t s) {
+static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, const int32_t* q_len, const DecPacked* pk, int32_t* pk_head,
+                        int MT, dim3 grid, hipStream_t s) {
     DecArgsFor<A0, EXT> a;
     DecArgsFor<G0, EXT> g;
     static_cast<A0&>(a) = a0;
@@ -646,6 +755,22 @@ static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, const i
     const long threads = g.rows * (D / 4);
     const dim3 mgrid((unsigned)((threads + DEC_NT - 1) / DEC_NT));
     if constexpr (EXT) {
+        if (pk) {           // the packed instantiations behind the scan of cu_seqlens_q: three launches
+            DecPk<A0> ap;
+            DecPk<G0> gp;
+            static_cast<DecExt<A0>&>(ap) = a;
+            static_cast<DecExt<G0>&>(gp) = g;
+            ap.row_start = gp.row_start = pk_head;
+            ap.piece_start = gp.piece_start = pk_head + pk->B + 1;
+            ap.pk_B = gp.pk_B = pk->B;
+            ap.pk_steps = gp.pk_steps = pk_steps(pk->B);
+            pk_scan_launch(pk->cu, pk->B, pk->T, a0.Sq, a0.blk, gr.qg, gr.cpb, pk_head, nullptr, pk_head + pk->B + 1, s);
+            if (MT == 1) decode_split_kernel<Tag, D, 1, true, false, true><<<grid, DEC_NT, 0, s>>>(ap);
+            else if (MT == 2) decode_split_kernel<Tag, D, 2, true, false, true><<<grid, DEC_NT, 0, s>>>(ap);
+            else decode_split_kernel<Tag, D, 4, true, false, true><<<grid, DEC_NT, 0, s>>>(ap);
+            decode_merge_kernel<Tag, D, true, false, true><<<mgrid, DEC_NT, 0, s>>>(gp);
+            return;
+        }
         if (q_len) {        // the ragged instantiations
             DecRag<A0> ar;
             DecRag<G0> gr2;
@@ -666,10 +791,10 @@ static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, const i
 }
 
 template <typename Tag, int D, typename A, typename G>
-static void dec_launch(bool ext, const A& a, const G& g, const DecGroups& gr, const int32_t* q_len, int MT, dim3 grid,
-                       hipStream_t s) {
-    if (ext) dec_launch2<Tag, D, true>(a, g, gr, q_len, MT, grid, s);
-    else dec_launch2<Tag, D, false>(a, g, gr, nullptr, MT, grid, s);
+static void dec_launch(bool ext, const A& a, const G& g, const DecGroups& gr, const int32_t* q_len, const DecPacked* pk,
+                       int32_t* pk_head, int MT, dim3 grid, hipStream_t s) {
+    if (ext) dec_launch2<Tag, D, true>(a, g, gr, q_len, pk, pk_head, MT, grid, s);
+    else dec_launch2<Tag, D, false>(a, g, gr, nullptr, nullptr, nullptr, MT, grid, s);
 }
 
 // An e4m3 cache view as the loads need it: K is read 8 bytes a lane, V 16 (strides in elements = bytes).
@@ -679,13 +804,15 @@ static int dec_check_cache8(const rsa_tensor4& t, int align) {
     return RSA_OK;
 }
 
-// All six entries: kv8 = the cache holds e4m3 codes and the two scale arrays are there; ext = the extend call (any Sq, row groups);
-// q_len_dev = the ragged extend call's rows per batch item (null: Sq; never given without ext).
+// All eight entries: kv8 = the cache holds e4m3 codes and the two scale arrays are there; ext = the extend call (any Sq, row groups);
+// q_len_dev = the ragged extend call's rows per batch item (null: Sq; never given without ext); pk = the packed call's batch (null:
+// a padded q; never given without ext or with q_len_dev): Sq is then M, q / out are read through stride_h and stride_s (the row's).
 static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
                    const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
                    rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* cols,
                    const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
-                   const float* k_scale, const float* v_scale, const int32_t* q_len_dev, void* stream) {
+                   const float* k_scale, const float* v_scale, const int32_t* q_len_dev, void* stream,
+                   const DecPacked* pk = nullptr) {
     if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || Sk <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
     if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
@@ -696,9 +823,11 @@ static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, in
     if ((!ext && Sq > block) || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
     if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
     DecPlan p;
-    const int st = ext ? ext_plan(B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p)
-                       : dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
+    const int st = pk    ? pk_plan(pk->T, B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p)
+                   : ext ? ext_plan(B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p)
+                         : dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
     if (st != RSA_OK) return st;
+    if (pk && (!pk->cu || (reinterpret_cast<uintptr_t>(pk->cu) & 3))) return RSA_ERR_BAD_ARG;
     if (!cols || !counts || !ws || !out.ptr) return RSA_ERR_BAD_ARG;
     if (rsa_check_tensor(q) != RSA_OK) return RSA_ERR_BAD_ARG;
     if (kv8) {
@@ -739,7 +868,9 @@ static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, in
     a.H = H; a.Hkv = Hkv; a.Hl = Hl; a.U = p.U; a.Sq = Sq; a.Sk = Sk; a.NK = NK; a.blk = block; a.causal = causal != 0;
     a.C = p.C; a.nsplit = p.nsplit; a.R16 = 16 * p.MT;
     a.qk_scale = (float)(sm_scale * 1.44269504);    // (as rsa_block_sparse_plain_fwd)
-    a.ws_o = static_cast<float*>(ws);
+    // (packed: row_start and piece_start stand at the head of the workspace, the partials 16-byte aligned behind them)
+    int32_t* const pk_head = pk ? static_cast<int32_t*>(ws) : nullptr;
+    a.ws_o = pk ? reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + pk_head_bytes(2 * ((long)B + 1))) : static_cast<float*>(ws);
     a.ws_ml = reinterpret_cast<float2*>(a.ws_o + parts * a.R16 * D);
     a.k_scale = k_scale;
     a.v_scale = v_scale;
@@ -754,24 +885,25 @@ static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, in
     g.counts = counts;
     g.Hl = Hl; g.NK = NK; g.C = p.C;
     g.H = H; g.U = p.U; g.Sq = Sq; g.nsplit = p.nsplit; g.R16 = a.R16;
-    g.rows = (long)B * H * Sq;
+    g.rows = pk ? (long)pk->T * H : (long)B * H * Sq;
+    if (pk) a.qsb = 0, g.osb = 0;
     const dim3 grid((unsigned)p.groups, (unsigned)p.nsplit);
     const DecArgs& a2 = a;              // the 2-byte kernels take the base structs
     const DecMergeArgs& g2 = g;
     if (kv8) {
         if (dtype == RSA_BF16) {
-            if (D == 128) dec_launch<kv8_tag<bf16_tag>, 128>(ext, a, g, p.g, q_len_dev, p.MT, grid, s);
-            else dec_launch<kv8_tag<bf16_tag>, 64>(ext, a, g, p.g, q_len_dev, p.MT, grid, s);
+            if (D == 128) dec_launch<kv8_tag<bf16_tag>, 128>(ext, a, g, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
+            else dec_launch<kv8_tag<bf16_tag>, 64>(ext, a, g, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
         } else {
-            if (D == 128) dec_launch<kv8_tag<fp16_tag>, 128>(ext, a, g, p.g, q_len_dev, p.MT, grid, s);
-            else dec_launch<kv8_tag<fp16_tag>, 64>(ext, a, g, p.g, q_len_dev, p.MT, grid, s);
+            if (D == 128) dec_launch<kv8_tag<fp16_tag>, 128>(ext, a, g, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
+            else dec_launch<kv8_tag<fp16_tag>, 64>(ext, a, g, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
         }
     } else if (dtype == RSA_BF16) {
-        if (D == 128) dec_launch<bf16_tag, 128>(ext, a2, g2, p.g, q_len_dev, p.MT, grid, s);
-        else dec_launch<bf16_tag, 64>(ext, a2, g2, p.g, q_len_dev, p.MT, grid, s);
+        if (D == 128) dec_launch<bf16_tag, 128>(ext, a2, g2, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
+        else dec_launch<bf16_tag, 64>(ext, a2, g2, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
     } else {
-        if (D == 128) dec_launch<fp16_tag, 128>(ext, a2, g2, p.g, q_len_dev, p.MT, grid, s);
-        else dec_launch<fp16_tag, 64>(ext, a2, g2, p.g, q_len_dev, p.MT, grid, s);
+        if (D == 128) dec_launch<fp16_tag, 128>(ext, a2, g2, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
+        else dec_launch<fp16_tag, 64>(ext, a2, g2, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
     }
     return rsa_launch_status();
 }
@@ -842,4 +974,34 @@ extern "C" int rsa_block_sparse_extend_ragged_kv8(int B, int H, int Hkv, int Hl,
     return dec_run(true, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
                    block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale,
                    q_len_dev, stream);
+}
+
+// ---- packed extend: q [T, H, D] with cu_seqlens_q.  The extend entries' argument lists with T in front, M
+// = max_q_len where Sq stood, and cu_seqlens_q_dev, DEVICE int32 [B + 1], in front of the stream; q and out are read through
+// stride_h and stride_s (a row of the packed tensor), stride_b is not read.
+extern "C" int rsa_block_sparse_extend_packed(int T, int B, int H, int Hkv, int Hl, int max_q_len, int Sk, int D, int dtype, int block,
+                                              int NK, const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale,
+                                              rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table,
+                                              int64_t table_stride_b, int num_pages, const int32_t* cols, const int32_t* counts,
+                                              int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
+                                              const int32_t* cu_seqlens_q_dev, void* stream) {
+    const DecPacked pk = {T, B, cu_seqlens_q_dev};
+    q.stride_b = 0, out.stride_b = 0;
+    return dec_run(true, false, B, H, Hkv, Hl, max_q_len, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
+                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr,
+                   nullptr, stream, &pk);
+}
+
+extern "C" int rsa_block_sparse_extend_packed_kv8(int T, int B, int H, int Hkv, int Hl, int max_q_len, int Sk, int D, int dtype,
+                                                  int block, int NK, const int32_t* kv_len_dev, int kv_valid, int causal,
+                                                  double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                                                  const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                                                  const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
+                                                  size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale,
+                                                  const float* v_scale, const int32_t* cu_seqlens_q_dev, void* stream) {
+    const DecPacked pk = {T, B, cu_seqlens_q_dev};
+    q.stride_b = 0, out.stride_b = 0;
+    return dec_run(true, true, B, H, Hkv, Hl, max_q_len, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
+                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale,
+                   nullptr, stream, &pk);
 }
