@@ -116,7 +116,9 @@ int rsa_abi_check(int header_version, size_t sizeof_rsa_buffers, size_t sizeof_r
  * split over its idle slots.  Both change the summation order of the rows they touch, so a head-sharded run (3 heads per
  * rank) and the unsharded one (24 heads) agree on those rows within rounding, not byte for byte.  on != 0 plans both per
  * head (16 text pieces, no tail split): every rank then produces exactly the bytes the unsharded call produces for its
- * heads, at 3-5 % of K5 on short grids.  Returns the previous value. */
+ * heads, at 3-5 % of K5 on short grids.  Returns the previous value.
+ * Nothing else looks at the launch: the selection pass is per (b, h) with or without the switch -- K4 picks between its two
+ * forms (which differ in bits) from NBv alone -- so mask, lists, R and comp of a rank are the unsharded call's bytes always. */
 int rsa_set_shard_invariant(int on);
 
 /* Bytes needed for each rsa_buffers member, written in member order into sizes[RSA_NUM_BUFFERS], and their sum

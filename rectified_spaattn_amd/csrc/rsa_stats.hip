@@ -1119,7 +1119,8 @@ __global__ __launch_bounds__(D * 2) void compensation_split_kernel(const float* 
         if (i < NBv) comp[((long)bh * NBv + i) * D + 32 * wv + r] = acc[e];
     }
 }
-int g_rsa_k4_split = 1;   // tuning key "k4_split": 0 = the fp32 chain form (A/B, tests)
+int g_rsa_k4_split = 1;   // tuning key "k4_split": 0 = the fp32 chain form (A/B, tests), 2 = the split form, 1 = by NBv (compensation_b)
+constexpr int RSA_K4_SPLIT_MIN_NBV = 256;   // rows from this many visual blocks take the split form: per head, never per launch
 
 // =====================================================================================================
 // stand-alone GAPR mask for estimate_pr_gain callers: mask = !(|s| > |aq.kbar| + |qbar.ak|)
@@ -1396,9 +1397,15 @@ static int compensation_b(const rsa_layout* l, int blk, const rsa_buffers* buf, 
     const int L = l->NBv + (l->n_txt > 0 ? 1 : 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
     dim3 grid((l->NBv + 31) / 32, l->B * l->H);
-    // (measured, HunyuanVideo 720p: 24 heads 66.8 -> 58.8 us, 3 heads 30.7 -> 34.3 us: the split form only where the grid fills the chip;
-    // k4_split = 2 forces it)
-    if (g_rsa_k4_split == 2 || (g_rsa_k4_split == 1 && (long)grid.x * grid.y >= 512)) {
+    // The two forms differ in bits (split: 2^-15 sum |w| |vbar|, chain: fp32-exact), and comp is promised byte for byte to a rank
+    // that holds a slice of the heads or of the batch: the form is a function of the (b, h) problem alone -- NBv -- and never of B,
+    // H or the grid.  Rows of 256 blocks and more take the split form, shorter ones the chain form (k4_split = 2 / 0 force one): the
+    // full launch of every bench workload keeps the form the grid rule gave it (Flux 4096^2 moves to the split form, a tie).
+    // Measured, chain -> split (profiles/k4_form_rule.md): HunyuanVideo 720p (NBv 900) 24 heads 70.3 -> 59.0 us, Wan2.1 720p (591) 40
+    // heads 48.4 -> 42.6, CogVideoX 768p (330, head dim 64) 48 heads 26.2 -> 24.0, Flux 4096^2 (512) 24 heads 31.2 -> 30.4; a launch
+    // that leaves the chip idle pays for it -- 3 heads of the HunyuanVideo shape 30.9 -> 34.4 us, which the grid rule this replaces
+    // (split from 512 workgroups) spared it.
+    if (g_rsa_k4_split == 2 || (g_rsa_k4_split == 1 && l->NBv >= RSA_K4_SPLIT_MIN_NBV)) {
         if (l->D == 128) compensation_split_kernel<128><<<grid, 256, 0, s>>>(buf->w, buf->vbar, buf->comp, l->NBv, L, l->NB_total);
         else compensation_split_kernel<64><<<grid, 128, 0, s>>>(buf->w, buf->vbar, buf->comp, l->NBv, L, l->NB_total);
         return rsa_launch_status();

@@ -129,3 +129,20 @@ def teacache_sequence(seed, n, drift, shape):
             synth.normal(seed, i + 1, shape).astype(np.float32))
         seq.append(x.clone())
     return seq
+
+
+def tail_blocks(H, spec):
+    """[H, NBv] bool: the query blocks a launch of H heads (B * H for a batch) walks in pieces -- the tail split of
+    rsa_attn.hip::rsa_plan_walk for a layout WITHOUT text rows, 128-token blocks (text pieces take slots from the tail's)."""
+    NBp = (spec.NBv + 7) // 8 * 8
+    n_sparse = H * NBp
+    full, T = divmod(n_sparse, 512)
+    touched = torch.zeros(H, spec.NBv, dtype=torch.bool)
+    if full < 1 or T == 0 or min(512 // T, 4) < 2:
+        return touched
+    for vv in range(full * 512, n_sparse):
+        h, j = divmod(vv, NBp)
+        qb = (j & 7) * (NBp // 8) + (j >> 3)
+        if qb < spec.NBv:
+            touched[h, qb] = True
+    return touched

@@ -1,13 +1,29 @@
 """Head sharding: a rank that holds heads [h0, h0+n) computes, for those heads, exactly the unsharded call's
 bitmask, kept lists, R and compensation -- always (no statistic crosses heads: softmax, sort and the cumulative rule are per
 (b, h, query block); top_k, p and the neighbour matrix are head-independent) -- and exactly its O wherever K5 planned the row's
-walk the same way in both launches.  Two plans depend on the size of the launch (rsa_attn.hip::rsa_plan_walk): the tail split
-(which query blocks of the last, partial generation are walked in pieces) and the piece count of the dense text rows (32 on
-short grids, 16 otherwise); the rows they touch agree within rounding.  `parallel.set_shard_invariant(True)` (C:
-rsa_set_shard_invariant) plans both per head: byte-identical O everywhere, which the second test pins at a shape where one
-side splits.  The first test's shape (8 x 48 = 384 workgroups) is below one generation: nothing is ever split there."""
+walk the same way in both launches; everywhere under `parallel.set_shard_invariant(True)` (C: rsa_set_shard_invariant).
+
+Three decisions have looked at the size of the launch (B x H: a slice of the batch is a shard too), and a test pins the promise
+only where the full call stands on one side of the threshold and the shard on the other:
+
+1. K4's form (rsa_stats.hip::compensation_b): the split kernel from 512 workgroups, the fp32 chain below -- different bits in
+   comp and O, outside the switch.  Decided from NBv alone since tests/test_gpu_shard_cross.py crossed it (512 workgroups
+   against 64 and 128, heads and a batch item, also through the one-call entry).  The shapes of this file, of
+   test_gpu_block64.py::test_block64_shard_invariance and of test_gpu_walk_order.py::test_head_shard_with_the_order_on give 16
+   to 32 workgroups on both sides: their comp assertions never saw the threshold.
+2. The piece count of the dense text rows (rsa_attn.hip::rsa_plan_walk: 32 at most on grids of fewer than 8 generations, 16
+   otherwise; it matters from 272 key blocks): the rows agree within rounding, byte for byte under the switch.  Crossed by
+   test_gpu_shard_cross.py::test_text_piece_cap_across_eight_generations only.
+3. The tail split (rsa_plan_walk: which query blocks of the last, partial generation are walked in pieces): within rounding on
+   the blocks either launch splits, byte for byte under the switch.  Crossed for the 2-byte 128-block kernel by the second test
+   here (8 x 72 = 576 workgroups against 288), for the e4m3 and pv kernels (own policy, rsa_attn_fp8_kernel.hip) by
+   test_gpu_shard_cross.py::test_fp8_kernels_where_one_side_splits_its_tail.
+
+The first test's shape (8 x 48 = 384 workgroups) is below one generation: nothing is ever split there."""
 import pytest
 import torch
+
+import helpers
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -39,22 +55,6 @@ def test_head_shard_equals_full_run(layout):
         assert torch.equal(torch.where(valid, pb["cols"], -1), torch.where(valid, fb["cols"][h0:h0 + hl], -1))
 
 
-def _tail_blocks(H, spec):
-    """[H, NBv] bool: the query blocks a launch of H heads walks in pieces (the tail split of rsa_attn.hip::rsa_plan_walk)."""
-    NBp = (spec.NBv + 7) // 8 * 8
-    n_sparse = H * NBp
-    full, T = divmod(n_sparse, 512)
-    touched = torch.zeros(H, spec.NBv, dtype=torch.bool)
-    if full < 1 or T == 0 or min(512 // T, 4) < 2:
-        return touched
-    for vv in range(full * 512, n_sparse):
-        h, j = divmod(vv, NBp)
-        qb = (j & 7) * (NBp // 8) + (j >> 3)
-        if qb < spec.NBv:
-            touched[h, qb] = True
-    return touched
-
-
 def test_head_shard_where_one_side_splits_its_tail():
     """8 heads x 72 query blocks = 576 workgroups: the unsharded launch splits the 64 walks of its second generation 4 ways;
     a rank with 4 heads (288 workgroups, less than a generation) splits nothing.  Default: the selection results and every
@@ -68,8 +68,8 @@ def test_head_shard_where_one_side_splits_its_tail():
     dev = torch.device(DEV)
     q, k, v = gen_qkv(H, 0, S, S, D, dev, seed=23)
     spec = _core.LayoutSpec.wan(S, 2)
-    touched_full = _tail_blocks(H, spec)
-    assert int(touched_full.sum()) == 64 and int(_tail_blocks(H // world, spec).sum()) == 0
+    touched_full = helpers.tail_blocks(H, spec)
+    assert int(touched_full.sum()) == 64 and int(helpers.tail_blocks(H // world, spec).sum()) == 0
     for invariant in (False, True):
         prev = parallel.set_shard_invariant(invariant)
         try:
