@@ -595,6 +595,52 @@ int rsa_kv8_append_packed(int B, int Hkv, int T, int Sk, int D, int dtype, int b
                           const int32_t* start_dev, int start, const int32_t* cu_seqlens_dev, int32_t* item_ws,
                           const float* k_scale, const float* v_scale, void* stream);
 
+/* ---- block selection by per-channel key BOUNDS: a min/max cache and the selection from it (found by symbol: the header version
+ * stays 6.1).  The pooled selection scores a key block by qs . mean(k); this one by the upper bound of
+ * qs . k over every key the block could hold (Quest's criterion), so one aligned key among many others cannot hide:
+ *     t[b, hl, i, j] = sum over d of max(qs_d * mn_d, qs_d * mx_d),
+ * qs the pooled query of rsa_block_select (the sum over the list head's query heads, ascending, of each head's fp32 row mean), mn /
+ * mx the per-channel minimum / maximum of the keys of block j of (b, K/V head) below len_b.  fp32 in a fixed order: per group of
+ * four channels the terms -- each the larger of two separately rounded products, no fused form -- are added as ((x + y) + z) + w,
+ * the D / 4 partial sums meet over xor strides 1 .. D / 8.  One decode step is rsa_pool_key_bounds (the blocks the step touched) ->
+ * rsa_block_select_bound -> rsa_block_sparse_decode: all on the device, no host read, capturable in one graph.
+ *
+ * rsa_pool_key_bounds / rsa_pool_key_bounds_kv8 take the argument lists of rsa_pool_keys / rsa_pool_keys_kv8 and their contract
+ * word for word -- the forms of k, the limits, the written set (exactly the blocks start_b / block <= j < ceil(len_b / block), no
+ * other byte), the table rule, workgroups_per_head, the refusals and their order -- with out fp32 [B, Hkv, NK, 2, D] contiguous,
+ * 16-byte aligned: out[b, hk, j, 0, :] the minimum and out[b, hk, j, 1, :] the maximum over the keys of block j below len_b.  A
+ * table entry outside [0, num_pages) gives zeros, min and max alike.  kv8: min and max over float(code), each multiplied once by
+ * k_scale[hk] (positive: the order is kept).  Keys at or beyond len_b are never loaded; keys below it are taken to be finite (a NaN
+ * there gives an unspecified value and forms no address).  min and max are exact and order-free: every workgroups_per_head gives
+ * the same values, two calls the same bytes.  One pass over K, one launch.
+ *
+ * rsa_block_select_bound takes the argument list of rsa_block_select_pooled_ragged (p16 = -1: plain top-k, c and mass are then not
+ * read; q_len_dev NULL: every item has Sq rows), rsa_block_select_bound_packed that of rsa_block_select_pooled_packed; pooled_k is
+ * the bounds cache, fp32 [B, Hkv, NK, 2, D] contiguous, 16-byte aligned.  Everything behind the score -- the visible prefix, the
+ * forced blocks, top-k with ties to the lower block, top-p with its weights, target, cap and mass, the lists, the scores (-inf at
+ * invisible blocks), the ragged and the packed rows -- is the contract and the device code of the pooled entries.  Only the
+ * visible prefix of the cache is read; the rest may hold anything.  score_splits workgroups per list row (0: the library's choice;
+ * at most 256) write the row's scores to the workspace at every count, one included; every value gives the same bytes.
+ * ws: rsa_block_select_bound_bytes(...) bytes (= rsa_block_select_pooled_bytes), 16-byte aligned.  Three launches (the pooled
+ * queries, the scores, the selection); packed: four.  Refusals: the pooled entries', with their statuses, in their order. */
+int rsa_pool_key_bounds(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                        int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid, const int32_t* start_dev,
+                        int start, int workgroups_per_head, float* out, void* stream);
+int rsa_pool_key_bounds_kv8(int B, int Hkv, int Sk, int D, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                            int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
+                            const int32_t* start_dev, int start, int workgroups_per_head, float* out, const float* k_scale,
+                            void* stream);
+int rsa_block_select_bound_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes);
+int rsa_block_select_bound(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q,
+                           const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k, int keep_first,
+                           int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                           int32_t* counts, float* scores, int p16, float c, float* mass, const int32_t* q_len_dev, void* stream);
+int rsa_block_select_bound_packed(int T, int B, int H, int Hkv, int Hl, int max_q_len, int D, int dtype, int block, int NQ, int NK,
+                                  rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal,
+                                  int top_k, int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes,
+                                  uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass,
+                                  const int32_t* cu_seqlens_q_dev, int32_t* item_ws, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

@@ -133,6 +133,30 @@ def select_blocks_pooled(q, pooled_k, top_k, *, block_size=128, kv_len=None, cau
                                              cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len)
 
 
+def pool_key_bounds(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None,
+                    k_scale=None):
+    """The cache of per-channel key bounds for select_blocks_bound: pool_keys' arguments -> fp32 [B, Hkv, ceil(Sk/block), 2, D],
+    [..., 0, :] the minimum and [..., 1, :] the maximum of each block's keys below kv_len; updated block by block with start= and
+    out= as pool_keys is.  See rectified_spaattn_amd.block_sparse.pool_key_bounds."""
+    from . import block_sparse
+    return block_sparse.pool_key_bounds(k, block_size=block_size, kv_len=kv_len, block_table=block_table, out=out, start=start,
+                                        workgroups_per_head=workgroups_per_head, k_scale=k_scale)
+
+
+def select_blocks_bound(q, key_bounds, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0,
+                        mask_heads="kv", return_scores=False, as_lists=False, score_splits=None, top_p=None, score_scale=None,
+                        return_mass=False, q_len=None, cu_seqlens_q=None, max_q_len=None):
+    """select_blocks_pooled from the cache of pool_key_bounds: a key block scores by the upper bound of q . k over every key it
+    could hold, sum_d max(q_d min_d, q_d max_d) (Quest's criterion: training-free sparse decode of a dense model); everything
+    behind the score is select_blocks_pooled's.  See rectified_spaattn_amd.block_sparse.select_blocks_bound."""
+    from . import block_sparse
+    return block_sparse.select_blocks_bound(q, key_bounds, top_k, block_size=block_size, kv_len=kv_len, causal=causal,
+                                            keep_first=keep_first, keep_local=keep_local, mask_heads=mask_heads,
+                                            return_scores=return_scores, as_lists=as_lists, score_splits=score_splits,
+                                            top_p=top_p, score_scale=score_scale, return_mass=return_mass, q_len=q_len,
+                                            cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len)
+
+
 def clear_buffer_cache() -> None:
     """Drops the intermediate buffers the operators keep per (geometry, device, stream) between calls (about 0.45 GB per
     set at the HunyuanVideo shape; `_core.BUFFER_CACHE_MAX_BYTES` bounds the total, `_core.BUFFER_CACHE = False` turns the

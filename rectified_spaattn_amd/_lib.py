@@ -166,6 +166,14 @@ PROTOTYPES = {
     "rsa_set_tuning": (i32, [cstr, i32]),
     "rsa_status_string": (cstr, [i32]),
     "rsa_last_hip_error": (cstr, []),
+    # the bounds cache and the selection from it: additive and found by symbol, in front of the packed ones
+    "rsa_pool_key_bounds": (i32, [i32, i32, i32, i32, i32, i32, i32, T4, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp]),
+    "rsa_pool_key_bounds_kv8": (i32, [i32, i32, i32, i32, i32, i32, T4, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp, vp]),
+    "rsa_block_select_bound_bytes": (i32, [i32, i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_block_select_bound": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, vp, vp, i32, i32, i32, i32, i32, i32, vp,
+                                     sz, vp, vp, vp, vp, i32, f32, vp, vp, vp]),
+    "rsa_block_select_bound_packed": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, vp, vp, i32, i32, i32, i32,
+                                            i32, i32, vp, sz, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp]),
     # the packed entries: additive and found by symbol, in front of the ragged ones for the same reason
     "rsa_block_sparse_extend_packed_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz), P(i64)]),
     "rsa_block_sparse_extend_packed": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp,

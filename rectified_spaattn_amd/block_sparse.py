@@ -17,6 +17,10 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              grows, directly or through a block table (rsa_pool_keys)
     select_blocks_pooled     select_blocks from that cache instead of K: the same bytes without a pass over K
                              (rsa_block_select_pooled)
+    pool_key_bounds          the cache of per-channel key minima and maxima, pool_keys' twin with its argument contract
+                             (rsa_pool_key_bounds)
+    select_blocks_bound      select_blocks_pooled from that cache: a block scores by the upper bound of q . k over its keys
+                             (rsa_block_select_bound), everything behind the score unchanged
     append_kv_e4m3           the writer of a one-byte K/V cache: new rows become e4m3 codes under one static fp32 scale per K/V
                              head (rsa_kv8_append); block_sparse_decode and pool_keys read such a cache in place
                              (k_scale= / v_scale=: rsa_block_sparse_decode_kv8, rsa_pool_keys_kv8)
@@ -112,17 +116,28 @@ E4M3 = torch.float8_e4m3fn
 KV8_HEAD_DIMS = (64, 128)
 
 
-def _check_operands(q, k, v=None, *, dims=HEAD_DIMS, block_table=None, blk: int = 0, pooled: bool = False, kv8_ok: bool = False):
+def _check_operands(q, k, v=None, *, dims=HEAD_DIMS, block_table=None, blk: int = 0, pooled: bool = False, kv8_ok: bool = False,
+                    bounds: bool = False):
     """The tensor operands a call takes -> (B, H, Hkv, Sq, Sk, D).  q [B,H,Sq,D] or None (pool_keys: B from k, H = Hkv, Sq = 1);
     k [B,Hkv,Sk,D], or with a block_table [B, NKt] a page pool [P,Hkv,blk,D] of capacity Sk = NKt * blk, or with pooled the
     fp32 cache [B,Hkv,NK,D] of pool_keys (Sk is then NK); v like k, or None.  One 2-byte dtype -- or, where the call serves it
     (kv8_ok), k and v both float8_e4m3fn beside a 2-byte q; D among dims, the head dims the call serves (another of HEAD_DIMS is
-    NotImplementedError); nothing empty."""
-    kname = "pooled_k" if pooled else "k"
+    NotImplementedError); nothing empty.  bounds (beside pooled): k is the fp32 cache [B,Hkv,NK,2,D] of pool_key_bounds, held
+    whole to that form here and read below as the [B,Hkv,NK,D] of its minima."""
+    kname = "key_bounds" if bounds else "pooled_k" if pooled else "k"
+    if bounds:
+        if (not isinstance(k, torch.Tensor) or k.dim() != 5 or k.shape[3] != 2 or k.dtype != torch.float32
+                or not k.is_contiguous()):
+            raise ValueError(f"key_bounds: a contiguous float32 tensor [B, Hkv, NK, 2, D] (pool_key_bounds' result; the 4-d cache "
+                             f"[B, Hkv, NK, D] of pool_keys belongs to select_blocks_pooled), got "
+                             f"{getattr(k, 'dtype', type(k))} {tuple(getattr(k, 'shape', ()))}, strides "
+                             f"{tuple(k.stride()) if isinstance(k, torch.Tensor) else ()}")
+        k = k[:, :, :, 0]
     for t in (q, k, v):
         if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 4):
             raise ValueError(f"{_names(q, kname, v)}: 4-d tensors -- q [B, H, Sq, D], k / v [B, Hkv, Sk, D] or with block_table "
-                             "page pools [P, Hkv, block_size, D], pooled_k [B, Hkv, NK, D]")
+                             "page pools [P, Hkv, block_size, D], pooled_k [B, Hkv, NK, D] (the 5-d cache [B, Hkv, NK, 2, D] of "
+                             "pool_key_bounds belongs to select_blocks_bound)")
     kB, Hkv, Sk, kD = k.shape
     B, H, Sq, D = (kB, Hkv, 1, kD) if q is None else q.shape
     if v is not None and v.shape[1] != Hkv:
@@ -151,7 +166,7 @@ def _check_operands(q, k, v=None, *, dims=HEAD_DIMS, block_table=None, blk: int 
     elif dt not in (torch.bfloat16, torch.float16) or (not pooled and k.dtype != dt) or (v is not None and v.dtype != dt):
         raise ValueError(f"{_names(q, kname, v)}: one dtype, bfloat16 or float16 (pooled_k apart), got "
                          f"{', '.join(str(t.dtype) for t in (q, k, v) if t is not None)}")
-    if pooled and (k.dtype != torch.float32 or not k.is_contiguous()):
+    if pooled and not bounds and (k.dtype != torch.float32 or not k.is_contiguous()):
         raise ValueError(f"pooled_k: a contiguous float32 tensor (pool_keys' result), got dtype {k.dtype}, "
                          f"strides {tuple(k.stride())}")
     if D not in dims:
@@ -239,7 +254,7 @@ def _packed_view(name: str, x, cu, keys, block_table):
                          f"otherwise), got {tuple(getattr(x, 'shape', ()))} with cu_seqlens")
     if isinstance(block_table, torch.Tensor) and block_table.dim() == 2:
         B = block_table.shape[0]
-    elif isinstance(keys, torch.Tensor) and keys.dim() == 4:
+    elif isinstance(keys, torch.Tensor) and keys.dim() in (4, 5):       # (5: the bounds cache [B, Hkv, NK, 2, D])
         B = keys.shape[0]
     else:
         raise ValueError("packed call: the number of items comes from block_table [B, NKt] or from the cache [B, Hkv, Sk, D]")
@@ -634,12 +649,14 @@ def _check_top_p(top_p, score_scale, return_mass):
 
 def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
             return_scores, as_lists, score_splits=None, top_p=None, score_scale=None, return_mass=False, q_len=None,
-            cu_seqlens_q=None, max_q_len=None):
+            cu_seqlens_q=None, max_q_len=None, bound: bool = False):
     """select_blocks (keys = k, rsa_block_select) and select_blocks_pooled (keys = pool_keys' cache, rsa_block_select_pooled,
     with its score_splits): the two differ in where kbar comes from and in nothing else.  With top_p the entries are their _p
     forms, which take (p16, c, mass) in front of the stream.  With q_len the entries are their _ragged forms: the _p argument
     lists (p16 = -1: top-k) and the device row counts in front of the stream.  With cu_seqlens_q (pooled only) the entry is
-    rsa_block_select_pooled_packed: q [T, H, D], the ragged argument list with T in front and M for Sq."""
+    rsa_block_select_pooled_packed: q [T, H, D], the ragged argument list with T in front and M for Sq.  bound (beside pooled):
+    select_blocks_bound -- keys = pool_key_bounds' cache; rsa_block_select_bound has the ragged argument list alone (p16 = -1:
+    top-k; no row counts: NULL) and rsa_block_select_bound_packed the packed one."""
     blk = _check_block(what, block_size)
     if mask_heads not in ("kv", "q"):
         raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
@@ -653,7 +670,7 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         raise ValueError("q_len belongs to a padded q: with cu_seqlens_q the rows of an item are cu_seqlens_q[b + 1] - cu_seqlens_q[b]")
     if Bp is None and max_q_len is not None:
         raise ValueError("max_q_len belongs to cu_seqlens_q")
-    B, H, Hkv, Sq, Sk, D = _check_operands(q, keys, pooled=pooled)
+    B, H, Hkv, Sq, Sk, D = _check_operands(q, keys, pooled=pooled, bounds=bound)
     if Bp is not None:
         T = Sq
         cu, Sq = _check_packed("cu_seqlens_q", cu_seqlens_q, max_q_len, B, T)
@@ -666,7 +683,7 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
     _core._require_device(q, keys)
     dev = q.device
     if pooled and keys.data_ptr() % 16:
-        raise ValueError("pooled_k: 16-byte aligned")
+        raise ValueError(f"{'key_bounds' if bound else 'pooled_k'}: 16-byte aligned")
     kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
     q_dev = _row_limit(rows, B, Sq, dev)
     L = _lib.lib()
@@ -675,11 +692,12 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         q = q3 if _core._read_in_place(q3) else q3.contiguous()
     else:
         q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
-    entry = ("rsa_block_select_pooled" if pooled else "rsa_block_select") + ("" if top_p is None else "_p")
+    base = "rsa_block_select_bound" if bound else "rsa_block_select_pooled" if pooled else "rsa_block_select"
+    entry = base + ("" if top_p is None or bound else "_p")
     need = ctypes.c_size_t(0)
     _lib.check(getattr(L, entry + "_bytes")(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), entry + "_bytes")
-    if q_dev is not None:
-        entry = "rsa_block_select_pooled_ragged" if pooled else "rsa_block_select_ragged"
+    if q_dev is not None and not bound:
+        entry = base + "_ragged"
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
     out = _empty_lists(B * Hl, NQ, NK, dev)
     scores = torch.empty((B, Hl, NQ, NK), dtype=torch.float32, device=dev) if return_scores else None
@@ -693,11 +711,11 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         mass = torch.empty((B, Hl, NQ), dtype=torch.float32, device=dev) if return_mass else None
         scale = 1.0 / ((H // Hl) * math.sqrt(D)) if score_scale is None else float(score_scale)
         budget = (int(round(float(top_p) * 65536.0)), scale * LOG2_E, _ptr(mass))
-    if q_dev is not None:
-        budget = (budget or (-1, 0.0, None)) + (q_dev.data_ptr(),)
+    if q_dev is not None or (bound and Bp is None):
+        budget = (budget or (-1, 0.0, None)) + (_ptr(q_dev),)
     tq = _core._t4(q) if Bp is None else _t3(q)
     if Bp is not None:      # T in front, M where Sq stood, cu_seqlens_q and the scan's scratch where q_len stood
-        entry, shape = "rsa_block_select_pooled_packed", (T,) + shape
+        entry, shape = base + "_packed", (T,) + shape
         cu, items = cu.contiguous(), torch.empty((2 * (B + 1),), dtype=torch.int32, device=dev)
         budget = (budget or (-1, 0.0, None)) + (cu.data_ptr(), items.data_ptr())
     with torch.cuda.device(dev):
@@ -734,16 +752,23 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
     with k_scale a positive float or a float32 device tensor of 1 or Hkv values (required then, refused otherwise).  The value of
     a block is the fp32 sum of float(code) over its keys below kv_len[b], in the same order, divided once by their count and
     multiplied once by k_scale[hkv]; every other clause above holds.  select_blocks_pooled reads the result as before."""
-    blk = _check_block("pool_keys", block_size)
+    return _pool_cache("pool_keys", (), k, block_size, kv_len, block_table, out, start, workgroups_per_head, k_scale)
+
+
+def _pool_cache(what: str, pair, k, block_size, kv_len, block_table, out, start, workgroups_per_head, k_scale) -> torch.Tensor:
+    """pool_keys (pair = (): the cache [B, Hkv, NK, D], rsa_pool_keys[_kv8]) and pool_key_bounds (pair = (2,): the cache
+    [B, Hkv, NK, 2, D], rsa_pool_key_bounds[_kv8]): one argument contract, and C entries with the same argument lists."""
+    blk = _check_block(what, block_size)
     _check_count("workgroups_per_head", workgroups_per_head, 1, optional=True)
     B, _, Hkv, _, Sk, D = _check_operands(None, k, block_table=block_table, blk=blk, kv8_ok=True)
     _check_scales(k, Hkv, k_scale=k_scale)
     NK = _key_blocks(Sk, blk)
     if start is not None and out is None:
         raise ValueError("out: required when start is given (an update writes into the cache it is given)")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, Hkv, NK, D)
+    shape = (B, Hkv, NK) + pair + (D,)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape
                             or not out.is_contiguous()):
-        raise ValueError(f"out: a contiguous float32 tensor [{B}, {Hkv}, {NK}, {D}], got {getattr(out, 'dtype', type(out))} "
+        raise ValueError(f"out: a contiguous float32 tensor {list(shape)}, got {getattr(out, 'dtype', type(out))} "
                          f"{tuple(getattr(out, 'shape', ()))}")
     lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
     starts = _check_limit("start", start, B, Sk, 0)
@@ -751,7 +776,7 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
     _core._require_device(k)
     dev = k.device
     if out is None:
-        out = torch.empty((B, Hkv, NK, D), dtype=torch.float32, device=dev)
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
     else:
         _core._require_device(out)
     if out.data_ptr() % 16:
@@ -765,17 +790,35 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
         wph = max([1] + [-(-n // blk) - s // blk for n, s in zip(lens, starts) if s <= n])
     else:
         wph = NK if start is None else 2
+    entry = ("rsa_pool_key_bounds" if pair else "rsa_pool_keys") + ("_kv8" if k.dtype == E4M3 else "")
     with torch.cuda.device(dev):
         if k.dtype == E4M3:
             ks = _scale_arg(k_scale, Hkv, dev)
-            _lib.check(_lib.lib().rsa_pool_keys_kv8(B, Hkv, Sk, D, blk, NK, _core._t4(k), *table, _ptr(kv_dev), kv_valid,
-                                                    _ptr(st_dev), st_host, wph, out.data_ptr(), ks.data_ptr(), _core._stream()),
-                       "rsa_pool_keys_kv8")
+            _lib.check(getattr(_lib.lib(), entry)(B, Hkv, Sk, D, blk, NK, _core._t4(k), *table, _ptr(kv_dev), kv_valid,
+                                                  _ptr(st_dev), st_host, wph, out.data_ptr(), ks.data_ptr(), _core._stream()), entry)
         else:
-            _lib.check(_lib.lib().rsa_pool_keys(B, Hkv, Sk, D, _core.dtype_code(k.dtype), blk, NK, _core._t4(k), *table,
-                                                _ptr(kv_dev), kv_valid, _ptr(st_dev), st_host, wph, out.data_ptr(),
-                                                _core._stream()), "rsa_pool_keys")
+            _lib.check(getattr(_lib.lib(), entry)(B, Hkv, Sk, D, _core.dtype_code(k.dtype), blk, NK, _core._t4(k), *table,
+                                                  _ptr(kv_dev), kv_valid, _ptr(st_dev), st_host, wph, out.data_ptr(),
+                                                  _core._stream()), entry)
     return out
+
+
+def pool_key_bounds(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_table=None, out: Optional[torch.Tensor] = None,
+                    start=None, workgroups_per_head: Optional[int] = None, k_scale=None) -> torch.Tensor:
+    """The cache of per-channel key bounds select_blocks_bound reads: per key block and channel the
+    minimum and the maximum of the block's keys below kv_len[b].  Returns (and fills) out, fp32 [B, Hkv, NKt, 2, D] contiguous:
+    out[..., 0, :] the minima, out[..., 1, :] the maxima; 1/32 of K's bytes at 128-token blocks of bf16.
+    The argument contract is pool_keys' word for word: k [B,Hkv,Sk,D] or page pools behind block_table, bf16 / fp16 at head dim
+    16, 32, 64 or 128, float8_e4m3fn with k_scale at head dim 64 / 128; kv_len / start in all their forms, device tensors clamped
+    on the device and never read on the host; the call writes exactly the blocks start[b] // block <= j < ceil(kv_len[b] / block)
+    and no other byte of out (out is required when start is given); a table entry outside [0, P) gives a block of zeros, min and
+    max alike; keys at or beyond kv_len[b] are never loaded and may hold NaN; out is 16-byte aligned; workgroups_per_head is a
+    performance hint; asynchronous on the current stream, capturable.
+    An e4m3 cache: min and max are taken over float(code) and each is multiplied once by k_scale[hkv] (positive: the order is
+    kept).  Keys below kv_len are taken to be finite: a NaN there gives an unspecified value (and forms no address).
+    min and max are exact and order-free, so every workgroups_per_head gives the same values and two calls the same bytes; one
+    pass over K writes both halves."""
+    return _pool_cache("pool_key_bounds", (2,), k, block_size, kv_len, block_table, out, start, workgroups_per_head, k_scale)
 
 
 def append_kv_e4m3(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, start, k_scale,
@@ -878,6 +921,30 @@ def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *,
     if cu_seqlens_q is given; q_len= beside it is refused.  One launch more than the q_len= call (the scan of cu_seqlens_q)."""
     return _select("select_blocks_pooled", q, pooled_k, True, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
                    return_scores, as_lists, score_splits, top_p, score_scale, return_mass, q_len, cu_seqlens_q, max_q_len)
+
+
+def select_blocks_bound(q: torch.Tensor, key_bounds: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None,
+                        causal: bool = False, keep_first: int = 0, keep_local: int = 0, mask_heads: str = "kv",
+                        return_scores: bool = False, as_lists: bool = False, score_splits: Optional[int] = None,
+                        top_p: Optional[float] = None, score_scale: Optional[float] = None, return_mass: bool = False,
+                        q_len=None, cu_seqlens_q=None, max_q_len: Optional[int] = None):
+    """select_blocks_pooled with one thing changed, the score (Quest's criterion): key_bounds is the fp32
+    cache [B, Hkv, NK, 2, D] of pool_key_bounds (contiguous, 16-byte aligned) and list row (b, hl, i) scores key block j by the
+    upper bound of qs . k over every key the block could hold,
+        t = sum over d of max(qs_d * mn_d, qs_d * mx_d)
+    with qs the pooled query of select_blocks (the sum over the list head's query heads, ascending, of each head's fp32 row mean;
+    the bound of the summed query, not the sum of per-head bounds) and mn / mx the block's per-channel minimum / maximum.  A
+    block that holds one key aligned with the query among many that are not keeps a high score, where its mean is near zero:
+    the criterion for training-free sparse decode of a dense model.  fp32 in a fixed order (rsa.h): two calls, the same bytes.
+    Everything else is select_blocks_pooled's contract and device code: the visible prefix and the forced blocks, top-k with
+    ties to the lower block, top_p / score_scale / return_mass with the top_k cap, as_lists, return_scores (-inf where a block is
+    not visible), q_len and the packed cu_seqlens_q / max_q_len layout, kv_len never read on the host, only the visible prefix of
+    the cache read (the rest may hold NaN), capture in a graph.  score_splits: workgroups per list row of the score pass, which
+    here is a launch of its own at every count, 1 included; every value gives the same bytes; None = select_blocks_pooled's
+    choice (measured for this form too: DESIGN.md section 5.19).  Where every key of a block is the same the bound is the mean
+    score: select_blocks_pooled's result up to fp32 rounding, and its bytes where the sums are exact."""
+    return _select("select_blocks_bound", q, key_bounds, True, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
+                   return_scores, as_lists, score_splits, top_p, score_scale, return_mass, q_len, cu_seqlens_q, max_q_len, bound=True)
 
 
 DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_decode.hip)

@@ -9,6 +9,10 @@
 //                              write sel_pool_mean of each, read directly or through a block table, into the fp32 cache
 //   block_score_kernel         `splits` workgroups per list row: each writes its slice of the row's ordered keys to the workspace
 //                              (a lane group computes a whole score: nothing is summed across workgroups)
+//   pool_key_bounds_kernel     pool_keys_kernel's min/max twin: per key block and channel the minimum and the maximum of the keys, into
+//                              the fp32 bounds cache [.., NK, 2, D] (rsa_pool_key_bounds; section 5.19)
+//   block_bound_score_kernel   block_score_kernel's twin over that cache: t = sum_d max(q_d mn_d, q_d mx_d), the upper bound of q . k
+//                              over every key the block could hold (rsa_block_select_bound); the select kernels rank its keys LOADED
 //   block_select[_p]_kernel    one 256-thread workgroup per list row (b, list head, query block): top-k; top-p capped at top_k
 //
 // The two select kernels are sel_row_body<L, LOADED, BUDGET>: the pooled scores of the visible key blocks into LDS as
@@ -259,6 +263,131 @@ __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hk
     }
 }
 
+// ---- the bounds cache -----------------------------------------------------------------------------------------
+// What a lane reads for its 8 channels of a row, as floats (e4m3: float(code)); sel_add8's loads and conversions.
+template <typename Tag>
+__device__ __forceinline__ void sel_unpack8(float (&x)[8], const typename SelElem<Tag>::vec v) {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        x[2 * i] = rsa_to_f32<Tag>((unsigned short)(w[i] & 0xFFFFu));
+        x[2 * i + 1] = rsa_to_f32<Tag>((unsigned short)(w[i] >> 16));
+    }
+}
+template <>
+__device__ __forceinline__ void sel_unpack8<e4m3_tag>(float (&x)[8], const uint2 v) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const unsigned w[2] = {v.x, v.y};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        x[4 * i] = lo[0];
+        x[4 * i + 1] = lo[1];
+        x[4 * i + 2] = hi[0];
+        x[4 * i + 3] = hi[1];
+    }
+}
+template <typename Tag>
+__device__ __forceinline__ void sel_minmax8(float (&mn)[8], float (&mx)[8], const typename SelElem<Tag>::vec v) {
+    float x[8];
+    sel_unpack8<Tag>(x, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        mn[e] = fminf(mn[e], x[e]);
+        mx[e] = fmaxf(mx[e], x[e]);
+    }
+}
+
+// The min/max twin of sel_pool_block: per channel the minimum and the maximum over `rows` rows (>= 1, uniform over the workgroup);
+// thread t < D returns channel t's pair (x: min, y: max).  The same loads, row striding and xor strides; a thread without a row
+// holds (+inf, -inf), which no minimum or maximum keeps.  min and max are exact and order-free: any split of the rows gives the
+// same values.
+template <typename Tag>
+__device__ __forceinline__ float2 sel_bounds_block(const typename SelElem<Tag>::type* __restrict__ base, long stride_s, int rows,
+                                                   int D, float (*redn)[128], float (*redx)[128]) {
+    using vec = typename SelElem<Tag>::vec;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int C = D >> 3, RP = SEL_NT / C;
+    const int c = tid % C;
+    const typename SelElem<Tag>::type* p = base + c * 8;
+    float mn[8], mx[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) mn[e] = INFINITY, mx[e] = -INFINITY;
+    int r = tid / C;
+    for (; r + 3 * RP < rows; r += 4 * RP) {
+        vec v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const vec*>(p + (long)(r + u * RP) * stride_s);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sel_minmax8<Tag>(mn, mx, v[u]);
+    }
+    for (; r < rows; r += RP) sel_minmax8<Tag>(mn, mx, *reinterpret_cast<const vec*>(p + (long)r * stride_s));
+    for (int m = C; m < 64; m <<= 1) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            mn[e] = fminf(mn[e], __shfl_xor(mn[e], m, 64));
+            mx[e] = fmaxf(mx[e], __shfl_xor(mx[e], m, 64));
+        }
+    }
+    __syncthreads();   // (the reductions may still be read from the previous block)
+    if (lane < C) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            redn[wave][lane * 8 + e] = mn[e];
+            redx[wave][lane * 8 + e] = mx[e];
+        }
+    }
+    __syncthreads();
+    if (tid >= D) return make_float2(0.f, 0.f);
+    return make_float2(fminf(fminf(redn[0][tid], redn[1][tid]), fminf(redn[2][tid], redn[3][tid])),
+                       fmaxf(fmaxf(redx[0][tid], redx[1][tid]), fmaxf(redx[2][tid], redx[3][tid])));
+}
+
+// The bounds cache: pool_keys_kernel over sel_bounds_block.  out fp32 [B, Hkv, NK, 2, D]: the minima, then the maxima of a block.
+// The written set, the table rule (an entry outside [0, num_pages): zeros, min and max alike) and the limits are pool_keys_kernel's.
+// Tag = e4m3_tag: min and max over float(code), each multiplied once by k_scale[hk] (> 0: the order is kept).
+template <typename Tag>
+__global__ __launch_bounds__(SEL_NT) void pool_key_bounds_kernel(rsa_tensor4 k, int Hkv, int Sk, int D, int blk, int NK, int W,
+                                                                 const int32_t* __restrict__ kv_len, int kv_valid,
+                                                                 const int32_t* __restrict__ start_dev, int start_host,
+                                                                 const int32_t* __restrict__ table, long table_stride_b,
+                                                                 int num_pages, float* __restrict__ out,
+                                                                 const float* __restrict__ k_scale) {
+    using KT = typename SelElem<Tag>::type;
+    __shared__ float redn[4][128], redx[4][128];
+    const int tid = threadIdx.x;
+    const int w = (int)(blockIdx.x % (unsigned)W);
+    const long bh = blockIdx.x / (unsigned)W;
+    const int hk = (int)(bh % Hkv);
+    const long b = bh / Hkv;
+    const int len = sel_key_limit(kv_len, (int)b, kv_valid, Sk);
+    const int st = sel_key_limit(start_dev, (int)b, start_host, Sk);
+    if (st > len) return;
+    const int j_hi = min(NK, (len + blk - 1) / blk);
+    for (int j = st / blk + w; j < j_hi; j += W) {
+        const int rows = min(blk, len - j * blk);       // >= 1 below j_hi
+        const KT* base;
+        bool have = true;
+        if (table) {
+            const int page = table[b * table_stride_b + j];
+            have = page >= 0 && page < num_pages;
+            base = static_cast<const KT*>(k.ptr) + (long)(have ? page : 0) * k.stride_b + (long)hk * k.stride_h;
+        } else {
+            base = static_cast<const KT*>(k.ptr) + b * k.stride_b + (long)hk * k.stride_h + (long)j * blk * k.stride_s;
+        }
+        float2 mm = have ? sel_bounds_block<Tag>(base, k.stride_s, rows, D, redn, redx) : make_float2(0.f, 0.f);
+        if constexpr (std::is_same<Tag, e4m3_tag>::value) {
+            const float sc = k_scale[hk];
+            mm.x *= sc, mm.y *= sc;
+        }
+        if (tid < D) {
+            float* o = out + (bh * NK + j) * 2 * D + tid;
+            o[0] = mm.x;
+            o[D] = mm.y;
+        }
+    }
+}
+
 // ---- scores ----------------------------------------------------------------------------------------------------------------------
 // Scores of the key blocks [lo, hi) of one list row as ordered keys into dst[j], by one workgroup.  L = D / 4 lanes share one
 // pooled key row (a float4 each); a wave scores 64 / L key blocks per step.  kb: the pooled rows of (b, K/V head); qrow: the row's
@@ -309,6 +438,58 @@ __global__ __launch_bounds__(SEL_NT) void block_score_kernel(const float* __rest
     const int chunk = (NK + splits - 1) / splits;
     const int lo = part * chunk, hi = min(lo + chunk, nvis);
     sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, lo, hi, wkeys + row * NK);
+}
+
+// The bound scores of the key blocks [lo, hi) of one list row: sel_score_blocks over the bounds cache.  kb:
+// the (min, max) row pairs of (b, K/V head), 2 D floats a block.  t = sum over d of max(q_d mn_d, q_d mx_d): per lane four terms,
+// each the larger of two separately rounded fp32 products, added as ((x + y) + z) + w; the lanes meet over the same xor strides.
+template <int L>
+__device__ __forceinline__ void sel_bound_score_blocks(const float* __restrict__ kb, const float* __restrict__ qrow, int lo, int hi,
+                                                       unsigned* dst) {
+    constexpr int D = 4 * L, RW = 64 / L, U = 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cl = lane % L, sub = lane / L;
+    const float4 qv = *reinterpret_cast<const float4*>(qrow + cl * 4);
+    kb += cl * 4;
+    for (int j0 = lo + wave * RW; j0 < hi; j0 += 4 * RW * U) {
+        float4 mn[U], mx[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * 4 * RW + sub;
+            mn[u] = j < hi ? *reinterpret_cast<const float4*>(kb + (long)j * 2 * D) : make_float4(0.f, 0.f, 0.f, 0.f);
+            mx[u] = j < hi ? *reinterpret_cast<const float4*>(kb + (long)j * 2 * D + D) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * 4 * RW + sub;
+            float p = ((fmaxf(qv.x * mn[u].x, qv.x * mx[u].x) + fmaxf(qv.y * mn[u].y, qv.y * mx[u].y)) +
+                       fmaxf(qv.z * mn[u].z, qv.z * mx[u].z)) + fmaxf(qv.w * mn[u].w, qv.w * mx[u].w);
+#pragma unroll
+            for (int m = 1; m < L; m <<= 1) p += __shfl_xor(p, m, 64);
+            if (cl == 0 && j < hi) dst[j] = sel_key(p);
+        }
+    }
+}
+
+// block_score_kernel over the bounds cache kbounds [B, Hkv, NK, 2, D]: the score pass of the bound selection, at every `splits`.
+template <int L, bool RAG = false, typename... Q>
+__global__ __launch_bounds__(SEL_NT) void block_bound_score_kernel(const float* __restrict__ kbounds, const float* __restrict__ qsum,
+                                                                   int Hkv, int Hl, int Sq, int Sk, int blk, int NQ, int NK, int splits,
+                                                                   const int32_t* __restrict__ kv_len, int kv_valid, int causal,
+                                                                   unsigned* __restrict__ wkeys, Q... q_len) {
+    constexpr int D = 4 * L;
+    const int part = (int)(blockIdx.x % (unsigned)splits);
+    const long row = blockIdx.x / (unsigned)splits;
+    const int i = (int)(row % NQ);
+    const long bh = row / NQ;
+    const int hl = (int)(bh % Hl);
+    const long b = bh / Hl;
+    const int hk = hl / (Hl / Hkv);
+    const int nvis = sel_visible<RAG>(sel_key_limit(kv_len, (int)b, kv_valid, Sk), sel_row_count<RAG>(sel_q_len(q_len...), (int)b, Sq),
+                                      blk, NK, i, causal);
+    const int chunk = (NK + splits - 1) / splits;
+    const int lo = part * chunk, hi = min(lo + chunk, nvis);
+    sel_bound_score_blocks<L>(kbounds + ((b * Hkv + hk) * NK) * 2 * D, qsum + row * D, lo, hi, wkeys + row * NK);
 }
 
 // ---- select ----------------------------------------------------------------------------------------------------------------------
@@ -697,8 +878,9 @@ extern "C" int rsa_block_select_p(int B, int H, int Hkv, int Hl, int Sq, int Sk,
 }
 
 // ---- the pooled-key cache ----------------------------------------------------------------------------------
-// Both entries: kv8 = k holds e4m3 codes (no dtype; head dims 64 / 128; 8-byte loads) and k_scale is there.
-static int sel_pool_keys_run(bool kv8, int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k,
+// Both entries: kv8 = k holds e4m3 codes (no dtype; head dims 64 / 128; 8-byte loads) and k_scale is there.  bounds: the entries of
+// the bounds cache (section 5.19), whose out holds 2 D floats a block: the same checks and grid, pool_key_bounds_kernel.
+static int sel_pool_keys_run(bool kv8, bool bounds, int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k,
                              const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev,
                              int kv_valid, const int32_t* start_dev, int start, int workgroups_per_head, float* out,
                              const float* k_scale, void* stream) {
@@ -734,6 +916,9 @@ static int sel_pool_keys_run(bool kv8, int B, int Hkv, int Sk, int D, int dtype,
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((size_t)B * Hkv * W));
     auto* kernel = kv8 ? pool_keys_kernel<e4m3_tag> : dtype == RSA_BF16 ? pool_keys_kernel<bf16_tag> : pool_keys_kernel<fp16_tag>;
+    if (bounds)
+        kernel = kv8 ? pool_key_bounds_kernel<e4m3_tag>
+                     : dtype == RSA_BF16 ? pool_key_bounds_kernel<bf16_tag> : pool_key_bounds_kernel<fp16_tag>;
     kernel<<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start, block_table,
                                    (long)table_stride_b, num_pages, out, k_scale);     // (k_scale: NULL unless kv8)
     return rsa_launch_status();
@@ -742,7 +927,7 @@ static int sel_pool_keys_run(bool kv8, int B, int Hkv, int Sk, int D, int dtype,
 extern "C" int rsa_pool_keys(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
                              int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
                              const int32_t* start_dev, int start, int workgroups_per_head, float* out, void* stream) {
-    return sel_pool_keys_run(false, B, Hkv, Sk, D, dtype, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
+    return sel_pool_keys_run(false, false, B, Hkv, Sk, D, dtype, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
                              start_dev, start, workgroups_per_head, out, nullptr, stream);
 }
 
@@ -752,7 +937,24 @@ extern "C" int rsa_pool_keys_kv8(int B, int Hkv, int Sk, int D, int block, int N
                                  int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
                                  const int32_t* start_dev, int start, int workgroups_per_head, float* out, const float* k_scale,
                                  void* stream) {
-    return sel_pool_keys_run(true, B, Hkv, Sk, D, 0, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
+    return sel_pool_keys_run(true, false, B, Hkv, Sk, D, 0, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
+                             start_dev, start, workgroups_per_head, out, k_scale, stream);
+}
+
+// The bounds cache: rsa_pool_keys' and rsa_pool_keys_kv8's argument lists; out fp32 [B, Hkv, NK, 2, D].
+extern "C" int rsa_pool_key_bounds(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k,
+                                   const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev,
+                                   int kv_valid, const int32_t* start_dev, int start, int workgroups_per_head, float* out,
+                                   void* stream) {
+    return sel_pool_keys_run(false, true, B, Hkv, Sk, D, dtype, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev,
+                             kv_valid, start_dev, start, workgroups_per_head, out, nullptr, stream);
+}
+
+extern "C" int rsa_pool_key_bounds_kv8(int B, int Hkv, int Sk, int D, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                                       int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
+                                       const int32_t* start_dev, int start, int workgroups_per_head, float* out,
+                                       const float* k_scale, void* stream) {
+    return sel_pool_keys_run(true, true, B, Hkv, Sk, D, 0, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
                              start_dev, start, workgroups_per_head, out, k_scale, stream);
 }
 
@@ -760,6 +962,8 @@ extern "C" int rsa_pool_keys_kv8(int B, int Hkv, int Sk, int D, int block, int N
 // One pass of sel_score_blocks' loop per score workgroup (4096 / D key blocks: 32 at D = 128), which is the best or within the
 // baseline's spread of the best at both measured row counts (8 rows x 1024 blocks: 32 splits; 64 rows x 256 blocks: 8); at most 64
 // splits and about 1024 workgroups, and none where the list rows alone give two workgroups per compute unit (not measured there).
+// The bound selection (section 5.19) takes the same choice: at both row counts it is the best split count measured for it too
+// (profiles/select_bound_perf.txt).
 static int sel_default_splits(size_t rows, int NK, int D) {
     if (rows >= 512) return 1;
     const int pass = 4096 / D;
@@ -775,10 +979,12 @@ struct SelPacked {
 };
 
 // The body of rsa_block_select_pooled and rsa_block_select_pooled_p (top_p NULL: top-k).  r: the call's arguments; Sk, kbar, qsum
-// and wkeys are set here.  pk: the packed entry (r.Sq = M; q_len is then set here, to the scan's row counts).
+// and wkeys are set here.  pk: the packed entry (r.Sq = M; q_len is then set here, to the scan's row counts).  bound: pooled_k is the
+// bounds cache (section 5.19) -- the score pass is then block_bound_score_kernel at every split count, one included, and the select
+// kernels run LOADED: they gain no form of their own.
 static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const float* pooled_k, int score_splits, void* ws,
                           size_t ws_bytes, sel_rows r, const sel_top_p* top_p, const int32_t* q_len, void* stream,
-                          const SelPacked* pk = nullptr) {
+                          const SelPacked* pk = nullptr, bool bound = false) {
     if ((top_p && !selp_budget_ok(*top_p)) || r.NK <= 0) return RSA_ERR_BAD_ARG;
     if (pk) {
         if (pk->T <= 0 || r.Sq <= 0 || r.Sq > pk->T || !pk->cu || !pk->items || B >= 0x7FFFFFFF) return RSA_ERR_BAD_ARG;
@@ -799,11 +1005,24 @@ static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const f
     float* qsum = static_cast<float*>(ws);                              // [B, Hl, NQ, D]
     unsigned* wkeys = reinterpret_cast<unsigned*>(qsum + q_jobs * D);   // [B, Hl, NQ, NK]
     r.Sk = r.NK * r.blk;        // the capacity of the cache
-    r.kbar = pooled_k, r.qsum = qsum, r.wkeys = splits > 1 ? wkeys : nullptr;
+    r.kbar = pooled_k, r.qsum = qsum, r.wkeys = (bound || splits > 1) ? wkeys : nullptr;
     if (pk) pk_scan_launch(pk->cu, B, pk->T, r.Sq, r.blk, 0, 0, pk->items, pk->items + B + 1, nullptr, s);
     int rc = sel_launch_pool(dtype, H, D, q, q, q_jobs, 0, r, nullptr, qsum, q_len, s, pk ? pk->items : nullptr);    // the pooled queries
     if (rc != RSA_OK) return rc;
-    if (splits > 1) {
+    if (bound) {
+        sel_with_lanes(D, [&](auto lanes) {
+            constexpr int L = decltype(lanes)::value;
+            const dim3 grid((unsigned)(q_jobs * splits));
+            if (q_len)
+                block_bound_score_kernel<L, true><<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK,
+                                                                          splits, r.kv_len, r.kv_valid, r.causal, wkeys, q_len);
+            else
+                block_bound_score_kernel<L><<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits,
+                                                                    r.kv_len, r.kv_valid, r.causal, wkeys);
+        });
+        rc = rsa_launch_status();
+        if (rc != RSA_OK) return rc;
+    } else if (splits > 1) {
         sel_with_lanes(D, [&](auto lanes) {
             constexpr int L = decltype(lanes)::value;
             const dim3 grid((unsigned)(q_jobs * splits));
@@ -887,4 +1106,35 @@ extern "C" int rsa_block_select_pooled_packed(int T, int B, int H, int Hkv, int 
     return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, max_q_len, 0,
                           block, NQ, NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores},
                           p16 == -1 ? nullptr : &p, nullptr, stream, &pk);
+}
+
+// ---- bound selection: the selection from the bounds cache.  rsa_block_select_pooled_ragged's and
+// rsa_block_select_pooled_packed's argument lists and statuses; pooled_k is the bounds cache, fp32 [B, Hkv, NK, 2, D].  p16 = -1:
+// plain top-k; q_len_dev NULL: every item has Sq rows.
+extern "C" int rsa_block_select_bound_bytes(int B, int Hkv, int Hl, int D, int NQ, int NK, size_t* bytes) {
+    return sel_sizes(true, B, Hkv, Hl, D, NQ, NK, bytes);
+}
+
+extern "C" int rsa_block_select_bound(int B, int H, int Hkv, int Hl, int Sq, int D, int dtype, int block, int NQ, int NK, rsa_tensor4 q,
+                                      const float* pooled_k, const int32_t* kv_len_dev, int kv_valid, int causal, int top_k,
+                                      int keep_first, int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask,
+                                      int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass,
+                                      const int32_t* q_len_dev, void* stream) {
+    const sel_top_p p = {p16, c, mass};
+    return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, Sq, 0, block, NQ,
+                          NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores},
+                          p16 == -1 ? nullptr : &p, q_len_dev, stream, nullptr, true);
+}
+
+extern "C" int rsa_block_select_bound_packed(int T, int B, int H, int Hkv, int Hl, int max_q_len, int D, int dtype, int block, int NQ,
+                                             int NK, rsa_tensor4 q, const float* pooled_k, const int32_t* kv_len_dev, int kv_valid,
+                                             int causal, int top_k, int keep_first, int keep_local, int score_splits, void* ws,
+                                             size_t ws_bytes, uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores,
+                                             int p16, float c, float* mass, const int32_t* cu_seqlens_q_dev, int32_t* item_ws,
+                                             void* stream) {
+    const sel_top_p p = {p16, c, mass};
+    const SelPacked pk = {T, cu_seqlens_q_dev, item_ws};
+    return sel_pooled_run(B, H, D, dtype, q, pooled_k, score_splits, ws, ws_bytes, {nullptr, nullptr, nullptr, Hkv, Hl, max_q_len, 0,
+                          block, NQ, NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores},
+                          p16 == -1 ? nullptr : &p, nullptr, stream, &pk, true);
 }
