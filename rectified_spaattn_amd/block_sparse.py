@@ -41,6 +41,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import torch
@@ -275,6 +276,28 @@ def _check_packed(name: str, cu, max_len, B: int, T: int, need_max: bool = True)
     elif max_len is not None:
         raise ValueError(f"max_q_len belongs to {name}")
     return cu.reshape(-1), (int(max_len) if need_max else T)
+
+
+def _query_rows(q, q_len, cu_seqlens_q, max_q_len, keys, block_table, check_operands):
+    """Where a call's query rows come from, for _select and _sparse_rows: "padded" (q [B, H, Sq, D]), "counted" (with q_len) or "packed"
+    (q [T, H, D], cu_seqlens_q, max_q_len).  -> the kind, q as a 4-d view (q4; q3: the caller's tensor), the
+    shapes of check_operands(q4), the caller's _check_operands call (Sq is M = max_q_len when packed), T and the checked cu."""
+    q4, Bp = _packed_view("q", q, cu_seqlens_q, keys, block_table)
+    if Bp is not None and q_len is not None:
+        raise ValueError("q_len belongs to a padded q: with cu_seqlens_q the rows of an item are cu_seqlens_q[b + 1] - cu_seqlens_q[b]")
+    if Bp is None and max_q_len is not None:
+        raise ValueError("max_q_len belongs to cu_seqlens_q")
+    B, H, Hkv, Sq, Sk, D = check_operands(q4)
+    T = cu = None
+    if Bp is not None:      # T: the rows of q; Sq is M from here on, the rows of an item at most
+        T, (cu, Sq) = Sq, _check_packed("cu_seqlens_q", cu_seqlens_q, max_q_len, B, Sq)
+    kind = "packed" if Bp is not None else "counted" if q_len is not None else "padded"
+    return SimpleNamespace(kind=kind, q4=q4, q3=q, B=B, H=H, Hkv=Hkv, Sq=Sq, Sk=Sk, D=D, T=T, cu=cu)
+
+
+def _packed_on_device(r):      # what a packed call holds: q [T, H, D] as the kernels read it and cu_seqlens_q, contiguous
+    _core._require_device(r.cu)
+    return (r.q3 if _core._read_in_place(r.q3) else r.q3.contiguous()), r.cu.contiguous()
 
 
 def _t3(t: torch.Tensor) -> RsaTensor4:
@@ -664,16 +687,8 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         _check_count(name, val, 0)
     _check_count("score_splits", score_splits, 1, MAX_SCORE_SPLITS, optional=True)
     _check_top_p(top_p, score_scale, return_mass)
-    q3 = q
-    q, Bp = _packed_view("q", q, cu_seqlens_q, keys, None)
-    if Bp is not None and q_len is not None:
-        raise ValueError("q_len belongs to a padded q: with cu_seqlens_q the rows of an item are cu_seqlens_q[b + 1] - cu_seqlens_q[b]")
-    if Bp is None and max_q_len is not None:
-        raise ValueError("max_q_len belongs to cu_seqlens_q")
-    B, H, Hkv, Sq, Sk, D = _check_operands(q, keys, pooled=pooled, bounds=bound)
-    if Bp is not None:
-        T = Sq
-        cu, Sq = _check_packed("cu_seqlens_q", cu_seqlens_q, max_q_len, B, T)
+    r = _query_rows(q, q_len, cu_seqlens_q, max_q_len, keys, None, lambda q4: _check_operands(q4, keys, pooled=pooled, bounds=bound))
+    packed, q, B, H, Hkv, Sq, Sk, D = r.kind == "packed", r.q4, r.B, r.H, r.Hkv, r.Sq, r.Sk, r.D
     if pooled:      # the cache holds NK blocks: the capacity is taken as NK * block
         Sk *= blk
     NQ, NK = -(-Sq // blk), _key_blocks(Sk, blk)
@@ -687,9 +702,8 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
     kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
     q_dev = _row_limit(rows, B, Sq, dev)
     L = _lib.lib()
-    if Bp is not None:
-        _core._require_device(cu)
-        q = q3 if _core._read_in_place(q3) else q3.contiguous()
+    if packed:
+        q, cu = _packed_on_device(r)
     else:
         q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
     base = "rsa_block_select_bound" if bound else "rsa_block_select_pooled" if pooled else "rsa_block_select"
@@ -711,12 +725,12 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         mass = torch.empty((B, Hl, NQ), dtype=torch.float32, device=dev) if return_mass else None
         scale = 1.0 / ((H // Hl) * math.sqrt(D)) if score_scale is None else float(score_scale)
         budget = (int(round(float(top_p) * 65536.0)), scale * LOG2_E, _ptr(mass))
-    if q_dev is not None or (bound and Bp is None):
+    if q_dev is not None or (bound and not packed):
         budget = (budget or (-1, 0.0, None)) + (_ptr(q_dev),)
-    tq = _core._t4(q) if Bp is None else _t3(q)
-    if Bp is not None:      # T in front, M where Sq stood, cu_seqlens_q and the scan's scratch where q_len stood
-        entry, shape = base + "_packed", (T,) + shape
-        cu, items = cu.contiguous(), torch.empty((2 * (B + 1),), dtype=torch.int32, device=dev)
+    tq = _t3(q) if packed else _core._t4(q)
+    if packed:              # T in front, M where Sq stood, cu_seqlens_q and the scan's scratch where q_len stood
+        entry, shape = base + "_packed", (r.T,) + shape
+        items = torch.empty((2 * (B + 1),), dtype=torch.int32, device=dev)
         budget = (budget or (-1, 0.0, None)) + (cu.data_ptr(), items.data_ptr())
     with torch.cuda.device(dev):
         _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, NQ, NK, tq, source, _ptr(kv_dev), kv_valid,
@@ -1124,16 +1138,9 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
     entries: q [T, H, D], T in front, M = max_q_len where Sq stood, cu_seqlens_q where q_len stood."""
     blk = _check_block("block-sparse extend" if ext else "block-sparse decode", block_size)
     _check_count("blocks_per_split", blocks_per_split, 1, optional=True)
-    q3 = q
-    q, Bp = _packed_view("q", q, cu_seqlens_q if ext else None, k, block_table)
-    if Bp is not None and q_len is not None:
-        raise ValueError("q_len belongs to a padded q: with cu_seqlens_q the rows of an item are cu_seqlens_q[b + 1] - cu_seqlens_q[b]")
-    if Bp is None and max_q_len is not None:
-        raise ValueError("max_q_len belongs to cu_seqlens_q")
-    B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v, dims=(64, 128), block_table=block_table, blk=blk, kv8_ok=True)
-    if Bp is not None:      # Sq is M from here on: the rows of an item at most
-        T = Sq
-        cu, Sq = _check_packed("cu_seqlens_q", cu_seqlens_q, max_q_len, B, T)
+    r = _query_rows(q, q_len, cu_seqlens_q if ext else None, max_q_len, k, block_table,
+                    lambda q4: _check_operands(q4, k, v, dims=(64, 128), block_table=block_table, blk=blk, kv8_ok=True))
+    packed, q, B, H, Hkv, Sq, Sk, D, T = r.kind == "packed", r.q4, r.B, r.H, r.Hkv, r.Sq, r.Sk, r.D, r.T
     _check_scales(k, Hkv, k_scale=k_scale, v_scale=v_scale)
     NQ = -(-Sq // blk) if ext else 1
     if Sq > blk and not ext:
@@ -1186,42 +1193,34 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
     bps = 0 if blocks_per_split is None else int(blocks_per_split)
     need = ctypes.c_size_t(0)
     kv8 = k.dtype == E4M3
-    if Bp is not None:
-        _core._require_device(cu)
-        q, cu = (q3 if _core._read_in_place(q3) else q3.contiguous()), cu.contiguous()
+    if packed:
+        q, cu = _packed_on_device(r)
         _lib.check(L.rsa_block_sparse_extend_packed_bytes(T, B, H, Hkv, Hl, Sq, D, blk, NK, bps, ctypes.byref(need), None),
                    "rsa_block_sparse_extend_packed_bytes")
-        ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
-        out = torch.empty((T, H, D), dtype=q.dtype, device=dev)
-        lse = torch.empty((T, H), dtype=torch.float32, device=dev) if return_lse else None
-        entry = "rsa_block_sparse_extend_packed" + ("_kv8" if kv8 else "")
-        held = [_scale_arg(sc, Hkv, dev) for sc in (k_scale, v_scale)] if kv8 else []
-        with torch.cuda.device(dev):
-            _lib.check(getattr(L, entry)(T, B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
-                                         int(bool(causal)), scale, _t3(q), _core._t4(k), _core._t4(v), *table, cols.data_ptr(),
-                                         counts.data_ptr(), bps, ws.data_ptr(), need.value,
-                                         RsaOut4(out.data_ptr(), 0, out.stride(1), out.stride(0)), _ptr(lse),
-                                         *[t.data_ptr() for t in held], cu.data_ptr(), _core._stream()), entry)
-        return (out, lse) if return_lse else out
-    q = _core._as_bhsd(q)
-    if ext:
-        _lib.check(L.rsa_block_sparse_extend_bytes(B, H, Hkv, Hl, Sq, D, blk, NK, bps, ctypes.byref(need)),
-                   "rsa_block_sparse_extend_bytes")
+        shape, entry = (T, H, D), "rsa_block_sparse_extend_packed"
     else:
-        _lib.check(L.rsa_block_sparse_decode_bytes(B, H, Hkv, Hl, Sq, D, NK, bps, ctypes.byref(need)),
-                   "rsa_block_sparse_decode_bytes")
+        q = _core._as_bhsd(q)
+        if ext:
+            _lib.check(L.rsa_block_sparse_extend_bytes(B, H, Hkv, Hl, Sq, D, blk, NK, bps, ctypes.byref(need)),
+                       "rsa_block_sparse_extend_bytes")
+        else:
+            _lib.check(L.rsa_block_sparse_decode_bytes(B, H, Hkv, Hl, Sq, D, NK, bps, ctypes.byref(need)),
+                       "rsa_block_sparse_decode_bytes")
+        shape = (B, H, Sq, D)
+        entry = ("rsa_block_sparse_extend" if ext else "rsa_block_sparse_decode") + ("_ragged" if q_dev is not None else "")
+    entry += "_kv8" if kv8 else ""
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
-    out = torch.empty((B, H, Sq, D), dtype=q.dtype, device=dev)
-    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
-    entry = ("rsa_block_sparse_extend" if ext else "rsa_block_sparse_decode") + ("_ragged" if q_dev is not None else "") \
-        + ("_kv8" if kv8 else "")
+    out = torch.empty(shape, dtype=q.dtype, device=dev)
+    lse = torch.empty(shape[:-1], dtype=torch.float32, device=dev) if return_lse else None
     held = [_scale_arg(sc, Hkv, dev) for sc in (k_scale, v_scale)] if kv8 else []
-    if q_dev is not None:
-        held.append(q_dev)
+    if packed:      # T in front, M where Sq stood, q and out by their row and head strides, cu_seqlens_q where q_len stood
+        lead, tq, to, held = (T,), _t3(q), RsaOut4(out.data_ptr(), 0, out.stride(1), out.stride(0)), held + [cu]
+    else:
+        lead, tq, to, held = (), _core._t4(q), _out4(out), held + ([q_dev] if q_dev is not None else [])
     with torch.cuda.device(dev):
-        _lib.check(getattr(L, entry)(B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
-                                     int(bool(causal)), scale, _core._t4(q), _core._t4(k), _core._t4(v), *table,
-                                     cols.data_ptr(), counts.data_ptr(), bps, ws.data_ptr(), need.value, _out4(out), _ptr(lse),
+        _lib.check(getattr(L, entry)(*lead, B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
+                                     int(bool(causal)), scale, tq, _core._t4(k), _core._t4(v), *table, cols.data_ptr(),
+                                     counts.data_ptr(), bps, ws.data_ptr(), need.value, to, _ptr(lse),
                                      *[t.data_ptr() for t in held], _core._stream()), entry)
     return (out, lse) if return_lse else out
 

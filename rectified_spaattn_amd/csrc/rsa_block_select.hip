@@ -11,7 +11,7 @@
 //                              (a lane group computes a whole score: nothing is summed across workgroups)
 //   pool_key_bounds_kernel     pool_keys_kernel's min/max twin: per key block and channel the minimum and the maximum of the keys, into
 //                              the fp32 bounds cache [.., NK, 2, D] (rsa_pool_key_bounds; section 5.19)
-//   block_bound_score_kernel   block_score_kernel's twin over that cache: t = sum_d max(q_d mn_d, q_d mx_d), the upper bound of q . k
+//   block_score_kernel<BOUND>  block_score_kernel over that cache: t = sum_d max(q_d mn_d, q_d mx_d), the upper bound of q . k
 //                              over every key the block could hold (rsa_block_select_bound); the select kernels rank its keys LOADED
 //   block_select[_p]_kernel    one 256-thread workgroup per list row (b, list head, query block): top-k; top-p capped at top_k
 //
@@ -27,7 +27,7 @@
 // exp2 is __builtin_amdgcn_exp2f (v_exp_f32), the function of the attention kernels: exact at integer arguments.  Every fp32 sum has
 // a fixed order; histograms and weights are unsigned integer sums (at most 8192 weights of at most 2^18): two calls, the same bytes.
 #include "rsa_common.h"
-#include "rsa_packed.h"
+#include "rsa_rows.h"
 
 #include <math.h>
 #include <type_traits>
@@ -69,30 +69,16 @@ __device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
     return run;
 }
 
-// The ragged entries run instantiations of their own, RAG, which take the rows of each batch item, DEVICE
-// int32 q_len [B], as one more kernel argument behind the others (the pack Q: empty without RAG, so those kernels keep their
-// arguments and their code).  sel_row_count: q_len[b] clamped into [0, Sq]; Sq without RAG.
-__device__ __forceinline__ const int32_t* sel_q_len() { return nullptr; }
-__device__ __forceinline__ const int32_t* sel_q_len(const int32_t* q_len) { return q_len; }
-// The packed entry hands the pool kernel a second pointer behind the row counts: row_start, DEVICE int32
-// [B + 1], the first row of each item in q [T, H, D] (both written by pk_scan_kernel: sanitised).  Its other kernels are the ragged
-// instantiations over the sanitised row counts.
-__device__ __forceinline__ const int32_t* sel_q_len(const int32_t* q_len, const int32_t*) { return q_len; }
-__device__ __forceinline__ long sel_row_base(long) { return 0; }
-__device__ __forceinline__ long sel_row_base(long, const int32_t*) { return 0; }
-__device__ __forceinline__ long sel_row_base(long b, const int32_t*, const int32_t* row_start) { return row_start[b]; }
-template <bool RAG>
-__device__ __forceinline__ int sel_row_count(const int32_t* __restrict__ q_len, int b, int Sq) {
-    if constexpr (RAG) return min(max(q_len[b], 0), Sq);
-    else return Sq;
-}
-
-// Visible blocks of list row (b, i): a prefix [0, nvis) of the row.  Sq: the batch item's row count (sel_row_count); RAG: a query
-// block without a row sees nothing.
-template <bool RAG = false>
+// The kernels that ask for a batch item's query rows are instantiated over the row source (rsa_rows.h; DESIGN.md sections 5.17, 5.18),
+// their last argument: RowsPadded for the entries without row counts (no size: those kernels keep their arguments and their code),
+// RowsCounted for the ragged entries and, over the scan's sanitised counts, for the packed ones, whose pool kernel alone also
+// needs each item's first row of q [T, H, D]: RowsAt.
+// Visible blocks of list row (b, i): a prefix [0, nvis) of the row.  Sq: the batch item's row count (Rows::count); SHORT (Rows::SHORT):
+// a query block without a row sees nothing.
+template <bool SHORT = false>
 __device__ __forceinline__ int sel_visible(int len, int Sq, int blk, int NK, int i, int causal) {
     const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
-    if (RAG && r0 >= Sq) return 0;
+    if (SHORT && r0 >= Sq) return 0;
     int nvis = min(NK, (len + blk - 1) / blk);
     if (causal) nvis = r1 + off < 0 ? 0 : (int)min((long)nvis, (r1 + off) / blk + 1);
     return nvis;
@@ -178,11 +164,11 @@ __device__ __forceinline__ float sel_pool_mean(const typename SelElem<Tag>::type
     return sel_pool_block<Tag>(base, stride_s, rows, D, red) / (float)rows;
 }
 
-template <typename Tag, bool RAG = false, typename... Q>
+template <typename Tag, typename Rows, typename At>
 __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q, rsa_tensor4 k, int H, int Hkv, int Hl, int Sq,
                                                                    int Sk, int D, int blk, int NQ, int NK, long q_jobs,
                                                                    const int32_t* __restrict__ kv_len, int kv_valid,
-                                                                   float* __restrict__ kbar, float* __restrict__ qsum, Q... q_len) {
+                                                                   float* __restrict__ kbar, float* __restrict__ qsum, Rows src, At at) {
     __shared__ float red[4][128];
     const int tid = threadIdx.x;
     long job = blockIdx.x;
@@ -192,16 +178,16 @@ __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q
         const int hl = (int)(bh % Hl), gl = H / Hl;
         const long b = bh / Hl;
         const long r0 = (long)i * blk;
-        // the block's rows below the batch item's count (uniform over the workgroup); RAG: none, in a block of padding -- the block's
-        // value is then 0, q is not read and cnt is not used
-        const int rows = (int)min((long)blk, (long)sel_row_count<RAG>(sel_q_len(q_len...), (int)b, Sq) - r0);
+        // the block's rows below the batch item's count (uniform over the workgroup); a short item: none, in a block of padding --
+        // the block's value is then 0, q is not read and cnt is not used
+        const int rows = (int)min((long)blk, (long)src.count((int)b, Sq) - r0);
         const float cnt = (float)rows;
         float tot = 0.f;
         // the list head's query heads, ascending: each head's own mean, then the sum
-        for (int u = 0; (!RAG || rows > 0) && u < gl; ++u) {
+        for (int u = 0; (!Rows::SHORT || rows > 0) && u < gl; ++u) {
             const unsigned short* base = static_cast<const unsigned short*>(q.ptr) + b * q.stride_b +
                                          (long)(hl * gl + u) * q.stride_h + r0 * q.stride_s;
-            if constexpr (sizeof...(Q) == 2) base += sel_row_base(b, q_len...) * q.stride_s;    // packed: the item's first row
+            base += at.first(b) * q.stride_s;       // (0 where q has a batch dimension)
             tot += sel_pool_block<Tag>(base, q.stride_s, rows, D, red) / cnt;
         }
         if (tid < D) qsum[job * D + tid] = tot;
@@ -418,28 +404,6 @@ __device__ __forceinline__ void sel_score_blocks(const float* __restrict__ kb, c
     }
 }
 
-// The score pass of the pooled selection spread over `splits` workgroups per list row: workgroup (row, part) writes the keys of
-// its slice of the visible blocks to wkeys[row, :].
-template <int L, bool RAG = false, typename... Q>
-__global__ __launch_bounds__(SEL_NT) void block_score_kernel(const float* __restrict__ kbar, const float* __restrict__ qsum, int Hkv,
-                                                             int Hl, int Sq, int Sk, int blk, int NQ, int NK, int splits,
-                                                             const int32_t* __restrict__ kv_len, int kv_valid, int causal,
-                                                             unsigned* __restrict__ wkeys, Q... q_len) {
-    constexpr int D = 4 * L;
-    const int part = (int)(blockIdx.x % (unsigned)splits);
-    const long row = blockIdx.x / (unsigned)splits;
-    const int i = (int)(row % NQ);
-    const long bh = row / NQ;
-    const int hl = (int)(bh % Hl);
-    const long b = bh / Hl;
-    const int hk = hl / (Hl / Hkv);
-    const int nvis = sel_visible<RAG>(sel_key_limit(kv_len, (int)b, kv_valid, Sk), sel_row_count<RAG>(sel_q_len(q_len...), (int)b, Sq),
-                                      blk, NK, i, causal);
-    const int chunk = (NK + splits - 1) / splits;
-    const int lo = part * chunk, hi = min(lo + chunk, nvis);
-    sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, lo, hi, wkeys + row * NK);
-}
-
 // The bound scores of the key blocks [lo, hi) of one list row: sel_score_blocks over the bounds cache.  kb:
 // the (min, max) row pairs of (b, K/V head), 2 D floats a block.  t = sum over d of max(q_d mn_d, q_d mx_d): per lane four terms,
 // each the larger of two separately rounded fp32 products, added as ((x + y) + z) + w; the lanes meet over the same xor strides.
@@ -471,12 +435,14 @@ __device__ __forceinline__ void sel_bound_score_blocks(const float* __restrict__
     }
 }
 
-// block_score_kernel over the bounds cache kbounds [B, Hkv, NK, 2, D]: the score pass of the bound selection, at every `splits`.
-template <int L, bool RAG = false, typename... Q>
-__global__ __launch_bounds__(SEL_NT) void block_bound_score_kernel(const float* __restrict__ kbounds, const float* __restrict__ qsum,
-                                                                   int Hkv, int Hl, int Sq, int Sk, int blk, int NQ, int NK, int splits,
-                                                                   const int32_t* __restrict__ kv_len, int kv_valid, int causal,
-                                                                   unsigned* __restrict__ wkeys, Q... q_len) {
+// The score pass of the pooled selection spread over `splits` workgroups per list row: workgroup (row, part) writes the keys of
+// its slice of the visible blocks to wkeys[row, :].  BOUND: kbar is the bounds cache kbounds [B, Hkv, NK, 2, D] and the scores are
+// the bound selection's, at every `splits`.
+template <int L, bool BOUND, typename Rows>
+__global__ __launch_bounds__(SEL_NT) void block_score_kernel(const float* __restrict__ kbar, const float* __restrict__ qsum, int Hkv,
+                                                             int Hl, int Sq, int Sk, int blk, int NQ, int NK, int splits,
+                                                             const int32_t* __restrict__ kv_len, int kv_valid, int causal,
+                                                             unsigned* __restrict__ wkeys, Rows src) {
     constexpr int D = 4 * L;
     const int part = (int)(blockIdx.x % (unsigned)splits);
     const long row = blockIdx.x / (unsigned)splits;
@@ -485,11 +451,11 @@ __global__ __launch_bounds__(SEL_NT) void block_bound_score_kernel(const float* 
     const int hl = (int)(bh % Hl);
     const long b = bh / Hl;
     const int hk = hl / (Hl / Hkv);
-    const int nvis = sel_visible<RAG>(sel_key_limit(kv_len, (int)b, kv_valid, Sk), sel_row_count<RAG>(sel_q_len(q_len...), (int)b, Sq),
-                                      blk, NK, i, causal);
+    const int nvis = sel_visible<Rows::SHORT>(sel_key_limit(kv_len, (int)b, kv_valid, Sk), src.count((int)b, Sq), blk, NK, i, causal);
     const int chunk = (NK + splits - 1) / splits;
     const int lo = part * chunk, hi = min(lo + chunk, nvis);
-    sel_bound_score_blocks<L>(kbounds + ((b * Hkv + hk) * NK) * 2 * D, qsum + row * D, lo, hi, wkeys + row * NK);
+    if constexpr (BOUND) sel_bound_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * 2 * D, qsum + row * D, lo, hi, wkeys + row * NK);
+    else sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, lo, hi, wkeys + row * NK);
 }
 
 // ---- select ----------------------------------------------------------------------------------------------------------------------
@@ -579,7 +545,7 @@ __device__ __forceinline__ void sel_radix(const unsigned* keys, int nvis, SelFor
 
 // One list row by one workgroup.  LOADED = 0: the scores are computed here (r.kbar, r.qsum); LOADED = 1: their keys are loaded from
 // r.wkeys (block_score_kernel).  BUDGET = false: top-k (p16, c and mass are not read); true: top-p capped at top_k.
-template <int L, int LOADED, bool BUDGET, bool RAG>
+template <int L, int LOADED, bool BUDGET, bool SHORT>
 __device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c, float* __restrict__ mass,
                                              const int32_t* __restrict__ q_len) {
     extern __shared__ unsigned keys[];              // [NK]: the scores of the visible blocks as ordered keys
@@ -598,11 +564,11 @@ __device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c
     const long b = bh / r.Hl;
     const int hk = hl / (r.Hl / r.Hkv);
     const int len = sel_key_limit(r.kv_len, (int)b, r.kv_valid, r.Sk);
-    const int Sq = sel_row_count<RAG>(q_len, (int)b, r.Sq);    // the batch item's rows: r1 and off count from them
+    const int Sq = SHORT ? RowsCounted{q_len}.count((int)b, r.Sq) : r.Sq;      // the batch item's rows: r1 and off count from them
 
     // 1. visible blocks: a prefix [0, nvis) of the row; forced blocks: [0, kf) and [flo, fhi] within it
     const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
-    const int nvis = sel_visible<RAG>(len, Sq, blk, NK, i, r.causal);
+    const int nvis = sel_visible<SHORT>(len, Sq, blk, NK, i, r.causal);
     SelForced forced = {min(r.keep_first, nvis), 1, 0};
     if (r.keep_local >= 1 && nvis > 0) {
         const long jd_lo = max(r0 + off, 0L) / blk, jd_hi = min(max(r1 + off, 0L), (long)len - 1) / blk;
@@ -720,15 +686,14 @@ __device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c
     }
 }
 
-template <int L, int LOADED, bool RAG = false, typename... Q>
-__global__ __launch_bounds__(SEL_NT) void block_select_kernel(const sel_rows r, Q... q_len) {
-    sel_row_body<L, LOADED, false, RAG>(r, 0, 0.f, nullptr, sel_q_len(q_len...));
+template <int L, int LOADED, typename Rows>
+__global__ __launch_bounds__(SEL_NT) void block_select_kernel(const sel_rows r, Rows src) {
+    sel_row_body<L, LOADED, false, Rows::SHORT>(r, 0, 0.f, nullptr, src.counts());
 }
 
-template <int L, int LOADED, bool RAG = false, typename... Q>
-__global__ __launch_bounds__(SEL_NT) void block_select_p_kernel(const sel_rows r, int p16, float c, float* __restrict__ mass,
-                                                                Q... q_len) {
-    sel_row_body<L, LOADED, true, RAG>(r, p16, c, mass, sel_q_len(q_len...));
+template <int L, int LOADED, typename Rows>
+__global__ __launch_bounds__(SEL_NT) void block_select_p_kernel(const sel_rows r, int p16, float c, float* __restrict__ mass, Rows src) {
+    sel_row_body<L, LOADED, true, Rows::SHORT>(r, p16, c, mass, src.counts());
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
@@ -751,46 +716,45 @@ static void sel_with_lanes(int D, F f) {
     }
 }
 
-// The select kernel over `rows` list rows: LOADED from r.wkeys, the top-p kernel with a budget; with q_len (the ragged entries:
-// the rows of each batch item) their RAG instantiations.
+// The one place that maps a call's row counts to the row source its kernels run over: f(RowsCounted) with q_len (the ragged
+// entries' counts, or the scan's for the packed ones), f(RowsPadded) without.
+template <typename F>
+static void sel_with_rows(const int32_t* q_len, F f) {
+    if (q_len) f(RowsCounted{q_len});
+    else f(RowsPadded{});
+}
+
+// The select kernel over `rows` list rows: LOADED from r.wkeys, the top-p kernel with a budget.
 static int sel_launch_select(int D, long rows, const sel_rows& r, const sel_top_p* p, const int32_t* q_len, hipStream_t s) {
     const dim3 grid((unsigned)rows);
     const size_t lds = (size_t)r.NK * sizeof(unsigned);
     sel_with_lanes(D, [&](auto lanes) {
-        constexpr int L = decltype(lanes)::value;
-        if (q_len) {
-            if (p && r.wkeys) block_select_p_kernel<L, 1, true><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass, q_len);
-            else if (p) block_select_p_kernel<L, 0, true><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass, q_len);
-            else if (r.wkeys) block_select_kernel<L, 1, true><<<grid, SEL_NT, lds, s>>>(r, q_len);
-            else block_select_kernel<L, 0, true><<<grid, SEL_NT, lds, s>>>(r, q_len);
-        } else if (p && r.wkeys) block_select_p_kernel<L, 1><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass);
-        else if (p) block_select_p_kernel<L, 0><<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass);
-        else if (r.wkeys) block_select_kernel<L, 1><<<grid, SEL_NT, lds, s>>>(r);
-        else block_select_kernel<L, 0><<<grid, SEL_NT, lds, s>>>(r);
+        sel_with_rows(q_len, [&](auto src) {
+            constexpr int L = decltype(lanes)::value;
+            using R = decltype(src);
+            auto* top_p = r.wkeys ? block_select_p_kernel<L, 1, R> : block_select_p_kernel<L, 0, R>;
+            auto* top_k = r.wkeys ? block_select_kernel<L, 1, R> : block_select_kernel<L, 0, R>;
+            if (p) top_p<<<grid, SEL_NT, lds, s>>>(r, p->p16, p->c, p->mass, src);
+            else top_k<<<grid, SEL_NT, lds, s>>>(r, src);
+        });
     });
     return rsa_launch_status();
 }
 
-// The pool kernel over the query jobs of r's rows and k_jobs key jobs behind them (none: k and kbar are not touched).
+// The pool kernel over the query jobs of r's rows and k_jobs key jobs behind them (none: k and kbar are not touched).  row_start: the
+// packed entry, q [T, H, D] behind stride_h and stride_s, item b from row row_start[b].
 static int sel_launch_pool(int dtype, int H, int D, rsa_tensor4 q, rsa_tensor4 k, long q_jobs, long k_jobs, const sel_rows& r,
                            float* kbar, float* qsum, const int32_t* q_len, hipStream_t s, const int32_t* row_start = nullptr) {
     const dim3 grid((unsigned)(q_jobs + k_jobs));
-    if (row_start) {        // the packed entry: q [T, H, D] behind stride_h and stride_s, item b from row row_start[b]
-        auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag, true, const int32_t*, const int32_t*>
-                                         : block_select_pool_kernel<fp16_tag, true, const int32_t*, const int32_t*>;
+    auto launch = [&](auto src, auto at) {
+        using R = decltype(src);
+        using A = decltype(at);
+        auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag, R, A> : block_select_pool_kernel<fp16_tag, R, A>;
         kernel<<<grid, SEL_NT, 0, s>>>(q, k, H, r.Hkv, r.Hl, r.Sq, r.Sk, D, r.blk, r.NQ, r.NK, q_jobs, r.kv_len, r.kv_valid, kbar, qsum,
-                                       q_len, row_start);
-        return rsa_launch_status();
-    }
-    if (q_len) {
-        auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag, true, const int32_t*>
-                                         : block_select_pool_kernel<fp16_tag, true, const int32_t*>;
-        kernel<<<grid, SEL_NT, 0, s>>>(q, k, H, r.Hkv, r.Hl, r.Sq, r.Sk, D, r.blk, r.NQ, r.NK, q_jobs, r.kv_len, r.kv_valid, kbar, qsum,
-                                       q_len);
-        return rsa_launch_status();
-    }
-    auto* kernel = dtype == RSA_BF16 ? block_select_pool_kernel<bf16_tag> : block_select_pool_kernel<fp16_tag>;
-    kernel<<<grid, SEL_NT, 0, s>>>(q, k, H, r.Hkv, r.Hl, r.Sq, r.Sk, D, r.blk, r.NQ, r.NK, q_jobs, r.kv_len, r.kv_valid, kbar, qsum);
+                                       src, at);
+    };
+    if (row_start) launch(RowsCounted{q_len}, RowsAt{row_start});
+    else sel_with_rows(q_len, [&](auto src) { launch(src, RowsPadded{}); });
     return rsa_launch_status();
 }
 
@@ -980,7 +944,7 @@ struct SelPacked {
 
 // The body of rsa_block_select_pooled and rsa_block_select_pooled_p (top_p NULL: top-k).  r: the call's arguments; Sk, kbar, qsum
 // and wkeys are set here.  pk: the packed entry (r.Sq = M; q_len is then set here, to the scan's row counts).  bound: pooled_k is the
-// bounds cache (section 5.19) -- the score pass is then block_bound_score_kernel at every split count, one included, and the select
+// bounds cache (section 5.19) -- the score pass is then block_score_kernel<L, true> at every split count, one included, and the select
 // kernels run LOADED: they gain no form of their own.
 static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const float* pooled_k, int score_splits, void* ws,
                           size_t ws_bytes, sel_rows r, const sel_top_p* top_p, const int32_t* q_len, void* stream,
@@ -1009,29 +973,16 @@ static int sel_pooled_run(int B, int H, int D, int dtype, rsa_tensor4 q, const f
     if (pk) pk_scan_launch(pk->cu, B, pk->T, r.Sq, r.blk, 0, 0, pk->items, pk->items + B + 1, nullptr, s);
     int rc = sel_launch_pool(dtype, H, D, q, q, q_jobs, 0, r, nullptr, qsum, q_len, s, pk ? pk->items : nullptr);    // the pooled queries
     if (rc != RSA_OK) return rc;
-    if (bound) {
+    if (bound || splits > 1) {
+        const dim3 grid((unsigned)(q_jobs * splits));
         sel_with_lanes(D, [&](auto lanes) {
-            constexpr int L = decltype(lanes)::value;
-            const dim3 grid((unsigned)(q_jobs * splits));
-            if (q_len)
-                block_bound_score_kernel<L, true><<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK,
-                                                                          splits, r.kv_len, r.kv_valid, r.causal, wkeys, q_len);
-            else
-                block_bound_score_kernel<L><<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits,
-                                                                    r.kv_len, r.kv_valid, r.causal, wkeys);
-        });
-        rc = rsa_launch_status();
-        if (rc != RSA_OK) return rc;
-    } else if (splits > 1) {
-        sel_with_lanes(D, [&](auto lanes) {
-            constexpr int L = decltype(lanes)::value;
-            const dim3 grid((unsigned)(q_jobs * splits));
-            if (q_len)
-                block_score_kernel<L, true><<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits,
-                                                                    r.kv_len, r.kv_valid, r.causal, wkeys, q_len);
-            else
-                block_score_kernel<L><<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits, r.kv_len,
-                                                              r.kv_valid, r.causal, wkeys);
+            sel_with_rows(q_len, [&](auto src) {
+                constexpr int L = decltype(lanes)::value;
+                using R = decltype(src);
+                auto* kernel = bound ? block_score_kernel<L, true, R> : block_score_kernel<L, false, R>;
+                kernel<<<grid, SEL_NT, 0, s>>>(pooled_k, qsum, r.Hkv, r.Hl, r.Sq, r.Sk, r.blk, r.NQ, r.NK, splits, r.kv_len, r.kv_valid,
+                                               r.causal, wkeys, src);
+            });
         });
         rc = rsa_launch_status();
         if (rc != RSA_OK) return rc;

@@ -22,36 +22,39 @@
 // their scores are replaced by selection, their V rows are zeroed on the way into LDS, and blocks without a key below the limit
 // (or with a list / table entry out of range) are not read at all.  No atomics: the same inputs give the same bytes.
 //
-// The e4m3 cache (rsa_block_sparse_decode_kv8) is the same two kernels instantiated over the cache's
-// element: Tag = kv8_tag<query type>.  K and V are then one-byte codes with one fp32 scale per K/V head: a lane loads 8 bytes of K
-// where it loads 16 (same keys, same d range) and half as many 16-byte pieces of V, and the codes become the query's 2-byte type in
-// registers (the packed scaled conversions with a unit scale: exact, every finite e4m3 value is a bf16 and an fp16).  The K scale multiplies the fp32
-// score behind the MFMA chain, the V scale the merged row once; the V image, the MFMAs, the softmax and the meet are the code below.
+// The cache's element.  The e4m3 cache (the _kv8 entries) is the same two kernels instantiated over Tag =
+// kv8_tag<query type>.  K and V are then one-byte codes with one fp32 scale per K/V head: a lane loads 8 bytes of K where it loads
+// 16 (same keys, same d range) and half as many 16-byte pieces of V, and the codes become the query's 2-byte type in registers (the
+// packed scaled conversions with a unit scale: exact, every finite e4m3 value is a bf16 and an fp16).  The K scale multiplies the
+// fp32 score behind the MFMA chain, the V scale the merged row once; the V image, the MFMAs, the softmax and the meet are the code
+// below.
 //
-// Extend (rsa_block_sparse_extend, rsa_block_sparse_extend_kv8) is the same two kernels instantiated with
-// EXT: any number of query rows and query blocks, any number of heads in a unit.  A workgroup then serves a ROW GROUP (DecGroups: at
-// most 64 rows of one batch item, unit and query block) where the decode kernel serves a whole unit: the list row is the query
-// block's, a row's causal limit comes from its index in the whole call, a chunk that starts at or beyond the limit of the group's
-// last row is skipped before its loads (byte-neutral), and partials and the merge are indexed by (row group, split).  The decode
-// instantiations keep their arguments' layout and their code: the group arithmetic lives behind `if constexpr (EXT)`.
-//
-// Ragged (rsa_block_sparse_extend_ragged, rsa_block_sparse_extend_ragged_kv8) is the extend kernels with a
-// row count per batch item, n_b = q_len[b] clamped into [0, Sq]: instantiations of their own (RAG, whose arguments are DecRag: the
-// extend kernels' and q_len behind them), so the decode and the extend instantiations keep their code.  n_b stands where Sq is a
-// row count -- the rows of the group (qn), the group's and each row's causal limit, the merge's row test -- and nowhere else: the
-// grid, the groups and the partials are the padded call's.  A group whose first row is at or beyond n_b leaves before it reads a
-// list entry, a table entry or a K/V byte; the merge writes its rows (0, -inf) unread.
-//
-// Packed (rsa_block_sparse_extend_packed, rsa_block_sparse_extend_packed_kv8) is a third family, PK (arguments:
-// DecPk, the extend kernels' and the packed batch behind them): q, out are [T, H, D] and item b is rows [s_b, s_b + n_b) of them.  A
-// one-workgroup scan (rsa_packed.h) sanitises cu_seqlens_q into row_start and piece_start, the exclusive prefix sums of the items'
-// row groups, at the head of the workspace.  Split workgroup (piece p, unit, hc) finds its item by a bounded binary search over
-// piece_start -- the live groups are the launch's first workgroups by construction, and p >= piece_start[B] leaves before it reads
-// a list entry, a table entry or a K/V byte -- and stands where the ragged group stands from there on: n_b for the row count, s_b
-// added to the row of q.  Partials are indexed by (compact group, split); the merge runs one thread group per row t of [0, T),
-// finds the item over row_start and writes rows outside every item (0, -inf) before it looks at a list row or a partial.
+// The row form: the one further template parameter of both kernels, which says whose rows a workgroup serves.
+//   DecodeForm         rsa_block_sparse_decode: a whole unit, at most 64 rows of one query block.  Arguments: DecArgs / DecMergeArgs.
+//   ExtendForm<Rows>   the extend entries (section 5.16): any number of query rows, query blocks and heads of a unit.  A workgroup
+//                      serves a ROW GROUP (DecGroups: at most 64 rows of one batch item, unit and query block): the list row is the
+//                      query block's, a row's causal limit comes from its index in its item, a chunk that starts at or beyond the
+//                      limit of the group's last row is skipped before its loads (byte-neutral), and partials and the merge are
+//                      indexed by (row group, split).  Arguments: decode's, the row groups and the row source behind them.  Rows
+//                      (rsa_rows.h) says where an item's rows are and how many:
+//     RowsPadded       rsa_block_sparse_extend: q [B, H, Sq, D], every item Sq rows.  Adds no argument.
+//     RowsCounted      the _ragged entries (section 5.17): n_b = q_len[b] clamped into [0, Sq] stands where Sq is a row count -- the
+//                      rows of the group (qn), the group's and each row's causal limit, the merge's row test -- and nowhere else:
+//                      the grid, the groups and the partials are the padded call's.  A group whose first row is at or beyond n_b
+//                      leaves before it reads a list entry, a table entry or a K/V byte; the merge writes its rows (0, -inf) unread.
+//     RowsPacked       the _packed entries (section 5.18): q, out are [T, H, D], item b is rows [s_b, s_b + n_b) of them, Sq holds M.
+//                      A one-workgroup scan (rsa_rows.h) sanitises cu_seqlens_q into row_start and piece_start, the exclusive
+//                      prefix sums of the items' row groups, at the head of the workspace.  Split workgroup (piece p, unit, hc)
+//                      finds its item by a bounded binary search over piece_start -- the live groups are the launch's first
+//                      workgroups by construction, and p >= piece_start[B] leaves before it reads a list entry, a table entry or a
+//                      K/V byte -- and stands where the counted group stands from there on, s_b added to the row of q.  Partials
+//                      are indexed by (compact group, split); the merge runs one thread group per row t of [0, T), finds the item
+//                      over row_start and writes rows outside every item (0, -inf) before it looks at a list row or a partial.
+// A combination that does not exist (row counts without row groups, counts beside cu_seqlens_q) has no type.  The statements that
+// find a workgroup's rows stand in the kernels under `if constexpr` on the form, in the order that keeps every kernel's instruction
+// stream what it was (profiles/rows_refactor_isa.md).
 #include "rsa_attn.h"
-#include "rsa_packed.h"
+#include "rsa_rows.h"
 
 #include <math.h>
 
@@ -96,20 +99,20 @@ struct DecExt : A {
     DecGroups g;
     int qblk;                   // rows of a query block (the merge's base struct holds no block size)
 };
-// The ragged kernels' arguments: the extend kernels' and the rows of each batch item behind them.
-template <typename A>
-struct DecRag : DecExt<A> {
-    const int32_t* q_len;       // DEVICE [B], clamped into [0, Sq] in the kernel
+
+// The row form a kernel is instantiated over.  Args<A>: its arguments where decode takes A -- A itself, or A, the row groups and
+// the row source behind them (a padded source adds nothing; Sq holds M, the rows of an item at most, in the packed call).
+struct DecodeForm {
+    static constexpr bool EXT = false, BATCHED = true, SHORT = false;
+    template <typename A> using Args = A;
 };
-// The packed kernels' arguments: the extend kernels' and the packed batch behind them (Sq holds M, the rows of an item at most).
-template <typename A>
-struct DecPk : DecExt<A> {
-    const int32_t *row_start, *piece_start;     // DEVICE [B + 1] each, written by pk_scan_kernel: sanitised, ascending
-    int pk_B, pk_steps;                         // items; halvings of the search (ceil(log2 B))
+template <typename R>
+struct ExtendForm {
+    static constexpr bool EXT = true, BATCHED = R::BATCHED, SHORT = R::SHORT;
+    using Rows = R;
+    template <typename A> using Args = WithRows<DecExt<A>, R>;
+    R rows;                     // (host: the source the launch hands to both kernels)
 };
-template <typename A, bool EXT, bool RAG = false, bool PK = false>
-using DecArgsFor = typename std::conditional<
-    PK, DecPk<A>, typename std::conditional<RAG, DecRag<A>, typename std::conditional<EXT, DecExt<A>, A>::type>::type>::type;
 
 // The cache's element: the query's own 2-byte type (Tag = bf16_tag / fp16_tag), or e4m3 codes (kv8_tag<query type>).
 template <typename QTag>
@@ -119,6 +122,7 @@ struct DecCache {
     using Q = Tag;
     using elem = unsigned short;
     using Args = DecArgs;
+    using MergeArgs = struct DecMergeArgs;
     using kfrag = uint4;                // 8 elements of a key: one A fragment
     static constexpr bool kv8 = false;
     static constexpr int VPIECE = 8;    // elements of a 16-byte piece of V
@@ -128,6 +132,7 @@ struct DecCache<kv8_tag<QTag>> {
     using Q = QTag;
     using elem = unsigned char;
     using Args = DecArgs8;
+    using MergeArgs = struct DecMergeArgs8;
     using kfrag = uint2;
     static constexpr bool kv8 = true;
     static constexpr int VPIECE = 16;
@@ -182,10 +187,10 @@ __device__ __forceinline__ s16x4 dec_tr_read(const unsigned char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
-template <typename CTag, int D, int MT, bool EXT, bool RAG = false, bool PK = false>
+template <typename CTag, int D, int MT, typename Form>
 __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
-    DecArgsFor<typename DecCache<CTag>::Args, EXT, RAG, PK> a) {
-    static_assert((EXT || !(RAG || PK)) && !(RAG && PK), "row counts belong to the extend kernels, from q_len or from cu_seqlens_q");
+    const typename Form::template Args<typename DecCache<CTag>::Args> a) {
+    constexpr bool EXT = Form::EXT, PACKED = !Form::BATCHED, COUNTED = Form::SHORT && !PACKED;
     using Cache = DecCache<CTag>;
     using Tag = typename Cache::Q;      // the type of q, of the MFMA operands and of the output
     using KT = typename Cache::elem;
@@ -218,17 +223,17 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
         const int hc = g % a.g.HC;
         g /= a.g.HC;
         int qc;
-        if constexpr (PK) {
+        if constexpr (PACKED) {
             // packed: blockIdx.x = (piece * U + unit) * HC + hc over the QP pieces the host's bound allows.  The live pieces are
             // [0, piece_start[B]): the rest leave here.  Everything below is uniform: scalar loads, scalar registers.
             ext_unit = g % a.U;
             const int piece = g / a.U;
-            if (piece >= a.piece_start[a.pk_B]) return;
-            ext_b = pk_find(a.piece_start, a.pk_B, a.pk_steps, piece);
-            qc = piece - a.piece_start[ext_b];
-            pk_row0 = a.row_start[ext_b];
-            nrow = min(a.row_start[ext_b + 1] - pk_row0, a.Sq);
-        } else if constexpr (RAG) {
+            if (piece >= a.src.piece_start[a.src.B]) return;
+            ext_b = pk_find(a.src.piece_start, a.src.B, a.src.steps, piece);
+            qc = piece - a.src.piece_start[ext_b];
+            pk_row0 = (int)a.src.first(ext_b);
+            nrow = min(a.src.row_start[ext_b + 1] - pk_row0, a.Sq);
+        } else if constexpr (COUNTED) {
             // ragged: the workgroups are dealt query chunk by query chunk, (qc, b, unit, hc).  An item's live groups are its first
             // chunks, so the live groups of a batch of short items are the launch's first workgroups, side by side on the chip; in
             // the groups' own order they sit QC * HC apart and pile up on the few compute units that stride reaches.
@@ -248,9 +253,9 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
         qw = a.g.qg;
         nq = a.g.NQ;
         q0 = qb * a.blk + (qc - qb * a.g.cpb) * qw;
-        if constexpr (RAG) nrow = min(max(a.q_len[ext_b], 0), a.Sq);     // the batch item's rows: the causal offset counts from them
+        if constexpr (COUNTED) nrow = a.src.count(ext_b, a.Sq);     // the batch item's rows: the causal offset counts from them
         qn = min(qw, min((qb + 1) * a.blk, nrow) - q0);
-        if ((RAG || PK) && qn <= 0) return;     // (uniform) a group of padding rows: the merge writes them without a partial
+        if ((COUNTED || PACKED) && qn <= 0) return;     // (uniform) a group of padding rows: the merge writes them without a partial
         h0 = hc * a.g.gh;
         hn = min(a.g.gh, a.H / a.U - h0);
     }
@@ -289,7 +294,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
             qrow = ok ? q0 + qr : 0;
         }
         const unsigned short* qp = a.q + (long)b * a.qsb + (long)(unit * gu + hu) * a.qsh + (long)qrow * a.qss + 8 * lh;
-        if constexpr (PK) qp = a.q + (long)(unit * gu + hu) * a.qsh + (long)(pk_row0 + qrow) * a.qss + 8 * lh;
+        if constexpr (PACKED) qp = a.q + (long)(unit * gu + hu) * a.qsh + (long)(pk_row0 + qrow) * a.qss + 8 * lh;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const s16x8 f = rsa_q_frag<Tag>(qp + 32 * ks, ok, a.qk_scale);
@@ -514,38 +519,38 @@ struct DecMergeArgs8 : DecMergeArgs {
 };
 
 // D / 4 threads per output row, four channels each; the splits in ascending order.
-template <typename CTag, int D, bool EXT, bool RAG = false, bool PK = false>
-__global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
-    DecArgsFor<typename std::conditional<DecCache<CTag>::kv8, DecMergeArgs8, DecMergeArgs>::type, EXT, RAG, PK> a) {
+template <typename CTag, int D, typename Form>
+__global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(const typename Form::template Args<typename DecCache<CTag>::MergeArgs> a) {
     using Tag = typename DecCache<CTag>::Q;
     constexpr int TPR = D / 4;
     const long g = (long)blockIdx.x * DEC_NT + threadIdx.x;
     const long row = g / TPR;
     const int c = (int)(g % TPR);
     if (row >= a.rows) return;
+    constexpr bool EXT = Form::EXT, PACKED = !Form::BATCHED, COUNTED = Form::SHORT && !PACKED;
     int qrow = (int)(row % a.Sq), h = (int)((row / a.Sq) % a.H);
     long b = row / ((long)a.Sq * a.H);
     long orow = qrow;           // the row's place in out (behind b * osb: 0 in the packed call)
     int pk_piece0 = 0;
-    if constexpr (PK) {         // row = t * H + h over q's T rows: the item by search, the row's index in it, or no item at all
+    if constexpr (PACKED) {         // row = t * H + h over q's T rows: the item by search, the row's index in it, or no item at all
         h = (int)(row % a.H);
         orow = row / a.H;
-        b = pk_find(a.row_start, a.pk_B, a.pk_steps, (int)orow);
-        const int s0 = a.row_start[b];
+        b = a.src.item_of_row((int)orow);
+        const int s0 = a.src.row_start[b];
         qrow = (int)orow - s0;
-        if (qrow < 0 || qrow >= min(a.row_start[b + 1] - s0, a.Sq)) {      // 0 / -inf, no list row and no partial read
+        if (qrow < 0 || qrow >= min(a.src.row_start[b + 1] - s0, a.Sq)) {      // 0 / -inf, no list row and no partial read
             *reinterpret_cast<uint2*>(a.out + (long)h * a.osh + orow * a.oss + 4 * c) = make_uint2(0u, 0u);
             if (a.lse && c == 0) a.lse[row] = -INFINITY;
             return;
         }
-        pk_piece0 = a.piece_start[b];
+        pk_piece0 = a.src.piece_start[b];
     }
     const int gu = a.H / a.U, unit = h / gu, rr = (h % gu) * a.Sq + qrow;
     long p0 = ((b * a.U + unit) * a.nsplit) * a.R16 + rr;       // decode: the unit's partials, head-major rows
     long lrow = b * a.Hl + unit / (a.U / a.Hl);
     if constexpr (EXT) {        // the row's group and its place in it (DecGroups)
-        if constexpr (RAG) {
-            if (qrow >= min(max(a.q_len[b], 0), a.Sq)) {    // a padding row: 0 / -inf, no list row and no partial read
+        if constexpr (COUNTED) {
+            if (qrow >= min(max(a.src.q_len[b], 0), a.Sq)) {    // a padding row: 0 / -inf, no list row and no partial read
                 *reinterpret_cast<uint2*>(a.out + b * a.osb + (long)h * a.osh + (long)qrow * a.oss + 4 * c) = make_uint2(0u, 0u);
                 if (a.lse && c == 0) a.lse[row] = -INFINITY;
                 return;
@@ -553,7 +558,7 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
         }
         const int hu = h % gu, hc = hu / a.g.gh, qb = qrow / a.qblk, qi = qrow - qb * a.qblk, qcl = qi / a.g.qg;
         long grp = ((b * a.U + unit) * a.g.QC + qb * a.g.cpb + qcl) * a.g.HC + hc;
-        if constexpr (PK) grp = ((long)(pk_piece0 + qb * a.g.cpb + qcl) * a.U + unit) * a.g.HC + hc;    // the compact group
+        if constexpr (PACKED) grp = ((long)(pk_piece0 + qb * a.g.cpb + qcl) * a.U + unit) * a.g.HC + hc;    // the compact group
         p0 = (grp * a.nsplit) * a.R16 + (hu - hc * a.g.gh) * a.g.qg + (qi - qcl * a.g.qg);
         lrow = lrow * a.g.NQ + qb;
     }
@@ -588,213 +593,149 @@ __global__ __launch_bounds__(DEC_NT) void decode_merge_kernel(
     uint2 pk;
     pk.x = (unsigned)Elem<Tag>::from_f32(r[0]) | ((unsigned)Elem<Tag>::from_f32(r[1]) << 16);
     pk.y = (unsigned)Elem<Tag>::from_f32(r[2]) | ((unsigned)Elem<Tag>::from_f32(r[3]) << 16);
-    *reinterpret_cast<uint2*>(a.out + (PK ? 0 : b * a.osb) + (long)h * a.osh + orow * a.oss + 4 * c) = pk;
+    *reinterpret_cast<uint2*>(a.out + (PACKED ? 0 : b * a.osb) + (long)h * a.osh + orow * a.oss + 4 * c) = pk;
     if (a.lse && c == 0) a.lse[row] = any ? (ms + __builtin_amdgcn_logf(lt)) * 0.69314718055994530942f : -INFINITY;
 }
+
+// Kernarg offsets are in the instruction stream: in all four argument structs the row groups stand where DecExt has them, a
+// counted or packed source directly behind them, and a padded source takes no room.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+template <typename A, typename R>
+constexpr bool dec_src_behind() {
+    using E = DecExt<A>;
+    using W = WithRows<E, R>;
+    return sizeof(W) == sizeof(E) + sizeof(R) && __builtin_offsetof(W, src) == sizeof(E) &&
+           __builtin_offsetof(W, g) == __builtin_offsetof(E, g) && __builtin_offsetof(W, qblk) == __builtin_offsetof(E, qblk);
+}
+template <typename A>
+constexpr bool dec_args_pinned() {
+    return sizeof(WithRows<DecExt<A>, RowsPadded>) == sizeof(DecExt<A>) && dec_src_behind<A, RowsCounted>() && dec_src_behind<A, RowsPacked>();
+}
+static_assert(dec_args_pinned<DecArgs>() && dec_args_pinned<DecArgs8>() && dec_args_pinned<DecMergeArgs>() && dec_args_pinned<DecMergeArgs8>(),
+              "kernarg offsets");
+#pragma clang diagnostic pop
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 struct DecPlan {
     int U, MT, C, nsplit;
     size_t bytes;
     long groups;                // workgroups per split: units (decode) or row groups (extend)
+    long pieces;                // packed: QP, the pieces (row groups per (unit, head chunk)) the grid holds
     DecGroups g;
 };
 
 #define EXT_FILL_GROUPS 256     // row groups from which a launch fills the chip (256 CUs) without splitting its lists
 
-// Shapes only: units, rows per unit, split size (0 = the library's choice) and the workspace.
-static int dec_plan(int B, int H, int Hkv, int Hl, int Sq, int D, int NK, int blocks_per_split, DecPlan* p) {
+enum DecKind { DEC_DECODE, DEC_EXTEND, DEC_PACKED };
+
+// A call's plan, from host values alone: units, the row groups (DecGroups), the rows of a group, the split size (0 = the library's
+// choice) and the workspace.  Decode: a group is a whole unit of at most 64 rows (block is not read).  Extend: groups of gh heads x
+// qg rows.  Packed: T rows of q hold B items of at most Sq = M rows each; the extend call's row groups with M for Sq (qg = min(64 /
+// gh, block, M)) and QP pieces in the grid.  An item of n rows has pk_pieces(n) of them; piece j of an item starts at row (j / cpb)
+// * block + (j % cpb) * qg >= j * qmax / cpb (qmax = min(M, block); cpb * qg >= qmax), so k non-empty items that hold J pieces in
+// all own at least k + (J - k) * qmax / cpb <= T rows: J <= k + (T - k) * cpb / qmax, which grows with k <= min(B, T).  QP is that
+// bound, capped by B * pk_pieces(M); groups = QP * U * HC, and bytes includes the head of the workspace, row_start and piece_start.
+static int dec_plan(DecKind kind, int T, int B, int H, int Hkv, int Hl, int Sq, int D, int block, int NK, int blocks_per_split,
+                    DecPlan* p) {
+    if (kind == DEC_PACKED && (T <= 0 || Sq <= 0 || Sq > T)) return RSA_ERR_BAD_ARG;
     if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
     if (NK > DEC_MAX_NK || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
     if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
-    p->U = Hl > Hkv ? Hl : Hkv;
-    const long rows = (long)Sq * (H / p->U);
-    if (rows > DEC_MAX_ROWS) return RSA_ERR_UNSUPPORTED;
-    p->MT = rows <= 16 ? 1 : (rows <= 32 ? 2 : 4);
-    const long units = (long)B * p->U;
-    if (units > 0x7FFFFFFFl) return RSA_ERR_UNSUPPORTED;
-    if (blocks_per_split > 0) {
-        p->C = blocks_per_split < NK ? blocks_per_split : NK;
-    } else {
-        p->C = DEC_SPLIT < NK ? DEC_SPLIT : NK;
-    }
-    p->nsplit = (NK + p->C - 1) / p->C;
-    p->bytes = (size_t)units * p->nsplit * (16 * p->MT) * ((size_t)D + 2) * sizeof(float);
-    p->groups = units;
-    p->g = DecGroups{1, 1, 1, 1, H / p->U, Sq};
-    return RSA_OK;
-}
-
-// The extend call's plan, from the shapes alone: the row groups (DecGroups), the rows of a group, the split size and the workspace.
-static int ext_plan(int B, int H, int Hkv, int Hl, int Sq, int D, int block, int NK, int blocks_per_split, DecPlan* p) {
-    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
-    if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
-    if (NK > DEC_MAX_NK || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
-    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
-    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
+    if (kind != DEC_DECODE && block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
+    if (kind == DEC_PACKED && B >= 0x7FFFFFFF) return RSA_ERR_UNSUPPORTED;
     p->U = Hl > Hkv ? Hl : Hkv;
     const int gu = H / p->U;
     DecGroups& g = p->g;
-    g.HC = (gu + DEC_MAX_ROWS - 1) / DEC_MAX_ROWS;
-    g.gh = (gu + g.HC - 1) / g.HC;                  // the unit's heads in HC even chunks of at most 64
-    const int qmax = Sq < block ? Sq : block;       // query rows of a full query block
-    g.qg = DEC_MAX_ROWS / g.gh < qmax ? DEC_MAX_ROWS / g.gh : qmax;
-    g.NQ = (int)(((long)Sq + block - 1) / block);
-    g.cpb = (qmax + g.qg - 1) / g.qg;
-    const long qc = (long)(g.NQ - 1) * g.cpb + (Sq - (g.NQ - 1) * block + g.qg - 1) / g.qg;
+    p->pieces = 0;
+    if (kind == DEC_DECODE) {
+        if ((long)Sq * gu > DEC_MAX_ROWS) return RSA_ERR_UNSUPPORTED;
+        g = DecGroups{1, 1, 1, 1, gu, Sq};
+        p->groups = (long)B * p->U;
+        if (p->groups > 0x7FFFFFFFl) return RSA_ERR_UNSUPPORTED;
+    } else {
+        g.HC = (gu + DEC_MAX_ROWS - 1) / DEC_MAX_ROWS;
+        g.gh = (gu + g.HC - 1) / g.HC;                  // the unit's heads in HC even chunks of at most 64
+        const int qmax = Sq < block ? Sq : block;       // query rows of a full query block
+        g.qg = DEC_MAX_ROWS / g.gh < qmax ? DEC_MAX_ROWS / g.gh : qmax;
+        g.NQ = (int)(((long)Sq + block - 1) / block);
+        g.cpb = (qmax + g.qg - 1) / g.qg;
+        // grid limits: the row groups are the grid's x extent, the merge runs one thread per four output channels
+        if (kind == DEC_EXTEND) {
+            const long qc = (long)(g.NQ - 1) * g.cpb + (Sq - (g.NQ - 1) * block + g.qg - 1) / g.qg;
+            if (qc > 0x7FFFFFFFl / g.HC || (long)B * p->U > 0x7FFFFFFFl / (qc * g.HC)) return RSA_ERR_UNSUPPORTED;
+            if ((long)B * H > (0x7FFFFFFFl * (long)DEC_NT) / ((long)Sq * (D / 4))) return RSA_ERR_UNSUPPORTED;
+            g.QC = (int)qc;
+            p->groups = (long)B * p->U * qc * g.HC;
+        } else {
+            g.QC = pk_pieces(Sq, block, g.qg, g.cpb);   // (of an item of M rows: the kernels do not read it)
+            const long k = B < T ? B : T;
+            long qp = k + ((long)T - k) * g.cpb / qmax;
+            if (qp > (long)B * g.QC) qp = (long)B * g.QC;
+            if (qp > 0x7FFFFFFFl / ((long)p->U * g.HC)) return RSA_ERR_UNSUPPORTED;
+            if ((long)H > (0x7FFFFFFFl * (long)DEC_NT) / ((long)T * (D / 4))) return RSA_ERR_UNSUPPORTED;
+            p->pieces = qp;
+            p->groups = qp * p->U * g.HC;
+        }
+    }
     const int rows = g.gh * g.qg;
     p->MT = rows <= 16 ? 1 : (rows <= 32 ? 2 : 4);
-    // grid limits: the row groups are the grid's x extent, the merge runs one thread per four output channels
-    if (qc > 0x7FFFFFFFl / g.HC || (long)B * p->U > 0x7FFFFFFFl / (qc * g.HC)) return RSA_ERR_UNSUPPORTED;
-    if ((long)B * H > (0x7FFFFFFFl * (long)DEC_NT) / ((long)Sq * (D / 4))) return RSA_ERR_UNSUPPORTED;
-    g.QC = (int)qc;
-    p->groups = (long)B * p->U * qc * g.HC;
     if (blocks_per_split > 0) {
         p->C = blocks_per_split < NK ? blocks_per_split : NK;
-    } else {
-        p->C = p->groups < EXT_FILL_GROUPS ? (DEC_SPLIT < NK ? DEC_SPLIT : NK) : NK;
+    } else {        // an extend launch that fills the chip with its row groups does not split its lists
+        p->C = kind == DEC_DECODE || p->groups < EXT_FILL_GROUPS ? (DEC_SPLIT < NK ? DEC_SPLIT : NK) : NK;
     }
     p->nsplit = (NK + p->C - 1) / p->C;
-    p->bytes = (size_t)p->groups * p->nsplit * (16 * p->MT) * ((size_t)D + 2) * sizeof(float);
+    p->bytes = (kind == DEC_PACKED ? pk_head_bytes(2 * ((long)B + 1)) : 0) +
+               (size_t)p->groups * p->nsplit * (16 * p->MT) * ((size_t)D + 2) * sizeof(float);
     return RSA_OK;
 }
 
-// The packed call: T rows of q hold B items of at most M rows each.
-struct DecPacked {
-    int T, B;
-    const int32_t* cu;          // DEVICE [B + 1]
-};
-
-// The packed call's plan, from host values alone: the extend call's row groups with M for Sq (qg = min(64 / gh, block, M)), and
-// QP, the pieces (row groups per (unit, head chunk)) the grid holds.  An item of n rows has pk_pieces(n) of them; piece j of an
-// item starts at row (j / cpb) * block + (j % cpb) * qg >= j * qmax / cpb (qmax = min(M, block); cpb * qg >= qmax), so k non-empty
-// items that hold J pieces in all own at least k + (J - k) * qmax / cpb <= T rows: J <= k + (T - k) * cpb / qmax, which grows with
-// k <= min(B, T).  QP is that bound, capped by B * pk_pieces(M).  p->groups = QP * U * HC; p->bytes includes the head of the
-// workspace, row_start and piece_start.
-static int pk_plan(int T, int B, int H, int Hkv, int Hl, int M, int D, int block, int NK, int blocks_per_split, DecPlan* p,
-                   long* qp_out = nullptr) {
-    if (T <= 0 || M <= 0 || M > T) return RSA_ERR_BAD_ARG;
-    if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
-    if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
-    if (NK > DEC_MAX_NK || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
-    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
-    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
-    if (B >= 0x7FFFFFFF) return RSA_ERR_UNSUPPORTED;
-    p->U = Hl > Hkv ? Hl : Hkv;
-    const int gu = H / p->U;
-    DecGroups& g = p->g;
-    g.HC = (gu + DEC_MAX_ROWS - 1) / DEC_MAX_ROWS;
-    g.gh = (gu + g.HC - 1) / g.HC;
-    const int qmax = M < block ? M : block;
-    g.qg = DEC_MAX_ROWS / g.gh < qmax ? DEC_MAX_ROWS / g.gh : qmax;
-    g.NQ = (int)(((long)M + block - 1) / block);
-    g.cpb = (qmax + g.qg - 1) / g.qg;
-    g.QC = pk_pieces(M, block, g.qg, g.cpb);        // (of an item of M rows: the kernels do not read it)
-    const long k = B < T ? B : T;
-    long qp = k + ((long)T - k) * g.cpb / qmax;
-    if (qp > (long)B * g.QC) qp = (long)B * g.QC;
-    const int rows = g.gh * g.qg;
-    p->MT = rows <= 16 ? 1 : (rows <= 32 ? 2 : 4);
-    if (qp > 0x7FFFFFFFl / ((long)p->U * g.HC)) return RSA_ERR_UNSUPPORTED;
-    if ((long)H > (0x7FFFFFFFl * (long)DEC_NT) / ((long)T * (D / 4))) return RSA_ERR_UNSUPPORTED;
-    p->groups = qp * p->U * g.HC;
-    if (blocks_per_split > 0) {
-        p->C = blocks_per_split < NK ? blocks_per_split : NK;
-    } else {
-        p->C = p->groups < EXT_FILL_GROUPS ? (DEC_SPLIT < NK ? DEC_SPLIT : NK) : NK;
+static int dec_plan_bytes(DecKind kind, int T, int B, int H, int Hkv, int Hl, int Sq, int D, int block, int NK, int blocks_per_split,
+                          size_t* bytes, int64_t* pieces) {
+    if (!bytes) return RSA_ERR_BAD_ARG;
+    DecPlan p;
+    const int st = dec_plan(kind, T, B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p);
+    if (st == RSA_OK) {
+        *bytes = p.bytes;
+        if (pieces) *pieces = p.pieces;
     }
-    p->nsplit = (NK + p->C - 1) / p->C;
-    p->bytes = pk_head_bytes(2 * ((long)B + 1)) + (size_t)p->groups * p->nsplit * (16 * p->MT) * ((size_t)D + 2) * sizeof(float);
-    if (qp_out) *qp_out = qp;
-    return RSA_OK;
+    return st;
 }
 
 extern "C" int rsa_block_sparse_extend_packed_bytes(int T, int B, int H, int Hkv, int Hl, int max_q_len, int D, int block, int NK,
                                                     int blocks_per_split, size_t* bytes, int64_t* pieces) {
-    if (!bytes) return RSA_ERR_BAD_ARG;
-    DecPlan p;
-    long qp = 0;
-    const int st = pk_plan(T, B, H, Hkv, Hl, max_q_len, D, block, NK, blocks_per_split, &p, &qp);
-    if (st == RSA_OK) {
-        *bytes = p.bytes;
-        if (pieces) *pieces = qp;
-    }
-    return st;
+    return dec_plan_bytes(DEC_PACKED, T, B, H, Hkv, Hl, max_q_len, D, block, NK, blocks_per_split, bytes, pieces);
 }
 
 extern "C" int rsa_block_sparse_decode_bytes(int B, int H, int Hkv, int Hl, int Sq, int D, int NK, int blocks_per_split,
                                              size_t* bytes) {
-    if (!bytes) return RSA_ERR_BAD_ARG;
-    DecPlan p;
-    const int st = dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
-    if (st == RSA_OK) *bytes = p.bytes;
-    return st;
+    return dec_plan_bytes(DEC_DECODE, 0, B, H, Hkv, Hl, Sq, D, 0, NK, blocks_per_split, bytes, nullptr);
 }
 
 extern "C" int rsa_block_sparse_extend_bytes(int B, int H, int Hkv, int Hl, int Sq, int D, int block, int NK,
                                              int blocks_per_split, size_t* bytes) {
-    if (!bytes) return RSA_ERR_BAD_ARG;
-    DecPlan p;
-    const int st = ext_plan(B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p);
-    if (st == RSA_OK) *bytes = p.bytes;
-    return st;
+    return dec_plan_bytes(DEC_EXTEND, 0, B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, bytes, nullptr);
 }
 
-template <typename Tag, int D, bool EXT, typename A0, typename G0>
-static void dec_launch2(const A0& a0, const G0& g0, const DecGroups& gr, const int32_t* q_len, const DecPacked* pk, int32_t* pk_head,
-                        int MT, dim3 grid, hipStream_t s) {
-    DecArgsFor<A0, EXT> a;
-    DecArgsFor<G0, EXT> g;
-    static_cast<A0&>(a) = a0;
-    static_cast<G0&>(g) = g0;
-    if constexpr (EXT) {
-        a.g = g.g = gr;
-        a.qblk = g.qblk = a0.blk;
-    }
-    const long threads = g.rows * (D / 4);
-    const dim3 mgrid((unsigned)((threads + DEC_NT - 1) / DEC_NT));
-    if constexpr (EXT) {
-        if (pk) {           // the packed instantiations behind the scan of cu_seqlens_q: three launches
-            DecPk<A0> ap;
-            DecPk<G0> gp;
-            static_cast<DecExt<A0>&>(ap) = a;
-            static_cast<DecExt<G0>&>(gp) = g;
-            ap.row_start = gp.row_start = pk_head;
-            ap.piece_start = gp.piece_start = pk_head + pk->B + 1;
-            ap.pk_B = gp.pk_B = pk->B;
-            ap.pk_steps = gp.pk_steps = pk_steps(pk->B);
-            pk_scan_launch(pk->cu, pk->B, pk->T, a0.Sq, a0.blk, gr.qg, gr.cpb, pk_head, nullptr, pk_head + pk->B + 1, s);
-            if (MT == 1) decode_split_kernel<Tag, D, 1, true, false, true><<<grid, DEC_NT, 0, s>>>(ap);
-            else if (MT == 2) decode_split_kernel<Tag, D, 2, true, false, true><<<grid, DEC_NT, 0, s>>>(ap);
-            else decode_split_kernel<Tag, D, 4, true, false, true><<<grid, DEC_NT, 0, s>>>(ap);
-            decode_merge_kernel<Tag, D, true, false, true><<<mgrid, DEC_NT, 0, s>>>(gp);
-            return;
-        }
-        if (q_len) {        // the ragged instantiations
-            DecRag<A0> ar;
-            DecRag<G0> gr2;
-            static_cast<DecExt<A0>&>(ar) = a;
-            static_cast<DecExt<G0>&>(gr2) = g;
-            ar.q_len = gr2.q_len = q_len;
-            if (MT == 1) decode_split_kernel<Tag, D, 1, true, true><<<grid, DEC_NT, 0, s>>>(ar);
-            else if (MT == 2) decode_split_kernel<Tag, D, 2, true, true><<<grid, DEC_NT, 0, s>>>(ar);
-            else decode_split_kernel<Tag, D, 4, true, true><<<grid, DEC_NT, 0, s>>>(ar);
-            decode_merge_kernel<Tag, D, true, true><<<mgrid, DEC_NT, 0, s>>>(gr2);
-            return;
-        }
-    }
-    if (MT == 1) decode_split_kernel<Tag, D, 1, EXT><<<grid, DEC_NT, 0, s>>>(a);
-    else if (MT == 2) decode_split_kernel<Tag, D, 2, EXT><<<grid, DEC_NT, 0, s>>>(a);
-    else decode_split_kernel<Tag, D, 4, EXT><<<grid, DEC_NT, 0, s>>>(a);
-    decode_merge_kernel<Tag, D, EXT><<<mgrid, DEC_NT, 0, s>>>(g);
-}
-
-template <typename Tag, int D, typename A, typename G>
-static void dec_launch(bool ext, const A& a, const G& g, const DecGroups& gr, const int32_t* q_len, const DecPacked* pk,
-                       int32_t* pk_head, int MT, dim3 grid, hipStream_t s) {
-    if (ext) dec_launch2<Tag, D, true>(a, g, gr, q_len, pk, pk_head, MT, grid, s);
-    else dec_launch2<Tag, D, false>(a, g, gr, nullptr, nullptr, nullptr, MT, grid, s);
+// The one place that maps a call's cache element, query type, head dimension and row tiles to the kernels' template arguments:
+// f(cache tag, std::integral_constant<int, D>, std::integral_constant<int, MT>).
+template <typename F>
+static void dec_with_shape(bool kv8, int dtype, int D, int MT, F f) {
+    auto with_tag = [&](auto ctag) {
+        auto with_d = [&](auto d) {
+            if (MT == 1) f(ctag, d, std::integral_constant<int, 1>());
+            else if (MT == 2) f(ctag, d, std::integral_constant<int, 2>());
+            else f(ctag, d, std::integral_constant<int, 4>());
+        };
+        if (D == 128) with_d(std::integral_constant<int, 128>());
+        else with_d(std::integral_constant<int, 64>());
+    };
+    if (kv8 && dtype == RSA_BF16) with_tag(kv8_tag<bf16_tag>());
+    else if (kv8) with_tag(kv8_tag<fp16_tag>());
+    else if (dtype == RSA_BF16) with_tag(bf16_tag());
+    else with_tag(fp16_tag());
 }
 
 // An e4m3 cache view as the loads need it: K is read 8 bytes a lane, V 16 (strides in elements = bytes).
@@ -804,34 +745,53 @@ static int dec_check_cache8(const rsa_tensor4& t, int align) {
     return RSA_OK;
 }
 
-// All eight entries: kv8 = the cache holds e4m3 codes and the two scale arrays are there; ext = the extend call (any Sq, row groups);
-// q_len_dev = the ragged extend call's rows per batch item (null: Sq; never given without ext); pk = the packed call's batch (null:
-// a padded q; never given without ext or with q_len_dev): Sq is then M, q / out are read through stride_h and stride_s (the row's).
-static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
-                   const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
-                   rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* cols,
-                   const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
-                   const float* k_scale, const float* v_scale, const int32_t* q_len_dev, void* stream,
-                   const DecPacked* pk = nullptr) {
+// What the eight entries hand to dec_run: their own arguments by name, and kind -- decode, extend, or the packed extend call: Sq is
+// then M, T the rows of q, and q / out are read through stride_h and stride_s (the row's); kv8: the cache holds e4m3 codes and the two
+// scale arrays are there; q_len_dev: the ragged call's rows per batch item (null: Sq); cu: the packed call's cu_seqlens_q [B + 1].
+struct DecCall {
+    DecKind kind;
+    bool kv8;
+    int T, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK;
+    const int32_t* kv_len_dev;
+    int kv_valid, causal;
+    double sm_scale;
+    rsa_tensor4 q, k, v;
+    const int32_t* block_table;
+    int64_t table_stride_b;
+    int num_pages;
+    const int32_t *cols, *counts;
+    int blocks_per_split;
+    void* ws;
+    size_t ws_bytes;
+    rsa_out4 out;
+    float* lse;
+    const float *k_scale, *v_scale;
+    const int32_t *q_len_dev, *cu;
+    void* stream;
+};
+
+static int dec_run(const DecCall& c) {
+    const bool pk = c.kind == DEC_PACKED;
+    const int B = c.B, H = c.H, Hkv = c.Hkv, Hl = c.Hl, Sq = c.Sq, Sk = c.Sk, D = c.D, block = c.block, NK = c.NK;
+    const rsa_tensor4 &q = c.q, &k = c.k, &v = c.v;
+    const rsa_out4& out = c.out;
     if (B <= 0 || H <= 0 || Hkv <= 0 || Hl <= 0 || Sq <= 0 || Sk <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (H % Hkv || (Hl != 1 && Hl != Hkv && Hl != H)) return RSA_ERR_BAD_ARG;
     if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
-    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (c.dtype != RSA_BF16 && c.dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
     if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
     const long nkmax = ((long)Sk + block - 1) / block;
     if (NK > (nkmax < DEC_MAX_NK ? nkmax : DEC_MAX_NK)) return RSA_ERR_BAD_ARG;
-    if ((!ext && Sq > block) || blocks_per_split < 0) return RSA_ERR_BAD_ARG;
-    if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
+    if ((c.kind == DEC_DECODE && Sq > block) || c.blocks_per_split < 0) return RSA_ERR_BAD_ARG;
+    if (!c.kv_len_dev && (c.kv_valid < 0 || c.kv_valid > Sk)) return RSA_ERR_BAD_ARG;
     DecPlan p;
-    const int st = pk    ? pk_plan(pk->T, B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p)
-                   : ext ? ext_plan(B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, &p)
-                         : dec_plan(B, H, Hkv, Hl, Sq, D, NK, blocks_per_split, &p);
+    const int st = dec_plan(c.kind, c.T, B, H, Hkv, Hl, Sq, D, block, NK, c.blocks_per_split, &p);
     if (st != RSA_OK) return st;
-    if (pk && (!pk->cu || (reinterpret_cast<uintptr_t>(pk->cu) & 3))) return RSA_ERR_BAD_ARG;
-    if (!cols || !counts || !ws || !out.ptr) return RSA_ERR_BAD_ARG;
+    if (pk && (!c.cu || (reinterpret_cast<uintptr_t>(c.cu) & 3))) return RSA_ERR_BAD_ARG;
+    if (!c.cols || !c.counts || !c.ws || !out.ptr) return RSA_ERR_BAD_ARG;
     if (rsa_check_tensor(q) != RSA_OK) return RSA_ERR_BAD_ARG;
-    if (kv8) {
-        if (!k_scale || !v_scale || ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3))
+    if (c.kv8) {
+        if (!c.k_scale || !c.v_scale || ((reinterpret_cast<uintptr_t>(c.k_scale) | reinterpret_cast<uintptr_t>(c.v_scale)) & 3))
             return RSA_ERR_BAD_ARG;
         if (dec_check_cache8(k, 8) != RSA_OK || dec_check_cache8(v, 16) != RSA_OK) return RSA_ERR_BAD_ARG;
     } else if (rsa_check_tensor(k) != RSA_OK || rsa_check_tensor(v) != RSA_OK) {
@@ -842,68 +802,79 @@ static int dec_run(bool ext, bool kv8, int B, int H, int Hkv, int Hl, int Sq, in
         return RSA_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(out.ptr) & 7) || (out.stride_b % 4) || (out.stride_h % 4) || (out.stride_s % 4))
         return RSA_ERR_BAD_ARG;         // 8-byte stores of four channels
-    if ((reinterpret_cast<uintptr_t>(cols) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(kv_len_dev) |
-         reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(lse) | reinterpret_cast<uintptr_t>(q_len_dev)) & 3)
+    if ((reinterpret_cast<uintptr_t>(c.cols) | reinterpret_cast<uintptr_t>(c.counts) | reinterpret_cast<uintptr_t>(c.kv_len_dev) |
+         reinterpret_cast<uintptr_t>(c.block_table) | reinterpret_cast<uintptr_t>(c.lse) | reinterpret_cast<uintptr_t>(c.q_len_dev)) & 3)
         return RSA_ERR_BAD_ARG;
-    if (block_table && (num_pages <= 0 || table_stride_b < 0)) return RSA_ERR_BAD_ARG;
-    if (reinterpret_cast<uintptr_t>(ws) & 15) return RSA_ERR_BAD_ARG;
-    if (ws_bytes < p.bytes) return RSA_ERR_WORKSPACE;
+    if (c.block_table && (c.num_pages <= 0 || c.table_stride_b < 0)) return RSA_ERR_BAD_ARG;
+    if (reinterpret_cast<uintptr_t>(c.ws) & 15) return RSA_ERR_BAD_ARG;
+    if (c.ws_bytes < p.bytes) return RSA_ERR_WORKSPACE;
 
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
     const long parts = p.groups * p.nsplit;
-    DecArgs8 a;
+    DecArgs8 a;                         // (the 2-byte kernels take the base structs)
     a.q = static_cast<const unsigned short*>(q.ptr);
     a.k = static_cast<const unsigned short*>(k.ptr);
     a.v = static_cast<const unsigned short*>(v.ptr);
     a.qsb = q.stride_b; a.qsh = q.stride_h; a.qss = q.stride_s;
     a.ksb = k.stride_b; a.ksh = k.stride_h; a.kss = k.stride_s;
     a.vsb = v.stride_b; a.vsh = v.stride_h; a.vss = v.stride_s;
-    a.table = block_table;
-    a.tsb = table_stride_b;
-    a.num_pages = num_pages;
-    a.cols = cols;
-    a.counts = counts;
-    a.kv_len = kv_len_dev;
-    a.kv_valid = kv_valid;
-    a.H = H; a.Hkv = Hkv; a.Hl = Hl; a.U = p.U; a.Sq = Sq; a.Sk = Sk; a.NK = NK; a.blk = block; a.causal = causal != 0;
+    a.table = c.block_table;
+    a.tsb = c.table_stride_b;
+    a.num_pages = c.num_pages;
+    a.cols = c.cols;
+    a.counts = c.counts;
+    a.kv_len = c.kv_len_dev;
+    a.kv_valid = c.kv_valid;
+    a.H = H; a.Hkv = Hkv; a.Hl = Hl; a.U = p.U; a.Sq = Sq; a.Sk = Sk; a.NK = NK; a.blk = block; a.causal = c.causal != 0;
     a.C = p.C; a.nsplit = p.nsplit; a.R16 = 16 * p.MT;
-    a.qk_scale = (float)(sm_scale * 1.44269504);    // (as rsa_block_sparse_plain_fwd)
+    a.qk_scale = (float)(c.sm_scale * 1.44269504);  // (as rsa_block_sparse_plain_fwd)
     // (packed: row_start and piece_start stand at the head of the workspace, the partials 16-byte aligned behind them)
-    int32_t* const pk_head = pk ? static_cast<int32_t*>(ws) : nullptr;
-    a.ws_o = pk ? reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + pk_head_bytes(2 * ((long)B + 1))) : static_cast<float*>(ws);
+    int32_t* const pk_head = static_cast<int32_t*>(c.ws);
+    a.ws_o = reinterpret_cast<float*>(static_cast<unsigned char*>(c.ws) + (pk ? pk_head_bytes(2 * ((long)B + 1)) : 0));
     a.ws_ml = reinterpret_cast<float2*>(a.ws_o + parts * a.R16 * D);
-    a.k_scale = k_scale;
-    a.v_scale = v_scale;
+    a.k_scale = c.k_scale;
+    a.v_scale = c.v_scale;
     DecMergeArgs8 g;
-    g.v_scale = v_scale;
+    g.v_scale = c.v_scale;
     g.Hkv = Hkv;
     g.ws_o = a.ws_o;
     g.ws_ml = a.ws_ml;
     g.out = static_cast<unsigned short*>(out.ptr);
     g.osb = out.stride_b; g.osh = out.stride_h; g.oss = out.stride_s;
-    g.lse = lse;
-    g.counts = counts;
+    g.lse = c.lse;
+    g.counts = c.counts;
     g.Hl = Hl; g.NK = NK; g.C = p.C;
     g.H = H; g.U = p.U; g.Sq = Sq; g.nsplit = p.nsplit; g.R16 = a.R16;
-    g.rows = pk ? (long)pk->T * H : (long)B * H * Sq;
-    if (pk) a.qsb = 0, g.osb = 0;
-    const dim3 grid((unsigned)p.groups, (unsigned)p.nsplit);
-    const DecArgs& a2 = a;              // the 2-byte kernels take the base structs
-    const DecMergeArgs& g2 = g;
-    if (kv8) {
-        if (dtype == RSA_BF16) {
-            if (D == 128) dec_launch<kv8_tag<bf16_tag>, 128>(ext, a, g, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
-            else dec_launch<kv8_tag<bf16_tag>, 64>(ext, a, g, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
-        } else {
-            if (D == 128) dec_launch<kv8_tag<fp16_tag>, 128>(ext, a, g, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
-            else dec_launch<kv8_tag<fp16_tag>, 64>(ext, a, g, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
-        }
-    } else if (dtype == RSA_BF16) {
-        if (D == 128) dec_launch<bf16_tag, 128>(ext, a2, g2, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
-        else dec_launch<bf16_tag, 64>(ext, a2, g2, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
+    g.rows = pk ? (long)c.T * H : (long)B * H * Sq;
+    const dim3 grid((unsigned)p.groups, (unsigned)p.nsplit), mgrid((unsigned)((g.rows * (D / 4) + DEC_NT - 1) / DEC_NT));
+
+    // the two kernels of one row form, over the call's types
+    auto launch = [&](auto form) {
+        using Form = decltype(form);
+        dec_with_shape(c.kv8, c.dtype, D, p.MT, [&](auto ctag, auto d, auto mt) {
+            using CTag = decltype(ctag);
+            typename Form::template Args<typename DecCache<CTag>::Args> sa;
+            typename Form::template Args<typename DecCache<CTag>::MergeArgs> ma;
+            static_cast<typename DecCache<CTag>::Args&>(sa) = a;
+            static_cast<typename DecCache<CTag>::MergeArgs&>(ma) = g;
+            if constexpr (Form::EXT) {
+                sa.g = ma.g = p.g;
+                sa.qblk = ma.qblk = block;
+                sa.src = ma.src = form.rows;
+            }
+            decode_split_kernel<CTag, decltype(d)::value, decltype(mt)::value, Form><<<grid, DEC_NT, 0, s>>>(sa);
+            decode_merge_kernel<CTag, decltype(d)::value, Form><<<mgrid, DEC_NT, 0, s>>>(ma);
+        });
+    };
+    if (c.kind == DEC_DECODE) {
+        launch(DecodeForm{});
+    } else if (pk) {        // behind the scan of cu_seqlens_q: three launches
+        pk_scan_launch(c.cu, B, c.T, Sq, block, p.g.qg, p.g.cpb, pk_head, nullptr, pk_head + B + 1, s);
+        launch(ExtendForm<RowsPacked>{{pk_head, pk_head + B + 1, B, pk_steps(B)}});
+    } else if (c.q_len_dev) {
+        launch(ExtendForm<RowsCounted>{{c.q_len_dev}});
     } else {
-        if (D == 128) dec_launch<fp16_tag, 128>(ext, a2, g2, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
-        else dec_launch<fp16_tag, 64>(ext, a2, g2, p.g, q_len_dev, pk, pk_head, p.MT, grid, s);
+        launch(ExtendForm<RowsPadded>{});
     }
     return rsa_launch_status();
 }
@@ -913,8 +884,11 @@ extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, in
                                        rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
                                        int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
                                        size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
-    return dec_run(false, false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
-                   table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr, nullptr, stream);
+    return dec_run({.kind = DEC_DECODE, .kv8 = false, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = Sq, .Sk = Sk, .D = D,
+                    .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid, .causal = causal,
+                    .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table, .table_stride_b = table_stride_b,
+                    .num_pages = num_pages, .cols = cols, .counts = counts, .blocks_per_split = blocks_per_split, .ws = ws,
+                    .ws_bytes = ws_bytes, .out = out, .lse = lse, .stream = stream});
 }
 
 // The e4m3 cache: dtype names q's type; k / v hold one-byte codes (strides in bytes) and the scales are DEVICE fp32 [Hkv].
@@ -924,8 +898,11 @@ extern "C" int rsa_block_sparse_decode_kv8(int B, int H, int Hkv, int Hl, int Sq
                                            int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split,
                                            void* ws, size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale,
                                            const float* v_scale, void* stream) {
-    return dec_run(false, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v, block_table,
-                   table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale, nullptr, stream);
+    return dec_run({.kind = DEC_DECODE, .kv8 = true, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = Sq, .Sk = Sk, .D = D,
+                    .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid, .causal = causal,
+                    .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table, .table_stride_b = table_stride_b,
+                    .num_pages = num_pages, .cols = cols, .counts = counts, .blocks_per_split = blocks_per_split, .ws = ws,
+                    .ws_bytes = ws_bytes, .out = out, .lse = lse, .k_scale = k_scale, .v_scale = v_scale, .stream = stream});
 }
 
 // ---- extend: any number of query rows.  The decode entries' argument lists; NQ = ceil(Sq / block) and cols /
@@ -935,9 +912,11 @@ extern "C" int rsa_block_sparse_extend(int B, int H, int Hkv, int Hl, int Sq, in
                                        rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
                                        int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
                                        size_t ws_bytes, rsa_out4 out, float* lse, void* stream) {
-    return dec_run(true, false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
-                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr,
-                   nullptr, stream);
+    return dec_run({.kind = DEC_EXTEND, .kv8 = false, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = Sq, .Sk = Sk, .D = D,
+                    .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid, .causal = causal,
+                    .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table, .table_stride_b = table_stride_b,
+                    .num_pages = num_pages, .cols = cols, .counts = counts, .blocks_per_split = blocks_per_split, .ws = ws,
+                    .ws_bytes = ws_bytes, .out = out, .lse = lse, .stream = stream});
 }
 
 extern "C" int rsa_block_sparse_extend_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
@@ -946,9 +925,11 @@ extern "C" int rsa_block_sparse_extend_kv8(int B, int H, int Hkv, int Hl, int Sq
                                            int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split,
                                            void* ws, size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale,
                                            const float* v_scale, void* stream) {
-    return dec_run(true, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
-                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale,
-                   nullptr, stream);
+    return dec_run({.kind = DEC_EXTEND, .kv8 = true, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = Sq, .Sk = Sk, .D = D,
+                    .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid, .causal = causal,
+                    .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table, .table_stride_b = table_stride_b,
+                    .num_pages = num_pages, .cols = cols, .counts = counts, .blocks_per_split = blocks_per_split, .ws = ws,
+                    .ws_bytes = ws_bytes, .out = out, .lse = lse, .k_scale = k_scale, .v_scale = v_scale, .stream = stream});
 }
 
 // ---- ragged extend: a row count per batch item.  The extend entries' argument lists with q_len_dev, DEVICE
@@ -959,9 +940,11 @@ extern "C" int rsa_block_sparse_extend_ragged(int B, int H, int Hkv, int Hl, int
                                               int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split,
                                               void* ws, size_t ws_bytes, rsa_out4 out, float* lse, const int32_t* q_len_dev,
                                               void* stream) {
-    return dec_run(true, false, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
-                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr,
-                   q_len_dev, stream);
+    return dec_run({.kind = DEC_EXTEND, .kv8 = false, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = Sq, .Sk = Sk, .D = D,
+                    .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid, .causal = causal,
+                    .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table, .table_stride_b = table_stride_b,
+                    .num_pages = num_pages, .cols = cols, .counts = counts, .blocks_per_split = blocks_per_split, .ws = ws,
+                    .ws_bytes = ws_bytes, .out = out, .lse = lse, .q_len_dev = q_len_dev, .stream = stream});
 }
 
 extern "C" int rsa_block_sparse_extend_ragged_kv8(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
@@ -971,9 +954,12 @@ extern "C" int rsa_block_sparse_extend_ragged_kv8(int B, int H, int Hkv, int Hl,
                                                   int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
                                                   const float* k_scale, const float* v_scale, const int32_t* q_len_dev,
                                                   void* stream) {
-    return dec_run(true, true, B, H, Hkv, Hl, Sq, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
-                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale,
-                   q_len_dev, stream);
+    return dec_run({.kind = DEC_EXTEND, .kv8 = true, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = Sq, .Sk = Sk, .D = D,
+                    .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid, .causal = causal,
+                    .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table, .table_stride_b = table_stride_b,
+                    .num_pages = num_pages, .cols = cols, .counts = counts, .blocks_per_split = blocks_per_split, .ws = ws,
+                    .ws_bytes = ws_bytes, .out = out, .lse = lse, .k_scale = k_scale, .v_scale = v_scale, .q_len_dev = q_len_dev,
+                    .stream = stream});
 }
 
 // ---- packed extend: q [T, H, D] with cu_seqlens_q.  The extend entries' argument lists with T in front, M
@@ -985,11 +971,13 @@ extern "C" int rsa_block_sparse_extend_packed(int T, int B, int H, int Hkv, int 
                                               int64_t table_stride_b, int num_pages, const int32_t* cols, const int32_t* counts,
                                               int blocks_per_split, void* ws, size_t ws_bytes, rsa_out4 out, float* lse,
                                               const int32_t* cu_seqlens_q_dev, void* stream) {
-    const DecPacked pk = {T, B, cu_seqlens_q_dev};
     q.stride_b = 0, out.stride_b = 0;
-    return dec_run(true, false, B, H, Hkv, Hl, max_q_len, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
-                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, nullptr, nullptr,
-                   nullptr, stream, &pk);
+    return dec_run({.kind = DEC_PACKED, .kv8 = false, .T = T, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = max_q_len, .Sk = Sk,
+                    .D = D, .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid,
+                    .causal = causal, .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table,
+                    .table_stride_b = table_stride_b, .num_pages = num_pages, .cols = cols, .counts = counts,
+                    .blocks_per_split = blocks_per_split, .ws = ws, .ws_bytes = ws_bytes, .out = out, .lse = lse,
+                    .cu = cu_seqlens_q_dev, .stream = stream});
 }
 
 extern "C" int rsa_block_sparse_extend_packed_kv8(int T, int B, int H, int Hkv, int Hl, int max_q_len, int Sk, int D, int dtype,
@@ -999,9 +987,11 @@ extern "C" int rsa_block_sparse_extend_packed_kv8(int T, int B, int H, int Hkv, 
                                                   const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws,
                                                   size_t ws_bytes, rsa_out4 out, float* lse, const float* k_scale,
                                                   const float* v_scale, const int32_t* cu_seqlens_q_dev, void* stream) {
-    const DecPacked pk = {T, B, cu_seqlens_q_dev};
     q.stride_b = 0, out.stride_b = 0;
-    return dec_run(true, true, B, H, Hkv, Hl, max_q_len, Sk, D, dtype, block, NK, kv_len_dev, kv_valid, causal, sm_scale, q, k, v,
-                   block_table, table_stride_b, num_pages, cols, counts, blocks_per_split, ws, ws_bytes, out, lse, k_scale, v_scale,
-                   nullptr, stream, &pk);
+    return dec_run({.kind = DEC_PACKED, .kv8 = true, .T = T, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = max_q_len, .Sk = Sk,
+                    .D = D, .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid,
+                    .causal = causal, .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table,
+                    .table_stride_b = table_stride_b, .num_pages = num_pages, .cols = cols, .counts = counts,
+                    .blocks_per_split = blocks_per_split, .ws = ws, .ws_bytes = ws_bytes, .out = out, .lse = lse,
+                    .k_scale = k_scale, .v_scale = v_scale, .cu = cu_seqlens_q_dev, .stream = stream});
 }

@@ -14,11 +14,11 @@
 // since no address depends on a scale.
 //
 // The packed form (rsa_kv8_append_packed) is an instantiation of its own, PK: k_new / v_new are [T, Hkv, D]
-// with cu_seqlens, and token t < n_b of item b is row s_b + t of them (rsa_packed.h: s the sanitised starts, n_b = s_{b+1} - s_b).
+// with cu_seqlens, and token t < n_b of item b is row s_b + t of them (rsa_rows.h: s the sanitised starts, n_b = s_{b+1} - s_b).
 // One lane per 8 elements of a row of [0, T): the row's item by pk_find over row_start, which pk_scan_kernel wrote; a row of no
 // item places nothing.
 #include "rsa_common.h"
-#include "rsa_packed.h"
+#include "rsa_rows.h"
 
 #include <type_traits>
 

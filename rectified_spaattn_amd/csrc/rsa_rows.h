@@ -1,6 +1,21 @@
-// The packed batch: q [T, H, D] holds the items of a batch back to back and cu_seqlens_q, DEVICE int32
-// [B + 1], where each starts.  What the three packed calls (rsa_block_sparse_extend_packed, rsa_block_select_pooled_packed,
-// rsa_kv8_append_packed) share: the sanitising scan and the search that takes a row or a piece to its item.
+// Where a batch item's query rows come from, and how many there are (DESIGN.md sections 5.16 - 5.18): the row sources that the
+// decode / extend kernels (rsa_decode.hip) and the selection kernels (rsa_block_select.hip) are instantiated over, and what the
+// three packed calls (rsa_block_sparse_extend_packed, rsa_block_select_pooled_packed, rsa_kv8_append_packed) share.
+//
+//   RowsPadded       q [B, H, Sq, D]: every item has Sq rows.  It has no size: a kernel over it carries no argument for it.
+//   RowsCounted      the same q with q_len, DEVICE int32 [B]: item b has q_len[b] rows, clamped into [0, Sq].
+//   RowsPacked       q [T, H, D] holds the items back to back: item b is rows [row_start[b], row_start[b + 1]) of it, at most Sq
+//                    (= M) of them.  piece_start, B and steps take a row group or a row of q to its item (pk_find).
+//   RowsAt           first(b) alone, = row_start[b], for the packed selection's pool kernel: the scan has written the clamped counts
+//                    by then, so it takes them as RowsCounted with RowsAt beside it, and the other kernels are RowsCounted's.
+//   They have        count(b, Sq)   the item's rows (b: an int or a long, as the caller holds it; RowsPacked: its kernels in
+//                                   rsa_decode.hip take the difference of row_start themselves);
+//                    first(b)       the item's first row in q: 0 where q has a batch dimension;
+//                    SHORT          whether count can fall below Sq at all (a group, a block or a row can then be padding);
+//                    BATCHED        whether q has a batch dimension (item b at b * stride_b) or is packed (at row first(b)).
+//   WithRows<A, R>   the kernel arguments A with the source behind them; every member of A keeps its offset.
+//
+// The packed batch (section 5.18): cu_seqlens_q, DEVICE int32 [B + 1], says where each item starts.
 //
 //   pk_scan_kernel   ONE workgroup.  s_b = the running maximum of clamp(cu[b], 0, T), n_b = min(s_{b+1} - s_b, M): whatever cu holds,
 //                    0 <= s_0 <= .. <= s_B <= T and the items' rows [s_b, s_b + n_b) are disjoint ranges of [0, T).  It writes
@@ -47,6 +62,40 @@ __device__ __forceinline__ int pk_find(const int32_t* start, int B, int steps, i
     }
     return lo;
 }
+
+struct RowsPadded {
+    int none[0];                // (an empty struct would still take 4 bytes as a kernel argument; this takes none)
+    static constexpr bool SHORT = false, BATCHED = true;
+    template <typename I> __device__ __forceinline__ int count(I, int Sq) const { return Sq; }
+    __device__ __forceinline__ const int32_t* counts() const { return nullptr; }
+    template <typename I> __device__ __forceinline__ long first(I) const { return 0; }
+};
+
+struct RowsCounted {
+    const int32_t* q_len;       // DEVICE [B]
+    static constexpr bool SHORT = true, BATCHED = true;
+    template <typename I> __device__ __forceinline__ int count(I b, int Sq) const { return min(max(q_len[b], 0), Sq); }
+    __device__ __forceinline__ const int32_t* counts() const { return q_len; }
+    template <typename I> __device__ __forceinline__ long first(I) const { return 0; }
+};
+
+struct RowsAt {
+    const int32_t* row_start;   // DEVICE [B + 1], written by pk_scan_kernel
+    template <typename I> __device__ __forceinline__ long first(I b) const { return row_start[b]; }
+};
+
+struct RowsPacked {
+    const int32_t *row_start, *piece_start;     // DEVICE [B + 1] each, written by pk_scan_kernel: sanitised, ascending
+    int B, steps;                               // items; halvings of the search (pk_steps)
+    static constexpr bool SHORT = true, BATCHED = false;
+    template <typename I> __device__ __forceinline__ long first(I b) const { return row_start[b]; }
+    __device__ __forceinline__ int item_of_row(int t) const { return pk_find(row_start, B, steps, t); }     // the item of row t of q
+};
+
+template <typename A, typename R>
+struct WithRows : A {
+    [[no_unique_address]] R src;
+};
 
 // (a template so that every translation unit that launches it carries its own copy)
 template <int UNUSED>
