@@ -1,7 +1,8 @@
 // Mask-selection pass of the rectified block-sparse attention path: K1 pool_stats, K2 pooled_scores,
 // K3 select_mask, K4 compensation.  gfx950 only.  Compiled with -ffp-contract=off: every fused multiply-add
 // is an explicit __builtin_fmaf so the arithmetic equals the fp32 statistics contract (oracle/rsa_oracle.c)
-// bit for bit.  All of this is HBM/LDS-bound integer-and-fp32 work; no MFMA on purpose.
+// bit for bit.  K1 and K3 are HBM/LDS-bound integer-and-fp32 work on the vector unit; K2 and K4 run on the matrix pipe: the fp32
+// MFMA chain, which equals the fmaf chain bit for bit, and for K4 from 256 visual blocks the split bf16 form (compensation_b).
 #include "rsa_common.h"
 #include "rsa_fp8_emit.h"
 

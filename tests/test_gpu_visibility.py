@@ -96,7 +96,8 @@ def test_rectified_attention_over_a_mask_sees_exactly_the_documented_keys(cid):
     pool_valid of the Flux layout, a ragged last block), 128- and 64-token blocks (an odd number of 64-token text blocks among
     them), the 2-byte, e4m3 and pv kernels; text rows whose walk is split (the tile census of those rows shows that the pieces
     tile [0, kv_text_valid) exactly) and the tail split with text pieces behind it.  Visual rows: R * census + comp with the
-    call's own R and comp (pinned bit for bit elsewhere); the sensitivity condition is checked again with them."""
+    call's own R and comp (R is pinned bit for bit against the oracle by the selection tests; comp, which has no bit-exact oracle, by
+    the exact and per-element witnesses of tests/test_gpu_comp.py); the sensitivity condition is checked again with them."""
     from rectified_spaattn_amd import _core
     c = vis.CASES[cid]
     spec = vis.rect_spec(c)

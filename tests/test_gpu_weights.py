@@ -112,7 +112,8 @@ def test_dense_attention_weighs_every_key_exactly(cid):
 # ---- 3. the rectified call over a caller's mask -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("cid", [c["id"] for c in w.RECT_CASES + w.RECT_FP8_CASES])
 def test_rectified_attention_over_a_mask_weighs_every_key_exactly(cid):
-    """Visual rows: R * weighted census + comp with the call's own R and comp, as tests/test_gpu_visibility.py does; text rows
+    """Visual rows: R * weighted census + comp with the call's own R and comp, as tests/test_gpu_visibility.py does (R pinned bit for
+    bit by the selection tests, comp by tests/test_gpu_comp.py); text rows
     through the text split where the layout has one, visual walks through the tail split (on and off) in the 104-block layout.
     The sensitivity condition is checked again with the call's parts.  The e4m3 and pv cases go in as qkv_fp8=."""
     from rectified_spaattn_amd import _core
