@@ -641,6 +641,40 @@ int rsa_block_select_bound_packed(int T, int B, int H, int Hkv, int Hl, int max_
                                   uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass,
                                   const int32_t* cu_seqlens_q_dev, int32_t* item_ws, void* stream);
 
+/* ---- the MERGE of attention partials: N results over disjoint key sets -- another rank's share of the cache, a shared prefix
+ * beside each item's suffix, a dense branch beside the selected blocks -- become the result over their union (found by symbol:
+ * the header version stays 6.1).  Partial i is what the decode and extend entries return: out_i, 2-byte
+ * (dtype, one type for all), and lse_i, fp32, the natural-log log-sum-exp of its keys.  A non-NULL sink (DEVICE fp32 [H]) is one
+ * more partial whose out is zero and whose lse is sink[h] for every row of head h (attention-sink logits).
+ *   shape     1 <= N <= 8.  outs: a HOST array of N rsa_tensor4, each a [B, H, S, D] view; lses: a HOST array of N DEVICE pointers;
+ *             lse_strides: a HOST array of 3 N element strides, (b, h, s) of lse_0, then of lse_1, ...  The three arrays are read
+ *             during the call and not kept.  The packed form [T, H, D] / [T, H] is B = 1, S = T, stride_s the row's stride,
+ *             stride_h the head's.  lse_out NULL or fp32 through its three element strides.
+ *   per row   in fp32, the partials in ascending index order and the sink last:
+ *                 m*  = max over the live entries of lse_i     (live: lse_i > -inf; the sink is live iff sink[h] > -inf)
+ *                 w_i = exp2((lse_i - m*) * log2 e)            one subtraction, one multiplication, the hardware exp2
+ *                 acc = fmaf(w_i, out_i[c], acc)               a partial that is not live is SKIPPED, never multiplied
+ *                 l   = l + w_i                                the sink's weight enters l and not acc
+ *                 out[c] = acc / l (IEEE), one conversion;  lse = m* + ln 2 * log2 l;  no live entry: 0 and -inf
+ *             The out of a partial whose lse is -inf may hold NaN: it never reaches the result.  A row with exactly one live
+ *             entry returns that partial's out and lse bytes.  Two calls give the same bytes.  A +inf lse is the caller's error and
+ *             garbles its own row alone; a NaN lse counts as not live.
+ *   strides   D contiguous; every other stride of every out_i and of out a non-negative multiple of 4 elements, the pointers
+ *             8-byte aligned (the extend entries' output contract).  Where every pointer is 16-byte aligned and every stride a
+ *             multiple of 8 a lane moves 16 bytes, else 8: the same arithmetic per element, the same bytes.  The lse tensors take
+ *             any non-negative element strides (pointers 4-byte aligned); a stride of out or lse_out along an axis of more than
+ *             one entry is positive.
+ *   alias     out may be one out_i exactly (the same pointer and the same strides: an in-place accumulate), lse_out one lse_i
+ *             exactly: every element a lane needs is read before it stores.  A result whose address range meets that of a partial,
+ *             of the sink or of the other result in any other way is refused.
+ * One launch over a bounded grid, no workspace, no host read of device memory: capturable in a HIP graph.
+ * N outside [1, 8], a negative size, a NULL outs / lses / lse_strides / out_i / lse_i / out, a pointer or stride outside the above,
+ * an overlap that is not an exact alias: RSA_ERR_BAD_ARG; D outside {64, 128}, an unknown dtype, more than 2^31 - 1 rows:
+ * RSA_ERR_UNSUPPORTED.  Every check runs before the first HIP call; B, H or S of 0 then returns RSA_OK without a launch. */
+int rsa_merge_partials(int N, int B, int H, int S, int D, int dtype, const rsa_tensor4* outs, const float* const* lses,
+                       const int64_t* lse_strides, const float* sink, rsa_out4 out, float* lse_out, int64_t lse_out_stride_b,
+                       int64_t lse_out_stride_h, int64_t lse_out_stride_s, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

@@ -157,6 +157,14 @@ def select_blocks_bound(q, key_bounds, top_k, *, block_size=128, kv_len=None, ca
                                             cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len)
 
 
+def merge_partials(outs, lses, *, sink=None, out=None, lse=None, return_lse=True):
+    """The merge of N <= 8 attention partials (out_i, lse_i) over disjoint key sets -- what block_sparse_decode / block_sparse_extend
+    return with return_lse=True -- into the result over their union, with optional attention-sink logits: one launch, no copy, the
+    same bytes from two calls.  See rectified_spaattn_amd.block_sparse.merge_partials."""
+    from . import block_sparse
+    return block_sparse.merge_partials(outs, lses, sink=sink, out=out, lse=lse, return_lse=return_lse)
+
+
 def clear_buffer_cache() -> None:
     """Drops the intermediate buffers the operators keep per (geometry, device, stream) between calls (about 0.45 GB per
     set at the HunyuanVideo shape; `_core.BUFFER_CACHE_MAX_BYTES` bounds the total, `_core.BUFFER_CACHE = False` turns the

@@ -24,6 +24,8 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
     append_kv_e4m3           the writer of a one-byte K/V cache: new rows become e4m3 codes under one static fp32 scale per K/V
                              head (rsa_kv8_append); block_sparse_decode and pool_keys read such a cache in place
                              (k_scale= / v_scale=: rsa_block_sparse_decode_kv8, rsa_pool_keys_kv8)
+    merge_partials           the merge of N (out, lse) partials of block_sparse_decode / block_sparse_extend over disjoint key sets,
+                             with optional sink logits: one launch, no copy (rsa_merge_partials)
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
@@ -1222,6 +1224,144 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
                                      int(bool(causal)), scale, tq, _core._t4(k), _core._t4(v), *table, cols.data_ptr(),
                                      counts.data_ptr(), bps, ws.data_ptr(), need.value, to, _ptr(lse),
                                      *[t.data_ptr() for t in held], _core._stream()), entry)
+    return (out, lse) if return_lse else out
+
+
+MERGE_MAX_PARTIALS = 8      # partials of one merge_partials call (rsa_merge.hip: MERGE_MAX_N)
+MERGE_MAX_GRID = 2048       # workgroups of its launch, at most; 256 / (D / 8) rows each and pass, 256 / (D / 4) in the 8-byte form
+
+
+def _merge_span(t: torch.Tensor):
+    """The bytes a strided view touches, as [lo, hi)."""
+    lo = t.data_ptr()
+    return lo, lo + (sum((n - 1) * st for n, st in zip(t.shape, t.stride())) + 1) * t.element_size()
+
+
+def _merge_alias(name: str, res, parts, others, pname: str):
+    """A result of merge_partials against what the call reads: it may be one partial exactly, and meets nothing else."""
+    lo, hi = _merge_span(res)
+    for i, p in enumerate(parts):
+        plo, phi = _merge_span(p)
+        if lo < phi and plo < hi and not (p.data_ptr() == res.data_ptr() and p.stride() == res.stride()):
+            raise ValueError(f"{name}: overlaps {pname}[{i}] without being it (the result may alias one partial exactly: the same "
+                             f"pointer and the same strides)")
+    for oname, o in others:
+        if o is not None and o.device == res.device:
+            olo, ohi = _merge_span(o)
+            if lo < ohi and olo < hi:
+                raise ValueError(f"{name}: overlaps {oname}")
+
+
+def merge_partials(outs, lses, *, sink=None, out: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
+                   return_lse: bool = True):
+    """The merge of N attention partials over disjoint key sets into the result over their union (rsa_merge_partials, DESIGN.md
+    section 5.20): another rank's share of a key-sharded cache, a shared prefix beside each item's suffix (cascade), a dense local
+    branch beside the selected blocks, attention-sink logits.  Partial i is what block_sparse_decode / block_sparse_extend return
+    with return_lse=True: out_i (bf16 or fp16, one type for all) and lse_i (fp32, natural log).
+    outs: a sequence of 1 <= N <= 8 tensors of one shape, dtype and device -- [B,H,Sq,D] or packed [T,H,D], D in {64, 128} -- or
+    one stacked tensor [N, ...] (what all_gather_into_tensor fills); lses matches it: [B,H,Sq] / [T,H] each, or stacked.
+    sink: None, a float (-inf: no sink), or a float32 device tensor of 1 or H values: one more partial whose out is zero and whose
+    lse is sink[h] for every row of head h.
+    Per row, in fp32, the partials in ascending order and the sink last: m* = max of the live lse_i (live: > -inf), w_i =
+    exp2((lse_i - m*) * log2 e), acc = fmaf(w_i, out_i, acc) and l = l + w_i over the live partials -- one that is not live is
+    skipped, never multiplied: its out may hold NaN (the rows extend writes as 0 / -inf, rows of padding) --, the sink's weight into
+    l alone, out = acc / l rounded once, lse = m* + ln 2 * log2 l; a row without a live entry is 0 / -inf.  A row with exactly one
+    live entry returns that partial's bytes; two calls give the same bytes.  A +inf lse is the caller's error and garbles its
+    own row alone.
+    No copies: views go through as strides -- a contiguous head dim, every other stride a multiple of 4 elements, the pointer
+    8-byte aligned (where every pointer is 16-byte aligned and every stride a multiple of 8 a lane moves 16 bytes, else 8: the
+    same bytes); the lse tensors take any strides.  A tensor outside that is refused (ValueError naming it), not made contiguous.
+    out= / lse=: preallocated results under the same rule; out may be one of outs and lse one of lses (an in-place accumulate),
+    any other overlap is refused.  Returns (out, lse), or out with return_lse=False (lse= is then not written).
+    One launch, no workspace, no host read: asynchronous on the current stream and capturable in a HIP graph.  CPU tensors are
+    refused: there is no fallback."""
+    def parts(name, x, ranks):
+        if isinstance(x, torch.Tensor):
+            if x.dim() - 1 not in ranks:
+                raise ValueError(f"{name}: a sequence of tensors or one stacked tensor [N, ...], got a tensor {tuple(x.shape)}")
+            x = x.unbind(0)
+        elif not isinstance(x, (list, tuple)) or not all(isinstance(t, torch.Tensor) for t in x):
+            raise ValueError(f"{name}: a sequence of tensors or one stacked tensor [N, ...], got {type(x).__name__}")
+        return list(x)
+    po, pl = parts("outs", outs, (3, 4)), parts("lses", lses, (2, 3))
+    N = len(po)
+    if not 1 <= N <= MERGE_MAX_PARTIALS:
+        raise ValueError(f"outs: 1..{MERGE_MAX_PARTIALS} partials, got {N}")
+    if len(pl) != N:
+        raise ValueError(f"lses: {len(pl)} log-sum-exps for {N} partials")
+    o0 = po[0]
+    if o0.dim() not in (3, 4):
+        raise ValueError(f"outs[0]: [B, H, Sq, D] or packed [T, H, D], got {tuple(o0.shape)}")
+    if o0.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"outs: one dtype, bfloat16 or float16 (the partials decode and extend return), got {o0.dtype}")
+    shape, D, H = tuple(o0.shape), o0.shape[-1], o0.shape[1]       # ([B, H, Sq, D] and packed [T, H, D] alike)
+    if D not in (64, 128):
+        if D in HEAD_DIMS:
+            raise NotImplementedError(f"head dim {D}: this call serves (64, 128)")
+        raise ValueError(f"head dim {D}: one of (64, 128)")
+    if 0 in shape:
+        raise ValueError(f"empty operands {shape}")
+
+    def held(name, t, want_shape, want_dtype, two_byte, result=False):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != want_shape or t.dtype != want_dtype or t.device != o0.device:
+            raise ValueError(f"{name}: a {want_dtype} tensor {want_shape} on {o0.device}, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+        if two_byte:
+            *outer, inner = t.stride()
+            if inner != 1 or any(st % 4 or st < 0 for st in outer) or t.data_ptr() % 8:
+                raise ValueError(f"{name}: a contiguous head dim, strides that are non-negative multiples of 4 elements and an 8-byte "
+                                 f"aligned pointer (a partial is not copied), got strides {tuple(t.stride())}, pointer % 8 = "
+                                 f"{t.data_ptr() % 8}")
+        elif any(st < 0 for st in t.stride()):
+            raise ValueError(f"{name}: non-negative strides, got {tuple(t.stride())}")
+        if result and any(st <= 0 for n, st in zip(t.shape, t.stride()) if n > 1):
+            raise ValueError(f"{name}: a result is written once per element: positive strides, got {tuple(t.stride())}")
+    for i in range(N):
+        held(f"outs[{i}]", po[i], shape, o0.dtype, True)
+        held(f"lses[{i}]", pl[i], shape[:-1], torch.float32, False)
+    if isinstance(sink, torch.Tensor):
+        if sink.dtype != torch.float32 or sink.numel() not in (1, H):
+            raise ValueError(f"sink: a float32 tensor of 1 or {H} values, got {sink.dtype} {tuple(sink.shape)}")
+        if sink.device != o0.device:
+            raise ValueError(f"sink is on {sink.device}, the partials on {o0.device}")
+    elif sink is not None and (isinstance(sink, bool) or not isinstance(sink, (int, float)) or not float(sink) < float("inf")):
+        raise ValueError(f"sink: None, a float below +inf or a float32 tensor of 1 or {H} values, got {sink!r}")
+    if out is not None:
+        held("out", out, shape, o0.dtype, True, result=True)
+        _merge_alias("out", out, po, [(f"lses[{i}]", t) for i, t in enumerate(pl)] + [("sink", sink if isinstance(sink, torch.Tensor) else None)],
+                     "outs")
+    if lse is not None:
+        if not return_lse:
+            raise ValueError("lse= belongs to return_lse=True")
+        held("lse", lse, shape[:-1], torch.float32, False, result=True)
+        _merge_alias("lse", lse, pl, [(f"outs[{i}]", t) for i, t in enumerate(po)] + [("out", out), ("sink", sink if isinstance(sink, torch.Tensor) else None)],
+                     "lses")
+    _core._require_device(*po, *pl)
+    dev = o0.device
+    if out is None:
+        out = torch.empty(shape, dtype=o0.dtype, device=dev)
+    if lse is None and return_lse:
+        lse = torch.empty(shape[:-1], dtype=torch.float32, device=dev)
+    sink_dev = None
+    if isinstance(sink, torch.Tensor):
+        sink_dev = sink.reshape(-1).expand(H).contiguous()
+    elif sink is not None and float(sink) > float("-inf"):      # (a Python float is filled in by torch: capturable)
+        sink_dev = torch.full((H,), float(sink), dtype=torch.float32, device=dev)
+    if len(shape) == 4:
+        B, S = shape[0], shape[2]
+        t4 = lambda t: (t.data_ptr(), t.stride(0), t.stride(1), t.stride(2))        # noqa: E731
+        l3 = lambda t: (t.stride(0), t.stride(1), t.stride(2))                      # noqa: E731
+    else:       # packed [T, H, D] / [T, H]: one item of T rows, stride_s the row's and stride_h the head's
+        B, S = 1, shape[0]
+        t4 = lambda t: (t.data_ptr(), 0, t.stride(1), t.stride(0))                  # noqa: E731
+        l3 = lambda t: (0, t.stride(1), t.stride(0))                                # noqa: E731
+    c_outs = (RsaTensor4 * N)(*[RsaTensor4(*t4(t)) for t in po])
+    c_lses = (ctypes.c_void_p * N)(*[t.data_ptr() for t in pl])
+    c_strides = (ctypes.c_int64 * (3 * N))(*[st for t in pl for st in l3(t)])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rsa_merge_partials(N, B, H, S, D, _core.dtype_code(o0.dtype), c_outs, c_lses, c_strides, _ptr(sink_dev),
+                                                 RsaOut4(*t4(out)), _ptr(lse), *(l3(lse) if lse is not None else (0, 0, 0)),
+                                                 _core._stream()), "rsa_merge_partials")
     return (out, lse) if return_lse else out
 
 
