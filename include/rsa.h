@@ -675,6 +675,38 @@ int rsa_merge_partials(int N, int B, int H, int S, int D, int dtype, const rsa_t
                        const int64_t* lse_strides, const float* sink, rsa_out4 out, float* lse_out, int64_t lse_out_stride_b,
                        int64_t lse_out_stride_h, int64_t lse_out_stride_s, void* stream);
 
+/* ---- block-sparse attention BACKWARD: dq, dk, dv of the plain / grouped-query forward over a caller's block mask, with a causal
+ * limit and per-item key limits (found by symbol: the header version stays 6.1).  q, out, dout
+ * [B, H, Sq, D], k, v [B, Hkv, Sk, D], H a multiple of Hkv, query head h reads K/V head h / (H / Hkv) and walks the lists of list
+ * head h / (H / Hl), Hl in {1, Hkv, H}.  len_b = kv_len_dev[b] clamped into [0, Sk] (DEVICE int32, B values, read on the device
+ * only) or, with kv_len_dev NULL, kv_valid in [0, Sk].
+ *   visible   row r of (b, h) sees key j iff its query block keeps key block j / block, j < len_b, and with causal
+ *             j <= r + len_b - Sq (bottom-right aligned)
+ *   lists     row_cols [B * Hl, NQ, NK] / row_counts [B * Hl, NQ]: rsa_block_mask_to_lists of the mask [B, Hl, NQ, NK];
+ *             col_cols [B * Hl, NK, NQ] / col_counts [B * Hl, NK]: the same call on the mask with its last two axes exchanged (the
+ *             query blocks that keep a key block, ascending).  NQ = ceil(Sq / block), NK <= ceil(Sk / block): key blocks >= NK are
+ *             never visited.  Entries outside their range are skipped; no address is formed from an unchecked index.
+ *   numerics  scores as the forward: q * (float)(sm_scale * 1.44269504) rounded to the 2-byte type, log2 domain, fp32.  The row
+ *             statistics are recomputed (lse2 = m + log2 l, delta = sum_d dout * out, fp32 [B, H, Sq] each in ws), P = exp2(S -
+ *             lse2) and dS = P * (dP - delta) are rounded to the 2-byte type for the products they feed, everything is accumulated
+ *             in fp32 and dq = sm_scale * sum, dk = sm_scale * sum, dv = sum are converted once.
+ *   keys      at or beyond len_b are never multiplied (k / v may hold NaN there); their dk / dv rows are zeros, as are those of key
+ *             blocks no query block keeps.  A query row that sees no key gets a zero dq row.  Every element of dq [B, H, Sq, D] and
+ *             dk, dv [B, Hkv, Sk, D] is written exactly once.
+ * Three launches (row statistics; dq; dk and dv), no float atomics and no hand-off between workgroups: the same inputs give the same
+ * bytes.  ws: DEVICE scratch of at least rsa_block_sparse_bwd_bytes(...) bytes, 16-byte aligned.  Inputs: 16-byte aligned pointers,
+ * non-negative strides that are multiples of 8 elements, D contiguous; results: 8-byte aligned, strides multiples of 4 and positive
+ * where an axis has more than one entry.  A NULL pointer, a bad stride, Hkv or Hl not dividing H, Hl outside {1, Hkv, H}, NQ / NK
+ * not matching Sq / Sk, kv_valid outside [0, Sk]: RSA_ERR_BAD_ARG; block other than 64 / 128, D other than 64 / 128, another dtype,
+ * more than 8192 query or key blocks, B or H above 65535: RSA_ERR_UNSUPPORTED; ws_bytes too small: RSA_ERR_WORKSPACE.  Every check
+ * runs before the first HIP call; B, H or Sq of 0: RSA_OK without a launch. */
+int rsa_block_sparse_bwd_bytes(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int block, int NQ, int NK, size_t* bytes);
+int rsa_block_sparse_bwd(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NQ, int NK, int kv_valid,
+                         const int32_t* kv_len_dev, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k, rsa_tensor4 v,
+                         rsa_tensor4 out, rsa_tensor4 dout, const int32_t* row_cols, const int32_t* row_counts,
+                         const int32_t* col_cols, const int32_t* col_counts, void* ws, size_t ws_bytes, rsa_out4 dq, rsa_out4 dk,
+                         rsa_out4 dv, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

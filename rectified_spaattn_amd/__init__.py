@@ -165,6 +165,25 @@ def merge_partials(outs, lses, *, sink=None, out=None, lse=None, return_lse=True
     return block_sparse.merge_partials(outs, lses, sink=sink, out=out, lse=lse, return_lse=return_lse)
 
 
+def block_sparse_attention_backward(dout, q, k, v, out, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False,
+                                    window=None, row_range=None):
+    """(dq, dk, dv) of block_sparse_attention(q, k, v, block_mask, ...) for the upstream gradient dout of its result out: three
+    launches for the whole batch, no float atomics, the same bytes from two calls.  See
+    rectified_spaattn_amd.block_sparse.block_sparse_attention_backward."""
+    from . import block_sparse
+    return block_sparse.block_sparse_attention_backward(dout, q, k, v, out, block_mask, kv_len=kv_len, sm_scale=sm_scale,
+                                                        block_size=block_size, causal=causal, window=window, row_range=row_range)
+
+
+def block_sparse_attention_autograd(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, window=None,
+                                    row_range=None):
+    """block_sparse_attention as a differentiable call: the forward's bytes, and .backward() fills q.grad, k.grad and v.grad through
+    block_sparse_attention_backward.  See rectified_spaattn_amd.block_sparse.block_sparse_attention_autograd."""
+    from . import block_sparse
+    return block_sparse.block_sparse_attention_autograd(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale,
+                                                        block_size=block_size, causal=causal, window=window, row_range=row_range)
+
+
 def clear_buffer_cache() -> None:
     """Drops the intermediate buffers the operators keep per (geometry, device, stream) between calls (about 0.45 GB per
     set at the HunyuanVideo shape; `_core.BUFFER_CACHE_MAX_BYTES` bounds the total, `_core.BUFFER_CACHE = False` turns the

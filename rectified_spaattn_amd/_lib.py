@@ -194,6 +194,10 @@ PROTOTYPES = {
                                              i32, vp, sz, vp, vp, vp, vp, i32, f32, vp, vp, vp]),
     # the merge of attention partials: additive and found by symbol, in front of the extend entries as well
     "rsa_merge_partials": (i32, [i32, i32, i32, i32, i32, i32, P(T4), P(vp), P(i64), vp, O4, vp, i64, i64, i64, vp]),
+    # the block-sparse backward: additive and found by symbol, in front of the extend entries too
+    "rsa_block_sparse_bwd_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_block_sparse_bwd": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, f64, T4, T4, T4, T4, T4, vp,
+                                   vp, vp, vp, vp, sz, O4, O4, O4, vp]),
     "rsa_block_sparse_extend_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz)]),
     "rsa_block_sparse_extend": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp, i64,
                                       i32, vp, vp, i32, vp, sz, O4, vp, vp]),

@@ -26,6 +26,9 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              (k_scale= / v_scale=: rsa_block_sparse_decode_kv8, rsa_pool_keys_kv8)
     merge_partials           the merge of N (out, lse) partials of block_sparse_decode / block_sparse_extend over disjoint key sets,
                              with optional sink logits: one launch, no copy (rsa_merge_partials)
+    block_sparse_attention_backward   dq, dk, dv of block_sparse_attention (mask, kv_len, causal, GQA): row statistics recomputed,
+                             two sweeps, no float atomics (rsa_block_sparse_bwd), and
+                             block_sparse_attention_autograd, the torch.autograd.Function over the two
     build_block_index        K1..K3 of the rectified call (pooling, pooled scores + GAPR, selection), then
                              rsa_lists_to_block_mask for the reference's dense one-hot form
 
@@ -597,6 +600,116 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
     if kv_valid == 0:   # no visible key at all
         return torch.zeros((B, H, Sq, D), dtype=q.dtype, device=q.device)
     return _k5_launch(q, k, v, block_mask, blk, scale, [(0, B, kv_valid)], lo, hi)
+
+
+def _check_no_ranges(what: str, window, row_range):
+    if window is not None or row_range is not None:
+        raise NotImplementedError(f"{what}: window= and row_range= have no backward yet (the backward serves the block mask, kv_len "
+                                  "and causal=; DESIGN.md section 5.21)")
+
+
+def _bwd_launch(dout, q, k, v, out, block_mask, blk: int, scale: float, lens, causal: bool):
+    """block_sparse_attention_backward's launch sequence (rsa_block_sparse_bwd: row statistics, dq, dk / dv) for the whole batch."""
+    B, H, Sq, D = q.shape
+    if D in _core._PAD_HEAD_DIM:   # zero columns add exact zeros to every dot product; the caller's scale is kept
+        pad = (0, _core._PAD_HEAD_DIM[D] - D)
+        F = torch.nn.functional
+        res = _bwd_launch(*(F.pad(t, pad) for t in (dout, q, k, v, out)), block_mask, blk, scale, lens, causal)
+        return tuple(t[..., :D].contiguous() for t in res)
+    Hkv, Sk = k.shape[1], k.shape[2]
+    dev = q.device
+    L = _lib.lib()
+    dout, q, k, v, out = (_core._as_bhsd(t) for t in (dout, q, k, v, out))
+    NQ, NK, Hl = -(-Sq // blk), block_mask.shape[3], int(block_mask.shape[1])
+    # the row lists (the key blocks a query block keeps) and the column lists (the query blocks that keep a key block): the same
+    # conversion on the mask and on its transpose
+    rows = block_mask_to_lists(block_mask, B, Hl)
+    cols = block_mask_to_lists(block_mask.transpose(-1, -2).contiguous(), B, Hl)
+    len_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
+    dq = torch.empty((B, H, Sq, D), dtype=q.dtype, device=dev)
+    dk = torch.empty((B, Hkv, Sk, D), dtype=q.dtype, device=dev)
+    dv = torch.empty((B, Hkv, Sk, D), dtype=q.dtype, device=dev)
+    shape = (B, H, Hkv, Hl, Sq, Sk, D)
+    need = ctypes.c_size_t(0)
+    _lib.check(L.rsa_block_sparse_bwd_bytes(*shape, blk, NQ, NK, ctypes.byref(need)), "rsa_block_sparse_bwd_bytes")
+    ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.rsa_block_sparse_bwd(*shape, _core.dtype_code(q.dtype), blk, NQ, NK, kv_valid, _ptr(len_dev), int(causal), scale,
+                                          _core._t4(q), _core._t4(k), _core._t4(v), _core._t4(out), _core._t4(dout),
+                                          rows["cols"].data_ptr(), rows["counts"].data_ptr(), cols["cols"].data_ptr(),
+                                          cols["counts"].data_ptr(), ws.data_ptr(), ws.numel(), _out4(dq), _out4(dk), _out4(dv),
+                                          _core._stream()), "rsa_block_sparse_bwd")
+    return dq, dk, dv
+
+
+def block_sparse_attention_backward(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor,
+                                    block_mask: torch.Tensor, *, kv_len=None, sm_scale: Optional[float] = None,
+                                    block_size: int = 128, causal: bool = False, window=None, row_range=None):
+    """The gradients (dq, dk, dv) of out = block_sparse_attention(q, k, v, block_mask, kv_len=, sm_scale=, block_size=, causal=)
+    for the upstream gradient dout; every argument means what it means there.  q, out, dout [B,H,Sq,D]; k, v [B,Hkv,Sk,D] with
+    H % Hkv == 0; block_mask bool / uint8 [B|1, Hl, ceil(Sq/block), NK] with Hl in {1, Hkv, H}; both block sizes; causal (aligned
+    bottom-right, j <= r + kv_len[b] - Sq) at 128-token blocks as the forward; bf16 / fp16; head dims 64 / 128 native, 16 / 32
+    zero-padded.  Any strides with a contiguous head dim run without a copy.  kv_len None, an int, one value per item or a device
+    tensor: all become one device int32 [B] array, the call is ONE launch sequence for the whole batch, and a device tensor is never
+    read on the host.  Returns dq [B,H,Sq,D] and dk, dv [B,Hkv,Sk,D] in the input dtype.
+
+    The row statistics are recomputed from q and k (the forward keeps none): two sweeps over the kept tiles, no float atomics --
+    two calls give the same bytes.  Keys at or beyond kv_len are never multiplied (k / v may hold NaN
+    there) and get zero dk / dv rows, as do key blocks no query block keeps; a query row that sees no key gets a zero dq row.
+    window= and row_range= are not served (NotImplementedError), nor are the rectified calls, the fp8 forms and paged caches."""
+    blk = _check_block_pair(block_size, block_size)
+    _check_no_ranges("block_sparse_attention_backward", window, row_range)
+    if causal and blk != _lib.BLOCK:
+        raise NotImplementedError(f"causal needs block_size = {_lib.BLOCK}, as in block_sparse_attention")
+    B, H, Hkv, Sq, Sk, D = _check_operands(q, k, v)
+    for name, t in (("out", out), ("dout", dout)):
+        if not isinstance(t, torch.Tensor) or t.shape != q.shape or t.dtype != q.dtype:
+            raise ValueError(f"{name}: a {q.dtype} tensor {tuple(q.shape)} like q, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    NQ, NKmax = -(-Sq // blk), -(-Sk // blk)
+    if not isinstance(block_mask, torch.Tensor) or block_mask.dim() != 4 or block_mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"block_mask: a 4-d bool or uint8 tensor, got {getattr(block_mask, 'dtype', type(block_mask))} "
+                         f"{tuple(getattr(block_mask, 'shape', ()))}")
+    if (block_mask.shape[0] not in (1, B) or block_mask.shape[1] not in (1, Hkv, H) or block_mask.shape[2] != NQ
+            or not 1 <= block_mask.shape[3] <= min(NKmax, MAX_KEY_BLOCKS) or NQ > MAX_KEY_BLOCKS):
+        raise ValueError(f"block_mask {tuple(block_mask.shape)}: expected [{B}|1, {H}|{Hkv}|1, {NQ}, 1..{min(NKmax, MAX_KEY_BLOCKS)}] "
+                         f"for block {blk} (at most {MAX_KEY_BLOCKS} query and key blocks)")
+    lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
+    _core._require_device(dout, q, k, v, out)
+    scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
+    if block_mask.device != q.device:
+        block_mask = block_mask.to(q.device)
+    return _bwd_launch(dout, q, k, v, out, block_mask, blk, scale, lens, bool(causal))
+
+
+class _BlockSparseAttention(torch.autograd.Function):
+    """block_sparse_attention with block_sparse_attention_backward behind it; the mask and kv_len get no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, block_mask, kv_len, sm_scale, block_size, causal):
+        out = block_sparse_attention(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size, causal=causal)
+        ctx.save_for_backward(q, k, v, out, block_mask)
+        ctx.opts = (kv_len, sm_scale, block_size, causal)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, block_mask = ctx.saved_tensors
+        kv_len, sm_scale, block_size, causal = ctx.opts
+        dq, dk, dv = block_sparse_attention_backward(dout, q, k, v, out, block_mask, kv_len=kv_len, sm_scale=sm_scale,
+                                                     block_size=block_size, causal=causal)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def block_sparse_attention_autograd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask: torch.Tensor, *, kv_len=None,
+                                    sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, window=None,
+                                    row_range=None) -> torch.Tensor:
+    """block_sparse_attention(q, k, v, block_mask, kv_len=, sm_scale=, block_size=, causal=) as a torch.autograd.Function: the
+    forward is that call (the same bytes), the backward block_sparse_attention_backward; q, k and v get gradients, the mask and
+    kv_len none.  Under torch.no_grad() it is the forward.  window= and row_range= are not served (NotImplementedError).
+    block_sparse_attention itself stays as it is: it builds no graph."""
+    _check_no_ranges("block_sparse_attention_autograd", window, row_range)
+    return _BlockSparseAttention.apply(q, k, v, block_mask, kv_len, sm_scale, block_size, bool(causal))
 
 
 def select_blocks(q: torch.Tensor, k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None, causal: bool = False,
