@@ -9,6 +9,11 @@
 #include "rsa_walk_order.h"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+// The transposed LDS read of 16-bit elements (ds_read_b64_tr_b16): the decode and the backward kernels' V and image fragments.
+__device__ __forceinline__ s16x4 rsa_tr_read(const unsigned char* p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+}
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));

@@ -7,13 +7,18 @@
 //                              query side adds the means of the list head's query heads in ascending order (H / Hl of them).
 //   pool_keys_kernel           W workgroups per (b, K/V head) stride over the key blocks [start / block, ceil(len / block)) and
 //                              write sel_pool_mean of each, read directly or through a block table, into the fp32 cache
-//   block_score_kernel         `splits` workgroups per list row: each writes its slice of the row's ordered keys to the workspace
-//                              (a lane group computes a whole score: nothing is summed across workgroups)
 //   pool_key_bounds_kernel     pool_keys_kernel's min/max twin: per key block and channel the minimum and the maximum of the keys, into
-//                              the fp32 bounds cache [.., NK, 2, D] (rsa_pool_key_bounds; section 5.19)
-//   block_score_kernel<BOUND>  block_score_kernel over that cache: t = sum_d max(q_d mn_d, q_d mx_d), the upper bound of q . k
-//                              over every key the block could hold (rsa_block_select_bound); the select kernels rank its keys LOADED
+//                              the fp32 bounds cache [.., NK, 2, D] (rsa_pool_key_bounds; section 5.19).  Kept as a twin: the one
+//                              kernel over a reducer was slower (profiles/select_twins_isa.md)
+//   block_score_kernel<BOUND>  `splits` workgroups per list row: each writes its slice of the row's ordered keys to the workspace
+//                              (a lane group computes a whole score: nothing is summed across workgroups).  Over the mean cache
+//                              t = q . mean; BOUND, over the bounds cache: t = sum_d max(q_d mn_d, q_d mx_d), the upper bound of
+//                              q . k over every key the block could hold (rsa_block_select_bound); the select kernels rank its
+//                              keys LOADED
 //   block_select[_p]_kernel    one 256-thread workgroup per list row (b, list head, query block): top-k; top-p capped at top_k
+//
+// The element loader (sel_unpack8) and the score body (sel_score_blocks<L, Form> over the score forms SelMean / SelBounds) exist
+// once.
 //
 // The two select kernels are sel_row_body<L, LOADED, BUDGET>: the pooled scores of the visible key blocks into LDS as
 // order-preserving 32-bit keys (computed, or LOADED from block_score_kernel's workspace), one decision (take_all, cut, T, need_eq),
@@ -37,10 +42,6 @@
 #define SEL_MAX_STEPS (SEL_MAX_NK / 64)
 #define SEL_MAX_SPLITS 256      // score workgroups per list row of the pooled selection, at most
 #define SELP_ONE 262144u        // 2^18: the weight of the row's best block
-
-__device__ __forceinline__ int sel_key_limit(const int32_t* __restrict__ kv_len, int b, int kv_valid, int Sk) {
-    return kv_len ? min(max(kv_len[b], 0), Sk) : kv_valid;
-}
 
 // fp32 -> u32 with the order of the floats (-0 counts as +0); and back.
 __device__ __forceinline__ unsigned sel_key(float x) {
@@ -85,9 +86,9 @@ __device__ __forceinline__ int sel_visible(int len, int Sq, int blk, int NK, int
 }
 
 // ---- pooling ---------------------------------------------------------------------------------------------------------------------
-// The element loaders: what a lane reads for its 8 channels of a row, and how it adds them.  bf16 / fp16: 16 bytes.  e4m3_tag (the
-// one-byte K cache of DESIGN.md section 5.14, rsa_pool_keys_kv8): 8 bytes of codes, added as float(code); the head's scale
-// multiplies the finished mean once.  Everything below the loaders exists once.
+// The element loader: what a lane reads for its 8 channels of a row, as 8 floats.  bf16 / fp16: 16 bytes.  e4m3_tag (the one-byte
+// K cache of DESIGN.md section 5.14, rsa_pool_keys_kv8): 8 bytes of codes, each as float(code); the head's scale multiplies the
+// finished block once.  sel_add8 and sel_minmax8 are the two steps over the 8 floats: the mean cache's and the bounds cache's.
 struct e4m3_tag {};
 template <typename Tag>
 struct SelElem {
@@ -101,25 +102,42 @@ struct SelElem<e4m3_tag> {
 };
 
 template <typename Tag>
-__device__ __forceinline__ void sel_add8(float (&a)[8], const typename SelElem<Tag>::vec v) {
+__device__ __forceinline__ void sel_unpack8(float (&x)[8], const typename SelElem<Tag>::vec v) {
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        a[2 * i] += rsa_to_f32<Tag>((unsigned short)(w[i] & 0xFFFFu));
-        a[2 * i + 1] += rsa_to_f32<Tag>((unsigned short)(w[i] >> 16));
+        x[2 * i] = rsa_to_f32<Tag>((unsigned short)(w[i] & 0xFFFFu));
+        x[2 * i + 1] = rsa_to_f32<Tag>((unsigned short)(w[i] >> 16));
     }
 }
 template <>
-__device__ __forceinline__ void sel_add8<e4m3_tag>(float (&a)[8], const uint2 v) {
+__device__ __forceinline__ void sel_unpack8<e4m3_tag>(float (&x)[8], const uint2 v) {
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const unsigned w[2] = {v.x, v.y};
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
-        a[4 * i] += lo[0];
-        a[4 * i + 1] += lo[1];
-        a[4 * i + 2] += hi[0];
-        a[4 * i + 3] += hi[1];
+        x[4 * i] = lo[0];
+        x[4 * i + 1] = lo[1];
+        x[4 * i + 2] = hi[0];
+        x[4 * i + 3] = hi[1];
+    }
+}
+template <typename Tag>
+__device__ __forceinline__ void sel_add8(float (&a)[8], const typename SelElem<Tag>::vec v) {
+    float x[8];
+    sel_unpack8<Tag>(x, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] += x[e];
+}
+template <typename Tag>
+__device__ __forceinline__ void sel_minmax8(float (&mn)[8], float (&mx)[8], const typename SelElem<Tag>::vec v) {
+    float x[8];
+    sel_unpack8<Tag>(x, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        mn[e] = fminf(mn[e], x[e]);
+        mx[e] = fmaxf(mx[e], x[e]);
     }
 }
 
@@ -198,7 +216,7 @@ __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q
     const long bh = job / NK;
     const int hk = (int)(bh % Hkv);
     const long b = bh / Hkv;
-    const int len = sel_key_limit(kv_len, (int)b, kv_valid, Sk);
+    const int len = rsa_key_limit(kv_len, (int)b, kv_valid, Sk);
     const int rows = min(blk, len - j * blk);       // keys of block j below the limit (uniform over the workgroup)
     float mean = 0.f;
     if (rows > 0) {
@@ -228,8 +246,8 @@ __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hk
     const long bh = blockIdx.x / (unsigned)W;
     const int hk = (int)(bh % Hkv);
     const long b = bh / Hkv;
-    const int len = sel_key_limit(kv_len, (int)b, kv_valid, Sk);
-    const int st = sel_key_limit(start_dev, (int)b, start_host, Sk);
+    const int len = rsa_key_limit(kv_len, (int)b, kv_valid, Sk);
+    const int st = rsa_key_limit(start_dev, (int)b, start_host, Sk);
     if (st > len) return;
     const int j_hi = min(NK, (len + blk - 1) / blk);
     for (int j = st / blk + w; j < j_hi; j += W) {
@@ -250,40 +268,6 @@ __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hk
 }
 
 // ---- the bounds cache -----------------------------------------------------------------------------------------
-// What a lane reads for its 8 channels of a row, as floats (e4m3: float(code)); sel_add8's loads and conversions.
-template <typename Tag>
-__device__ __forceinline__ void sel_unpack8(float (&x)[8], const typename SelElem<Tag>::vec v) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        x[2 * i] = rsa_to_f32<Tag>((unsigned short)(w[i] & 0xFFFFu));
-        x[2 * i + 1] = rsa_to_f32<Tag>((unsigned short)(w[i] >> 16));
-    }
-}
-template <>
-__device__ __forceinline__ void sel_unpack8<e4m3_tag>(float (&x)[8], const uint2 v) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    const unsigned w[2] = {v.x, v.y};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
-        x[4 * i] = lo[0];
-        x[4 * i + 1] = lo[1];
-        x[4 * i + 2] = hi[0];
-        x[4 * i + 3] = hi[1];
-    }
-}
-template <typename Tag>
-__device__ __forceinline__ void sel_minmax8(float (&mn)[8], float (&mx)[8], const typename SelElem<Tag>::vec v) {
-    float x[8];
-    sel_unpack8<Tag>(x, v);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        mn[e] = fminf(mn[e], x[e]);
-        mx[e] = fmaxf(mx[e], x[e]);
-    }
-}
-
 // The min/max twin of sel_pool_block: per channel the minimum and the maximum over `rows` rows (>= 1, uniform over the workgroup);
 // thread t < D returns channel t's pair (x: min, y: max).  The same loads, row striding and xor strides; a thread without a row
 // holds (+inf, -inf), which no minimum or maximum keeps.  min and max are exact and order-free: any split of the rows gives the
@@ -346,8 +330,8 @@ __global__ __launch_bounds__(SEL_NT) void pool_key_bounds_kernel(rsa_tensor4 k, 
     const long bh = blockIdx.x / (unsigned)W;
     const int hk = (int)(bh % Hkv);
     const long b = bh / Hkv;
-    const int len = sel_key_limit(kv_len, (int)b, kv_valid, Sk);
-    const int st = sel_key_limit(start_dev, (int)b, start_host, Sk);
+    const int len = rsa_key_limit(kv_len, (int)b, kv_valid, Sk);
+    const int st = rsa_key_limit(start_dev, (int)b, start_host, Sk);
     if (st > len) return;
     const int j_hi = min(NK, (len + blk - 1) / blk);
     for (int j = st / blk + w; j < j_hi; j += W) {
@@ -375,59 +359,52 @@ __global__ __launch_bounds__(SEL_NT) void pool_key_bounds_kernel(rsa_tensor4 k, 
 }
 
 // ---- scores ----------------------------------------------------------------------------------------------------------------------
+// The score forms: how many rows of D floats a cached block has (N) and what a lane adds to a block's score from its four channels
+// of the pooled query (q) and of the block's rows (k).
+struct SelMean {        // the mean cache: t = q . mean, one fmaf chain per lane
+    static constexpr int N = 1;
+    static __device__ __forceinline__ float term(const float4 q, const float4 (&k)[1]) {
+        return fmaf(q.w, k[0].w, fmaf(q.z, k[0].z, fmaf(q.y, k[0].y, q.x * k[0].x)));
+    }
+};
+struct SelBounds {      // the bounds cache, row 0 the minima, row 1 the maxima: t = sum over d of
+                        // max(q_d mn_d, q_d mx_d), per lane four terms, each the larger of two separately rounded fp32 products,
+                        // added as ((x + y) + z) + w
+    static constexpr int N = 2;
+    static __device__ __forceinline__ float term(const float4 q, const float4 (&k)[2]) {
+        return ((fmaxf(q.x * k[0].x, q.x * k[1].x) + fmaxf(q.y * k[0].y, q.y * k[1].y)) + fmaxf(q.z * k[0].z, q.z * k[1].z)) +
+               fmaxf(q.w * k[0].w, q.w * k[1].w);
+    }
+};
+
 // Scores of the key blocks [lo, hi) of one list row as ordered keys into dst[j], by one workgroup.  L = D / 4 lanes share one
-// pooled key row (a float4 each); a wave scores 64 / L key blocks per step.  kb: the pooled rows of (b, K/V head); qrow: the row's
-// pooled query.
-template <int L>
+// cached block (a float4 of each of its Form::N rows); a wave scores 64 / L key blocks per step.  kb: the cached blocks of (b, K/V
+// head), Form::N * D floats each; qrow: the row's pooled query.  The lanes' terms meet over xor strides 1 .. L / 2.
+template <int L, typename Form>
 __device__ __forceinline__ void sel_score_blocks(const float* __restrict__ kb, const float* __restrict__ qrow, int lo, int hi,
                                                  unsigned* dst) {
-    constexpr int D = 4 * L, RW = 64 / L, U = 4;
+    constexpr int D = 4 * L, RW = 64 / L, U = 4, N = Form::N;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int cl = lane % L, sub = lane / L;
     const float4 qv = *reinterpret_cast<const float4*>(qrow + cl * 4);
     kb += cl * 4;
     for (int j0 = lo + wave * RW; j0 < hi; j0 += 4 * RW * U) {
-        float4 kv[U];
+        float4 kv[U][N];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = j0 + u * 4 * RW + sub;
-            kv[u] = j < hi ? *reinterpret_cast<const float4*>(kb + (long)j * D) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4* row = reinterpret_cast<const float4*>(kb + (long)j * N * D);
+#pragma unroll
+            for (int n = 0; n < N; ++n) kv[u][n] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (j < hi) {       // (one branch for all rows of the block)
+#pragma unroll
+                for (int n = 0; n < N; ++n) kv[u][n] = row[n * L];
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = j0 + u * 4 * RW + sub;
-            float p = fmaf(qv.w, kv[u].w, fmaf(qv.z, kv[u].z, fmaf(qv.y, kv[u].y, qv.x * kv[u].x)));
-#pragma unroll
-            for (int m = 1; m < L; m <<= 1) p += __shfl_xor(p, m, 64);
-            if (cl == 0 && j < hi) dst[j] = sel_key(p);
-        }
-    }
-}
-
-// The bound scores of the key blocks [lo, hi) of one list row: sel_score_blocks over the bounds cache.  kb:
-// the (min, max) row pairs of (b, K/V head), 2 D floats a block.  t = sum over d of max(q_d mn_d, q_d mx_d): per lane four terms,
-// each the larger of two separately rounded fp32 products, added as ((x + y) + z) + w; the lanes meet over the same xor strides.
-template <int L>
-__device__ __forceinline__ void sel_bound_score_blocks(const float* __restrict__ kb, const float* __restrict__ qrow, int lo, int hi,
-                                                       unsigned* dst) {
-    constexpr int D = 4 * L, RW = 64 / L, U = 4;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int cl = lane % L, sub = lane / L;
-    const float4 qv = *reinterpret_cast<const float4*>(qrow + cl * 4);
-    kb += cl * 4;
-    for (int j0 = lo + wave * RW; j0 < hi; j0 += 4 * RW * U) {
-        float4 mn[U], mx[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * 4 * RW + sub;
-            mn[u] = j < hi ? *reinterpret_cast<const float4*>(kb + (long)j * 2 * D) : make_float4(0.f, 0.f, 0.f, 0.f);
-            mx[u] = j < hi ? *reinterpret_cast<const float4*>(kb + (long)j * 2 * D + D) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * 4 * RW + sub;
-            float p = ((fmaxf(qv.x * mn[u].x, qv.x * mx[u].x) + fmaxf(qv.y * mn[u].y, qv.y * mx[u].y)) +
-                       fmaxf(qv.z * mn[u].z, qv.z * mx[u].z)) + fmaxf(qv.w * mn[u].w, qv.w * mx[u].w);
+            float p = Form::term(qv, kv[u]);
 #pragma unroll
             for (int m = 1; m < L; m <<= 1) p += __shfl_xor(p, m, 64);
             if (cl == 0 && j < hi) dst[j] = sel_key(p);
@@ -451,11 +428,11 @@ __global__ __launch_bounds__(SEL_NT) void block_score_kernel(const float* __rest
     const int hl = (int)(bh % Hl);
     const long b = bh / Hl;
     const int hk = hl / (Hl / Hkv);
-    const int nvis = sel_visible<Rows::SHORT>(sel_key_limit(kv_len, (int)b, kv_valid, Sk), src.count((int)b, Sq), blk, NK, i, causal);
+    const int nvis = sel_visible<Rows::SHORT>(rsa_key_limit(kv_len, (int)b, kv_valid, Sk), src.count((int)b, Sq), blk, NK, i, causal);
     const int chunk = (NK + splits - 1) / splits;
     const int lo = part * chunk, hi = min(lo + chunk, nvis);
-    if constexpr (BOUND) sel_bound_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * 2 * D, qsum + row * D, lo, hi, wkeys + row * NK);
-    else sel_score_blocks<L>(kbar + ((b * Hkv + hk) * NK) * D, qsum + row * D, lo, hi, wkeys + row * NK);
+    using Form = std::conditional_t<BOUND, SelBounds, SelMean>;
+    sel_score_blocks<L, Form>(kbar + ((b * Hkv + hk) * NK) * Form::N * D, qsum + row * D, lo, hi, wkeys + row * NK);
 }
 
 // ---- select ----------------------------------------------------------------------------------------------------------------------
@@ -563,7 +540,7 @@ __device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c
     const int hl = (int)(bh % r.Hl);
     const long b = bh / r.Hl;
     const int hk = hl / (r.Hl / r.Hkv);
-    const int len = sel_key_limit(r.kv_len, (int)b, r.kv_valid, r.Sk);
+    const int len = rsa_key_limit(r.kv_len, (int)b, r.kv_valid, r.Sk);
     const int Sq = SHORT ? RowsCounted{q_len}.count((int)b, r.Sq) : r.Sq;      // the batch item's rows: r1 and off count from them
 
     // 1. visible blocks: a prefix [0, nvis) of the row; forced blocks: [0, kf) and [flo, fhi] within it
@@ -583,7 +560,7 @@ __device__ __forceinline__ void sel_row_body(const sel_rows& r, int p16, float c
         const unsigned* wr = r.wkeys + row * NK;
         for (int j = tid; j < nvis; j += SEL_NT) keys[j] = wr[j];
     } else {
-        sel_score_blocks<L>(r.kbar + ((b * r.Hkv + hk) * NK) * D, r.qsum + row * D, 0, nvis, keys);
+        sel_score_blocks<L, SelMean>(r.kbar + ((b * r.Hkv + hk) * NK) * D, r.qsum + row * D, 0, nvis, keys);
     }
     __syncthreads();
     if (r.scores) {
@@ -879,10 +856,8 @@ static int sel_pool_keys_run(bool kv8, bool bounds, int B, int Hkv, int Sk, int 
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((size_t)B * Hkv * W));
-    auto* kernel = kv8 ? pool_keys_kernel<e4m3_tag> : dtype == RSA_BF16 ? pool_keys_kernel<bf16_tag> : pool_keys_kernel<fp16_tag>;
-    if (bounds)
-        kernel = kv8 ? pool_key_bounds_kernel<e4m3_tag>
-                     : dtype == RSA_BF16 ? pool_key_bounds_kernel<bf16_tag> : pool_key_bounds_kernel<fp16_tag>;
+    auto form = [&](auto tag) { return bounds ? pool_key_bounds_kernel<decltype(tag)> : pool_keys_kernel<decltype(tag)>; };
+    auto* kernel = kv8 ? form(e4m3_tag{}) : dtype == RSA_BF16 ? form(bf16_tag{}) : form(fp16_tag{});
     kernel<<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start, block_table,
                                    (long)table_stride_b, num_pages, out, k_scale);     // (k_scale: NULL unless kv8)
     return rsa_launch_status();

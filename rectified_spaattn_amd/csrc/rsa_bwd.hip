@@ -58,10 +58,6 @@ struct BwdImg {
     static constexpr int BYTES = 32 * ROWB;
 };
 
-__device__ __forceinline__ s16x4 bwd_tr_read(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-
 // 32 rows x D elements from global memory (row stride `stride` elements) into an image, by NT threads; rows >= nrows become zeros
 // and are not read
 template <int D, int NT>
@@ -91,7 +87,7 @@ template <int D>
 __device__ __forceinline__ s16x8 bwd_tr_frag(const unsigned char* img, int lane, int dt, int s) {
     const int hh = lane >> 5, g4 = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
     const unsigned char* p = img + (16 * s + 4 * hh + tq) * BwdImg<D>::ROWB + 2 * (32 * dt + 16 * (g4 & 1) + 4 * tp);
-    const s16x4 lo = bwd_tr_read(p), hi = bwd_tr_read(p + 8 * BwdImg<D>::ROWB);
+    const s16x4 lo = rsa_tr_read(p), hi = rsa_tr_read(p + 8 * BwdImg<D>::ROWB);
     return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
@@ -126,7 +122,7 @@ __device__ __forceinline__ BwdRows bwd_rows(const BwdArgs& a, int wave, int r) {
     w.r0 = w.qb * a.blk + (blockIdx.x - w.qb * gpb) * 64 + 32 * wave;
     w.row = w.r0 + r;
     w.ok = w.row < a.Sq;
-    w.kvlen = a.kv_len ? min(max(a.kv_len[w.b], 0), a.Sk) : a.kv_valid;
+    w.kvlen = rsa_key_limit(a.kv_len, w.b, a.kv_valid, a.Sk);
     // one past the last key the lane's row sees; glim: the same of the wave's last row (no row of the wave sees a key from there on)
     const int rl = min(w.r0 + 31, a.Sq - 1);
     w.lim = !w.ok ? 0 : (a.causal ? min(w.kvlen, max(0, w.row + w.kvlen - a.Sq + 1)) : w.kvlen);
@@ -294,7 +290,7 @@ __global__ __launch_bounds__(2 * BLK) void bwd_dkdv_kernel(const BwdArgs a) {
     int* const rlim = reinterpret_cast<int*>(negd + 32);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
     const int jb = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-    const int kvlen = a.kv_len ? min(max(a.kv_len[b], 0), a.Sk) : a.kv_valid;
+    const int kvlen = rsa_key_limit(a.kv_len, b, a.kv_valid, a.Sk);
     const int key = jb * BLK + 32 * wave + r;
     const bool kok = key < kvlen;
     s16x8 kf[KS], vf[KS];

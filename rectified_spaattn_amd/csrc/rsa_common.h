@@ -39,6 +39,11 @@ __device__ __forceinline__ float rsa_exp(float x) {
     return __builtin_ldexpf(p, (int)n);
 }
 
+// The key limit of batch item b: the device value clamped into [0, Sk], or the host value where there is none.
+__device__ __forceinline__ int rsa_key_limit(const int32_t* __restrict__ kv_len, int b, int kv_valid, int Sk) {
+    return kv_len ? min(max(kv_len[b], 0), Sk) : kv_valid;
+}
+
 __device__ __forceinline__ float wave_xor_add(float v, int mask) { return v + __shfl_xor(v, mask, 64); }
 
 // Contract C6 tree over the 256 per-thread partials: strides 1..32 inside the wave, 64 and 128 through LDS.

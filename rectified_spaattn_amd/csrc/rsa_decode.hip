@@ -183,10 +183,6 @@ struct DecRaw {
     int key0;
 };
 
-__device__ __forceinline__ s16x4 dec_tr_read(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-
 template <typename CTag, int D, int MT, typename Form>
 __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
     const typename Form::template Args<typename DecCache<CTag>::Args> a) {
@@ -262,7 +258,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
     const int unit = EXT ? ext_unit : blockIdx.x % a.U, b = EXT ? ext_b : blockIdx.x / a.U, split = blockIdx.y;
     const int gu = a.H / a.U, R = a.Sq * gu;
     const int hk = unit / (a.U / a.Hkv), hl = unit / (a.U / a.Hl);
-    const int kvlen = a.kv_len ? min(max(a.kv_len[b], 0), a.Sk) : a.kv_valid;
+    const int kvlen = rsa_key_limit(a.kv_len, b, a.kv_valid, a.Sk);
     // no row of the group sees a key at or beyond glim (causal: the limit of the group's last query row): chunks from there on
     // are skipped before their loads.  Decode's last row is the call's last: its glim is kvlen.
     const int glim = EXT && a.causal ? min(kvlen, max(0, q0 + qn + kvlen - nrow)) : kvlen;
@@ -436,7 +432,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
             const unsigned char* vp = vst + (4 * lh + (lr >> 2)) * VROW + 8 * (lr & 3);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
-                const s16x4 lo = dec_tr_read(vp + 32 * dt), hi = dec_tr_read(vp + 16 * VROW + 32 * dt);
+                const s16x4 lo = rsa_tr_read(vp + 32 * dt), hi = rsa_tr_read(vp + 16 * VROW + 32 * dt);
                 const s16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) o[dt][mt] = Mfma16<Tag>::mfma(vf, pf[mt], o[dt][mt]);

@@ -99,7 +99,7 @@ def test_exact_class_small_rows(dt, D, blk):
     assert blind > 0        # (the last shape, causal: whole row blocks without a visible block, count 0)
 
 
-MANY = [("bf16", 64, 64, 70), ("fp16", 16, 64, 300), ("bf16", 16, 128, 70)]
+MANY = [("bf16", 64, 64, 70), ("fp16", 16, 64, 300), ("bf16", 16, 128, 70), ("fp16", 32, 64, 70)]
 
 
 @pytest.mark.parametrize("dt,D,blk,NK", MANY, ids=[f"{a}-D{b}-b{c}-NK{d}" for a, b, c, d in MANY])

@@ -55,7 +55,7 @@ def _full(shape, value):
 
 
 # ---- 1. the cache, exact by value ----------------------------------------------------------------------------------------------------
-CACHE = [(dt, D, blk) for dt in DT for D in (16, 64, 128) for blk in (64, 128)]
+CACHE = [(dt, D, blk) for dt in DT for D in (16, 64, 128) for blk in (64, 128)] + [("fp16", 32, 64)]
 
 
 @pytest.mark.parametrize("dt,D,blk", CACHE, ids=[f"{a}-D{b}-b{c}" for a, b, c in CACHE])
@@ -85,14 +85,14 @@ def test_cache_is_numpy_min_and_max_by_value(dt, D, blk):
 
 # ---- 2. incremental updates ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("blk", [64, 128])
-@pytest.mark.parametrize("paged", [False, True], ids=["contiguous", "paged"])
+@pytest.mark.parametrize("paged", [False, True, "fp16"], ids=["contiguous", "paged", "paged-fp16"])
 def test_incremental_update_writes_its_blocks_and_nothing_else(paged, blk):
     """A cache full of NaN; a prefill, an append across a block edge, a rollback (start = kv_len).  Paged: a permuted table, spare
-    pages full of NaN, and one entry of a written block outside [0, P): zeros, min and max alike."""
+    pages full of NaN, and one entry of a written block outside [0, P): zeros, min and max alike; once more in fp16."""
     from rectified_spaattn_amd import pool_key_bounds
-    B, Hkv, D, NK, dt = 2, 2, 64, 5, "bf16"
+    B, Hkv, D, NK, dt = 2, 2, 64, 5, "fp16" if paged == "fp16" else "bf16"
     Sk = NK * blk
-    full = _randn((B, Hkv, Sk, D), dt, blk + int(paged))
+    full = _randn((B, Hkv, Sk, D), dt, blk + int(bool(paged)))
     steps = [([blk + blk // 2, 2 * blk + 5], [0, 0]),                           # prefill
              ([2 * blk + 3, 2 * blk + 9], [blk + blk // 2, 2 * blk + 5]),       # append: item 0 crosses a block edge
              ([blk + 7, 2 * blk + 2], [blk + 7, 2 * blk + 2])]                   # rollback: the ragged tail block alone
@@ -226,7 +226,7 @@ def test_exact_class_small_rows(D, blk):
     assert blind > 0 and ties > 0
 
 
-MANY = [("bf16", 64, 64, 70), ("fp16", 16, 64, 300)]
+MANY = [("bf16", 64, 64, 70), ("fp16", 16, 64, 300), ("bf16", 32, 64, 70)]
 
 
 @pytest.mark.parametrize("dt,D,blk,NK", MANY, ids=[f"{a}-D{b}-b{c}-NK{d}" for a, b, c, d in MANY])

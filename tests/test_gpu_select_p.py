@@ -195,7 +195,7 @@ def test_rounding_class_every_row(dt, D, blk):
 
 # ---- 3. byte for byte ------------------------------------------------------------------------------------------------------------
 POOLED = [("bf16", 128, 128, 70, 1, 2, "kv", True), ("fp16", 16, 64, 300, 3, 1, "q", False), ("bf16", 64, 64, 3, 160, 4, "kv", True),
-          ("fp16", 64, 128, 300, 1, 2, "q", True)]
+          ("fp16", 64, 128, 300, 1, 2, "q", True), ("bf16", 32, 64, 3, 1, 2, "kv", True)]
 
 
 @pytest.mark.parametrize("dt,D,blk,NK,Sq,Hkv,heads,causal", POOLED, ids=[f"{a}-D{b}-b{c}-NK{d}-Sq{e}" for a, b, c, d, e, *_ in POOLED])
