@@ -641,6 +641,29 @@ int rsa_block_select_bound_packed(int T, int B, int H, int Hkv, int Hl, int max_
                                   uint32_t* bitmask, int32_t* cols, int32_t* counts, float* scores, int p16, float c, float* mass,
                                   const int32_t* cu_seqlens_q_dev, int32_t* item_ws, void* stream);
 
+/* ---- block selection by ANTI-DIAGONAL scores, for the training-free sparse prefill of a dense model (XAttention's criterion; found
+ * by symbol: the header version stays 6.1).  rsa_block_select scores a block pair by mean(q) . mean(k); this
+ * one by the softmax mass of its strided logits.  With s = stride, row group u = rows [u s, u s + s), key group w = keys
+ * [w s, w s + s), q~ = q below Sq and 0 beyond, k~ = k below len_b and 0 beyond (keys at or beyond len_b are never loaded):
+ *     a[b, h, u, w] = sum over t < s of <q~[u s + s - 1 - t], k~[w s + t]>   (matrix pipe, fp32 accumulation),  x = a sm_scale / s
+ *     u is live iff u s < Sq; w is visible to u iff w s < len_b and, with causal, w s <= u s + s - 1 + len_b - Sq
+ *     lse[u] = ln sum over the visible w of exp(x[u, w])
+ *     P[b, hl, i, j] = sum over the list head's query heads, the live u of query block i and the visible w of key block j of
+ *                      exp(x[u, w] - lse[u]);   t = ln(max(P, 2^-126)), always finite
+ * and t takes the place of rsa_block_select's score: the visible prefix, the forced blocks, top-k with ties to the lower block,
+ * top-p (p16 = -1: plain top-k, c and mass are then not read; the logit is c / log2(e) * t, so a block's weight is proportional to
+ * its mass), the lists, the scores (-inf at invisible blocks) and the mass are rsa_block_select_ragged's, by the same device code.
+ * q [B, H, Sq, D], k [B, Hkv, Sk, D], bf16 / fp16, D 64 or 128, block 64 or 128, stride 8 or 16, NK <= 8192, sm_scale finite and
+ * > 0.  ws: rsa_block_select_antidiag_bytes(...) bytes, 16-byte aligned: the ordered keys [B, Hl, NQ, NK] and nothing that grows
+ * with the number of groups.  Two launches (the scores: two walks over the visible key tiles; the selection), no float atomics:
+ * two calls give the same bytes.  Refusals: rsa_block_select's, with their statuses, in their order; then D or stride ->
+ * RSA_ERR_UNSUPPORTED, sm_scale -> RSA_ERR_BAD_ARG, k and ws -> RSA_ERR_BAD_ARG, a short workspace -> RSA_ERR_WORKSPACE. */
+int rsa_block_select_antidiag_bytes(int B, int H, int Hkv, int Hl, int Sq, int D, int block, int stride, int NQ, int NK, size_t* bytes);
+int rsa_block_select_antidiag(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int stride, int NQ, int NK,
+                              rsa_tensor4 q, rsa_tensor4 k, const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale,
+                              int top_k, int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                              int32_t* counts, float* scores, int p16, float c, float* mass, void* stream);
+
 /* ---- the MERGE of attention partials: N results over disjoint key sets -- another rank's share of the cache, a shared prefix
  * beside each item's suffix, a dense branch beside the selected blocks -- become the result over their union (found by symbol:
  * the header version stays 6.1).  Partial i is what the decode and extend entries return: out_i, 2-byte

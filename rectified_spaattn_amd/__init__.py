@@ -157,6 +157,19 @@ def select_blocks_bound(q, key_bounds, top_k, *, block_size=128, kv_len=None, ca
                                             cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len)
 
 
+def select_blocks_antidiag(q, k, top_k, *, stride=8, sm_scale=None, block_size=128, kv_len=None, causal=False, keep_first=0,
+                           keep_local=0, mask_heads="kv", as_lists=False, return_scores=False, top_p=None, score_scale=None,
+                           return_mass=False, **not_served):
+    """select_blocks scored by the softmax mass of a block pair's anti-diagonal strided logits (XAttention's criterion: the mask
+    for the training-free sparse prefill of a dense model), an MFMA score pass in front of select_blocks' selection.
+    See rectified_spaattn_amd.block_sparse.select_blocks_antidiag."""
+    from . import block_sparse
+    return block_sparse.select_blocks_antidiag(q, k, top_k, stride=stride, sm_scale=sm_scale, block_size=block_size, kv_len=kv_len,
+                                               causal=causal, keep_first=keep_first, keep_local=keep_local, mask_heads=mask_heads,
+                                               as_lists=as_lists, return_scores=return_scores, top_p=top_p,
+                                               score_scale=score_scale, return_mass=return_mass, **not_served)
+
+
 def merge_partials(outs, lses, *, sink=None, out=None, lse=None, return_lse=True):
     """The merge of N <= 8 attention partials (out_i, lse_i) over disjoint key sets -- what block_sparse_decode / block_sparse_extend
     return with return_lse=True -- into the result over their union, with optional attention-sink logits: one launch, no copy, the

@@ -174,6 +174,10 @@ PROTOTYPES = {
                                      sz, vp, vp, vp, vp, i32, f32, vp, vp, vp]),
     "rsa_block_select_bound_packed": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, vp, vp, i32, i32, i32, i32,
                                             i32, i32, vp, sz, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp]),
+    # the selection by anti-diagonal scores: additive and found by symbol, behind the bound entries
+    "rsa_block_select_antidiag_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz)]),
+    "rsa_block_select_antidiag": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, T4, T4, vp, i32, i32, f64, i32,
+                                        i32, i32, vp, sz, vp, vp, vp, vp, i32, f32, vp, vp]),
     # the packed entries: additive and found by symbol, in front of the ragged ones for the same reason
     "rsa_block_sparse_extend_packed_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz), P(i64)]),
     "rsa_block_sparse_extend_packed": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp,

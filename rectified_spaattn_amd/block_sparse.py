@@ -21,6 +21,8 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              (rsa_pool_key_bounds)
     select_blocks_bound      select_blocks_pooled from that cache: a block scores by the upper bound of q . k over its keys
                              (rsa_block_select_bound), everything behind the score unchanged
+    select_blocks_antidiag   select_blocks with the score of training-free sparse prefill: the softmax mass of a block pair's
+                             anti-diagonal strided logits, an MFMA pass over K (rsa_block_select_antidiag)
     append_kv_e4m3           the writer of a one-byte K/V cache: new rows become e4m3 codes under one static fp32 scale per K/V
                              head (rsa_kv8_append); block_sparse_decode and pool_keys read such a cache in place
                              (k_scale= / v_scale=: rsa_block_sparse_decode_kv8, rsa_pool_keys_kv8)
@@ -787,14 +789,17 @@ def _check_top_p(top_p, score_scale, return_mass):
 
 def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
             return_scores, as_lists, score_splits=None, top_p=None, score_scale=None, return_mass=False, q_len=None,
-            cu_seqlens_q=None, max_q_len=None, bound: bool = False):
+            cu_seqlens_q=None, max_q_len=None, bound: bool = False, antidiag=None):
     """select_blocks (keys = k, rsa_block_select) and select_blocks_pooled (keys = pool_keys' cache, rsa_block_select_pooled,
     with its score_splits): the two differ in where kbar comes from and in nothing else.  With top_p the entries are their _p
     forms, which take (p16, c, mass) in front of the stream.  With q_len the entries are their _ragged forms: the _p argument
     lists (p16 = -1: top-k) and the device row counts in front of the stream.  With cu_seqlens_q (pooled only) the entry is
     rsa_block_select_pooled_packed: q [T, H, D], the ragged argument list with T in front and M for Sq.  bound (beside pooled):
     select_blocks_bound -- keys = pool_key_bounds' cache; rsa_block_select_bound has the ragged argument list alone (p16 = -1:
-    top-k; no row counts: NULL) and rsa_block_select_bound_packed the packed one."""
+    top-k; no row counts: NULL) and rsa_block_select_bound_packed the packed one.  antidiag = (stride, sm_scale):
+    select_blocks_antidiag -- keys = k, head dims 64 / 128; rsa_block_select_antidiag has the _p argument list alone (p16 = -1:
+    top-k) with H in front of its size query's Hkv, Sq and the block behind, stride behind block and sm_scale behind causal; the
+    top-p logit is score_scale * t with score_scale defaulting to 1."""
     blk = _check_block(what, block_size)
     if mask_heads not in ("kv", "q"):
         raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
@@ -802,7 +807,8 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         _check_count(name, val, 0)
     _check_count("score_splits", score_splits, 1, MAX_SCORE_SPLITS, optional=True)
     _check_top_p(top_p, score_scale, return_mass)
-    r = _query_rows(q, q_len, cu_seqlens_q, max_q_len, keys, None, lambda q4: _check_operands(q4, keys, pooled=pooled, bounds=bound))
+    r = _query_rows(q, q_len, cu_seqlens_q, max_q_len, keys, None, lambda q4: _check_operands(q4, keys, pooled=pooled, bounds=bound,
+                                                                                   dims=ANTIDIAG_HEAD_DIMS if antidiag else HEAD_DIMS))
     packed, q, B, H, Hkv, Sq, Sk, D = r.kind == "packed", r.q4, r.B, r.H, r.Hkv, r.Sq, r.Sk, r.D
     if pooled:      # the cache holds NK blocks: the capacity is taken as NK * block
         Sk *= blk
@@ -821,10 +827,12 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         q, cu = _packed_on_device(r)
     else:
         q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
-    base = "rsa_block_select_bound" if bound else "rsa_block_select_pooled" if pooled else "rsa_block_select"
-    entry = base + ("" if top_p is None or bound else "_p")
+    base = ("rsa_block_select_antidiag" if antidiag else "rsa_block_select_bound" if bound else
+            "rsa_block_select_pooled" if pooled else "rsa_block_select")
+    entry = base + ("" if top_p is None or bound or antidiag else "_p")
     need = ctypes.c_size_t(0)
-    _lib.check(getattr(L, entry + "_bytes")(B, Hkv, Hl, D, NQ, NK, ctypes.byref(need)), entry + "_bytes")
+    sizes = (B, H, Hkv, Hl, Sq, D, blk, antidiag[0], NQ, NK) if antidiag else (B, Hkv, Hl, D, NQ, NK)
+    _lib.check(getattr(L, entry + "_bytes")(*sizes, ctypes.byref(need)), entry + "_bytes")
     if q_dev is not None and not bound:
         entry = base + "_ragged"
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
@@ -838,18 +846,22 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
     mass, budget = None, ()
     if top_p is not None:
         mass = torch.empty((B, Hl, NQ), dtype=torch.float32, device=dev) if return_mass else None
-        scale = 1.0 / ((H // Hl) * math.sqrt(D)) if score_scale is None else float(score_scale)
+        default = 1.0 if antidiag else 1.0 / ((H // Hl) * math.sqrt(D))
+        scale = default if score_scale is None else float(score_scale)
         budget = (int(round(float(top_p) * 65536.0)), scale * LOG2_E, _ptr(mass))
     if q_dev is not None or (bound and not packed):
         budget = (budget or (-1, 0.0, None)) + (_ptr(q_dev),)
+    stride, sm_scale = ((antidiag[0],), (antidiag[1],)) if antidiag else ((), ())
+    if antidiag:
+        budget = budget or (-1, 0.0, None)
     tq = _t3(q) if packed else _core._t4(q)
     if packed:              # T in front, M where Sq stood, cu_seqlens_q and the scan's scratch where q_len stood
         entry, shape = base + "_packed", (r.T,) + shape
         items = torch.empty((2 * (B + 1),), dtype=torch.int32, device=dev)
         budget = (budget or (-1, 0.0, None)) + (cu.data_ptr(), items.data_ptr())
     with torch.cuda.device(dev):
-        _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, NQ, NK, tq, source, _ptr(kv_dev), kv_valid,
-                                     int(bool(causal)), min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), *splits,
+        _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, *stride, NQ, NK, tq, source, _ptr(kv_dev), kv_valid,
+                                     int(bool(causal)), *sm_scale, min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), *splits,
                                      ws.data_ptr(), need.value, out["bitmask"].data_ptr(), out["cols"].data_ptr(),
                                      out["counts"].data_ptr(), _ptr(scores), *budget, _core._stream()), entry)
     sel = out if as_lists else lists_to_block_mask(out["bitmask"], B, Hl, NQ, NK).view(torch.bool)
@@ -1074,6 +1086,50 @@ def select_blocks_bound(q: torch.Tensor, key_bounds: torch.Tensor, top_k: int, *
     score: select_blocks_pooled's result up to fp32 rounding, and its bytes where the sums are exact."""
     return _select("select_blocks_bound", q, key_bounds, True, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
                    return_scores, as_lists, score_splits, top_p, score_scale, return_mass, q_len, cu_seqlens_q, max_q_len, bound=True)
+
+
+ANTIDIAG_HEAD_DIMS = (64, 128)
+ANTIDIAG_STRIDES = (8, 16)
+
+
+def select_blocks_antidiag(q: torch.Tensor, k: torch.Tensor, top_k: int, *, stride: int = 8, sm_scale: Optional[float] = None,
+                           block_size: int = 128, kv_len=None, causal: bool = False, keep_first: int = 0, keep_local: int = 0,
+                           mask_heads: str = "kv", as_lists: bool = False, return_scores: bool = False,
+                           top_p: Optional[float] = None, score_scale: Optional[float] = None, return_mass: bool = False,
+                           q_len=None, cu_seqlens_q=None, max_q_len=None, block_table=None):
+    """select_blocks with one thing changed, the score (XAttention's anti-diagonal criterion): the block mask
+    for the training-free sparse prefill of a dense model.  A block pair scores by the softmax mass of its strided logits, so one
+    key aligned with a query among 127 that are not still counts, at 2 / stride of the cost of a dense Q K^T:
+      logit     a[u, w] = sum over t < s of <q[u s + s - 1 - t], k[w s + t]> (s = stride; rows >= Sq and keys >= kv_len[b] count as
+                zeros and keys >= kv_len[b] are never read), on the matrix pipe with fp32 accumulation; x = a * sm_scale / s,
+                sm_scale defaulting to D ** -0.5
+      visible   row group u (rows u s ..) is live iff u s < Sq; key group w is visible to it iff w s < kv_len[b] and, with causal,
+                w s <= u s + s - 1 + kv_len[b] - Sq
+      mass      P[b, hl, i, j] = sum over the list head's query heads, the live u of query block i and the visible w of key block
+                j of softmax_w(x[u, :])[w];  t = ln(max(P, 2^-126)), finite at every visible block
+    and t takes the place of select_blocks' score: visible / forced / kept, top_k, keep_first, keep_local, mask_heads, as_lists,
+    return_scores (-inf at invisible blocks) and the returns are select_blocks', by the same device code.  top_p: the logit is
+    score_scale * t with score_scale defaulting to 1, so a block weighs in proportion to its mass and top_p is the share of the
+    estimated attention mass a row block keeps; return_mass as in select_blocks.
+    q [B,H,Sq,D], k [B,Hkv,Sk,D], bf16 / fp16, H % Hkv == 0, D 64 or 128, block_size 64 or 128, stride 8 or 16, NK <= 8192, any
+    strides select_blocks takes; kv_len in select_blocks' forms (a device tensor is never read on the host).  Two calls give the
+    same bytes.  Not served (NotImplementedError / ValueError, never a fallback): head dims 16 / 32, other strides, ragged or
+    packed queries (q_len, cu_seqlens_q, max_q_len), a paged K (block_table), a float8_e4m3fn K."""
+    for name, val in (("q_len", q_len), ("cu_seqlens_q", cu_seqlens_q), ("max_q_len", max_q_len), ("block_table", block_table)):
+        if val is not None:
+            raise NotImplementedError(f"select_blocks_antidiag: {name} is not served (padded queries over a contiguous K)")
+    if isinstance(k, torch.Tensor) and k.dtype == E4M3:
+        raise NotImplementedError("select_blocks_antidiag: a float8_e4m3fn K is not served")
+    _check_count("stride", stride, 1)
+    if stride not in ANTIDIAG_STRIDES:
+        raise NotImplementedError(f"select_blocks_antidiag: stride in {ANTIDIAG_STRIDES}, got {stride}")
+    if sm_scale is not None and (isinstance(sm_scale, bool) or not isinstance(sm_scale, (int, float))
+                                 or not 0.0 < float(sm_scale) < float("inf")):
+        raise ValueError(f"sm_scale: None or a finite number > 0, got {sm_scale!r}")
+    D = q.shape[-1] if isinstance(q, torch.Tensor) and q.dim() == 4 else 1       # (anything else: _check_operands refuses it)
+    scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
+    return _select("select_blocks_antidiag", q, k, False, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
+                   return_scores, as_lists, None, top_p, score_scale, return_mass, antidiag=(int(stride), scale))
 
 
 DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_decode.hip)

@@ -33,22 +33,16 @@
 // a fixed order; histograms and weights are unsigned integer sums (at most 8192 weights of at most 2^18): two calls, the same bytes.
 #include "rsa_common.h"
 #include "rsa_rows.h"
+#include "rsa_select_shared.h"      // SEL_NT, SEL_MAX_NK, sel_key, sel_visible: shared with rsa_select_antidiag.hip
 
 #include <math.h>
 #include <type_traits>
 
-#define SEL_NT 256
-#define SEL_MAX_NK 8192
 #define SEL_MAX_STEPS (SEL_MAX_NK / 64)
 #define SEL_MAX_SPLITS 256      // score workgroups per list row of the pooled selection, at most
 #define SELP_ONE 262144u        // 2^18: the weight of the row's best block
 
-// fp32 -> u32 with the order of the floats (-0 counts as +0); and back.
-__device__ __forceinline__ unsigned sel_key(float x) {
-    unsigned u = __float_as_uint(x);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// u32 -> fp32: sel_key (rsa_select_shared.h) back.
 __device__ __forceinline__ float sel_unkey(unsigned key) {
     return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
 }
@@ -73,17 +67,7 @@ __device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
 // The kernels that ask for a batch item's query rows are instantiated over the row source (rsa_rows.h; DESIGN.md sections 5.17, 5.18),
 // their last argument: RowsPadded for the entries without row counts (no size: those kernels keep their arguments and their code),
 // RowsCounted for the ragged entries and, over the scan's sanitised counts, for the packed ones, whose pool kernel alone also
-// needs each item's first row of q [T, H, D]: RowsAt.
-// Visible blocks of list row (b, i): a prefix [0, nvis) of the row.  Sq: the batch item's row count (Rows::count); SHORT (Rows::SHORT):
-// a query block without a row sees nothing.
-template <bool SHORT = false>
-__device__ __forceinline__ int sel_visible(int len, int Sq, int blk, int NK, int i, int causal) {
-    const long r0 = (long)i * blk, r1 = min(r0 + blk, (long)Sq) - 1, off = (long)len - Sq;
-    if (SHORT && r0 >= Sq) return 0;
-    int nvis = min(NK, (len + blk - 1) / blk);
-    if (causal) nvis = r1 + off < 0 ? 0 : (int)min((long)nvis, (r1 + off) / blk + 1);
-    return nvis;
-}
+// needs each item's first row of q [T, H, D]: RowsAt.  (The visible prefix of a list row, sel_visible: rsa_select_shared.h.)
 
 // ---- pooling ---------------------------------------------------------------------------------------------------------------------
 // The element loader: what a lane reads for its 8 channels of a row, as 8 floats.  bf16 / fp16: 16 bytes.  e4m3_tag (the one-byte
@@ -771,6 +755,26 @@ static int sel_check(bool pooled, int B, int H, int D, int dtype, rsa_tensor4 q,
 
 static bool selp_budget_ok(const sel_top_p& p) {
     return p.p16 >= 0 && p.p16 <= 65536 && isfinite(p.c) && p.c > 0.f && !(reinterpret_cast<uintptr_t>(p.mass) & 3);
+}
+
+// The door for a score pass in a unit of its own (rsa_select_shared.h; the anti-diagonal scores): its call as
+// sel_rows, checked as rsa_block_select's, and its keys ranked by the LOADED select kernels.
+static sel_rows sel_ext_rows(const sel_ext_call& e, const unsigned* wkeys) {
+    return {nullptr, nullptr, wkeys, e.Hkv, e.Hl, e.Sq, e.Sk, e.blk, e.NQ, e.NK, e.kv_len, e.kv_valid, e.causal, e.top_k, e.keep_first,
+            e.keep_local, e.bitmask, e.cols, e.counts, e.scores};
+}
+
+int sel_ext_check(const sel_ext_call& e) {
+    const sel_top_p p = {e.p16, e.c, e.mass};
+    if ((e.p16 != -1 && !selp_budget_ok(p)) || e.Sk <= 0) return RSA_ERR_BAD_ARG;
+    size_t need = 0;    // (the plain selection's workspace: the caller has its own)
+    return sel_check(false, e.B, e.H, e.D, e.dtype, e.q, sel_ext_rows(e, nullptr), nullptr, e.Sk, &need);
+}
+
+int sel_ext_select(const sel_ext_call& e, const unsigned* wkeys, void* stream) {
+    const sel_top_p p = {e.p16, e.c, e.mass};
+    return sel_launch_select(e.D, (long)e.B * e.Hl * e.NQ, sel_ext_rows(e, wkeys), e.p16 == -1 ? nullptr : &p, nullptr,
+                             static_cast<hipStream_t>(stream));
 }
 
 // The body of rsa_block_select and rsa_block_select_p (top_p NULL: top-k).  r: the call's arguments; kbar, qsum are set here.
