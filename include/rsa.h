@@ -730,6 +730,49 @@ int rsa_block_sparse_bwd(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, i
                          const int32_t* col_cols, const int32_t* col_counts, void* ws, size_t ws_bytes, rsa_out4 dq, rsa_out4 dk,
                          rsa_out4 dv, void* stream);
 
+/* ---- the decode step over an MXFP4 K/V cache: OCP e2m1 codes with one e8m0 scale per 32 channels of a row (found by symbol: the
+ * header version stays 6.1).  Codes: one byte per two elements, element 2 i in the low nibble of byte i,
+ * [B, Hkv, Sk, D / 2] or with a block_table page pools [num_pages, Hkv, block, D / 2].  Scales: one byte per 32 channels,
+ * [B, Hkv, Sk, D / 32] or page pools [num_pages, Hkv, block, D / 32] behind the same table; byte s means 2^(s - 127).  All strides
+ * count bytes.  The value of element d of a row is e2m1(code_d) * 2^(scale[d / 32] - 127); e2m1 magnitudes are {0, 0.5, 1, 1.5, 2,
+ * 3, 4, 6}.  The writer keeps every scale byte in [114, 140] (exponents -13 .. 13), where every value is exactly a bf16 and an
+ * fp16; there is no fp32 per-head scale beside the block scales.  Head dims 64 and 128 only.
+ *
+ * rsa_kv4_append writes new rows: rsa_kv8_append's arguments, placement rule and guarantees, with the four cache views where its
+ * two caches and two scales stood.  Per row and 32-channel group: a = the largest |x_d|, a NaN element left out; e =
+ * clamp(exponent_field(a as fp32) - 127 - 2, -13, 13) (a zero or subnormal a gives -13); the scale byte is e + 127; code_d is
+ * x_d * 2^-e rounded to nearest even onto the e2m1 grid, saturating at +-6 (+-Inf included), with the sign of x_d kept (-0 and a
+ * negative that rounds to zero are 0x8).  A NaN element becomes code 0x0: e2m1 has no NaN.  The call writes the D / 2 + D / 32
+ * bytes of every placed row, for each of K and V, and no other byte; a position at or beyond Sk, or one whose table entry lies
+ * outside [0, num_pages), is dropped and no address is formed from it.  Code views: pointer and strides multiples of 16 bytes
+ * (16-byte stores); scale views: any.  One launch; the grid is sized from T alone.
+ *
+ * rsa_block_sparse_decode_kv4 is rsa_block_sparse_decode over such a cache: its argument list with the two scale views in front
+ * of the stream; dtype names q's (and out's) type; the workspace is rsa_block_sparse_decode_bytes'.  Codes become q's type in
+ * registers with the scale as the conversion's own operand (exact for a scale byte in [114, 140]); the MFMAs, the softmax, the
+ * splits and the merge are those of the 2-byte call and no scale acts behind them: the bytes of out and lse are those of
+ * rsa_block_sparse_decode on the dequantised 2-byte cache.  Every rule of that call holds word for word; keys at or beyond len_b
+ * and unvisited pages may hold any byte in codes and scales.  A scale byte outside [114, 140] at a visible key garbles that row's
+ * contribution and nothing else: no address depends on a scale.  k: pointer and strides multiples of 4 bytes; v: of 16 bytes;
+ * k_block_scale: of D / 32 bytes; v_block_scale: any; other views are RSA_ERR_BAD_ARG.
+ *
+ * rsa_pool_keys_kv4 is rsa_pool_keys from MXFP4 codes (no dtype argument; k: pointer and strides multiples of 4 bytes) and their
+ * scale view: out[b, hk, j, :] = the fp32 sum of the dequantised values of the block's keys below len_b, in rsa_pool_keys' order,
+ * divided once by their count: the bytes of rsa_pool_keys on the dequantised 2-byte K.  Every other clause of rsa_pool_keys holds.
+ * Refusals as the e4m3 entries'; D outside {64, 128}: RSA_ERR_UNSUPPORTED.  Every check runs before the first HIP call. */
+int rsa_kv4_append(int B, int Hkv, int T, int Sk, int D, int dtype, int block, rsa_tensor4 k_new, rsa_tensor4 v_new,
+                   rsa_out4 k_codes, rsa_out4 k_scales, rsa_out4 v_codes, rsa_out4 v_scales, const int32_t* block_table,
+                   int64_t table_stride_b, int num_pages, const int32_t* start_dev, int start, const int32_t* n_new_dev, int n_new,
+                   void* stream);
+int rsa_block_sparse_decode_kv4(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q, rsa_tensor4 k,
+                                rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                                const int32_t* cols, const int32_t* counts, int blocks_per_split, void* ws, size_t ws_bytes,
+                                rsa_out4 out, float* lse, rsa_tensor4 k_block_scale, rsa_tensor4 v_block_scale, void* stream);
+int rsa_pool_keys_kv4(int B, int Hkv, int Sk, int D, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                      int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid, const int32_t* start_dev,
+                      int start, int workgroups_per_head, float* out, rsa_tensor4 k_block_scale, void* stream);
+
 /* ---- rectified attention over a caller-supplied block mask (the reference's combine, hunyuan :346-357, flux :334-343,
  * cogvideo :338-347, wan21 :328-338, on a selection the caller made, reused or edited).  Additive: no struct above changes. ----
  *

@@ -69,21 +69,24 @@ def select_blocks(q, k, top_k, *, block_size=128, kv_len=None, causal=False, kee
 
 
 def block_sparse_decode(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
-                        return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None):
+                        return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None, k_block_scale=None,
+                        v_block_scale=None):
     """Block-sparse decode attention: q [B,H,Sq,D] with Sq <= block over a K/V cache [B,Hkv,Sk,D], or over page pools
     [P,Hkv,block,D] behind block_table int32 [B,NKt]; block_mask bool / uint8 [B|1, Hl, 1, NK] or select_blocks' lists;
     return_lse=True adds the fp32 log-sum-exp [B,H,Sq].  k / v float8_e4m3fn with k_scale / v_scale (one fp32 scale per K/V
-    head): the one-byte cache append_kv_e4m3 writes.  No q_len: a ragged decode batch is block_sparse_extend(q_len=), with this
+    head): the one-byte cache append_kv_e4m3 writes; k / v uint8 e2m1 codes [.., D/2] with k_block_scale / v_block_scale (e8m0 bytes
+    [.., D/32]): the MXFP4 cache append_kv_mxfp4 writes, with the bytes of this call on the dequantised cache.  No q_len: a ragged decode batch is block_sparse_extend(q_len=), with this
     call's bytes.  See rectified_spaattn_amd.block_sparse.block_sparse_decode."""
     from . import block_sparse
     return block_sparse.block_sparse_decode(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                             causal=causal, block_table=block_table, return_lse=return_lse,
-                                            blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale)
+                                            blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale,
+                                            k_block_scale=k_block_scale, v_block_scale=v_block_scale)
 
 
 def block_sparse_extend(q, k, v, block_mask, *, kv_len=None, sm_scale=None, block_size=128, causal=False, block_table=None,
                         return_lse=False, blocks_per_split=None, k_scale=None, v_scale=None, q_len=None,
-                        cu_seqlens_q=None, max_q_len=None):
+                        cu_seqlens_q=None, max_q_len=None, k_block_scale=None, v_block_scale=None):
     """Block-sparse extend attention: a chunk q [B,H,Sq,D] of any length over a K/V cache that already holds a prefix --
     block_sparse_decode without the one-query-block and 64-row limits; block_mask bool / uint8 [B|1, Hl, ceil(Sq/block), NK] or
     select_blocks' lists for that many query blocks; causal is bottom-right aligned; return_lse=True adds the fp32 log-sum-exp
@@ -96,16 +99,30 @@ def block_sparse_extend(q, k, v, block_mask, *, kv_len=None, sm_scale=None, bloc
     return block_sparse.block_sparse_extend(q, k, v, block_mask, kv_len=kv_len, sm_scale=sm_scale, block_size=block_size,
                                             causal=causal, block_table=block_table, return_lse=return_lse,
                                             blocks_per_split=blocks_per_split, k_scale=k_scale, v_scale=v_scale, q_len=q_len,
-                                            cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len)
+                                            cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len, k_block_scale=k_block_scale,
+                                            v_block_scale=v_block_scale)
 
 
-def pool_keys(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None, k_scale=None):
+def pool_keys(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None, k_scale=None,
+              k_block_scale=None):
     """The cache of pooled keys for select_blocks_pooled: k [B,Hkv,Sk,D] (or a page pool behind block_table) -> fp32
     [B, Hkv, ceil(Sk/block), D]; with start= and out= only the blocks from start // block up to kv_len are written again; k
-    float8_e4m3fn with k_scale: from the one-byte cache.  See rectified_spaattn_amd.block_sparse.pool_keys."""
+    float8_e4m3fn with k_scale: from the one-byte cache; k uint8 e2m1 codes with k_block_scale: from the MXFP4 cache.
+    See rectified_spaattn_amd.block_sparse.pool_keys."""
     from . import block_sparse
     return block_sparse.pool_keys(k, block_size=block_size, kv_len=kv_len, block_table=block_table, out=out, start=start,
-                                  workgroups_per_head=workgroups_per_head, k_scale=k_scale)
+                                  workgroups_per_head=workgroups_per_head, k_scale=k_scale, k_block_scale=k_block_scale)
+
+
+def append_kv_mxfp4(k_new, v_new, k_codes, k_scales, v_codes, v_scales, *, start, n_new=None, cu_seqlens=None, block_size=128,
+                    block_table=None):
+    """The writer of the MXFP4 K/V cache: k_new / v_new [B,Hkv,T,D] (bf16 / fp16) become e2m1 codes, two to a byte, with one e8m0
+    scale byte per 32 channels of a row, at positions start[b] + t of the uint8 caches k_codes / v_codes [B,Hkv,Sk,D/2] and
+    k_scales / v_scales [B,Hkv,Sk,D/32], or of page pools behind block_table.
+    See rectified_spaattn_amd.block_sparse.append_kv_mxfp4."""
+    from . import block_sparse
+    return block_sparse.append_kv_mxfp4(k_new, v_new, k_codes, k_scales, v_codes, v_scales, start=start, n_new=n_new,
+                                        cu_seqlens=cu_seqlens, block_size=block_size, block_table=block_table)
 
 
 def append_kv_e4m3(k_new, v_new, k_cache, v_cache, *, start, k_scale, v_scale, n_new=None, block_size=128, block_table=None,
@@ -134,13 +151,13 @@ def select_blocks_pooled(q, pooled_k, top_k, *, block_size=128, kv_len=None, cau
 
 
 def pool_key_bounds(k, *, block_size=128, kv_len=None, block_table=None, out=None, start=None, workgroups_per_head=None,
-                    k_scale=None):
+                    k_scale=None, k_block_scale=None):
     """The cache of per-channel key bounds for select_blocks_bound: pool_keys' arguments -> fp32 [B, Hkv, ceil(Sk/block), 2, D],
     [..., 0, :] the minimum and [..., 1, :] the maximum of each block's keys below kv_len; updated block by block with start= and
     out= as pool_keys is.  See rectified_spaattn_amd.block_sparse.pool_key_bounds."""
     from . import block_sparse
     return block_sparse.pool_key_bounds(k, block_size=block_size, kv_len=kv_len, block_table=block_table, out=out, start=start,
-                                        workgroups_per_head=workgroups_per_head, k_scale=k_scale)
+                                        workgroups_per_head=workgroups_per_head, k_scale=k_scale, k_block_scale=k_block_scale)
 
 
 def select_blocks_bound(q, key_bounds, top_k, *, block_size=128, kv_len=None, causal=False, keep_first=0, keep_local=0,

@@ -202,6 +202,11 @@ PROTOTYPES = {
     "rsa_block_sparse_bwd_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz)]),
     "rsa_block_sparse_bwd": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, f64, T4, T4, T4, T4, T4, vp,
                                    vp, vp, vp, vp, sz, O4, O4, O4, vp]),
+    # the MXFP4 cache: additive and found by symbol, in front of the extend entries like the others
+    "rsa_kv4_append": (i32, [i32, i32, i32, i32, i32, i32, i32, T4, T4, O4, O4, O4, O4, vp, i64, i32, vp, i32, vp, i32, vp]),
+    "rsa_block_sparse_decode_kv4": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp,
+                                          i64, i32, vp, vp, i32, vp, sz, O4, vp, T4, T4, vp]),
+    "rsa_pool_keys_kv4": (i32, [i32, i32, i32, i32, i32, i32, T4, vp, i64, i32, vp, i32, vp, i32, i32, vp, T4, vp]),
     "rsa_block_sparse_extend_bytes": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, P(sz)]),
     "rsa_block_sparse_extend": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, f64, T4, T4, T4, vp, i64,
                                       i32, vp, vp, i32, vp, sz, O4, vp, vp]),

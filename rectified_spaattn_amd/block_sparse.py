@@ -23,6 +23,10 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              (rsa_block_select_bound), everything behind the score unchanged
     select_blocks_antidiag   select_blocks with the score of training-free sparse prefill: the softmax mass of a block pair's
                              anti-diagonal strided logits, an MFMA pass over K (rsa_block_select_antidiag)
+    append_kv_mxfp4          the writer of an MXFP4 K/V cache: e2m1 codes, two to a byte, with one e8m0 scale byte per 32 channels
+                             of a row (rsa_kv4_append); block_sparse_decode and pool_keys read such a cache in place
+                             (k_block_scale= / v_block_scale=: rsa_block_sparse_decode_kv4, rsa_pool_keys_kv4; DESIGN.md section
+                             5.23) and return the bytes of the same calls on the dequantised 2-byte cache
     append_kv_e4m3           the writer of a one-byte K/V cache: new rows become e4m3 codes under one static fp32 scale per K/V
                              head (rsa_kv8_append); block_sparse_decode and pool_keys read such a cache in place
                              (k_scale= / v_scale=: rsa_block_sparse_decode_kv8, rsa_pool_keys_kv8)
@@ -312,6 +316,70 @@ def _t3(t: torch.Tensor) -> RsaTensor4:
     return RsaTensor4(t.data_ptr(), 0, t.stride(1), t.stride(0))
 
 
+# The MXFP4 cache: e2m1 codes, two to a byte, and one e8m0 scale byte per 32 channels of a row.
+FP4X2 = getattr(torch, "float4_e2m1fn_x2", None)
+E8M0 = getattr(torch, "float8_e8m0fnu", None)
+KV4_CODE_DTYPES = tuple(d for d in (torch.uint8, FP4X2) if d is not None)
+KV4_SCALE_DTYPES = tuple(d for d in (torch.uint8, E8M0) if d is not None)
+KV4_HEAD_DIMS = (64, 128)
+KV4_GROUP = 32              # channels per scale byte
+KV4_E_MIN, KV4_E_MAX = -13, 13      # the writer's shared exponents: scale bytes 114 .. 140
+
+
+def _refuse_mxfp4(what: str, k, **scales):
+    """The calls an MXFP4 cache is out of scope for: refused in their own words, never served through a copy."""
+    if any(sc is not None for sc in scales.values()) or (FP4X2 is not None and getattr(k, "dtype", None) == FP4X2):
+        raise NotImplementedError(f"{what} does not serve an MXFP4 cache (block_sparse_decode, pool_keys and append_kv_mxfp4 do)")
+
+
+def _kv4_cache(what: str, pairs, per_head_scales=()):
+    """The views of an MXFP4 cache a call takes.  pairs: (name, codes, scale name, scales, code alignment, scale alignment of a
+    head dim) per operand -> (D, [codes as uint8, ...], [scales as uint8, ...]).  Codes uint8 / float4_e2m1fn_x2 [.., D / 2],
+    scales uint8 / float8_e8m0fnu of the same leading shape [.., D / 32]; both with a contiguous last dim, the codes' pointer and
+    strides multiples of the load's width (a cache is never copied)."""
+    if any(sc is not None for sc in per_head_scales):
+        raise NotImplementedError(f"{what}: an fp32 per-head scale beside the block scales of an MXFP4 cache is not served")
+    missing = [sn for _, _, sn, sc, _, _ in pairs if sc is None]
+    if missing:
+        raise ValueError(f"{', '.join(missing)}: required beside {', '.join(sn for _, _, sn, sc, _, _ in pairs if sc is not None)} "
+                         "(an MXFP4 cache has scale bytes for K and for V)")
+    D, codes_out, scales_out = None, [], []
+    for name, codes, sname, sc, calign, salign in pairs:
+        if not isinstance(codes, torch.Tensor) or codes.dtype not in KV4_CODE_DTYPES or codes.dim() != 4:
+            raise ValueError(f"{sname}: block scales belong to an MXFP4 cache -- {name} a 4-d uint8 / float4_e2m1fn_x2 tensor of e2m1 "
+                             f"codes [.., D / 2], got {getattr(codes, 'dtype', type(codes))} {tuple(getattr(codes, 'shape', ()))}")
+        d = 2 * codes.shape[-1]
+        if d not in KV4_HEAD_DIMS:
+            if d in HEAD_DIMS:
+                raise NotImplementedError(f"head dim {d}: an MXFP4 cache serves {KV4_HEAD_DIMS}")
+            raise ValueError(f"{name}: {codes.shape[-1]} code bytes a row are head dim {d}: one of {KV4_HEAD_DIMS}")
+        if D is not None and d != D:
+            raise ValueError(f"{name}: head dim {d}, the other operand has {D}")
+        D = d
+        want = tuple(codes.shape[:-1]) + (D // KV4_GROUP,)
+        if not isinstance(sc, torch.Tensor) or sc.dtype not in KV4_SCALE_DTYPES or tuple(sc.shape) != want:
+            raise ValueError(f"{sname}: a uint8 / float8_e8m0fnu tensor {list(want)} (one scale byte per {KV4_GROUP} channels of a row "
+                             f"of {name}), got {getattr(sc, 'dtype', type(sc))} {tuple(getattr(sc, 'shape', ()))}")
+        if sc.device != codes.device:
+            raise ValueError(f"{sname} is on {sc.device}, {name} on {codes.device}")
+        codes = codes if codes.dtype == torch.uint8 else codes.view(torch.uint8)
+        sc = sc if sc.dtype == torch.uint8 else sc.view(torch.uint8)
+        for n, t, align in ((name, codes, calign), (sname, sc, salign * D // KV4_GROUP if salign else 1)):
+            *outer, inner = t.stride()
+            if inner != 1 or any(st % align for st in outer) or t.data_ptr() % align:
+                raise ValueError(f"{n}: a contiguous last dim, strides that are multiples of {align} bytes and a {align}-byte aligned "
+                                 f"pointer (a cache is not copied), got strides {tuple(t.stride())}, pointer % {align} = "
+                                 f"{t.data_ptr() % align}")
+        codes_out.append(codes)
+        scales_out.append(sc)
+    return D, codes_out, scales_out
+
+
+def _kv4_standin(codes: torch.Tensor, D: int, dtype) -> torch.Tensor:
+    """What _check_operands reads of an MXFP4 operand: the shape of the dequantised cache, in the query's dtype, without storage."""
+    return torch.empty(tuple(codes.shape[:-1]) + (D,), dtype=dtype, device="meta")
+
+
 def _check_scales(k, Hkv: int, **scales):
     """k_scale= / v_scale= of a call over the cache k: required with an e4m3 cache, refused with a 2-byte one.  A scale is a
     positive finite Python float or a float32 tensor of 1 or Hkv values on the cache's device (its values are not read)."""
@@ -556,6 +624,7 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bl
     are built once per K/V head) or 1.  Both block sizes; ranges with 128-token blocks as above.  With Hkv == H nothing changes.
     Only this call is grouped: triton_block_sparse_attention_onehot, build_block_index, the rectified_* calls and the fp8
     switches stay MHA-only (the selection statistics pool K per head, and the reference has no grouped form)."""
+    _refuse_mxfp4("block_sparse_attention", k)
     blk = _check_block_pair(block_size, block_size)
     if int(bool(causal)) + (window is not None) + (row_range is not None) > 1:
         raise ValueError("causal, window and row_range exclude one another: give at most one")
@@ -870,7 +939,7 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
 
 
 def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_table=None, out: Optional[torch.Tensor] = None,
-              start=None, workgroups_per_head: Optional[int] = None, k_scale=None) -> torch.Tensor:
+              start=None, workgroups_per_head: Optional[int] = None, k_scale=None, k_block_scale=None) -> torch.Tensor:
     """The cache of pooled keys select_blocks_pooled reads: per key block the kbar of select_blocks, the
     fp32 sum of the block's keys below kv_len[b] divided once by their count, in select_blocks' summation order.
     k [B,Hkv,Sk,D], any strides block_sparse_decode accepts (a cache is never copied), or with block_table int32 [B, NKt] a page
@@ -892,15 +961,26 @@ def pool_keys(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_tabl
     An e4m3 cache: k float8_e4m3fn, contiguous or paged, head dim 64 / 128, strides multiples of 8 bytes,
     with k_scale a positive float or a float32 device tensor of 1 or Hkv values (required then, refused otherwise).  The value of
     a block is the fp32 sum of float(code) over its keys below kv_len[b], in the same order, divided once by their count and
-    multiplied once by k_scale[hkv]; every other clause above holds.  select_blocks_pooled reads the result as before."""
-    return _pool_cache("pool_keys", (), k, block_size, kv_len, block_table, out, start, workgroups_per_head, k_scale)
+    multiplied once by k_scale[hkv]; every other clause above holds.  select_blocks_pooled reads the result as before.
+    An MXFP4 cache: k the uint8 / float4_e2m1fn_x2 codes [B,Hkv,Sk,D/2] (or page pools), strides multiples
+    of 4 bytes, with k_block_scale the uint8 / float8_e8m0fnu scale bytes [B,Hkv,Sk,D/32]; head dim 64 / 128; k_scale refused.  The
+    value of a block is the fp32 sum of the dequantised keys below kv_len[b], in the same order, divided once by their count: the
+    bytes of this call on the dequantised 2-byte cache.  Every other clause above holds."""
+    return _pool_cache("pool_keys", (), k, block_size, kv_len, block_table, out, start, workgroups_per_head, k_scale, k_block_scale)
 
 
-def _pool_cache(what: str, pair, k, block_size, kv_len, block_table, out, start, workgroups_per_head, k_scale) -> torch.Tensor:
+def _pool_cache(what: str, pair, k, block_size, kv_len, block_table, out, start, workgroups_per_head, k_scale,
+                k_block_scale=None) -> torch.Tensor:
     """pool_keys (pair = (): the cache [B, Hkv, NK, D], rsa_pool_keys[_kv8]) and pool_key_bounds (pair = (2,): the cache
     [B, Hkv, NK, 2, D], rsa_pool_key_bounds[_kv8]): one argument contract, and C entries with the same argument lists."""
     blk = _check_block(what, block_size)
     _check_count("workgroups_per_head", workgroups_per_head, 1, optional=True)
+    kv4 = None
+    if k_block_scale is not None or (FP4X2 is not None and getattr(k, "dtype", None) == FP4X2):
+        if k_block_scale is None:
+            raise ValueError("k_block_scale: required with float4_e2m1fn_x2 codes")
+        D4, (codes,), (kbs,) = _kv4_cache(what, (("k", k, "k_block_scale", k_block_scale, 4, 0),), (k_scale,))
+        kv4, k, k_scale = (codes, kbs), _kv4_standin(codes, D4, torch.bfloat16), None
     B, _, Hkv, _, Sk, D = _check_operands(None, k, block_table=block_table, blk=blk, kv8_ok=True)
     _check_scales(k, Hkv, k_scale=k_scale)
     NK = _key_blocks(Sk, blk)
@@ -913,9 +993,12 @@ def _pool_cache(what: str, pair, k, block_size, kv_len, block_table, out, start,
                          f"{tuple(getattr(out, 'shape', ()))}")
     lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
     starts = _check_limit("start", start, B, Sk, 0)
-    _check_cache(k)
-    _core._require_device(k)
-    dev = k.device
+    if kv4 is None:
+        _check_cache(k)
+        _core._require_device(k)
+    else:
+        _core._require_device(*kv4)
+    dev = k.device if kv4 is None else kv4[0].device
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     else:
@@ -933,7 +1016,11 @@ def _pool_cache(what: str, pair, k, block_size, kv_len, block_table, out, start,
         wph = NK if start is None else 2
     entry = ("rsa_pool_key_bounds" if pair else "rsa_pool_keys") + ("_kv8" if k.dtype == E4M3 else "")
     with torch.cuda.device(dev):
-        if k.dtype == E4M3:
+        if kv4 is not None:
+            _lib.check(_lib.lib().rsa_pool_keys_kv4(B, Hkv, Sk, D, blk, NK, _core._t4(kv4[0]), *table, _ptr(kv_dev), kv_valid,
+                                                    _ptr(st_dev), st_host, wph, out.data_ptr(), _core._t4(kv4[1]),
+                                                    _core._stream()), "rsa_pool_keys_kv4")
+        elif k.dtype == E4M3:
             ks = _scale_arg(k_scale, Hkv, dev)
             _lib.check(getattr(_lib.lib(), entry)(B, Hkv, Sk, D, blk, NK, _core._t4(k), *table, _ptr(kv_dev), kv_valid,
                                                   _ptr(st_dev), st_host, wph, out.data_ptr(), ks.data_ptr(), _core._stream()), entry)
@@ -945,7 +1032,7 @@ def _pool_cache(what: str, pair, k, block_size, kv_len, block_table, out, start,
 
 
 def pool_key_bounds(k: torch.Tensor, *, block_size: int = 128, kv_len=None, block_table=None, out: Optional[torch.Tensor] = None,
-                    start=None, workgroups_per_head: Optional[int] = None, k_scale=None) -> torch.Tensor:
+                    start=None, workgroups_per_head: Optional[int] = None, k_scale=None, k_block_scale=None) -> torch.Tensor:
     """The cache of per-channel key bounds select_blocks_bound reads: per key block and channel the
     minimum and the maximum of the block's keys below kv_len[b].  Returns (and fills) out, fp32 [B, Hkv, NKt, 2, D] contiguous:
     out[..., 0, :] the minima, out[..., 1, :] the maxima; 1/32 of K's bytes at 128-token blocks of bf16.
@@ -958,7 +1045,8 @@ def pool_key_bounds(k: torch.Tensor, *, block_size: int = 128, kv_len=None, bloc
     An e4m3 cache: min and max are taken over float(code) and each is multiplied once by k_scale[hkv] (positive: the order is
     kept).  Keys below kv_len are taken to be finite: a NaN there gives an unspecified value (and forms no address).
     min and max are exact and order-free, so every workgroups_per_head gives the same values and two calls the same bytes; one
-    pass over K writes both halves."""
+    pass over K writes both halves.  An MXFP4 cache (k_block_scale=) is not served: NotImplementedError."""
+    _refuse_mxfp4("pool_key_bounds", k, k_block_scale=k_block_scale)
     return _pool_cache("pool_key_bounds", (2,), k, block_size, kv_len, block_table, out, start, workgroups_per_head, k_scale)
 
 
@@ -1034,6 +1122,53 @@ def append_kv_e4m3(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tens
                                              _core._t4(v_new), _out4(k_cache), _out4(v_cache), *table, _ptr(st_dev), st_host,
                                              _ptr(n_dev), n_host, ks.data_ptr(), vs.data_ptr(), _core._stream()),
                    "rsa_kv8_append")
+
+
+def append_kv_mxfp4(k_new: torch.Tensor, v_new: torch.Tensor, k_codes: torch.Tensor, k_scales: torch.Tensor, v_codes: torch.Tensor,
+                    v_scales: torch.Tensor, *, start, n_new=None, cu_seqlens=None, block_size: int = 128, block_table=None) -> None:
+    """The writer of an MXFP4 K/V cache: new K / V rows become OCP e2m1 codes, two to a byte, with one
+    e8m0 scale byte per 32 channels of a row, and land where block_sparse_decode and pool_keys read them.
+    k_new / v_new [B,Hkv,T,D], bf16 / fp16, through any strides block_sparse_decode accepts for k / v (never copied).  k_codes /
+    v_codes uint8 or float4_e2m1fn_x2 [B,Hkv,Sk,D/2] (element 2 i in the low nibble of byte i), k_scales / v_scales uint8 or
+    float8_e8m0fnu [B,Hkv,Sk,D/32] (byte s means 2^(s - 127)); or with block_table int32 [B, NKt] page pools [P,Hkv,block_size,D/2]
+    and [P,Hkv,block_size,D/32] of capacity Sk = NKt * block_size.  Code views: strides and pointer multiples of 16 bytes.  Head dim
+    64 or 128.  The value of element d of a row is e2m1(code_d) * 2^(scale[d // 32] - 127).
+    Token t < n_new[b] (default T) of batch item b goes to position start[b] + t.  start, n_new: an int, one value per batch item,
+    or an int32 / int64 device tensor of 1 or B values, which is clamped on the device (into [0, Sk] / [0, T]) and never read on
+    the host; the grid is sized from T alone.  Prefill is the call with start=0.
+    Per row and 32-channel group, as tests/kv4_ref.py spells it: a = the largest |x_d| (a NaN element left out); e =
+    clamp(exponent_field(a) - 127 - 2, -13, 13), -13 for a zero or subnormal a; the scale byte is e + 127; code_d is x_d * 2^-e
+    rounded to nearest even onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at +-6 (+-Inf included), the sign of x_d kept (-0 and a
+    negative that rounds to zero are 0x8).  A NaN element becomes code 0x0: e2m1 has no NaN, and nothing here reads a value on
+    the host to refuse one.  With e in [-13, 13] every written value is exactly a bf16 and an fp16, so one cache serves both.
+    The call writes exactly the D/2 + D/32 bytes of every placed row, for each of K and V, and no other byte.  A position at or
+    beyond the capacity is dropped, and so is one whose table entry lies outside [0, P).  A scale belongs to 32 channels of one
+    token row: an append never re-quantises what a page already holds.  Asynchronous on the current stream, no host
+    synchronisation, capturable.  cu_seqlens (the packed layout of append_kv_e4m3) is not served: NotImplementedError."""
+    blk = _check_block("append_kv_mxfp4", block_size)
+    if cu_seqlens is not None:
+        raise NotImplementedError("append_kv_mxfp4: the packed layout (cu_seqlens) is not served")
+    B, _, Hkv, T, _, D = _check_operands(k_new, k_new, v_new, dims=KV4_HEAD_DIMS)
+    D4, (kc, vc), (ks, vs) = _kv4_cache("append_kv_mxfp4", (("k_codes", k_codes, "k_scales", k_scales, 16, 0),
+                                                            ("v_codes", v_codes, "v_scales", v_scales, 16, 0)))
+    _, _, _, _, Sk, _ = _check_operands(None, _kv4_standin(kc, D4, k_new.dtype), _kv4_standin(vc, D4, k_new.dtype),
+                                        dims=KV4_HEAD_DIMS, block_table=block_table, blk=blk)
+    if (kc.shape[1], D4) != (Hkv, D) or (block_table is None and kc.shape[0] != B):
+        raise ValueError(f"k_codes {tuple(kc.shape)} does not match k_new {tuple(k_new.shape)}")
+    if block_table is not None:
+        _check_block_table(block_table, B)
+    starts = _check_limit("start", start, B, Sk, 0)
+    counts = _check_limit("n_new", n_new, B, T, T)
+    _check_cache(k_new, v_new)
+    _core._require_device(k_new, v_new, kc, ks, vc, vs)
+    dev = kc.device
+    table, _held = _table_args(block_table, kc)
+    st_dev, st_host, _ = _device_limit(starts, B, Sk, dev)
+    n_dev, n_host, _ = _device_limit(counts, B, T, dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().rsa_kv4_append(B, Hkv, T, Sk, D, _core.dtype_code(k_new.dtype), blk, _core._t4(k_new),
+                                             _core._t4(v_new), _out4(kc), _out4(ks), _out4(vc), _out4(vs), *table, _ptr(st_dev),
+                                             st_host, _ptr(n_dev), n_host, _core._stream()), "rsa_kv4_append")
 
 
 def select_blocks_pooled(q: torch.Tensor, pooled_k: torch.Tensor, top_k: int, *, block_size: int = 128, kv_len=None,
@@ -1137,7 +1272,8 @@ DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_dec
 
 def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask, *, kv_len=None,
                         sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, block_table=None,
-                        return_lse: bool = False, blocks_per_split: Optional[int] = None, k_scale=None, v_scale=None):
+                        return_lse: bool = False, blocks_per_split: Optional[int] = None, k_scale=None, v_scale=None,
+                        k_block_scale=None, v_block_scale=None):
     """Block-sparse attention of a few query rows (decode: one token, or a handful of speculative ones) over a long K/V cache:
     block_sparse_attention's result at one query block, from kernels built for it.
     q [B,H,Sq,D] with Sq <= block_size; k / v [B,Hkv,Sk,D], H % Hkv == 0, query head h reads K/V head h // (H // Hkv); any strides
@@ -1168,10 +1304,18 @@ def block_sparse_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
     dequantised 2-byte cache.  Every rule above holds unchanged; K views need strides and a pointer that are multiples of 8 bytes, V
     views of 16 (others are refused, never copied).  The scales' values are not checked: a zero, negative or non-finite one garbles
     its head's rows only.
+    An MXFP4 cache (DESIGN.md section 5.23): k and v the uint8 / float4_e2m1fn_x2 codes [B,Hkv,Sk,D/2] (append_kv_mxfp4 writes them;
+    element 2 i in the low nibble of byte i), contiguous or paged, with k_block_scale and v_block_scale the uint8 / float8_e8m0fnu
+    scale bytes [B,Hkv,Sk,D/32] (pools [P,Hkv,block,D/32] behind the same table), byte s meaning 2^(s - 127) -- both required then,
+    refused with any other cache, and k_scale / v_scale refused beside them.  Codes become q's type in registers with the scale as
+    the conversion's operand; for scale bytes in [114, 140], the writer's range, that is exact and out and lse are the bytes of this
+    call on the dequantised 2-byte cache.  Every rule above holds unchanged, for codes and scale bytes alike; a scale byte outside
+    the range at a visible key garbles that key's contribution only.  k views need strides and a pointer that are multiples of 4
+    bytes, v views of 16, k_block_scale views of D / 32 (others are refused, never copied).
     There is no q_len here: a ragged decode or draft-verification batch (items of different row counts in one padded q) is
     block_sparse_extend(..., q_len=), which gives this call's bytes on every shape this call serves."""
     return _sparse_rows(False, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
-                        k_scale, v_scale)
+                        k_scale, v_scale, k_block_scale=k_block_scale, v_block_scale=v_block_scale)
 
 
 EXTEND_FILL_GROUPS = 256    # row groups from which block_sparse_extend's default is one split (rsa_decode.hip: EXT_FILL_GROUPS)
@@ -1204,7 +1348,7 @@ def extend_default_split(groups: int, NK: int) -> int:
 def block_sparse_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_mask, *, kv_len=None,
                         sm_scale: Optional[float] = None, block_size: int = 128, causal: bool = False, block_table=None,
                         return_lse: bool = False, blocks_per_split: Optional[int] = None, k_scale=None, v_scale=None,
-                        q_len=None, cu_seqlens_q=None, max_q_len: Optional[int] = None):
+                        q_len=None, cu_seqlens_q=None, max_q_len: Optional[int] = None, k_block_scale=None, v_block_scale=None):
     """Block-sparse attention of a chunk of new tokens over a K/V cache that already holds a prefix ("extend": chunked prefill, a
     second turn on a cached conversation, a prefix-cache hit, verification of a speculative draft): block_sparse_decode with the
     one-query-block limit and the 64-row limit lifted.  Everything not said here is block_sparse_decode's
@@ -1274,6 +1418,7 @@ def block_sparse_extend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block
         pool_keys(kc, kv_len=kv_len, start=prev, block_table=table, out=pooled, ...)
         lists = select_blocks_pooled(q, pooled, 16, kv_len=kv_len, cu_seqlens_q=cu, max_q_len=M, causal=True, as_lists=True)
         out, lse = block_sparse_extend(q, kc, vc, lists, kv_len=kv_len, cu_seqlens_q=cu, max_q_len=M, causal=True, ...)"""
+    _refuse_mxfp4("block_sparse_extend", k, k_block_scale=k_block_scale, v_block_scale=v_block_scale)
     return _sparse_rows(True, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
                         k_scale, v_scale, q_len, cu_seqlens_q, max_q_len)
 
@@ -1303,12 +1448,19 @@ def packed_row_groups(T: int, B: int, H: int, Hkv: int, Hl: int, max_q_len: int,
 
 
 def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, causal, block_table, return_lse, blocks_per_split,
-                 k_scale, v_scale, q_len=None, cu_seqlens_q=None, max_q_len=None):
+                 k_scale, v_scale, q_len=None, cu_seqlens_q=None, max_q_len=None, k_block_scale=None, v_block_scale=None):
     """block_sparse_decode (ext False) and block_sparse_extend: one argument layer, the C entries of either; with row counts
     (q_len, extend only) the _ragged entries, which take them in front of the stream; with cu_seqlens_q (extend only) the _packed
     entries: q [T, H, D], T in front, M = max_q_len where Sq stood, cu_seqlens_q where q_len stood."""
     blk = _check_block("block-sparse extend" if ext else "block-sparse decode", block_size)
     _check_count("blocks_per_split", blocks_per_split, 1, optional=True)
+    kv4 = None      # an MXFP4 cache (decode only): the byte views of codes and scales; k / v stand in for the dequantised cache
+    if k_block_scale is not None or v_block_scale is not None or (FP4X2 is not None and getattr(k, "dtype", None) == FP4X2):
+        qdt = q.dtype if isinstance(q, torch.Tensor) and q.dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
+        D4, kv4, scales4 = _kv4_cache("block_sparse_decode", (("k", k, "k_block_scale", k_block_scale, 4, 1),
+                                                              ("v", v, "v_block_scale", v_block_scale, 16, 0)), (k_scale, v_scale))
+        kv4 += scales4
+        k, v, k_scale, v_scale = _kv4_standin(kv4[0], D4, qdt), _kv4_standin(kv4[1], D4, qdt), None, None
     r = _query_rows(q, q_len, cu_seqlens_q if ext else None, max_q_len, k, block_table,
                     lambda q4: _check_operands(q4, k, v, dims=(64, 128), block_table=block_table, blk=blk, kv8_ok=True))
     packed, q, B, H, Hkv, Sq, Sk, D, T = r.kind == "packed", r.q4, r.B, r.H, r.Hkv, r.Sq, r.Sk, r.D, r.T
@@ -1348,8 +1500,11 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
                                   f"serves at most {DECODE_MAX_ROWS}; use block_sparse_attention")
     lens = _check_limit("kv_len", kv_len, B, Sk, Sk)
     nrows = _check_limit("q_len", q_len, B, Sq, Sq)
-    _check_cache(k, v)
-    _core._require_device(q, k, v)
+    if kv4 is None:
+        _check_cache(k, v)
+        _core._require_device(q, k, v)
+    else:
+        _core._require_device(q, *kv4)
     dev = q.device
     kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
     q_dev = _row_limit(nrows, B, Sq, dev) if ext else None
@@ -1379,7 +1534,7 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
                        "rsa_block_sparse_decode_bytes")
         shape = (B, H, Sq, D)
         entry = ("rsa_block_sparse_extend" if ext else "rsa_block_sparse_decode") + ("_ragged" if q_dev is not None else "")
-    entry += "_kv8" if kv8 else ""
+    entry += "_kv8" if kv8 else "_kv4" if kv4 is not None else ""
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
     out = torch.empty(shape, dtype=q.dtype, device=dev)
     lse = torch.empty(shape[:-1], dtype=torch.float32, device=dev) if return_lse else None
@@ -1388,11 +1543,14 @@ def _sparse_rows(ext: bool, q, k, v, block_mask, kv_len, sm_scale, block_size, c
         lead, tq, to, held = (T,), _t3(q), RsaOut4(out.data_ptr(), 0, out.stride(1), out.stride(0)), held + [cu]
     else:
         lead, tq, to, held = (), _core._t4(q), _out4(out), held + ([q_dev] if q_dev is not None else [])
+    tail = [t.data_ptr() for t in held]
+    if kv4 is not None:     # the scale views where the e4m3 entry has its two scale pointers
+        k, v, tail = kv4[0], kv4[1], [_core._t4(kv4[2]), _core._t4(kv4[3])]
     with torch.cuda.device(dev):
         _lib.check(getattr(L, entry)(*lead, B, H, Hkv, Hl, Sq, Sk, D, _core.dtype_code(q.dtype), blk, NK, _ptr(kv_dev), kv_valid,
                                      int(bool(causal)), scale, tq, _core._t4(k), _core._t4(v), *table, cols.data_ptr(),
-                                     counts.data_ptr(), bps, ws.data_ptr(), need.value, to, _ptr(lse),
-                                     *[t.data_ptr() for t in held], _core._stream()), entry)
+                                     counts.data_ptr(), bps, ws.data_ptr(), need.value, to, _ptr(lse), *tail, _core._stream()),
+                   entry)
     return (out, lse) if return_lse else out
 
 

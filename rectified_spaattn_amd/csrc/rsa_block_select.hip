@@ -72,8 +72,13 @@ __device__ __forceinline__ int sel_wave_scan(int* cnt, int n, int lane) {
 // ---- pooling ---------------------------------------------------------------------------------------------------------------------
 // The element loader: what a lane reads for its 8 channels of a row, as 8 floats.  bf16 / fp16: 16 bytes.  e4m3_tag (the one-byte
 // K cache of DESIGN.md section 5.14, rsa_pool_keys_kv8): 8 bytes of codes, each as float(code); the head's scale multiplies the
-// finished block once.  sel_add8 and sel_minmax8 are the two steps over the 8 floats: the mean cache's and the bounds cache's.
+// finished block once.  mxfp4_tag (the MXFP4 K cache of section 5.23, rsa_pool_keys_kv4): the dword of the 8 codes and, beside it,
+// the scale byte of their 32-channel group; the 8 floats are the dequantised values themselves, code * 2^(byte - 127), exact, so
+// nothing is multiplied afterwards.  sel_add8 and sel_minmax8 are the two steps over the 8 floats: the mean cache's and the bounds
+// cache's.  SelRows is where a lane's 8 channels of a row come from: a base and a row stride (in units of SelElem::type), and for
+// MXFP4 the scale rows and their stride as well.
 struct e4m3_tag {};
+struct mxfp4_tag {};
 template <typename Tag>
 struct SelElem {
     using type = unsigned short;
@@ -83,6 +88,30 @@ template <>
 struct SelElem<e4m3_tag> {
     using type = unsigned char;
     using vec = uint2;
+};
+template <>
+struct SelElem<mxfp4_tag> {
+    using type = unsigned char;
+    using vec = uint2;                  // x: the 8 codes, y: the scale byte
+};
+
+template <typename Tag>
+struct SelRows {
+    const typename SelElem<Tag>::type* base;
+    long stride_s;
+    __device__ __forceinline__ typename SelElem<Tag>::vec load(int c, long r) const {
+        return *reinterpret_cast<const typename SelElem<Tag>::vec*>(base + c * 8 + r * stride_s);
+    }
+};
+template <>
+struct SelRows<mxfp4_tag> {
+    const unsigned char* base;
+    long stride_s;
+    const unsigned char* scales;
+    long scale_stride_s;
+    __device__ __forceinline__ uint2 load(int c, long r) const {
+        return make_uint2(*reinterpret_cast<const unsigned*>(base + c * 4 + r * stride_s), scales[(c >> 2) + r * scale_stride_s]);
+    }
 };
 
 template <typename Tag>
@@ -107,6 +136,18 @@ __device__ __forceinline__ void sel_unpack8<e4m3_tag>(float (&x)[8], const uint2
         x[4 * i + 3] = hi[1];
     }
 }
+template <>
+__device__ __forceinline__ void sel_unpack8<mxfp4_tag>(float (&x)[8], const uint2 v) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const float sc = __uint_as_float((v.y & 0xFFu) << 23);      // the conversion's scale operand: the float 2^(byte - 127)
+    const f32x2 p[4] = {__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v.x, sc, 0), __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v.x, sc, 1),
+                        __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v.x, sc, 2), __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(v.x, sc, 3)};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        x[2 * i] = p[i][0];
+        x[2 * i + 1] = p[i][1];
+    }
+}
 template <typename Tag>
 __device__ __forceinline__ void sel_add8(float (&a)[8], const typename SelElem<Tag>::vec v) {
     float x[8];
@@ -129,23 +170,21 @@ __device__ __forceinline__ void sel_minmax8(float (&mn)[8], float (&mx)[8], cons
 // 16-byte chunk t % (D / 8) of rows t / (D / 8), + 2048 / D, ...; the partials meet over xor strides D / 8 .. 32 inside the wave
 // and as (w0 + w1) + (w2 + w3) through LDS.
 template <typename Tag>
-__device__ __forceinline__ float sel_pool_block(const typename SelElem<Tag>::type* __restrict__ base, long stride_s, int rows,
-                                                int D, float (*red)[128]) {
+__device__ __forceinline__ float sel_pool_block(const SelRows<Tag> src, int rows, int D, float (*red)[128]) {
     using vec = typename SelElem<Tag>::vec;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = D >> 3, RP = SEL_NT / C;
     const int c = tid % C;
-    const typename SelElem<Tag>::type* p = base + c * 8;
     float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int r = tid / C;
     for (; r + 3 * RP < rows; r += 4 * RP) {
         vec v[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const vec*>(p + (long)(r + u * RP) * stride_s);
+        for (int u = 0; u < 4; ++u) v[u] = src.load(c, r + u * RP);
 #pragma unroll
         for (int u = 0; u < 4; ++u) sel_add8<Tag>(a, v[u]);
     }
-    for (; r < rows; r += RP) sel_add8<Tag>(a, *reinterpret_cast<const vec*>(p + (long)r * stride_s));
+    for (; r < rows; r += RP) sel_add8<Tag>(a, src.load(c, r));
     for (int m = C; m < 64; m <<= 1) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] += __shfl_xor(a[e], m, 64);
@@ -158,12 +197,21 @@ __device__ __forceinline__ float sel_pool_block(const typename SelElem<Tag>::typ
     __syncthreads();
     return tid < D ? (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]) : 0.f;
 }
+template <typename Tag>
+__device__ __forceinline__ float sel_pool_block(const typename SelElem<Tag>::type* __restrict__ base, long stride_s, int rows,
+                                                int D, float (*red)[128]) {
+    return sel_pool_block<Tag>(SelRows<Tag>{base, stride_s}, rows, D, red);
+}
 
 // The value of a key block in the selection: the fp32 sum of its `rows` (>= 1) keys below the limit, divided once by their count.
 template <typename Tag>
+__device__ __forceinline__ float sel_pool_mean(const SelRows<Tag> src, int rows, int D, float (*red)[128]) {
+    return sel_pool_block<Tag>(src, rows, D, red) / (float)rows;
+}
+template <typename Tag>
 __device__ __forceinline__ float sel_pool_mean(const typename SelElem<Tag>::type* __restrict__ base, long stride_s, int rows,
                                                int D, float (*red)[128]) {
-    return sel_pool_block<Tag>(base, stride_s, rows, D, red) / (float)rows;
+    return sel_pool_mean<Tag>(SelRows<Tag>{base, stride_s}, rows, D, red);
 }
 
 template <typename Tag, typename Rows, typename At>
@@ -215,15 +263,25 @@ __global__ __launch_bounds__(SEL_NT) void block_select_pool_kernel(rsa_tensor4 q
 // nothing else.  Both limits are uniform over the workgroup, so every barrier of sel_pool_block is met by all of it.  With a table
 // the page of a block is read for written blocks only, and an entry outside [0, num_pages) gives zeros: no address is formed
 // from it.  Tag = e4m3_tag: k holds codes (strides in bytes) and the mean of the codes is multiplied once by k_scale[hk]; the
-// 2-byte forms never read k_scale.
+// 2-byte forms never read k_scale.  Tag = mxfp4_tag: k holds e2m1 codes (strides in bytes) and the last argument is the view of
+// their scale bytes, laid out as k is (the same batch item or page, head and row); the values are dequantised in the loader.
+template <typename Tag>
+struct SelScale {
+    using type = const float*;          // [Hkv], or unread
+};
+template <>
+struct SelScale<mxfp4_tag> {
+    using type = rsa_tensor4;           // e8m0 bytes [B, Hkv, Sk, D / 32] or page pools
+};
 template <typename Tag>
 __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hkv, int Sk, int D, int blk, int NK, int W,
                                                            const int32_t* __restrict__ kv_len, int kv_valid,
                                                            const int32_t* __restrict__ start_dev, int start_host,
                                                            const int32_t* __restrict__ table, long table_stride_b,
                                                            int num_pages, float* __restrict__ out,
-                                                           const float* __restrict__ k_scale) {
+                                                           const typename SelScale<Tag>::type k_scale) {
     using KT = typename SelElem<Tag>::type;
+    constexpr bool MX = std::is_same<Tag, mxfp4_tag>::value;
     __shared__ float red[4][128];
     const int tid = threadIdx.x;
     const int w = (int)(blockIdx.x % (unsigned)W);
@@ -236,16 +294,23 @@ __global__ __launch_bounds__(SEL_NT) void pool_keys_kernel(rsa_tensor4 k, int Hk
     const int j_hi = min(NK, (len + blk - 1) / blk);
     for (int j = st / blk + w; j < j_hi; j += W) {
         const int rows = min(blk, len - j * blk);       // >= 1 below j_hi
-        const KT* base;
         bool have = true;
+        long item = b, row0 = (long)j * blk;    // where block j lives: the batch item or page, and its first row there
         if (table) {
             const int page = table[b * table_stride_b + j];
             have = page >= 0 && page < num_pages;
-            base = static_cast<const KT*>(k.ptr) + (long)(have ? page : 0) * k.stride_b + (long)hk * k.stride_h;
-        } else {
-            base = static_cast<const KT*>(k.ptr) + b * k.stride_b + (long)hk * k.stride_h + (long)j * blk * k.stride_s;
+            item = have ? page : 0;
+            row0 = 0;
         }
-        float mean = have ? sel_pool_mean<Tag>(base, k.stride_s, rows, D, red) : 0.f;
+        SelRows<Tag> src;
+        src.base = static_cast<const KT*>(k.ptr) + item * k.stride_b + (long)hk * k.stride_h + row0 * k.stride_s;
+        src.stride_s = k.stride_s;
+        if constexpr (MX) {
+            src.scales = static_cast<const unsigned char*>(k_scale.ptr) + item * k_scale.stride_b + (long)hk * k_scale.stride_h +
+                         row0 * k_scale.stride_s;
+            src.scale_stride_s = k_scale.stride_s;
+        }
+        float mean = have ? sel_pool_mean<Tag>(src, rows, D, red) : 0.f;
         if constexpr (std::is_same<Tag, e4m3_tag>::value) mean *= k_scale[hk];
         if (tid < D) out[(bh * NK + j) * D + tid] = mean;
     }
@@ -342,6 +407,9 @@ __global__ __launch_bounds__(SEL_NT) void pool_key_bounds_kernel(rsa_tensor4 k, 
     }
 }
 
+// rsa_pool_kv4.hip (RSA_POOL_KV4_UNIT) is this file again as the translation unit of the MXFP4 cache kernel, pool_keys_kernel<mxfp4_tag>,
+// and its entry: everything between the pooling above and the cache's host code below belongs to this unit alone.
+#ifndef RSA_POOL_KV4_UNIT
 // ---- scores ----------------------------------------------------------------------------------------------------------------------
 // The score forms: how many rows of D floats a cached block has (N) and what a lane adds to a block's score from its four channels
 // of the pooled query (q) and of the block's rows (k).
@@ -822,17 +890,20 @@ extern "C" int rsa_block_select_p(int B, int H, int Hkv, int Hl, int Sq, int Sk,
                    causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores}, &p, nullptr, stream);
 }
 
+#endif      // RSA_POOL_KV4_UNIT
 // ---- the pooled-key cache ----------------------------------------------------------------------------------
 // Both entries: kv8 = k holds e4m3 codes (no dtype; head dims 64 / 128; 8-byte loads) and k_scale is there.  bounds: the entries of
-// the bounds cache (section 5.19), whose out holds 2 D floats a block: the same checks and grid, pool_key_bounds_kernel.
+// the bounds cache (section 5.19), whose out holds 2 D floats a block: the same checks and grid, pool_key_bounds_kernel.  k_bs (the
+// mean cache only): k holds MXFP4 codes (section 5.23; no dtype; head dims 64 / 128; 4-byte loads) and *k_bs is the view of their
+// scale bytes.
 static int sel_pool_keys_run(bool kv8, bool bounds, int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k,
                              const int32_t* block_table, int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev,
                              int kv_valid, const int32_t* start_dev, int start, int workgroups_per_head, float* out,
-                             const float* k_scale, void* stream) {
+                             const float* k_scale, void* stream, const rsa_tensor4* k_bs = nullptr) {
     if (B <= 0 || Hkv <= 0 || Sk <= 0 || NK <= 0) return RSA_ERR_BAD_ARG;
     if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
-    if (!kv8 && dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
-    if (kv8 ? (D != 64 && D != 128) : (D != 16 && D != 32 && D != 64 && D != 128)) return RSA_ERR_UNSUPPORTED;
+    if (!kv8 && !k_bs && dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
+    if (kv8 || k_bs ? (D != 64 && D != 128) : (D != 16 && D != 32 && D != 64 && D != 128)) return RSA_ERR_UNSUPPORTED;
     if (NK != (int)(((long)Sk + block - 1) / block)) return RSA_ERR_BAD_ARG;
     if (NK > SEL_MAX_NK) return RSA_ERR_UNSUPPORTED;
     if (!kv_len_dev && (kv_valid < 0 || kv_valid > Sk)) return RSA_ERR_BAD_ARG;
@@ -842,6 +913,9 @@ static int sel_pool_keys_run(bool kv8, bool bounds, int B, int Hkv, int Sk, int 
     if (kv8) {      // (strides in bytes: 8 of them per lane and load)
         if (!k_scale || (reinterpret_cast<uintptr_t>(k_scale) & 3)) return RSA_ERR_BAD_ARG;
         if ((reinterpret_cast<uintptr_t>(k.ptr) & 7) || (k.stride_b % 8) || (k.stride_h % 8) || (k.stride_s % 8)) return RSA_ERR_BAD_ARG;
+    } else if (k_bs) {  // (strides in bytes: 4 of codes per lane and load, the scale bytes one by one)
+        if ((reinterpret_cast<uintptr_t>(k.ptr) & 3) || (k.stride_b % 4) || (k.stride_h % 4) || (k.stride_s % 4)) return RSA_ERR_BAD_ARG;
+        if (!k_bs->ptr || k_bs->stride_b < 0 || k_bs->stride_h < 0 || k_bs->stride_s < 0) return RSA_ERR_BAD_ARG;
     } else if (rsa_check_tensor(k) != RSA_OK) {
         return RSA_ERR_BAD_ARG;
     }
@@ -860,13 +934,19 @@ static int sel_pool_keys_run(bool kv8, bool bounds, int B, int Hkv, int Sk, int 
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((size_t)B * Hkv * W));
+#ifdef RSA_POOL_KV4_UNIT
+    pool_keys_kernel<mxfp4_tag><<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start, block_table,
+                                                        (long)table_stride_b, num_pages, out, *k_bs);
+#else
     auto form = [&](auto tag) { return bounds ? pool_key_bounds_kernel<decltype(tag)> : pool_keys_kernel<decltype(tag)>; };
     auto* kernel = kv8 ? form(e4m3_tag{}) : dtype == RSA_BF16 ? form(bf16_tag{}) : form(fp16_tag{});
     kernel<<<grid, SEL_NT, 0, s>>>(k, Hkv, Sk, D, block, NK, W, kv_len_dev, kv_valid, start_dev, start, block_table,
                                    (long)table_stride_b, num_pages, out, k_scale);     // (k_scale: NULL unless kv8)
+#endif
     return rsa_launch_status();
 }
 
+#ifndef RSA_POOL_KV4_UNIT
 extern "C" int rsa_pool_keys(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
                              int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
                              const int32_t* start_dev, int start, int workgroups_per_head, float* out, void* stream) {
@@ -883,6 +963,20 @@ extern "C" int rsa_pool_keys_kv8(int B, int Hkv, int Sk, int D, int block, int N
     return sel_pool_keys_run(true, false, B, Hkv, Sk, D, 0, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
                              start_dev, start, workgroups_per_head, out, k_scale, stream);
 }
+
+#else
+// The cache from an MXFP4 K: per block the fp32 sum of code * 2^(scale byte - 127) in sel_pool_block's order,
+// divided once by the count: the bytes of rsa_pool_keys on the dequantised 2-byte K.
+extern "C" int rsa_pool_keys_kv4(int B, int Hkv, int Sk, int D, int block, int NK, rsa_tensor4 k, const int32_t* block_table,
+                                 int64_t table_stride_b, int num_pages, const int32_t* kv_len_dev, int kv_valid,
+                                 const int32_t* start_dev, int start, int workgroups_per_head, float* out,
+                                 rsa_tensor4 k_block_scale, void* stream) {
+    return sel_pool_keys_run(false, false, B, Hkv, Sk, D, 0, block, NK, k, block_table, table_stride_b, num_pages, kv_len_dev, kv_valid,
+                             start_dev, start, workgroups_per_head, out, nullptr, stream, &k_block_scale);
+}
+#endif
+
+#ifndef RSA_POOL_KV4_UNIT
 
 // The bounds cache: rsa_pool_keys' and rsa_pool_keys_kv8's argument lists; out fp32 [B, Hkv, NK, 2, D].
 extern "C" int rsa_pool_key_bounds(int B, int Hkv, int Sk, int D, int dtype, int block, int NK, rsa_tensor4 k,
@@ -1068,3 +1162,4 @@ extern "C" int rsa_block_select_bound_packed(int T, int B, int H, int Hkv, int H
                           block, NQ, NK, kv_len_dev, kv_valid, causal != 0, top_k, keep_first, keep_local, bitmask, cols, counts, scores},
                           p16 == -1 ? nullptr : &p, nullptr, stream, &pk, true);
 }
+#endif      // RSA_POOL_KV4_UNIT

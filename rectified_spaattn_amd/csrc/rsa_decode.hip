@@ -29,6 +29,17 @@
 // fp32 score behind the MFMA chain, the V scale the merged row once; the V image, the MFMAs, the softmax and the meet are the code
 // below.
 //
+// The MXFP4 cache (the _kv4 entry) is the third element, Tag = kv4_tag<query type>, in the decode form only and in
+// a translation unit of its own (rsa_decode_kv4.hip).  K and V are e2m1 codes, two to a byte, with one e8m0 scale byte per 32
+// channels of a row.  An A fragment of K -- 8 channels of a key, all in one scale group -- is ONE dword of codes: a lane loads 4 bytes
+// where the 2-byte kernel loads 16 (same keys, same d range, so the MFMA's summation order is the 2-byte kernel's), and the D / 32
+// scale bytes of its key in one load per key tile (a dword at D = 128).  A 16-byte piece of V codes is exactly one scale group of 32
+// channels: a lane loads a quarter as many pieces as the 2-byte kernel, one scale byte beside each, and writes the piece's 64 bytes
+// of the unchanged [32][D] LDS image.  Codes and scale bytes ride the double-buffered register set (DecRaw) together.  The scale is
+// the conversion's own operand (v_cvt_scalef32_pk_{bf16,f16}_fp4 with the float byte << 23): K just before its MFMA, V on the way
+// into LDS, exact (code * 2^e with e in [-13, 13] is a bf16 and an fp16), so nothing is multiplied behind the MFMA and the merge
+// sees no scale.  Rows at or beyond the limit are read as the last row below it, codes and scales alike.
+//
 // The row form: the one further template parameter of both kernels, which says whose rows a workgroup serves.
 //   DecodeForm         rsa_block_sparse_decode: a whole unit, at most 64 rows of one query block.  Arguments: DecArgs / DecMergeArgs.
 //   ExtendForm<Rows>   the extend entries (section 5.16): any number of query rows, query blocks and heads of a unit.  A workgroup
@@ -93,6 +104,11 @@ struct DecArgs8 : DecArgs {
     const float *k_scale, *v_scale;     // [Hkv]: the value of a code is float(code) * scale[hk]
 };
 
+struct DecArgs4 : DecArgs {
+    const unsigned char *k_bs, *v_bs;   // e8m0 scale bytes [B, Hkv, Sk, D / 32] or page pools: strides in bytes, as k's and v's
+    long kbsb, kbsh, kbss, vbsb, vbsh, vbss;
+};
+
 // The extend kernels' arguments: the decode kernels' (whose layout stays as it is) and the row groups behind them.
 template <typename A>
 struct DecExt : A {
@@ -114,9 +130,12 @@ struct ExtendForm {
     R rows;                     // (host: the source the launch hands to both kernels)
 };
 
-// The cache's element: the query's own 2-byte type (Tag = bf16_tag / fp16_tag), or e4m3 codes (kv8_tag<query type>).
+// The cache's element: the query's own 2-byte type (Tag = bf16_tag / fp16_tag), e4m3 codes (kv8_tag<query type>), or MXFP4
+// codes and block scales (kv4_tag<query type>).  PACK: elements per unit of `elem`, in which the strides count.
 template <typename QTag>
 struct kv8_tag {};
+template <typename QTag>
+struct kv4_tag {};
 template <typename Tag>
 struct DecCache {
     using Q = Tag;
@@ -124,8 +143,9 @@ struct DecCache {
     using Args = DecArgs;
     using MergeArgs = struct DecMergeArgs;
     using kfrag = uint4;                // 8 elements of a key: one A fragment
-    static constexpr bool kv8 = false;
+    static constexpr bool kv8 = false, kv4 = false;
     static constexpr int VPIECE = 8;    // elements of a 16-byte piece of V
+    static constexpr int PACK = 1;
 };
 template <typename QTag>
 struct DecCache<kv8_tag<QTag>> {
@@ -134,8 +154,20 @@ struct DecCache<kv8_tag<QTag>> {
     using Args = DecArgs8;
     using MergeArgs = struct DecMergeArgs8;
     using kfrag = uint2;
-    static constexpr bool kv8 = true;
+    static constexpr bool kv8 = true, kv4 = false;
     static constexpr int VPIECE = 16;
+    static constexpr int PACK = 1;
+};
+template <typename QTag>
+struct DecCache<kv4_tag<QTag>> {
+    using Q = QTag;
+    using elem = unsigned char;
+    using Args = DecArgs4;
+    using MergeArgs = struct DecMergeArgs;      // (no scale acts in the merge)
+    using kfrag = unsigned;
+    static constexpr bool kv8 = false, kv4 = true;
+    static constexpr int VPIECE = 32;
+    static constexpr int PACK = 2;
 };
 
 // Four e4m3 codes -> four elements of the query's type (element i from byte i): gfx950's packed scaled conversions with a unit
@@ -157,6 +189,26 @@ __device__ __forceinline__ uint4 dec_cvt8(uint2 w) {
     return make_uint4(a.x, a.y, b.x, b.y);
 }
 
+// Eight e2m1 codes of one scale group -> eight elements of the query's type (elements 2 i, 2 i + 1 from the low and the high nibble
+// of byte i): v_cvt_scalef32_pk_bf16_fp4 / v_cvt_scalef32_pk_f16_fp4, one per byte: four instructions per dword, as many as the
+// e4m3 form spends on 8 elements.  sc: the group's scale as the instruction takes it, the float whose exponent field is the e8m0
+// byte.  Exact for a byte in [114, 140].
+template <typename QTag>
+__device__ __forceinline__ uint4 dec_cvt8_fp4(unsigned w, float sc) {
+    if constexpr (std::is_same<QTag, bf16_tag>::value) {
+        return make_uint4(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0)),
+                          __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1)),
+                          __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2)),
+                          __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3)));
+    } else {
+        return make_uint4(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 0)),
+                          __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 1)),
+                          __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 2)),
+                          __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 3)));
+    }
+}
+__device__ __forceinline__ float dec_e8m0(unsigned byte) { return __uint_as_float((byte & 0xFFu) << 23); }
+
 template <typename Tag>
 struct Mfma16;
 template <>
@@ -174,8 +226,16 @@ struct Mfma16<fp16_tag> {
 
 // A chunk's operands as they come from global memory: K as the A fragments of S^T (key = 16 t + (lane & 15), d = 32 ks +
 // 8 (lane >> 4) ..), V as 16-byte pieces of its [32][D] row image.  key0 < 0: nothing to do (the block is not visited).
+// (MXFP4: beside them ksc, the D / 32 scale bytes of the lane's key of each key tile, and vsc, the scale byte of each piece.)
+template <bool KV4, int VL>
+struct DecRawScales {};
+template <int VL>
+struct DecRawScales<true, VL> {
+    unsigned ksc[2], vsc[VL];
+    const unsigned char* vsb;           // the V scale rows of the chunk's batch item or page
+};
 template <int D, typename Cache>
-struct DecRaw {
+struct DecRaw : DecRawScales<Cache::kv4, 32 * D / Cache::VPIECE / 64> {
     typename Cache::kfrag kf[2][D / 32];
     uint4 vf[32 * D / Cache::VPIECE / 64];
     const typename Cache::elem* vb;     // the V rows of the chunk's batch item or page, and the offset of its row numbers
@@ -191,7 +251,8 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
     using Tag = typename Cache::Q;      // the type of q, of the MFMA operands and of the output
     using KT = typename Cache::elem;
     using Raw = DecRaw<D, Cache>;
-    constexpr bool KV8 = Cache::kv8;
+    constexpr bool KV8 = Cache::kv8, KV4 = Cache::kv4;
+    constexpr int PK = Cache::PACK;     // elements per unit of KT
     constexpr int VP = Cache::VPIECE;   // elements of a 16-byte piece of V
     constexpr int KS = D / 32, DT = D / 16, CH = D / VP, VL = 32 * CH / 64;
     // At head dim 128 with four row tiles Q (64 registers) and O^T (128) do not fit beside two sets of K and V: the scaled Q
@@ -318,6 +379,11 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
     const KT* vbase = reinterpret_cast<const KT*>(a.v) + (long)hk * a.vsh;
     float kscale = 1.f;
     if constexpr (KV8) kscale = a.k_scale[hk];
+    const unsigned char *ksbase = nullptr, *vsbase = nullptr;
+    if constexpr (KV4) {
+        ksbase = a.k_bs + (long)hk * a.kbsh;
+        vsbase = a.v_bs + (long)hk * a.vbsh;
+    }
 
     for (int e0 = 0; e0 < n_items; e0 += 64) {
         // this lane's list entry: the key block and where it lives, or -1 (out of range, no key below the limit, no page).  No
@@ -336,12 +402,13 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
         }
         const int nch = min(64, n_items - e0) << cshift;
 
-        auto load_v = [&](uint4 (&vf)[VL], const Raw& r) {
+        auto load_v = [&](uint4 (&vf)[VL], Raw& r) {
 #pragma unroll
             for (int i = 0; i < VL; ++i) {
                 const int idx = i * 64 + lane, vr = idx / CH, ch = idx % CH;
                 const long row = min(r.key0 + vr, kvlen - 1) + r.roff;
-                vf[i] = *reinterpret_cast<const uint4*>(r.vb + row * a.vss + VP * ch);
+                vf[i] = *reinterpret_cast<const uint4*>(r.vb + row * a.vss + VP / PK * ch);
+                if constexpr (KV4) r.vsc[i] = r.vsb[row * a.vbss + ch];
             }
         };
         auto load = [&](Raw& r, int c) {
@@ -356,12 +423,21 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
             const KT* kb = kbase + (a.table ? (long)pg * a.ksb : (long)b * a.ksb);
             r.vb = vbase + (a.table ? (long)pg * a.vsb : (long)b * a.vsb);
             r.roff = roff;
+            const unsigned char* ksb = nullptr;
+            if constexpr (KV4) {
+                ksb = ksbase + (a.table ? (long)pg * a.kbsb : (long)b * a.kbsb);
+                r.vsb = vsbase + (a.table ? (long)pg * a.vbsb : (long)b * a.vbsb);
+            }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const long row = min(key0 + 16 * t + lr, kvlen - 1) + roff;
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)
-                    r.kf[t][ks] = *reinterpret_cast<const typename Cache::kfrag*>(kb + row * a.kss + 32 * ks + 8 * lh);
+                    r.kf[t][ks] = *reinterpret_cast<const typename Cache::kfrag*>(kb + row * a.kss + (32 * ks + 8 * lh) / PK);
+                if constexpr (KV4) {    // the key's D / 32 scale bytes: byte ks is the group of fragment ks, whatever lh
+                    if constexpr (KS == 4) r.ksc[t] = *reinterpret_cast<const unsigned*>(ksb + row * a.kbss);
+                    else r.ksc[t] = *reinterpret_cast<const unsigned short*>(ksb + row * a.kbss);
+                }
             }
             load_v(r.vf, r);
         };
@@ -372,6 +448,7 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
         };
         auto kfrag = [&](const Raw& r, int t, int ks) {
             if constexpr (KV8) return __builtin_bit_cast(s16x8, dec_cvt8<Tag>(r.kf[t][ks]));
+            else if constexpr (KV4) return __builtin_bit_cast(s16x8, dec_cvt8_fp4<Tag>(r.kf[t][ks], dec_e8m0(r.ksc[t] >> (8 * ks))));
             else return __builtin_bit_cast(s16x8, r.kf[t][ks]);
         };
         auto compute = [&](const Raw& r) {
@@ -423,6 +500,13 @@ __global__ __launch_bounds__(DEC_NT, MT == 1 ? 2 : 1) void decode_split_kernel(
                 if constexpr (KV8) {        // (the zero code is the zero element)
                     *reinterpret_cast<uint4*>(vst + vr * VROW + 32 * ch) = dec_cvt8<Tag>(make_uint2(x.x, x.y));
                     *reinterpret_cast<uint4*>(vst + vr * VROW + 32 * ch + 16) = dec_cvt8<Tag>(make_uint2(x.z, x.w));
+                } else if constexpr (KV4) {     // (the zero code is the zero element under every scale in the range)
+                    const float sc = dec_e8m0(r.vsc[i]);
+                    unsigned char* const vd = vst + vr * VROW + 64 * ch;
+                    *reinterpret_cast<uint4*>(vd) = dec_cvt8_fp4<Tag>(x.x, sc);
+                    *reinterpret_cast<uint4*>(vd + 16) = dec_cvt8_fp4<Tag>(x.y, sc);
+                    *reinterpret_cast<uint4*>(vd + 32) = dec_cvt8_fp4<Tag>(x.z, sc);
+                    *reinterpret_cast<uint4*>(vd + 48) = dec_cvt8_fp4<Tag>(x.w, sc);
                 } else {
                     *reinterpret_cast<uint4*>(vst + vr * VROW + 16 * ch) = x;
                 }
@@ -700,6 +784,7 @@ static int dec_plan_bytes(DecKind kind, int T, int B, int H, int Hkv, int Hl, in
     return st;
 }
 
+#ifndef RSA_DECODE_KV4_UNIT
 extern "C" int rsa_block_sparse_extend_packed_bytes(int T, int B, int H, int Hkv, int Hl, int max_q_len, int D, int block, int NK,
                                                     int blocks_per_split, size_t* bytes, int64_t* pieces) {
     return dec_plan_bytes(DEC_PACKED, T, B, H, Hkv, Hl, max_q_len, D, block, NK, blocks_per_split, bytes, pieces);
@@ -714,9 +799,11 @@ extern "C" int rsa_block_sparse_extend_bytes(int B, int H, int Hkv, int Hl, int 
                                              int blocks_per_split, size_t* bytes) {
     return dec_plan_bytes(DEC_EXTEND, 0, B, H, Hkv, Hl, Sq, D, block, NK, blocks_per_split, bytes, nullptr);
 }
+#endif
 
 // The one place that maps a call's cache element, query type, head dimension and row tiles to the kernels' template arguments:
 // f(cache tag, std::integral_constant<int, D>, std::integral_constant<int, MT>).
+// rsa_decode_kv4.hip (RSA_DECODE_KV4_UNIT) holds the MXFP4 instantiations and this unit the others: each maps only its own.
 template <typename F>
 static void dec_with_shape(bool kv8, int dtype, int D, int MT, F f) {
     auto with_tag = [&](auto ctag) {
@@ -728,13 +815,19 @@ static void dec_with_shape(bool kv8, int dtype, int D, int MT, F f) {
         if (D == 128) with_d(std::integral_constant<int, 128>());
         else with_d(std::integral_constant<int, 64>());
     };
+#ifdef RSA_DECODE_KV4_UNIT
+    if (dtype == RSA_BF16) with_tag(kv4_tag<bf16_tag>());
+    else with_tag(kv4_tag<fp16_tag>());
+#else
     if (kv8 && dtype == RSA_BF16) with_tag(kv8_tag<bf16_tag>());
     else if (kv8) with_tag(kv8_tag<fp16_tag>());
     else if (dtype == RSA_BF16) with_tag(bf16_tag());
     else with_tag(fp16_tag());
+#endif
 }
 
-// An e4m3 cache view as the loads need it: K is read 8 bytes a lane, V 16 (strides in elements = bytes).
+// An e4m3 cache view as the loads need it: K is read 8 bytes a lane, V 16 (strides in elements = bytes).  The MXFP4 views likewise:
+// K codes 4 bytes a lane, V codes 16, the K scale bytes of a key in one load of D / 32 bytes, the V scale bytes one by one.
 static int dec_check_cache8(const rsa_tensor4& t, int align) {
     if (!t.ptr || (reinterpret_cast<uintptr_t>(t.ptr) & (align - 1))) return RSA_ERR_BAD_ARG;
     if ((t.stride_b % align) || (t.stride_h % align) || (t.stride_s % align)) return RSA_ERR_BAD_ARG;
@@ -743,7 +836,7 @@ static int dec_check_cache8(const rsa_tensor4& t, int align) {
 
 // What the eight entries hand to dec_run: their own arguments by name, and kind -- decode, extend, or the packed extend call: Sq is
 // then M, T the rows of q, and q / out are read through stride_h and stride_s (the row's); kv8: the cache holds e4m3 codes and the two
-// scale arrays are there; q_len_dev: the ragged call's rows per batch item (null: Sq); cu: the packed call's cu_seqlens_q [B + 1].
+// scale arrays are there; kv4: the cache holds MXFP4 codes and k_bs / v_bs their scale bytes (decode only); q_len_dev: the ragged call's rows per batch item (null: Sq); cu: the packed call's cu_seqlens_q [B + 1].
 struct DecCall {
     DecKind kind;
     bool kv8;
@@ -764,6 +857,8 @@ struct DecCall {
     const float *k_scale, *v_scale;
     const int32_t *q_len_dev, *cu;
     void* stream;
+    bool kv4;
+    rsa_tensor4 k_bs, v_bs;
 };
 
 static int dec_run(const DecCall& c) {
@@ -790,6 +885,14 @@ static int dec_run(const DecCall& c) {
         if (!c.k_scale || !c.v_scale || ((reinterpret_cast<uintptr_t>(c.k_scale) | reinterpret_cast<uintptr_t>(c.v_scale)) & 3))
             return RSA_ERR_BAD_ARG;
         if (dec_check_cache8(k, 8) != RSA_OK || dec_check_cache8(v, 16) != RSA_OK) return RSA_ERR_BAD_ARG;
+    } else if (c.kv4) {
+        if (c.kind != DEC_DECODE) return RSA_ERR_UNSUPPORTED;
+        if (dec_check_cache8(k, 4) != RSA_OK || dec_check_cache8(v, 16) != RSA_OK || dec_check_cache8(c.k_bs, D / 32) != RSA_OK ||
+            !c.v_bs.ptr)
+            return RSA_ERR_BAD_ARG;
+        if (c.k_bs.stride_b < 0 || c.k_bs.stride_h < 0 || c.k_bs.stride_s < 0 || c.v_bs.stride_b < 0 || c.v_bs.stride_h < 0 ||
+            c.v_bs.stride_s < 0)
+            return RSA_ERR_BAD_ARG;
     } else if (rsa_check_tensor(k) != RSA_OK || rsa_check_tensor(v) != RSA_OK) {
         return RSA_ERR_BAD_ARG;
     }
@@ -825,7 +928,7 @@ static int dec_run(const DecCall& c) {
     a.C = p.C; a.nsplit = p.nsplit; a.R16 = 16 * p.MT;
     a.qk_scale = (float)(c.sm_scale * 1.44269504);  // (as rsa_block_sparse_plain_fwd)
     // (packed: row_start and piece_start stand at the head of the workspace, the partials 16-byte aligned behind them)
-    int32_t* const pk_head = static_cast<int32_t*>(c.ws);
+    [[maybe_unused]] int32_t* const pk_head = static_cast<int32_t*>(c.ws);
     a.ws_o = reinterpret_cast<float*>(static_cast<unsigned char*>(c.ws) + (pk ? pk_head_bytes(2 * ((long)B + 1)) : 0));
     a.ws_ml = reinterpret_cast<float2*>(a.ws_o + parts * a.R16 * D);
     a.k_scale = c.k_scale;
@@ -851,7 +954,15 @@ static int dec_run(const DecCall& c) {
             using CTag = decltype(ctag);
             typename Form::template Args<typename DecCache<CTag>::Args> sa;
             typename Form::template Args<typename DecCache<CTag>::MergeArgs> ma;
-            static_cast<typename DecCache<CTag>::Args&>(sa) = a;
+            if constexpr (DecCache<CTag>::kv4) {
+                static_cast<DecArgs&>(sa) = a;
+                sa.k_bs = static_cast<const unsigned char*>(c.k_bs.ptr);
+                sa.v_bs = static_cast<const unsigned char*>(c.v_bs.ptr);
+                sa.kbsb = c.k_bs.stride_b; sa.kbsh = c.k_bs.stride_h; sa.kbss = c.k_bs.stride_s;
+                sa.vbsb = c.v_bs.stride_b; sa.vbsh = c.v_bs.stride_h; sa.vbss = c.v_bs.stride_s;
+            } else {
+                static_cast<typename DecCache<CTag>::Args&>(sa) = a;
+            }
             static_cast<typename DecCache<CTag>::MergeArgs&>(ma) = g;
             if constexpr (Form::EXT) {
                 sa.g = ma.g = p.g;
@@ -862,6 +973,9 @@ static int dec_run(const DecCall& c) {
             decode_merge_kernel<CTag, decltype(d)::value, Form><<<mgrid, DEC_NT, 0, s>>>(ma);
         });
     };
+#ifdef RSA_DECODE_KV4_UNIT
+    launch(DecodeForm{});
+#else
     if (c.kind == DEC_DECODE) {
         launch(DecodeForm{});
     } else if (pk) {        // behind the scan of cu_seqlens_q: three launches
@@ -872,9 +986,27 @@ static int dec_run(const DecCall& c) {
     } else {
         launch(ExtendForm<RowsPadded>{});
     }
+#endif
     return rsa_launch_status();
 }
 
+#ifdef RSA_DECODE_KV4_UNIT
+// The MXFP4 cache: dtype names q's type; k / v hold e2m1 codes, two to a byte (strides in bytes), and
+// k_block_scale / v_block_scale their e8m0 scale bytes, [B, Hkv, Sk, D / 32] or page pools behind the same table.
+extern "C" int rsa_block_sparse_decode_kv4(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
+                                           const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
+                                           rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
+                                           int num_pages, const int32_t* cols, const int32_t* counts, int blocks_per_split,
+                                           void* ws, size_t ws_bytes, rsa_out4 out, float* lse, rsa_tensor4 k_block_scale,
+                                           rsa_tensor4 v_block_scale, void* stream) {
+    return dec_run({.kind = DEC_DECODE, .kv8 = false, .B = B, .H = H, .Hkv = Hkv, .Hl = Hl, .Sq = Sq, .Sk = Sk, .D = D,
+                    .dtype = dtype, .block = block, .NK = NK, .kv_len_dev = kv_len_dev, .kv_valid = kv_valid, .causal = causal,
+                    .sm_scale = sm_scale, .q = q, .k = k, .v = v, .block_table = block_table, .table_stride_b = table_stride_b,
+                    .num_pages = num_pages, .cols = cols, .counts = counts, .blocks_per_split = blocks_per_split, .ws = ws,
+                    .ws_bytes = ws_bytes, .out = out, .lse = lse, .stream = stream, .kv4 = true, .k_bs = k_block_scale,
+                    .v_bs = v_block_scale});
+}
+#else
 extern "C" int rsa_block_sparse_decode(int B, int H, int Hkv, int Hl, int Sq, int Sk, int D, int dtype, int block, int NK,
                                        const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, rsa_tensor4 q,
                                        rsa_tensor4 k, rsa_tensor4 v, const int32_t* block_table, int64_t table_stride_b,
@@ -991,3 +1123,4 @@ extern "C" int rsa_block_sparse_extend_packed_kv8(int T, int B, int H, int Hkv, 
                     .blocks_per_split = blocks_per_split, .ws = ws, .ws_bytes = ws_bytes, .out = out, .lse = lse,
                     .k_scale = k_scale, .v_scale = v_scale, .cu = cu_seqlens_q_dev, .stream = stream});
 }
+#endif      // RSA_DECODE_KV4_UNIT

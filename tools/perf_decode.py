@@ -24,6 +24,13 @@ code * scale -- the two outputs must be byte-equal -- then the writer at a prefi
 time) and rsa_pool_keys_kv8 next to rsa_pool_keys at prefill.
 
     python tools/perf_decode.py --kv8 [--out profiles/decode_kv8_perf.txt]
+
+--kv4 times, on the same six shapes and by the same method, the three C entries interleaved in one process
+on the same content: rsa_block_sparse_decode_kv4 over an MXFP4 cache (filled by rsa_kv4_append), rsa_block_sparse_decode over the
+dequantised bf16 cache and rsa_block_sparse_decode_kv8 over the same values as e4m3 codes under unit scales (exact: a written value
+of N(0, 1) rows is an e4m3); then the writer at a prefill-sized append and rsa_pool_keys_kv4 next to rsa_pool_keys at prefill.
+
+    python tools/perf_decode.py --kv4 [--out profiles/decode_kv4_perf.txt]
 """
 import argparse
 import ctypes
@@ -268,6 +275,139 @@ def kv8_writer_and_pool(say, args, B, Sk):
     return dict(B=B, Sk=Sk, writer_us=round(1e3 * med[0], 2), pool_bf16_us=round(1e3 * med[1], 2), pool_e4m3_us=round(1e3 * med[2], 2))
 
 
+def _kv4_cache(B, Hkv, Sk, D, g, dev):
+    """([kc, ks, vc, vs], [kd, vd], [k8, v8], append): MXFP4 caches written by the writer from N(0, 1) bf16 rows, their dequantised
+    bf16 twins, the same values as e4m3 codes, and the writer call as a function (for its own timing)."""
+    L = _lib.lib()
+    new = [torch.randn(B, Hkv, Sk, D, device=dev, generator=g).to(torch.bfloat16) for _ in range(2)]
+    c4 = [torch.empty((B, Hkv, Sk, last), dtype=torch.uint8, device=dev) for last in (D // 2, D // 32, D // 2, D // 32)]
+    o4 = [_lib.RsaOut4(t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)) for t in c4]
+
+    def append():
+        _lib.check(L.rsa_kv4_append(B, Hkv, Sk, Sk, D, _lib.RSA_BF16, 128, _core._t4(new[0]), _core._t4(new[1]), *o4, None, 0, 0, None, 0,
+                                    None, Sk, _core._stream()), "rsa_kv4_append")
+    append()
+    lut = torch.tensor([0, 0.5, 1, 1.5, 2, 3, 4, 6, -0.0, -0.5, -1, -1.5, -2, -3, -4, -6], device=dev)
+    deq = []
+    for codes, scales in ((c4[0], c4[1]), (c4[2], c4[3])):
+        d = torch.empty((B, Hkv, Sk, D), dtype=torch.bfloat16, device=dev)
+        for b in range(B):
+            nib = torch.stack([codes[b] & 0xF, codes[b] >> 4], -1).reshape(Hkv, Sk, D).long()
+            d[b] = (lut[nib] * torch.exp2(scales[b].float() - 127).repeat_interleave(32, -1)).to(torch.bfloat16)
+        deq.append(d)
+    c8 = [d.to(torch.float8_e4m3fn) for d in deq]
+    assert all(torch.equal(c.to(torch.bfloat16), d) for c, d in zip(c8, deq)), "the written values are e4m3 values"
+    return c4, deq, c8, append
+
+
+def kv4_row(say, args, name, B, Sk, Sq, top_k, paged):
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    H, Hkv, D, blk = 32, 8, 128, 128
+    NK = Sk // blk
+    g = torch.Generator(device=dev).manual_seed(B * 7 + Sq + top_k)
+    q = torch.randn(B, H, Sq, D, device=dev, generator=g).to(torch.bfloat16)
+    c4, deq, c8, _ = _kv4_cache(B, Hkv, Sk, D, g, dev)
+    one = torch.ones((Hkv,), dtype=torch.float32, device=dev)
+    lists = block_sparse.select_blocks(q, deq[0], top_k, causal=True, as_lists=True)
+    cols, counts = lists["cols"], lists["counts"]
+    kept_blocks = int(counts.sum())
+    keys = kept_blocks * blk
+    outs = [torch.zeros((B, H, Sq, D), dtype=q.dtype, device=dev) for _ in range(3)]
+    lses = [torch.zeros((B, H, Sq), dtype=torch.float32, device=dev) for _ in range(3)]
+    o4 = [_lib.RsaOut4(o.data_ptr(), o.stride(0), o.stride(1), o.stride(2)) for o in outs]
+    st = _core._stream()
+    targs = (None, 0, 0)
+    if paged:
+        P = B * NK
+        perm = torch.randperm(P, device=dev, generator=g)
+        table = perm.view(B, NK).to(torch.int32).contiguous()
+        targs = (table.data_ptr(), NK, P)
+
+        def pages(t):
+            seq = t.view(B, Hkv, NK, blk, t.shape[-1]).permute(0, 2, 1, 3, 4).reshape(P, Hkv, blk, t.shape[-1])
+            out = torch.empty_like(seq)
+            out[perm] = seq
+            return out
+        c4, deq = [pages(t) for t in c4], [pages(t) for t in deq]
+        c8 = [pages(t.view(torch.uint8)).view(torch.float8_e4m3fn) for t in c8]
+    need = ctypes.c_size_t(0)
+    _lib.check(L.rsa_block_sparse_decode_bytes(B, H, Hkv, Hkv, Sq, D, NK, 0, ctypes.byref(need)), "decode_bytes")
+    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
+    head = (B, H, Hkv, Hkv, Sq, Sk, D, _lib.RSA_BF16, blk, NK, None, Sk, 1, D ** -0.5, _core._t4(q))
+
+    def tail(i):
+        return (*targs, cols.data_ptr(), counts.data_ptr(), 0, ws.data_ptr(), need.value, o4[i], lses[i].data_ptr())
+
+    def two_byte():
+        _lib.check(L.rsa_block_sparse_decode(*head, _core._t4(deq[0]), _core._t4(deq[1]), *tail(0), st), "rsa_block_sparse_decode")
+
+    def e4m3():
+        _lib.check(L.rsa_block_sparse_decode_kv8(*head, _core._t4(c8[0]), _core._t4(c8[1]), *tail(1), one.data_ptr(), one.data_ptr(), st),
+                   "rsa_block_sparse_decode_kv8")
+
+    def mxfp4():
+        _lib.check(L.rsa_block_sparse_decode_kv4(*head, _core._t4(c4[0]), _core._t4(c4[2]), *tail(2), _core._t4(c4[1]), _core._t4(c4[3]), st),
+                   "rsa_block_sparse_decode_kv4")
+    fns = [two_byte, e4m3, mxfp4]
+    for _ in range(2):
+        for f in fns:
+            f()
+    torch.cuda.synchronize()
+    equal = all(bool(torch.equal(outs[0].view(torch.int16), outs[i].view(torch.int16)) and torch.equal(lses[0], lses[i])) for i in (1, 2))
+    rounds = [_round(fns, args.reps) for _ in range(args.rounds)]
+    med = [statistics.median(r[i] for r in rounds) for i in range(3)]
+    spread = [max(r[i] for r in rounds) - min(r[i] for r in rounds) for i in range(3)]
+    per_key = (2 * 2 * D, 2 * D, 2 * (D // 2 + D // 32))        # bytes of K and V per key: bf16, e4m3, MXFP4
+    say(f"{name}: B = {B}, Sk = {Sk} ({NK} blocks), Sq = {Sq}, top_k = {top_k}{', paged' if paged else ''}; {kept_blocks} kept blocks = "
+        + ", ".join(f"{keys * n / 1e6:.1f} MB of {w}" for n, w in zip(per_key, ("bf16 K and V", "e4m3", "MXFP4"))))
+    for i, w in enumerate(("2-byte call", "e4m3 call ", "MXFP4 call ")):
+        say(f"  {w}: {1e3 * med[i]:.1f} us   (rounds: {' '.join(f'{1e3 * r[i]:.1f}' for r in rounds)}; spread {1e3 * spread[i]:.1f} us) = "
+            f"{keys * per_key[i] / med[i] / 1e9:.3f} TB/s of what it reads of the kept K and V")
+    gain = med[1] - med[2]
+    say(f"  e4m3 - MXFP4 = {1e3 * gain:+.1f} us ({med[1] / med[2]:.2f} x); slower than the e4m3 call by more than its spread: "
+        f"{-gain > spread[1]}; faster by more: {gain > spread[1]}; all three outputs and log-sum-exps byte-equal: {equal}")
+    return dict(name=name, B=B, Sk=Sk, Sq=Sq, top_k=top_k, paged=paged, two_byte_us=round(1e3 * med[0], 2), e4m3_us=round(1e3 * med[1], 2),
+                mxfp4_us=round(1e3 * med[2], 2), e4m3_spread_us=round(1e3 * spread[1], 2), slower=bool(-gain > spread[1]), byte_equal=equal)
+
+
+def kv4_writer_and_pool(say, args, B, Sk):
+    """The writer at a prefill-sized append, and pool_keys at prefill from the MXFP4 and from the bf16 cache."""
+    dev = torch.device("cuda:0")
+    L = _lib.lib()
+    Hkv, D, blk = 8, 128, 128
+    NK = Sk // blk
+    c4, deq, _, append = _kv4_cache(B, Hkv, Sk, D, torch.Generator(device=dev).manual_seed(B), dev)
+    outs = [torch.empty((B, Hkv, NK, D), dtype=torch.float32, device=dev) for _ in range(2)]
+    st = _core._stream()
+
+    def pool2():
+        _lib.check(L.rsa_pool_keys(B, Hkv, Sk, D, _lib.RSA_BF16, blk, NK, _core._t4(deq[0]), None, 0, 0, None, Sk, None, 0, 0,
+                                   outs[0].data_ptr(), st), "rsa_pool_keys")
+
+    def pool4():
+        _lib.check(L.rsa_pool_keys_kv4(B, Hkv, Sk, D, blk, NK, _core._t4(c4[0]), None, 0, 0, None, Sk, None, 0, 0, outs[1].data_ptr(),
+                                       _core._t4(c4[1]), st), "rsa_pool_keys_kv4")
+    fns = [append, pool2, pool4]
+    for _ in range(2):
+        for f in fns:
+            f()
+    torch.cuda.synchronize()
+    equal = bool(torch.equal(outs[0], outs[1]))
+    rounds = [_round(fns, args.reps) for _ in range(args.rounds)]
+    med = [statistics.median(r[i] for r in rounds) for i in range(3)]
+    spread = [max(r[i] for r in rounds) - min(r[i] for r in rounds) for i in range(3)]
+    elems = 2 * B * Hkv * Sk * D        # K and V
+    moved = elems * 2 + elems // 2 + elems // 32
+    say(f"writer, B = {B}, Hkv = {Hkv}, T = Sk = {Sk}, D = {D} (prefill): {1e3 * med[0]:.1f} us (spread {1e3 * spread[0]:.1f}); "
+        f"{elems * 2 / 1e6:.1f} MB read + {(elems // 2 + elems // 32) / 1e6:.1f} MB written = {moved / med[0] / 1e9:.3f} TB/s")
+    say(f"pool_keys at prefill, same shape: bf16 cache {1e3 * med[1]:.1f} us (spread {1e3 * spread[1]:.1f}) = "
+        f"{elems / med[1] / 1e9:.3f} TB/s of K; MXFP4 cache {1e3 * med[2]:.1f} us (spread {1e3 * spread[2]:.1f}) = "
+        f"{(elems // 4 + elems // 64) / med[2] / 1e9:.3f} TB/s of codes and scales; byte-equal: {equal}")
+    return dict(B=B, Sk=Sk, writer_us=round(1e3 * med[0], 2), pool_bf16_us=round(1e3 * med[1], 2), pool_mxfp4_us=round(1e3 * med[2], 2),
+                pool_equal=equal)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=8)
@@ -275,6 +415,7 @@ def main():
     ap.add_argument("--sweep", default="1,2,4,8,16,32,64")
     ap.add_argument("--out", default=None)
     ap.add_argument("--kv8", action="store_true", help="the e4m3 cache next to the 2-byte call, the writer and pool_keys")
+    ap.add_argument("--kv4", action="store_true", help="the MXFP4 cache next to the 2-byte and the e4m3 call, the writer and pool_keys")
     args = ap.parse_args()
     sweep = [int(x) for x in args.sweep.split(",")]
     lines = []
@@ -286,6 +427,19 @@ def main():
     res = dict(reps=args.reps, rounds=args.rounds, device=torch.cuda.get_device_name(0), rows=[])
     rows = [("long-16", 1, 131072, 1, 16, False), ("long-64", 1, 131072, 1, 64, False), ("batch-16", 8, 32768, 1, 16, False),
             ("batch-64", 8, 32768, 1, 64, False), ("batch-64-Sq4", 8, 32768, 4, 64, False), ("batch-64-paged", 8, 32768, 1, 64, True)]
+    if args.kv4:
+        say(f"block_sparse_decode over an MXFP4 cache against the 2-byte and the e4m3 call on the same dequantised content: bf16 q, D = 128, "
+            f"H = 32 over Hkv = 8, 128-token blocks, lists per K/V head, default split; {args.rounds} rounds x {args.reps} launches per "
+            "form, interleaved; cache-resident rates")
+        for row in rows:
+            res["rows"].append(kv4_row(say, args, *row))
+            torch.cuda.empty_cache()
+        res["writer_pool"] = [kv4_writer_and_pool(say, args, B, Sk) for B, Sk in ((8, 32768), (1, 131072))]
+        say(json.dumps(res))
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if args.kv8:
         say(f"block_sparse_decode over an e4m3 cache against the 2-byte call on the dequantised cache: bf16 q, D = 128, H = 32 over "
             f"Hkv = 8, 128-token blocks, lists per K/V head, default split; {args.rounds} rounds x {args.reps} launches per form, "
