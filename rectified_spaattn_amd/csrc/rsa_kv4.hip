@@ -19,28 +19,15 @@
 // v_cvt_scalef32_pk_fp4_{bf16,f16} does the division by 2^e, the rounding and the saturation of a pair of elements in one
 // instruction; what it is not asked to decide is done in integer code in front of it: a NaN element is cleared to +0 in the packed
 // input word, and the exponent comes from the integer maximum.
-#include "rsa_common.h"
+#include "rsa_kv_append.h"
 
-#include <type_traits>
-
-#define KV4_NT 256
 #define KV4_E_MIN (-13)
 #define KV4_E_MAX 13
 
-struct Kv4Args {
-    const unsigned short* src[2];       // k_new, v_new [B, Hkv, T, D]: strides in elements
-    long ssb[2], ssh[2], sss[2];
-    unsigned char* codes[2];            // [B, Hkv, Sk, D / 2] or page pools [P, Hkv, blk, D / 2]: strides in bytes
-    long csb[2], csh[2], css[2];
-    unsigned char* scales[2];           // [B, Hkv, Sk, D / 32] or page pools [P, Hkv, blk, D / 32]
+struct Kv4Own {
+    unsigned char* scales[2];           // [B, Hkv, Sk, D / 32] or page pools [P, Hkv, blk, D / 32]: beside the codes, which are dst
     long esb[2], esh[2], ess[2];
-    const int32_t* table;               // [B, >= Sk / blk] or null: contiguous caches
-    long tsb;
-    int num_pages;
-    const int32_t *start_dev, *n_new_dev;       // device values (clamped here) or null: the host values
-    int start, n_new;
-    int Hkv, T, Sk, blk, G;             // G = D / 32 lanes per row
-    long lanes;                         // B * Hkv * T * G
+    static constexpr int ELEMS = 32, ALIGN = 16;    // one lane: a 32-channel group of a row, a 16-byte store of codes
 };
 
 // The type's layout: the magnitude bits of Inf, and the shared exponent of a group whose largest magnitude is m (15 bits, not a
@@ -91,29 +78,11 @@ __device__ __forceinline__ unsigned kv4_clean(unsigned w, unsigned& amax) {
 }
 
 template <typename Tag>
-__global__ __launch_bounds__(KV4_NT) void kv4_append_kernel(const Kv4Args a) {
-    const long g = (long)blockIdx.x * KV4_NT + threadIdx.x;
-    if (g >= a.lanes) return;
-    const int w = blockIdx.y;           // 0: K, 1: V
-    const int c = (int)(g % a.G);
-    const int t = (int)((g / a.G) % a.T);
-    const int hk = (int)((g / ((long)a.G * a.T)) % a.Hkv);
-    const long b = g / ((long)a.G * a.T * a.Hkv);
-    const int n = a.n_new_dev ? min(max(a.n_new_dev[b], 0), a.T) : a.n_new;
-    if (t >= n) return;
-    const int st = a.start_dev ? min(max(a.start_dev[b], 0), a.Sk) : a.start;
-    const long pos = (long)st + t;
-    if (pos >= a.Sk) return;            // beyond the capacity: dropped
-    long row = pos, item = b;
-    if (a.table) {
-        const int page = a.table[b * a.tsb + pos / a.blk];
-        if (page < 0 || page >= a.num_pages) return;        // no page: dropped
-        item = page;
-        row = pos % a.blk;
-    }
-#define KV4_SEL(f) (w ? a.f[1] : a.f[0])      // (uniform selects: the argument arrays are never indexed by a register)
-    const uint4* sp = reinterpret_cast<const uint4*>(KV4_SEL(src) + b * KV4_SEL(ssb) + (long)hk * KV4_SEL(ssh) +
-                                                     (long)t * KV4_SEL(sss) + 32 * c);
+__global__ __launch_bounds__(KV_NT) void kv4_append_kernel(const KvAppendArgs<Kv4Own> a) {
+    KvPlace at;
+    if (!kv_place<false>(a, (long)blockIdx.x * KV_NT + threadIdx.x, at)) return;
+    const uint4* sp = reinterpret_cast<const uint4*>(KV_SEL(src) + at.b * KV_SEL(ssb) + (long)at.hk * KV_SEL(ssh) +
+                                                     at.srow * KV_SEL(sss) + 32 * at.c);
     uint4 x[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = sp[i];
@@ -132,60 +101,30 @@ __global__ __launch_bounds__(KV4_NT) void kv4_append_kernel(const Kv4Args a) {
     unsigned o[4] = {0u, 0u, 0u, 0u};   // pair j is byte j & 3 of word j >> 2
 #pragma unroll
     for (int j = 0; j < 16; ++j) o[j >> 2] = Kv4Elem<Tag>::cvt(o[j >> 2], p[j], scale, j & 3);
-    *reinterpret_cast<uint4*>(KV4_SEL(codes) + item * KV4_SEL(csb) + (long)hk * KV4_SEL(csh) + row * KV4_SEL(css) + 16 * c) =
+    *reinterpret_cast<uint4*>(KV_SEL(dst) + at.item * KV_SEL(dsb) + (long)at.hk * KV_SEL(dsh) + at.row * KV_SEL(dss) + 16 * at.c) =
         make_uint4(o[0], o[1], o[2], o[3]);
-    KV4_SEL(scales)[item * KV4_SEL(esb) + (long)hk * KV4_SEL(esh) + row * KV4_SEL(ess) + c] = (unsigned char)sbyte;
-#undef KV4_SEL
+    KV_SEL(x.scales)[at.item * KV_SEL(x.esb) + (long)at.hk * KV_SEL(x.esh) + at.row * KV_SEL(x.ess) + at.c] = (unsigned char)sbyte;
 }
 
 extern "C" int rsa_kv4_append(int B, int Hkv, int T, int Sk, int D, int dtype, int block, rsa_tensor4 k_new, rsa_tensor4 v_new,
                               rsa_out4 k_codes, rsa_out4 k_scales, rsa_out4 v_codes, rsa_out4 v_scales, const int32_t* block_table,
                               int64_t table_stride_b, int num_pages, const int32_t* start_dev, int start, const int32_t* n_new_dev,
                               int n_new, void* stream) {
-    if (B <= 0 || Hkv <= 0 || T <= 0 || Sk <= 0) return RSA_ERR_BAD_ARG;
-    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
-    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
-    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
-    if (!start_dev && (start < 0 || start > Sk)) return RSA_ERR_BAD_ARG;
-    if (!n_new_dev && (n_new < 0 || n_new > T)) return RSA_ERR_BAD_ARG;
-    if (rsa_check_tensor(k_new) != RSA_OK || rsa_check_tensor(v_new) != RSA_OK) return RSA_ERR_BAD_ARG;
-    const rsa_tensor4 src[2] = {k_new, v_new};
-    const rsa_out4 codes[2] = {k_codes, v_codes}, scales[2] = {k_scales, v_scales};
+    const rsa_out4 scales[2] = {k_scales, v_scales};
+    bool own_ok = true;
+    for (int w = 0; w < 2; ++w)
+        own_ok = own_ok && scales[w].ptr && scales[w].stride_b >= 0 && scales[w].stride_h >= 0 && scales[w].stride_s >= 0;
+    KvAppendArgs<Kv4Own> a;
+    dim3 grid;
+    const int st = kv_append_door(B, Hkv, T, Sk, D, dtype, block, {k_new, v_new}, {k_codes, v_codes}, block_table, table_stride_b,
+                                  num_pages, start_dev, start, n_new_dev, n_new, own_ok, 0, false, a, grid);
+    if (st != RSA_OK) return st;
     for (int w = 0; w < 2; ++w) {
-        if (src[w].stride_b < 0 || src[w].stride_h < 0 || src[w].stride_s < 0) return RSA_ERR_BAD_ARG;
-        if (!codes[w].ptr || (reinterpret_cast<uintptr_t>(codes[w].ptr) & 15)) return RSA_ERR_BAD_ARG;     // 16-byte stores
-        if (codes[w].stride_b < 0 || codes[w].stride_h < 0 || codes[w].stride_s < 0) return RSA_ERR_BAD_ARG;
-        if ((codes[w].stride_b % 16) || (codes[w].stride_h % 16) || (codes[w].stride_s % 16)) return RSA_ERR_BAD_ARG;
-        if (!scales[w].ptr || scales[w].stride_b < 0 || scales[w].stride_h < 0 || scales[w].stride_s < 0) return RSA_ERR_BAD_ARG;
+        a.x.scales[w] = static_cast<unsigned char*>(scales[w].ptr);
+        a.x.esb[w] = scales[w].stride_b; a.x.esh[w] = scales[w].stride_h; a.x.ess[w] = scales[w].stride_s;
     }
-    if (block_table && (num_pages <= 0 || table_stride_b < 0 || Sk % block)) return RSA_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(start_dev) | reinterpret_cast<uintptr_t>(n_new_dev)) & 3)
-        return RSA_ERR_BAD_ARG;
-    const long lanes = (long)B * Hkv * T * (D / 32);
-    const long groups = (lanes + KV4_NT - 1) / KV4_NT;
-    if (groups > 0x7FFFFFFFl) return RSA_ERR_UNSUPPORTED;
-
-    Kv4Args a;
-    for (int w = 0; w < 2; ++w) {
-        a.src[w] = static_cast<const unsigned short*>(src[w].ptr);
-        a.ssb[w] = src[w].stride_b; a.ssh[w] = src[w].stride_h; a.sss[w] = src[w].stride_s;
-        a.codes[w] = static_cast<unsigned char*>(codes[w].ptr);
-        a.csb[w] = codes[w].stride_b; a.csh[w] = codes[w].stride_h; a.css[w] = codes[w].stride_s;
-        a.scales[w] = static_cast<unsigned char*>(scales[w].ptr);
-        a.esb[w] = scales[w].stride_b; a.esh[w] = scales[w].stride_h; a.ess[w] = scales[w].stride_s;
-    }
-    a.table = block_table;
-    a.tsb = table_stride_b;
-    a.num_pages = num_pages;
-    a.start_dev = start_dev;
-    a.n_new_dev = n_new_dev;
-    a.start = start;
-    a.n_new = n_new;
-    a.Hkv = Hkv; a.T = T; a.Sk = Sk; a.blk = block; a.G = D / 32;
-    a.lanes = lanes;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)groups, 2);
-    if (dtype == RSA_BF16) kv4_append_kernel<bf16_tag><<<grid, KV4_NT, 0, s>>>(a);
-    else kv4_append_kernel<fp16_tag><<<grid, KV4_NT, 0, s>>>(a);
+    if (dtype == RSA_BF16) kv4_append_kernel<bf16_tag><<<grid, KV_NT, 0, s>>>(a);
+    else kv4_append_kernel<fp16_tag><<<grid, KV_NT, 0, s>>>(a);
     return rsa_launch_status();
 }

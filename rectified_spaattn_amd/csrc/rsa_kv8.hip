@@ -17,26 +17,21 @@
 // with cu_seqlens, and token t < n_b of item b is row s_b + t of them (rsa_rows.h: s the sanitised starts, n_b = s_{b+1} - s_b).
 // One lane per 8 elements of a row of [0, T): the row's item by pk_find over row_start, which pk_scan_kernel wrote; a row of no
 // item places nothing.
-#include "rsa_common.h"
+#include "rsa_kv_append.h"
 #include "rsa_rows.h"
 
 #include <type_traits>
 
-#define KV8_NT 256
-
-struct Kv8Args {
-    const unsigned short* src[2];       // k_new, v_new [B, Hkv, T, D]: strides in elements
-    long ssb[2], ssh[2], sss[2];
-    unsigned char* dst[2];              // the caches [B, Hkv, Sk, D] or page pools [P, Hkv, blk, D]: strides in bytes
-    long dsb[2], dsh[2], dss[2];
+struct Kv8Own {
     const float* scale[2];              // [Hkv] each
-    const int32_t* table;               // [B, >= Sk / blk] or null: contiguous caches
-    long tsb;
-    int num_pages;
-    const int32_t *start_dev, *n_new_dev;       // device values (clamped here) or null: the host values
-    int start, n_new;
-    int Hkv, T, Sk, blk, CH;            // CH = D / 8 lanes per row
-    long lanes;                         // B * Hkv * T * CH
+    static constexpr int ELEMS = 8, ALIGN = 8;      // one lane: 8 elements of a row, an 8-byte store
+};
+
+// The packed kernel's arguments: the padded kernel's (T = the rows of k_new, lanes = T * Hkv * CH, ssb unused) and the items.
+struct Kv8Packed : KvAppendArgs<Kv8Own> {
+    const int32_t* row_start;           // DEVICE [B + 1], written by pk_scan_kernel
+    int B, steps;
+    __device__ __forceinline__ int item_of(int row) const { return pk_find(row_start, B, steps, row); }
 };
 
 template <typename Tag>
@@ -61,50 +56,18 @@ __device__ __forceinline__ unsigned kv8_quant4(unsigned w0, unsigned w1, float s
     return ((unsigned)r & ~lanes) | nan;
 }
 
-// The packed kernel's arguments: the padded kernel's (T = the rows of k_new, lanes = T * Hkv * CH, ssb unused) and the items.
-struct Kv8Packed : Kv8Args {
-    const int32_t* row_start;           // DEVICE [B + 1], written by pk_scan_kernel
-    int B, steps;
-};
-
 template <typename Tag, bool PK = false>
-__global__ __launch_bounds__(KV8_NT) void kv8_append_kernel(typename std::conditional<PK, Kv8Packed, Kv8Args>::type a) {
-    const long g = (long)blockIdx.x * KV8_NT + threadIdx.x;
-    if (g >= a.lanes) return;
-    const int w = blockIdx.y;           // 0: K, 1: V
-    const int c = (int)(g % a.CH);
-    int t = (int)((g / a.CH) % a.T);
-    int hk = (int)((g / ((long)a.CH * a.T)) % a.Hkv);
-    long b = g / ((long)a.CH * a.T * a.Hkv);
-    long srow = t;                      // the token's row in k_new / v_new (behind b * ssb)
-    if constexpr (PK) {                 // lanes run (row, head, piece): the row's item, and its index in it
-        hk = (int)((g / a.CH) % a.Hkv);
-        srow = g / ((long)a.CH * a.Hkv);
-        b = pk_find(a.row_start, a.B, a.steps, (int)srow);
-        t = (int)srow - a.row_start[b];
-        if (t < 0 || t >= a.row_start[b + 1] - a.row_start[b]) return;     // a row of no item
-    }
-    const int n = PK ? a.T : (a.n_new_dev ? min(max(a.n_new_dev[b], 0), a.T) : a.n_new);
-    if (t >= n) return;
-    const int st = a.start_dev ? min(max(a.start_dev[b], 0), a.Sk) : a.start;
-    const long pos = (long)st + t;
-    if (pos >= a.Sk) return;            // beyond the capacity: dropped
-    long row = pos, item = b;
-    if (a.table) {
-        const int page = a.table[b * a.tsb + pos / a.blk];
-        if (page < 0 || page >= a.num_pages) return;        // no page: dropped
-        item = page;
-        row = pos % a.blk;
-    }
-#define KV8_SEL(f) (w ? a.f[1] : a.f[0])      // (uniform selects: the argument arrays are never indexed by a register)
-    const uint4 x = *reinterpret_cast<const uint4*>(KV8_SEL(src) + (PK ? 0 : b * KV8_SEL(ssb)) + (long)hk * KV8_SEL(ssh) +
-                                                    srow * KV8_SEL(sss) + 8 * c);
-    const float s = KV8_SEL(scale)[hk];
+__global__ __launch_bounds__(KV_NT) void kv8_append_kernel(
+    typename std::conditional<PK, Kv8Packed, KvAppendArgs<Kv8Own>>::type a) {
+    KvPlace at;
+    if (!kv_place<PK>(a, (long)blockIdx.x * KV_NT + threadIdx.x, at)) return;
+    const uint4 x = *reinterpret_cast<const uint4*>(KV_SEL(src) + (PK ? 0 : at.b * KV_SEL(ssb)) + (long)at.hk * KV_SEL(ssh) +
+                                                    at.srow * KV_SEL(sss) + 8 * at.c);
+    const float s = KV_SEL(x.scale)[at.hk];
     uint2 o;
     o.x = kv8_quant4<Tag>(x.x, x.y, s);
     o.y = kv8_quant4<Tag>(x.z, x.w, s);
-    *reinterpret_cast<uint2*>(KV8_SEL(dst) + item * KV8_SEL(dsb) + (long)hk * KV8_SEL(dsh) + row * KV8_SEL(dss) + 8 * c) = o;
-#undef KV8_SEL
+    *reinterpret_cast<uint2*>(KV_SEL(dst) + at.item * KV_SEL(dsb) + (long)at.hk * KV_SEL(dsh) + at.row * KV_SEL(dss) + 8 * at.c) = o;
 }
 
 // Both entries.  cu: the packed entry's cu_seqlens (then T = the rows of k_new / v_new, n_new is not read and item_ws, DEVICE
@@ -115,62 +78,27 @@ static int kv8_run(int B, int Hkv, int T, int Sk, int D, int dtype, int block, r
                    const float* v_scale, const int32_t* cu, int32_t* item_ws, bool packed, void* stream) {
     if (packed && (!cu || !item_ws || ((reinterpret_cast<uintptr_t>(cu) | reinterpret_cast<uintptr_t>(item_ws)) & 3) || B >= 0x7FFFFFFF))
         return RSA_ERR_BAD_ARG;
-    if (B <= 0 || Hkv <= 0 || T <= 0 || Sk <= 0) return RSA_ERR_BAD_ARG;
-    if (block != 64 && block != 128) return RSA_ERR_UNSUPPORTED;
-    if (dtype != RSA_BF16 && dtype != RSA_FP16) return RSA_ERR_UNSUPPORTED;
-    if (D != 64 && D != 128) return RSA_ERR_UNSUPPORTED;
-    if (!start_dev && (start < 0 || start > Sk)) return RSA_ERR_BAD_ARG;
-    if (!n_new_dev && (n_new < 0 || n_new > T)) return RSA_ERR_BAD_ARG;
-    if (!k_scale || !v_scale) return RSA_ERR_BAD_ARG;
-    if (rsa_check_tensor(k_new) != RSA_OK || rsa_check_tensor(v_new) != RSA_OK) return RSA_ERR_BAD_ARG;
-    const rsa_tensor4 src[2] = {k_new, v_new};
-    const rsa_out4 dst[2] = {k_cache, v_cache};
-    for (int w = 0; w < 2; ++w) {
-        if (src[w].stride_b < 0 || src[w].stride_h < 0 || src[w].stride_s < 0) return RSA_ERR_BAD_ARG;
-        if (!dst[w].ptr || (reinterpret_cast<uintptr_t>(dst[w].ptr) & 7)) return RSA_ERR_BAD_ARG;      // 8-byte stores
-        if (dst[w].stride_b < 0 || dst[w].stride_h < 0 || dst[w].stride_s < 0) return RSA_ERR_BAD_ARG;
-        if ((dst[w].stride_b % 8) || (dst[w].stride_h % 8) || (dst[w].stride_s % 8)) return RSA_ERR_BAD_ARG;
-    }
-    if (block_table && (num_pages <= 0 || table_stride_b < 0 || Sk % block)) return RSA_ERR_BAD_ARG;
-    if ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(start_dev) | reinterpret_cast<uintptr_t>(n_new_dev) |
-         reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3)
-        return RSA_ERR_BAD_ARG;
-    const long lanes = (packed ? 1L : (long)B) * Hkv * T * (D / 8);
-    const long groups = (lanes + KV8_NT - 1) / KV8_NT;
-    if (groups > 0x7FFFFFFFl) return RSA_ERR_UNSUPPORTED;
-
     Kv8Packed a;
-    for (int w = 0; w < 2; ++w) {
-        a.src[w] = static_cast<const unsigned short*>(src[w].ptr);
-        a.ssb[w] = src[w].stride_b; a.ssh[w] = src[w].stride_h; a.sss[w] = src[w].stride_s;
-        a.dst[w] = static_cast<unsigned char*>(dst[w].ptr);
-        a.dsb[w] = dst[w].stride_b; a.dsh[w] = dst[w].stride_h; a.dss[w] = dst[w].stride_s;
-    }
-    a.scale[0] = k_scale;
-    a.scale[1] = v_scale;
-    a.table = block_table;
-    a.tsb = table_stride_b;
-    a.num_pages = num_pages;
-    a.start_dev = start_dev;
-    a.n_new_dev = n_new_dev;
-    a.start = start;
-    a.n_new = n_new;
-    a.Hkv = Hkv; a.T = T; a.Sk = Sk; a.blk = block; a.CH = D / 8;
-    a.lanes = lanes;
+    dim3 grid;
+    const int st = kv_append_door(B, Hkv, T, Sk, D, dtype, block, {k_new, v_new}, {k_cache, v_cache}, block_table, table_stride_b,
+                                  num_pages, start_dev, start, n_new_dev, n_new, k_scale && v_scale,
+                                  reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale), packed, a, grid);
+    if (st != RSA_OK) return st;
+    a.x.scale[0] = k_scale;
+    a.x.scale[1] = v_scale;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)groups, 2);
     if (packed) {
         a.row_start = item_ws;
         a.B = B;
         a.steps = pk_steps(B);
         pk_scan_launch(cu, B, T, T, block, 0, 0, item_ws, nullptr, nullptr, s);
-        if (dtype == RSA_BF16) kv8_append_kernel<bf16_tag, true><<<grid, KV8_NT, 0, s>>>(a);
-        else kv8_append_kernel<fp16_tag, true><<<grid, KV8_NT, 0, s>>>(a);
+        if (dtype == RSA_BF16) kv8_append_kernel<bf16_tag, true><<<grid, KV_NT, 0, s>>>(a);
+        else kv8_append_kernel<fp16_tag, true><<<grid, KV_NT, 0, s>>>(a);
         return rsa_launch_status();
     }
-    const Kv8Args& a0 = a;
-    if (dtype == RSA_BF16) kv8_append_kernel<bf16_tag><<<grid, KV8_NT, 0, s>>>(a0);
-    else kv8_append_kernel<fp16_tag><<<grid, KV8_NT, 0, s>>>(a0);
+    const KvAppendArgs<Kv8Own>& a0 = a;
+    if (dtype == RSA_BF16) kv8_append_kernel<bf16_tag><<<grid, KV_NT, 0, s>>>(a0);
+    else kv8_append_kernel<fp16_tag><<<grid, KV_NT, 0, s>>>(a0);
     return rsa_launch_status();
 }
 

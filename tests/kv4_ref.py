@@ -43,14 +43,15 @@ def dequant(codes, scales) -> np.ndarray:
     return val * np.repeat(np.exp2(scales.astype(np.float64) - 127), GROUP, -1)
 
 
-def paged(arrays, blk: int, lens, seed: int, bad: int):
-    """arrays: contiguous [B, Hkv, Sk, X] uint8 caches -> (their page pools [P, Hkv, blk, X], table int32 [B, NK], P): B * NK + 3
-    pages placed by one random permutation, FILL in spare pages and ragged tails, `bad` in the table where no key is."""
+def paged(arrays, blk: int, lens, seed: int, bad: int, fill: int = FILL, perm=None):
+    """arrays: contiguous [B, Hkv, Sk, X] uint8 caches that share B and Sk -> (their page pools [P, Hkv, blk, X], table int32
+    [B, NK], P): B * NK + 3 pages placed by one random permutation (perm, else numpy's for the seed), `fill` in spare pages and
+    ragged tails, `bad` in the table where no key is.  The e4m3 tests' pools come from here too (test_gpu_kv8._pool8)."""
     B, _, Sk, _ = arrays[0].shape
     NK = -(-Sk // blk)
     P = B * NK + 3
-    perm = np.random.default_rng(seed).permutation(P)
-    pools = [np.full((P, a.shape[1], blk, a.shape[3]), FILL, np.uint8) for a in arrays]
+    perm = np.random.default_rng(seed).permutation(P) if perm is None else perm
+    pools = [np.full((P, a.shape[1], blk, a.shape[3]), fill, np.uint8) for a in arrays]
     table = np.full((B, NK), bad, np.int32)
     for b in range(B):
         for j in range(-(-lens[b] // blk)):

@@ -104,6 +104,34 @@ def test_writer_bytes_placement_and_untouched_sentinel(dt, D, paged):
     assert {114, 140} <= set(np.unique(model[1]).tolist())           # both clamp ends were written
 
 
+@pytest.mark.parametrize("writer", ["e4m3", "mxfp4"])
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+@pytest.mark.parametrize("D", [64, 128])
+def test_both_writers_place_across_a_page_edge_under_device_limits(writer, dt, D):
+    """B = 2, Hkv = 2, T = 3, two 64-token pages per item: item 0 starts at 62 and straddles the page edge, its second page's entry
+    is P (out of range: that token is dropped); item 1 starts at 126 with n_new = 2 on the device, and its third token would lie
+    beyond the capacity.  Every byte of codes and scales against the model, the sentinel everywhere else."""
+    from rectified_spaattn_amd import append_kv_e4m3, append_kv_mxfp4
+    T, blk, P, start, n_new = 3, 64, 5, [62, 126], [3, 2]
+    table = np.array([[3, P], [0, 4]], np.int32)
+    news = [_new_rows(T, D, dt, s) for s in (1, 2)]
+    if writer == "e4m3":
+        pair = (np.array([0.37, 4.0], np.float32), np.array([2.3, 0.11], np.float32))
+        want, lasts = [kv8_ref.quantize(x, s) for x, s in zip(news, pair)], (D, D)
+        call = lambda *c, **kw: append_kv_e4m3(*c[:2], *(t.view(torch.float8_e4m3fn) for t in c[2:]), **kw,     # noqa: E731
+                                               k_scale=_dev(pair[0]), v_scale=_dev(pair[1]))
+    else:
+        want, lasts, call = kv4.quantize(news[0]) + kv4.quantize(news[1]), (D // 2, D // 32, D // 2, D // 32), append_kv_mxfp4
+    caches = [_dev(np.full((P, HKV, blk, last), SENTINEL, np.uint8)) for last in lasts]
+    kw = dict(start=torch.tensor(start, dtype=torch.int32, device=DEV), n_new=torch.tensor(n_new, dtype=torch.int32, device=DEV),
+              block_size=blk, block_table=_dev(table))
+    call(news[0].to(DEV), news[1].to(DEV), *caches, **kw)
+    for j, (cache, new) in enumerate(zip(caches, want)):
+        model, wrote = kv8_ref.append(np.full(cache.shape, SENTINEL, np.uint8), new, start, n_new, blk, table)
+        assert np.array_equal(cache.cpu().numpy(), model), j
+        assert int(wrote[:, 0, :, 0].sum()) == 4 and not wrote[[1, 2]].any()      # 62, 63 of item 0 and 126, 127 of item 1; no other page
+
+
 # ---- 2. decode: the bytes of the 2-byte call ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dt,D,paged", FORMS, ids=IDS)
 def test_decode_gives_the_bytes_of_the_two_byte_call_on_the_dequantised_cache(dt, D, paged):

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import decode_ref as ref
+import kv4_ref
 import kv8_ref as kv8
 import select_ref
 from test_gpu_decode import COMBOS, LENS, LSE_TOL, TOL, _hl, _id, _kv_arg
@@ -57,24 +58,11 @@ def _quantised(kf, vf, scales, lens, dt):
 
 
 def _pool8(kc, vc, blk, lens, seed, bad=-1):
-    """test_gpu_decode._pool's layout over uint8 codes: B * NK + 3 pages placed by a random permutation, the spare ones and the
-    ragged tails full of the NaN code, garbage table entries past ceil(kv_len[b] / block)."""
-    B, Hkv, Sk, D = kc.shape
-    NK = -(-Sk // blk)
-    P = B * NK + 3
+    """test_gpu_decode._pool's layout over uint8 codes (kv4_ref.paged with torch's permutation): B * NK + 3 pages, the spare ones
+    and the ragged tails full of the NaN code, garbage table entries past ceil(kv_len[b] / block)."""
+    P = kc.shape[0] * -(-kc.shape[2] // blk) + 3
     perm = torch.randperm(P, generator=torch.Generator().manual_seed(seed)).tolist()
-    kp = np.full((P, Hkv, blk, D), kv8.NAN_CODE, np.uint8)
-    vp = kp.copy()
-    table = np.full((B, NK), P + 5 if bad == "P+5" else bad, np.int32)
-    for b in range(B):
-        for j in range(NK):
-            if j * blk >= lens[b]:
-                continue
-            pg = perm[b * NK + j]
-            rows = min(blk, Sk - j * blk)
-            kp[pg, :, :rows] = kc[b, :, j * blk:j * blk + rows]
-            vp[pg, :, :rows] = vc[b, :, j * blk:j * blk + rows]
-            table[b, j] = pg
+    (kp, vp), table, P = kv4_ref.paged([kc, vc], blk, lens, seed, P + 5 if bad == "P+5" else bad, kv8.NAN_CODE, perm)
     return kp, vp, table, P
 
 
