@@ -664,6 +664,45 @@ int rsa_block_select_antidiag(int B, int H, int Hkv, int Hl, int Sq, int Sk, int
                               int top_k, int keep_first, int keep_local, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
                               int32_t* counts, float* scores, int p16, float c, float* mass, void* stream);
 
+/* ---- block selection by the OBSERVED attention mass of the last query rows, for the moment between prefill and decode (the
+ * observation window of SnapKV, MInference's last-q estimate, FlexPrefill; found by symbol: the header version stays 6.1; DESIGN.md
+ * section 5.24).  q_obs [B, H, W, D], 1 <= W <= 64, holds the last W query rows of the prompt; a key block scores by the true softmax
+ * mass those rows put into it.  With g = H / Hkv:
+ *   visible   row r of item b sees key j iff j < len_b and, with causal, j <= r + len_b - W (bottom-right aligned, as in
+ *             rsa_block_sparse_decode).  Keys at or beyond len_b are never loaded and may hold NaN, and so may the pages of blocks
+ *             without a visible key.  A row that sees no key takes no part.
+ *   logit     x[h, r, j] = sm_scale <q_obs[b, h, r], k[b, h / g, j]>: matrix pipe, fp32 accumulation; sm_scale finite and > 0
+ *   p         the softmax of x[h, r, :] over the keys row r sees
+ *   mass      P[b, hl, jb] = the sum over the list head's query heads, the live rows and the visible keys of block jb of p;
+ *             t = ln(max(P, 2^-126)), finite at every visible block
+ * and t takes the place of rsa_block_select's score at one query block (NQ = 1, W where Sq stood): the visible prefix, the forced
+ * blocks, top-k with ties to the lower block, top-p (p16 = -1: plain top-k, c and mass are then not read; the logit is
+ * c / log2(e) * t, so a block's weight is proportional to its mass), the lists, the scores (-inf at invisible blocks) and the mass
+ * are rsa_block_select_ragged's, by the same device code.  The lists [B * Hl, 1, NK] are what rsa_block_sparse_decode takes.
+ * Arithmetic, all fp32, c2 = (float)(sm_scale log2(e)), a = the raw dot product: per (h, r, jb) the pair m = max of a over the
+ * row's visible keys of the block (-3e38 where it sees none), l = sum of exp2((a - m) c2) -- over the block's 16-key column groups
+ * ascending per column, then over the 16 columns by xor strides 1, 2, 4, 8.  Per (h, r): (M, L) = the combine
+ * (max(M, m), L exp2((M - M') c2) + l exp2((m - M') c2)) of the pairs, over jb = jl, jl + JL, .. ascending per lane jl < JL =
+ * 1024 / W, then over the lanes by a halving tree.  Per jb: P = sum over ascending r of (sum over ascending h of
+ * l exp2((m - M) c2) / L).  One fixed order, no atomics: two calls give the same bytes, and so does every score_splits.
+ * k [B, Hkv, Sk, D], or with block_table (DEVICE int32, row b at block_table + b table_stride_b, NK entries read at most) the page
+ * pool [num_pages, Hkv, block, D] of rsa_block_sparse_decode: one page = one key block, Sk = NK block; an entry outside
+ * [0, num_pages) gives a block of zero keys; the table is read only at blocks with a visible key.  bf16 / fp16, D 64 or 128, block
+ * 64 or 128, NK <= 8192.  score_splits: workgroups per (b, K/V head, pass of four query heads) of the score launch, each over the
+ * blocks sp, sp + score_splits, ..; 0 = the library's choice, a function of the shapes alone; at most 256.
+ * ws: rsa_block_select_observed_bytes(...) bytes, 16-byte aligned: the ordered keys [B, Hl, 1, NK], the pairs [B, H, NK, W, 2] and
+ * the row statistics [B, H, W, 2].  Four launches (the pairs: one pass over K; the row statistics; the masses; the selection);
+ * capturable.  Refusals: rsa_block_select's, with their
+ * statuses, in their order (W > block among them: NQ != 1); then D -> RSA_ERR_UNSUPPORTED, sm_scale -> RSA_ERR_BAD_ARG, W > 64 ->
+ * RSA_ERR_BAD_ARG, k, ws, block_table (misaligned, num_pages
+ * <= 0, a negative stride) and score_splits outside [0, 256] -> RSA_ERR_BAD_ARG, a short workspace -> RSA_ERR_WORKSPACE. */
+int rsa_block_select_observed_bytes(int B, int H, int Hkv, int Hl, int W, int D, int block, int NQ, int NK, size_t* bytes);
+int rsa_block_select_observed(int B, int H, int Hkv, int Hl, int W, int Sk, int D, int dtype, int block, int NQ, int NK,
+                              rsa_tensor4 q, rsa_tensor4 k, const int32_t* block_table, int64_t table_stride_b, int num_pages,
+                              const int32_t* kv_len_dev, int kv_valid, int causal, double sm_scale, int top_k, int keep_first,
+                              int keep_local, int score_splits, void* ws, size_t ws_bytes, uint32_t* bitmask, int32_t* cols,
+                              int32_t* counts, float* scores, int p16, float c, float* mass, void* stream);
+
 /* ---- the MERGE of attention partials: N results over disjoint key sets -- another rank's share of the cache, a shared prefix
  * beside each item's suffix, a dense branch beside the selected blocks -- become the result over their union (found by symbol:
  * the header version stays 6.1).  Partial i is what the decode and extend entries return: out_i, 2-byte

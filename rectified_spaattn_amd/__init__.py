@@ -187,6 +187,20 @@ def select_blocks_antidiag(q, k, top_k, *, stride=8, sm_scale=None, block_size=1
                                                score_scale=score_scale, return_mass=return_mass, **not_served)
 
 
+def select_blocks_observed(q_obs, k, top_k, *, sm_scale=None, block_size=128, kv_len=None, causal=False, keep_first=0,
+                           keep_local=0, mask_heads="kv", as_lists=False, return_scores=False, top_p=None, score_scale=None,
+                           return_mass=False, block_table=None, score_splits=None):
+    """select_blocks at one query block, scored by the true softmax mass the last W <= 64 query rows of the prompt put into a key
+    block (the observation window of SnapKV / MInference / FlexPrefill): one MFMA pass over a contiguous or paged K, the lists
+    block_sparse_decode takes.  See rectified_spaattn_amd.block_sparse.select_blocks_observed."""
+    from . import block_sparse
+    return block_sparse.select_blocks_observed(q_obs, k, top_k, sm_scale=sm_scale, block_size=block_size, kv_len=kv_len,
+                                               causal=causal, keep_first=keep_first, keep_local=keep_local, mask_heads=mask_heads,
+                                               as_lists=as_lists, return_scores=return_scores, top_p=top_p,
+                                               score_scale=score_scale, return_mass=return_mass, block_table=block_table,
+                                               score_splits=score_splits)
+
+
 def merge_partials(outs, lses, *, sink=None, out=None, lse=None, return_lse=True):
     """The merge of N <= 8 attention partials (out_i, lse_i) over disjoint key sets -- what block_sparse_decode / block_sparse_extend
     return with return_lse=True -- into the result over their union, with optional attention-sink logits: one launch, no copy, the

@@ -23,6 +23,9 @@ any boolean block mask), rectified_hunyuan_attn.py:108-280 and the same in the f
                              (rsa_block_select_bound), everything behind the score unchanged
     select_blocks_antidiag   select_blocks with the score of training-free sparse prefill: the softmax mass of a block pair's
                              anti-diagonal strided logits, an MFMA pass over K (rsa_block_select_antidiag)
+    select_blocks_observed   select_blocks at one query block with the score of the moment between prefill and decode: the true
+                             softmax mass the last W <= 64 query rows put into a key block, one MFMA pass over a (paged) K
+                             (rsa_block_select_observed)
     append_kv_mxfp4          the writer of an MXFP4 K/V cache: e2m1 codes, two to a byte, with one e8m0 scale byte per 32 channels
                              of a row (rsa_kv4_append); block_sparse_decode and pool_keys read such a cache in place
                              (k_block_scale= / v_block_scale=: rsa_block_sparse_decode_kv4, rsa_pool_keys_kv4; DESIGN.md section
@@ -858,7 +861,7 @@ def _check_top_p(top_p, score_scale, return_mass):
 
 def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
             return_scores, as_lists, score_splits=None, top_p=None, score_scale=None, return_mass=False, q_len=None,
-            cu_seqlens_q=None, max_q_len=None, bound: bool = False, antidiag=None):
+            cu_seqlens_q=None, max_q_len=None, bound: bool = False, antidiag=None, observed=None):
     """select_blocks (keys = k, rsa_block_select) and select_blocks_pooled (keys = pool_keys' cache, rsa_block_select_pooled,
     with its score_splits): the two differ in where kbar comes from and in nothing else.  With top_p the entries are their _p
     forms, which take (p16, c, mass) in front of the stream.  With q_len the entries are their _ragged forms: the _p argument
@@ -868,7 +871,9 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
     top-k; no row counts: NULL) and rsa_block_select_bound_packed the packed one.  antidiag = (stride, sm_scale):
     select_blocks_antidiag -- keys = k, head dims 64 / 128; rsa_block_select_antidiag has the _p argument list alone (p16 = -1:
     top-k) with H in front of its size query's Hkv, Sq and the block behind, stride behind block and sm_scale behind causal; the
-    top-p logit is score_scale * t with score_scale defaulting to 1."""
+    top-p logit is score_scale * t with score_scale defaulting to 1.  observed = (sm_scale, block_table): select_blocks_observed --
+    q = q_obs (Sq is W), keys = k or, with a table, the page pool, which is read where it lies; rsa_block_select_observed is the
+    antidiag list without the stride, with the table's three arguments behind k and score_splits in front of the workspace."""
     blk = _check_block(what, block_size)
     if mask_heads not in ("kv", "q"):
         raise ValueError(f"mask_heads: 'kv' (one selection per K/V head) or 'q' (one per query head), got {mask_heads!r}")
@@ -876,8 +881,10 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         _check_count(name, val, 0)
     _check_count("score_splits", score_splits, 1, MAX_SCORE_SPLITS, optional=True)
     _check_top_p(top_p, score_scale, return_mass)
-    r = _query_rows(q, q_len, cu_seqlens_q, max_q_len, keys, None, lambda q4: _check_operands(q4, keys, pooled=pooled, bounds=bound,
-                                                                                   dims=ANTIDIAG_HEAD_DIMS if antidiag else HEAD_DIMS))
+    block_table = observed[1] if observed else None
+    r = _query_rows(q, q_len, cu_seqlens_q, max_q_len, keys, None, lambda q4: _check_operands(
+        q4, keys, pooled=pooled, bounds=bound, dims=ANTIDIAG_HEAD_DIMS if antidiag or observed else HEAD_DIMS,
+        block_table=block_table, blk=blk))
     packed, q, B, H, Hkv, Sq, Sk, D = r.kind == "packed", r.q4, r.B, r.H, r.Hkv, r.Sq, r.Sk, r.D
     if pooled:      # the cache holds NK blocks: the capacity is taken as NK * block
         Sk *= blk
@@ -892,36 +899,46 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
     kv_dev, kv_valid, _ = _device_limit(lens, B, Sk, dev)
     q_dev = _row_limit(rows, B, Sq, dev)
     L = _lib.lib()
+    table = ()
+    if observed:
+        table, _held = _table_args(block_table, keys)
     if packed:
         q, cu = _packed_on_device(r)
+    elif block_table is not None:       # a page pool is read where it lies
+        _check_cache(keys)
+        q = _core._as_bhsd(q)
     else:
         q, keys = _core._as_bhsd(q), keys if pooled else _core._as_bhsd(keys)
-    base = ("rsa_block_select_antidiag" if antidiag else "rsa_block_select_bound" if bound else
+    base = ("rsa_block_select_observed" if observed else "rsa_block_select_antidiag" if antidiag else "rsa_block_select_bound" if bound else
             "rsa_block_select_pooled" if pooled else "rsa_block_select")
-    entry = base + ("" if top_p is None or bound or antidiag else "_p")
+    entry = base + ("" if top_p is None or bound or antidiag or observed else "_p")
     need = ctypes.c_size_t(0)
-    sizes = (B, H, Hkv, Hl, Sq, D, blk, antidiag[0], NQ, NK) if antidiag else (B, Hkv, Hl, D, NQ, NK)
+    sizes = ((B, H, Hkv, Hl, Sq, D, blk, NQ, NK) if observed else (B, H, Hkv, Hl, Sq, D, blk, antidiag[0], NQ, NK) if antidiag else
+             (B, Hkv, Hl, D, NQ, NK))
     _lib.check(getattr(L, entry + "_bytes")(*sizes, ctypes.byref(need)), entry + "_bytes")
     if q_dev is not None and not bound:
         entry = base + "_ragged"
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
     out = _empty_lists(B * Hl, NQ, NK, dev)
     scores = torch.empty((B, Hl, NQ, NK), dtype=torch.float32, device=dev) if return_scores else None
+    if pooled or observed:
+        splits = (0 if score_splits is None else int(score_splits),)
     if pooled:
         shape, source = (B, H, Hkv, Hl, Sq, D), keys.data_ptr()
-        splits = (0 if score_splits is None else int(score_splits),)
+    elif observed:
+        shape, source = (B, H, Hkv, Hl, Sq, Sk, D), _core._t4(keys)
     else:
         shape, source, splits = (B, H, Hkv, Hl, Sq, Sk, D), _core._t4(keys), ()
     mass, budget = None, ()
     if top_p is not None:
         mass = torch.empty((B, Hl, NQ), dtype=torch.float32, device=dev) if return_mass else None
-        default = 1.0 if antidiag else 1.0 / ((H // Hl) * math.sqrt(D))
+        default = 1.0 if antidiag or observed else 1.0 / ((H // Hl) * math.sqrt(D))
         scale = default if score_scale is None else float(score_scale)
         budget = (int(round(float(top_p) * 65536.0)), scale * LOG2_E, _ptr(mass))
     if q_dev is not None or (bound and not packed):
         budget = (budget or (-1, 0.0, None)) + (_ptr(q_dev),)
-    stride, sm_scale = ((antidiag[0],), (antidiag[1],)) if antidiag else ((), ())
-    if antidiag:
+    stride, sm_scale = ((antidiag[0],), (antidiag[1],)) if antidiag else ((), (observed[0],)) if observed else ((), ())
+    if antidiag or observed:
         budget = budget or (-1, 0.0, None)
     tq = _t3(q) if packed else _core._t4(q)
     if packed:              # T in front, M where Sq stood, cu_seqlens_q and the scan's scratch where q_len stood
@@ -929,7 +946,7 @@ def _select(what: str, q, keys, pooled: bool, top_k, block_size, kv_len, causal,
         items = torch.empty((2 * (B + 1),), dtype=torch.int32, device=dev)
         budget = (budget or (-1, 0.0, None)) + (cu.data_ptr(), items.data_ptr())
     with torch.cuda.device(dev):
-        _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, *stride, NQ, NK, tq, source, _ptr(kv_dev), kv_valid,
+        _lib.check(getattr(L, entry)(*shape, _core.dtype_code(q.dtype), blk, *stride, NQ, NK, tq, source, *table, _ptr(kv_dev), kv_valid,
                                      int(bool(causal)), *sm_scale, min(top_k, NK), min(keep_first, NK), min(keep_local, NK + 1), *splits,
                                      ws.data_ptr(), need.value, out["bitmask"].data_ptr(), out["cols"].data_ptr(),
                                      out["counts"].data_ptr(), _ptr(scores), *budget, _core._stream()), entry)
@@ -1265,6 +1282,53 @@ def select_blocks_antidiag(q: torch.Tensor, k: torch.Tensor, top_k: int, *, stri
     scale = float(D) ** -0.5 if sm_scale is None else float(sm_scale)
     return _select("select_blocks_antidiag", q, k, False, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
                    return_scores, as_lists, None, top_p, score_scale, return_mass, antidiag=(int(stride), scale))
+
+
+OBSERVED_MAX_ROWS = 64  # observation rows of select_blocks_observed: four 16-row MFMA tiles (rsa_select_observed.hip)
+
+
+def select_blocks_observed(q_obs: torch.Tensor, k: torch.Tensor, top_k: int, *, sm_scale: Optional[float] = None,
+                           block_size: int = 128, kv_len=None, causal: bool = False, keep_first: int = 0, keep_local: int = 0,
+                           mask_heads: str = "kv", as_lists: bool = False, return_scores: bool = False,
+                           top_p: Optional[float] = None, score_scale: Optional[float] = None, return_mass: bool = False,
+                           block_table=None, score_splits: Optional[int] = None):
+    """select_blocks with one thing changed, the score (the observation window of SnapKV, MInference's
+    last-q estimate, FlexPrefill): a key block scores by the true softmax mass the last W query rows of the prompt put into it.
+    One list row per K/V head -- the [B, Hl, 1, NK] mask (or, as_lists, the lists) block_sparse_decode takes: select once after
+    prefill and decode many steps on it, re-select every n steps from the latest rows, or evict pages by mass.
+    q_obs [B,H,W,D], 1 <= W <= 64, normally q[:, :, -W:] (a view runs without a copy under select_blocks' stride rules for q);
+    k [B,Hkv,Sk,D] under the strides select_blocks takes, or with block_table int32 [B, NKt] the page pool [P,Hkv,block_size,D] as
+    block_sparse_decode reads it (never copied; an entry outside [0, P) gives a block of zero keys).  bf16 / fp16, H % Hkv == 0,
+    D 64 or 128, block_size 64 or 128, NK <= 8192; kv_len in select_blocks' forms (a device tensor is never read on the host).
+      visible   row r of item b sees key j iff j < kv_len[b] and, with causal, j <= r + kv_len[b] - W (bottom-right aligned, as
+                in block_sparse_decode).  Keys at or beyond kv_len[b] are never read and may hold NaN, and so may the pages of
+                blocks with no visible key.  A row that sees no key takes no part.
+      logit     x[h, r, j] = sm_scale * <q_obs[b, h, r], k[b, h // g, j]>, on the matrix pipe with fp32 accumulation; sm_scale
+                defaults to D ** -0.5 and is a finite number > 0
+      p         the softmax of x[h, r, :] over the keys row r sees
+      mass      P[b, hl, jb] = the sum over the list head's query heads, the live rows r and the visible keys of block jb of p;
+                t = ln(max(P, 2^-126)), finite at every visible block
+    and t takes the place of select_blocks' score at one query block (NQ = 1, Sq = W): visible / forced / kept, top_k, keep_first,
+    keep_local, mask_heads, as_lists, return_scores (-inf at invisible blocks) and the returned shapes are select_blocks', by the
+    same device code.  top_p: the logit is score_scale * t with score_scale defaulting to 1, so top_p is the share of the
+    observed attention a list keeps; return_mass as in select_blocks.
+    Every sum has one fixed order and nothing is added atomically: two calls give the same bytes, and so does every score_splits
+    (workgroups per K/V head and pass of four query heads of the score launch; None = the library's choice, a function of the
+    shapes alone).  Asynchronous on the current stream, capturable.  Not served (never a fallback, never a copy): W == 0 or
+    W > 64 (ValueError), head dims 16 / 32, other block sizes, a float8_e4m3fn or MXFP4 K (NotImplementedError); ragged or packed
+    queries have no argument here."""
+    if not isinstance(q_obs, torch.Tensor) or q_obs.dim() != 4 or not 1 <= q_obs.shape[2] <= OBSERVED_MAX_ROWS:
+        raise ValueError(f"q_obs: [B, H, W, D] with 1 <= W <= {OBSERVED_MAX_ROWS} observation rows, got "
+                         f"{tuple(getattr(q_obs, 'shape', ()))}")
+    _refuse_mxfp4("select_blocks_observed", k)
+    if isinstance(k, torch.Tensor) and k.dtype in (E4M3,) + KV4_CODE_DTYPES:
+        raise NotImplementedError(f"select_blocks_observed: a {k.dtype} K is not served")
+    if sm_scale is not None and (isinstance(sm_scale, bool) or not isinstance(sm_scale, (int, float))
+                                 or not 0.0 < float(sm_scale) < float("inf")):
+        raise ValueError(f"sm_scale: None or a finite number > 0, got {sm_scale!r}")
+    scale = float(q_obs.shape[-1]) ** -0.5 if sm_scale is None else float(sm_scale)
+    return _select("select_blocks_observed", q_obs, k, False, top_k, block_size, kv_len, causal, keep_first, keep_local, mask_heads,
+                   return_scores, as_lists, score_splits, top_p, score_scale, return_mass, observed=(scale, block_table))
 
 
 DECODE_MAX_ROWS = 64    # rows of a decode unit: four 16-row MFMA tiles (rsa_decode.hip)
